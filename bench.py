@@ -1,15 +1,22 @@
 #!/usr/bin/env python3
 """Headline benchmark: multigrid V-cycles per second of the pressure solve on the seamount 512x512x64 problem
-(BASELINE.json `metric`, configs[2]: the configuration the metric is quoted on; it fits one GPU), plus the
-HBM roofline fraction of the level-1 smoother kernel and the CPU baseline (oracle) timed on the host cores.
+(BASELINE.json `metric`, configs[2]: the configuration the metric is quoted on; it fits one GPU).
 
   python bench.py --gpus N --steps K --warmup W        (N>1: one rank per GPU; under torch.distributed.run the ranks are
                                                         taken from the environment, from a bare shell bench.py starts them itself)
+  python bench.py ... --dump-outputs DIR               (also writes what the last timed step computed, see dump_outputs)
+  python bench.py ... --full                           (also everything beside the headline figure, see below)
 
 A step = one Vcycle(1) (mg_solvers.f90:129) over the resident fields: ns_pre=3 sweeps + residual + restriction on
 every level down, 40 sweeps on the coarsest, prolongation + ns_post=2 sweeps up.  Inputs are synthetic (the
 reference's seamount geometry, u=v=0, w=-1) and resident in HBM before the timed region.  Weak scaling: every rank
 owns a 512x512x64 block; `value` is V-cycles/s scaled by (global cells / cells of one block), i.e. block-V-cycles/s.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  With --full the line also carries the
+rate with a host synchronisation after every step, the HBM roofline of the level-1 smoother kernel (HIP events; PMC
+traffic from rocprofv3 child passes), the F-cycle and solve_p rates, the red-black and direct-coarsest-solve variants,
+for N>1 the transport cross-check, the exchange report and the rate at the reference's own nsmall, and the CPU
+baseline (oracle) timed on the host cores.
 """
 import argparse
 import json
@@ -36,6 +43,22 @@ PGRID = {1: (1, 1), 2: (2, 1), 4: (2, 2), 8: (4, 2)}
 CALIBRATION = {"host": "development container, 8 cores, 4x2 (emulated) ranks, seamount 512x512x64",
                "FC": {"solve_iteration": 0.66 / 0.711, "level1_sweep": 75.0 / 92.8, "level1_residual": 36.0 / 48.3},
                "RB": {"solve_iteration": 0.68 / 0.750, "level1_sweep": 67.0 / 75.9, "level1_residual": 44.0 / 42.7}}
+# --dump-outputs: float64 values of p kept in all (32 MiB, within the 64 MB bound); a larger field is sampled
+DUMP_VALUES = 1 << 22
+
+
+def dump_outputs(d, rank, world):
+    """What a caller of the timed path reads back after its last step: the level-1 pressure p (grid(1).p) without its
+    halo, float64, as DIR/p.npy of shape (nx, ny, nz) -- or, when it holds more than DUMP_VALUES / N values, those at a
+    fixed sample of flat indices (seed 0, sorted), the same for every run with the same --size and --gpus.
+    N>1: every rank writes its own block as DIR/p_rank<r>.npy."""
+    import mgroms_amd as mg
+    p = mg.grid(1).p[1:-1, 1:-1, :]
+    k = DUMP_VALUES // world
+    if p.size > k:
+        p = p.reshape(-1)[np.sort(np.random.default_rng(0).choice(p.size, size=k, replace=False))]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "p.npy" if world == 1 else f"p_rank{rank}.npy"), np.ascontiguousarray(p))
 
 
 def cpu_baseline(nx, ny, nz, method, cycles=2):
@@ -153,16 +176,23 @@ def main():
                     help="do not measure roofline.traffic in this invocation (two rocprofv3 --pmc passes over a child process, ~20 s): read the committed capture")
     ap.add_argument("--native-rccl", action="store_true",
                     help="N>1: libmgx.so's own RCCL communicator instead of the torch.distributed callbacks (opt-in: never run on more than one GPU yet)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the level-1 pressure p of the last step to DIR (float64 .npy; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (roofline, PMC traffic, other rates and orderings, "
+                         "N>1 transport check and exchanges, CPU baseline); off: set-up, warm-up, the K timed steps and the headline line only")
     args = ap.parse_args()
     if args.gpus not in PGRID:
         raise SystemExit("--gpus must be 1, 2, 4 or 8")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         _spawn_ranks(args.gpus)
 
     # N = 1: the dominant kernel's HBM traffic from the PMC counters, measured now, in child processes, before this process touches the GPU
     live_kname = (f"k_relax_nz<{args.size[2]}, true, {'true' if args.method == 'RB' else 'false'}, 3, true, true>" if args.size[2] == 64 else None)
     traffic_live = None
-    if args.gpus == 1 and not args.no_live_traffic and live_kname and "WORLD_SIZE" not in os.environ:
+    if args.full and args.gpus == 1 and not args.no_live_traffic and live_kname and "WORLD_SIZE" not in os.environ:
         traffic_live = live_traffic(*args.size, args.method, live_kname)
 
     import torch
@@ -204,7 +234,7 @@ def main():
     mg.nhydro_matrices(dx, dy, zeta, h, None, 4e3, 0.0, 0.0)
     u, v, w = resting_column_state(nx, ny, nz)
     nhydro.compute_rhs(u, v, w)
-    res0 = mg.compute_residual(1)
+    res0 = mg.compute_residual(1) if args.full else None
 
     def sync():
         torch.cuda.synchronize()
@@ -229,6 +259,41 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world)
+    scale = npx * npy
+    cells = nx * ny * nz
+
+    def headline(dt, transport, transport_check, nlev):
+        return {
+            "metric": "V-cycles/sec, seamount 512x512x64 (fine-grid smoother HBM GB/s and % of 8 TB/s: see roofline)",
+            "value": args.steps / dt * scale, "unit": "V-cycles/s (x number of 512x512x64 blocks when N>1: weak scaling)",
+            "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            "enqueue": "async (the K steps are enqueued back to back; the region closes with barrier + synchronize)",
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": f"seamount {nx * npx}x{ny * npy}x{nz} ({npx}x{npy} ranks of {nx}x{ny}x{nz}), "
+                                   f"relax_method={args.method}, ns_pre=3 ns_post=2 ns_coarsest=40, cmatrix=real, interp=linear",
+                       "levels": nlev, "step": "one Vcycle(1)", "halo_transport": transport,
+                       "native_rccl": (None if comm is None else (True if comm.native_active else f"off: {comm.native_error}")),
+                       "transport_check": transport_check, "nsmall": (8 if world == 1 else args.nsmall),
+                       "nsmall_note": (None if world == 1 else f"timed region: nsmall={args.nsmall} (coarse levels agglomerated early; a namelist member of the reference, "
+                                       f"default 8); the reference's own value for this configuration, {REFERENCE_NSMALL[world]}, is timed in also_reference_nsmall (--full)")},
+            "vcycle_roofline": {"bytes_per_cell": VCYCLE_BYTES_PER_CELL, "ms": dt / args.steps * 1e3,
+                                "frac": VCYCLE_BYTES_PER_CELL * cells / (dt / args.steps) / 1e9 / HBM_PEAK_GBS},
+        }
+
+    def finish(out):
+        mg.nhydro_clean()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(out))
+
+    if not args.full:
+        finish(headline(dt, None if comm is None else comm.transport(), None if world == 1 else "not run (--full runs it)", mg.nlevs()))
+        return
+
     res1 = mg.compute_residual(1)
     # the same K steps with a host synchronisation after every cycle (how rounds 1 and 2 timed the step): reported beside `value`
     sync()
@@ -284,7 +349,6 @@ def main():
     sweep_ms = nhydro.time_relax(1, args.sweep_reps)
     resid_ms = nhydro.time_residual(1, args.sweep_reps)
     ncol = 4 if args.method == "FC" else 2
-    cells = nx * ny * nz
     launch_bytes = SMOOTHER_BYTES_PER_CELL * cells / ncol
     achieved = launch_bytes / (sweep_ms / ncol * 1e-3) / 1e9
     # F-cycle iteration rate (solve_p iteration = Fcycle + residual), for reference.  Fcycle is enqueued (option "async"), the residual
@@ -475,23 +539,9 @@ def main():
                        "calibrated in profiles/r04_pmc_traffic.json on an 8-B/lane read of known size), WRITE exact; the largest dispatch of the kernel")
     out = None
     if rank == 0:
-        scale = npx * npy
-        out = {
-            "metric": "V-cycles/sec, seamount 512x512x64 (fine-grid smoother HBM GB/s and % of 8 TB/s: see roofline)",
-            "value": args.steps / dt * scale, "unit": "V-cycles/s (x number of 512x512x64 blocks when N>1: weak scaling)",
-            "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "enqueue": "async (the K steps are enqueued back to back; the region closes with barrier + synchronize)",
+        out = headline(dt, transport, transport_check, nlev_main)
+        out.update({
             "value_sync_each_step": args.steps / dt_sync_each * scale, "ms_per_step_sync_each_step": dt_sync_each / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"seamount {nx * npx}x{ny * npy}x{nz} ({npx}x{npy} ranks of {nx}x{ny}x{nz}), "
-                                   f"relax_method={args.method}, ns_pre=3 ns_post=2 ns_coarsest=40, cmatrix=real, interp=linear",
-                       "levels": nlev_main, "step": "one Vcycle(1)", "halo_transport": transport,
-                       "native_rccl": (None if comm is None else (True if comm.native_active else f"off: {comm.native_error}")),
-                       "transport_check": transport_check, "nsmall": (8 if world == 1 else args.nsmall),
-                       "nsmall_note": (None if world == 1 else f"timed region: nsmall={args.nsmall} (coarse levels agglomerated early; a namelist member of the reference, "
-                                       f"default 8); the reference's own value for this configuration, {REFERENCE_NSMALL[world]}, is timed in also_reference_nsmall")},
-            "vcycle_roofline": {"bytes_per_cell": VCYCLE_BYTES_PER_CELL, "ms": dt / args.steps * 1e3,
-                                "frac": VCYCLE_BYTES_PER_CELL * cells / (dt / args.steps) / 1e9 / HBM_PEAK_GBS},
             # what solve_p iterates: one F-cycle + the closing residual norm (mg_solvers.f90:61-68), through solve_p itself
             "fcycle_roofline": {"bytes_per_cell": FCYCLE_BYTES_PER_CELL, "ms": 1e3 / sp_rate, "frac": FCYCLE_BYTES_PER_CELL * cells * sp_rate / 1e9 / HBM_PEAK_GBS,
                                 "unit": "one solve_p iteration (Fcycle + closing residual norm), SURVEY 8(d): 812 B per fine cell"},
@@ -514,17 +564,12 @@ def main():
             "residual_before": res0, "residual_after": res1,
             "counters": counters_main,
             "also_rb": also_rb, "also_coarsest_direct": also_direct,
-        }
+        })
         if args.gpus == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(nx, ny, nz, args.method)
         else:
             out["cpu_baseline"] = None
-    mg.nhydro_clean()
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        print(json.dumps(out))
+    finish(out)
 
 
 if __name__ == "__main__":

@@ -11,7 +11,7 @@ cd /tmp; export TMPDIR=/tmp
 export MASTER_ADDR=127.0.0.1 MASTER_PORT=29561 WORLD_SIZE=2
 for r in 0 1; do
   RANK=$r LOCAL_RANK=$r timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/rank$r" -o r$r --output-format csv -- \
-    python3 "$R/bench.py" --gpus 2 --backend gloo --size $NX $NY $NZ --nsmall $NS --steps 20 --warmup 3 --no-cpu-baseline > "$OUT/rank$r.log" 2>&1 &
+    python3 "$R/bench.py" --full --gpus 2 --backend gloo --size $NX $NY $NZ --nsmall $NS --steps 20 --warmup 3 --no-cpu-baseline > "$OUT/rank$r.log" 2>&1 &
 done
 wait
 tail -1 "$OUT/rank0.log" | cut -c1-300

@@ -12,7 +12,7 @@ for mode in overlap onestream; do
   export MASTER_PORT=$((29570 + RANDOM % 200))
   if [ $mode = onestream ]; then export MGX_OVERLAP=0; else export MGX_OVERLAP=1; fi
   for r in 0 1; do
-    RANK=$r LOCAL_RANK=$r timeout -k 10 200 python3 "$R/bench.py" --gpus 2 --backend gloo --size $NX $NY $NZ --nsmall $NS --steps 20 --warmup 3 --no-cpu-baseline > "$OUT/${mode}_rank$r.log" 2>&1 &
+    RANK=$r LOCAL_RANK=$r timeout -k 10 200 python3 "$R/bench.py" --full --gpus 2 --backend gloo --size $NX $NY $NZ --nsmall $NS --steps 20 --warmup 3 --no-cpu-baseline > "$OUT/${mode}_rank$r.log" 2>&1 &
   done
   wait
   python3 - "$OUT/${mode}_rank0.log" $mode <<'PY'
@@ -25,7 +25,7 @@ export MGX_OVERLAP=1
 export MASTER_PORT=$((29570 + RANDOM % 200))
 for r in 0 1; do
   RANK=$r LOCAL_RANK=$r timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/rank$r" -o r$r --output-format csv -- \
-    python3 "$R/bench.py" --gpus 2 --backend gloo --size $NX $NY $NZ --nsmall $NS --steps 10 --warmup 2 --no-cpu-baseline > "$OUT/prof_rank$r.log" 2>&1 &
+    python3 "$R/bench.py" --full --gpus 2 --backend gloo --size $NX $NY $NZ --nsmall $NS --steps 10 --warmup 2 --no-cpu-baseline > "$OUT/prof_rank$r.log" 2>&1 &
 done
 wait
 python3 "$R/scripts/overlap_trace.py" $(ls "$OUT"/rank0/*kernel_trace.csv | head -1)

@@ -434,3 +434,26 @@ def test_native_rccl_world_size_one(mg):
     finally:
         L.mgx_rccl_disconnect()
         mg.nhydro_clean()
+
+
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """`bench.py` without --full: set-up, warm-up, the K timed steps and the headline line, nothing of --full's figures.  With
+    --dump-outputs it writes the level-1 p after the last timed step: at 64x64x16 the whole interior, which must be the oracle's
+    p after warmup + steps four-colour V-cycles, bit for bit."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--size", "64", "64", "16", "--steps", "3",
+                          "--warmup", "2", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert (j["steps"], j["warmup"], j["n_gpus"], j["dtype"], j["higher_is_better"]) == (3, 2, 1, "f64", True)
+    assert j["value"] > 0 and abs(j["ms_per_step"] * j["value"] - 1e3) <= 1e-9 * 1e3
+    assert not {"roofline", "cpu_baseline", "also_rb", "value_sync_each_step"} & set(j)
+    p = np.load(tmp_path / "p.npy")
+    o = _oracle(64, 64, 16, relax_method="FC")
+    for _ in range(5):
+        o.vcycle(1)
+    assert p.dtype == np.float64 and np.array_equal(p, o.field("p")[1:-1, 1:-1, :])
+    o.close()
