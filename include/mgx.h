@@ -57,7 +57,12 @@ int mgx_read_namelist(const char *path, mgx_params *p);
 
 /* nhydro_init(nx,ny,nz,npxg,npyg) (nhydro.f90:18-33).  nx,ny,nz: local block; npx,npy: process grid;
  * rank: this process's rank, placed at pi=mod(rank,npx), pj=rank/npx (mg_grids.f90:593-594).
- * par == NULL: read ./nh_namelist if present, else defaults (what the reference does). */
+ * par == NULL: read ./nh_namelist if present, else defaults (what the reference does).
+ * nx, ny, nz must be even; nz need not be a power of two.  Coarser levels halve nz as the reference does (an odd level drops its
+ * top row on restriction, mg_intergrids.f90:149-160).  Level-1 colour pass: a register-resident kernel for nz in {2, 4, 8, 12, 16,
+ * 20, 24, 32, 40, 48, 64}; a tall-column kernel for nz in {80, 96, 128} when the matrix is matrix-free (define_matrices, no bmask);
+ * every other nz, and the tall sizes with stored coefficients, run the generic kernel plus a physical-halo launch per colour.
+ * relax_method = 'GS' accepts any nz (register-resident columns for the powers of two up to 64, the generic column otherwise). */
 int mgx_init(int nx, int ny, int nz, int npx, int npy, int rank, const mgx_params *par);
 /* nhydro_matrices(dx,dy,zeta,h,rmask,hc,theta_b,theta_s) (nhydro.f90:36-50) -> define_matrices
  * (mg_define_matrix.f90:28-208).  rmask may be NULL (= all ones; only read when bmask). */

@@ -556,7 +556,7 @@ int relax(int lev, int nsweeps) {
   if (S.tictoc && S.tt_done.size() > 4096) tt_collect();
   if (S.method == M_GS) {  // exact lexicographic order by hyperplanes; halo fill once per sweep (mg_relax.f90:131-141)
     for (int it = 1; it <= nsweeps; it++) {
-      if (!mgxk_relax_gs_sweep(S.stream, &L.v, S.real)) return fail("relax_method='GS': nz=%d has no register-resident kernel (nz must be a power of two <= 64)", L.nz);
+      if (!mgxk_relax_gs_sweep(S.stream, &L.v, S.real)) return fail("relax_method='GS': the sweep of level %d could not be launched", lev);
       S.n_launch += L.ny + 2 * L.nx - 2;
       CHK(fill_halo_js(L, L.v.p));
     }
@@ -616,8 +616,11 @@ int relax(int lev, int nsweeps) {
           if (S.rbseq_window && L.rbs_m > 0) {
             if (!have_d0) { mgxk_rbseq_d0(S.stream, &L.v, rb); S.n_launch++; }   // (the nz = 128 colour pass does not leave it)
           }
-          if (S.rbseq_window && L.rbs_m > 0 && mgxk_rbseq_window(S.stream, &L.v, rb, ph, closed ? 1 : 0, L.rbs_m, S.rbseq_rowcut ? L.rbs_rows : L.nz)) {
-            S.n_launch++; S.n_window++; fused = 1;
+          const int kcut = S.rbseq_rowcut ? L.rbs_rows : L.nz;
+          if (S.rbseq_window && L.rbs_m > 0 && mgxk_rbseq_window(S.stream, &L.v, rb, ph, closed ? 1 : 0, L.rbs_m, kcut)) {
+            // the window stores the physical images of the rows it corrects (k < kcut) only: the rows below the cut keep those of the
+            // colour pass, which the generic kernel (no register instance for this nz / matrix) does not store
+            S.n_launch++; S.n_window++; fused = (pass & 1) || kcut >= L.nz;
             CHK(fill_halo_js(L, L.v.p, fused));
             continue;
           }

@@ -733,7 +733,9 @@ void mgxk_rbseq_setup(hipStream_t st, const LevView *L) {
 // rows per correction wave: enough waves to fill the chip on the large levels, whole columns on the small ones
 static void rbseq_apply_shape(const LevView *L, int *ku, int *kr) {
   const int nyh = L->ny / 2, nz = L->nz;
-  *ku = nz % 8 == 0 ? 8 : (nz % 4 == 0 ? 4 : 2);
+  // (ku divides nz: an odd coarse level -- nz = 3 or 5 below nz = 24, 40, 48, 80, 96 -- takes one row at a time, or a wave would write
+  // the row above its column's top, i.e. the bottom row of the next plane)
+  *ku = nz % 8 == 0 ? 8 : (nz % 4 == 0 ? 4 : (nz % 2 == 0 ? 2 : 1));
   *kr = nz;
   const long long waves = (long long)((nyh + WAVE - 1) / WAVE) * L->nx;
   while (*kr > *ku && *kr % 2 == 0 && (*kr / 2) % *ku == 0 && waves * (nz / *kr) < 4096) *kr /= 2;
@@ -928,7 +930,7 @@ void mgxk_rbseq_apply(hipStream_t st, const LevView *L, int rb, Sides ph, int sn
 #define APPLY_CASE(KUV)                                                                                              \
   { if (snapw) hipLaunchKernelGGL((k_rbseq_apply<KUV, true>), grd, blk, 0, st, *L, rb, ph, kr, nt);                 \
     else hipLaunchKernelGGL((k_rbseq_apply<KUV, false>), grd, blk, 0, st, *L, rb, ph, kr, nt); }
-  if (ku == 8) APPLY_CASE(8) else if (ku == 4) APPLY_CASE(4) else APPLY_CASE(2)
+  if (ku == 8) APPLY_CASE(8) else if (ku == 4) APPLY_CASE(4) else if (ku == 2) APPLY_CASE(2) else APPLY_CASE(1)
 #undef APPLY_CASE
 }
 

@@ -16,15 +16,9 @@
 // diagonals (red-black): those are then read from the snapshot L.p1 taken before the pass (SNAP).
 // The tridiagonal pivots (bet, gam) depend on the matrix only and are precomputed at set-up.
 // ------------------------------------------------------------------------------------------------
+// One column (any nz >= 2, a runtime value): forward sweep through p, back substitution re-reading it.  No mirrors.
 template <bool REAL, bool SNAP>
-__global__ __launch_bounds__(256) void k_relax_colour(LevView L, int i0, int istep, int nplanes, int jodd_fixed, int rb, Sides ph) {
-  const int jh = blockIdx.x * WAVE + threadIdx.x;
-  const int ipl = blockIdx.y * blockDim.y + threadIdx.y;
-  if (jh >= (L.ny >> 1) || ipl >= nplanes) return;
-  const int i = i0 + istep * ipl;
-  // RB: j = 1+mod(i+rb,2),ny,2 (mg_relax.f90:174) ; FC: fixed parity (:216-217)
-  const int jodd = jodd_fixed >= 0 ? jodd_fixed : (((i + rb) & 1) == 0);
-  if (sides_part_skip(ph, i, L.nx, jodd, blockIdx.x, gridDim.x)) return;
+__device__ __forceinline__ void relax_col_any(const LevView &L, const int i, const int jh, const int jodd) {
   int c, jm, jp;  // positions of columns j, j-1, j+1 inside a row
   if (jodd) { c = L.HO + jh; jm = L.EO + jh; jp = jm + 1; }
   else      { c = L.EO + jh + 1; jm = L.HO + jh; jp = jm + 1; }
@@ -92,6 +86,18 @@ __global__ __launch_bounds__(256) void k_relax_colour(LevView L, int i0, int ist
     p[ko] = x;
   }
 #undef LOAD_ROW
+}
+
+template <bool REAL, bool SNAP>
+__global__ __launch_bounds__(256) void k_relax_colour(LevView L, int i0, int istep, int nplanes, int jodd_fixed, int rb, Sides ph) {
+  const int jh = blockIdx.x * WAVE + threadIdx.x;
+  const int ipl = blockIdx.y * blockDim.y + threadIdx.y;
+  if (jh >= (L.ny >> 1) || ipl >= nplanes) return;
+  const int i = i0 + istep * ipl;
+  // RB: j = 1+mod(i+rb,2),ny,2 (mg_relax.f90:174) ; FC: fixed parity (:216-217)
+  const int jodd = jodd_fixed >= 0 ? jodd_fixed : (((i + rb) & 1) == 0);
+  if (sides_part_skip(ph, i, L.nx, jodd, blockIdx.x, gridDim.x)) return;
+  relax_col_any<REAL, SNAP>(L, i, jh, jodd);
 }
 
 
@@ -506,6 +512,15 @@ __global__ __launch_bounds__(64, 1) void k_relax_gs_front(LevView L, int t) {
   const Sides none = {0, 0, 0, 0};  // halo is refreshed once per sweep, after the loop (mg_relax.f90:141)
   relax_col_nz<NZ, REAL, false, 1>(L, i, (j - 1) >> 1, j & 1, none);
 }
+// the same hyperplane for a level with no register-resident instance (runtime nz: 128, and the sizes that are not powers of two)
+template <bool REAL>
+__global__ __launch_bounds__(64, 1) void k_relax_gs_front_any(LevView L, int t) {
+  int ilo = (t - L.ny + 1) / 2; if (ilo < 1) ilo = 1;
+  const int i = ilo + blockIdx.x * WAVE + threadIdx.x;
+  const int j = t - 2 * i;
+  if (i > L.nx || j < 1 || j > L.ny) return;
+  relax_col_any<REAL, false>(L, i, (j - 1) >> 1, j & 1);
+}
 
 // Whole relax(lev, nsweeps) of a SMALL level (<= 1024 columns per colour, no neighbours) in ONE launch of ONE
 // workgroup: colours are separated by __syncthreads() instead of kernel boundaries.  The coarsest-level solve of
@@ -762,7 +777,7 @@ static void launch_relax_nz(hipStream_t st, const LevView *L, int i0, int istep,
 
 extern "C" {
 
-// one Gauss-Seidel sweep as ny+2nx-2 hyperplane launches; returns 0 when nz has no register-resident variant
+// one Gauss-Seidel sweep as ny+2nx-2 hyperplane launches (register-resident columns for nz a power of two <= 64, any nz otherwise)
 int mgxk_relax_gs_sweep(hipStream_t st, const LevView *L, int real) {
   for (int t = 3; t <= L->ny + 2 * L->nx; t++) {
     int ilo = (t - L->ny + 1) / 2; if (ilo < 1) ilo = 1;
@@ -771,7 +786,11 @@ int mgxk_relax_gs_sweep(hipStream_t st, const LevView *L, int real) {
     dim3 grd((ihi - ilo + 1 + WAVE - 1) / WAVE), blk(WAVE);
 #define GS_CASE(NZV) case NZV: if (real) hipLaunchKernelGGL((k_relax_gs_front<NZV, true>), grd, blk, 0, st, *L, t); \
                                else hipLaunchKernelGGL((k_relax_gs_front<NZV, false>), grd, blk, 0, st, *L, t); break;
-    switch (L->nz) { GS_CASE(2) GS_CASE(4) GS_CASE(8) GS_CASE(16) GS_CASE(32) GS_CASE(64) default: return 0; }
+    switch (L->nz) {
+      GS_CASE(2) GS_CASE(4) GS_CASE(8) GS_CASE(16) GS_CASE(32) GS_CASE(64)
+      default: if (real) hipLaunchKernelGGL((k_relax_gs_front_any<true>), grd, blk, 0, st, *L, t);
+               else hipLaunchKernelGGL((k_relax_gs_front_any<false>), grd, blk, 0, st, *L, t);
+    }
 #undef GS_CASE
   }
   return 1;
@@ -838,7 +857,7 @@ int mgxk_relax_small(hipStream_t st, const LevView *L, int nsweeps, int method, 
 
 // returns 1 when the launched kernel also wrote the physical-boundary mirrors of p (no k_halo_phys needed)
 int mgxk_relax_ks(hipStream_t, const LevView *, int, int, int, int, int, int, int, Sides);  // mgx_relax_ks.hip
-int mgxk_relax_nz128(hipStream_t, const LevView *, int, int, int, int, int, int, int, Sides);  // mgx_relax_tall.hip
+int mgxk_relax_tall(hipStream_t, const LevView *, int, int, int, int, int, int, int, Sides);  // mgx_relax_tall.hip
 // returns bit 0: the kernel stored the physical mirrors itself; bit 1: it wrote L->d0w
 int mgxk_relax_colour(hipStream_t st, const LevView *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, Sides ph) {
   if (const int ks = mgxk_relax_ks(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph)) return ks;  // mid levels: rows split over the waves of a workgroup
@@ -852,7 +871,13 @@ int mgxk_relax_colour(hipStream_t st, const LevView *L, int i0, int istep, int n
 #endif
     case 64: launch_relax_nz<64>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
 #ifndef MGX_QUICK
-    case 128: if (mgxk_relax_nz128(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph)) return 1; break;
+    // vertical sizes that are not powers of two (ROMS / CROCO users choose nz for their physics) and their coarser levels
+    case 12: launch_relax_nz<12>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
+    case 20: launch_relax_nz<20>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
+    case 24: launch_relax_nz<24>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
+    case 40: launch_relax_nz<40>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
+    case 48: launch_relax_nz<48>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
+    case 80: case 96: case 128: if (mgxk_relax_tall(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph)) return 1; break;
 #endif
     default: break;
   }
@@ -864,7 +889,11 @@ int mgxk_relax_colour(hipStream_t st, const LevView *L, int i0, int istep, int n
 }
 // does mgxk_relax_colour run a register-resident kernel (which writes mirrors and chained snapshots) on this level?
 int mgxk_has_reg_kernel(const LevView *L) {
-  switch (L->nz) { case 2: case 4: case 8: case 16: case 32: case 64: return 1; case 128: return L->zy != nullptr && getenv("MGX_NO_TALL") == nullptr; default: return 0; }
+  switch (L->nz) {
+    case 2: case 4: case 8: case 16: case 32: case 64: case 12: case 20: case 24: case 40: case 48: return 1;
+    case 80: case 96: case 128: return L->zy != nullptr && getenv("MGX_NO_TALL") == nullptr;
+    default: return 0;
+  }
 }
 void mgxk_snapshot_k1(hipStream_t st, const LevView *L) {
   hipLaunchKernelGGL(k_snapshot_k1, dim3((L->RS + 255) / 256, L->nx + 2), dim3(256), 0, st, *L);

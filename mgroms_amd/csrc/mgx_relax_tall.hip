@@ -1,4 +1,4 @@
-// z-line smoother for tall columns (nz = 128, BASELINE config 5): one colour pass, matrix-free cross terms, the lower 64 rows'
+// z-line smoother for tall columns (nz = 128, BASELINE config 5; 96 and 80 alike): one colour pass, matrix-free cross terms, the lower 64 rows'
 // forward values in LDS.  mg_relax.f90:237-305 + :308-334.  Its own translation unit: x and gam of 64 rows stay in registers here
 // (500 of 512), it needs a larger `#pragma unroll` budget than the others (Makefile), and the 16-byte pair loads of mgx_relax.hip
 // do not fit next to them (0.8 KB/lane of scratch); slots 4 / 7 from regenerated zw do.
@@ -256,35 +256,38 @@ __global__ __launch_bounds__(128, 1) void k_relax_tall(LevView L, int i0, int is
 }
 
 
-// nz = 128 (BASELINE config 5): matrix-free form only, lower 64 rows through memory (relax_col_mf_tall)
-extern "C" int mgxk_relax_nz128(hipStream_t st, const LevView *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, Sides ph) {
-  if (L->zy == nullptr) return 0;
+// nz = 128 (BASELINE config 5), 96 and 80: matrix-free form only, lower 64 rows through memory (relax_col_mf_tall)
+extern "C" int mgxk_relax_tall(hipStream_t st, const LevView *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, Sides ph) {
+  if (L->zy == nullptr || (L->nz != 128 && L->nz != 96 && L->nz != 80)) return 0;
   mgx_before_launch();
   static const bool noxcd = getenv("MGX_NO_XCD") != nullptr, notall = getenv("MGX_NO_TALL") != nullptr;
   if (notall) return 0;
   const int gx0 = (L->ny / 2 + WAVE - 1) / WAVE, gx = noxcd ? -gx0 : gx0;
   const int by = gx0 * nplanes >= 2048 ? 2 : 1;
   dim3 blk(WAVE, by), grd(gx0 * ((nplanes + by - 1) / by));
-  const bool stream = (double)L->nx * L->ny * 128 * 72.0 > 256e6;
+  const bool stream = (double)L->nx * L->ny * L->nz * 72.0 > 256e6;
   const size_t lds = (size_t)by * 64 * WAVE * sizeof(double);  // the lower 64 rows' forward values: 32 KB per wave
-#define LAUNCH128_ONE(RV, SV, STV)                                                                                       \
+#define LAUNCH_TALL_ONE(NZV, RV, SV, STV)                                                                                \
   {                                                                                                                     \
     static bool attr = false;                                                                                           \
     if (!attr) {                                                                                                        \
-      if (hipFuncSetAttribute((const void *)k_relax_tall<128, 64, RV, SV, 3, STV>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * WAVE * (int)sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return 0; } \
+      if (hipFuncSetAttribute((const void *)k_relax_tall<NZV, 64, RV, SV, 3, STV>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * WAVE * (int)sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return 0; } \
       attr = true;                                                                                                      \
     }                                                                                                                   \
-    hipLaunchKernelGGL((k_relax_tall<128, 64, RV, SV, 3, STV>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx); \
+    hipLaunchKernelGGL((k_relax_tall<NZV, 64, RV, SV, 3, STV>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx); \
   }
-#define LAUNCH128(STV)                                                                                                  \
+#define LAUNCH_TALL(NZV, STV)                                                                                           \
   {                                                                                                                     \
-    if (real && snap) LAUNCH128_ONE(true, true, STV)                                                                    \
-    else if (real) LAUNCH128_ONE(true, false, STV)                                                                      \
-    else LAUNCH128_ONE(false, false, STV)                                                                               \
+    if (real && snap) LAUNCH_TALL_ONE(NZV, true, true, STV)                                                             \
+    else if (real) LAUNCH_TALL_ONE(NZV, true, false, STV)                                                               \
+    else LAUNCH_TALL_ONE(NZV, false, false, STV)                                                                        \
   }
-  if (stream) LAUNCH128(true) else LAUNCH128(false)
-#undef LAUNCH128
-#undef LAUNCH128_ONE
+#define LAUNCH_TALL_NZ(NZV) { if (stream) LAUNCH_TALL(NZV, true) else LAUNCH_TALL(NZV, false) }
+  if (L->nz == 128) LAUNCH_TALL_NZ(128)
+  else if (L->nz == 96) LAUNCH_TALL_NZ(96)
+  else LAUNCH_TALL_NZ(80)
+#undef LAUNCH_TALL_NZ
+#undef LAUNCH_TALL
+#undef LAUNCH_TALL_ONE
   return mgx_launched();
 }
-
