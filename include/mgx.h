@@ -212,6 +212,15 @@ int mgx_set_verbose(int level);
  * "overlap" (default 0; MGX_OVERLAP=1): four colours on a level with neighbours, halos by the pushes: the boundary part of a colour pass and
  *   the exchange on a second stream beside the interior part.  Same bits; slower where it could be measured.
  * "ksp" (default 1): the persistent relax of the closed mid levels; read back 0 after it timed out (then off until mgx_init or "ksp" = 1).
+ * "cycle_precision" (64 default, or 32; any other value is refused; survives mgx_clean / mgx_init): 32 = mixed-precision solve_p.  The iterate,
+ *   r = b - A p, its norm, the history, the stopping test and the prints stay fp64 as in solve_p; each iteration runs the F-cycle in correction
+ *   form on fp32 copies of every level (A e = r / ||r|| from e = 0, same nsmall hierarchy, interp_type and relax_method; red-black as the parallel
+ *   pass of rb_seq = 0) and adds the correction to p (iterative refinement, mgx_mixed.hip).  Applies to mgx_solve_p and through it to
+ *   mgx_solve / mgx_solve_device.  The operator entry points (mgx_fcycle, mgx_vcycle, mgx_vcycle2, mgx_relax, mgx_residual, mgx_fine2coarse,
+ *   mgx_coarse2fine) stay the reference's fp64 operators on grid(lev) fields whatever the option says.  Refused at the first mixed solve:
+ *   a process grid larger than 1 x 1, relax_method = 'GS', option "rb_exact".  The fp32 copies (~48 B per cell) are allocated at the first
+ *   mixed solve and their coefficients converted again after every mgx_matrices / mgx_set_field of cA.
+ *   Read-only: "mixed_iterations" (solve_p iterations run with fp32 cycles since mgx_init).
  * Read-only through mgx_get_option: "p2p_failed" (a peer-to-peer wait of THIS rank timed out since the ranks last agreed: see below),
  *   "overlapped_passes". */
 int mgx_set_option(const char *name, int value);
@@ -243,6 +252,11 @@ int mgx_selftest_divc(const double *a, const double *b, int n, long long *nbad);
 int mgx_time_residual(int lev, int reps, float *ms);
 /* counters since mgx_init: out[0]=kernel launches, out[1]=halo fills, out[2]=exchanges, out[3]=allreduces */
 int mgx_counters(long long *out);
+/* test hook of the fp32 cycle of option "cycle_precision" = 32 (single rank): converts the level's fp64 fields into its fp32 copy, runs one
+ * fp32 operator, converts the result back.  op = "relax" (n sweeps on p, b of level lev -> p), "residual" (p, b -> r), "fine2coarse"
+ * (r of lev -> b of lev+1, p of lev+1 = 0), "coarse2fine" (p of lev += interpolation of p of lev+1), "resrest" (restriction of b - A p of lev
+ * -> b of lev+1, p of lev+1 = 0: the down leg of a V-cycle).  No Fortran counterpart. */
+int mgx_mixed_op(const char *op, int lev, int n);
 
 /* ---- peer-to-peer halo transport (replaces the MPI_Isend/MPI_Irecv/MPI_Waitall of fill_halo_3D[_relax],
  * mg_mpi_exchange.f90:504-718, for the p/b/r halos of the cycle) ----

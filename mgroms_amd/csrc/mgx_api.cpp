@@ -111,6 +111,15 @@ void mgxr_disconnect(void);
 int mgxr_exchange(hipStream_t, int, const int *, double *const *, double *const *, const int *);
 int mgxr_allreduce(hipStream_t, double *, int);
 int mgxr_allgather(hipStream_t, const int *, int, const double *, double *, int);
+// fp32 cycle of the mixed-precision solve_p (mgx_mixed.hip)
+void mgxx_relax_pass(hipStream_t, const LevView32 *, int, int, int, int, int, int, int);
+void mgxx_snapshot(hipStream_t, const LevView32 *);
+void mgxx_residual(hipStream_t, const LevView32 *, int);
+void mgxx_resrest(hipStream_t, const LevView32 *, const LevView32 *, int);
+void mgxx_restrict(hipStream_t, const LevView32 *, const LevView32 *, const float *);
+void mgxx_coarse2fine(hipStream_t, const LevView32 *, const LevView32 *, int);
+void mgxx_to32(hipStream_t, const LevView *, const LevView32 *, const double *, float *, double);
+void mgxx_to64(hipStream_t, const LevView *, const LevView32 *, const float *, double *, double, int);
 }
 
 // a HIP error that was pending when a kernel wrapper started (mgx_before_launch, mgx_device.h): reported by the next synchronising call
@@ -145,6 +154,8 @@ struct Level {
   double *zy_store, *zx_store;  // slope arrays; v.zy/v.zx point here while the matrix is the one define_matrices built
   double *f2d_store[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, *tab_store[2] = {nullptr, nullptr};  // m4,d4,m7,d7,h2,hi2,ze2 and cffw,csw (LevView)
   double *zg_store[4] = {nullptr, nullptr, nullptr, nullptr};  // dx2,dy2,cffr,csr (LevView)
+  LevView32 v32 = {};           // fp32 shadow of the mixed-precision solve_p (allocated at the first mixed solve)
+  size_t n3js32 = 0;            // floats in one of its JS arrays
 };
 
 struct TicRec { int lev, sub; hipEvent_t e0, e1; };
@@ -224,6 +235,13 @@ struct State {
   int rbseq_fuse = 1;    // option "rbseq_fuse" / MGX_NO_RBSEQ_FUSE=1: the correction of the sequential-order red-black inside the walk's launch (k_rbseq_scan, FUSE) instead of a launch behind it (A/B)
   int use_chain = 1;     // option "restrict_chain" / MGX_NO_RESTRICT_CHAIN=1: Fcycle's first-leg restrictions below level 1 as one launch (A/B)
   int fuse_closing = 1;  // option "fuse_closing" / MGX_NO_FUSE_CLOSING=1: the closing compute_residual(1) of a solve_p iteration also restricts its r for the next Fcycle, one kernel, no r written (A/B)
+  // option "cycle_precision" (64 default, 32): solve_p keeps its fp64 iterate, residual, norm and stopping test and runs the F-cycle in
+  // correction form on fp32 shadows of every level (solve_p_mixed, mgx_mixed.hip).  The shadows are allocated at the first mixed solve and
+  // their coefficients converted again whenever the fp64 coefficients changed (coef_gen: define_matrices, mgx_set_field of cA)
+  int cycle_precision = 64;
+  long long n_mixed = 0;          // read-only option "mixed_iterations": solve_p iterations run with fp32 cycles since mgx_init
+  bool mx_ready = false;
+  unsigned long long coef_gen = 0, mx_gen = ~0ULL;
   int c2f_skip = 1;   // the cycles' prolongation leaves the columns alone that the first colour of the following four-colour relax overwrites unread (option "c2f_skip", MGX_C2F_NOSKIP=1)
   long long n_launch = 0, n_halo = 0, n_exch = 0, n_allred = 0;
   std::string err, transport_name;
@@ -970,6 +988,152 @@ int solve_p(double tol, int maxite, int *nite_out, double *res_out, double *hist
   return 0;
 }
 
+// ---- mixed-precision solve_p (option "cycle_precision" = 32) ------------------------------------------------------------
+// Iterative refinement around the reference's F-cycle: the fp64 loop below keeps p, r = b - A p, ||r||, the history and the stopping
+// test of solve_p (the accuracy contract is solver_prec on the fp64 relative residual, mg_solvers.f90:50-80); each iteration runs the
+// F-cycle in correction form, A e = s r from e = 0, on fp32 shadows of every level (mgx_mixed.hip) and adds e / s to p.  The cycle only
+// has to deliver a correction good to ~1e-2 of r, which fp32 does.  Single rank only: the halo and gather callbacks carry doubles.
+
+// the layout of LevView with 4-byte elements: the first interior column of either half-row 128-byte aligned
+void make_view32(LevView32 &v, int nx, int ny, int nz) {
+  v.nx = nx; v.ny = ny; v.nz = nz;
+  v.EO = 31;
+  v.HO = roundup(32 + ny / 2, 32);
+  v.RS = roundup(v.HO + ny / 2 + 1, 32);
+  v.plane = (long long)nz * v.RS;
+}
+int fmalloc(float **p, size_t n) { double *q = nullptr; CHK(dmalloc(&q, (n + 1) / 2)); *p = (float *)q; return 0; }
+
+// the combinations the fp32 cycle does not serve
+int mixed_check() {
+  if (S.nranks > 1) return fail("cycle_precision = 32 needs a single rank (process grid %d x %d): the halo and gather callbacks carry doubles", S.npx, S.npy);
+  if (S.method == M_GS) return fail("cycle_precision = 32 does not serve relax_method = 'GS' (four colours or red-black only)");
+  if (S.rb_exact) return fail("cycle_precision = 32 does not serve option rb_exact (the fp32 red-black pass is the parallel one)");
+  return 0;
+}
+
+// allocate the fp32 shadow on first use (through the allocation list: mgx_clean frees it) and convert the coefficients and pivots
+// whenever the fp64 ones have changed since the last conversion
+int mixed_prepare() {
+  if (!S.mx_ready) {
+    for (auto &L : S.lev) {
+      LevView32 &v = L.v32;
+      make_view32(v, L.nx, L.ny, L.nz);
+      L.n3js32 = (size_t)(L.nx + 2) * v.plane;
+      CHK(fmalloc(&v.e, L.n3js32)); CHK(fmalloc(&v.f, L.n3js32)); CHK(fmalloc(&v.r, L.n3js32));
+      for (int s = 0; s < 8; s++) CHK(fmalloc(&v.cA[s], L.n3js32));
+      CHK(fmalloc(&v.bet, L.n3js32));
+      v.p1 = nullptr;
+      if (S.method == M_RB && S.real) CHK(fmalloc(&v.p1, (size_t)(L.nx + 2) * v.RS));
+    }
+    S.mx_ready = true;
+    S.mx_gen = ~0ULL;
+  }
+  if (S.mx_gen != S.coef_gen) {
+    for (auto &L : S.lev) {
+      for (int s = 0; s < 8; s++) mgxx_to32(S.stream, &L.v, &L.v32, L.v.cA[s], L.v32.cA[s], 1.0);
+      mgxx_to32(S.stream, &L.v, &L.v32, L.v.bet, L.v32.bet, 1.0);   // pivots: computed in fp64 from the fp64 slots (k_pivots), rounded
+      S.n_launch += 9;
+    }
+    S.mx_gen = S.coef_gen;
+  }
+  return 0;
+}
+
+// relax(lev, nsweeps) on the fp32 shadow: four colours, or the parallel red-black pass (k = 1 same-colour diagonals from a snapshot
+// taken before each colour: the fp64 pass with rb_seq = 0)
+void relax32(int lev, int nsweeps) {
+  LevView32 &v = S.lev[lev - 1].v32;
+  for (int it = 1; it <= nsweeps; it++) {
+    if (S.method == M_FC) {
+      for (int fc1 = 1; fc1 <= 2; fc1++)
+        for (int fc2 = 1; fc2 <= 2; fc2++) { mgxx_relax_pass(S.stream, &v, fc1, 2, v.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0); S.n_launch++; }
+    } else {
+      for (int rb = 1; rb <= 2; rb++) {
+        if (S.real) { mgxx_snapshot(S.stream, &v); S.n_launch++; }
+        mgxx_relax_pass(S.stream, &v, 1, 1, v.nx, -1, rb, S.real, S.real); S.n_launch++;
+      }
+    }
+  }
+}
+void coarse2fine32(int lev) { mgxx_coarse2fine(S.stream, &S.lev[lev - 1].v32, &S.lev[lev].v32, S.linear); S.n_launch++; }
+
+// mg_solvers.f90:129-151 on the shadow; lead_c2f: Fcycle's coarse2fine(lev1) comes first (:119-120)
+void vcycle32(int lev1, bool lead_c2f) {
+  for (int lev = lev1; lev <= S.nlevs - 1; lev++) {
+    if (lead_c2f && lev == lev1) coarse2fine32(lev);
+    relax32(lev, S.par.ns_pre);
+    mgxx_resrest(S.stream, &S.lev[lev - 1].v32, &S.lev[lev].v32, S.real); S.n_launch++;   // compute_residual(lev) + fine2coarse(lev)
+  }
+  relax32(S.nlevs, S.par.ns_coarsest);
+  for (int lev = S.nlevs - 1; lev >= lev1; lev--) {
+    coarse2fine32(lev);
+    relax32(lev, S.par.ns_post);
+  }
+}
+
+// mg_solvers.f90:104-126 on the shadow, level 1 holding (e, f) = (0, s r): the first leg restricts f (the residual of e = 0)
+void fcycle32() {
+  TicScope ts(1, "Fcycle");
+  for (int lev = 1; lev <= S.nlevs - 1; lev++) {
+    mgxx_restrict(S.stream, &S.lev[lev - 1].v32, &S.lev[lev].v32, S.lev[lev - 1].v32.f); S.n_launch++;
+  }
+  relax32(S.nlevs, S.par.ns_coarsest);
+  for (int lev = S.nlevs - 1; lev >= 1; lev--) vcycle32(lev, true);
+}
+
+// solve_p with fp32 cycles: the same prints, fort.100 lines, history, warm_start handling and res0 relative to ||b|| as solve_p
+int solve_p_mixed(double tol, int maxite, int *nite_out, double *res_out, double *hist) {
+  CHK(mixed_check());
+  CHK(mixed_prepare());
+  Level &L = S.lev[0];
+  if (S.verbose && S.rank == 0) printf(" - solve p:\n");
+  TicScope ts(1, "solve");
+  const auto tstart = std::chrono::steady_clock::now();
+  if (!S.warm_start) HIPCHK(hipMemsetAsync(L.v.p, 0, L.n3js * sizeof(double), S.stream));
+  mgxk_sumsq(S.stream, &L.v, L.v.b, S.d_partial, S.d_scalar); S.n_launch += 2;
+  double bnorm; CHK(global_sum(L, &bnorm)); bnorm = sqrt(bnorm);
+  int nite = 0;
+  double rabs; CHK(residual(1, &rabs));   // fp64 r = b - A p, written into grid(1)%r
+  double res0 = rabs / bnorm, rnorm = res0;
+  const double rnorm0 = res0;
+  if (hist) hist[0] = res0;
+  FILE *f100 = (S.verbose && S.rank == 0) ? fopen("fort.100", "a") : nullptr;
+  if (f100) fprintf(f100, " %24.16E %d\n", res0, nite);
+  while (nite < maxite && res0 > tol) {
+    // f = s r with s = 1 / ||r||: |f| <= 1, nothing underflows however small the residual has become; e = 0
+    const double sc = rabs > 0.0 ? 1.0 / rabs : 1.0;
+    mgxx_to32(S.stream, &L.v, &L.v32, L.v.r, L.v32.f, sc); S.n_launch++;
+    HIPCHK(hipMemsetAsync(L.v32.e, 0, L.n3js32 * sizeof(float), S.stream));
+    fcycle32();
+    mgxx_to64(S.stream, &L.v, &L.v32, L.v32.e, L.v.p, rabs > 0.0 ? rabs : 1.0, 1); S.n_launch++;   // p += e / s, halo images included
+    CHK(residual(1, &rabs));
+    rnorm = rabs / bnorm;
+    const double conv = res0 / rnorm;
+    res0 = rnorm;
+    nite++;
+    S.n_mixed++;
+    if (hist) hist[nite] = rnorm;
+    if (S.verbose && S.rank == 0) printf("ite = %2d: res = %s / conv = %10.3f\n", nite, fortran_e3(rnorm, 10).c_str(), conv);
+    if (f100) fprintf(f100, " %24.16E %24.16E\n", rnorm, conv);
+  }
+  if (f100) fclose(f100);
+  if (S.verbose && S.rank == 0) {
+    const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - tstart).count();
+    const double np = (double)L.npx * L.npy, ncell = (double)L.nx * L.npx * (double)L.ny * L.npy * (double)L.nz;
+    const double perf = dt * np / (-log(res0 / rnorm0) / log(10.0)) / ncell;
+    printf(" --- summary ---\ntime spent to solve :%8.3f s\nrescaled performance:%s\n ---------------\n", dt, fortran_e3(perf, 10).c_str());
+  }
+  if (nite_out) *nite_out = nite;
+  if (res_out) *res_out = res0;
+  return 0;
+}
+
+// the solve_p of mgx_solve_p / mgx_solve / mgx_solve_device: fp64 cycles or fp32 cycles under fp64 refinement
+int solve_p_opt(double tol, int maxite, int *nite_out, double *res_out, double *hist) {
+  return S.cycle_precision == 32 ? solve_p_mixed(tol, maxite, nite_out, res_out, hist) : solve_p(tol, maxite, nite_out, res_out, hist);
+}
+
 // ---- set-up: mg_define_matrix.f90:28-208 ----------------------------------------------------------
 int gather2d(Level &L, double *src_tmp, double *dst) {
   const int nxc = L.nx / L.ngx, nyc = L.ny / L.ngy, Ng = nxc * nyc;
@@ -1068,6 +1232,7 @@ int define_matrices() {
   CHK(sync_stream());
   set_window_planes();
   S.cd_valid = 0;
+  S.coef_gen++;
   S.have_matrix = true;
   return 0;
 }
@@ -1463,7 +1628,7 @@ void mgx_clean(void) {
   if (S.ev_s) (void)hipEventDestroy(S.ev_s);
   if (S.ev_x) (void)hipEventDestroy(S.ev_x);
   tt_collect();
-  hipStream_t st = S.stream; int vb = S.verbose, ws = S.warm_start, tc = S.tictoc, eh = S.exact_halos, rx = S.rb_exact, rq = S.rb_seq, kr = S.keep_r, cs = S.c2f_skip, fc = S.fuse_closing, uc = S.use_chain, rf = S.rbseq_fuse, rw = S.rbseq_window, cdo = S.coarsest_direct, rfm = S.rbseq_fuse_min, ovl = S.overlap, kp = S.use_ksp, fz = S.use_fuse, ao = S.async_ops;
+  hipStream_t st = S.stream; int vb = S.verbose, ws = S.warm_start, tc = S.tictoc, eh = S.exact_halos, rx = S.rb_exact, rq = S.rb_seq, kr = S.keep_r, cs = S.c2f_skip, fc = S.fuse_closing, uc = S.use_chain, rf = S.rbseq_fuse, rw = S.rbseq_window, cdo = S.coarsest_direct, rfm = S.rbseq_fuse_min, ovl = S.overlap, kp = S.use_ksp, fz = S.use_fuse, ao = S.async_ops, cp = S.cycle_precision;
   mgx_exchange_fn ex = S.ex; mgx_allreduce_fn ar = S.ar; mgx_allgather_fn ag = S.ag; void *ctx = S.ctx; const bool nat = S.native_rccl;
   // the timer table is module state of mg_tictoc in the reference: it outlives nhydro_clean (the drivers print it afterwards, mg_testseamount.f90:220-221)
   std::vector<std::string> tn = S.tt_names; std::vector<HostTic> th = S.tt_host; const int tnb = S.tt_nblev;
@@ -1472,7 +1637,7 @@ void mgx_clean(void) {
   S = State();
   S.tt_names = tn; S.tt_host = th; S.tt_nblev = tnb; memcpy(S.tt_time, tsave, sizeof tsave); memcpy(S.tt_calls, csave, sizeof csave);
   S.native_rccl = nat;
-  S.stream = st; S.verbose = vb; S.warm_start = ws; S.tictoc = tc; S.exact_halos = eh; S.rb_exact = rx; S.rb_seq = rq; S.keep_r = kr; S.c2f_skip = cs; S.fuse_closing = fc; S.use_chain = uc; S.rbseq_fuse = rf; S.rbseq_window = rw; S.coarsest_direct = cdo; S.rbseq_fuse_min = rfm; S.overlap = ovl; S.use_ksp = kp; S.use_fuse = fz; S.async_ops = ao; S.ex = ex; S.ar = ar; S.ag = ag; S.ctx = ctx;
+  S.stream = st; S.verbose = vb; S.warm_start = ws; S.tictoc = tc; S.exact_halos = eh; S.rb_exact = rx; S.rb_seq = rq; S.keep_r = kr; S.c2f_skip = cs; S.fuse_closing = fc; S.use_chain = uc; S.rbseq_fuse = rf; S.rbseq_window = rw; S.coarsest_direct = cdo; S.rbseq_fuse_min = rfm; S.overlap = ovl; S.use_ksp = kp; S.use_fuse = fz; S.async_ops = ao; S.cycle_precision = cp; S.ex = ex; S.ar = ar; S.ag = ag; S.ctx = ctx;
 }
 
 int mgx_init(int nx, int ny, int nz, int npx, int npy, int rank, const mgx_params *par) {
@@ -1662,7 +1827,7 @@ int mgx_solve(double *u, double *v, double *w, const double *rmask) {
   CHK(set_call_mask(rmask, false));
   CHK(upload_uvw(u, v, w));
   CHK(compute_rhs_dev());
-  CHK(solve_p(S.par.solver_prec, S.par.solver_maxiter, nullptr, nullptr, nullptr));
+  CHK(solve_p_opt(S.par.solver_prec, S.par.solver_maxiter, nullptr, nullptr, nullptr));
   Level &L = S.lev[0];
   CHK(correct_uvw_dev());
   const size_t nu = (size_t)(L.nx + 1) * (L.ny + 2) * L.nz, nv = (size_t)(L.nx + 2) * (L.ny + 1) * L.nz, nw = (size_t)(L.nx + 2) * (L.ny + 2) * (L.nz + 1);
@@ -1682,7 +1847,7 @@ int mgx_solve_device(double *u_dev, double *v_dev, double *w_dev, const double *
   double *su = S.d_u, *sv = S.d_v, *sw = S.d_w;
   S.d_u = u_dev; S.d_v = v_dev; S.d_w = w_dev;
   int rc = compute_rhs_dev();
-  if (!rc) rc = solve_p(S.par.solver_prec, S.par.solver_maxiter, nullptr, nullptr, nullptr);
+  if (!rc) rc = solve_p_opt(S.par.solver_prec, S.par.solver_maxiter, nullptr, nullptr, nullptr);
   if (!rc) rc = correct_uvw_dev();
   if (!rc) rc = sync_stream();
   S.d_u = su; S.d_v = sv; S.d_w = sw;
@@ -1697,7 +1862,7 @@ int mgx_check_nondivergence(double *u, double *v, double *w, const double *rmask
 int mgx_solve_p(double tol, int maxite, int *nite, double *res, double *hist) {
   NEED_INIT();
   if (!S.have_matrix) return fail("no matrix: call mgx_matrices (or mgx_set_field(lev, MGX_CA, ...)) first");
-  return solve_p(tol, maxite, nite, res, hist);
+  return solve_p_opt(tol, maxite, nite, res, hist);
 }
 int mgx_fcycle(void) { NEED_INIT(); CHK(fcycle()); CHK(op_sync()); return 0; }
 int mgx_vcycle(int lev) { NEED_LEV(lev); CHK(vcycle(lev)); CHK(op_sync()); return 0; }
@@ -1793,6 +1958,10 @@ int mgx_set_option(const char *name, int value) {
   else if (streq(name, "ksp")) { S.use_ksp = value; if (value) S.ksp_down = 0; }  // switching it on again also clears a time-out of this solver
   else if (streq(name, "async")) S.async_ops = value;
   else if (streq(name, "fuse_tail")) S.use_fuse = value;
+  else if (streq(name, "cycle_precision")) {
+    if (value != 32 && value != 64) return fail("cycle_precision must be 64 (fp64 cycles) or 32 (fp32 cycles under fp64 refinement), got %d", value);
+    S.cycle_precision = value;
+  }
   else if (streq(name, "ksp_test_stall")) S.ksp_test_stall = value;
   else if (streq(name, "rbseq_test_stall")) S.rbseq_test_stall = value;
   else if (streq(name, "rbseq_fuse_min")) S.rbseq_fuse_min = value;
@@ -1847,6 +2016,8 @@ int mgx_get_option(const char *name, int *value) {
   else if (streq(name, "ksp")) *value = (S.use_ksp && !S.ksp_down) ? 1 : 0;
   else if (streq(name, "async")) *value = S.async_ops;
   else if (streq(name, "fuse_tail")) *value = S.use_fuse;
+  else if (streq(name, "cycle_precision")) *value = S.cycle_precision;
+  else if (streq(name, "mixed_iterations")) *value = (int)S.n_mixed;
   else if (streq(name, "p2p_failed")) *value = S.p2p_failed;
   else if (streq(name, "p2p")) *value = S.p2p_on ? 1 : 0;
   else return fail("unknown option '%s'", name);
@@ -1977,6 +2148,7 @@ int mgx_set_field(int lev, int field, const double *host) {
     L.v.zy = L.v.zx = nullptr;  // a user-supplied matrix is used as stored
     L.v.m4 = nullptr;
     S.cd_valid = 0;
+    S.coef_gen++;
     S.have_matrix = true;
   } else if (!field_ptr(L, field, &a, &n)) {
     HIPCHK(hipMemcpyAsync(a, host, n * sizeof(double), hipMemcpyHostToDevice, S.stream));
@@ -2016,6 +2188,48 @@ int mgx_selftest_divc(const double *a, const double *b, int n, long long *nbad) 
 }
 int mgx_time_relax(int lev, int reps, float *ms) { return time_op(lev, reps, ms, 0); }
 int mgx_time_residual(int lev, int reps, float *ms) { return time_op(lev, reps, ms, 1); }
+// test hook of the fp32 cycle: one fp32 operator on the shadow of level lev, inputs converted from the level's fp64 fields, results
+// converted back into them -- so each fp32 kernel can be checked against the fp64 operator of the same name on the same input
+int mgx_mixed_op(const char *op, int lev, int n) {
+  NEED_LEV(lev);
+  if (!S.have_matrix) return fail("mgx_mixed_op: no matrix: call mgx_matrices first");
+  if (!op) return fail("mgx_mixed_op: op is NULL");
+  CHK(mixed_check());
+  CHK(mixed_prepare());
+  Level &L = S.lev[lev - 1];
+  const bool two = streq(op, "fine2coarse") || streq(op, "coarse2fine") || streq(op, "resrest");
+  if (two && lev >= S.nlevs) return fail("mgx_mixed_op(%s, %d): no coarser level", op, lev);
+  if (streq(op, "relax")) {
+    if (n < 0) return fail("mgx_mixed_op(relax): n = %d sweeps", n);
+    mgxx_to32(S.stream, &L.v, &L.v32, L.v.p, L.v32.e, 1.0); mgxx_to32(S.stream, &L.v, &L.v32, L.v.b, L.v32.f, 1.0);
+    relax32(lev, n);
+    mgxx_to64(S.stream, &L.v, &L.v32, L.v32.e, L.v.p, 1.0, 0);
+  } else if (streq(op, "residual")) {
+    mgxx_to32(S.stream, &L.v, &L.v32, L.v.p, L.v32.e, 1.0); mgxx_to32(S.stream, &L.v, &L.v32, L.v.b, L.v32.f, 1.0);
+    mgxx_residual(S.stream, &L.v32, S.real);
+    mgxx_to64(S.stream, &L.v, &L.v32, L.v32.r, L.v.r, 1.0, 0);
+    L.r_halo_stale = false;   // the kernel stored the physical images, and a single rank has no others
+  } else if (streq(op, "fine2coarse") || streq(op, "resrest")) {
+    Level &C = S.lev[lev];
+    if (streq(op, "fine2coarse")) {   // grid(lev+1)%b = restriction of grid(lev)%r, grid(lev+1)%p = 0
+      mgxx_to32(S.stream, &L.v, &L.v32, L.v.r, L.v32.r, 1.0);
+      mgxx_restrict(S.stream, &L.v32, &C.v32, L.v32.r);
+    } else {                          // the down leg of a V-cycle: restriction of b - A p of level lev
+      mgxx_to32(S.stream, &L.v, &L.v32, L.v.p, L.v32.e, 1.0); mgxx_to32(S.stream, &L.v, &L.v32, L.v.b, L.v32.f, 1.0);
+      mgxx_resrest(S.stream, &L.v32, &C.v32, S.real);
+    }
+    mgxx_to64(S.stream, &C.v, &C.v32, C.v32.f, C.v.b, 1.0, 0);
+    mgxx_to64(S.stream, &C.v, &C.v32, C.v32.e, C.v.p, 1.0, 0);
+    C.b_halo_stale = false;
+  } else if (streq(op, "coarse2fine")) {   // grid(lev)%p += interpolation of grid(lev+1)%p
+    Level &C = S.lev[lev];
+    mgxx_to32(S.stream, &C.v, &C.v32, C.v.p, C.v32.e, 1.0); mgxx_to32(S.stream, &L.v, &L.v32, L.v.p, L.v32.e, 1.0);
+    coarse2fine32(lev);
+    mgxx_to64(S.stream, &L.v, &L.v32, L.v32.e, L.v.p, 1.0, 0);
+  } else return fail("mgx_mixed_op: unknown operator '%s' (relax, residual, fine2coarse, coarse2fine, resrest)", op);
+  return sync_stream();
+}
+
 int mgx_counters(long long *out) { out[0] = S.n_launch; out[1] = S.n_halo; out[2] = S.n_exch; out[3] = S.n_allred; return 0; }
 long long mgx_p2p_exchanges(void) { return S.n_p2p; }
 

@@ -67,3 +67,18 @@ __host__ __device__ inline bool sides_part_skip(const Sides &ph, int i, int nx, 
   const bool edge = (!ph.W && i == 1) || (!ph.E && i == nx) || (!ph.S && jodd && bx == 0) || (!ph.N && !jodd && bx == gx - 1);
   return edge != (ph.part == 1);
 }
+
+// fp32 shadow of one level for the mixed-precision solve_p (option "cycle_precision" = 32, mgx_mixed.hip): the same JS layout as
+// LevView with 4-byte elements, EO / HO chosen so that the first interior column of either half is 128-byte aligned for floats.
+// e is the correction (the cycle's p), f its right-hand side (the cycle's b); cA, bet are the fp64 slots and pivots rounded to fp32.
+struct LevView32 {
+  int nx, ny, nz;
+  int RS, EO, HO;
+  long long plane;  // nz * RS
+  float *e, *f, *r;
+  float *cA[8];
+  float *bet;
+  float *p1;        // red-black: snapshot of e(k=1,:,:) taken before a colour, (nx+2) rows of RS
+};
+
+__host__ __device__ inline int jpos32(const LevView32 &L, int j) { return (j & 1) ? L.HO + (j >> 1) : L.EO + (j >> 1); }

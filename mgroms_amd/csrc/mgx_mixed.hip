@@ -1,0 +1,342 @@
+// fp32 kernels of the mixed-precision solve_p (option "cycle_precision" = 32, include/mgx.h).  The fp64 outer loop of
+// mgx_api.cpp (solve_p_mixed) keeps the iterate, the residual, its norm and the stopping test; each iteration runs the
+// reference's F-cycle in correction form, A e = s r with e = 0 on entry, on fp32 shadows of every level (LevView32,
+// mgx_internal.h), and adds e / s to p.  Hand-written, fp32, single rank (every side of every level physical).
+//
+// These kernels have no bit-parity duty: they are compiled with -ffp-contract=fast (Makefile) and sum in whatever order is
+// convenient.  They keep the operator of the fp64 kernels term for term (mgx_kernels.hip k_residual, mgx_relax.hip
+// relax_col_any), so each one can be checked against its fp64 counterpart through mgx_mixed_op.
+//
+// Thread mapping as in the fp64 kernels: one lane = one (j,i) column, lanes along the unit-stride half-row of the JS layout.
+#include "mgx_device.h"
+
+// physical-boundary images of an interior value (homogeneous Neumann mirror incl. corners, as mirror_store; all four sides)
+__device__ __forceinline__ void mirror32(const LevView32 &L, float *__restrict__ a, const long long ro, const int j, const int i, const int c, const float v) {
+  const bool mS = j == 1, mN = j == L.ny, mW = i == 1, mE = i == L.nx;
+  if (!(mS | mN | mW | mE)) return;
+  const int cS = L.EO, cN = jpos32(L, L.ny + 1);
+  const long long o = (long long)i * L.plane + ro, oW = ro, oE = (long long)(L.nx + 1) * L.plane + ro;
+  if (mS) a[o + cS] = v;
+  if (mN) a[o + cN] = v;
+  if (mW) { a[oW + c] = v; if (mS) a[oW + cS] = v; if (mN) a[oW + cN] = v; }
+  if (mE) { a[oE + c] = v; if (mS) a[oE + cS] = v; if (mN) a[oE + cN] = v; }
+}
+
+// positions of column j (= 2 jh + 1 odd, 2 jh + 2 even) and of its j-1, j+1 neighbours inside a row
+__device__ __forceinline__ void col_pos(const LevView32 &L, const int jh, const int jodd, int &c, int &jm, int &jp) {
+  if (jodd) { c = L.HO + jh; jm = L.EO + jh; }
+  else      { c = L.EO + jh + 1; jm = L.HO + jh; }
+  jp = jm + 1;
+}
+
+// Sum of the off-column couplings of row k of column (c, plane offset o), i.e. (A e)(k) without the own-column terms a1, a2
+// (mg_relax.f90:262-301, the same terms as k_residual / relax_col_any).  SNAP: the k = 1 diagonal neighbours (same colour in
+// red-black) come from the snapshot p1 taken before the colour; s = the column's snapshot row offset i * RS.
+template <bool REAL, bool SNAP>
+__device__ __forceinline__ float off32(const LevView32 &L, const float *__restrict__ e, const long long o, const long long s, const int c,
+                                       const int jm, const int jp, const int k) {
+  const long long RS = L.RS, om = o - L.plane, op = o + L.plane;
+  const long long r0 = (long long)(k - 1) * RS, rm = r0 - RS, rp = r0 + RS;
+  const float *__restrict__ a3 = L.cA[2], *__restrict__ a4 = L.cA[3], *__restrict__ a5 = L.cA[4],
+              *__restrict__ a6 = L.cA[5], *__restrict__ a7 = L.cA[6], *__restrict__ a8 = L.cA[7];
+  float t = a4[o + r0 + c] * e[o + r0 + jm] + a4[o + r0 + jp] * e[o + r0 + jp] + a7[o + r0 + c] * e[om + r0 + c] + a7[op + r0 + c] * e[op + r0 + c];
+  if (k > 1)
+    t += a3[o + rm + jp] * e[o + rm + jp] + a5[o + r0 + c] * e[o + rm + jm] + a6[op + rm + c] * e[op + rm + c] + a8[o + r0 + c] * e[om + rm + c];
+  if (k < L.nz)
+    t += a3[o + r0 + c] * e[o + rp + jm] + a5[o + rp + jp] * e[o + rp + jp] + a6[o + r0 + c] * e[om + rp + c] + a8[op + rp + c] * e[op + rp + c];
+  if (REAL && k == 1) {
+    const float *__restrict__ q1 = SNAP ? L.p1 : e;
+    const long long sm = SNAP ? s - RS : om, sp = SNAP ? s + RS : op;
+    t += a5[o + c] * q1[sm + jp] + a5[op + jm] * q1[sp + jm] + a8[o + c] * q1[sm + jm] + a8[op + jp] * q1[sp + jp];
+  }
+  return t;
+}
+
+// residual f - A e of row k
+template <bool REAL>
+__device__ __forceinline__ float res32(const LevView32 &L, const long long o, const int c, const int jm, const int jp, const int k) {
+  const long long RS = L.RS, r0 = (long long)(k - 1) * RS;
+  const float *__restrict__ e = L.e, *__restrict__ a1 = L.cA[0], *__restrict__ a2 = L.cA[1];
+  float t = a1[o + r0 + c] * e[o + r0 + c] + off32<REAL, false>(L, e, o, 0, c, jm, jp, k);
+  if (k > 1) t += a2[o + r0 + c] * e[o + r0 - RS + c];
+  if (k < L.nz) t += a2[o + r0 + RS + c] * e[o + r0 + RS + c];
+  return L.f[o + r0 + c] - t;
+}
+
+// ------------------------------------------------------------------------------------------------
+// z-line smoother, one colour pass (mg_relax.f90:237-334): rhs = f - off-column couplings, then the column's tridiagonal solve
+// with the stored pivots bet (gam(k) = a2(k) * bet(k-1), mg_relax.f90:325, formed on the fly).  NZ > 0: the rows of the solve
+// live in registers and e is written once; NZ = 0: any nz >= 2, the forward sweep goes through e.  Either way the lane stores the
+// physical-boundary images of its column (no halo launch behind the pass).
+// ------------------------------------------------------------------------------------------------
+template <int NZ, bool REAL, bool SNAP>
+__device__ __forceinline__ void relax32_col(const LevView32 &L, const int i, const int jh, const int jodd) {
+  int c, jm, jp;
+  col_pos(L, jh, jodd, c, jm, jp);
+  const long long RS = L.RS, o = (long long)i * L.plane, s = (long long)i * RS;
+  const int nz = NZ > 0 ? NZ : L.nz;
+  float *__restrict__ e = L.e;
+  const float *__restrict__ f = L.f, *__restrict__ a2 = L.cA[1], *__restrict__ bet = L.bet;
+  const int j = jodd ? 2 * jh + 1 : 2 * jh + 2;
+  if (NZ > 0) {
+    float x[NZ > 0 ? NZ : 1], g[NZ > 0 ? NZ : 1];
+    float xv = 0.f, betp = 0.f;
+#pragma unroll
+    for (int k = 1; k <= NZ; k++) {
+      const long long ko = o + (long long)(k - 1) * RS + c;
+      const float rhs = f[ko] - off32<REAL, SNAP>(L, e, o, s, c, jm, jp, k);
+      const float bk = bet[ko];
+      if (k == 1) xv = rhs * bk;
+      else { const float a = a2[ko]; g[k - 1] = a * betp; xv = (rhs - a * xv) * bk; }
+      betp = bk;
+      x[k - 1] = xv;
+    }
+#pragma unroll
+    for (int k = NZ - 1; k >= 1; k--) x[k - 1] = x[k - 1] - g[k] * x[k];
+#pragma unroll
+    for (int k = 1; k <= NZ; k++) {
+      const long long ro = (long long)(k - 1) * RS;
+      e[o + ro + c] = x[k - 1];
+      mirror32(L, e, ro, j, i, c, x[k - 1]);
+    }
+  } else {
+    float xv = 0.f;
+    for (int k = 1; k <= nz; k++) {
+      const long long ko = o + (long long)(k - 1) * RS + c;
+      const float rhs = f[ko] - off32<REAL, SNAP>(L, e, o, s, c, jm, jp, k);
+      xv = k == 1 ? rhs * bet[ko] : (rhs - a2[ko] * xv) * bet[ko];
+      e[ko] = xv;
+    }
+    mirror32(L, e, (long long)(nz - 1) * RS, j, i, c, xv);
+    for (int k = nz - 1; k >= 1; k--) {
+      const long long ro = (long long)(k - 1) * RS, ko = o + ro + c;
+      xv = e[ko] - a2[ko + RS] * bet[ko] * xv;
+      e[ko] = xv;
+      mirror32(L, e, ro, j, i, c, xv);
+    }
+  }
+}
+
+template <int NZ, bool REAL, bool SNAP>
+__global__ __launch_bounds__(256) void k_relax32(LevView32 L, int i0, int istep, int nplanes, int jodd_fixed, int rb) {
+  const int jh = blockIdx.x * WAVE + threadIdx.x;
+  const int ipl = blockIdx.y * blockDim.y + threadIdx.y;
+  if (jh >= (L.ny >> 1) || ipl >= nplanes) return;
+  const int i = i0 + istep * ipl;
+  // RB: j = 1+mod(i+rb,2),ny,2 (mg_relax.f90:174) ; FC: fixed parity (:216-217)
+  const int jodd = jodd_fixed >= 0 ? jodd_fixed : (((i + rb) & 1) == 0);
+  relax32_col<NZ, REAL, SNAP>(L, i, jh, jodd);
+}
+
+// snapshot of e(k=1,:,:), halo included, for the red-black pass
+__global__ void k_snapshot32(LevView32 L) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int i = blockIdx.y;
+  if (t < L.RS) L.p1[(long long)i * L.RS + t] = L.e[(long long)i * L.plane + t];
+}
+
+// r = f - A e with the physical images of r (mgx_mixed_op "residual"; the cycle never writes r).  blockIdx.z = j parity.
+template <bool REAL>
+__global__ __launch_bounds__(256) void k_residual32(LevView32 L) {
+  const int jh = blockIdx.x * WAVE + threadIdx.x;
+  const int i = 1 + blockIdx.y * blockDim.y + threadIdx.y;
+  if (jh >= (L.ny >> 1) || i > L.nx) return;
+  const int jodd = blockIdx.z == 0;
+  int c, jm, jp;
+  col_pos(L, jh, jodd, c, jm, jp);
+  const int j = jodd ? 2 * jh + 1 : 2 * jh + 2;
+  const long long o = (long long)i * L.plane;
+  for (int k = 1; k <= L.nz; k++) {
+    const long long ro = (long long)(k - 1) * L.RS;
+    const float v = res32<REAL>(L, o, c, jm, jp, k);
+    L.r[o + ro + c] = v;
+    mirror32(L, L.r, ro, j, i, c, v);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Down leg of a V-cycle: compute_residual(lev) + fine2coarse(lev) in one pass, f_c = sum of the 8 fine residuals
+// (mg_intergrids.f90:139-162), e_c = 0; no r written, no norm.  One lane = one coarse column = 2 x 2 fine columns.
+// ------------------------------------------------------------------------------------------------
+template <bool REAL>
+__global__ __launch_bounds__(256) void k_resrest32(LevView32 F, LevView32 C) {
+  const int j2 = 1 + blockIdx.x * WAVE + threadIdx.x;
+  const int i2 = 1 + blockIdx.y * blockDim.y + threadIdx.y;
+  if (j2 > C.ny || i2 > C.nx) return;
+  const int i = 2 * i2 - 1, jh = j2 - 1;
+  int co, jmo, jpo, ce, jme, jpe;
+  col_pos(F, jh, 1, co, jmo, jpo);   // fine j = 2 j2 - 1
+  col_pos(F, jh, 0, ce, jme, jpe);   // fine j = 2 j2
+  const long long o0 = (long long)i * F.plane, o1 = o0 + F.plane;
+  const int cc = jpos32(C, j2);
+  const long long oc = (long long)i2 * C.plane + cc;
+  for (int k2 = 1; k2 <= C.nz; k2++) {
+    float z = 0.f;
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const int k = 2 * k2 - 1 + h;
+      z += res32<REAL>(F, o0, co, jmo, jpo, k) + res32<REAL>(F, o1, co, jmo, jpo, k) + res32<REAL>(F, o0, ce, jme, jpe, k) + res32<REAL>(F, o1, ce, jme, jpe, k);
+    }
+    const long long ro = (long long)(k2 - 1) * C.RS;
+    C.f[oc + ro] = z; mirror32(C, C.f, ro, j2, i2, cc, z);
+    C.e[oc + ro] = 0.f; mirror32(C, C.e, ro, j2, i2, cc, 0.f);
+  }
+}
+
+// First leg of the F-cycle (mg_solvers.f90:110-115): f_c = sum of the 8 fine values of `src` (the fine f, which is the fine residual
+// there because the fine e is 0), e_c = 0.  mg_intergrids.f90:139-162.
+__global__ __launch_bounds__(256) void k_restrict32(LevView32 F, LevView32 C, const float *__restrict__ x) {
+  const int j2 = 1 + blockIdx.x * WAVE + threadIdx.x;
+  const int i2 = 1 + blockIdx.y * blockDim.y + threadIdx.y;
+  if (j2 > C.ny || i2 > C.nx) return;
+  const int i = 2 * i2 - 1;
+  const int po = F.HO + (j2 - 1), pe = F.EO + j2;  // fine j = 2*j2-1 (odd) and 2*j2 (even)
+  const long long o0 = (long long)i * F.plane, o1 = o0 + F.plane;
+  const int cc = jpos32(C, j2);
+  const long long oc = (long long)i2 * C.plane + cc;
+  for (int k2 = 1; k2 <= C.nz; k2++) {
+    const long long r0 = (long long)(2 * k2 - 2) * F.RS, r1 = r0 + F.RS;
+    const float z = x[o0 + r0 + po] + x[o1 + r0 + po] + x[o0 + r0 + pe] + x[o1 + r0 + pe] + x[o0 + r1 + po] + x[o1 + r1 + po] + x[o0 + r1 + pe] + x[o1 + r1 + pe];
+    const long long ro = (long long)(k2 - 1) * C.RS;
+    C.f[oc + ro] = z; mirror32(C, C.f, ro, j2, i2, cc, z);
+    C.e[oc + ro] = 0.f; mirror32(C, C.e, ro, j2, i2, cc, 0.f);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// coarse2fine: fine e += interp(coarse e), mg_intergrids.f90:366-450 (tri-linear, top level x 1/2), :336-363 (nearest), :226.
+// The expressions of k_coarse2fine (mgx_kernels.hip); the interpolated correction is not stored in r.
+// ------------------------------------------------------------------------------------------------
+template <bool LINEAR>
+__global__ __launch_bounds__(256) void k_coarse2fine32(LevView32 F, LevView32 C) {
+  const int j2 = 1 + blockIdx.x * WAVE + threadIdx.x;
+  const int k2 = 1 + blockIdx.y * blockDim.y + threadIdx.y;
+  const int i2 = 1 + blockIdx.z;
+  if (j2 > C.ny || k2 > C.nz) return;
+  const int i = 2 * i2 - 1;
+  const int po = F.HO + (j2 - 1), pe = F.EO + j2;
+  const int c0 = jpos32(C, j2), cm = jpos32(C, j2 - 1), cp = jpos32(C, j2 + 1);
+  const long long q0 = (long long)i2 * C.plane, qm = q0 - C.plane, qp = q0 + C.plane;
+  const long long o0 = (long long)i * F.plane, o1 = o0 + F.plane;
+  const float *__restrict__ xc = C.e;
+  float *__restrict__ pf = F.e;
+  const int nz = C.nz;
+#define XC(kk, JJ, QQ) xc[QQ + (long long)((kk)-1) * C.RS + JJ]
+#define PUT(k, OO, PP, val) { const long long ro_ = (long long)((k)-1) * F.RS, t_ = OO + ro_ + PP; const float w_ = pf[t_] + (val); pf[t_] = w_; \
+    mirror32(F, pf, ro_, (PP == po) ? 2 * j2 - 1 : 2 * j2, (OO == o0) ? i : i + 1, PP, w_); }
+  if (!LINEAR) {
+    const float v = XC(k2, c0, q0);
+    const int k = 2 * k2 - 1;
+    PUT(k, o0, po, v); PUT(k + 1, o0, po, v); PUT(k, o0, pe, v); PUT(k + 1, o0, pe, v);
+    PUT(k, o1, po, v); PUT(k + 1, o1, po, v); PUT(k, o1, pe, v); PUT(k + 1, o1, pe, v);
+    return;
+  }
+  const float a = 9.f / 16.f, b = 3.f / 16.f, c = 1.f / 16.f, d = 27.f / 64.f, e = 9.f / 64.f, f = 3.f / 64.f, g = 1.f / 64.f;
+  const float x00 = XC(k2, c0, q0), xmm = XC(k2, cm, qm), xm0 = XC(k2, cm, q0), x0m = XC(k2, c0, qm),
+              xpm = XC(k2, cp, qm), xp0 = XC(k2, cp, q0), xmp = XC(k2, cm, qp), x0p = XC(k2, c0, qp), xpp = XC(k2, cp, qp);
+#pragma unroll
+  for (int half = 0; half < 2; half++) {
+    const int k = 2 * k2 - 1 + half;
+    if (k == 1) {
+      PUT(1, o0, po, a * x00 + c * xmm + b * xm0 + b * x0m);
+      PUT(1, o0, pe, a * x00 + c * xpm + b * xp0 + b * x0m);
+      PUT(1, o1, po, a * x00 + c * xmp + b * xm0 + b * x0p);
+      PUT(1, o1, pe, a * x00 + c * xpp + b * xp0 + b * x0p);
+    } else if (k == 2 * nz) {
+      PUT(k, o0, po, 0.5f * (a * x00 + c * xmm + b * xm0 + b * x0m));
+      PUT(k, o0, pe, 0.5f * (a * x00 + c * xpm + b * xp0 + b * x0m));
+      PUT(k, o1, po, 0.5f * (a * x00 + c * xmp + b * xm0 + b * x0p));
+      PUT(k, o1, pe, 0.5f * (a * x00 + c * xpp + b * xp0 + b * x0p));
+    } else {
+      const int kp = k2 - ((k % 2) * 2 - 1);
+      const float y00 = XC(kp, c0, q0), ymm = XC(kp, cm, qm), ym0 = XC(kp, cm, q0), y0m = XC(kp, c0, qm),
+                  ypm = XC(kp, cp, qm), yp0 = XC(kp, cp, q0), ymp = XC(kp, cm, qp), y0p = XC(kp, c0, qp), ypp = XC(kp, cp, qp);
+      PUT(k, o0, po, d * x00 + f * xmm + e * xm0 + e * x0m + e * y00 + g * ymm + f * ym0 + f * y0m);
+      PUT(k, o0, pe, d * x00 + f * xpm + e * xp0 + e * x0m + e * y00 + g * ypm + f * yp0 + f * y0m);
+      PUT(k, o1, po, d * x00 + f * xmp + e * xm0 + e * x0p + e * y00 + g * ymp + f * ym0 + f * y0p);
+      PUT(k, o1, pe, d * x00 + f * xpp + e * xp0 + e * x0p + e * y00 + g * ypp + f * yp0 + f * y0p);
+    }
+  }
+#undef XC
+#undef PUT
+}
+
+// ------------------------------------------------------------------------------------------------
+// fp64 <-> fp32 over a whole JS array, halo included (the two layouts differ in EO / HO / RS).  One lane = one half-row position
+// h = 0..ny/2 of parity blockIdx.z (j = 2h+1 odd, 2h even) in plane i, walking up k.
+//   to32: dst = (float)(scale * src)                    (coefficients, pivots, the demoted residual, mgx_mixed_op inputs)
+//   to64: dst = (add ? dst : 0) + (double)src * scale    (p += e / s after the cycle, mgx_mixed_op results)
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_to32(LevView D, LevView32 S, const double *__restrict__ src, float *__restrict__ dst, double scale) {
+  const int h = blockIdx.x * WAVE + threadIdx.x;
+  const int i = blockIdx.y * blockDim.y + threadIdx.y;
+  if (h > (D.ny >> 1) || i > D.nx + 1) return;
+  const int j = blockIdx.z ? 2 * h : 2 * h + 1;
+  const long long od = (long long)i * D.plane + jpos(D, j), os = (long long)i * S.plane + jpos32(S, j);
+  for (int k = 0; k < D.nz; k++) dst[os + (long long)k * S.RS] = (float)(scale * src[od + (long long)k * D.RS]);
+}
+__global__ __launch_bounds__(256) void k_to64(LevView D, LevView32 S, const float *__restrict__ src, double *__restrict__ dst, double scale, int add) {
+  const int h = blockIdx.x * WAVE + threadIdx.x;
+  const int i = blockIdx.y * blockDim.y + threadIdx.y;
+  if (h > (D.ny >> 1) || i > D.nx + 1) return;
+  const int j = blockIdx.z ? 2 * h : 2 * h + 1;
+  const long long od = (long long)i * D.plane + jpos(D, j), os = (long long)i * S.plane + jpos32(S, j);
+  for (int k = 0; k < D.nz; k++) {
+    const double v = (double)src[os + (long long)k * S.RS] * scale;
+    dst[od + (long long)k * D.RS] = add ? dst[od + (long long)k * D.RS] + v : v;
+  }
+}
+
+template <int NZ>
+static void launch_relax32(hipStream_t st, const LevView32 *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap) {
+  const dim3 blk(WAVE, 4), grd = col_grid(L->ny / 2, nplanes);
+  if (real && snap) hipLaunchKernelGGL((k_relax32<NZ, true, true>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb);
+  else if (real) hipLaunchKernelGGL((k_relax32<NZ, true, false>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb);
+  else hipLaunchKernelGGL((k_relax32<NZ, false, false>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb);
+}
+
+static dim3 whole_grid(int ny, int nx) { return dim3((ny / 2 + 1 + WAVE - 1) / WAVE, (nx + 2 + 3) / 4, 2); }
+
+extern "C" {
+// one colour pass: planes i0, i0+istep, ... (nplanes of them), j parity jodd_fixed (-1: red-black colour rb); snap: read the k=1
+// diagonals from L->p1
+void mgxx_relax_pass(hipStream_t st, const LevView32 *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap) {
+  switch (L->nz) {
+    case 2: launch_relax32<2>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap); return;
+    case 4: launch_relax32<4>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap); return;
+    case 8: launch_relax32<8>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap); return;
+    case 16: launch_relax32<16>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap); return;
+    case 32: launch_relax32<32>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap); return;
+    case 64: launch_relax32<64>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap); return;
+    default: launch_relax32<0>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap); return;
+  }
+}
+void mgxx_snapshot(hipStream_t st, const LevView32 *L) {
+  hipLaunchKernelGGL(k_snapshot32, dim3((L->RS + 255) / 256, L->nx + 2), dim3(256), 0, st, *L);
+}
+void mgxx_residual(hipStream_t st, const LevView32 *L, int real) {
+  const dim3 grd = col_grid(L->ny / 2, L->nx, 2), blk(WAVE, 4);
+  if (real) hipLaunchKernelGGL(k_residual32<true>, grd, blk, 0, st, *L);
+  else hipLaunchKernelGGL(k_residual32<false>, grd, blk, 0, st, *L);
+}
+void mgxx_resrest(hipStream_t st, const LevView32 *F, const LevView32 *C, int real) {
+  const dim3 grd = col_grid(C->ny, C->nx), blk(WAVE, 4);
+  if (real) hipLaunchKernelGGL(k_resrest32<true>, grd, blk, 0, st, *F, *C);
+  else hipLaunchKernelGGL(k_resrest32<false>, grd, blk, 0, st, *F, *C);
+}
+void mgxx_restrict(hipStream_t st, const LevView32 *F, const LevView32 *C, const float *src) {
+  hipLaunchKernelGGL(k_restrict32, col_grid(C->ny, C->nx), dim3(WAVE, 4), 0, st, *F, *C, src);
+}
+void mgxx_coarse2fine(hipStream_t st, const LevView32 *F, const LevView32 *C, int linear) {
+  const int by = C->nz >= 4 ? 4 : C->nz;
+  const dim3 blk(WAVE, by), grd((C->ny + WAVE - 1) / WAVE, (C->nz + by - 1) / by, C->nx);
+  if (linear) hipLaunchKernelGGL(k_coarse2fine32<true>, grd, blk, 0, st, *F, *C);
+  else hipLaunchKernelGGL(k_coarse2fine32<false>, grd, blk, 0, st, *F, *C);
+}
+void mgxx_to32(hipStream_t st, const LevView *D, const LevView32 *S, const double *src, float *dst, double scale) {
+  hipLaunchKernelGGL(k_to32, whole_grid(D->ny, D->nx), dim3(WAVE, 4), 0, st, *D, *S, src, dst, scale);
+}
+void mgxx_to64(hipStream_t st, const LevView *D, const LevView32 *S, const float *src, double *dst, double scale, int add) {
+  hipLaunchKernelGGL(k_to64, whole_grid(D->ny, D->nx), dim3(WAVE, 4), 0, st, *D, *S, src, dst, scale, add);
+}
+}  // extern "C"

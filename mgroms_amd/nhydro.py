@@ -208,6 +208,12 @@ def nlevs():
     return lib().mgx_nlevs()
 
 
+def mixed_op(op, lev, n=1):
+    """one fp32 operator of the mixed-precision cycle (option "cycle_precision" = 32) on level lev's fp64 fields, converted in and
+    back: "relax" (n sweeps), "residual", "fine2coarse", "coarse2fine", "resrest" (include/mgx.h: mgx_mixed_op)."""
+    check(lib().mgx_mixed_op(op.encode(), int(lev), int(n)))
+
+
 def rbseq_window_info(lev):
     """(rho, planes): the contraction bound of the level's red-black walk and the planes of warm-up of the windowed walk
     (option "rbseq_window", include/mgx.h); planes = 0: the walk over the whole level stays."""
