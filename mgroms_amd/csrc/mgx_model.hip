@@ -290,13 +290,15 @@ void mgxm_js_model(hipStream_t st, const LevView *L, double *js, double *md, int
 // Rows per block in z.  The divergence pass: eight.  The flux kernels and correct_uvw carry values from row to row (a run re-reads one
 // row of its neighbour run): runs as long as possible while there are >= 16 384 waves to hide the load -> use chain of a row
 // (scripts/probe/ab_model_runs.sh at 512x512x64: runs of 16 rows 0.86 ms for the four kernels, 32 rows 0.91, whole columns 0.91).
+// MGX_MODEL_KR (A/B and test hook) asks for runs of that many rows, and gets them: the eight-row floor is the heuristic's, so that
+// runs of 1..7 rows -- every row, or nearly, a run start that reloads the carried values -- can be forced too.
 static inline dim3 igrid_k(int ni, int nj, int klast, int *KR) { *KR = klast >= 16 ? 8 : klast; return dim3((ni + 63) / 64, (nj + 3) / 4, (klast + *KR - 1) / *KR); }
 static inline dim3 igrid_run(int ni, int nj, int klast, int *KR) {
   static const int krenv = getenv("MGX_MODEL_KR") ? atoi(getenv("MGX_MODEL_KR")) : 0;
   const long long waves = (long long)((ni + 63) / 64) * nj;
   long long nrun = krenv > 0 ? (klast + krenv - 1) / krenv : (16384 + waves - 1) / waves;
   if (nrun < 1) nrun = 1;
-  if (nrun > (klast + 7) / 8) nrun = (klast + 7) / 8;  // at least eight rows per run
+  if (krenv <= 0 && nrun > (klast + 7) / 8) nrun = (klast + 7) / 8;  // at least eight rows per run
   *KR = (int)((klast + nrun - 1) / nrun);
   return dim3((ni + 63) / 64, (nj + 3) / 4, (klast + *KR - 1) / *KR);
 }

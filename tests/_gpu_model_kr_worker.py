@@ -1,0 +1,35 @@
+"""Worker of test_forced_run_lengths_against_the_oracle: MGX_MODEL_KR (the model kernels' run length) is read once per process, so
+every run length is a process of its own.  compute_rhs, then correct_uvw with a random p (nhydro_solve with warm_start and
+solver_maxiter = 0); writes b, p and the corrected u, v, w (and the u it started from) as .npy files into the directory argv[4]."""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+import mgroms_amd as mg  # noqa: E402
+from mgroms_amd import nhydro  # noqa: E402
+from mgroms_amd.testcases import rndtopo_geometry  # noqa: E402
+
+nx, ny, nz = (int(a) for a in sys.argv[1:4])
+out = sys.argv[4]
+torch.cuda.set_device(0)
+nhydro.set_verbose(0)
+mg.nhydro_init(nx, ny, nz, 1, 1, 0, nhydro.default_params(relax_method="FC", solver_prec=1e-10, solver_maxiter=0))
+mg.nhydro_matrices(*rndtopo_geometry(nx, ny, 1, 1, 0), None, 4e3, 0.0, 0.0)
+rng = np.random.default_rng(23)  # the draws of _velocities(..., seed=23) in the test
+u = rng.standard_normal((nz, ny + 2, nx + 1)); v = rng.standard_normal((nz, ny + 1, nx + 2)); w = rng.standard_normal((nz + 1, ny + 2, nx + 2))
+np.save(os.path.join(out, "u0.npy"), u)
+g1 = mg.grid(1)
+g1.set("p", np.random.default_rng(29).standard_normal(g1._shape("p")))
+mg.fill_halo(1, "p")
+p = g1.p
+nhydro.set_option("warm_start", 1)
+mg.nhydro_solve(u, v, w)
+assert np.array_equal(g1.p, p)  # no iteration ran
+for name, a in (("b", g1.b), ("p", p), ("u", u), ("v", v), ("w", w)):
+    np.save(os.path.join(out, name + ".npy"), a)
+mg.nhydro_clean()
+print("ok")

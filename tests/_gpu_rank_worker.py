@@ -22,6 +22,11 @@ def main():
     rndtopo = "rndtopo" in opts    # mg_testrndtopo's geometry (BASELINE config 4) instead of the seamount
     fuse0 = "fuse0" in opts        # red-black, sequential order: the correction inside the walk's launch on every level that has an instance (rbseq_fuse_min = 0), open sides included
     connectfail = "connectfail" in opts  # rank 1 cannot open its neighbours' buffers (test hook): everybody must end up on the hooks, and every norm's all-reduce must carry the same count on all ranks
+    uvw = "uvw" in opts            # random u, v, w: one global field cut per rank, so the copies of a shared face agree
+    uvw_indep = "uvw_indep" in opts  # random u, v, w drawn per rank: the copies of a shared face disagree, and the reference takes the neighbour's flux there
+    overlap0 = "overlap0" in opts  # the shipped default overlap = 0 (nhydro_solve as a model calls it) instead of the exchange beside the interior sweep
+    model = uvw or uvw_indep       # ... and nhydro_solve on both sides afterwards: u, v, w per rank, bit for bit
+    assert not model or method == "FC" or exact
     if connectfail:
         os.environ["MGX_P2P_TEST_FAIL_CONNECT"] = "1"
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
@@ -46,13 +51,14 @@ def main():
     nhydro.set_verbose(0)
     comm = Comm(device="cuda", p2p=p2p)
     tol, maxit, nsc = (1e-6, 50, 40) if golden else (1e-9, 3, 6)
-    par = nhydro.default_params(relax_method=method, solver_prec=tol, nsmall=nsmall, ns_coarsest=nsc, bmask=1 if bmask else 0)
+    mkw = dict(solver_maxiter=maxit) if model else {}
+    par = nhydro.default_params(relax_method=method, solver_prec=tol, nsmall=nsmall, ns_coarsest=nsc, bmask=1 if bmask else 0, **mkw)
     nhydro.set_option("rb_exact", 1 if exact else 0)
     nhydro.set_option("rb_seq", 0 if par else 1)
     if fuse0:
         nhydro.set_option("rbseq_fuse_min", 0)
         nhydro.set_option("rbseq_window", 0)   # (the windowed walk, the default, needs no hand-off: this case is about the launch that has one)
-    nhydro.set_option("overlap", 1)   # the exchange beside the interior sweep (off by default: slower on a shared GPU); the bits must not depend on it
+    nhydro.set_option("overlap", 0 if overlap0 else 1)   # the exchange beside the interior sweep (off by default: slower on a shared GPU); the bits must not depend on it
     mg.nhydro_init(nx, ny, nz, npx, npy, rank, par, comm=comm)
     stamp("init")
     geometry = rndtopo_geometry if rndtopo else seamount_geometry
@@ -60,7 +66,22 @@ def main():
     from mgroms_amd.testcases import island_mask
     rmask = island_mask(nx, ny, npx, npy, rank) if bmask else None
     mg.nhydro_matrices(dx, dy, zeta, h, rmask, 4e3, 0.0, 0.0)
-    u = np.zeros((nz, ny + 2, nx + 1)); v = np.zeros((nz, ny + 1, nx + 2)); w = -np.ones((nz + 1, ny + 2, nx + 2)); w[0] = 0
+    def rank_uvw(r):
+        """u, v, w of rank r: (nz, ny+2, nx+1), (nz, ny+1, nx+2), (nz+1, ny+2, nx+2)"""
+        if uvw_indep:
+            g = np.random.default_rng(1000 + r)
+            return g.standard_normal((nz, ny + 2, nx + 1)), g.standard_normal((nz, ny + 1, nx + 2)), g.standard_normal((nz + 1, ny + 2, nx + 2))
+        g = np.random.default_rng(999)
+        ug = g.standard_normal((nz, npy * ny + 2, npx * nx + 1))
+        vg = g.standard_normal((nz, npy * ny + 1, npx * nx + 2))
+        wg = g.standard_normal((nz + 1, npy * ny + 2, npx * nx + 2))
+        qj, qi = (r // npx) * ny, (r % npx) * nx
+        return (ug[:, qj:qj + ny + 2, qi:qi + nx + 1].copy(), vg[:, qj:qj + ny + 1, qi:qi + nx + 2].copy(),
+                wg[:, qj:qj + ny + 2, qi:qi + nx + 2].copy())
+    if model:
+        u, v, w = rank_uvw(rank)
+    else:
+        u = np.zeros((nz, ny + 2, nx + 1)); v = np.zeros((nz, ny + 1, nx + 2)); w = -np.ones((nz + 1, ny + 2, nx + 2)); w[0] = 0
     nhydro.compute_rhs(u, v, w)
     stamp("matrices_rhs")
     t0 = time.time()
@@ -68,7 +89,7 @@ def main():
     t_solve = time.time() - t0
     stamp("solve")
 
-    o = make_seamount(nx, ny, nz, npx, npy, relax_method=method, solver_prec=tol, nsmall=nsmall, ns_coarsest=nsc, bmask=bmask)
+    o = make_seamount(nx, ny, nz, npx, npy, relax_method=method, solver_prec=tol, nsmall=nsmall, ns_coarsest=nsc, bmask=bmask, **mkw)
     if bmask or rndtopo:  # rebuild the oracle's matrices with every rank's mask / topography in place
         for r in range(o.nranks):
             if bmask:
@@ -76,6 +97,10 @@ def main():
             if rndtopo:
                 o.field("h", 1, r)[...] = rndtopo_geometry(nx, ny, npx, npy, r)[3]
         o.matrices(4e3, 0.0, 0.0)
+    if model:
+        for r in range(o.nranks):
+            for name, a in zip(("u", "v", "w"), rank_uvw(r)):
+                o.field(name, 1, r)[...] = a
     o.compute_rhs()
     no, ho, _ = o.solve_p(tol, maxit)
     stamp("oracle")
@@ -125,7 +150,7 @@ def main():
         assert np.array_equal(mg.grid(1).r, o.field("r", 1, rank)), rank
     c = nhydro.counters()
     assert c["exchanges"] > 0 and c["allreduces"] > 0  # the set-up halos always use the callback
-    if method == "FC" and p2p and not connectfail and not bmask:
+    if method == "FC" and p2p and not connectfail and not bmask and not overlap0:
         # the colour passes of the levels with neighbours ran in two parts on two streams, the exchange beside the interior part
         # (mgx_api.cpp relax()); the bits above are the oracle's, and the re-run through the hooks below (one stream) repeats them
         assert nhydro.get_option("overlap") == 1 and nhydro.get_option("overlapped_passes") > 0, rank
@@ -142,6 +167,16 @@ def main():
         assert n2 == n and np.array_equal(hist2, hist) and np.array_equal(mg.grid(1).p, p_first)
         assert nhydro.counters()["p2p_exchanges"] == c["p2p_exchanges"]
         comm.set_p2p(True)
+    if model:
+        # nhydro_solve as the model calls it: compute_rhs (with the flux exchange of mg_compute_rhs.f90:170-172, 271-273 unless bmask),
+        # solve_p, correct_uvw on this rank's u, v, w -- every rank's p, u, v, w bit for bit against the oracle's emulated ranks
+        mg.nhydro_solve(u, v, w)
+        no2, _, _ = o.nhydro_solve()
+        assert no2 == n, (no2, n)
+        assert np.array_equal(mg.grid(1).b, o.field("b", 1, rank)), rank
+        assert np.array_equal(mg.grid(1).p, o.field("p", 1, rank)), rank
+        for name, a in (("u", u), ("v", v), ("w", w)):
+            assert np.array_equal(a, o.field(name, 1, rank)), (rank, name)
     # src/old_tests/mg_testhalo.f90:75-92: fill p with the rank number, fill the halo: every halo plane holds the neighbour's
     # rank, or the own one across a physical boundary
     g1 = mg.grid(1)

@@ -41,6 +41,11 @@ def _free_port():
     (2, 2, 32, 32, 16, 8, "RB+exact+golden"),  # reference default in the reference's order: its recorded 2x2 history to 1e-10, p bitwise
     (2, 1, 32, 32, 16, 8, "RB+exact"),  # exact-order red-black with one open side and a 2x1 gather
     (2, 2, 32, 32, 16, 8, "FC+connectfail"),  # one rank fails to open its peers' buffers: all ranks fall back to the hooks together, the norms' all-reduce keeps one count on every rank
+    # the model coupling across ranks, with the shipped overlap = 0: random u, v, w; b after compute_rhs and p, u, v, w after nhydro_solve per rank
+    (2, 2, 32, 32, 16, 8, "FC+uvw_indep+overlap0"),  # every rank draws its own u, v, w: my last flux face must be the neighbour's first (flux_halo)
+    (2, 1, 64, 128, 64, 8, "FC+uvw+overlap0"),        # one global field cut per rank; nz = 64 (the bench's level-1 kernels) with an open side
+    (2, 2, 16, 16, 8, 8, "FC+bmask+uvw_indep+overlap0"),  # bmask: no flux exchange (mg_compute_rhs.f90:170, 271), the local faces stay
+    (1, 2, 16, 32, 8, 8, "FC+uvw+overlap0"),          # N/S only, ragged block
 ])
 def test_multirank_solve(npx, npy, nx, ny, nz, nsmall, method):
     world, port = npx * npy, _free_port()
