@@ -221,6 +221,16 @@ int mgx_set_verbose(int level);
  *   a process grid larger than 1 x 1, relax_method = 'GS', option "rb_exact".  The fp32 copies (~48 B per cell) are allocated at the first
  *   mixed solve and their coefficients converted again after every mgx_matrices / mgx_set_field of cA.
  *   Read-only: "mixed_iterations" (solve_p iterations run with fp32 cycles since mgx_init).
+ * "krylov" (default 0 = off, or m = 1..8; any other value is refused; survives mgx_clean / mgx_init): solve_p as right-preconditioned truncated GCR
+ *   (Orthomin(m)) with one F-cycle from p = 0 as preconditioner and m retained direction pairs (mgx_krylov.hip).  Same contract as solve_p:
+ *   tol is on ||b - A p|| / ||b||, maxite counts F-cycles, *nite, *res, hist, the printed lines and fort.100 keep their meaning; "warm_start"
+ *   works; every relax_method, bmask, the per-call mask, any process grid.  Applies to mgx_solve_p and through it to mgx_solve / mgx_solve_device.
+ *   The history entries of the iterations are the recurrence's residual norms; before the loop is left the true b - A p is computed, and where it
+ *   is not below tol it replaces the recurrence's r, the retained pairs are dropped and the loop goes on.  On return grid(1)%r, *res and the last
+ *   hist entry are the true residual's.  A vanishing or non-finite step leaves p as it was and ends the solve.  Costs 2 m + 2 extra level-1
+ *   fields, allocated at the first solve with the option on and freed by mgx_clean (143 MB each at 512x512x64: 1.4 GB for m = 4).  Refused by
+ *   solve_p together with "cycle_precision" = 32.  Three all-reduce calls per iteration on a process grid (one per pass).
+ *   Read-only: "krylov_restarts" (times the last solve fell back to the true residual).
  * Read-only through mgx_get_option: "p2p_failed" (a peer-to-peer wait of THIS rank timed out since the ranks last agreed: see below),
  *   "overlapped_passes". */
 int mgx_set_option(const char *name, int value);

@@ -120,6 +120,12 @@ void mgxx_restrict(hipStream_t, const LevView32 *, const LevView32 *, const floa
 void mgxx_coarse2fine(hipStream_t, const LevView32 *, const LevView32 *, int);
 void mgxx_to32(hipStream_t, const LevView *, const LevView32 *, const double *, float *, double);
 void mgxx_to64(hipStream_t, const LevView *, const LevView32 *, const float *, double *, double, int);
+// Krylov-accelerated solve_p (mgx_krylov.hip)
+long long mgxq_partials(const LevView *);
+void mgxq_apply(hipStream_t, const LevView *, double *, const double *const *, int, double *, double *, int);
+void mgxq_ortho(hipStream_t, const LevView *, double *, double *, const double *, const double *const *, const double *const *, const int *, int, const double *,
+                const double *, double *, double *);
+void mgxq_update(hipStream_t, const LevView *, double *, double *, const double *, const double *, const double *, double *, double *, double *);
 }
 
 // a HIP error that was pending when a kernel wrapper started (mgx_before_launch, mgx_device.h): reported by the next synchronising call
@@ -239,6 +245,14 @@ struct State {
   // correction form on fp32 shadows of every level (solve_p_mixed, mgx_mixed.hip).  The shadows are allocated at the first mixed solve and
   // their coefficients converted again whenever the fp64 coefficients changed (coef_gen: define_matrices, mgx_set_field of cA)
   int cycle_precision = 64;
+  // option "krylov" (0 default, 1..8): solve_p as truncated GCR / Orthomin(m) with one F-cycle from p = 0 as right preconditioner (solve_p_krylov,
+  // mgx_krylov.hip); m = retained direction pairs.  kr_z / kr_q: m + 1 level-1 fields each (the retained pairs and the one in work), allocated at
+  // the first solve with the option on (kr_n = pairs allocated); kr_sc: the scalars the kernels hand to each other, [0..7] (q, q_i), [8] s, [9] t,
+  // [16..24] (q_i, q_i) by slot
+  int krylov = 0;
+  int kr_restarts = 0;            // read-only option "krylov_restarts": times the last solve fell back to the true residual
+  int kr_n = 0;
+  double *kr_z[9] = {}, *kr_q[9] = {}, *kr_sc = nullptr, *kr_partial = nullptr;
   long long n_mixed = 0;          // read-only option "mixed_iterations": solve_p iterations run with fp32 cycles since mgx_init
   bool mx_ready = false;
   unsigned long long coef_gen = 0, mx_gen = ~0ULL;
@@ -872,9 +886,11 @@ int vcycle2(int lev1, int lev2) {
 // mg_solvers.f90:104-126
 // have_r2: grid(2)%r already holds the restriction of the level-1 residual (the closing compute_residual of the previous solve_p
 // iteration wrote it, residual_closing below): the first fine2coarse is then grid(2)%b = grid(2)%r and grid(2)%p = 0, two small copies
-int fcycle(bool have_r2 = false) {
+// have_r2 == 2: the caller has done the whole first fine2coarse(1) itself (grid(2)%b, %r and %p are set: solve_p_krylov)
+int fcycle(int have_r2 = 0) {
   TicScope ts(1, "Fcycle");  // mg_solvers.f90:108
   for (int lev = 1; lev <= S.nlevs - 1; lev++) {
+    if (lev == 1 && have_r2 == 2) continue;
     if (lev == 1 && have_r2) {
       Level &C = S.lev[1];
       HIPCHK(hipMemcpyAsync(C.v.b, C.v.r, C.n3js * sizeof(double), hipMemcpyDeviceToDevice, S.stream));   // physical images included (the kernel stored them)
@@ -1129,8 +1145,127 @@ int solve_p_mixed(double tol, int maxite, int *nite_out, double *res_out, double
   return 0;
 }
 
-// the solve_p of mgx_solve_p / mgx_solve / mgx_solve_device: fp64 cycles or fp32 cycles under fp64 refinement
+// ---- Krylov-accelerated solve_p (option "krylov" = m) -------------------------------------------------------------------
+// Right-preconditioned truncated GCR (Orthomin(m)) with M = one Fcycle from p = 0 on the right-hand side r: a fixed linear map, not a
+// symmetric one (3 pre / 2 post coloured sweeps), hence GCR and not CG.  Per iteration: z = M r, q = A z, (z, q) made A^T A-orthogonal to
+// the m retained pairs, p += (t / s) z, r -= (t / s) q with s = (q, q), t = (r, q).  The F-cycle reads level 1 through its view, so the
+// view's p / b / r are pointed at (z, r, scratch) for the cycle and back afterwards: nothing is copied.  r of the recurrence lives in
+// grid(1)%r; the scratch r of the cycle is the q of the pair in work, which is only written after the cycle.
+// The recurrence's r drifts away from b - A p near round-off, so no convergence is reported on its word: the true residual is computed
+// (compute_residual(1)) before the loop is left, and where it is not below tol it becomes r, the retained pairs are dropped
+// (kr_restarts) and the loop goes on.  On every exit grid(1)%r, *res and the last hist entry are the true residual's.
+struct ViewSwap {   // level 1's p / b / r as the solver owns them, put back on every way out
+  LevView &v; double *p, *b, *r;
+  explicit ViewSwap(LevView &w) : v(w), p(w.p), b(w.b), r(w.r) {}
+  void restore() { v.p = p; v.b = b; v.r = r; }
+  ~ViewSwap() { restore(); }
+};
+
+int krylov_prepare(int m) {
+  Level &L = S.lev[0];
+  if (!S.kr_sc) { CHK(dmalloc(&S.kr_sc, 32)); CHK(dmalloc(&S.kr_partial, (size_t)mgxq_partials(&L.v))); }
+  for (; S.kr_n < m + 1; S.kr_n++) { CHK(dmalloc(&S.kr_z[S.kr_n], L.n3js)); CHK(dmalloc(&S.kr_q[S.kr_n], L.n3js)); }
+  return 0;
+}
+
+// the inner products of one pass summed over the ranks: ONE call of the all-reduce hook
+int krylov_allreduce(double *buf, int n) {
+  if (S.nranks <= 1 || n == 0) return 0;
+  if (!S.ar) return fail("an all-reduce is needed (npx*npy > 1) but mgx_set_comm was not called");
+  S.n_allred++;
+  if (S.ar(S.ctx, buf, n)) return fail("allreduce callback failed");
+  return 0;
+}
+
+int solve_p_krylov(double tol, int maxite, int *nite_out, double *res_out, double *hist) {
+  const int m = S.krylov;
+  CHK(krylov_prepare(m));
+  Level &L = S.lev[0];
+  if (S.verbose && S.rank == 0) printf(" - solve p:\n");
+  TicScope ts(1, "solve");
+  const auto tstart = std::chrono::steady_clock::now();
+  if (!S.warm_start) HIPCHK(hipMemsetAsync(L.v.p, 0, L.n3js * sizeof(double), S.stream));
+  mgxk_sumsq(S.stream, &L.v, L.v.b, S.d_partial, S.d_scalar); S.n_launch += 2;
+  double bnorm; CHK(global_sum(L, &bnorm)); bnorm = sqrt(bnorm);
+  int nite = 0;
+  double rnorm; CHK(residual(1, &rnorm));   // the true residual, into grid(1)%r
+  double res0 = rnorm / bnorm;
+  const double rnorm0 = res0;
+  if (hist) hist[0] = res0;
+  struct F100 { FILE *f; ~F100() { if (f) fclose(f); } } f100 = {(S.verbose && S.rank == 0) ? fopen("fort.100", "a") : nullptr};
+  if (f100.f) fprintf(f100.f, " %24.16E %d\n", res0, nite);
+  ViewSwap own(L.v);
+  double *sc = S.kr_sc, *qq = S.kr_sc + 16;
+  int kept = 0, head = 0;   // retained pairs: the `kept` slots before `head` in the ring of m + 1; head = the pair in work
+  bool fresh = true, broke = false;   // fresh: grid(1)%r is the true residual of grid(1)%p
+  S.kr_restarts = 0;
+  for (;;) {
+    while (nite < maxite && res0 > tol) {
+      double *z = S.kr_z[head], *q = S.kr_q[head];
+      {  // z = M r: Fcycle on (p, b) = (0, r).  The first leg restricts the view's r, the rest of the cycle may use it as scratch.
+        HIPCHK(hipMemsetAsync(z, 0, L.n3js * sizeof(double), S.stream));
+        L.v.p = z; L.v.b = own.r; L.v.r = own.r;
+        int rc = S.nlevs >= 2 ? fine2coarse(1, true) : 0;
+        L.v.r = q;
+        if (!rc) rc = fcycle(2);
+        own.restore();
+        if (rc) return rc;
+      }
+      const double *zi[8], *qi[8]; int slot[8];
+      for (int n = 0; n < kept; n++) { slot[n] = (head + m + 1 - kept + n) % (m + 1); zi[n] = S.kr_z[slot[n]]; qi[n] = S.kr_q[slot[n]]; }
+      {
+        TicScope t1(1, "krylov_apply");
+        LevView zv = L.v; zv.p = z;
+        mgxq_apply(S.stream, &zv, q, qi, kept, S.kr_partial, sc, S.real); S.n_launch += kept ? 2 : 1;
+        CHK(krylov_allreduce(sc, kept));
+      }
+      {
+        TicScope t2(1, "krylov_ortho");
+        mgxq_ortho(S.stream, &L.v, z, q, own.r, zi, qi, slot, kept, sc, qq, S.kr_partial, sc + 8); S.n_launch += 2;
+        CHK(krylov_allreduce(sc + 8, 2));
+      }
+      double s2;
+      {
+        TicScope t3(1, "krylov_update");
+        mgxq_update(S.stream, &L.v, own.p, own.r, z, q, sc + 8, qq + head, S.kr_partial, S.d_scalar); S.n_launch += 2;
+        CHK(global_sum(L, &s2));   // the iteration's one host synchronisation: the stopping test
+      }
+      fresh = false;
+      if (!(s2 >= 0.0)) { broke = true; break; }   // no step was taken (s == 0 or a non-finite scalar): p is what it was
+      rnorm = sqrt(s2) / bnorm;
+      const double conv = res0 / rnorm;
+      res0 = rnorm;
+      nite++;
+      if (hist) hist[nite] = rnorm;
+      if (S.verbose && S.rank == 0) printf("ite = %2d: res = %s / conv = %10.3f\n", nite, fortran_e3(rnorm, 10).c_str(), conv);
+      if (f100.f) fprintf(f100.f, " %24.16E %24.16E\n", rnorm, conv);
+      if (kept < m) kept++;
+      head = (head + 1) % (m + 1);
+    }
+    if (fresh) break;
+    CHK(residual(1, &rnorm));   // b - A p into grid(1)%r: the word that counts
+    fresh = true;
+    res0 = rnorm / bnorm;
+    if (hist) hist[nite] = res0;
+    if (broke || nite >= maxite || !(res0 > tol)) break;
+    S.kr_restarts++; kept = 0;   // the recurrence had drifted: go on from the true residual with no history
+  }
+  if (S.verbose && S.rank == 0) {
+    const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - tstart).count();
+    const double np = (double)L.npx * L.npy, ncell = (double)L.nx * L.npx * (double)L.ny * L.npy * (double)L.nz;
+    const double perf = dt * np / (-log(res0 / rnorm0) / log(10.0)) / ncell;
+    printf(" --- summary ---\ntime spent to solve :%8.3f s\nrescaled performance:%s\n ---------------\n", dt, fortran_e3(perf, 10).c_str());
+  }
+  if (nite_out) *nite_out = nite;
+  if (res_out) *res_out = res0;
+  return 0;
+}
+
+// the solve_p of mgx_solve_p / mgx_solve / mgx_solve_device: fp64 cycles, fp32 cycles under fp64 refinement, or the Krylov-accelerated loop
 int solve_p_opt(double tol, int maxite, int *nite_out, double *res_out, double *hist) {
+  if (S.krylov > 0 && S.cycle_precision == 32)
+    return fail("options \"krylov\" = %d and \"cycle_precision\" = 32 cannot be combined (fp32 cycles under the Krylov loop are not served): set one of them back", S.krylov);
+  if (S.krylov > 0) return solve_p_krylov(tol, maxite, nite_out, res_out, hist);
   return S.cycle_precision == 32 ? solve_p_mixed(tol, maxite, nite_out, res_out, hist) : solve_p(tol, maxite, nite_out, res_out, hist);
 }
 
@@ -1628,7 +1763,7 @@ void mgx_clean(void) {
   if (S.ev_s) (void)hipEventDestroy(S.ev_s);
   if (S.ev_x) (void)hipEventDestroy(S.ev_x);
   tt_collect();
-  hipStream_t st = S.stream; int vb = S.verbose, ws = S.warm_start, tc = S.tictoc, eh = S.exact_halos, rx = S.rb_exact, rq = S.rb_seq, kr = S.keep_r, cs = S.c2f_skip, fc = S.fuse_closing, uc = S.use_chain, rf = S.rbseq_fuse, rw = S.rbseq_window, cdo = S.coarsest_direct, rfm = S.rbseq_fuse_min, ovl = S.overlap, kp = S.use_ksp, fz = S.use_fuse, ao = S.async_ops, cp = S.cycle_precision;
+  hipStream_t st = S.stream; int vb = S.verbose, ws = S.warm_start, tc = S.tictoc, eh = S.exact_halos, rx = S.rb_exact, rq = S.rb_seq, kr = S.keep_r, cs = S.c2f_skip, fc = S.fuse_closing, uc = S.use_chain, rf = S.rbseq_fuse, rw = S.rbseq_window, cdo = S.coarsest_direct, rfm = S.rbseq_fuse_min, ovl = S.overlap, kp = S.use_ksp, fz = S.use_fuse, ao = S.async_ops, cp = S.cycle_precision, kry = S.krylov;
   mgx_exchange_fn ex = S.ex; mgx_allreduce_fn ar = S.ar; mgx_allgather_fn ag = S.ag; void *ctx = S.ctx; const bool nat = S.native_rccl;
   // the timer table is module state of mg_tictoc in the reference: it outlives nhydro_clean (the drivers print it afterwards, mg_testseamount.f90:220-221)
   std::vector<std::string> tn = S.tt_names; std::vector<HostTic> th = S.tt_host; const int tnb = S.tt_nblev;
@@ -1637,7 +1772,7 @@ void mgx_clean(void) {
   S = State();
   S.tt_names = tn; S.tt_host = th; S.tt_nblev = tnb; memcpy(S.tt_time, tsave, sizeof tsave); memcpy(S.tt_calls, csave, sizeof csave);
   S.native_rccl = nat;
-  S.stream = st; S.verbose = vb; S.warm_start = ws; S.tictoc = tc; S.exact_halos = eh; S.rb_exact = rx; S.rb_seq = rq; S.keep_r = kr; S.c2f_skip = cs; S.fuse_closing = fc; S.use_chain = uc; S.rbseq_fuse = rf; S.rbseq_window = rw; S.coarsest_direct = cdo; S.rbseq_fuse_min = rfm; S.overlap = ovl; S.use_ksp = kp; S.use_fuse = fz; S.async_ops = ao; S.cycle_precision = cp; S.ex = ex; S.ar = ar; S.ag = ag; S.ctx = ctx;
+  S.stream = st; S.verbose = vb; S.warm_start = ws; S.tictoc = tc; S.exact_halos = eh; S.rb_exact = rx; S.rb_seq = rq; S.keep_r = kr; S.c2f_skip = cs; S.fuse_closing = fc; S.use_chain = uc; S.rbseq_fuse = rf; S.rbseq_window = rw; S.coarsest_direct = cdo; S.rbseq_fuse_min = rfm; S.overlap = ovl; S.use_ksp = kp; S.use_fuse = fz; S.async_ops = ao; S.cycle_precision = cp; S.krylov = kry; S.ex = ex; S.ar = ar; S.ag = ag; S.ctx = ctx;
 }
 
 int mgx_init(int nx, int ny, int nz, int npx, int npy, int rank, const mgx_params *par) {
@@ -1962,6 +2097,10 @@ int mgx_set_option(const char *name, int value) {
     if (value != 32 && value != 64) return fail("cycle_precision must be 64 (fp64 cycles) or 32 (fp32 cycles under fp64 refinement), got %d", value);
     S.cycle_precision = value;
   }
+  else if (streq(name, "krylov")) {
+    if (value < 0 || value > 8) return fail("krylov must be 0 (off) or 1..8 (retained direction pairs of the truncated GCR), got %d", value);
+    S.krylov = value;
+  }
   else if (streq(name, "ksp_test_stall")) S.ksp_test_stall = value;
   else if (streq(name, "rbseq_test_stall")) S.rbseq_test_stall = value;
   else if (streq(name, "rbseq_fuse_min")) S.rbseq_fuse_min = value;
@@ -2018,6 +2157,8 @@ int mgx_get_option(const char *name, int *value) {
   else if (streq(name, "fuse_tail")) *value = S.use_fuse;
   else if (streq(name, "cycle_precision")) *value = S.cycle_precision;
   else if (streq(name, "mixed_iterations")) *value = (int)S.n_mixed;
+  else if (streq(name, "krylov")) *value = S.krylov;
+  else if (streq(name, "krylov_restarts")) *value = S.kr_restarts;
   else if (streq(name, "p2p_failed")) *value = S.p2p_failed;
   else if (streq(name, "p2p")) *value = S.p2p_on ? 1 : 0;
   else return fail("unknown option '%s'", name);
