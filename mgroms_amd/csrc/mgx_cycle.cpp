@@ -1,0 +1,735 @@
+// Host side of libmgx.so, cycle control: the tictoc timers, the operators (relax, residual, fine2coarse, coarse2fine), the V- and
+// F-cycle and the three solve_p drivers (fp64 cycles, fp32 cycles under fp64 refinement, Krylov-accelerated).  Every operator is a HIP
+// kernel launch through a wrapper of mgx_wrappers.h; which kernel serves a level is decided here.
+#include "mgx_host.h"
+
+namespace mgx_host {
+
+// ---- mg_tictoc.f90: tic(lev,name) / toc(lev,name) / print_tictoc, timed with HIP events on the solver's stream ----
+
+int tt_sub(const char *name) {
+  for (size_t q = 0; q < S.tt_names.size(); q++) if (S.tt_names[q] == name) return (int)q;
+  S.tt_names.push_back(name);
+  return (int)S.tt_names.size() - 1;
+}
+void tic(int lev, const char *name) {
+  if (!S.tictoc) return;
+  TicRec r; r.lev = lev; r.sub = tt_sub(name);
+  if (r.sub >= 32 || lev > 32) return;
+  (void)hipEventCreate(&r.e0); (void)hipEventCreate(&r.e1);
+  (void)hipEventRecord(r.e0, S.stream);
+  S.tt_open.push_back(r);
+}
+void toc(int lev, const char *name) {
+  if (!S.tictoc) return;
+  const int sub = tt_sub(name);
+  for (int q = (int)S.tt_open.size() - 1; q >= 0; q--)
+    if (S.tt_open[q].lev == lev && S.tt_open[q].sub == sub) {
+      (void)hipEventRecord(S.tt_open[q].e1, S.stream);
+      S.tt_done.push_back(S.tt_open[q]);
+      S.tt_open.erase(S.tt_open.begin() + q);
+      if (lev > S.tt_nblev) S.tt_nblev = lev;
+      return;
+    }
+}
+void tt_collect() {
+  if (S.tt_done.empty()) return;
+  (void)hipStreamSynchronize(S.stream);
+  for (auto &r : S.tt_done) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, r.e0, r.e1) == hipSuccess) { S.tt_time[r.lev - 1][r.sub] += ms * 1e-3; S.tt_calls[r.lev - 1][r.sub]++; }
+    (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1);
+  }
+  S.tt_done.clear();
+}
+
+// ---- operators ------------------------------------------------------------------------------------
+// mg_relax.f90:16-47 relax ; :151-190 RB ; :193-234 FC
+int relax(int lev, int nsweeps) {
+  Level &L = S.lev[lev - 1];
+  TicScope ts(lev, S.method == M_RB ? "relax_3D_8_RB" : (S.method == M_FC ? "relax_3D_8_FC" : "relax_3D_8_GS"));  // mg_relax.f90:128,167,209
+  if (S.tictoc && S.tt_done.size() > 4096) tt_collect();
+  if (S.method == M_GS) {  // exact lexicographic order by hyperplanes; halo fill once per sweep (mg_relax.f90:131-141)
+    for (int it = 1; it <= nsweeps; it++) {
+      if (!mgxk_relax_gs_sweep(S.stream, &L.v, S.real)) return fail("relax_method='GS': the sweep of level %d could not be launched", lev);
+      S.n_launch += L.ny + 2 * L.nx - 2;
+      CHK(fill_halo_js(L, L.v.p));
+    }
+    return 0;
+  }
+  const Sides ph = sides_of(L);
+  const int rbm = rb_mode(L), exact = rbm == RB_EXACT;
+  // sequential-order red-black (mgx_rbseq.hip); the one-workgroup kernels of the small levels run the reference's plane loop itself
+  const int seq = rbm == RB_SEQ;
+  if (S.use_small && nsweeps > 0 && mgxk_relax_small(S.stream, &L.v, nsweeps, S.method, S.real, ph, exact ? 1 : (seq ? 2 : 0))) { S.n_launch++; return 0; }
+  const bool closed = all_physical(ph);
+  // closed mid levels, four colours: the whole call in one persistent launch, one workgroup per plane (mgx_relax_ks.hip: k_relax_ksp)
+  if (S.method == M_FC && closed && S.use_ksp && !S.ksp_down && live_instances() == 1 && mgxk_relax_ks_persist(S.stream, &L.v, nsweeps, S.real, ph, L.ksp_done, L.ksp_seq, S.kerr, S.ksp_test_stall)) {
+    S.ksp_test_stall = 0;
+    L.ksp_seq += (unsigned int)nsweeps; S.n_launch++;
+    return 0;
+  }
+  double *const p1a = L.v.p1;
+  for (int it = 1; it <= nsweeps; it++) {
+    if (exact) {
+      // The reference's red-black loop is sequential (mg_relax.f90:170-186): with cmatrix='real' a column of plane i reads the
+      // same-colour k=1 diagonals (j+-1,i-1) already updated and (j+-1,i+1) not yet (:271-276).  Columns of one colour inside a
+      // plane are independent, so one launch per plane, in order, reproduces the loop bit for bit -- on one rank and, with the
+      // halo filled after each colour as in the reference, its decomposition-dependent result on several.
+      for (int rb = 1; rb <= 2; rb++) {
+        int fused = 0;
+        for (int i = 1; i <= L.nx; i++) { fused = mgxk_relax_colour(S.stream, &L.v, i, 1, 1, -1, rb, 1, 0, ph); S.n_launch++; }
+        CHK(fill_halo_js(L, L.v.p, fused));
+      }
+      continue;
+    }
+    if (S.method == M_RB) {
+      // cmatrix='real': the k=1 diagonal neighbours have the column's own colour and must be read as they were before the
+      // pass (snapshot).  On a closed level the register kernels write the next sweep's snapshot themselves (two buffers
+      // swapped per sweep: a pass reads only entries of its own colour, which the other colour's pass never touches), so
+      // one snapshot launch per relax call suffices; with neighbours the halo part changes after every exchange.
+      const bool chain = S.rb_chain && S.real && closed && mgxk_has_reg_kernel(&L.v) && !seq;
+      if (chain) {
+        if (it == 1) { mgxk_snapshot_k1(S.stream, &L.v); S.n_launch++; }
+        L.v.p1w = (L.v.p1 == p1a) ? L.p1b : p1a;
+      }
+      for (int rb = 1; rb <= 2; rb++) {
+        // seq on a closed level: the correction keeps the snapshot current (its colour's new bottom values and their physical images), so one
+        // snapshot launch per relax call; with neighbours the halo part changes with every exchange
+        if (S.real && !chain && !(seq && closed && !(it == 1 && rb == 1))) { mgxk_snapshot_k1(S.stream, &L.v); S.n_launch++; }
+        // (seq, wide half-rows: the pass also leaves the walk's d0 = y(k=1) - snapshot in u1 where its kernel can -- one launch less)
+        L.v.d0w = (seq && S.rbseq_d0_in_pass && (mgxk_rbseq_wants_d0(&L.v) || (S.rbseq_window && L.rbs_m > 0))) ? L.v.u1 : nullptr;
+        const int pass = mgxk_relax_colour(S.stream, &L.v, 1, 1, L.nx, -1, rb, S.real, S.real, ph); S.n_launch++;
+        L.v.d0w = nullptr;
+        int fused = pass & 1;
+        const int have_d0 = (pass & 2) ? 1 : 0;
+        if (seq) {
+          // y is in p; the walk over the planes, then p += g s with the mirrors (mgx_rbseq.hip).  A level wider than the walk takes
+          // (ny > 2048) would have to run plane by plane: refuse loudly rather than fall back to another iteration
+          // small levels whose pass left d0 in u1: walk and correction in one launch, every workgroup walking for itself (k_rbseq_walk_apply)
+          // the windowed walk where the level's contraction bound allows it (k_rbseq_window): one launch, no hand-off, no walk over the level
+          if (S.rbseq_window && L.rbs_m > 0) {
+            if (!have_d0) { mgxk_rbseq_d0(S.stream, &L.v, rb); S.n_launch++; }   // (the nz = 128 colour pass does not leave it)
+          }
+          const int kcut = S.rbseq_rowcut ? L.rbs_rows : L.nz;
+          if (S.rbseq_window && L.rbs_m > 0 && mgxk_rbseq_window(S.stream, &L.v, rb, ph, closed ? 1 : 0, L.rbs_m, kcut)) {
+            // the window stores the physical images of the rows it corrects (k < kcut) only: the rows below the cut keep those of the
+            // colour pass, which the generic kernel (no register instance for this nz / matrix) does not store
+            S.n_launch++; S.n_window++; fused = (pass & 1) || kcut >= L.nz;
+            CHK(fill_halo_js(L, L.v.p, fused));
+            continue;
+          }
+          if (have_d0 && S.rbseq_fuse && mgxk_rbseq_walk_apply(S.stream, &L.v, rb, ph, closed ? 1 : 0)) {
+            S.n_launch++; fused = 1;
+            CHK(fill_halo_js(L, L.v.p, fused));
+            continue;
+          }
+          // (where an instance exists the correction runs inside the walk's launch, chasing it: option "rbseq_fuse")
+          const int ran = S.rbseq_fuse ? mgxk_rbseq_scan_apply(S.stream, &L.v, rb, ph, closed ? 1 : 0, have_d0, L.rbs_flag, ++L.rbs_seq, S.kerr, S.rbseq_test_stall, (long long)S.rbseq_fuse_min) : mgxk_rbseq_scan(S.stream, &L.v, rb, have_d0);
+          if (ran == 2) S.rbseq_test_stall = 0;
+          if (!ran) return fail("rb_seq: level %d (ny = %d) has no scan instance; set option rb_exact or rb_seq = 0", lev, L.ny);
+          if (ran == 1) { mgxk_rbseq_apply(S.stream, &L.v, rb, ph, closed ? 1 : 0); S.n_launch++; }
+          S.n_launch += 2 - have_d0;
+          fused = 1;  // the correction stores the physical images of every column it updates
+        }
+        CHK(fill_halo_js(L, L.v.p, fused));
+      }
+      if (chain) { L.v.p1 = L.v.p1w; L.v.p1w = nullptr; if (it == nsweeps) L.v.p1 = p1a; }
+    } else {
+      // A level with neighbours, halos by the pushes: the boundary part of a colour (the waves that hold a column next to a neighbour's
+      // halo -- what the exchange sends, and all that reads what the last exchange delivered) and the exchange behind it go to a second
+      // stream; the interior part runs beside them on the solver's stream and waits only for the previous colour's boundary part
+      // (mg_relax.f90:181,224 exchange after every colour; SURVEY 7 "split boundary columns from interior, exchange while the interior runs").
+      const bool ov = S.overlap && S.p2p_on && S.stream2 && !closed && mgxk_has_reg_kernel(&L.v);
+      for (int fc1 = 1; fc1 <= 2; fc1++) {
+        // closed mid levels: the two colours of a plane set in one launch (mgx_relax_ks.hip)
+        if (closed && mgxk_relax_ks_pair(S.stream, &L.v, fc1, L.nx / 2, S.real, ph)) { S.n_launch++; continue; }
+        for (int fc2 = 1; fc2 <= 2; fc2++) {
+          if (ov) {
+            Sides ps = ph;
+            HIPCHK(hipEventRecord(S.ev_a, S.stream));                 // the interior of the previous colour (and whatever came before)
+            HIPCHK(hipStreamWaitEvent(S.stream2, S.ev_a, 0));
+            ps.part = 1;
+            const int fused = mgxk_relax_colour(S.stream2, &L.v, 1 + (fc1 - 1) % 2, 2, L.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0, ps);
+            HIPCHK(hipEventRecord(S.ev_s, S.stream2));
+            { hipStream_t keep = S.stream; S.stream = S.stream2; const int rc = fill_halo_js(L, L.v.p, fused); S.stream = keep; if (rc) return rc; }
+            ps.part = 2;
+            mgxk_relax_colour(S.stream, &L.v, 1 + (fc1 - 1) % 2, 2, L.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0, ps);
+            HIPCHK(hipStreamWaitEvent(S.stream, S.ev_s, 0));          // what follows on the solver's stream reads this colour's boundary part -- not its exchange
+            S.n_launch += 2; S.n_overlap++;
+            continue;
+          }
+          const int fused = mgxk_relax_colour(S.stream, &L.v, 1 + (fc1 - 1) % 2, 2, L.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0, ph); S.n_launch++;
+          CHK(fill_halo_js(L, L.v.p, fused));
+        }
+      }
+      if (ov && it == nsweeps) {  // the call ends: the solver's stream continues behind the last exchange
+        HIPCHK(hipEventRecord(S.ev_x, S.stream2));
+        HIPCHK(hipStreamWaitEvent(S.stream, S.ev_x, 0));
+      }
+    }
+  }
+  return 0;
+}
+
+// mg_relax.f90:337-383 compute_residual.  res == nullptr: the caller discards the norm (mg_solvers.f90:140),
+// so neither the reduction nor the all-reduce is issued.
+int residual(int lev, double *res) {
+  Level &L = S.lev[lev - 1];
+  TicScope ts(lev, "residual_3D_8");  // mg_relax.f90:367
+  const Sides ph = sides_of(L);
+  mgxk_residual(S.stream, &L.v, S.d_partial, S.d_scalar, S.real, res != nullptr, ph); S.n_launch += res ? 2 : 1;
+  // the kernel wrote the physical mirrors of r; the neighbour part of r's halo is never read by the cycle (restriction
+  // uses interior cells only), so the exchange is deferred until someone asks for r (mgx_get_field / mgx_fill_halo)
+  if (S.exact_halos) CHK(fill_halo_js(L, L.v.r, true)); else L.r_halo_stale = true;
+  if (res) { double s; CHK(global_sum(L, &s)); *res = sqrt(s); }
+  return 0;
+}
+
+// mg_intergrids.f90:16-72.  with_residual: the caller is the down leg of a V-cycle, which would call compute_residual(lev)
+// right before and discards both the norm and r (mg_solvers.f90:138-142): residual and restriction then run as ONE kernel
+// that never writes r (mgx_resrest.hip), when the level has its matrix-free slopes; otherwise the two kernels in sequence.
+int fine2coarse(int lev, bool dup_r, bool with_residual) {
+  Level &F = S.lev[lev - 1], &C = S.lev[lev];
+  const Sides phc = sides_of(C), none = {0, 0, 0, 0};
+  bool fused = false;
+  // returns true when the fused residual+restriction kernel took the job
+  auto down = [&](const LevView *Cv, double *dst, Sides ph, double *zero) -> int {
+    if (!with_residual) return 0;
+    if (!S.exact_halos && !S.keep_r && !dup_r) {  // keep_r: the caller wants the reference's r, which the fused kernel never writes
+      TicScope ts(lev, "residual_3D_8");
+      if (mgxk_residual_restrict(S.stream, &F.v, Cv, dst, S.real, ph, zero)) { S.n_launch++; return 1; }
+    }
+    return residual(lev, nullptr) ? -1 : 0;
+  };
+  if (!C.gather) {
+    // closed level: the kernel also zeroes p_c and, for Fcycle, duplicates b_c into r_c (whole arrays through the mirrors)
+    fused = all_physical(phc);
+    const int d = down(&C.v, C.v.b, phc, fused ? C.v.p : nullptr);
+    if (d < 0) return 1;
+    if (!d) { mgxk_fine2coarse(S.stream, &F.v, &C.v, C.v.b, phc, fused && dup_r ? C.v.r : nullptr, fused ? C.v.p : nullptr); S.n_launch++; }
+  } else {
+    const int d = down(&C.vs, C.vs.b, none, nullptr);
+    if (d < 0) return 1;
+    if (!d) { mgxk_fine2coarse(S.stream, &F.v, &C.vs, C.vs.b, none, nullptr, nullptr); S.n_launch++; }
+    const int Ng = C.nz * (C.vs.ny + 2) * (C.vs.nx + 2);
+    if (S.p2p_on) {  // gather_3D (mg_gather.f90:95-174) as pushes into the members' gather buffers
+      const unsigned long long seq = ++C.p2p_gseq;
+      const int par = (int)(seq & 1), li = lev;
+      int me = -1;
+      for (int q = 0; q < C.ngroup; q++) if (C.group[q] == S.rank) me = q;
+      if (me < 0) return fail("gather: rank %d is not in its own group on level %d", S.rank, lev + 1);
+      double *dst[4]; unsigned long long *rflag[4];
+      for (int q = 0; q < C.ngroup; q++) {
+        // my own copy stays in ordinary device memory (C.blk): stores to the fine-grained slab are uncached and slow
+        dst[q] = q == me ? C.blk : S.peer_slab[C.group[q]] + C.p2p_goff[par] + (size_t)me * Ng;
+        rflag[q] = S.peer_flags[C.group[q]] + 1024 + (li * 4 + me) * 2 + par;
+      }
+      mgxk_gather_push(S.stream, &C.vs, C.vs.b, dst, rflag, C.ngroup, me, seq, S.p2p_counter, S.p2p_err); S.n_launch++;
+      for (int q = 0; q < C.ngroup; q++) {
+        unsigned long long *lflag = q == me ? nullptr : S.p2p_flags + 1024 + (li * 4 + q) * 2 + par;
+        mgxk_gather_place_wait(S.stream, &C.v, C.v.b, q == me ? C.blk : S.p2p_slab + C.p2p_goff[par] + (size_t)q * Ng, C.vs.nx, C.vs.ny, q % C.ngx, q / C.ngx, lflag, seq, S.p2p_err);
+        S.n_launch++;
+      }
+      S.n_p2p++;
+    } else {
+      mgxk_block_to_ref(S.stream, &C.vs, C.vs.b, C.blk); S.n_launch++;
+      if (!S.ag) return fail("a gather is needed but mgx_set_comm was not called");
+      if (S.ag(S.ctx, C.group, C.ngroup, C.blk, C.gbuf, Ng)) return fail("allgather callback failed");
+      for (int q = 0; q < C.ngroup; q++) {
+        mgxk_gather_place(S.stream, &C.v, C.v.b, C.gbuf + (size_t)q * Ng, C.vs.nx, C.vs.ny, q % C.ngx, q / C.ngx); S.n_launch++;
+      }
+    }
+  }
+  // b's halo is not read by relax/residual either: physical mirrors are in place, neighbour exchange deferred
+  if (S.exact_halos || C.gather) CHK(fill_halo_js(C, C.v.b, !C.gather)); else C.b_halo_stale = true;
+  if (!fused) {
+    HIPCHK(hipMemsetAsync(C.v.p, 0, C.n3js * sizeof(double), S.stream));
+    if (dup_r) HIPCHK(hipMemcpyAsync(C.v.r, C.v.b, C.n3js * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
+  }
+  return 0;
+}
+
+// mg_intergrids.f90:167-228.  keep_r: also leave the interpolated correction in the fine r, as the reference does (the C-ABI operator
+// and exact_halos = 1); the cycles do not -- nothing reads it before compute_residual overwrites it.
+// skip1: a four-colour relax(lev, n >= 1) follows immediately -- its first colour overwrites the (i odd, j odd) columns without reading
+// them, so the prolongation leaves them alone (never together with keep_r).
+int coarse2fine(int lev, bool keep_r, bool skip1) {
+  Level &F = S.lev[lev - 1], &C = S.lev[lev];
+  const Sides phf = sides_of(F);
+  if (!C.gather) {
+    mgxk_coarse2fine(S.stream, &F.v, &C.v, C.v.p, S.linear, phf, keep_r, skip1 && !keep_r); S.n_launch++;
+  } else {
+    mgxk_split(S.stream, &C.v, &C.vs, C.v.p, C.vs.p, C.key % 2, C.key / 2); S.n_launch++;
+    mgxk_coarse2fine(S.stream, &F.v, &C.vs, C.vs.p, S.linear, phf, keep_r, skip1 && !keep_r); S.n_launch++;
+  }
+  if (S.exact_halos && keep_r) CHK(fill_halo_js(F, F.v.r, true)); else F.r_halo_stale = true;
+  // p = p + r over the whole array: the interior was updated by the kernel; the halo of p + halo of r
+  // equals the halo fill of the updated p (both are images of the same interior cells)
+  CHK(fill_halo_js(F, F.v.p, true));
+  return 0;
+}
+
+// relax(lev, nsweeps) of the level below the coarsest one (a closed level the one-workgroup kernel serves), with coarse2fine(lev) folded
+// in front (flags & 1) and / or compute_residual(lev) + fine2coarse(lev) folded behind (flags & 2): mgx_relax_coarse.hip.  Returns 1 when
+// the fused kernel took the job (same bits as the separate operators), 0 = run them.
+int relax_fused(int lev, int nsweeps, int flags) {
+  if (lev >= S.nlevs || !S.use_small || !S.use_fuse || S.method == M_GS || S.tictoc || S.keep_r || S.exact_halos || !S.linear) return 0;
+  Level &F = S.lev[lev - 1], &C = S.lev[lev];
+  const int mode = rb_mode(F);
+  if (mode == RB_EXACT) return 0;
+  const Sides phf = sides_of(F), phc = sides_of(C);
+  if (!all_physical(phf) || !all_physical(phc) || C.gather) return 0;
+  if (!mgxk_relax_wave_fused(S.stream, &F.v, &C.v, nsweeps, S.method, S.real, phf, flags, mode)) return 0;
+  S.n_launch++;
+  if (flags & 1) F.r_halo_stale = true;  // what coarse2fine leaves (the correction is not stored in r inside a cycle)
+  return 1;
+}
+
+// relax(nlevs, ns_coarsest) inside a cycle (mg_solvers.f90:117,144), where the coarsest level is entered with p = 0 (fine2coarse, mg_intergrids.f90:70):
+// where option "coarsest_direct" allows it, one matrix-vector product with the operator the level's relax kernel built (mgx_relax_coarse.hip)
+// p_zero: the caller has just restricted onto the level (Vcycle(nlevs) called as an operator relaxes whatever p it finds: the sweeps)
+int coarsest_solve(bool p_zero) {
+  Level &L = S.lev[S.nlevs - 1];
+  const Sides ph = sides_of(L);
+  const int rbm = rb_mode(L), exact = rbm == RB_EXACT, seq = rbm == RB_SEQ;
+  const bool want = S.coarsest_direct == 2 || (S.coarsest_direct == 1 && seq);
+  if (want && p_zero && S.nlevs >= 2 && S.use_small && !S.tictoc && S.method != M_GS && !exact && all_physical(ph) && !L.gather && S.par.ns_coarsest >= 1 && S.cd_n >= 0) {
+    const int n = mgxk_coarse_direct_cells(&L.v), mode = seq ? 2 : 0;
+    if (n > 0) {
+      if (!S.cd_M) {
+        CHK(dmalloc(&S.cd_pb, (size_t)2 * n * L.n3js)); CHK(dmalloc(&S.cd_M, (size_t)n * n));
+        CHK(dmalloc(&S.cd_part, (size_t)mgxk_coarse_direct_slabs(n) * n));
+        { double *q = nullptr; CHK(dmalloc(&q, 512)); S.cd_cnt = (unsigned int *)q; }   // one word per 64 rows, 64 bytes apart (zeroed by dmalloc)
+        S.cd_n = n;
+      }
+      if (!S.cd_valid || S.cd_method != S.method || S.cd_mode != mode || S.cd_nsweeps != S.par.ns_coarsest) {
+        if (mgxk_coarse_direct_build(S.stream, &L.v, S.par.ns_coarsest, S.method, S.real, ph, mode, S.cd_pb, (long long)L.n3js, S.cd_M)) {
+          S.cd_valid = 1; S.cd_method = S.method; S.cd_mode = mode; S.cd_nsweeps = S.par.ns_coarsest; S.n_launch += 3;
+        } else { S.cd_valid = 0; S.cd_n = -1; }   // no one-workgroup kernel for this level: the sweeps
+      }
+      if (S.cd_valid && mgxk_coarse_direct_apply(S.stream, &L.v, S.cd_M, S.cd_part, S.cd_cnt, ph)) { S.n_launch++; S.n_direct++; return 0; }
+    } else S.cd_n = -1;
+  }
+  return relax(S.nlevs, S.par.ns_coarsest);
+}
+
+// mg_solvers.f90:129-151.  lead_c2f: the caller is Fcycle, whose coarse2fine(lev1) comes right before (:119-120)
+int vcycle(int lev1, bool lead_c2f) {
+  for (int lev = lev1; lev <= S.nlevs - 1; lev++) {
+    const bool lead = lead_c2f && lev == lev1;
+    if (relax_fused(lev, S.par.ns_pre, lead ? 3 : 2)) continue;
+    if (lead) CHK(coarse2fine(lev, S.exact_halos || S.keep_r, S.c2f_skip && S.method == M_FC && S.par.ns_pre >= 1));
+    CHK(relax(lev, S.par.ns_pre));
+    CHK(fine2coarse(lev, false, true));  // compute_residual(lev) + fine2coarse(lev)
+  }
+  CHK(coarsest_solve(lev1 < S.nlevs));
+  for (int lev = S.nlevs - 1; lev >= lev1; lev--) {
+    if (relax_fused(lev, S.par.ns_post, 1)) continue;
+    CHK(coarse2fine(lev, S.exact_halos || S.keep_r, S.c2f_skip && S.method == M_FC && S.par.ns_post >= 1));
+    CHK(relax(lev, S.par.ns_post));
+  }
+  return 0;
+}
+
+// mg_solvers.f90:155-177: partial V-cycle down to level lev2
+int vcycle2(int lev1, int lev2) {
+  for (int lev = lev1; lev <= lev2 - 1; lev++) {
+    CHK(relax(lev, S.par.ns_pre));
+    CHK(fine2coarse(lev, false, true));  // compute_residual(lev) + fine2coarse(lev)
+  }
+  CHK(relax(lev2, S.par.ns_coarsest));
+  for (int lev = lev2 - 1; lev >= lev1; lev--) {
+    CHK(coarse2fine(lev, S.exact_halos || S.keep_r, S.c2f_skip && S.method == M_FC && S.par.ns_post >= 1));
+    CHK(relax(lev, S.par.ns_post));
+  }
+  return 0;
+}
+
+// mg_solvers.f90:104-126
+// have_r2: grid(2)%r already holds the restriction of the level-1 residual (the closing compute_residual of the previous solve_p
+// iteration wrote it, residual_closing below): the first fine2coarse is then grid(2)%b = grid(2)%r and grid(2)%p = 0, two small copies
+// have_r2 == 2: the caller has done the whole first fine2coarse(1) itself (grid(2)%b, %r and %p are set: solve_p_krylov)
+int fcycle(int have_r2) {
+  TicScope ts(1, "Fcycle");  // mg_solvers.f90:108
+  for (int lev = 1; lev <= S.nlevs - 1; lev++) {
+    if (lev == 1 && have_r2 == 2) continue;
+    if (lev == 1 && have_r2) {
+      Level &C = S.lev[1];
+      HIPCHK(hipMemcpyAsync(C.v.b, C.v.r, C.n3js * sizeof(double), hipMemcpyDeviceToDevice, S.stream));   // physical images included (the kernel stored them)
+      HIPCHK(hipMemsetAsync(C.v.p, 0, C.n3js * sizeof(double), S.stream));
+      C.b_halo_stale = true; S.n_launch += 2;
+      continue;
+    }
+    if (lev >= 2 && S.use_chain && !S.exact_halos) {
+      // the rest of the first leg (closed, un-gathered levels: a single rank, or everything below the gathers) as ONE launch, up to four levels at a time
+      int dep = 0;
+      const LevView *vs[5] = {&S.lev[lev - 1].v, nullptr, nullptr, nullptr, nullptr};
+      bool ok = true;
+      for (int q = lev - 1; q < S.nlevs && ok; q++) { const Level &Lq = S.lev[q]; ok = all_physical(sides_of(Lq)) && (q == lev - 1 || !Lq.gather); }
+      if (ok) {
+        while (dep < 4 && lev + dep < S.nlevs) { dep++; vs[dep] = &S.lev[lev - 1 + dep].v; }
+        const Level &F = S.lev[lev - 1];
+        if (dep >= 2 && F.nx % (1 << dep) == 0 && F.ny % (1 << dep) == 0 && F.nz % (1 << dep) == 0) {
+          const Sides all = {1, 1, 1, 1};
+          mgxk_restrict_chain(S.stream, vs, dep, all); S.n_launch++;
+          lev += dep - 1;
+          continue;
+        }
+      }
+    }
+    CHK(fine2coarse(lev, true));  // + grid(lev+1)%r = grid(lev+1)%b (mg_solvers.f90:113)
+  }
+  CHK(coarsest_solve(S.nlevs >= 2));
+  for (int lev = S.nlevs - 1; lev >= 1; lev--) CHK(vcycle(lev, true));  // coarse2fine(lev) + Vcycle(lev), :119-120
+  return 0;
+}
+
+// compute_residual(1, res) at the end of a solve_p iteration (mg_solvers.f90:65).  If the loop goes on, the next thing that happens to this r
+// is Fcycle's fine2coarse(1) (:112-115): the fused residual+restriction kernel (mgx_resrest.hip) forms the norm's partial sums AND the
+// restricted r in one pass, into grid(2)%r only -- grid(2)%b and %p keep what the last cycle left, should the loop stop here.  The level-1 r
+// is NOT written; the caller materialises it after the loop.  Returns 1 = fused (grid(2)%r is ready), 0 = the caller runs residual(1).
+int residual_closing(double *res) {
+  if (!S.fuse_closing || S.nlevs < 2 || S.exact_halos || S.keep_r || S.tictoc) return 0;
+  Level &F = S.lev[0], &C = S.lev[1];
+  if (C.gather) return 0;
+  const int np = mgxk_residual_restrict_grid(&F.v, &C.v);
+  if (np > S.npartial) return 0;
+  const Sides phc = sides_of(C);
+  if (!mgxk_residual_restrict_ex(S.stream, &F.v, &C.v, C.v.r, S.real, phc, nullptr, S.d_partial, nullptr)) return 0;
+  mgxk_reduce(S.stream, S.d_partial, np, S.d_scalar); S.n_launch += 2;
+  C.r_halo_stale = true;
+  double s;
+  if (global_sum(F, &s)) return -1;
+  *res = sqrt(s);
+  return 1;
+}
+
+// Fortran's Ew.3 edit descriptor (0.dddE+ee), so that the printed history reads like the reference's (format 10, mg_solvers.f90:99)
+std::string fortran_e3(double v, int width) {
+  char buf[32];
+  if (v == 0.0 || !std::isfinite(v)) snprintf(buf, sizeof buf, v == 0.0 ? "0.000E+00" : "%f", v);
+  else {
+    const double a = fabs(v);
+    int e = (int)floor(log10(a)) + 1;
+    long m = lround(a / pow(10.0, e) * 1000.0);
+    if (m >= 1000) { m = 100; e++; }
+    if (m < 100) { m *= 10; e--; }
+    if (abs(e) < 100) snprintf(buf, sizeof buf, "%s0.%03ldE%c%02d", v < 0 ? "-" : "", m, e < 0 ? '-' : '+', abs(e));
+    else snprintf(buf, sizeof buf, "%s0.%03ld%c%03d", v < 0 ? "-" : "", m, e < 0 ? '-' : '+', abs(e));
+  }
+  std::string t(buf);
+  if ((int)t.size() < width) t.insert(0, width - t.size(), ' ');
+  return t;
+}
+
+// mg_solvers.f90:17-101
+int solve_p(double tol, int maxite, int *nite_out, double *res_out, double *hist) {
+  Level &L = S.lev[0];
+  if (S.verbose && S.rank == 0) printf(" - solve p:\n");
+  TicScope ts(1, "solve");  // mg_solvers.f90:45
+  const auto tstart = std::chrono::steady_clock::now();  // cpu_time(tstart) (:46); wall clock here, the work is on the GPU
+  if (!S.warm_start) HIPCHK(hipMemsetAsync(L.v.p, 0, L.n3js * sizeof(double), S.stream));  // grid(1)%p = 0 (:35)
+  mgxk_sumsq(S.stream, &L.v, L.v.b, S.d_partial, S.d_scalar); S.n_launch += 2;
+  double bnorm; CHK(global_sum(L, &bnorm)); bnorm = sqrt(bnorm);
+  int nite = 0;
+  double rnorm; CHK(residual(1, &rnorm));
+  double res0 = rnorm / bnorm;
+  const double rnorm0 = res0;
+  if (hist) hist[0] = res0;
+  FILE *f100 = (S.verbose && S.rank == 0) ? fopen("fort.100", "a") : nullptr;
+  if (f100) fprintf(f100, " %24.16E %d\n", res0, nite);
+  bool have_r2 = false;  // grid(2)%r = restriction of the current level-1 residual, and grid(1)%r not written (residual_closing)
+  while (nite < maxite && res0 > tol) {
+    CHK(fcycle(have_r2));
+    const int fz = residual_closing(&rnorm);
+    if (fz < 0) return 1;
+    have_r2 = fz == 1;
+    if (!fz) CHK(residual(1, &rnorm));
+    rnorm = rnorm / bnorm;
+    const double conv = res0 / rnorm;
+    res0 = rnorm;
+    nite++;
+    if (hist) hist[nite] = rnorm;
+    if (S.verbose && S.rank == 0) printf("ite = %2d: res = %s / conv = %10.3f\n", nite, fortran_e3(rnorm, 10).c_str(), conv);
+    if (f100) fprintf(f100, " %24.16E %24.16E\n", rnorm, conv);
+  }
+  if (f100) fclose(f100);
+  if (have_r2) CHK(residual(1, nullptr));  // grid(1)%r of the final iterate, which the fused closing residual did not write (once per solve)
+  if (S.verbose && S.rank == 0) {  // the summary block (mg_solvers.f90:83-97)
+    const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - tstart).count();
+    const double np = (double)L.npx * L.npy, ncell = (double)L.nx * L.npx * (double)L.ny * L.npy * (double)L.nz;
+    const double perf = dt * np / (-log(res0 / rnorm0) / log(10.0)) / ncell;
+    printf(" --- summary ---\ntime spent to solve :%8.3f s\nrescaled performance:%s\n ---------------\n", dt, fortran_e3(perf, 10).c_str());
+  }
+  if (nite_out) *nite_out = nite;
+  if (res_out) *res_out = res0;
+  return 0;
+}
+
+// ---- mixed-precision solve_p (option "cycle_precision" = 32) ------------------------------------------------------------
+// Iterative refinement around the reference's F-cycle: the fp64 loop below keeps p, r = b - A p, ||r||, the history and the stopping
+// test of solve_p (the accuracy contract is solver_prec on the fp64 relative residual, mg_solvers.f90:50-80); each iteration runs the
+// F-cycle in correction form, A e = s r from e = 0, on fp32 shadows of every level (mgx_mixed.hip) and adds e / s to p.  The cycle only
+// has to deliver a correction good to ~1e-2 of r, which fp32 does.  Single rank only: the halo and gather callbacks carry doubles.
+
+// the layout of LevView with 4-byte elements: the first interior column of either half-row 128-byte aligned
+void make_view32(LevView32 &v, int nx, int ny, int nz) {
+  v.nx = nx; v.ny = ny; v.nz = nz;
+  v.EO = 31;
+  v.HO = roundup(32 + ny / 2, 32);
+  v.RS = roundup(v.HO + ny / 2 + 1, 32);
+  v.plane = (long long)nz * v.RS;
+}
+int fmalloc(float **p, size_t n) { double *q = nullptr; CHK(dmalloc(&q, (n + 1) / 2)); *p = (float *)q; return 0; }
+
+// the combinations the fp32 cycle does not serve
+int mixed_check() {
+  if (S.nranks > 1) return fail("cycle_precision = 32 needs a single rank (process grid %d x %d): the halo and gather callbacks carry doubles", S.npx, S.npy);
+  if (S.method == M_GS) return fail("cycle_precision = 32 does not serve relax_method = 'GS' (four colours or red-black only)");
+  if (S.rb_exact) return fail("cycle_precision = 32 does not serve option rb_exact (the fp32 red-black pass is the parallel one)");
+  return 0;
+}
+
+// allocate the fp32 shadow on first use (through the allocation list: mgx_clean frees it) and convert the coefficients and pivots
+// whenever the fp64 ones have changed since the last conversion
+int mixed_prepare() {
+  if (!S.mx_ready) {
+    for (auto &L : S.lev) {
+      LevView32 &v = L.v32;
+      make_view32(v, L.nx, L.ny, L.nz);
+      L.n3js32 = (size_t)(L.nx + 2) * v.plane;
+      CHK(fmalloc(&v.e, L.n3js32)); CHK(fmalloc(&v.f, L.n3js32)); CHK(fmalloc(&v.r, L.n3js32));
+      for (int s = 0; s < 8; s++) CHK(fmalloc(&v.cA[s], L.n3js32));
+      CHK(fmalloc(&v.bet, L.n3js32));
+      v.p1 = nullptr;
+      if (S.method == M_RB && S.real) CHK(fmalloc(&v.p1, (size_t)(L.nx + 2) * v.RS));
+    }
+    S.mx_ready = true;
+    S.mx_gen = ~0ULL;
+  }
+  if (S.mx_gen != S.coef_gen) {
+    for (auto &L : S.lev) {
+      for (int s = 0; s < 8; s++) mgxx_to32(S.stream, &L.v, &L.v32, L.v.cA[s], L.v32.cA[s], 1.0);
+      mgxx_to32(S.stream, &L.v, &L.v32, L.v.bet, L.v32.bet, 1.0);   // pivots: computed in fp64 from the fp64 slots (k_pivots), rounded
+      S.n_launch += 9;
+    }
+    S.mx_gen = S.coef_gen;
+  }
+  return 0;
+}
+
+// relax(lev, nsweeps) on the fp32 shadow: four colours, or the parallel red-black pass (k = 1 same-colour diagonals from a snapshot
+// taken before each colour: the fp64 pass with rb_seq = 0)
+void relax32(int lev, int nsweeps) {
+  LevView32 &v = S.lev[lev - 1].v32;
+  for (int it = 1; it <= nsweeps; it++) {
+    if (S.method == M_FC) {
+      for (int fc1 = 1; fc1 <= 2; fc1++)
+        for (int fc2 = 1; fc2 <= 2; fc2++) { mgxx_relax_pass(S.stream, &v, fc1, 2, v.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0); S.n_launch++; }
+    } else {
+      for (int rb = 1; rb <= 2; rb++) {
+        if (S.real) { mgxx_snapshot(S.stream, &v); S.n_launch++; }
+        mgxx_relax_pass(S.stream, &v, 1, 1, v.nx, -1, rb, S.real, S.real); S.n_launch++;
+      }
+    }
+  }
+}
+void coarse2fine32(int lev) { mgxx_coarse2fine(S.stream, &S.lev[lev - 1].v32, &S.lev[lev].v32, S.linear); S.n_launch++; }
+
+// mg_solvers.f90:129-151 on the shadow; lead_c2f: Fcycle's coarse2fine(lev1) comes first (:119-120)
+void vcycle32(int lev1, bool lead_c2f) {
+  for (int lev = lev1; lev <= S.nlevs - 1; lev++) {
+    if (lead_c2f && lev == lev1) coarse2fine32(lev);
+    relax32(lev, S.par.ns_pre);
+    mgxx_resrest(S.stream, &S.lev[lev - 1].v32, &S.lev[lev].v32, S.real); S.n_launch++;   // compute_residual(lev) + fine2coarse(lev)
+  }
+  relax32(S.nlevs, S.par.ns_coarsest);
+  for (int lev = S.nlevs - 1; lev >= lev1; lev--) {
+    coarse2fine32(lev);
+    relax32(lev, S.par.ns_post);
+  }
+}
+
+// mg_solvers.f90:104-126 on the shadow, level 1 holding (e, f) = (0, s r): the first leg restricts f (the residual of e = 0)
+void fcycle32() {
+  TicScope ts(1, "Fcycle");
+  for (int lev = 1; lev <= S.nlevs - 1; lev++) {
+    mgxx_restrict(S.stream, &S.lev[lev - 1].v32, &S.lev[lev].v32, S.lev[lev - 1].v32.f); S.n_launch++;
+  }
+  relax32(S.nlevs, S.par.ns_coarsest);
+  for (int lev = S.nlevs - 1; lev >= 1; lev--) vcycle32(lev, true);
+}
+
+// solve_p with fp32 cycles: the same prints, fort.100 lines, history, warm_start handling and res0 relative to ||b|| as solve_p
+int solve_p_mixed(double tol, int maxite, int *nite_out, double *res_out, double *hist) {
+  CHK(mixed_check());
+  CHK(mixed_prepare());
+  Level &L = S.lev[0];
+  if (S.verbose && S.rank == 0) printf(" - solve p:\n");
+  TicScope ts(1, "solve");
+  const auto tstart = std::chrono::steady_clock::now();
+  if (!S.warm_start) HIPCHK(hipMemsetAsync(L.v.p, 0, L.n3js * sizeof(double), S.stream));
+  mgxk_sumsq(S.stream, &L.v, L.v.b, S.d_partial, S.d_scalar); S.n_launch += 2;
+  double bnorm; CHK(global_sum(L, &bnorm)); bnorm = sqrt(bnorm);
+  int nite = 0;
+  double rabs; CHK(residual(1, &rabs));   // fp64 r = b - A p, written into grid(1)%r
+  double res0 = rabs / bnorm, rnorm = res0;
+  const double rnorm0 = res0;
+  if (hist) hist[0] = res0;
+  FILE *f100 = (S.verbose && S.rank == 0) ? fopen("fort.100", "a") : nullptr;
+  if (f100) fprintf(f100, " %24.16E %d\n", res0, nite);
+  while (nite < maxite && res0 > tol) {
+    // f = s r with s = 1 / ||r||: |f| <= 1, nothing underflows however small the residual has become; e = 0
+    const double sc = rabs > 0.0 ? 1.0 / rabs : 1.0;
+    mgxx_to32(S.stream, &L.v, &L.v32, L.v.r, L.v32.f, sc); S.n_launch++;
+    HIPCHK(hipMemsetAsync(L.v32.e, 0, L.n3js32 * sizeof(float), S.stream));
+    fcycle32();
+    mgxx_to64(S.stream, &L.v, &L.v32, L.v32.e, L.v.p, rabs > 0.0 ? rabs : 1.0, 1); S.n_launch++;   // p += e / s, halo images included
+    CHK(residual(1, &rabs));
+    rnorm = rabs / bnorm;
+    const double conv = res0 / rnorm;
+    res0 = rnorm;
+    nite++;
+    S.n_mixed++;
+    if (hist) hist[nite] = rnorm;
+    if (S.verbose && S.rank == 0) printf("ite = %2d: res = %s / conv = %10.3f\n", nite, fortran_e3(rnorm, 10).c_str(), conv);
+    if (f100) fprintf(f100, " %24.16E %24.16E\n", rnorm, conv);
+  }
+  if (f100) fclose(f100);
+  if (S.verbose && S.rank == 0) {
+    const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - tstart).count();
+    const double np = (double)L.npx * L.npy, ncell = (double)L.nx * L.npx * (double)L.ny * L.npy * (double)L.nz;
+    const double perf = dt * np / (-log(res0 / rnorm0) / log(10.0)) / ncell;
+    printf(" --- summary ---\ntime spent to solve :%8.3f s\nrescaled performance:%s\n ---------------\n", dt, fortran_e3(perf, 10).c_str());
+  }
+  if (nite_out) *nite_out = nite;
+  if (res_out) *res_out = res0;
+  return 0;
+}
+
+// ---- Krylov-accelerated solve_p (option "krylov" = m) -------------------------------------------------------------------
+// Right-preconditioned truncated GCR (Orthomin(m)) with M = one Fcycle from p = 0 on the right-hand side r: a fixed linear map, not a
+// symmetric one (3 pre / 2 post coloured sweeps), hence GCR and not CG.  Per iteration: z = M r, q = A z, (z, q) made A^T A-orthogonal to
+// the m retained pairs, p += (t / s) z, r -= (t / s) q with s = (q, q), t = (r, q).  The F-cycle reads level 1 through its view, so the
+// view's p / b / r are pointed at (z, r, scratch) for the cycle and back afterwards: nothing is copied.  r of the recurrence lives in
+// grid(1)%r; the scratch r of the cycle is the q of the pair in work, which is only written after the cycle.
+// The recurrence's r drifts away from b - A p near round-off, so no convergence is reported on its word: the true residual is computed
+// (compute_residual(1)) before the loop is left, and where it is not below tol it becomes r, the retained pairs are dropped
+// (kr_restarts) and the loop goes on.  On every exit grid(1)%r, *res and the last hist entry are the true residual's.
+struct ViewSwap {   // level 1's p / b / r as the solver owns them, put back on every way out
+  LevView &v; double *p, *b, *r;
+  explicit ViewSwap(LevView &w) : v(w), p(w.p), b(w.b), r(w.r) {}
+  void restore() { v.p = p; v.b = b; v.r = r; }
+  ~ViewSwap() { restore(); }
+};
+
+int krylov_prepare(int m) {
+  Level &L = S.lev[0];
+  if (!S.kr_sc) { CHK(dmalloc(&S.kr_sc, 32)); CHK(dmalloc(&S.kr_partial, (size_t)mgxq_partials(&L.v))); }
+  for (; S.kr_n < m + 1; S.kr_n++) { CHK(dmalloc(&S.kr_z[S.kr_n], L.n3js)); CHK(dmalloc(&S.kr_q[S.kr_n], L.n3js)); }
+  return 0;
+}
+
+// the inner products of one pass summed over the ranks: ONE call of the all-reduce hook
+int krylov_allreduce(double *buf, int n) {
+  if (S.nranks <= 1 || n == 0) return 0;
+  if (!S.ar) return fail("an all-reduce is needed (npx*npy > 1) but mgx_set_comm was not called");
+  S.n_allred++;
+  if (S.ar(S.ctx, buf, n)) return fail("allreduce callback failed");
+  return 0;
+}
+
+int solve_p_krylov(double tol, int maxite, int *nite_out, double *res_out, double *hist) {
+  const int m = S.krylov;
+  CHK(krylov_prepare(m));
+  Level &L = S.lev[0];
+  if (S.verbose && S.rank == 0) printf(" - solve p:\n");
+  TicScope ts(1, "solve");
+  const auto tstart = std::chrono::steady_clock::now();
+  if (!S.warm_start) HIPCHK(hipMemsetAsync(L.v.p, 0, L.n3js * sizeof(double), S.stream));
+  mgxk_sumsq(S.stream, &L.v, L.v.b, S.d_partial, S.d_scalar); S.n_launch += 2;
+  double bnorm; CHK(global_sum(L, &bnorm)); bnorm = sqrt(bnorm);
+  int nite = 0;
+  double rnorm; CHK(residual(1, &rnorm));   // the true residual, into grid(1)%r
+  double res0 = rnorm / bnorm;
+  const double rnorm0 = res0;
+  if (hist) hist[0] = res0;
+  struct F100 { FILE *f; ~F100() { if (f) fclose(f); } } f100 = {(S.verbose && S.rank == 0) ? fopen("fort.100", "a") : nullptr};
+  if (f100.f) fprintf(f100.f, " %24.16E %d\n", res0, nite);
+  ViewSwap own(L.v);
+  double *sc = S.kr_sc, *qq = S.kr_sc + 16;
+  int kept = 0, head = 0;   // retained pairs: the `kept` slots before `head` in the ring of m + 1; head = the pair in work
+  bool fresh = true, broke = false;   // fresh: grid(1)%r is the true residual of grid(1)%p
+  S.kr_restarts = 0;
+  for (;;) {
+    while (nite < maxite && res0 > tol) {
+      double *z = S.kr_z[head], *q = S.kr_q[head];
+      {  // z = M r: Fcycle on (p, b) = (0, r).  The first leg restricts the view's r, the rest of the cycle may use it as scratch.
+        HIPCHK(hipMemsetAsync(z, 0, L.n3js * sizeof(double), S.stream));
+        L.v.p = z; L.v.b = own.r; L.v.r = own.r;
+        int rc = S.nlevs >= 2 ? fine2coarse(1, true) : 0;
+        L.v.r = q;
+        if (!rc) rc = fcycle(2);
+        own.restore();
+        if (rc) return rc;
+      }
+      const double *zi[8], *qi[8]; int slot[8];
+      for (int n = 0; n < kept; n++) { slot[n] = (head + m + 1 - kept + n) % (m + 1); zi[n] = S.kr_z[slot[n]]; qi[n] = S.kr_q[slot[n]]; }
+      {
+        TicScope t1(1, "krylov_apply");
+        LevView zv = L.v; zv.p = z;
+        mgxq_apply(S.stream, &zv, q, qi, kept, S.kr_partial, sc, S.real); S.n_launch += kept ? 2 : 1;
+        CHK(krylov_allreduce(sc, kept));
+      }
+      {
+        TicScope t2(1, "krylov_ortho");
+        mgxq_ortho(S.stream, &L.v, z, q, own.r, zi, qi, slot, kept, sc, qq, S.kr_partial, sc + 8); S.n_launch += 2;
+        CHK(krylov_allreduce(sc + 8, 2));
+      }
+      double s2;
+      {
+        TicScope t3(1, "krylov_update");
+        mgxq_update(S.stream, &L.v, own.p, own.r, z, q, sc + 8, qq + head, S.kr_partial, S.d_scalar); S.n_launch += 2;
+        CHK(global_sum(L, &s2));   // the iteration's one host synchronisation: the stopping test
+      }
+      fresh = false;
+      if (!(s2 >= 0.0)) { broke = true; break; }   // no step was taken (s == 0 or a non-finite scalar): p is what it was
+      rnorm = sqrt(s2) / bnorm;
+      const double conv = res0 / rnorm;
+      res0 = rnorm;
+      nite++;
+      if (hist) hist[nite] = rnorm;
+      if (S.verbose && S.rank == 0) printf("ite = %2d: res = %s / conv = %10.3f\n", nite, fortran_e3(rnorm, 10).c_str(), conv);
+      if (f100.f) fprintf(f100.f, " %24.16E %24.16E\n", rnorm, conv);
+      if (kept < m) kept++;
+      head = (head + 1) % (m + 1);
+    }
+    if (fresh) break;
+    CHK(residual(1, &rnorm));   // b - A p into grid(1)%r: the word that counts
+    fresh = true;
+    res0 = rnorm / bnorm;
+    if (hist) hist[nite] = res0;
+    if (broke || nite >= maxite || !(res0 > tol)) break;
+    S.kr_restarts++; kept = 0;   // the recurrence had drifted: go on from the true residual with no history
+  }
+  if (S.verbose && S.rank == 0) {
+    const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - tstart).count();
+    const double np = (double)L.npx * L.npy, ncell = (double)L.nx * L.npx * (double)L.ny * L.npy * (double)L.nz;
+    const double perf = dt * np / (-log(res0 / rnorm0) / log(10.0)) / ncell;
+    printf(" --- summary ---\ntime spent to solve :%8.3f s\nrescaled performance:%s\n ---------------\n", dt, fortran_e3(perf, 10).c_str());
+  }
+  if (nite_out) *nite_out = nite;
+  if (res_out) *res_out = res0;
+  return 0;
+}
+
+// the solve_p of mgx_solve_p / mgx_solve / mgx_solve_device: fp64 cycles, fp32 cycles under fp64 refinement, or the Krylov-accelerated loop
+int solve_p_opt(double tol, int maxite, int *nite_out, double *res_out, double *hist) {
+  if (S.krylov > 0 && S.cycle_precision == 32)
+    return fail("options \"krylov\" = %d and \"cycle_precision\" = 32 cannot be combined (fp32 cycles under the Krylov loop are not served): set one of them back", S.krylov);
+  if (S.krylov > 0) return solve_p_krylov(tol, maxite, nite_out, res_out, hist);
+  return S.cycle_precision == 32 ? solve_p_mixed(tol, maxite, nite_out, res_out, hist) : solve_p(tol, maxite, nite_out, res_out, hist);
+}
+
+}  // namespace mgx_host

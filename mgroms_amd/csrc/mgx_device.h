@@ -1,4 +1,4 @@
-// Device helpers shared by the HIP translation units of libmgx.so (mgx_relax.hip, mgx_kernels.hip).
+// Device helpers shared by the HIP translation units of libmgx.so.
 #pragma once
 #include "mgx_internal.h"
 
@@ -32,11 +32,11 @@ __device__ __forceinline__ void mirror_store(const LevView &L, double *__restric
 
 // A rejected launch (more LDS or registers than this ROCm / device grants) must not pass for a completed colour pass: wrappers that
 // have a generic fallback end in `return mgx_launched();` -- 0 = the launch was refused, nothing ran, the caller falls back; whatever
-// has no fallback is caught by the sticky-error check of the next synchronising call (sync_stream in mgx_api.cpp).
+// has no fallback is caught by the sticky-error check of the next synchronising call (sync_stream in mgx_comm.cpp).
 // hipGetLastError() is sticky per thread for ANY earlier HIP call (an ignored attribute call, the caller's own runtime use): a wrapper that
 // ends in mgx_launched() starts with mgx_before_launch(), which moves whatever is pending into mgx_pending_error (reported by the next
 // synchronising call) so that mgx_launched() sees the status of THIS launch only.
-extern thread_local hipError_t mgx_pending_error;  // mgx_api.cpp
+extern thread_local hipError_t mgx_pending_error;  // mgx_comm.cpp
 static inline void mgx_before_launch() { const hipError_t e = hipGetLastError(); if (e != hipSuccess && mgx_pending_error == hipSuccess) mgx_pending_error = e; }
 static inline int mgx_launched() { return hipGetLastError() == hipSuccess ? 1 : 0; }
 

@@ -1,4 +1,4 @@
-// Internal declarations shared by the HIP translation units of libmgx.so.
+// Internal declarations shared by every translation unit of libmgx.so, device and host: the views a kernel takes and (mgx_wrappers.h) the kernel wrappers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -57,7 +57,7 @@ struct GeoView {
 };
 
 // physical-boundary flags of a sub-domain (1 = no neighbour on that side)
-// part (colour passes of a level with neighbours, mgx_api.cpp relax()): 0 = every column of the colour; 1 = only the waves that hold a
+// part (colour passes of a level with neighbours, mgx_cycle.cpp relax()): 0 = every column of the colour; 1 = only the waves that hold a
 // column next to a NEIGHBOUR's halo (plane 1 / nx, first / last j-chunk on an open side): the columns the next exchange sends and the only
 // ones that read what the last exchange delivered; 2 = all the others.  The two parts run on two streams, the exchange behind part 1.
 struct Sides { int S, E, N, W; int part; };
@@ -82,3 +82,6 @@ struct LevView32 {
 };
 
 __host__ __device__ inline int jpos32(const LevView32 &L, int j) { return (j & 1) ? L.HO + (j >> 1) : L.EO + (j >> 1); }
+
+// the kernel wrappers: one prototype each, seen by the file that defines a wrapper and by every file that calls it
+#include "mgx_wrappers.h"

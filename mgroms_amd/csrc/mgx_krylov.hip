@@ -1,4 +1,4 @@
-// Kernels of the Krylov-accelerated solve_p (option "krylov" = m, mgx_api.cpp: solve_p_krylov) for gfx950 (MI355X): truncated GCR /
+// Kernels of the Krylov-accelerated solve_p (option "krylov" = m, mgx_cycle.cpp: solve_p_krylov) for gfx950 (MI355X): truncated GCR /
 // Orthomin(m) around the F-cycle.  Three launches per iteration on level 1, each followed by a one-launch reduction of its per-workgroup
 // partial sums in index order (the order of k_reduce_partials, mgx_kernels.hip): a solve is reproducible run to run.
 //   1. k_kr_apply[_mf]: q = A z and the inner products (q, q_i) with the retained q_i

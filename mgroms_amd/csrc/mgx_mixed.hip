@@ -1,5 +1,5 @@
 // fp32 kernels of the mixed-precision solve_p (option "cycle_precision" = 32, include/mgx.h).  The fp64 outer loop of
-// mgx_api.cpp (solve_p_mixed) keeps the iterate, the residual, its norm and the stopping test; each iteration runs the
+// mgx_cycle.cpp (solve_p_mixed) keeps the iterate, the residual, its norm and the stopping test; each iteration runs the
 // reference's F-cycle in correction form, A e = s r with e = 0 on entry, on fp32 shadows of every level (LevView32,
 // mgx_internal.h), and adds e / s to p.  Hand-written, fp32, single rank (every side of every level physical).
 //

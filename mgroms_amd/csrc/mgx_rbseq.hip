@@ -856,7 +856,7 @@ int mgxk_rbseq_walk_apply(hipStream_t st, const LevView *L, int rb, Sides ph, in
   return mgx_launched();
 }
 
-// rho of the level into *out (device memory, zero before the first call; mgx_api.cpp reads it back with the set-up's own synchronisation)
+// rho of the level into *out (device memory, zero before the first call; define_matrices in mgx_define.cpp reads it back with the set-up's own synchronisation)
 void mgxk_rbseq_rho(hipStream_t st, const LevView *L, double *out) {
   hipLaunchKernelGGL(k_rbseq_rho, dim3((L->ny + 63) / 64, (L->nx + 3) / 4), dim3(64, 4), 0, st, *L, (unsigned long long *)out);
 }

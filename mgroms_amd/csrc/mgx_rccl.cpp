@@ -20,6 +20,7 @@
 #include <rccl.h>
 
 #include "../../include/mgx.h"
+#include "mgx_internal.h"
 
 namespace {
 

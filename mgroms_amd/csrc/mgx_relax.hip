@@ -797,7 +797,6 @@ int mgxk_relax_gs_sweep(hipStream_t st, const LevView *L, int real) {
 }
 
 // one-launch relax of a small level; returns 0 if the level does not qualify
-int mgxk_relax_wave(hipStream_t, const LevView *, int, int, int, Sides, int);  // mgx_relax_coarse.hip
 // mode (red-black with cmatrix='real'): 0 = parallel colour passes (snapshot), 1 = the reference's plane loop bit for bit (rb_exact), 2 = the
 // same order by the walk of mgx_rbseq.hip where a kernel has it (k_relax_wave), else the plane loop
 int mgxk_relax_small(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode) {
@@ -856,8 +855,6 @@ int mgxk_relax_small(hipStream_t st, const LevView *L, int nsweeps, int method, 
 }
 
 // returns 1 when the launched kernel also wrote the physical-boundary mirrors of p (no k_halo_phys needed)
-int mgxk_relax_ks(hipStream_t, const LevView *, int, int, int, int, int, int, int, Sides);  // mgx_relax_ks.hip
-int mgxk_relax_tall(hipStream_t, const LevView *, int, int, int, int, int, int, int, Sides);  // mgx_relax_tall.hip
 // returns bit 0: the kernel stored the physical mirrors itself; bit 1: it wrote L->d0w
 int mgxk_relax_colour(hipStream_t st, const LevView *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, Sides ph) {
   if (const int ks = mgxk_relax_ks(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph)) return ks;  // mid levels: rows split over the waves of a workgroup

@@ -76,7 +76,6 @@ __global__ void k_coarsen2d(const double *__restrict__ src, double *__restrict__
 //   op 1: a(dst) = 2*a(src) - a(src2)        (nh=2 extrapolation, mg_mpi_exchange.f90:956-964)
 //   op 2: a(dst) = 0
 //   op 3: buf = a(dst rect)  (pack)          op 4: a(dst rect) = buf (unpack); buffer order (k fastest, then j, then i)
-struct RectOp { int op, nzz, nh, ny, j0, j1, i0, i1, mj, cj, mi, ci, mj2, cj2, mi2, ci2; };
 __global__ void k_rect(double *__restrict__ a, double *__restrict__ buf, RectOp R) {
   const long long nj = R.j1 - R.j0 + 1, ni = R.i1 - R.i0 + 1, n = nj * ni * R.nzz;
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;

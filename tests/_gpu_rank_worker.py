@@ -152,7 +152,7 @@ def main():
     assert c["exchanges"] > 0 and c["allreduces"] > 0  # the set-up halos always use the callback
     if method == "FC" and p2p and not connectfail and not bmask and not overlap0:
         # the colour passes of the levels with neighbours ran in two parts on two streams, the exchange beside the interior part
-        # (mgx_api.cpp relax()); the bits above are the oracle's, and the re-run through the hooks below (one stream) repeats them
+        # (mgx_cycle.cpp relax()); the bits above are the oracle's, and the re-run through the hooks below (one stream) repeats them
         assert nhydro.get_option("overlap") == 1 and nhydro.get_option("overlapped_passes") > 0, rank
     if connectfail:
         assert comm.p2p_active is False and comm.p2p_error, (rank, comm.p2p_error)

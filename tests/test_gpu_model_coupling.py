@@ -1,4 +1,4 @@
-"""The model coupling of nhydro_solve -- compute_rhs and correct_uvw on the model's own u, v, w (mgx_model.hip, mgx_api.cpp) --
+"""The model coupling of nhydro_solve -- compute_rhs and correct_uvw on the model's own u, v, w (mgx_model.hip, mgx_define.cpp) --
 against the CPU oracle, bit for bit, at the shapes and run layouts a model uses.
 
 The model kernels run one lane per (i,j) column and climb a run of rows in k, carrying row k+1 to the next step in registers; each

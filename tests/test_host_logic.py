@@ -44,6 +44,25 @@ def test_documented_options_exist(built):
         assert L.mgx_get_option(n.encode(), ctypes.byref(v)) == 0 and v.value == d, (n, v.value)
 
 
+def test_options_surface_matches_record(built):
+    """The whole option surface, replayed against tests/golden/options_surface.json -- the answers of the library as it was when
+    mgx_set_option and mgx_get_option were two if/else chains and mgx_clean carried its options by hand: for every name either chain knew
+    (the three write-only *_timeout_ms device constants apart) whether mgx_get_option knows it and its default, whether mgx_set_option
+    takes a legal non-default value and what reads back, what reads back after a following mgx_clean (carried, or the default again),
+    and the texts of the errors (an illegal cycle_precision / krylov, p2p without prepare, a read-only name, an unknown name).  No GPU
+    needed: options are plain state.  In a process of its own (tests/_options_surface_worker.py, which also puts every option back)."""
+    import json, subprocess
+    with open(os.path.join(ROOT, "tests", "golden", "options_surface.json")) as f:
+        want = json.load(f)["surface"]
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_options_surface_worker.py"), "surface"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-2000:])
+    got = json.loads(out.stdout)
+    assert set(got["options"]) == set(want["options"])
+    for name, w in want["options"].items():
+        assert got["options"][name] == w, (name, got["options"][name], w)
+    assert got["errors"] == want["errors"]
+
+
 @pytest.mark.parametrize("cfg", [(64, 64, 16, 1, 1, 8), (32, 32, 16, 2, 2, 8), (512, 512, 64, 1, 1, 8), (64, 32, 32, 4, 2, 8),
                                  (512, 512, 64, 2, 2, 8), (512, 1024, 128, 4, 2, 16), (128, 128, 64, 4, 2, 64), (16, 16, 8, 2, 1, 8),
                                  (16, 16, 8, 1, 2, 8), (32, 64, 8, 4, 4, 16)])
