@@ -16,8 +16,49 @@ __device__ __forceinline__ void st_rt(double *p, double v, int nt) { if (nt) __b
 __device__ __forceinline__ double ld_rt(const double *p, int nt) { return nt ? __builtin_nontemporal_load(p) : *p; }
 static inline int level_streams(const LevView *L) { return (double)L->nx * L->ny * L->nz * 72.0 > 256e6; }
 
-// store the physical-boundary images of an interior value (homogeneous Neumann mirror incl. the corner where two
-// physical sides meet, mg_mpi_exchange.f90:509-537,552-597): lets the producing kernel fill its own halo
+// positions c, jm, jp of columns j, j-1, j+1 inside a row of the JS layout (mgx_internal.h): j = 2 jh + 1 (jodd) or 2 jh + 2
+#define COL_POS(L, jh, jodd, c, jm, jp)                                 \
+  {                                                                     \
+    if (jodd) { c = L.HO + jh; jm = L.EO + jh; jp = jm + 1; }           \
+    else      { c = L.EO + jh + 1; jm = L.HO + jh; jp = jm + 1; }       \
+  }
+
+// The physical-boundary images of column (j, i): homogeneous Neumann mirror incl. the corner where two physical sides meet
+// (mg_mpi_exchange.f90:509-537,552-597).  The lane that owns a column stores them with it, which removes the halo kernel after a
+// pass.  COL_IMAGES declares which images the column has and where they sit; COL_STORE and COL_SNAPSHOT use them.  Macros, like
+// the column pass of mgx_relax_common.h and for its reason: as forceinline functions over a struct they moved the register
+// allocation of their callers (profiles/relax_mf_single_source_isa.json, "function_form_rejected", has the figures).
+#define COL_IMAGES(L, i, j, ph)                                                                                              \
+  const bool mS = ph.S && j == 1, mN = ph.N && j == L.ny, mW = ph.W && i == 1, mE = ph.E && i == L.nx;                       \
+  const int cS = L.EO, cN = jpos(L, L.ny + 1);                                                                               \
+  const long long oW = 0, oE = (long long)(L.nx + 1) * L.plane;
+// row ro of the column in p (plane offset o) with its images; ST: the column's own cell with the non-temporal hint
+#define COL_STORE(ST, p, o, ro, c, v)                                                                                        \
+  {                                                                                                                          \
+    if (ST) NT2_STORE(v, p + o + ro + c); else p[o + ro + c] = v;                                                            \
+    if (mS) p[o + ro + cS] = v;                                                                                              \
+    if (mN) p[o + ro + cN] = v;                                                                                              \
+    if (mW) { p[oW + ro + c] = v; if (mS) p[oW + ro + cS] = v; if (mN) p[oW + ro + cN] = v; }                                \
+    if (mE) { p[oE + ro + c] = v; if (mS) p[oE + ro + cS] = v; if (mN) p[oE + ro + cN] = v; }                                \
+  }
+// next sweep's k=1 snapshot entry of this column (and its physical mirrors): no snapshot launch per pass.
+// A mirrored halo cell is read (as a k=1 diagonal) only by columns of the OTHER colour, i.e. by the next pass of this
+// same sweep, which must see it updated: mirrors go to the buffer being read as well (no column of this pass reads them,
+// except a corner column its own corner, after which it is the one to overwrite it).
+#define SNAP_MIRROR(idx) { w1[idx] = v1; r1[idx] = v1; }
+#define COL_SNAPSHOT(L, RS, i, c, v)                                                                                          \
+  {                                                                                                                          \
+    double *w1 = L.p1w, *r1 = L.p1;                                                                                          \
+    const long long so = (long long)i * RS, sW = 0, sE = (long long)(L.nx + 1) * RS;                                  \
+    const double v1 = v;                                                                                                     \
+    w1[so + c] = v1;                                                                                                         \
+    if (mS) SNAP_MIRROR(so + cS)                                                                                             \
+    if (mN) SNAP_MIRROR(so + cN)                                                                                             \
+    if (mW) { SNAP_MIRROR(sW + c) if (mS) SNAP_MIRROR(sW + cS) if (mN) SNAP_MIRROR(sW + cN) }                                \
+    if (mE) { SNAP_MIRROR(sE + c) if (mS) SNAP_MIRROR(sE + cS) if (mN) SNAP_MIRROR(sE + cN) }                                \
+  }
+
+// the images alone of a value that a kernel outside the smoother has just stored at a[i * plane + ro + c]
 __device__ __forceinline__ void mirror_store(const LevView &L, double *__restrict__ a, const long long ro, const int j, const int i,
                                              const int c, const double v, const Sides ph) {
   const bool mS = ph.S && j == 1, mN = ph.N && j == L.ny, mW = ph.W && i == 1, mE = ph.E && i == L.nx;
@@ -42,30 +83,7 @@ static inline int mgx_launched() { return hipGetLastError() == hipSuccess ? 1 : 
 
 static inline dim3 col_grid(int ncol_half, int nplanes, int z = 1) { return dim3((ncol_half + WAVE - 1) / WAVE, (nplanes + 3) / 4, z); }
 
-// ---- switches and helpers shared by the smoother translation units ---------------------------------------------------
-// MGX_PV: the matrix-free colour pass rebuilds the diagonal and the tridiagonal pivots in the kernel instead of streaming
-// `bet` from HBM (relax_col_mf); -DMGX_NO_PV keeps the stored pivots for A/B measurements (same bits either way).
-#ifdef MGX_NO_PV
-#define MGX_PV 0
-#else
-#define MGX_PV 1
-#endif
-#ifndef MGX_GL
-#define MGX_GL 1
-#endif
-// The j-1 and j+1 neighbours of a column sit side by side in the other half-row (jp = jm + 1): ONE 16-byte load per lane fetches
-// both, instead of two 8-byte loads whose wave-wide footprints overlap by 63/64 (half the wave-level requests for these streams;
-// 8-byte alignment only: gfx950 global loads do not need natural alignment)
-#ifndef MGX_PAIR
-#define MGX_PAIR 1
-#endif
-#ifndef MGX_ZW
-#define MGX_ZW 1
-#endif
-// MGX_ZG: with MGX_ZW, the column's own slopes zy, zx are rebuilt in the kernel as well (relax_col_mf); -DMGX_ZG=0 streams them (A/B)
-#ifndef MGX_ZG
-#define MGX_ZG 1
-#endif
+// ---- helpers shared by the smoother translation units ---------------------------------------------------------------
 // A quotient whose divisor is a per-column constant: the divisor's reciprocal is refined once with the two Newton steps of the hardware
 // division sequence (v_rcp_f64, fma, fma, fma, fma) and each quotient then takes the sequence's last three operations (mul, fma, fma) --
 // the same operations on the same values as `/` while no operand needs v_div_scale's rescaling (depths, metric factors: normal range),
@@ -73,11 +91,10 @@ static inline dim3 col_grid(int ncol_half, int nplanes, int z = 1) { return dim3
 #define RCP_REF(b) ({ const double b_ = (b); double r_ = __builtin_amdgcn_rcp(b_); double e_ = __builtin_fma(-b_, r_, 1.0); r_ = __builtin_fma(r_, e_, r_); \
                       e_ = __builtin_fma(-b_, r_, 1.0); __builtin_fma(r_, e_, r_); })
 #define DIVC(a, b, rb) ({ const double a_ = (a); const double q_ = a_ * (rb); const double e_ = __builtin_fma(-(b), q_, a_); __builtin_fma(e_, (rb), q_); })
-#if MGX_PAIR
+// The j-1 and j+1 neighbours of a column sit side by side in the other half-row (jp = jm + 1): ONE 16-byte load per lane fetches
+// both, instead of two 8-byte loads whose wave-wide footprints overlap by 63/64 (half the wave-level requests for these streams;
+// 8-byte alignment only: gfx950 global loads do not need natural alignment)
 #define LD_PAIR(ptr, A, B) { double2 t2_; __builtin_memcpy(&t2_, (ptr), 16); A = t2_.x; B = t2_.y; }
-#else
-#define LD_PAIR(ptr, A, B) { A = (ptr)[0]; B = (ptr)[1]; }
-#endif
 
 // the value of the neighbouring lane across the whole wave (DPP wave shifts of gfx9: one v_mov_b32_dpp per half, no LDS)
 __device__ __forceinline__ double wave_shr1(double x) {  // lane n takes lane n-1's value, lane 0 takes 0

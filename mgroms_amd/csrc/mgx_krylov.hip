@@ -56,8 +56,7 @@ __global__ __launch_bounds__(256) void k_kr_apply(LevView L, double *__restrict_
   double acc[KR_MAX] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (jh < (L.ny >> 1) && i <= L.nx) {
     int c, jm, jp;
-    if (jodd) { c = L.HO + jh; jm = L.EO + jh; jp = jm + 1; }
-    else      { c = L.EO + jh + 1; jm = L.HO + jh; jp = jm + 1; }
+    COL_POS(L, jh, jodd, c, jm, jp)
     const long long RS = L.RS;
     const int nz = L.nz;
     const double *__restrict__ p = L.p;
@@ -122,8 +121,7 @@ __global__ __launch_bounds__(256) void k_kr_apply_mf(LevView L, double *__restri
   double acc[KR_MAX] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (jh < (L.ny >> 1) && i <= L.nx) {
     int c, jm, jp;
-    if (jodd) { c = L.HO + jh; jm = L.EO + jh; jp = jm + 1; }
-    else      { c = L.EO + jh + 1; jm = L.HO + jh; jp = jm + 1; }
+    COL_POS(L, jh, jodd, c, jm, jp)
     const long long RS = L.RS;
     const int nz = L.nz;
     const double *__restrict__ p = L.p;

@@ -8,7 +8,7 @@
 // the JS layout (mgx_internal.h), so every global access of a wave is one contiguous 512-byte run.
 #include <cstdlib>
 
-#include "mgx_device.h"
+#include "mgx_relax_common.h"
 
 // ------------------------------------------------------------------------------------------------
 // z-line smoother, one colour pass.  mg_relax.f90:237-305 (relax_3D_8_heart) + :308-334 (tridiag).
@@ -20,8 +20,7 @@
 template <bool REAL, bool SNAP>
 __device__ __forceinline__ void relax_col_any(const LevView &L, const int i, const int jh, const int jodd) {
   int c, jm, jp;  // positions of columns j, j-1, j+1 inside a row
-  if (jodd) { c = L.HO + jh; jm = L.EO + jh; jp = jm + 1; }
-  else      { c = L.EO + jh + 1; jm = L.HO + jh; jp = jm + 1; }
+  COL_POS(L, jh, jodd, c, jm, jp)
   const long long RS = L.RS;
   const int nz = L.nz;
   double *__restrict__ p = L.p;
@@ -116,8 +115,7 @@ __global__ __launch_bounds__(256) void k_relax_colour(LevView L, int i0, int ist
 template <int NZ, bool REAL, bool SNAP, int D>
 __device__ __forceinline__ void relax_col_nz(const LevView &L, const int i, const int jh, const int jodd, const Sides ph) {
   int c, jm, jp;
-  if (jodd) { c = L.HO + jh; jm = L.EO + jh; jp = jm + 1; }
-  else      { c = L.EO + jh + 1; jm = L.HO + jh; jp = jm + 1; }
+  COL_POS(L, jh, jodd, c, jm, jp)
   const long long RS = L.RS;
   double *__restrict__ p = L.p;
   const double *__restrict__ b = L.b;
@@ -205,284 +203,61 @@ __device__ __forceinline__ void relax_col_nz(const LevView &L, const int i, cons
   for (int k = NZ - 1; k >= 1; k--) x[k - 1] = x[k - 1] - g[k] * x[k];
 
   const int j = jodd ? 2 * jh + 1 : 2 * jh + 2;
-  const bool mS = ph.S && j == 1, mN = ph.N && j == L.ny, mW = ph.W && i == 1, mE = ph.E && i == L.nx;
-  const int cS = L.EO, cN = jpos(L, L.ny + 1);
-  const long long oW = 0, oE = (long long)(L.nx + 1) * L.plane;
+  COL_IMAGES(L, i, j, ph)
 #pragma unroll
   for (int k = 1; k <= NZ; k++) {
     const long long ro = (long long)(k - 1) * RS;
     const double v = x[k - 1];
-    p[o + ro + c] = v;
-    if (mS) p[o + ro + cS] = v;
-    if (mN) p[o + ro + cN] = v;
-    if (mW) { p[oW + ro + c] = v; if (mS) p[oW + ro + cS] = v; if (mN) p[oW + ro + cN] = v; }
-    if (mE) { p[oE + ro + c] = v; if (mS) p[oE + ro + cS] = v; if (mN) p[oE + ro + cN] = v; }
+    COL_STORE(false, p, o, ro, c, v)
   }
   if (SNAP && L.d0w != nullptr) L.d0w[(long long)i * RS + c] = x[0] - L.p1[(long long)i * RS + c];  // mgx_rbseq.hip (b): d0, what k_rbseq_d0 would compute from the stored y
-  if (SNAP && L.p1w != nullptr) {  // next sweep's k=1 snapshot entry of this column (and its physical mirrors): no snapshot launch per pass
-    // A mirrored halo cell is read (as a k=1 diagonal) only by columns of the OTHER colour, i.e. by the next pass of this
-    // same sweep, which must see it updated: mirrors go to the buffer being read as well (no column of this pass reads them,
-    // except a corner column its own corner, after which it is the one to overwrite it).
-    double *w1 = L.p1w, *r1 = L.p1;
-    const long long so = (long long)i * RS, sW = 0, sE = (long long)(L.nx + 1) * RS;
-    const double v1 = x[0];
-    w1[so + c] = v1;
-#define SNAP_MIRROR(idx) { w1[idx] = v1; r1[idx] = v1; }
-    if (mS) SNAP_MIRROR(so + cS)
-    if (mN) SNAP_MIRROR(so + cN)
-    if (mW) { SNAP_MIRROR(sW + c) if (mS) SNAP_MIRROR(sW + cS) if (mN) SNAP_MIRROR(sW + cN) }
-    if (mE) { SNAP_MIRROR(sE + c) if (mS) SNAP_MIRROR(sE + cS) if (mN) SNAP_MIRROR(sE + cN) }
-#undef SNAP_MIRROR
-  }
+  if (SNAP && L.p1w != nullptr) COL_SNAPSHOT(L, RS, i, c, x[0])
 #undef NB_LOAD
 #undef OW_LOAD
 #undef NB_USE
 }
 
 // ------------------------------------------------------------------------------------------------
-// Matrix-free cross terms.  Away from the special k=1 diagonals, slots 3,5,6,8 are sums of two slope values:
-//   cA3(k,j,i) =  qrt*(ZY(k+1,j,i) + ZY(k,j-1,i))     cA5(k,j,i) = -qrt*(ZY(k-1,j,i) + ZY(k,j-1,i))
-//   cA6(k,j,i) =  qrt*(ZX(k+1,j,i) + ZX(k,j,i-1))     cA8(k,j,i) = -qrt*(ZX(k-1,j,i) + ZX(k,j,i-1))
-// (mg_define_matrix.f90:357-359,397-399,519-555,584-606) with ZY = ((hlf*(zr(k,j+1,i)-zr(k,j-1,i)))/dy)*dx and
-// ZX likewise in i.  A column update needs slots 3,5 of itself AND of its j+1 neighbour (6,8: i+1): four stored
-// values per direction, but only three slope values (own column window + one row of each neighbour).  Rebuilding
-// the four coefficients in registers with the reference's own expression gives bit-identical values and removes
-// 2 of the 19 streams of the colour pass (16 B per updated cell).  Slots 2,4,7, the pivots and the k=1 diagonal
-// terms stay stored.  Used when the matrix came from define_matrices (not after mgx_set_field(cA)).
-// ------------------------------------------------------------------------------------------------
+// Matrix-free cross terms, generated slots 4 / 7 (ZW), own slopes (ZG) and pivots: the column pass of mgx_relax_common.h with x(k)
+// in registers.  ZW and ZG are parameters because the NZ < 32 instances use the stored slots (k_relax_nz decides).
 // GL: gam(k) waits in LDS (gl: NZ rows x 64 lanes per wave) instead of registers.  At NZ = 64 x and gam together take half of
 // the 512 registers; with the in-kernel pivots on top the kernel spilled (268 B/lane of scratch) -- 32 KB of LDS per wave
 // (one wave per SIMD: 128 KB of the CU's 160 KB) frees 128 registers, and the backward sweep's reads are independent of its
 // dependency chain.
-// ZW: the interior rows of slots 4 and 7 (own and of the j+1 / i+1 neighbour: four streams) are rebuilt from the interface depths
-// zw of the column and of its four face neighbours with the reference's expressions (mg_define_matrix.f90:532-534,549-551; the 2-D
-// factors come precomputed, k_zw_js), and those depths are not streamed either: the sigma coordinate generates them,
-// zw(k,j,i) = z0*h*hinv + zeta*(1.+z0*hinv) with z0 = cffw(k) + csw(k)*h (mg_zr_zw.f90:140-145), from three 2-D values per column
-// (h, hinv, zeta: loaded once) and two table entries per row that are the same for every lane (scalar loads).  Same expressions,
-// bit-identical values (the halo columns too: h and zeta carry the same mirror / exchange rules as zw), FOUR streams less, at seven
-// flops per depth and four fp64 divisions per row under the loads.  Rows 1 and nz of slots 4 / 7 have other formulas
-// (:361-372,:577-590): they read the stored slots.
-// ZG (with ZW): the column's OWN slopes are not streamed either.  zy(k,j,i) = ((hlf*(zr(k,j+1,i)-zr(k,j-1,i)))/dy(j,i))*dx(j,i), zx likewise in
-// i (mg_define_matrix.f90:358,398), need zr of the four face neighbours, whose h, hinv, zeta ZW holds already: zr = z0*h*hinv +
-// zeta*(1.+z0*hinv), z0 = cffr(k)+csr(k)*h (mg_zr_zw.f90:112-122) -- four depths, two slopes per row, TWO streams less (the slopes of the
-// face neighbours, which would need zr of the second ring, stay streamed).  All six divisors of the generated coefficients (dy, dx of the
-// column; the four of slots 4 / 7) are per-column constants: DIVC (mgx_device.h).
+// ------------------------------------------------------------------------------------------------
+template <int NZ, bool MF> constexpr bool gam_in_lds = MF && NZ == 64;  // read by k_relax_nz and by the launch that sizes its LDS
 template <int NZ, bool REAL, bool SNAP, int D, bool ST, bool GL = false, bool ZW = false, bool ZG = false>
 __device__ __forceinline__ void relax_col_mf(const LevView &L, const int i, const int jh, const int jodd, const Sides ph, double *__restrict__ gl = nullptr) {
   int c, jm, jp;
-  if (jodd) { c = L.HO + jh; jm = L.EO + jh; jp = jm + 1; }
-  else      { c = L.EO + jh + 1; jm = L.HO + jh; jp = jm + 1; }
-  const long long RS = L.RS;
-  double *__restrict__ p = L.p;
-  const double *__restrict__ b = L.b;
-  const double *__restrict__ a1 = L.cA[0], *__restrict__ a2 = L.cA[1], *__restrict__ a4 = L.cA[3], *__restrict__ a5 = L.cA[4],
-               *__restrict__ a7 = L.cA[6], *__restrict__ a8 = L.cA[7], *__restrict__ bet = L.bet,
-               *__restrict__ zy = L.zy, *__restrict__ zx = L.zx;
-  const long long o = (long long)i * L.plane, om = o - L.plane, op = o + L.plane;
-  const double qrt = 0.25;
-
-  constexpr int RN = D + 2;  // rows k .. k+1+D are live at iteration k (row k is still read after the look-ahead load is issued)
-  constexpr int RO = D + 2;  // own rows are needed one row early (zy(k+1), zx(k+1))
-  double r_pjm[RN], r_pim[RN], r_pjp[RN], r_pip[RN], r_zyjm[RN], r_zyjp[RN], r_zxim[RN], r_zxip[RN], r_a4[RN], r_a7[RN];
-  double o_b[RO], o_a2[RO], o_a4[RO], o_a7[RO], o_bet[RO], o_zy[ZG ? 1 : RO], o_zx[ZG ? 1 : RO];
-  double x[NZ], g[GL ? 1 : NZ];
-  double zw0[5], zw1[5];  // ZW: generated zw of the column and of its j-1, j+1, i-1, i+1 neighbours, rows k and k+1
-  const int lane = threadIdx.x;
-#define G_PUT(kk, v) { if (GL) gl[((kk)-1) * WAVE + lane] = (v); else g[GL ? 0 : (kk)-1] = (v); }
-
-#define NB_LOAD(q)                                                               \
-  if ((q) <= NZ) {                                                               \
-    const long long ro_ = (long long)((q)-1) * RS; const int s_ = (q) % RN;      \
-    LD_PAIR(p + o + ro_ + jm, r_pjm[s_], r_pjp[s_]) r_pim[s_] = p[om + ro_ + c];  \
-    r_pip[s_] = p[op + ro_ + c];                                                 \
-    LD_PAIR(zy + o + ro_ + jm, r_zyjm[s_], r_zyjp[s_])                            \
-    r_zxim[s_] = *(zx + om + ro_ + c); r_zxip[s_] = *(zx + op + ro_ + c); \
-    if (!ZW) { r_a4[s_] = *(a4 + o + ro_ + jp); r_a7[s_] = *(a7 + op + ro_ + c); }  \
-  }
-#define OW_LOAD(q)                                                               \
-  if ((q) <= NZ) {                                                               \
-    const long long ko_ = o + (long long)((q)-1) * RS + c; const int s_ = (q) % RO; \
-    o_b[s_] = ld_stream<ST>(b + ko_); o_a2[s_] = ld_stream<ST>(a2 + ko_); \
-    if (!ZW) { o_a4[s_] = ld_stream<ST>(a4 + ko_); o_a7[s_] = ld_stream<ST>(a7 + ko_); } \
-    if (!MGX_PV) o_bet[s_] = ld_stream<ST>(bet + ko_); \
-    if (!ZG) { o_zy[ZG ? 0 : s_] = ld_stream<ST>(zy + ko_); o_zx[ZG ? 0 : s_] = ld_stream<ST>(zx + ko_); }       \
-  }
-  // PV: the diagonal of the first and the last row is read (two rows of the stored slot 1), the interior rows rebuild it
-  double dg1 = 0, dgn = 0;
-  if (MGX_PV) { dg1 = a1[o + c]; dgn = a1[o + (long long)(NZ - 1) * RS + c]; }
-  // ZW: stored slots 4 and 7 of the first and the last row, and the per-column factors of the interior formula
-  double hh[5], hv[5], hz[5];  // h, hinv, zeta of the five columns
-  const double *__restrict__ cffw = L.cffw, *__restrict__ csw = L.csw, *__restrict__ cffr = L.cffr, *__restrict__ csr = L.csr;
-  double r4c = 0, r4p = 0, r7c = 0, r7p = 0;                 // refined reciprocals of d4c, d4p, d7c, d7p
-  double gdx = 1, gdy = 1, rdx = 0, rdy = 0;                 // ZG: dx, dy of the column and their reciprocals
-  const double hlf = 0.5;
-  double a4_1 = 0, a4j_1 = 0, a7_1 = 0, a7i_1 = 0, a4_n = 0, a4j_n = 0, a7_n = 0, a7i_n = 0, m4c = 0, m4p = 0, d4c = 1, d4p = 1, m7c = 0, m7p = 0, d7c = 1, d7p = 1;
-  if (ZW) {
-    const long long rn = (long long)(NZ - 1) * RS;
-    a4_1 = a4[o + c]; a4j_1 = a4[o + jp]; a7_1 = a7[o + c]; a7i_1 = a7[op + c];
-    a4_n = a4[o + rn + c]; a4j_n = a4[o + rn + jp]; a7_n = a7[o + rn + c]; a7i_n = a7[op + rn + c];
-    const long long q2 = (long long)i * RS;
-    m4c = L.m4[q2 + c]; m4p = L.m4[q2 + jp]; d4c = L.d4[q2 + c]; d4p = L.d4[q2 + jp];
-    m7c = L.m7[q2 + c]; m7p = L.m7[q2 + RS + c]; d7c = L.d7[q2 + c]; d7p = L.d7[q2 + RS + c];
-    const long long cq[5] = {q2 + c, q2 + jm, q2 + jp, q2 - RS + c, q2 + RS + c};  // the column, j-1, j+1, i-1, i+1
+  COL_POS(L, jh, jodd, c, jm, jp)
+  constexpr bool PAIR = true;
+#define MF_G_PUT(kk, v) { if (GL) gl[((kk)-1) * WAVE + lane] = (v); else g[GL ? 0 : (kk)-1] = (v); }
+#define MF_X_PUT(kk, v, a2k, betk) x[(kk)-1] = (v);
+  MF_PROLOGUE(NZ, GL ? 1 : NZ)
 #pragma unroll
-    for (int q = 0; q < 5; q++) { hh[q] = L.h2[cq[q]]; hv[q] = L.hi2[cq[q]]; hz[q] = L.ze2[cq[q]]; }
-    r4c = RCP_REF(d4c); r4p = RCP_REF(d4p); r7c = RCP_REF(d7c); r7p = RCP_REF(d7p);
-    if (ZG) { gdx = L.dx2[q2 + c]; gdy = L.dy2[q2 + c]; rdx = RCP_REF(gdx); rdy = RCP_REF(gdy); }
-  }
-  // zr(kk, column q) by its generating formula (mg_zr_zw.f90:112-122); own slopes of row kk from the four face neighbours
-#define ZR_GEN(kk, q) ({ const double z0_ = cffr[(kk)-1] + csr[(kk)-1] * hh[q]; z0_ * hh[q] * hv[q] + hz[q] * (1. + z0_ * hv[q]); })
-#define OWN_SLOPES(kk, ZY, ZX) { const double zn1_ = ZR_GEN(kk, 1), zn2_ = ZR_GEN(kk, 2), zn3_ = ZR_GEN(kk, 3), zn4_ = ZR_GEN(kk, 4); \
-    ZY = DIVC(hlf * (zn2_ - zn1_), gdy, rdy) * gdx; ZX = DIVC(hlf * (zn4_ - zn3_), gdx, rdx) * gdy; }
-  // zw(kk, column q) by its generating formula (mg_zr_zw.f90:140-145)
-#define ZW_GEN(kk, q) ({ const double z0_ = cffw[(kk)-1] + csw[(kk)-1] * hh[q]; z0_ * hh[q] * hv[q] + hz[q] * (1. + z0_ * hv[q]); })
-  double d1 = 0, d2 = 0, d3 = 0, d4 = 0, e1 = 0, e2 = 0, e3 = 0, e4 = 0;
-  if (REAL) {
-    const double *__restrict__ q1 = SNAP ? L.p1 : p;
-    const long long s = SNAP ? (long long)i * RS : o, sm = SNAP ? s - RS : om, sp = SNAP ? s + RS : op;
-    d1 = q1[sm + jp]; d2 = q1[sp + jm]; d3 = q1[sm + jm]; d4 = q1[sp + jp];
-    e1 = a5[o + c]; e2 = a5[op + jm]; e3 = a8[o + c]; e4 = a8[op + jp];
-  }
-#pragma unroll
-  for (int q = 1; q <= 1 + D; q++) { NB_LOAD(q) }
-#pragma unroll
-  for (int q = 1; q <= 1 + D; q++) { OW_LOAD(q) }
-
-  // three-row windows (k-1, k, k+1) of the neighbour columns' p and of the own slopes
-  double pjm_m = 0, pjm_0 = r_pjm[1 % RN], pjm_p = 0, pim_m = 0, pim_0 = r_pim[1 % RN], pim_p = 0;
-  double pjp_m = 0, pjp_0 = r_pjp[1 % RN], pjp_p = 0, pip_m = 0, pip_0 = r_pip[1 % RN], pip_p = 0;
-  double zy_m = 0, zy_0 = 0, zy_p = 0, zx_m = 0, zx_0 = 0, zx_p = 0;
-  if (ZG) OWN_SLOPES(1, zy_0, zx_0)
-  else { zy_0 = o_zy[ZG ? 0 : 1 % RO]; zx_0 = o_zx[ZG ? 0 : 1 % RO]; }
-  double xv = 0.0, betp = 0.0;
-#pragma unroll
-  for (int k = 1; k <= NZ; k++) {
-    NB_LOAD(k + 1 + D)
-    OW_LOAD(k + 1 + D)
-    if (k < NZ) {
-      const int s1 = (k + 1) % RN, t1 = (k + 1) % RO;
-      pjm_p = r_pjm[s1]; pim_p = r_pim[s1]; pjp_p = r_pjp[s1]; pip_p = r_pip[s1];
-      if (ZG) OWN_SLOPES(k + 1, zy_p, zx_p)
-      else { zy_p = o_zy[ZG ? 0 : t1]; zx_p = o_zx[ZG ? 0 : t1]; }
-    }
-    const int s = k % RO, n = k % RN;
-    const double zyjm = r_zyjm[n], zyjp = r_zyjp[n], zxim = r_zxim[n], zxip = r_zxip[n];
-    // the eight cross coefficients of this row, rebuilt from the slopes (header comment): own slots 3,5,6,8 and the
-    // mirrored ones stored at the j+1 / i+1 neighbours
-    const double c3 = qrt * (zy_p + zyjm), c3m = qrt * (zyjp + zy_m), c5 = -qrt * (zy_m + zyjm), c5m = -qrt * (zyjp + zy_p);
-    const double c6 = qrt * (zx_p + zxim), c6m = qrt * (zxip + zx_m), c8 = -qrt * (zx_m + zxim), c8m = -qrt * (zxip + zx_p);
-    double a4o, a4jp, a7o, a7ip;  // slots 4 and 7 of the cell and of its j+1 / i+1 neighbour
-    if (!ZW) { a4o = o_a4[s]; a4jp = r_a4[n]; a7o = o_a7[s]; a7ip = r_a7[n]; }
-    else if (k == 1) { a4o = a4_1; a4jp = a4j_1; a7o = a7_1; a7ip = a7i_1; }
-    else if (k == NZ) { a4o = a4_n; a4jp = a4j_n; a7o = a7_n; a7ip = a7i_n; }
-    else {
-      if (k == 2) {
-#pragma unroll
-        for (int q = 0; q < 5; q++) zw0[q] = ZW_GEN(2, q);
-      }
-#pragma unroll
-      for (int q = 0; q < 5; q++) zw1[q] = ZW_GEN(k + 1, q);
-      const double wo0 = zw0[0], wop1 = zw1[0];
-      a4o = DIVC(qrt * (wop1 - wo0 + zw1[1] - zw0[1]) * m4c, d4c, r4c);
-      a4jp = DIVC(qrt * (zw1[2] - zw0[2] + wop1 - wo0) * m4p, d4p, r4p);
-      a7o = DIVC(qrt * (wop1 - wo0 + zw1[3] - zw0[3]) * m7c, d7c, r7c);
-      a7ip = DIVC(qrt * (zw1[4] - zw0[4] + wop1 - wo0) * m7p, d7p, r7p);
-#pragma unroll
-      for (int q = 0; q < 5; q++) zw0[q] = zw1[q];
-    }
-    double betk;
-    if (MGX_PV) {
-      // pivots in the kernel: d(k) = cA(1,k,j,i) is minus the sum of the fourteen couplings of the row, added in the order of
-      // mg_define_matrix.f90:632-639 (bit-identical to the stored value; rows 1 and nz, which have their own formulas
-      // :619-627,:642-654, are read), then tridiag's recurrence (mg_relax.f90:322-326) -- no bet stream from HBM
-      double dk;
-      if (k == 1) dk = dg1;
-      else if (k == NZ) dk = dgn;
-      else dk = -o_a2[s] - o_a2[(k + 1) % RO] - a4o - a4jp - a7o - a7ip - c6 - c6m - c8 - c8m - c3 - c3m - c5 - c5m;
-      if (k == 1) betk = 1.0 / dk;
-      else { const double gk = o_a2[s] * betp; G_PUT(k, gk) betk = 1.0 / (dk - o_a2[s] * gk); }
-    } else {
-      if (k > 1) G_PUT(k, o_a2[s] * betp)
-      betk = o_bet[s];
-    }
-    betp = betk;
-    double rhs;
-    if (k == 1) {
-      rhs = o_b[s] - c3 * pjm_p - a4o * pjm_0 - a4jp * pjp_0 - c5m * pjp_p
-                   - c6 * pim_p - a7o * pim_0 - a7ip * pip_0 - c8m * pip_p;
-      if (REAL) rhs = rhs - e1 * d1 - e2 * d2 - e3 * d3 - e4 * d4;
-      xv = rhs * betk;
-    } else if (k < NZ) {
-      rhs = o_b[s] - c3 * pjm_p - c3m * pjp_m - a4o * pjm_0 - a4jp * pjp_0
-                   - c5 * pjm_m - c5m * pjp_p
-                   - c6 * pim_p - c6m * pip_m - a7o * pim_0 - a7ip * pip_0
-                   - c8 * pim_m - c8m * pip_p;
-      xv = (rhs - o_a2[s] * xv) * betk;
-    } else {
-      rhs = o_b[s] - c3m * pjp_m - a4o * pjm_0 - a4jp * pjp_0 - c5 * pjm_m
-                   - c6m * pip_m - a7o * pim_0 - a7ip * pip_0 - c8 * pim_m;
-      xv = (rhs - o_a2[s] * xv) * betk;
-    }
-    x[k - 1] = xv;
-    pjm_m = pjm_0; pjm_0 = pjm_p; pim_m = pim_0; pim_0 = pim_p;
-    pjp_m = pjp_0; pjp_0 = pjp_p; pip_m = pip_0; pip_0 = pip_p;
-    zy_m = zy_0; zy_0 = zy_p; zx_m = zx_0; zx_0 = zx_p;
-  }
+  for (int k = 1; k <= NZ; k++) MF_ROW(k)
+#undef MF_G_PUT
+#undef MF_X_PUT
 #pragma unroll
   for (int k = NZ - 1; k >= 1; k--) x[k - 1] = x[k - 1] - (GL ? gl[k * WAVE + lane] : g[GL ? 0 : k]) * x[k];
-#undef G_PUT
 
   const int j = jodd ? 2 * jh + 1 : 2 * jh + 2;
-  const bool mS = ph.S && j == 1, mN = ph.N && j == L.ny, mW = ph.W && i == 1, mE = ph.E && i == L.nx;
-  const int cS = L.EO, cN = jpos(L, L.ny + 1);
-  const long long oW = 0, oE = (long long)(L.nx + 1) * L.plane;
+  COL_IMAGES(L, i, j, ph)
 #pragma unroll
   for (int k = 1; k <= NZ; k++) {
     const long long ro = (long long)(k - 1) * RS;
     const double v = x[k - 1];
-    if (ST) NT2_STORE(v, p + o + ro + c); else p[o + ro + c] = v;
-    if (mS) p[o + ro + cS] = v;
-    if (mN) p[o + ro + cN] = v;
-    if (mW) { p[oW + ro + c] = v; if (mS) p[oW + ro + cS] = v; if (mN) p[oW + ro + cN] = v; }
-    if (mE) { p[oE + ro + c] = v; if (mS) p[oE + ro + cS] = v; if (mN) p[oE + ro + cN] = v; }
+    COL_STORE(ST, p, o, ro, c, v)
   }
   if (SNAP && L.d0w != nullptr) L.d0w[(long long)i * RS + c] = x[0] - L.p1[(long long)i * RS + c];  // mgx_rbseq.hip (b): d0, what k_rbseq_d0 would compute from the stored y
-  if (SNAP && L.p1w != nullptr) {  // next sweep's k=1 snapshot entry of this column (and its physical mirrors): no snapshot launch per pass
-    // A mirrored halo cell is read (as a k=1 diagonal) only by columns of the OTHER colour, i.e. by the next pass of this
-    // same sweep, which must see it updated: mirrors go to the buffer being read as well (no column of this pass reads them,
-    // except a corner column its own corner, after which it is the one to overwrite it).
-    double *w1 = L.p1w, *r1 = L.p1;
-    const long long so = (long long)i * RS, sW = 0, sE = (long long)(L.nx + 1) * RS;
-    const double v1 = x[0];
-    w1[so + c] = v1;
-#define SNAP_MIRROR(idx) { w1[idx] = v1; r1[idx] = v1; }
-    if (mS) SNAP_MIRROR(so + cS)
-    if (mN) SNAP_MIRROR(so + cN)
-    if (mW) { SNAP_MIRROR(sW + c) if (mS) SNAP_MIRROR(sW + cS) if (mN) SNAP_MIRROR(sW + cN) }
-    if (mE) { SNAP_MIRROR(sE + c) if (mS) SNAP_MIRROR(sE + cS) if (mN) SNAP_MIRROR(sE + cN) }
-#undef SNAP_MIRROR
-  }
-#undef NB_LOAD
-#undef OW_LOAD
-#undef ZW_GEN
-#undef ZR_GEN
-#undef OWN_SLOPES
+  if (SNAP && L.p1w != nullptr) COL_SNAPSHOT(L, RS, i, c, x[0])
 }
 
 template <int NZ, bool REAL, bool SNAP, int D, bool MF, bool ST>
 __global__ __launch_bounds__(128, 1) void k_relax_nz(LevView L, int i0, int istep, int nplanes, int jodd_fixed, int rb, Sides ph, int gx) {
-  // XCD-aware block -> (j-chunk, plane pair) map.  Blocks are dealt round-robin over the 8 XCDs (b and b+8 share one),
-  // each with its own 4 MB L2.  Give every XCD a contiguous range of planes: the pass over plane i and the pass over
-  // plane i+2 both read p and the slopes of plane i+1.  The two waves of a block take two consecutive planes of the
-  // colour, so those two readers also sit on one CU (speed only; any placement gives the same result).
   const int npair = (nplanes + blockDim.y - 1) / blockDim.y;
-  int bx, ipr;
-  if (gx < 0) { gx = -gx; ipr = blockIdx.x / gx; bx = blockIdx.x - ipr * gx; }  // MGX_NO_XCD=1 (A/B measurements)
-  else if ((npair & 7) == 0) {
-    const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-    ipr = xcd * (npair >> 3) + local / gx;
-    bx = local - (local / gx) * gx;
-  } else { ipr = blockIdx.x / gx; bx = blockIdx.x - ipr * gx; }
+  int bx, ipr;  // j-chunk, plane pair
+  XCD_BLOCK_MAP(npair, gx, bx, ipr)
   const int ipl = ipr * blockDim.y + threadIdx.y;
   const int jh = bx * WAVE + threadIdx.x;
   if (jh >= (L.ny >> 1) || ipl >= nplanes) return;
@@ -490,12 +265,12 @@ __global__ __launch_bounds__(128, 1) void k_relax_nz(LevView L, int i0, int iste
   // RB: j = 1+mod(i+rb,2),ny,2 (mg_relax.f90:174) ; FC: fixed parity (:216-217)
   const int jodd = jodd_fixed >= 0 ? jodd_fixed : (((i + rb) & 1) == 0);
   if (sides_part_skip(ph, i, L.nx, jodd, bx, gx)) return;  // wave-uniform
-  constexpr bool GL = MF && NZ == 64 && MGX_GL;  // keep in step with launch_relax_nz_d
-  constexpr bool ZW = MF && NZ >= 32 && MGX_ZW;
+  constexpr bool GL = gam_in_lds<NZ, MF>;
+  constexpr bool ZW = MF && NZ >= 32;  // generated slots 4 / 7 and own slopes: the levels whose streams come from HBM
   if (GL) {
     extern __shared__ double g_lds[];  // blockDim.y waves x NZ rows x 64 lanes
-    relax_col_mf<NZ, REAL, SNAP, D, ST, GL, ZW, ZW && MGX_ZG>(L, i, jh, jodd, ph, g_lds + (size_t)threadIdx.y * NZ * WAVE);
-  } else if (MF) relax_col_mf<NZ, REAL, SNAP, D, ST, false, ZW, ZW && MGX_ZG>(L, i, jh, jodd, ph);
+    relax_col_mf<NZ, REAL, SNAP, D, ST, GL, ZW, ZW>(L, i, jh, jodd, ph, g_lds + (size_t)threadIdx.y * NZ * WAVE);
+  } else if (MF) relax_col_mf<NZ, REAL, SNAP, D, ST, false, ZW, ZW>(L, i, jh, jodd, ph);
   else relax_col_nz<NZ, REAL, SNAP, D>(L, i, jh, jodd, ph);
 }
 
@@ -741,10 +516,9 @@ static void launch_relax_nz_d(hipStream_t st, const LevView *L, int i0, int iste
   // streaming (nontemporal) hints only when the level cannot live in the 256 MB Infinity Cache between passes:
   // measured +14 % on the 1.2 GB level 1, -20 % on the 150 MB level 2 which is otherwise re-read from cache
   const bool stream = mf && (double)L->nx * L->ny * NZ * 72.0 > 256e6;
-  // gam in LDS (GL, see relax_col_mf): 32 KB per wave of the matrix-free NZ = 64 kernel
 #define LAUNCH_NZ(MFV, STV)                                                                                              \
   {                                                                                                                       \
-    const size_t lds = (MFV && NZ == 64 && MGX_GL) ? (size_t)by * NZ * WAVE * sizeof(double) : 0;                          \
+    const size_t lds = gam_in_lds<NZ, MFV> ? (size_t)by * NZ * WAVE * sizeof(double) : 0;  /* 32 KB per wave (GL, relax_col_mf) */ \
     if (real && snap) hipLaunchKernelGGL((k_relax_nz<NZ, true, true, D, MFV, STV>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx); \
     else if (real) hipLaunchKernelGGL((k_relax_nz<NZ, true, false, D, MFV, STV>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx);   \
     else hipLaunchKernelGGL((k_relax_nz<NZ, false, false, D, MFV, STV>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx);            \
@@ -758,20 +532,7 @@ template <int NZ>
 static void launch_relax_nz(hipStream_t st, const LevView *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, Sides ph) {
   // look-ahead depth D (rows of loads in flight)
   // measured: NZ=16 6.3 us/pass at D=2 vs 9.3 at D=3; NZ>=32 flat for D=2..5
-#ifdef MGX_D64
-  constexpr int D = NZ == 64 ? MGX_D64 : (NZ >= 32 ? 3 : (NZ >= 8 ? 2 : 1));
-#else
   constexpr int D = NZ >= 32 ? 3 : (NZ >= 8 ? 2 : 1);
-#endif
-#ifdef MGX_TUNE_D
-  if (NZ >= 8) {
-    static const int dd = getenv("MGX_D") ? atoi(getenv("MGX_D")) : 3;
-    if (dd == 1) return launch_relax_nz_d<NZ, 1>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph);
-    if (dd == 2) return launch_relax_nz_d<NZ, 2>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph);
-    if (dd == 5) return launch_relax_nz_d<NZ, 5>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph);
-    if (dd == 7) return launch_relax_nz_d<NZ, 7>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph);
-  }
-#endif
   launch_relax_nz_d<NZ, D>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph);
 }
 

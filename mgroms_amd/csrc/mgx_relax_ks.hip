@@ -11,7 +11,7 @@
 // Same expressions in the same order as relax_col_mf: bit-identical results.
 #include <cstdlib>
 
-#include "mgx_device.h"
+#include "mgx_relax_common.h"
 
 // H > 1 (nz = 64, the second level of an nz = 128 hierarchy): a wave's NZ/NW rows are built in H runs of R rows one after the other (the register
 // arrays of a run are those of the nz = 32 kernel), the recurrence wave keeps only x(k) in registers and takes a2(k), bet(k) from LDS as it
@@ -27,14 +27,8 @@ __global__ __launch_bounds__(64 * NW, 1) void k_relax_ks(LevView L, int i0, int 
   constexpr int R = NZ / NW / H;  // rows per wave and run
   extern __shared__ double ks_lds[];
   double *__restrict__ sh = ks_lds, *__restrict__ sa2 = ks_lds + NZ * WAVE, *__restrict__ sbt = ks_lds + 2 * NZ * WAVE;  // rhs(k) then x(k); a2(k); bet(k): [k-1][lane]
-  // XCD-aware block -> (j-chunk, plane) map, as k_relax_nz: each XCD owns a contiguous range of planes (speed only)
-  int bx, ipl;
-  if (gx < 0) { gx = -gx; ipl = blockIdx.x / gx; bx = blockIdx.x - ipl * gx; }
-  else if ((nplanes & 7) == 0) {
-    const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-    ipl = xcd * (nplanes >> 3) + local / gx;
-    bx = local - (local / gx) * gx;
-  } else { ipl = blockIdx.x / gx; bx = blockIdx.x - ipl * gx; }
+  int bx, ipl;  // j-chunk, plane: one workgroup per plane here
+  XCD_BLOCK_MAP(nplanes, gx, bx, ipl)
   const int lane = threadIdx.x, w = __builtin_amdgcn_readfirstlane(threadIdx.y);  // wave-uniform: row ranges in scalar registers
   KS_STAMP(0) KS_STAMP(7)
   const int jh = bx * WAVE + lane;
@@ -44,8 +38,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_relax_ks(LevView L, int i0, int 
   const int jodd = jodd_fixed >= 0 ? jodd_fixed : (((i + rb) & 1) == 0);
   if (sides_part_skip(ph, i, L.nx, jodd, bx, gx)) return;  // workgroup-uniform (before any barrier)
   int c, jm, jp;
-  if (jodd) { c = L.HO + jh; jm = L.EO + jh; jp = jm + 1; }
-  else      { c = L.EO + jh + 1; jm = L.HO + jh; jp = jm + 1; }
+  COL_POS(L, jh, jodd, c, jm, jp)
   const long long RS = L.RS;
   double *__restrict__ p = L.p;
   const double *__restrict__ b = L.b;
@@ -159,20 +152,10 @@ __global__ __launch_bounds__(64 * NW, 1) void k_relax_ks(LevView L, int i0, int 
 #pragma unroll
     for (int k = 1; k <= NZ; k++) sh[(k - 1) * WAVE + lane] = x[k - 1];
     if (SNAP && L.d0w != nullptr) L.d0w[(long long)i * RS + c] = x[0] - L.p1[(long long)i * RS + c];  // mgx_rbseq.hip (b): the walk's d0
-    if (SNAP && L.p1w != nullptr) {  // next sweep's k=1 snapshot entry and its physical mirrors (see relax_col_nz)
+    if (SNAP && L.p1w != nullptr) {
       const int j = jodd ? 2 * jh + 1 : 2 * jh + 2;
-      const bool mS = ph.S && j == 1, mN = ph.N && j == L.ny, mW = ph.W && i == 1, mE = ph.E && i == L.nx;
-      const int cS = L.EO, cN = jpos(L, L.ny + 1);
-      double *w1 = L.p1w, *r1 = L.p1;
-      const long long so = (long long)i * RS, sW = 0, sE = (long long)(L.nx + 1) * RS;
-      const double v1 = x[0];
-      w1[so + c] = v1;
-#define SNAP_MIRROR(idx) { w1[idx] = v1; r1[idx] = v1; }
-      if (mS) SNAP_MIRROR(so + cS)
-      if (mN) SNAP_MIRROR(so + cN)
-      if (mW) { SNAP_MIRROR(sW + c) if (mS) SNAP_MIRROR(sW + cS) if (mN) SNAP_MIRROR(sW + cN) }
-      if (mE) { SNAP_MIRROR(sE + c) if (mS) SNAP_MIRROR(sE + cS) if (mN) SNAP_MIRROR(sE + cN) }
-#undef SNAP_MIRROR
+      COL_IMAGES(L, i, j, ph)
+      COL_SNAPSHOT(L, RS, i, c, x[0])
     }
   }
   __syncthreads();
@@ -180,19 +163,13 @@ __global__ __launch_bounds__(64 * NW, 1) void k_relax_ks(LevView L, int i0, int 
   // ---- phase 3: every wave stores its rows (+ the physical-boundary mirrors, mg_mpi_exchange.f90:509-537,552-597)
   if (!live) return;
   const int j = jodd ? 2 * jh + 1 : 2 * jh + 2;
-  const bool mS = ph.S && j == 1, mN = ph.N && j == L.ny, mW = ph.W && i == 1, mE = ph.E && i == L.nx;
-  const int cS = L.EO, cN = jpos(L, L.ny + 1);
-  const long long oW = 0, oE = (long long)(L.nx + 1) * L.plane;
+  COL_IMAGES(L, i, j, ph)
 #pragma unroll
   for (int r = 0; r < R * H; r++) {
     const int k = kw + r;
     const long long ro = (long long)(k - 1) * RS;
     const double v = sh[(k - 1) * WAVE + lane];
-    p[o + ro + c] = v;
-    if (mS) p[o + ro + cS] = v;
-    if (mN) p[o + ro + cN] = v;
-    if (mW) { p[oW + ro + c] = v; if (mS) p[oW + ro + cS] = v; if (mN) p[oW + ro + cN] = v; }
-    if (mE) { p[oE + ro + c] = v; if (mS) p[oE + ro + cS] = v; if (mN) p[oE + ro + cN] = v; }
+    COL_STORE(false, p, o, ro, c, v)
   }
 #ifdef MGX_KS_STAMP
   KS_STAMP(5)

@@ -26,5 +26,5 @@ nhydro.time_relax(1, 5)
 s = [nhydro.time_relax(1, reps) for _ in range(3)]
 r = [nhydro.time_residual(1, reps) for _ in range(3)]
 cells = nx * ny * nz
-print(f"{method} {nx}x{ny}x{nz} D={os.environ.get('MGX_D','-')}: sweep {min(s):.4f} ms ({88*cells/min(s)/1e6/8000*100:.1f}% of 8 TB/s), residual {min(r):.4f} ms ({88*cells/min(r)/1e6/8000*100:.1f}%)")
+print(f"{method} {nx}x{ny}x{nz}: sweep {min(s):.4f} ms ({88*cells/min(s)/1e6/8000*100:.1f}% of 8 TB/s), residual {min(r):.4f} ms ({88*cells/min(r)/1e6/8000*100:.1f}%)")
 mg.nhydro_clean()
