@@ -267,6 +267,18 @@ int mgx_counters(long long *out);
  * (r of lev -> b of lev+1, p of lev+1 = 0), "coarse2fine" (p of lev += interpolation of p of lev+1), "resrest" (restriction of b - A p of lev
  * -> b of lev+1, p of lev+1 = 0: the down leg of a V-cycle).  No Fortran counterpart. */
 int mgx_mixed_op(const char *op, int lev, int n);
+/* test hook of the three passes of option "krylov" (mgx_krylov.hip; single rank, after mgx_matrices): runs ONE pass on level 1 through the
+ * wrapper solve_p calls for it, on the buffers solve_p uses (its ring of direction pairs, partial sums and device scalars, grid(1)%p and %r,
+ * which it overwrites), and adds no kernel of its own.  Fields are host arrays (nz, 0:ny+1, 0:nx+1) as in mgx_get_field, halos taken as given.
+ * nd = retained pairs (0..8); pair n sits in ring slot slot[n] (distinct values of 0..nd; NULL = 0..nd-1), the pair in work in the free slot.
+ *   op = "apply":  fields = z, q, q_1 .. q_nd.  q = A z is written; sout[0..nd-1] = (q, q_n).  z needs valid halos.
+ *   op = "ortho":  fields = z, q, r, z_1, q_1, .. z_nd, q_nd; sin[0..7] = (q, q_n), sin[8..16] = (q_n, q_n) BY RING SLOT.  z, q are rewritten
+ *                  (z -= sum beta_n z_n, q -= sum beta_n q_n, beta_n = sin[n] / sin[8 + slot[n]]); sout[0] = (q, q), sout[1] = (r, q).
+ *   op = "update": fields = p, r, z, q; sin = {s, t}; the new pair's ring slot is nd.  p += (t / s) z, r -= (t / s) q are rewritten;
+ *                  sout[0] = ||r||^2, or -1 when s, t allow no step (p, r untouched); sout[1] = what the pass filed under that slot (s).
+ * Sums run over interior cells.  path (may be NULL) receives the launch taken: matrix-free operator (1) or stored slots (0), cmatrix='real',
+ * the non-temporal variant, gx, gy of pass 1's block map.  No Fortran counterpart. */
+int mgx_krylov_op(const char *op, int nd, double *const *fields, const int *slot, const double *sin, double *sout, int *path);
 
 /* ---- peer-to-peer halo transport (replaces the MPI_Isend/MPI_Irecv/MPI_Waitall of fill_halo_3D[_relax],
  * mg_mpi_exchange.f90:504-718, for the p/b/r halos of the cycle) ----

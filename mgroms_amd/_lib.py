@@ -67,6 +67,7 @@ _SIGS = {
     "mgx_time_residual": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "mgx_counters": (C.c_int, [C.POINTER(C.c_longlong)]),
     "mgx_mixed_op": (C.c_int, [C.c_char_p, C.c_int, C.c_int]),
+    "mgx_krylov_op": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_DP), C.POINTER(C.c_int), _DP, _DP, C.POINTER(C.c_int)]),
     "mgx_p2p_handle_bytes": (C.c_int, []),
     "mgx_p2p_prepare": (C.c_int, [C.c_void_p]),
     "mgx_p2p_connect": (C.c_int, [C.c_void_p, C.c_int]),

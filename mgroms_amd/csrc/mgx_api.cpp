@@ -608,6 +608,14 @@ int mgx_mixed_op(const char *op, int lev, int n) {
   return sync_stream();
 }
 
+// test hook of the three passes of option "krylov": one pass on level 1 through the wrapper and on the buffers solve_p_krylov uses (mgx_cycle.cpp: krylov_op)
+int mgx_krylov_op(const char *op, int nd, double *const *fields, const int *slot, const double *sin, double *sout, int *path) {
+  NEED_INIT();
+  if (S.nranks > 1) return fail("mgx_krylov_op needs a single rank (process grid %d x %d)", S.npx, S.npy);
+  if (!S.have_matrix) return fail("mgx_krylov_op: no matrix: call mgx_matrices first");
+  return krylov_op(op, nd, fields, slot, sin, sout, path);
+}
+
 int mgx_counters(long long *out) { out[0] = S.n_launch; out[1] = S.n_halo; out[2] = S.n_exch; out[3] = S.n_allred; return 0; }
 
 }  // extern "C"

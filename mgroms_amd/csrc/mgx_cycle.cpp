@@ -724,6 +724,69 @@ int solve_p_krylov(double tol, int maxite, int *nite_out, double *res_out, doubl
   return 0;
 }
 
+// Test hook of the three passes (mgx_krylov_op, include/mgx.h): ONE pass on level 1 through the wrapper solve_p_krylov calls, on the buffers
+// it uses -- the ring S.kr_z / S.kr_q after krylov_prepare(nd), S.kr_partial, the scalars in S.kr_sc, grid(1)%p and %r, the level's own view,
+// S.stream and S.real.  Fields cross as host arrays (nz, 0:ny+1, 0:nx+1) by the staging of mgx_set_field / mgx_get_field, halos as given.
+// The retained pair n sits in ring slot slot[n] (0..nd, distinct; nullptr = 0..nd-1) and the pair in work in the slot left free.
+int krylov_op(const char *op, int nd, double *const *f, const int *slot, const double *sin, double *sout, int *path) {
+  if (!op) return fail("mgx_krylov_op: op is NULL");
+  const int which = streq(op, "apply") ? 1 : streq(op, "ortho") ? 2 : streq(op, "update") ? 3 : 0;
+  if (!which) return fail("mgx_krylov_op: unknown pass '%s' (apply, ortho, update)", op);
+  if (nd < 0 || nd > 8) return fail("mgx_krylov_op(%s): nd = %d retained pairs (0..8)", op, nd);
+  int sl[8], head = nd, used = 0;
+  for (int n = 0; n < nd; n++) {
+    sl[n] = slot ? slot[n] : n;
+    if (sl[n] < 0 || sl[n] > nd || (used >> sl[n] & 1)) return fail("mgx_krylov_op(%s): slot[%d] = %d (distinct values of 0..%d)", op, n, sl[n], nd);
+    used |= 1 << sl[n];
+  }
+  if (which != 3) for (head = 0; used >> head & 1;) head++;
+  CHK(krylov_prepare(nd));
+  Level &L = S.lev[0];
+  const size_t n3 = (size_t)L.nz * (L.ny + 2) * (L.nx + 2);
+  auto put = [&](const double *host, double *js) -> int {
+    HIPCHK(hipMemcpyAsync(S.ref_scratch, host, n3 * sizeof(double), hipMemcpyHostToDevice, S.stream));
+    mgxk_convert(S.stream, &L.v, js, S.ref_scratch, 1, 0, 0);
+    return 0;
+  };
+  auto get = [&](double *host, double *js) -> int {
+    mgxk_convert(S.stream, &L.v, js, S.ref_scratch, 1, 0, 1);
+    HIPCHK(hipMemcpyAsync(host, S.ref_scratch, n3 * sizeof(double), hipMemcpyDeviceToHost, S.stream));
+    return 0;
+  };
+  double *sc = S.kr_sc, *qq = S.kr_sc + 16, *z = S.kr_z[head], *q = S.kr_q[head];
+  const double *zi[8], *qi[8];
+  for (int n = 0; n < nd; n++) { zi[n] = S.kr_z[sl[n]]; qi[n] = S.kr_q[sl[n]]; }
+  if (path) { int g[4]; mgxq_path(&L.v, g); path[0] = g[0]; path[1] = S.real; path[2] = g[1]; path[3] = g[2]; path[4] = g[3]; }
+  if (which == 1) {          // f = z, q (out), q_1 .. q_nd; sout[0..nd-1] = (q, q_i)
+    CHK(put(f[0], z));
+    for (int n = 0; n < nd; n++) CHK(put(f[2 + n], S.kr_q[sl[n]]));
+    LevView zv = L.v; zv.p = z;
+    mgxq_apply(S.stream, &zv, q, qi, nd, S.kr_partial, sc, S.real);
+    CHK(get(f[1], q));
+    if (nd) HIPCHK(hipMemcpyAsync(sout, sc, nd * sizeof(double), hipMemcpyDeviceToHost, S.stream));
+  } else if (which == 2) {   // f = z, q (both rewritten), r, then z_1, q_1, .. z_nd, q_nd; sin[0..7] = (q, q_i), sin[8..16] = (q_i, q_i) by ring slot
+    CHK(put(f[0], z)); CHK(put(f[1], q)); CHK(put(f[2], L.v.r));
+    L.r_halo_stale = false;
+    for (int n = 0; n < nd; n++) { CHK(put(f[3 + 2 * n], S.kr_z[sl[n]])); CHK(put(f[4 + 2 * n], S.kr_q[sl[n]])); }
+    HIPCHK(hipMemcpyAsync(sc, sin, 8 * sizeof(double), hipMemcpyHostToDevice, S.stream));
+    HIPCHK(hipMemcpyAsync(qq, sin + 8, 9 * sizeof(double), hipMemcpyHostToDevice, S.stream));
+    mgxq_ortho(S.stream, &L.v, z, q, L.v.r, zi, qi, sl, nd, sc, qq, S.kr_partial, sc + 8);
+    CHK(get(f[0], z)); CHK(get(f[1], q));
+    HIPCHK(hipMemcpyAsync(sout, sc + 8, 2 * sizeof(double), hipMemcpyDeviceToHost, S.stream));
+  } else {                   // f = p, r (both rewritten), z, q; sin = {s, t}; the new pair's ring slot is nd; sout = {||r||^2 or -1, what was filed there}
+    CHK(put(f[0], L.v.p)); CHK(put(f[1], L.v.r)); CHK(put(f[2], z)); CHK(put(f[3], q));
+    L.r_halo_stale = false;
+    HIPCHK(hipMemcpyAsync(sc + 8, sin, 2 * sizeof(double), hipMemcpyHostToDevice, S.stream));
+    HIPCHK(hipMemsetAsync(qq, 0xff, 9 * sizeof(double), S.stream));   // not-a-numbers: a slot nobody files reads back as one
+    mgxq_update(S.stream, &L.v, L.v.p, L.v.r, z, q, sc + 8, qq + head, S.kr_partial, S.d_scalar);
+    CHK(get(f[0], L.v.p)); CHK(get(f[1], L.v.r));
+    HIPCHK(hipMemcpyAsync(sout, S.d_scalar, sizeof(double), hipMemcpyDeviceToHost, S.stream));
+    HIPCHK(hipMemcpyAsync(sout + 1, qq + head, sizeof(double), hipMemcpyDeviceToHost, S.stream));
+  }
+  S.n_launch += 2;
+  return sync_stream();
+}
+
 // the solve_p of mgx_solve_p / mgx_solve / mgx_solve_device: fp64 cycles, fp32 cycles under fp64 refinement, or the Krylov-accelerated loop
 int solve_p_opt(double tol, int maxite, int *nite_out, double *res_out, double *hist) {
   if (S.krylov > 0 && S.cycle_precision == 32)

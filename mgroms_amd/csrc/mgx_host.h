@@ -240,6 +240,7 @@ int vcycle2(int lev1, int lev2);
 int fcycle(int have_r2 = 0);
 std::string fortran_e3(double v, int width);
 int solve_p_opt(double tol, int maxite, int *nite_out, double *res_out, double *hist);
+int krylov_op(const char *op, int nd, double *const *f, const int *slot, const double *sin, double *sout, int *path);
 int mixed_check();
 int mixed_prepare();
 void relax32(int lev, int nsweeps);

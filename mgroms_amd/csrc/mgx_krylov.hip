@@ -275,6 +275,12 @@ long long mgxq_partials(const LevView *L) {
   const long long a = (long long)KR_MAX * g3.x * g3.y * 2, b = 2LL * gs.x * gs.y;
   return a > b ? a : b;
 }
+// which launch the wrappers below choose for a level (reported by the test hook mgx_krylov_op): out[0] = pass 1 matrix-free (1) or from the
+// stored slots (0), out[1] = the non-temporal variant of all three passes, out[2] = gx, out[3] = gy of pass 1's block map
+void mgxq_path(const LevView *L, int *out) {
+  const dim3 g3 = col_grid(L->ny / 2, L->nx, 2);
+  out[0] = L->zy != nullptr && L->nz >= 3; out[1] = level_streams(L); out[2] = (int)g3.x; out[3] = (int)g3.y;
+}
 // q = A z (z = L->p, halos valid), sc[i] = (q, q_i) for the nd retained q_i
 void mgxq_apply(hipStream_t st, const LevView *L, double *qout, const double *const *qi, int nd, double *partial, double *sc, int real) {
   KrDirs D = {};

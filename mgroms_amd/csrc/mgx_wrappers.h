@@ -125,6 +125,7 @@ void mgxx_to64(hipStream_t st, const LevView *D, const LevView32 *S, const float
 
 // ---- mgx_krylov.hip ----
 long long mgxq_partials(const LevView *L);
+void mgxq_path(const LevView *L, int *out);
 void mgxq_apply(hipStream_t st, const LevView *L, double *qout, const double *const *qi, int nd, double *partial, double *sc, int real);
 void mgxq_ortho(hipStream_t st, const LevView *L, double *z, double *q, const double *r, const double *const *zi, const double *const *qi,
                 const int *slot, int nd, const double *sc, const double *qq, double *partial, double *out);

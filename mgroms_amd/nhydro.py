@@ -214,6 +214,26 @@ def mixed_op(op, lev, n=1):
     check(lib().mgx_mixed_op(op.encode(), int(lev), int(n)))
 
 
+def krylov_op(op, fields, nd=0, slot=None, sin=(), nout=2):
+    """one pass of option "krylov" on level 1 (include/mgx.h: mgx_krylov_op).  fields: the pass's level-1 arrays (nx+2, ny+2, nz) in the
+    header's order, C-contiguous float64; the ones the pass writes are rewritten in place.  -> (sout[:nout], path), path = the launch taken
+    as a dict (mf, real, stream, gx, gy)."""
+    nx, ny, nz = _state.dims
+    for a in fields:
+        if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.shape == (nx + 2, ny + 2, nz)):
+            raise ValueError(f"krylov_op: need C-contiguous float64 arrays of shape {(nx + 2, ny + 2, nz)}")
+    want = {"apply": 2 + nd, "ortho": 3 + 2 * nd, "update": 4}.get(op)
+    if want is not None and 0 <= nd <= 8 and len(fields) != want:   # (an unknown op or nd is the library's to refuse)
+        raise ValueError(f"krylov_op({op}, nd = {nd}): {want} fields expected, got {len(fields)}")
+    ptrs = (_DP * max(len(fields), 1))(*[_dp(a) for a in fields])
+    sl = None if slot is None else (C.c_int * max(len(slot), 1))(*[int(s) for s in slot])
+    si = (C.c_double * 17)(*[float(v) for v in sin])
+    so = (C.c_double * 8)()
+    path = (C.c_int * 5)()
+    check(lib().mgx_krylov_op(op.encode(), int(nd), ptrs, sl, si, so, path))
+    return np.array(so[:nout]), dict(zip(("mf", "real", "stream", "gx", "gy"), list(path)))
+
+
 def rbseq_window_info(lev):
     """(rho, planes): the contraction bound of the level's red-black walk and the planes of warm-up of the windowed walk
     (option "rbseq_window", include/mgx.h); planes = 0: the walk over the whole level stays."""

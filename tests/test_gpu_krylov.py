@@ -85,6 +85,59 @@ def test_history_follows_the_reference_gcr(mg):
     assert mg.nhydro.get_option("krylov_restarts") == 0
 
 
+def _oracle_bmask(nx, ny, nz, meth):
+    """the oracle with the island mask, set up as tests/test_gpu_parity.py::test_bmask_bitwise does (make_seamount takes no mask)"""
+    from oracle.mgoracle import Oracle, seamount_geometry
+    from mgroms_amd.testcases import island_mask
+    o = Oracle(nx, ny, nz, 1, 1, relax_method=meth, bmask=True)
+    for name, a in zip(("dx", "dy", "zeta", "h"), seamount_geometry(nx, ny, 1, 1, 0)):
+        o.field(name)[...] = a
+    o.field("rmask")[...] = island_mask(nx, ny)
+    o.matrices(4e3, 0.0, 0.0)
+    u, v, w = _uvw(nx, ny, nz)
+    o.field("u")[...] = u; o.field("v")[...] = v; o.field("w")[...] = w
+    o.compute_rhs()
+    return o
+
+
+@pytest.mark.parametrize("what", ["simple", "bmask"])
+def test_history_follows_the_reference_gcr_simple_and_masked(mg, what):
+    """64x64x16 four colours, m = 4, to 1e-10 with cmatrix = 'simple' (k_kr_apply_mf<false>) and with the island mask (the stored-slot operator
+    k_kr_apply): entry by entry within 10 x eps_ref of the reference GCR on the same case, same count"""
+    from tests._krylov_ref import eps_ref
+    if what == "simple":
+        e, nref, href = eps_ref(lambda: _oracle(64, 64, 16, "FC", cmatrix="simple"), 4, 1e-10)
+        _gpu(mg, 64, 64, 16, "FC", cmatrix="simple")
+    else:
+        e, nref, href = eps_ref(lambda: _oracle_bmask(64, 64, 16, "FC"), 4, 1e-10)
+        _gpu(mg, 64, 64, 16, "FC", bmask=True)
+        assert np.array_equal(mg.grid(1).b, _oracle_bmask(64, 64, 16, "FC").field("b"))
+    n, hist = _solve(mg, 4, 1e-10)
+    d = _ratio(hist, href, 1e-10)
+    print(f"\n64x64x16 FC m=4 {what}: GPU {n} it, reference {nref} it, eps_ref {e:.3e}, max rel. history difference {d:.3e} = {d / e:.2f} x eps_ref")
+    assert n == nref, (n, nref)
+    assert d <= 10 * e, (d, e)
+    assert mg.nhydro.get_option("krylov_restarts") == 0
+
+
+def test_history_follows_the_reference_gcr_above_the_streaming_threshold(mg):
+    """256x256x64 four colours, m = 4, tol 1e-8: 4.2 M cells, above the 3.56 M from which all three passes run their non-temporal variant.
+    Same count as the reference GCR, history within 10 x eps_ref.  eps_ref is measured on this very case at tol 1e-8, not on a cheaper one
+    (three oracle solves of 10 iterations: 77 s on 16 CPU threads, 21 s each for the plain order; the test prints its own time)."""
+    from tests._krylov_ref import eps_ref
+    import time
+    t0 = time.time()
+    e, nref, href = eps_ref(lambda: _oracle(256, 256, 64, "FC"), 4, 1e-8)
+    t1 = time.time() - t0
+    _gpu(mg, 256, 256, 64, "FC")
+    n, hist = _solve(mg, 4, 1e-8)
+    d = _ratio(hist, href, 1e-8)
+    print(f"\n256x256x64 FC m=4: GPU {n} it, reference {nref} it ({t1:.0f} s for eps_ref), eps_ref {e:.3e}, max rel. history difference {d:.3e} = {d / e:.2f} x eps_ref")
+    assert n == nref, (n, nref)
+    assert d <= 10 * e, (d, e)
+    assert mg.nhydro.get_option("krylov_restarts") == 0
+
+
 @pytest.mark.parametrize("dims,meth,slack", [((128, 128, 16), "FC", 0), ((256, 256, 32), "RB", 1)])
 def test_fewer_iterations_than_plain(mg, dims, meth, slack):
     from tests._krylov_ref import gcr
