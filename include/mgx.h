@@ -180,6 +180,8 @@ int mgx_set_verbose(int level);
  *   between decompositions for the same reason; 5e-5 on the history).
  * "fuse_closing" (default 1; MGX_NO_FUSE_CLOSING): inside solve_p the closing compute_residual(1) of an iteration also restricts its r
  *   for the next Fcycle in the same pass (into grid(2)%r; grid(1)%r is materialised once, after the loop); 0 = the two operators.
+ *   The fused kernel sums the norm in another order than compute_residual: between 1 and 0 the printed norms and hist agree to
+ *   rounding (the tests compare them at 1e-13 relative), not bit for bit.
  * "restrict_chain" (default 1; MGX_NO_RESTRICT_CHAIN): Fcycle's first-leg restrictions below level 1 on closed levels as one launch
  *   (mgx_kernels.hip: k_restrict_chain), 0 = one launch per level; the same bits.
  * "rbseq_fuse" (default 1; MGX_NO_RBSEQ_FUSE): with "rb_seq", walk and per-column correction of a colour in ONE launch -- on large levels

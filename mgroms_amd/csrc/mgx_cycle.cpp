@@ -423,47 +423,75 @@ std::string fortran_e3(double v, int width) {
   return t;
 }
 
+// What the three solve_p drivers share (mg_solvers.f90:17-101): the prints, the timer, the start (p = 0, ||b||, the first residual), the
+// bookkeeping of an iteration (history, "ite = ..." line, fort.100 line) and the summary.  A driver owns what happens between two norms.
+// fort.100 is closed and the timer stopped on every way out, a CHK that returns early included.
+namespace {
+struct SolveRun {
+  Level &L = S.lev[0];
+  const bool talk = S.verbose && S.rank == 0;
+  double *const hist;
+  std::chrono::steady_clock::time_point tstart;
+  FILE *f100 = nullptr;
+  double bnorm = 0.0, res0 = 0.0, rnorm0 = 0.0;   // ||b||; the relative residual of the current iterate and of the first one
+  int nite = 0;
+  explicit SolveRun(double *h) : hist(h) {
+    if (talk) printf(" - solve p:\n");
+    tic(1, "solve");  // mg_solvers.f90:45
+    tstart = std::chrono::steady_clock::now();  // cpu_time(tstart) (:46); wall clock here, the work is on the GPU
+  }
+  SolveRun(const SolveRun &) = delete;
+  ~SolveRun() { if (f100) fclose(f100); toc(1, "solve"); }
+  // *rabs = ||b - A p|| of the starting iterate, r written into grid(1)%r
+  int begin(double *rabs) {
+    if (!S.warm_start) HIPCHK(hipMemsetAsync(L.v.p, 0, L.n3js * sizeof(double), S.stream));  // grid(1)%p = 0 (:35)
+    mgxk_sumsq(S.stream, &L.v, L.v.b, S.d_partial, S.d_scalar); S.n_launch += 2;
+    CHK(global_sum(L, &bnorm)); bnorm = sqrt(bnorm);
+    CHK(residual(1, rabs));
+    res0 = rnorm0 = *rabs / bnorm;
+    if (hist) hist[0] = res0;
+    f100 = talk ? fopen("fort.100", "a") : nullptr;
+    if (f100) fprintf(f100, " %24.16E %d\n", res0, nite);
+    return 0;
+  }
+  bool more(double tol, int maxite) const { return nite < maxite && res0 > tol; }
+  // an iteration has ended with the relative residual rnorm
+  void step(double rnorm) {
+    const double conv = res0 / rnorm;
+    res0 = rnorm;
+    nite++;
+    if (hist) hist[nite] = rnorm;
+    if (talk) printf("ite = %2d: res = %s / conv = %10.3f\n", nite, fortran_e3(rnorm, 10).c_str(), conv);
+    if (f100) fprintf(f100, " %24.16E %24.16E\n", rnorm, conv);
+  }
+  void finish(int *nite_out, double *res_out) {
+    if (talk) {  // the summary block (mg_solvers.f90:83-97)
+      const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - tstart).count();
+      const double np = (double)L.npx * L.npy, ncell = (double)L.nx * L.npx * (double)L.ny * L.npy * (double)L.nz;
+      const double perf = dt * np / (-log(res0 / rnorm0) / log(10.0)) / ncell;
+      printf(" --- summary ---\ntime spent to solve :%8.3f s\nrescaled performance:%s\n ---------------\n", dt, fortran_e3(perf, 10).c_str());
+    }
+    if (nite_out) *nite_out = nite;
+    if (res_out) *res_out = res0;
+  }
+};
+}  // namespace
+
 // mg_solvers.f90:17-101
 int solve_p(double tol, int maxite, int *nite_out, double *res_out, double *hist) {
-  Level &L = S.lev[0];
-  if (S.verbose && S.rank == 0) printf(" - solve p:\n");
-  TicScope ts(1, "solve");  // mg_solvers.f90:45
-  const auto tstart = std::chrono::steady_clock::now();  // cpu_time(tstart) (:46); wall clock here, the work is on the GPU
-  if (!S.warm_start) HIPCHK(hipMemsetAsync(L.v.p, 0, L.n3js * sizeof(double), S.stream));  // grid(1)%p = 0 (:35)
-  mgxk_sumsq(S.stream, &L.v, L.v.b, S.d_partial, S.d_scalar); S.n_launch += 2;
-  double bnorm; CHK(global_sum(L, &bnorm)); bnorm = sqrt(bnorm);
-  int nite = 0;
-  double rnorm; CHK(residual(1, &rnorm));
-  double res0 = rnorm / bnorm;
-  const double rnorm0 = res0;
-  if (hist) hist[0] = res0;
-  FILE *f100 = (S.verbose && S.rank == 0) ? fopen("fort.100", "a") : nullptr;
-  if (f100) fprintf(f100, " %24.16E %d\n", res0, nite);
+  SolveRun run(hist);
+  double rnorm; CHK(run.begin(&rnorm));
   bool have_r2 = false;  // grid(2)%r = restriction of the current level-1 residual, and grid(1)%r not written (residual_closing)
-  while (nite < maxite && res0 > tol) {
+  while (run.more(tol, maxite)) {
     CHK(fcycle(have_r2));
     const int fz = residual_closing(&rnorm);
     if (fz < 0) return 1;
     have_r2 = fz == 1;
     if (!fz) CHK(residual(1, &rnorm));
-    rnorm = rnorm / bnorm;
-    const double conv = res0 / rnorm;
-    res0 = rnorm;
-    nite++;
-    if (hist) hist[nite] = rnorm;
-    if (S.verbose && S.rank == 0) printf("ite = %2d: res = %s / conv = %10.3f\n", nite, fortran_e3(rnorm, 10).c_str(), conv);
-    if (f100) fprintf(f100, " %24.16E %24.16E\n", rnorm, conv);
+    run.step(rnorm / run.bnorm);
   }
-  if (f100) fclose(f100);
   if (have_r2) CHK(residual(1, nullptr));  // grid(1)%r of the final iterate, which the fused closing residual did not write (once per solve)
-  if (S.verbose && S.rank == 0) {  // the summary block (mg_solvers.f90:83-97)
-    const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - tstart).count();
-    const double np = (double)L.npx * L.npy, ncell = (double)L.nx * L.npx * (double)L.ny * L.npy * (double)L.nz;
-    const double perf = dt * np / (-log(res0 / rnorm0) / log(10.0)) / ncell;
-    printf(" --- summary ---\ntime spent to solve :%8.3f s\nrescaled performance:%s\n ---------------\n", dt, fortran_e3(perf, 10).c_str());
-  }
-  if (nite_out) *nite_out = nite;
-  if (res_out) *res_out = res0;
+  run.finish(nite_out, res_out);
   return 0;
 }
 
@@ -565,21 +593,10 @@ void fcycle32() {
 int solve_p_mixed(double tol, int maxite, int *nite_out, double *res_out, double *hist) {
   CHK(mixed_check());
   CHK(mixed_prepare());
-  Level &L = S.lev[0];
-  if (S.verbose && S.rank == 0) printf(" - solve p:\n");
-  TicScope ts(1, "solve");
-  const auto tstart = std::chrono::steady_clock::now();
-  if (!S.warm_start) HIPCHK(hipMemsetAsync(L.v.p, 0, L.n3js * sizeof(double), S.stream));
-  mgxk_sumsq(S.stream, &L.v, L.v.b, S.d_partial, S.d_scalar); S.n_launch += 2;
-  double bnorm; CHK(global_sum(L, &bnorm)); bnorm = sqrt(bnorm);
-  int nite = 0;
-  double rabs; CHK(residual(1, &rabs));   // fp64 r = b - A p, written into grid(1)%r
-  double res0 = rabs / bnorm, rnorm = res0;
-  const double rnorm0 = res0;
-  if (hist) hist[0] = res0;
-  FILE *f100 = (S.verbose && S.rank == 0) ? fopen("fort.100", "a") : nullptr;
-  if (f100) fprintf(f100, " %24.16E %d\n", res0, nite);
-  while (nite < maxite && res0 > tol) {
+  SolveRun run(hist);
+  Level &L = run.L;
+  double rabs; CHK(run.begin(&rabs));   // fp64 r = b - A p, written into grid(1)%r
+  while (run.more(tol, maxite)) {
     // f = s r with s = 1 / ||r||: |f| <= 1, nothing underflows however small the residual has become; e = 0
     const double sc = rabs > 0.0 ? 1.0 / rabs : 1.0;
     mgxx_to32(S.stream, &L.v, &L.v32, L.v.r, L.v32.f, sc); S.n_launch++;
@@ -587,24 +604,10 @@ int solve_p_mixed(double tol, int maxite, int *nite_out, double *res_out, double
     fcycle32();
     mgxx_to64(S.stream, &L.v, &L.v32, L.v32.e, L.v.p, rabs > 0.0 ? rabs : 1.0, 1); S.n_launch++;   // p += e / s, halo images included
     CHK(residual(1, &rabs));
-    rnorm = rabs / bnorm;
-    const double conv = res0 / rnorm;
-    res0 = rnorm;
-    nite++;
     S.n_mixed++;
-    if (hist) hist[nite] = rnorm;
-    if (S.verbose && S.rank == 0) printf("ite = %2d: res = %s / conv = %10.3f\n", nite, fortran_e3(rnorm, 10).c_str(), conv);
-    if (f100) fprintf(f100, " %24.16E %24.16E\n", rnorm, conv);
+    run.step(rabs / run.bnorm);
   }
-  if (f100) fclose(f100);
-  if (S.verbose && S.rank == 0) {
-    const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - tstart).count();
-    const double np = (double)L.npx * L.npy, ncell = (double)L.nx * L.npx * (double)L.ny * L.npy * (double)L.nz;
-    const double perf = dt * np / (-log(res0 / rnorm0) / log(10.0)) / ncell;
-    printf(" --- summary ---\ntime spent to solve :%8.3f s\nrescaled performance:%s\n ---------------\n", dt, fortran_e3(perf, 10).c_str());
-  }
-  if (nite_out) *nite_out = nite;
-  if (res_out) *res_out = res0;
+  run.finish(nite_out, res_out);
   return 0;
 }
 
@@ -643,27 +646,16 @@ int krylov_allreduce(double *buf, int n) {
 int solve_p_krylov(double tol, int maxite, int *nite_out, double *res_out, double *hist) {
   const int m = S.krylov;
   CHK(krylov_prepare(m));
-  Level &L = S.lev[0];
-  if (S.verbose && S.rank == 0) printf(" - solve p:\n");
-  TicScope ts(1, "solve");
-  const auto tstart = std::chrono::steady_clock::now();
-  if (!S.warm_start) HIPCHK(hipMemsetAsync(L.v.p, 0, L.n3js * sizeof(double), S.stream));
-  mgxk_sumsq(S.stream, &L.v, L.v.b, S.d_partial, S.d_scalar); S.n_launch += 2;
-  double bnorm; CHK(global_sum(L, &bnorm)); bnorm = sqrt(bnorm);
-  int nite = 0;
-  double rnorm; CHK(residual(1, &rnorm));   // the true residual, into grid(1)%r
-  double res0 = rnorm / bnorm;
-  const double rnorm0 = res0;
-  if (hist) hist[0] = res0;
-  struct F100 { FILE *f; ~F100() { if (f) fclose(f); } } f100 = {(S.verbose && S.rank == 0) ? fopen("fort.100", "a") : nullptr};
-  if (f100.f) fprintf(f100.f, " %24.16E %d\n", res0, nite);
+  SolveRun run(hist);
+  Level &L = run.L;
+  double rnorm; CHK(run.begin(&rnorm));   // the true residual, into grid(1)%r
   ViewSwap own(L.v);
   double *sc = S.kr_sc, *qq = S.kr_sc + 16;
   int kept = 0, head = 0;   // retained pairs: the `kept` slots before `head` in the ring of m + 1; head = the pair in work
   bool fresh = true, broke = false;   // fresh: grid(1)%r is the true residual of grid(1)%p
   S.kr_restarts = 0;
   for (;;) {
-    while (nite < maxite && res0 > tol) {
+    while (run.more(tol, maxite)) {
       double *z = S.kr_z[head], *q = S.kr_q[head];
       {  // z = M r: Fcycle on (p, b) = (0, r).  The first leg restricts the view's r, the rest of the cycle may use it as scratch.
         HIPCHK(hipMemsetAsync(z, 0, L.n3js * sizeof(double), S.stream));
@@ -695,32 +687,19 @@ int solve_p_krylov(double tol, int maxite, int *nite_out, double *res_out, doubl
       }
       fresh = false;
       if (!(s2 >= 0.0)) { broke = true; break; }   // no step was taken (s == 0 or a non-finite scalar): p is what it was
-      rnorm = sqrt(s2) / bnorm;
-      const double conv = res0 / rnorm;
-      res0 = rnorm;
-      nite++;
-      if (hist) hist[nite] = rnorm;
-      if (S.verbose && S.rank == 0) printf("ite = %2d: res = %s / conv = %10.3f\n", nite, fortran_e3(rnorm, 10).c_str(), conv);
-      if (f100.f) fprintf(f100.f, " %24.16E %24.16E\n", rnorm, conv);
+      run.step(sqrt(s2) / run.bnorm);
       if (kept < m) kept++;
       head = (head + 1) % (m + 1);
     }
     if (fresh) break;
     CHK(residual(1, &rnorm));   // b - A p into grid(1)%r: the word that counts
     fresh = true;
-    res0 = rnorm / bnorm;
-    if (hist) hist[nite] = res0;
-    if (broke || nite >= maxite || !(res0 > tol)) break;
+    run.res0 = rnorm / run.bnorm;   // (not printed: the lines above are the recurrence's)
+    if (hist) hist[run.nite] = run.res0;
+    if (broke || run.nite >= maxite || !(run.res0 > tol)) break;
     S.kr_restarts++; kept = 0;   // the recurrence had drifted: go on from the true residual with no history
   }
-  if (S.verbose && S.rank == 0) {
-    const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - tstart).count();
-    const double np = (double)L.npx * L.npy, ncell = (double)L.nx * L.npx * (double)L.ny * L.npy * (double)L.nz;
-    const double perf = dt * np / (-log(res0 / rnorm0) / log(10.0)) / ncell;
-    printf(" --- summary ---\ntime spent to solve :%8.3f s\nrescaled performance:%s\n ---------------\n", dt, fortran_e3(perf, 10).c_str());
-  }
-  if (nite_out) *nite_out = nite;
-  if (res_out) *res_out = res0;
+  run.finish(nite_out, res_out);
   return 0;
 }
 

@@ -8,24 +8,19 @@
 // the JS layout (mgx_internal.h), so every global access of a wave is one contiguous 512-byte run.
 #include <cstdlib>
 
-#include "mgx_device.h"
+#include "mgx_operator.h"
 
 // ------------------------------------------------------------------------------------------------
-// residual r = b - A p on the interior and per-block partial sums of r^2.  mg_relax.f90:421-515.
-// gridDim.z = 2: z = 0 handles the odd-j half-rows, z = 1 the even-j ones.
+// residual r = b - A p on the interior and per-block partial sums of r^2.  mg_relax.f90:421-515: the column of mgx_operator.h with
+// the right-hand side b; a row goes to r with its physical images and into the norm.
+// 1-D grid of gx * gy * 2 blocks (op_block_map): bz = 0 handles the odd-j half-rows, bz = 1 the even-j ones.
 // ------------------------------------------------------------------------------------------------
+#define RES_RHS(ko) b[ko]
+#define RES_SINK(ro, ko, rr) { r[ko] = rr; mirror_store(L, r, ro, jcol, i, c, rr, ph); acc = acc + rr * rr; }
 template <bool REAL>
 __global__ __launch_bounds__(256) void k_residual(LevView L, double *__restrict__ partial, int want_norm, int gx, int gy, Sides ph, int stream) {
-  // 1-D grid of gx*gy*2 blocks; XCD-aware map (see k_relax_nz): each XCD owns a contiguous range of plane groups,
-  // and the two j-parities of a plane group run back to back on the same XCD (they read the same rows)
   int bx, by, bz;
-  {
-    const int per = gx * 2;
-    int grp, local;
-    if ((gy & 7) == 0) { const int xcd = blockIdx.x & 7; local = blockIdx.x >> 3; grp = xcd * (gy >> 3) + local / per; local -= (local / per) * per; }
-    else { grp = blockIdx.x / per; local = blockIdx.x - grp * per; }
-    by = grp; bz = local / gx; bx = local - bz * gx;
-  }
+  op_block_map(gx, gy, bx, by, bz);
   const int jh = bx * WAVE + threadIdx.x;
   const int i = 1 + by * blockDim.y + threadIdx.y;
   const int jodd = bz == 0;
@@ -33,92 +28,21 @@ __global__ __launch_bounds__(256) void k_residual(LevView L, double *__restrict_
   if (jh < (L.ny >> 1) && i <= L.nx) {
     int c, jm, jp;
     COL_POS(L, jh, jodd, c, jm, jp)
-    const long long RS = L.RS;
-    const int nz = L.nz;
-    const double *__restrict__ p = L.p, *__restrict__ b = L.b;
+    const double *__restrict__ b = L.b;
     double *__restrict__ r = L.r;
-    const double *__restrict__ a1 = L.cA[0], *__restrict__ a2 = L.cA[1], *__restrict__ a3 = L.cA[2],
-                 *__restrict__ a4 = L.cA[3], *__restrict__ a5 = L.cA[4], *__restrict__ a6 = L.cA[5],
-                 *__restrict__ a7 = L.cA[6], *__restrict__ a8 = L.cA[7];
-    const long long o = (long long)i * L.plane, om = o - L.plane, op = o + L.plane;
-    double pjm_m, pjm_0, pjm_p, pim_m, pim_0, pim_p, pc_m, pc_0, pc_p, a2_0, a2_p;
-    double m3_m, m3_0, m4_0, m5_p, n6_m, n6_0, n7_0, n8_p, m3_p, m4_p, n6_p, n7_p;
-#define LOAD_ROW(q, PJM, PIM, PC, A2, M3, M4, M5, N6, N7, N8)                  \
-  {                                                                            \
-    const long long ro = (long long)((q)-1) * RS;                              \
-    PJM = p[o + ro + jm]; PIM = p[om + ro + c]; PC = p[o + ro + c]; A2 = a2[o + ro + c]; \
-    const double pj_ = p[o + ro + jp], pi_ = p[op + ro + c];                   \
-    M3 = a3[o + ro + jp] * pj_; M4 = a4[o + ro + jp] * pj_; M5 = a5[o + ro + jp] * pj_; \
-    N6 = a6[op + ro + c] * pi_; N7 = a7[op + ro + c] * pi_; N8 = a8[op + ro + c] * pi_; \
-  }
-    double dum5, dum8;
-    LOAD_ROW(1, pjm_0, pim_0, pc_0, a2_0, m3_0, m4_0, dum5, n6_0, n7_0, dum8);
-    LOAD_ROW(2, pjm_p, pim_p, pc_p, a2_p, m3_p, m4_p, m5_p, n6_p, n7_p, n8_p);
-    (void)dum5; (void)dum8;
-    // k = 1 (:464-482)
-    double rr = b[o + c] - a1[o + c] * pc_0 - a2_p * pc_p - a3[o + c] * pjm_p - a4[o + c] * pjm_0 - m4_0 - m5_p
-                - a6[o + c] * pim_p - a7[o + c] * pim_0 - n7_0 - n8_p;
-    if (REAL)
-      rr = rr - a5[o + c] * p[om + jp] - a5[op + jm] * p[op + jm] - a8[o + c] * p[om + jm] - a8[op + jp] * p[op + jp];
-    const int jcol = jodd ? 2 * jh + 1 : 2 * jh + 2;
-    r[o + c] = rr;
-    mirror_store(L, r, 0, jcol, i, c, rr, ph);
-    acc = acc + rr * rr;
-    for (int k = 2; k <= nz - 1; k++) {  // (:484-496)
-      pjm_m = pjm_0; pjm_0 = pjm_p; pim_m = pim_0; pim_0 = pim_p; pc_m = pc_0; pc_0 = pc_p; a2_0 = a2_p;
-      m3_m = m3_0; m3_0 = m3_p; m4_0 = m4_p; n6_m = n6_0; n6_0 = n6_p; n7_0 = n7_p;
-      LOAD_ROW(k + 1, pjm_p, pim_p, pc_p, a2_p, m3_p, m4_p, m5_p, n6_p, n7_p, n8_p);
-      const long long ko = o + (long long)(k - 1) * RS + c;
-      rr = b[ko] - a1[ko] * pc_0 - a2_0 * pc_m - a2_p * pc_p - a3[ko] * pjm_p - m3_m - a4[ko] * pjm_0 - m4_0
-                 - a5[ko] * pjm_m - m5_p - a6[ko] * pim_p - n6_m - a7[ko] * pim_0 - n7_0 - a8[ko] * pim_m - n8_p;
-      r[ko] = rr;
-      mirror_store(L, r, (long long)(k - 1) * RS, jcol, i, c, rr, ph);
-      acc = acc + rr * rr;
-    }
-    {  // k = nz (:498-509)
-      pjm_m = pjm_0; pjm_0 = pjm_p; pim_m = pim_0; pim_0 = pim_p; pc_m = pc_0; pc_0 = pc_p; a2_0 = a2_p;
-      m3_m = m3_0; m4_0 = m4_p; n6_m = n6_0; n7_0 = n7_p;
-      const long long ko = o + (long long)(nz - 1) * RS + c;
-      rr = b[ko] - a1[ko] * pc_0 - a2_0 * pc_m - m3_m - a4[ko] * pjm_0 - m4_0 - a5[ko] * pjm_m - n6_m
-                 - a7[ko] * pim_0 - n7_0 - a8[ko] * pim_m;
-      r[ko] = rr;
-      mirror_store(L, r, (long long)(nz - 1) * RS, jcol, i, c, rr, ph);
-      acc = acc + rr * rr;
-    }
-#undef LOAD_ROW
+    OP_COLUMN(RES_RHS, RES_SINK)
   }
   if (!want_norm) return;
-  // block reduction: wave shuffle, then LDS across the waves of the block (deterministic order)
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  __shared__ double red[16];
-  const int tid = threadIdx.y * blockDim.x + threadIdx.x, w = tid >> 6;
-  if ((tid & 63) == 0) red[w] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    double s = 0.0;
-    const int nw = (blockDim.x * blockDim.y + 63) >> 6;
-    for (int q = 0; q < nw; q++) s += red[q];
-    partial[blockIdx.x] = s;
-  }
+  OP_BLOCK_SUM(acc, partial, blockIdx.x)
 }
 
-// residual with matrix-free cross terms (see relax_col_mf): 17 streams per cell instead of 22.  The diagonal of the interior rows is
-// rebuilt from the fourteen couplings the row holds anyway (mg_define_matrix.f90:632-639, summed in the reference's order: the same bits
-// as the stored slot 1 -- as the smoother and the fused residual+restriction do); rows 1 and nz, whose formula differs, read the stored one.
-// The j-1 / j+1 neighbours of p and zy sit side by side in the other half-row: one 16-byte load each.  What only this lane reads (b, a2)
-// is streamed past the caches on a level that does not fit them.
+// residual with matrix-free cross terms (OP_COLUMN_MF, mgx_operator.h): b and r of a level that does not fit the caches are streamed past them
+#define RES_RHS_MF(ko) ld_rt(b + ko, stream)
+#define RES_SINK_MF(ro, ko, rr) { st_rt(r + ko, rr, stream); mirror_store(L, r, ro, jodd ? 2 * jh + 1 : 2 * jh + 2, i, c, rr, ph); acc = acc + rr * rr; }
 template <bool REAL>
 __global__ __launch_bounds__(256) void k_residual_mf(LevView L, double *__restrict__ partial, int want_norm, int gx, int gy, Sides ph, int stream) {
-  // 1-D grid of gx*gy*2 blocks; XCD-aware map (see k_relax_nz): each XCD owns a contiguous range of plane groups,
-  // and the two j-parities of a plane group run back to back on the same XCD (they read the same rows)
   int bx, by, bz;
-  {
-    const int per = gx * 2;
-    int grp, local;
-    if ((gy & 7) == 0) { const int xcd = blockIdx.x & 7; local = blockIdx.x >> 3; grp = xcd * (gy >> 3) + local / per; local -= (local / per) * per; }
-    else { grp = blockIdx.x / per; local = blockIdx.x - grp * per; }
-    by = grp; bz = local / gx; bx = local - bz * gx;
-  }
+  op_block_map(gx, gy, bx, by, bz);
   const int jh = bx * WAVE + threadIdx.x;
   const int i = 1 + by * blockDim.y + threadIdx.y;
   const int jodd = bz == 0;
@@ -126,81 +50,12 @@ __global__ __launch_bounds__(256) void k_residual_mf(LevView L, double *__restri
   if (jh < (L.ny >> 1) && i <= L.nx) {
     int c, jm, jp;
     COL_POS(L, jh, jodd, c, jm, jp)
-    const long long RS = L.RS;
-    const int nz = L.nz;
-    const double *__restrict__ p = L.p, *__restrict__ b = L.b;
+    const double *__restrict__ b = L.b;
     double *__restrict__ r = L.r;
-    const double *__restrict__ a1 = L.cA[0], *__restrict__ a2 = L.cA[1], *__restrict__ a4 = L.cA[3], *__restrict__ a5 = L.cA[4],
-                 *__restrict__ a7 = L.cA[6], *__restrict__ a8 = L.cA[7], *__restrict__ zy = L.zy, *__restrict__ zx = L.zx;
-    const long long o = (long long)i * L.plane, om = o - L.plane, op = o + L.plane;
-    const double qrt = 0.25;
-    // Every request is unconditional (rows past the top clamped to nz, never used) and issued ONE STEP before its first use: the window row
-    // k+2 and the own-row values of k+1 are in flight while row k is computed.  (A request inside `if (k + 2 <= nz)` made the number of
-    // outstanding loads path-dependent: the compiler then waits for vmcnt(0) at every step and the look-ahead is void.)
-    double pc_m = 0, pc_0, pc_p, pc_n, pjm_m = 0, pjm_0, pjm_p, pjm_n, pim_m = 0, pim_0, pim_p, pim_n, pjp_m = 0, pjp_0, pjp_p, pjp_n, pip_m = 0, pip_0, pip_p, pip_n;
-    double zy_m = 0, zy_0, zy_p, zy_n, zx_m = 0, zx_0, zx_p, zx_n, a2_0, a2_p, a2_n;
-    double zyjm, zyjp, zxim, zxip, a4o, a4jp, a7o, a7ip, bk, zyjm_n, zyjp_n, zxim_n, zxip_n, a4o_n, a4jp_n, a7o_n, a7ip_n, bk_n;
-#define LOAD_WIN(q, PC, PJM, PIM, PJP, PIP, ZY, ZX, A2)                        \
-  { const long long ro = (long long)(((q) <= nz ? (q) : nz) - 1) * RS;         \
-    PC = p[o + ro + c]; LD_PAIR(p + o + ro + jm, PJM, PJP) PIM = p[om + ro + c]; PIP = p[op + ro + c]; \
-    ZY = *(zy + o + ro + c); ZX = *(zx + o + ro + c); A2 = ld_rt(a2 + o + ro + c, stream); }
-#define LOAD_ROWV(q, ZYJM, ZYJP, ZXIM, ZXIP, A4O, A4JP, A7O, A7IP, BK)         \
-  { const long long ro = (long long)(((q) <= nz ? (q) : nz) - 1) * RS, ko = o + ro + c; \
-    LD_PAIR(zy + o + ro + jm, ZYJM, ZYJP) ZXIM = zx[om + ro + c]; ZXIP = zx[op + ro + c]; \
-    A4O = *(a4 + ko); A4JP = a4[o + ro + jp]; A7O = *(a7 + ko); A7IP = a7[op + ro + c]; BK = ld_rt(b + ko, stream); }
-    // rows 1 and nz: stored diagonal; row 1: the k = 1 diagonal slots and the four corner values of p (cmatrix = 'real', mg_relax.f90:475-479)
-    const double d_first = a1[o + c], d_last = a1[o + (long long)(nz - 1) * RS + c];
-    double e0 = 0, e1 = 0, e2 = 0, e3 = 0, e4 = 0, e5 = 0, e6 = 0, e7 = 0;
-    if (REAL) { e0 = a5[o + c]; e1 = p[om + jp]; e2 = a5[op + jm]; e3 = p[op + jm]; e4 = a8[o + c]; e5 = p[om + jm]; e6 = a8[op + jp]; e7 = p[op + jp]; }
-    LOAD_WIN(1, pc_0, pjm_0, pim_0, pjp_0, pip_0, zy_0, zx_0, a2_0)
-    LOAD_ROWV(1, zyjm, zyjp, zxim, zxip, a4o, a4jp, a7o, a7ip, bk)
-    LOAD_WIN(2, pc_p, pjm_p, pim_p, pjp_p, pip_p, zy_p, zx_p, a2_p)
-    for (int k = 1; k <= nz; k++) {
-      const long long ro = (long long)(k - 1) * RS, ko = o + ro + c;
-      LOAD_WIN(k + 2, pc_n, pjm_n, pim_n, pjp_n, pip_n, zy_n, zx_n, a2_n)
-      LOAD_ROWV(k + 1, zyjm_n, zyjp_n, zxim_n, zxip_n, a4o_n, a4jp_n, a7o_n, a7ip_n, bk_n)
-      double rr;
-      if (k == 1) {
-        rr = bk - d_first * pc_0 - a2_p * pc_p - (qrt * (zy_p + zyjm)) * pjm_p - a4o * pjm_0 - a4jp * pjp_0
-                   - (-qrt * (zyjp + zy_p)) * pjp_p - (qrt * (zx_p + zxim)) * pim_p - a7o * pim_0 - a7ip * pip_0
-                   - (-qrt * (zxip + zx_p)) * pip_p;
-        if (REAL) rr = rr - e0 * e1 - e2 * e3 - e4 * e5 - e6 * e7;
-      } else if (k < nz) {
-        const double c3 = qrt * (zy_p + zyjm), c3m = qrt * (zyjp + zy_m), c5 = -qrt * (zy_m + zyjm), c5m = -qrt * (zyjp + zy_p);
-        const double c6 = qrt * (zx_p + zxim), c6m = qrt * (zxip + zx_m), c8 = -qrt * (zx_m + zxim), c8m = -qrt * (zxip + zx_p);
-        const double dk = -a2_0 - a2_p - a4o - a4jp - a7o - a7ip - c6 - c6m - c8 - c8m - c3 - c3m - c5 - c5m;  // = cA(1,k,j,i), mg_define_matrix.f90:632-639
-        rr = bk - dk * pc_0 - a2_0 * pc_m - a2_p * pc_p - c3 * pjm_p - c3m * pjp_m
-                   - a4o * pjm_0 - a4jp * pjp_0 - c5 * pjm_m - c5m * pjp_p
-                   - c6 * pim_p - c6m * pip_m - a7o * pim_0 - a7ip * pip_0
-                   - c8 * pim_m - c8m * pip_p;
-      } else {
-        rr = bk - d_last * pc_0 - a2_0 * pc_m - (qrt * (zyjp + zy_m)) * pjp_m - a4o * pjm_0 - a4jp * pjp_0
-                   - (-qrt * (zy_m + zyjm)) * pjm_m - (qrt * (zxip + zx_m)) * pip_m - a7o * pim_0 - a7ip * pip_0
-                   - (-qrt * (zx_m + zxim)) * pim_m;
-      }
-      st_rt(r + ko, rr, stream);
-      mirror_store(L, r, ro, jodd ? 2 * jh + 1 : 2 * jh + 2, i, c, rr, ph);
-      acc = acc + rr * rr;
-      pc_m = pc_0; pc_0 = pc_p; pc_p = pc_n; pjm_m = pjm_0; pjm_0 = pjm_p; pjm_p = pjm_n; pim_m = pim_0; pim_0 = pim_p; pim_p = pim_n;
-      pjp_m = pjp_0; pjp_0 = pjp_p; pjp_p = pjp_n; pip_m = pip_0; pip_0 = pip_p; pip_p = pip_n;
-      zy_m = zy_0; zy_0 = zy_p; zy_p = zy_n; zx_m = zx_0; zx_0 = zx_p; zx_p = zx_n; a2_0 = a2_p; a2_p = a2_n;
-      zyjm = zyjm_n; zyjp = zyjp_n; zxim = zxim_n; zxip = zxip_n; a4o = a4o_n; a4jp = a4jp_n; a7o = a7o_n; a7ip = a7ip_n; bk = bk_n;
-    }
-#undef LOAD_ROWV
-#undef LOAD_WIN
+    OP_COLUMN_MF(RES_RHS_MF, RES_SINK_MF)
   }
   if (!want_norm) return;
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  __shared__ double red[16];
-  const int tid = threadIdx.y * blockDim.x + threadIdx.x, w = tid >> 6;
-  if ((tid & 63) == 0) red[w] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    double s = 0.0;
-    const int nw = (blockDim.x * blockDim.y + 63) >> 6;
-    for (int q = 0; q < nw; q++) s += red[q];
-    partial[blockIdx.x] = s;
-  }
+  OP_BLOCK_SUM(acc, partial, blockIdx.x)
 }
 
 // sum of squares of the interior of a JS field (bnorm of solve_p, mg_solvers.f90:50)
@@ -213,17 +68,7 @@ __global__ __launch_bounds__(256) void k_sumsq(LevView L, const double *__restri
     const long long o = (long long)i * L.plane + c;
     for (int k = 0; k < L.nz; k++) { const double v = a[o + (long long)k * L.RS]; acc += v * v; }
   }
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  __shared__ double red[16];
-  const int tid = threadIdx.y * blockDim.x + threadIdx.x, w = tid >> 6;
-  if ((tid & 63) == 0) red[w] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    double s = 0.0;
-    const int nw = (blockDim.x * blockDim.y + 63) >> 6;
-    for (int q = 0; q < nw; q++) s += red[q];
-    partial[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s;
-  }
+  OP_BLOCK_SUM(acc, partial, (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x)
 }
 
 // inner product of the interiors of two JS fields (norm(lev,x,y), mg_solvers.f90:180-200)
@@ -236,17 +81,7 @@ __global__ __launch_bounds__(256) void k_dot(LevView L, const double *__restrict
     const long long o = (long long)i * L.plane + c;
     for (int k = 0; k < L.nz; k++) acc += a[o + (long long)k * L.RS] * b[o + (long long)k * L.RS];
   }
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  __shared__ double red[16];
-  const int tid = threadIdx.y * blockDim.x + threadIdx.x, w = tid >> 6;
-  if ((tid & 63) == 0) red[w] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    double s = 0.0;
-    const int nw = (blockDim.x * blockDim.y + 63) >> 6;
-    for (int q = 0; q < nw; q++) s += red[q];
-    partial[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s;
-  }
+  OP_BLOCK_SUM(acc, partial, (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x)
 }
 
 // second stage: one block sums the partials in index order -> out[0]

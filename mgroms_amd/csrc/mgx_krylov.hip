@@ -4,11 +4,12 @@
 //   1. k_kr_apply[_mf]: q = A z and the inner products (q, q_i) with the retained q_i
 //   2. k_kr_ortho:      q -= sum beta_i q_i, z -= sum beta_i z_i (beta_i = (q, q_i) / (q_i, q_i)), s = (q, q), t = (r, q)
 //   3. k_kr_update:     p += (t / s) z, r -= (t / s) q, ||r||^2
-// The scalars stay in device memory between the launches (kernels 2 and 3 read them there).  The operator is the one of k_residual /
-// k_residual_mf with b = 0 and the sign turned: the same products subtracted in the same order, so q is bit for bit the negative of what
-// compute_residual writes for a zero right-hand side.  Kernels 2 and 3 are streaming passes over WHOLE arrays (halo and padding included:
-// z and p keep consistent halos by linearity, q and r are zero / untouched there) with 16-byte accesses; only interior cells enter the sums.
-#include "mgx_device.h"
+// The scalars stay in device memory between the launches (kernels 2 and 3 read them there).  Pass 1 is the column text of k_residual /
+// k_residual_mf itself (mgx_operator.h) with the right-hand side 0 and each row negated on its way out: q is the negative of what
+// compute_residual writes for b = 0 because both are compiled from that one text.  Kernels 2 and 3 are streaming passes over WHOLE arrays
+// (halo and padding included: z and p keep consistent halos by linearity, q and r are zero / untouched there) with 16-byte accesses; only
+// interior cells enter the sums.
+#include "mgx_operator.h"
 
 #define KR_MAX 8
 struct KrDirs { const double *q[KR_MAX]; const double *z[KR_MAX]; int slot[KR_MAX]; int n; };  // slot: where (q_i, q_i) is filed
@@ -34,87 +35,19 @@ __device__ __forceinline__ void kr_block_sums(double (&acc)[NV], int nv, double 
   if (tid < nv) partial[(long long)tid * nblk + blk] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
 }
 
-// the block -> (j-chunk, plane group, j parity) map of k_residual: each XCD owns a contiguous range of plane groups
-__device__ __forceinline__ void kr_block_map(int gx, int gy, int &bx, int &by, int &bz) {
-  const int per = gx * 2;
-  int grp, local;
-  if ((gy & 7) == 0) { const int xcd = blockIdx.x & 7; local = blockIdx.x >> 3; grp = xcd * (gy >> 3) + local / per; local -= (local / per) * per; }
-  else { grp = blockIdx.x / per; local = blockIdx.x - grp * per; }
-  by = grp; bz = local / gx; bx = local - bz * gx;
-}
-
 // ------------------------------------------------------------------------------------------------
-// 1. q = A z from the stored slots (the operator of k_residual, mg_relax.f90:421-515), z = L.p with valid halos
+// 1. q = A z, z = L.p with valid halos: the operator's column (mgx_operator.h) on the right-hand side 0; a row goes, negated, to q and
+// into the products with the retained q_i.  From the stored slots, or matrix-free.
 // ------------------------------------------------------------------------------------------------
-template <bool REAL>
-__global__ __launch_bounds__(256) void k_kr_apply(LevView L, double *__restrict__ qout, KrDirs D, double *__restrict__ partial, int gx, int gy, int stream) {
-  int bx, by, bz;
-  kr_block_map(gx, gy, bx, by, bz);
-  const int jh = bx * WAVE + threadIdx.x;
-  const int i = 1 + by * blockDim.y + threadIdx.y;
-  const int jodd = bz == 0;
-  double acc[KR_MAX] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (jh < (L.ny >> 1) && i <= L.nx) {
-    int c, jm, jp;
-    COL_POS(L, jh, jodd, c, jm, jp)
-    const long long RS = L.RS;
-    const int nz = L.nz;
-    const double *__restrict__ p = L.p;
-    const double *__restrict__ a1 = L.cA[0], *__restrict__ a2 = L.cA[1], *__restrict__ a3 = L.cA[2],
-                 *__restrict__ a4 = L.cA[3], *__restrict__ a5 = L.cA[4], *__restrict__ a6 = L.cA[5],
-                 *__restrict__ a7 = L.cA[6], *__restrict__ a8 = L.cA[7];
-    const long long o = (long long)i * L.plane, om = o - L.plane, op = o + L.plane;
-    double pjm_m, pjm_0, pjm_p, pim_m, pim_0, pim_p, pc_m, pc_0, pc_p, a2_0, a2_p;
-    double m3_m, m3_0, m4_0, m5_p, n6_m, n6_0, n7_0, n8_p, m3_p, m4_p, n6_p, n7_p;
-#define LOAD_ROW(q, PJM, PIM, PC, A2, M3, M4, M5, N6, N7, N8)                  \
-  {                                                                            \
-    const long long ro = (long long)((q)-1) * RS;                              \
-    PJM = p[o + ro + jm]; PIM = p[om + ro + c]; PC = p[o + ro + c]; A2 = a2[o + ro + c]; \
-    const double pj_ = p[o + ro + jp], pi_ = p[op + ro + c];                   \
-    M3 = a3[o + ro + jp] * pj_; M4 = a4[o + ro + jp] * pj_; M5 = a5[o + ro + jp] * pj_; \
-    N6 = a6[op + ro + c] * pi_; N7 = a7[op + ro + c] * pi_; N8 = a8[op + ro + c] * pi_; \
-  }
-#define PUT_ROW(ko, rr)                                                        \
+#define KR_RHS(ko) zero
+#define KR_SINK(ro, ko, rr)                                                    \
   { const double qv = -(rr);                                                   \
     st_rt(qout + (ko), qv, stream);                                            \
     _Pragma("unroll") for (int n = 0; n < KR_MAX; n++) if (n < D.n) acc[n] = acc[n] + qv * D.q[n][ko]; }
-    const double zero = 0.0;
-    double dum5, dum8;
-    LOAD_ROW(1, pjm_0, pim_0, pc_0, a2_0, m3_0, m4_0, dum5, n6_0, n7_0, dum8);
-    LOAD_ROW(2, pjm_p, pim_p, pc_p, a2_p, m3_p, m4_p, m5_p, n6_p, n7_p, n8_p);
-    (void)dum5; (void)dum8;
-    double rr = zero - a1[o + c] * pc_0 - a2_p * pc_p - a3[o + c] * pjm_p - a4[o + c] * pjm_0 - m4_0 - m5_p
-                - a6[o + c] * pim_p - a7[o + c] * pim_0 - n7_0 - n8_p;
-    if (REAL)
-      rr = rr - a5[o + c] * p[om + jp] - a5[op + jm] * p[op + jm] - a8[o + c] * p[om + jm] - a8[op + jp] * p[op + jp];
-    PUT_ROW(o + c, rr)
-    for (int k = 2; k <= nz - 1; k++) {
-      pjm_m = pjm_0; pjm_0 = pjm_p; pim_m = pim_0; pim_0 = pim_p; pc_m = pc_0; pc_0 = pc_p; a2_0 = a2_p;
-      m3_m = m3_0; m3_0 = m3_p; m4_0 = m4_p; n6_m = n6_0; n6_0 = n6_p; n7_0 = n7_p;
-      LOAD_ROW(k + 1, pjm_p, pim_p, pc_p, a2_p, m3_p, m4_p, m5_p, n6_p, n7_p, n8_p);
-      const long long ko = o + (long long)(k - 1) * RS + c;
-      rr = zero - a1[ko] * pc_0 - a2_0 * pc_m - a2_p * pc_p - a3[ko] * pjm_p - m3_m - a4[ko] * pjm_0 - m4_0
-                - a5[ko] * pjm_m - m5_p - a6[ko] * pim_p - n6_m - a7[ko] * pim_0 - n7_0 - a8[ko] * pim_m - n8_p;
-      PUT_ROW(ko, rr)
-    }
-    {
-      pjm_m = pjm_0; pjm_0 = pjm_p; pim_m = pim_0; pim_0 = pim_p; pc_m = pc_0; pc_0 = pc_p; a2_0 = a2_p;
-      m3_m = m3_0; m4_0 = m4_p; n6_m = n6_0; n7_0 = n7_p;
-      const long long ko = o + (long long)(nz - 1) * RS + c;
-      rr = zero - a1[ko] * pc_0 - a2_0 * pc_m - m3_m - a4[ko] * pjm_0 - m4_0 - a5[ko] * pjm_m - n6_m
-                - a7[ko] * pim_0 - n7_0 - a8[ko] * pim_m;
-      PUT_ROW(ko, rr)
-    }
-#undef LOAD_ROW
-  }
-  if (D.n) kr_block_sums<KR_MAX>(acc, D.n, partial, blockIdx.x, gridDim.x);
-}
-
-// 1. matrix-free: the operator of k_residual_mf (cross terms from the slopes, the interior rows' diagonal rebuilt in the reference's order)
 template <bool REAL>
-__global__ __launch_bounds__(256) void k_kr_apply_mf(LevView L, double *__restrict__ qout, KrDirs D, double *__restrict__ partial, int gx, int gy, int stream) {
+__global__ __launch_bounds__(256) void k_kr_apply(LevView L, double *__restrict__ qout, KrDirs D, double *__restrict__ partial, int gx, int gy, int stream) {
   int bx, by, bz;
-  kr_block_map(gx, gy, bx, by, bz);
+  op_block_map(gx, gy, bx, by, bz);
   const int jh = bx * WAVE + threadIdx.x;
   const int i = 1 + by * blockDim.y + threadIdx.y;
   const int jodd = bz == 0;
@@ -122,66 +55,28 @@ __global__ __launch_bounds__(256) void k_kr_apply_mf(LevView L, double *__restri
   if (jh < (L.ny >> 1) && i <= L.nx) {
     int c, jm, jp;
     COL_POS(L, jh, jodd, c, jm, jp)
-    const long long RS = L.RS;
-    const int nz = L.nz;
-    const double *__restrict__ p = L.p;
-    const double *__restrict__ a1 = L.cA[0], *__restrict__ a2 = L.cA[1], *__restrict__ a4 = L.cA[3], *__restrict__ a5 = L.cA[4],
-                 *__restrict__ a7 = L.cA[6], *__restrict__ a8 = L.cA[7], *__restrict__ zy = L.zy, *__restrict__ zx = L.zx;
-    const long long o = (long long)i * L.plane, om = o - L.plane, op = o + L.plane;
-    const double qrt = 0.25, zero = 0.0;
-    // as in k_residual_mf: every request unconditional (rows past the top clamped to nz) and issued one step before its first use
-    double pc_m = 0, pc_0, pc_p, pc_n, pjm_m = 0, pjm_0, pjm_p, pjm_n, pim_m = 0, pim_0, pim_p, pim_n, pjp_m = 0, pjp_0, pjp_p, pjp_n, pip_m = 0, pip_0, pip_p, pip_n;
-    double zy_m = 0, zy_0, zy_p, zy_n, zx_m = 0, zx_0, zx_p, zx_n, a2_0, a2_p, a2_n;
-    double zyjm, zyjp, zxim, zxip, a4o, a4jp, a7o, a7ip, zyjm_n, zyjp_n, zxim_n, zxip_n, a4o_n, a4jp_n, a7o_n, a7ip_n;
-#define LOAD_WIN(q, PC, PJM, PIM, PJP, PIP, ZY, ZX, A2)                        \
-  { const long long ro = (long long)(((q) <= nz ? (q) : nz) - 1) * RS;         \
-    PC = p[o + ro + c]; LD_PAIR(p + o + ro + jm, PJM, PJP) PIM = p[om + ro + c]; PIP = p[op + ro + c]; \
-    ZY = *(zy + o + ro + c); ZX = *(zx + o + ro + c); A2 = ld_rt(a2 + o + ro + c, stream); }
-#define LOAD_ROWV(q, ZYJM, ZYJP, ZXIM, ZXIP, A4O, A4JP, A7O, A7IP)             \
-  { const long long ro = (long long)(((q) <= nz ? (q) : nz) - 1) * RS, ko = o + ro + c; \
-    LD_PAIR(zy + o + ro + jm, ZYJM, ZYJP) ZXIM = zx[om + ro + c]; ZXIP = zx[op + ro + c]; \
-    A4O = *(a4 + ko); A4JP = a4[o + ro + jp]; A7O = *(a7 + ko); A7IP = a7[op + ro + c]; }
-    const double d_first = a1[o + c], d_last = a1[o + (long long)(nz - 1) * RS + c];
-    double e0 = 0, e1 = 0, e2 = 0, e3 = 0, e4 = 0, e5 = 0, e6 = 0, e7 = 0;
-    if (REAL) { e0 = a5[o + c]; e1 = p[om + jp]; e2 = a5[op + jm]; e3 = p[op + jm]; e4 = a8[o + c]; e5 = p[om + jm]; e6 = a8[op + jp]; e7 = p[op + jp]; }
-    LOAD_WIN(1, pc_0, pjm_0, pim_0, pjp_0, pip_0, zy_0, zx_0, a2_0)
-    LOAD_ROWV(1, zyjm, zyjp, zxim, zxip, a4o, a4jp, a7o, a7ip)
-    LOAD_WIN(2, pc_p, pjm_p, pim_p, pjp_p, pip_p, zy_p, zx_p, a2_p)
-    for (int k = 1; k <= nz; k++) {
-      const long long ro = (long long)(k - 1) * RS, ko = o + ro + c;
-      LOAD_WIN(k + 2, pc_n, pjm_n, pim_n, pjp_n, pip_n, zy_n, zx_n, a2_n)
-      LOAD_ROWV(k + 1, zyjm_n, zyjp_n, zxim_n, zxip_n, a4o_n, a4jp_n, a7o_n, a7ip_n)
-      double rr;
-      if (k == 1) {
-        rr = zero - d_first * pc_0 - a2_p * pc_p - (qrt * (zy_p + zyjm)) * pjm_p - a4o * pjm_0 - a4jp * pjp_0
-                   - (-qrt * (zyjp + zy_p)) * pjp_p - (qrt * (zx_p + zxim)) * pim_p - a7o * pim_0 - a7ip * pip_0
-                   - (-qrt * (zxip + zx_p)) * pip_p;
-        if (REAL) rr = rr - e0 * e1 - e2 * e3 - e4 * e5 - e6 * e7;
-      } else if (k < nz) {
-        const double c3 = qrt * (zy_p + zyjm), c3m = qrt * (zyjp + zy_m), c5 = -qrt * (zy_m + zyjm), c5m = -qrt * (zyjp + zy_p);
-        const double c6 = qrt * (zx_p + zxim), c6m = qrt * (zxip + zx_m), c8 = -qrt * (zx_m + zxim), c8m = -qrt * (zxip + zx_p);
-        const double dk = -a2_0 - a2_p - a4o - a4jp - a7o - a7ip - c6 - c6m - c8 - c8m - c3 - c3m - c5 - c5m;  // = cA(1,k,j,i), mg_define_matrix.f90:632-639
-        rr = zero - dk * pc_0 - a2_0 * pc_m - a2_p * pc_p - c3 * pjm_p - c3m * pjp_m
-                   - a4o * pjm_0 - a4jp * pjp_0 - c5 * pjm_m - c5m * pjp_p
-                   - c6 * pim_p - c6m * pip_m - a7o * pim_0 - a7ip * pip_0
-                   - c8 * pim_m - c8m * pip_p;
-      } else {
-        rr = zero - d_last * pc_0 - a2_0 * pc_m - (qrt * (zyjp + zy_m)) * pjp_m - a4o * pjm_0 - a4jp * pjp_0
-                   - (-qrt * (zy_m + zyjm)) * pjm_m - (qrt * (zxip + zx_m)) * pip_m - a7o * pim_0 - a7ip * pip_0
-                   - (-qrt * (zx_m + zxim)) * pim_m;
-      }
-      PUT_ROW(ko, rr)
-      pc_m = pc_0; pc_0 = pc_p; pc_p = pc_n; pjm_m = pjm_0; pjm_0 = pjm_p; pjm_p = pjm_n; pim_m = pim_0; pim_0 = pim_p; pim_p = pim_n;
-      pjp_m = pjp_0; pjp_0 = pjp_p; pjp_p = pjp_n; pip_m = pip_0; pip_0 = pip_p; pip_p = pip_n;
-      zy_m = zy_0; zy_0 = zy_p; zy_p = zy_n; zx_m = zx_0; zx_0 = zx_p; zx_p = zx_n; a2_0 = a2_p; a2_p = a2_n;
-      zyjm = zyjm_n; zyjp = zyjp_n; zxim = zxim_n; zxip = zxip_n; a4o = a4o_n; a4jp = a4jp_n; a7o = a7o_n; a7ip = a7ip_n;
-    }
-#undef LOAD_ROWV
-#undef LOAD_WIN
+    const double zero = 0.0;
+    OP_COLUMN(KR_RHS, KR_SINK)
   }
   if (D.n) kr_block_sums<KR_MAX>(acc, D.n, partial, blockIdx.x, gridDim.x);
 }
-#undef PUT_ROW
+
+template <bool REAL>
+__global__ __launch_bounds__(256) void k_kr_apply_mf(LevView L, double *__restrict__ qout, KrDirs D, double *__restrict__ partial, int gx, int gy, int stream) {
+  int bx, by, bz;
+  op_block_map(gx, gy, bx, by, bz);
+  const int jh = bx * WAVE + threadIdx.x;
+  const int i = 1 + by * blockDim.y + threadIdx.y;
+  const int jodd = bz == 0;
+  double acc[KR_MAX] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (jh < (L.ny >> 1) && i <= L.nx) {
+    int c, jm, jp;
+    COL_POS(L, jh, jodd, c, jm, jp)
+    const double zero = 0.0;
+    OP_COLUMN_MF(KR_RHS, KR_SINK)
+  }
+  if (D.n) kr_block_sums<KR_MAX>(acc, D.n, partial, blockIdx.x, gridDim.x);
+}
 
 // ------------------------------------------------------------------------------------------------
 // streaming passes.  Grid: x = chunks of KR_CHUNK elements of a plane, y = the nx + 2 planes; a lane takes pairs of neighbouring elements

@@ -1,0 +1,167 @@
+// The level-1 operator, ONE text per form: the 15-point product of compute_residual (mg_relax.f90:421-515) from the stored slots and with
+// matrix-free cross terms, for the residual kernels (mgx_kernels.hip: k_residual, k_residual_mf) and pass 1 of the Krylov loop
+// (mgx_krylov.hip: k_kr_apply, k_kr_apply_mf), which is the same operator on b = 0 with the sign turned.  Both have a bit-parity duty that
+// rests on a row being formed from the same terms in the same order: a change to a row is made here, once.  With them, the block map of
+// these launches and the block reduction of the kernels that leave one partial sum per workgroup.  The column texts and the reduction are
+// macros with caller-supplied hooks, for the reason given in mgx_relax_common.h: the callers must compile to the instructions they had
+// as separate texts (profiles/operator_single_source_isa.json).
+#pragma once
+#include "mgx_device.h"
+
+// XCD-aware block -> (j-chunk bx, plane group by, j parity bz) map of a 1-D grid of gx * gy * 2 blocks: each XCD owns a contiguous range
+// of plane groups, as with XCD_BLOCK_MAP (mgx_relax_common.h, which explains why).  It differs from that map in its unit: the two
+// j-parities of a plane group (bz = 0: odd j, 1: even j) run back to back on the same XCD, since they read the same rows; and it has no
+// plain-map switch (spelt through XCD_BLOCK_MAP, that switch's branch stays in the kernels: 17 instructions more each).  A function and
+// not a macro because this is the form that leaves all four callers as they were: written out in k_kr_apply, the same text allocates
+// two more VGPRs there (the profile has the figures), while the residual kernels compile to the same instructions either way.
+__device__ __forceinline__ void op_block_map(int gx, int gy, int &bx, int &by, int &bz) {
+  const int per = gx * 2;
+  int grp, local;
+  if ((gy & 7) == 0) { const int xcd = blockIdx.x & 7; local = blockIdx.x >> 3; grp = xcd * (gy >> 3) + local / per; local -= (local / per) * per; }
+  else { grp = blockIdx.x / per; local = blockIdx.x - grp * per; }
+  by = grp; bz = local / gx; bx = local - bz * gx;
+}
+
+// Sum of one per-lane acc over the workgroup -> partial[idx]: wave shuffle, then LDS across the waves of the block in index order
+// (deterministic).  Every lane of the block must arrive.
+#define OP_BLOCK_SUM(acc, partial, idx)                                                                                                      \
+  {                                                                                                                                          \
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);                                                                 \
+    __shared__ double red[16];                                                                                                               \
+    const int tid = threadIdx.y * blockDim.x + threadIdx.x, w = tid >> 6;                                                                    \
+    if ((tid & 63) == 0) red[w] = acc;                                                                                                       \
+    __syncthreads();                                                                                                                         \
+    if (tid == 0) {                                                                                                                          \
+      double s = 0.0;                                                                                                                        \
+      const int nw = (blockDim.x * blockDim.y + 63) >> 6;                                                                                    \
+      for (int q = 0; q < nw; q++) s += red[q];                                                                                              \
+      partial[idx] = s;                                                                                                                      \
+    }                                                                                                                                        \
+  }
+
+// ------------------------------------------------------------------------------------------------
+// The column from the stored slots: rr(k) = rhs(k) - (A p)(k), k = 1 .. nz, one lane = one (j, i) column.
+// The caller has in scope: REAL (compile-time); L, i, jh, jodd, c, jm, jp; and two hooks,
+//   RHS(ko)           the row's right-hand side (ko = the row's offset in a level-1 array)
+//   SINK(ro, ko, rr)  the row's sink (ro = the row's offset inside its plane; jcol = the column's j is in scope, declared where
+//                     the residual has always computed it: earlier, its kernel allocates registers differently)
+// ------------------------------------------------------------------------------------------------
+#define LOAD_ROW(q, PJM, PIM, PC, A2, M3, M4, M5, N6, N7, N8)                                                                                \
+  {                                                                                                                                          \
+    const long long ro = (long long)((q)-1) * RS;                                                                                            \
+    PJM = p[o + ro + jm]; PIM = p[om + ro + c]; PC = p[o + ro + c]; A2 = a2[o + ro + c];                                                     \
+    const double pj_ = p[o + ro + jp], pi_ = p[op + ro + c];                                                                                 \
+    M3 = a3[o + ro + jp] * pj_; M4 = a4[o + ro + jp] * pj_; M5 = a5[o + ro + jp] * pj_;                                                      \
+    N6 = a6[op + ro + c] * pi_; N7 = a7[op + ro + c] * pi_; N8 = a8[op + ro + c] * pi_;                                                      \
+  }
+#define OP_COLUMN(RHS, SINK)                                                                                                                 \
+  {                                                                                                                                          \
+    const long long RS = L.RS;                                                                                                               \
+    const int nz = L.nz;                                                                                                                     \
+    const double *__restrict__ p = L.p;                                                                                                      \
+    const double *__restrict__ a1 = L.cA[0], *__restrict__ a2 = L.cA[1], *__restrict__ a3 = L.cA[2],                                         \
+                 *__restrict__ a4 = L.cA[3], *__restrict__ a5 = L.cA[4], *__restrict__ a6 = L.cA[5],                                         \
+                 *__restrict__ a7 = L.cA[6], *__restrict__ a8 = L.cA[7];                                                                     \
+    const long long o = (long long)i * L.plane, om = o - L.plane, op = o + L.plane;                                                          \
+    double pjm_m, pjm_0, pjm_p, pim_m, pim_0, pim_p, pc_m, pc_0, pc_p, a2_0, a2_p;                                                           \
+    double m3_m, m3_0, m4_0, m5_p, n6_m, n6_0, n7_0, n8_p, m3_p, m4_p, n6_p, n7_p;                                                           \
+    double dum5, dum8;                                                                                                                       \
+    LOAD_ROW(1, pjm_0, pim_0, pc_0, a2_0, m3_0, m4_0, dum5, n6_0, n7_0, dum8);                                                               \
+    LOAD_ROW(2, pjm_p, pim_p, pc_p, a2_p, m3_p, m4_p, m5_p, n6_p, n7_p, n8_p);                                                               \
+    (void)dum5; (void)dum8;                                                                                                                  \
+    /* k = 1 (:464-482) */                                                                                                                   \
+    double rr = RHS(o + c) - a1[o + c] * pc_0 - a2_p * pc_p - a3[o + c] * pjm_p - a4[o + c] * pjm_0 - m4_0 - m5_p                            \
+                - a6[o + c] * pim_p - a7[o + c] * pim_0 - n7_0 - n8_p;                                                                       \
+    if (REAL)                                                                                                                                \
+      rr = rr - a5[o + c] * p[om + jp] - a5[op + jm] * p[op + jm] - a8[o + c] * p[om + jm] - a8[op + jp] * p[op + jp];                       \
+    const int jcol = jodd ? 2 * jh + 1 : 2 * jh + 2;  /* the column's j, for a sink that stores the physical images */                       \
+    SINK(0, o + c, rr)                                                                                                                       \
+    for (int k = 2; k <= nz - 1; k++) {  /* (:484-496) */                                                                                    \
+      pjm_m = pjm_0; pjm_0 = pjm_p; pim_m = pim_0; pim_0 = pim_p; pc_m = pc_0; pc_0 = pc_p; a2_0 = a2_p;                                     \
+      m3_m = m3_0; m3_0 = m3_p; m4_0 = m4_p; n6_m = n6_0; n6_0 = n6_p; n7_0 = n7_p;                                                          \
+      LOAD_ROW(k + 1, pjm_p, pim_p, pc_p, a2_p, m3_p, m4_p, m5_p, n6_p, n7_p, n8_p);                                                         \
+      const long long ko = o + (long long)(k - 1) * RS + c;                                                                                  \
+      rr = RHS(ko) - a1[ko] * pc_0 - a2_0 * pc_m - a2_p * pc_p - a3[ko] * pjm_p - m3_m - a4[ko] * pjm_0 - m4_0                               \
+                   - a5[ko] * pjm_m - m5_p - a6[ko] * pim_p - n6_m - a7[ko] * pim_0 - n7_0 - a8[ko] * pim_m - n8_p;                          \
+      SINK((long long)(k - 1) * RS, ko, rr)                                                                                                  \
+    }                                                                                                                                        \
+    {  /* k = nz (:498-509) */                                                                                                               \
+      pjm_m = pjm_0; pjm_0 = pjm_p; pim_m = pim_0; pim_0 = pim_p; pc_m = pc_0; pc_0 = pc_p; a2_0 = a2_p;                                     \
+      m3_m = m3_0; m4_0 = m4_p; n6_m = n6_0; n7_0 = n7_p;                                                                                    \
+      const long long ko = o + (long long)(nz - 1) * RS + c;                                                                                 \
+      rr = RHS(ko) - a1[ko] * pc_0 - a2_0 * pc_m - m3_m - a4[ko] * pjm_0 - m4_0 - a5[ko] * pjm_m - n6_m                                      \
+                   - a7[ko] * pim_0 - n7_0 - a8[ko] * pim_m;                                                                                 \
+      SINK((long long)(nz - 1) * RS, ko, rr)                                                                                                 \
+    }                                                                                                                                        \
+  }
+
+// ------------------------------------------------------------------------------------------------
+// The column with matrix-free cross terms (see mgx_relax_common.h): 17 streams per cell instead of 22.  The diagonal of the interior rows
+// is rebuilt from the fourteen couplings the row holds anyway (mg_define_matrix.f90:632-639, summed in the reference's order: the same
+// bits as the stored slot 1 -- as the smoother and the fused residual+restriction do); rows 1 and nz, whose formula differs, read the
+// stored one.  The j-1 / j+1 neighbours of p and zy sit side by side in the other half-row: one 16-byte load each.  What only this lane
+// reads (a2, the right-hand side) is streamed past the caches on a level that does not fit them.
+// The caller has in scope: REAL (compile-time); L, i, c, jm, jp, stream; and two hooks,
+//   RHS_LOAD(ko)      the request for the row's right-hand side, issued one step ahead with the row's own values (a load or a constant)
+//   SINK(ro, ko, rr)  the row's sink
+// ------------------------------------------------------------------------------------------------
+#define LOAD_WIN(q, PC, PJM, PIM, PJP, PIP, ZY, ZX, A2)                                                                                      \
+  { const long long ro = (long long)(((q) <= nz ? (q) : nz) - 1) * RS;                                                                       \
+    PC = p[o + ro + c]; LD_PAIR(p + o + ro + jm, PJM, PJP) PIM = p[om + ro + c]; PIP = p[op + ro + c];                                       \
+    ZY = *(zy + o + ro + c); ZX = *(zx + o + ro + c); A2 = ld_rt(a2 + o + ro + c, stream); }
+#define LOAD_ROWV(RHS_LOAD, q, ZYJM, ZYJP, ZXIM, ZXIP, A4O, A4JP, A7O, A7IP, BK)                                                             \
+  { const long long ro = (long long)(((q) <= nz ? (q) : nz) - 1) * RS, ko = o + ro + c;                                                      \
+    LD_PAIR(zy + o + ro + jm, ZYJM, ZYJP) ZXIM = zx[om + ro + c]; ZXIP = zx[op + ro + c];                                                    \
+    A4O = *(a4 + ko); A4JP = a4[o + ro + jp]; A7O = *(a7 + ko); A7IP = a7[op + ro + c]; BK = RHS_LOAD(ko); }
+#define OP_COLUMN_MF(RHS_LOAD, SINK)                                                                                                         \
+  {                                                                                                                                          \
+    const long long RS = L.RS;                                                                                                               \
+    const int nz = L.nz;                                                                                                                     \
+    const double *__restrict__ p = L.p;                                                                                                      \
+    const double *__restrict__ a1 = L.cA[0], *__restrict__ a2 = L.cA[1], *__restrict__ a4 = L.cA[3], *__restrict__ a5 = L.cA[4],             \
+                 *__restrict__ a7 = L.cA[6], *__restrict__ a8 = L.cA[7], *__restrict__ zy = L.zy, *__restrict__ zx = L.zx;                   \
+    const long long o = (long long)i * L.plane, om = o - L.plane, op = o + L.plane;                                                          \
+    const double qrt = 0.25;                                                                                                                 \
+    /* Every request is unconditional (rows past the top clamped to nz, never used) and issued ONE STEP before its first use: the window row */ \
+    /* k+2 and the own-row values of k+1 are in flight while row k is computed.  (A request inside `if (k + 2 <= nz)` made the number of */  \
+    /* outstanding loads path-dependent: the compiler then waits for vmcnt(0) at every step and the look-ahead is void.) */                  \
+    double pc_m = 0, pc_0, pc_p, pc_n, pjm_m = 0, pjm_0, pjm_p, pjm_n, pim_m = 0, pim_0, pim_p, pim_n, pjp_m = 0, pjp_0, pjp_p, pjp_n, pip_m = 0, pip_0, pip_p, pip_n; \
+    double zy_m = 0, zy_0, zy_p, zy_n, zx_m = 0, zx_0, zx_p, zx_n, a2_0, a2_p, a2_n;                                                         \
+    double zyjm, zyjp, zxim, zxip, a4o, a4jp, a7o, a7ip, bk, zyjm_n, zyjp_n, zxim_n, zxip_n, a4o_n, a4jp_n, a7o_n, a7ip_n, bk_n;             \
+    /* rows 1 and nz: stored diagonal; row 1: the k = 1 diagonal slots and the four corner values of p (cmatrix = 'real', mg_relax.f90:475-479) */ \
+    const double d_first = a1[o + c], d_last = a1[o + (long long)(nz - 1) * RS + c];                                                         \
+    double e0 = 0, e1 = 0, e2 = 0, e3 = 0, e4 = 0, e5 = 0, e6 = 0, e7 = 0;                                                                   \
+    if (REAL) { e0 = a5[o + c]; e1 = p[om + jp]; e2 = a5[op + jm]; e3 = p[op + jm]; e4 = a8[o + c]; e5 = p[om + jm]; e6 = a8[op + jp]; e7 = p[op + jp]; } \
+    LOAD_WIN(1, pc_0, pjm_0, pim_0, pjp_0, pip_0, zy_0, zx_0, a2_0)                                                                          \
+    LOAD_ROWV(RHS_LOAD, 1, zyjm, zyjp, zxim, zxip, a4o, a4jp, a7o, a7ip, bk)                                                                 \
+    LOAD_WIN(2, pc_p, pjm_p, pim_p, pjp_p, pip_p, zy_p, zx_p, a2_p)                                                                          \
+    for (int k = 1; k <= nz; k++) {                                                                                                          \
+      const long long ro = (long long)(k - 1) * RS, ko = o + ro + c;                                                                         \
+      LOAD_WIN(k + 2, pc_n, pjm_n, pim_n, pjp_n, pip_n, zy_n, zx_n, a2_n)                                                                    \
+      LOAD_ROWV(RHS_LOAD, k + 1, zyjm_n, zyjp_n, zxim_n, zxip_n, a4o_n, a4jp_n, a7o_n, a7ip_n, bk_n)                                         \
+      double rr;                                                                                                                             \
+      if (k == 1) {                                                                                                                          \
+        rr = bk - d_first * pc_0 - a2_p * pc_p - (qrt * (zy_p + zyjm)) * pjm_p - a4o * pjm_0 - a4jp * pjp_0                                  \
+                   - (-qrt * (zyjp + zy_p)) * pjp_p - (qrt * (zx_p + zxim)) * pim_p - a7o * pim_0 - a7ip * pip_0                             \
+                   - (-qrt * (zxip + zx_p)) * pip_p;                                                                                         \
+        if (REAL) rr = rr - e0 * e1 - e2 * e3 - e4 * e5 - e6 * e7;                                                                           \
+      } else if (k < nz) {                                                                                                                   \
+        const double c3 = qrt * (zy_p + zyjm), c3m = qrt * (zyjp + zy_m), c5 = -qrt * (zy_m + zyjm), c5m = -qrt * (zyjp + zy_p);             \
+        const double c6 = qrt * (zx_p + zxim), c6m = qrt * (zxip + zx_m), c8 = -qrt * (zx_m + zxim), c8m = -qrt * (zxip + zx_p);             \
+        const double dk = -a2_0 - a2_p - a4o - a4jp - a7o - a7ip - c6 - c6m - c8 - c8m - c3 - c3m - c5 - c5m;  /* = cA(1,k,j,i), mg_define_matrix.f90:632-639 */ \
+        rr = bk - dk * pc_0 - a2_0 * pc_m - a2_p * pc_p - c3 * pjm_p - c3m * pjp_m                                                           \
+                   - a4o * pjm_0 - a4jp * pjp_0 - c5 * pjm_m - c5m * pjp_p                                                                   \
+                   - c6 * pim_p - c6m * pip_m - a7o * pim_0 - a7ip * pip_0                                                                   \
+                   - c8 * pim_m - c8m * pip_p;                                                                                               \
+      } else {                                                                                                                               \
+        rr = bk - d_last * pc_0 - a2_0 * pc_m - (qrt * (zyjp + zy_m)) * pjp_m - a4o * pjm_0 - a4jp * pjp_0                                   \
+                   - (-qrt * (zy_m + zyjm)) * pjm_m - (qrt * (zxip + zx_m)) * pip_m - a7o * pim_0 - a7ip * pip_0                             \
+                   - (-qrt * (zx_m + zxim)) * pim_m;                                                                                         \
+      }                                                                                                                                      \
+      SINK(ro, ko, rr)                                                                                                                       \
+      pc_m = pc_0; pc_0 = pc_p; pc_p = pc_n; pjm_m = pjm_0; pjm_0 = pjm_p; pjm_p = pjm_n; pim_m = pim_0; pim_0 = pim_p; pim_p = pim_n;       \
+      pjp_m = pjp_0; pjp_0 = pjp_p; pjp_p = pjp_n; pip_m = pip_0; pip_0 = pip_p; pip_p = pip_n;                                              \
+      zy_m = zy_0; zy_0 = zy_p; zy_p = zy_n; zx_m = zx_0; zx_0 = zx_p; zx_p = zx_n; a2_0 = a2_p; a2_p = a2_n;                                \
+      zyjm = zyjm_n; zyjp = zyjp_n; zxim = zxim_n; zxip = zxip_n; a4o = a4o_n; a4jp = a4jp_n; a7o = a7o_n; a7ip = a7ip_n; bk = bk_n;         \
+    }                                                                                                                                        \
+  }
