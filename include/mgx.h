@@ -60,8 +60,10 @@ int mgx_read_namelist(const char *path, mgx_params *p);
  * par == NULL: read ./nh_namelist if present, else defaults (what the reference does).
  * nx, ny, nz must be even; nz need not be a power of two.  Coarser levels halve nz as the reference does (an odd level drops its
  * top row on restriction, mg_intergrids.f90:149-160).  Level-1 colour pass: a register-resident kernel for nz in {2, 4, 8, 12, 16,
- * 20, 24, 32, 40, 48, 64}; a tall-column kernel for nz in {80, 96, 128} when the matrix is matrix-free (define_matrices, no bmask);
- * every other nz, and the tall sizes with stored coefficients, run the generic kernel plus a physical-halo launch per colour.
+ * 20, 24, 32, 40, 48, 64}; a tall-column kernel for nz in {80, 96, 128}, in its matrix-free form when the matrix came from
+ * define_matrices without bmask and on the stored coefficients otherwise (bmask, mgx_set_field(cA), MGX_NO_MF; the read-only option
+ * "tall_stored_passes" counts the colour passes served that way since mgx_init); every other nz runs the generic kernel plus a
+ * physical-halo launch per colour.
  * relax_method = 'GS' accepts any nz (register-resident columns for the powers of two up to 64, the generic column otherwise). */
 int mgx_init(int nx, int ny, int nz, int npx, int npy, int rank, const mgx_params *par);
 /* nhydro_matrices(dx,dy,zeta,h,rmask,hc,theta_b,theta_s) (nhydro.f90:36-50) -> define_matrices
@@ -234,7 +236,8 @@ int mgx_set_verbose(int level);
  *   solve_p together with "cycle_precision" = 32.  Three all-reduce calls per iteration on a process grid (one per pass).
  *   Read-only: "krylov_restarts" (times the last solve fell back to the true residual).
  * Read-only through mgx_get_option: "p2p_failed" (a peer-to-peer wait of THIS rank timed out since the ranks last agreed: see below),
- *   "overlapped_passes". */
+ *   "overlapped_passes", "tall_stored_passes" (colour passes of nz = 80, 96, 128 levels served by the stored-coefficient tall-column kernel
+ *   since mgx_init: bmask, mgx_set_field(cA) or MGX_NO_MF; 0 while the matrix-free form runs or under MGX_NO_TALL). */
 int mgx_set_option(const char *name, int value);
 /* Option "async" (default 0): the cycle / operator entry points (mgx_vcycle, mgx_vcycle2, mgx_fcycle, mgx_relax, mgx_fine2coarse,
  * mgx_coarse2fine) only ENQUEUE their kernels on the solver's stream and return -- what a GPU-resident model wants between its own

@@ -82,6 +82,7 @@ const Opt OPTIONS[] = {
   {"coarsest_direct_solves", nullptr, CNT(n_direct), nullptr, ENV_NONE, RO, false},
   {"rbseq_window_colours", nullptr, CNT(n_window), nullptr, ENV_NONE, RO, false},
   {"overlapped_passes", nullptr, CNT(n_overlap), nullptr, ENV_NONE, RO, false},
+  {"tall_stored_passes", nullptr, CNT(n_tall_stored), nullptr, ENV_NONE, RO, false},
   {"mixed_iterations", nullptr, CNT(n_mixed), nullptr, ENV_NONE, RO, false},
   {"krylov_restarts", nullptr, CNT(kr_restarts), nullptr, ENV_NONE, RO, false},
   {"p2p_failed", nullptr, CNT(p2p_failed), nullptr, ENV_NONE, RO, false},

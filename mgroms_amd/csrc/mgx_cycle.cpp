@@ -79,6 +79,7 @@ int relax(int lev, int nsweeps) {
       for (int rb = 1; rb <= 2; rb++) {
         int fused = 0;
         for (int i = 1; i <= L.nx; i++) { fused = mgxk_relax_colour(S.stream, &L.v, i, 1, 1, -1, rb, 1, 0, ph); S.n_launch++; }
+        if (fused & 4) S.n_tall_stored++;
         CHK(fill_halo_js(L, L.v.p, fused));
       }
       continue;
@@ -101,6 +102,7 @@ int relax(int lev, int nsweeps) {
         L.v.d0w = (seq && S.rbseq_d0_in_pass && (mgxk_rbseq_wants_d0(&L.v) || (S.rbseq_window && L.rbs_m > 0))) ? L.v.u1 : nullptr;
         const int pass = mgxk_relax_colour(S.stream, &L.v, 1, 1, L.nx, -1, rb, S.real, S.real, ph); S.n_launch++;
         L.v.d0w = nullptr;
+        if (pass & 4) S.n_tall_stored++;
         int fused = pass & 1;
         const int have_d0 = (pass & 2) ? 1 : 0;
         if (seq) {
@@ -157,9 +159,11 @@ int relax(int lev, int nsweeps) {
             mgxk_relax_colour(S.stream, &L.v, 1 + (fc1 - 1) % 2, 2, L.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0, ps);
             HIPCHK(hipStreamWaitEvent(S.stream, S.ev_s, 0));          // what follows on the solver's stream reads this colour's boundary part -- not its exchange
             S.n_launch += 2; S.n_overlap++;
+            if (fused & 4) S.n_tall_stored++;
             continue;
           }
           const int fused = mgxk_relax_colour(S.stream, &L.v, 1 + (fc1 - 1) % 2, 2, L.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0, ph); S.n_launch++;
+          if (fused & 4) S.n_tall_stored++;
           CHK(fill_halo_js(L, L.v.p, fused));
         }
       }

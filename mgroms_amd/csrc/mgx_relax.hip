@@ -110,94 +110,21 @@ __global__ __launch_bounds__(256) void k_relax_colour(LevView L, int i0, int ist
 //     once (no forward store + backward re-read), and the backward sweep does no dependent loads;
 //   * physical-boundary mirrors of the updated columns (mg_mpi_exchange.f90:509-537,552-597) are stored by
 //     the lane that owns the column, which removes the separate halo kernel after every colour.
-// Arithmetic and its order are identical to k_relax_colour (bit-identical results).
+// Arithmetic and its order are identical to k_relax_colour (bit-identical results).  The forward rows are the stored-coefficient text of
+// mgx_relax_common.h (SC_ROW), shared with the tall-column pass of mgx_relax_tall.hip.
 // ------------------------------------------------------------------------------------------------
 template <int NZ, bool REAL, bool SNAP, int D>
 __device__ __forceinline__ void relax_col_nz(const LevView &L, const int i, const int jh, const int jodd, const Sides ph) {
   int c, jm, jp;
   COL_POS(L, jh, jodd, c, jm, jp)
-  const long long RS = L.RS;
-  double *__restrict__ p = L.p;
-  const double *__restrict__ b = L.b;
-  const double *__restrict__ a2 = L.cA[1], *__restrict__ a3 = L.cA[2], *__restrict__ a4 = L.cA[3],
-               *__restrict__ a5 = L.cA[4], *__restrict__ a6 = L.cA[5], *__restrict__ a7 = L.cA[6],
-               *__restrict__ a8 = L.cA[7], *__restrict__ bet = L.bet;
-  const long long o = (long long)i * L.plane, om = o - L.plane, op = o + L.plane;
-
   constexpr bool ST = false;  // stored-slot path: coarser levels / user matrices, which live in the caches
-  constexpr int RN = D + 1;  // raw neighbour rows in flight
-  constexpr int RO = D + 1;  // raw own rows in flight
-  double r_pjm[RN], r_pim[RN], r_pjp[RN], r_pip[RN], r_a3[RN], r_a4[RN], r_a5[RN], r_a6[RN], r_a7[RN], r_a8[RN];
-  double o_b[RO], o_a2[RO], o_a3[RO], o_a4[RO], o_a5[RO], o_a6[RO], o_a7[RO], o_a8[RO], o_bet[RO];
-  double x[NZ], g[NZ];
-
-#define NB_LOAD(q)                                                               \
-  if ((q) <= NZ) {                                                               \
-    const long long ro_ = (long long)((q)-1) * RS; const int s_ = (q) % RN;      \
-    r_pjm[s_] = p[o + ro_ + jm]; r_pim[s_] = p[om + ro_ + c];                    \
-    r_pjp[s_] = p[o + ro_ + jp]; r_pip[s_] = p[op + ro_ + c];                    \
-    r_a3[s_] = a3[o + ro_ + jp]; r_a4[s_] = a4[o + ro_ + jp]; r_a5[s_] = a5[o + ro_ + jp]; \
-    r_a6[s_] = a6[op + ro_ + c]; r_a7[s_] = a7[op + ro_ + c]; r_a8[s_] = a8[op + ro_ + c]; \
-  }
-#define OW_LOAD(q)                                                               \
-  if ((q) <= NZ) {                                                               \
-    const long long ko_ = o + (long long)((q)-1) * RS + c; const int s_ = (q) % RO; \
-    o_b[s_] = ld_stream<ST>(b + ko_); o_a2[s_] = ld_stream<ST>(a2 + ko_); o_a3[s_] = ld_stream<ST>(a3 + ko_); o_a4[s_] = ld_stream<ST>(a4 + ko_); o_a5[s_] = ld_stream<ST>(a5 + ko_); \
-    o_a6[s_] = ld_stream<ST>(a6 + ko_); o_a7[s_] = ld_stream<ST>(a7 + ko_); o_a8[s_] = ld_stream<ST>(a8 + ko_); o_bet[s_] = ld_stream<ST>(bet + ko_); \
-  }
-  // products of a raw neighbour row (computed when the row is first needed)
-#define NB_USE(q, PJM, PIM, M3, M4, M5, N6, N7, N8)                              \
-  { const int s_ = (q) % RN; PJM = r_pjm[s_]; PIM = r_pim[s_];                   \
-    M3 = r_a3[s_] * r_pjp[s_]; M4 = r_a4[s_] * r_pjp[s_]; M5 = r_a5[s_] * r_pjp[s_]; \
-    N6 = r_a6[s_] * r_pip[s_]; N7 = r_a7[s_] * r_pip[s_]; N8 = r_a8[s_] * r_pip[s_]; }
-
-  // k = 1 horizontal-diagonal terms (issued first: independent of everything else)
-  double d1 = 0, d2 = 0, d3 = 0, d4 = 0, e1 = 0, e2 = 0, e3 = 0, e4 = 0;
-  if (REAL) {
-    const double *__restrict__ q1 = SNAP ? L.p1 : p;
-    const long long s = SNAP ? (long long)i * RS : o, sm = SNAP ? s - RS : om, sp = SNAP ? s + RS : op;
-    d1 = q1[sm + jp]; d2 = q1[sp + jm]; d3 = q1[sm + jm]; d4 = q1[sp + jp];
-    e1 = a5[o + c]; e2 = a5[op + jm]; e3 = a8[o + c]; e4 = a8[op + jp];
-  }
-  // prologue: neighbour rows 1..1+D... and own rows 1..D
+#define SC_G_PUT(kk, v) g[(kk)-1] = (v);
+#define SC_X_PUT(kk, v) x[(kk)-1] = (v);
+  SC_PROLOGUE(NZ, NZ)
 #pragma unroll
-  for (int q = 1; q <= 1 + D; q++) { NB_LOAD(q) }
-#pragma unroll
-  for (int q = 1; q <= D; q++) { OW_LOAD(q) }
-
-  double pjm_m = 0, pjm_0, pjm_p, pim_m = 0, pim_0, pim_p;
-  double m3_m = 0, m3_0, m4_0, m5_p, n6_m = 0, n6_0, n7_0, n8_p, m3_p, m4_p, n6_p, n7_p, dum5, dum8;
-  NB_USE(1, pjm_0, pim_0, m3_0, m4_0, dum5, n6_0, n7_0, dum8)
-  (void)dum5; (void)dum8;
-  double xv = 0.0, betp = 0.0;
-#pragma unroll
-  for (int k = 1; k <= NZ; k++) {
-    // keep the pipeline full
-    NB_LOAD(k + 1 + D)
-    OW_LOAD(k + D)
-    if (k < NZ) { NB_USE(k + 1, pjm_p, pim_p, m3_p, m4_p, m5_p, n6_p, n7_p, n8_p) }
-    const int s = k % RO;
-    double rhs;
-    // gam(k) = dd(k-1)*bet(k-1) (mg_relax.f90:325), from values already in registers: no gam stream from HBM
-    if (k > 1) g[k - 1] = o_a2[s] * betp;
-    betp = o_bet[s];
-    if (k == 1) {
-      rhs = o_b[s] - o_a3[s] * pjm_p - o_a4[s] * pjm_0 - m4_0 - m5_p - o_a6[s] * pim_p - o_a7[s] * pim_0 - n7_0 - n8_p;
-      if (REAL) rhs = rhs - e1 * d1 - e2 * d2 - e3 * d3 - e4 * d4;
-      xv = rhs * o_bet[s];
-    } else if (k < NZ) {
-      rhs = o_b[s] - o_a3[s] * pjm_p - m3_m - o_a4[s] * pjm_0 - m4_0 - o_a5[s] * pjm_m - m5_p
-                   - o_a6[s] * pim_p - n6_m - o_a7[s] * pim_0 - n7_0 - o_a8[s] * pim_m - n8_p;
-      xv = (rhs - o_a2[s] * xv) * o_bet[s];
-    } else {
-      rhs = o_b[s] - m3_m - o_a4[s] * pjm_0 - m4_0 - o_a5[s] * pjm_m - n6_m - o_a7[s] * pim_0 - n7_0 - o_a8[s] * pim_m;
-      xv = (rhs - o_a2[s] * xv) * o_bet[s];
-    }
-    x[k - 1] = xv;
-    // rotate the three-row window
-    pjm_m = pjm_0; pjm_0 = pjm_p; pim_m = pim_0; pim_0 = pim_p;
-    m3_m = m3_0; m3_0 = m3_p; m4_0 = m4_p; n6_m = n6_0; n6_0 = n6_p; n7_0 = n7_p;
-  }
+  for (int k = 1; k <= NZ; k++) SC_ROW(k)
+#undef SC_G_PUT
+#undef SC_X_PUT
   // back substitution in registers, then one store per cell (+ mirrors on physical boundaries)
 #pragma unroll
   for (int k = NZ - 1; k >= 1; k--) x[k - 1] = x[k - 1] - g[k] * x[k];
@@ -212,9 +139,6 @@ __device__ __forceinline__ void relax_col_nz(const LevView &L, const int i, cons
   }
   if (SNAP && L.d0w != nullptr) L.d0w[(long long)i * RS + c] = x[0] - L.p1[(long long)i * RS + c];  // mgx_rbseq.hip (b): d0, what k_rbseq_d0 would compute from the stored y
   if (SNAP && L.p1w != nullptr) COL_SNAPSHOT(L, RS, i, c, x[0])
-#undef NB_LOAD
-#undef OW_LOAD
-#undef NB_USE
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -615,8 +539,8 @@ int mgxk_relax_small(hipStream_t st, const LevView *L, int nsweeps, int method, 
 #undef SMALL_CASE
 }
 
-// returns 1 when the launched kernel also wrote the physical-boundary mirrors of p (no k_halo_phys needed)
-// returns bit 0: the kernel stored the physical mirrors itself; bit 1: it wrote L->d0w
+// returns bit 0: the kernel stored the physical mirrors of p itself (no k_halo_phys needed); bit 1: it wrote L->d0w; bit 2: it was the
+// stored-coefficient tall-column pass (mgx_relax_tall.hip; relax() counts those)
 int mgxk_relax_colour(hipStream_t st, const LevView *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, Sides ph) {
   if (const int ks = mgxk_relax_ks(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph)) return ks;  // mid levels: rows split over the waves of a workgroup
   switch (L->nz) {
@@ -635,7 +559,7 @@ int mgxk_relax_colour(hipStream_t st, const LevView *L, int i0, int istep, int n
     case 24: launch_relax_nz<24>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
     case 40: launch_relax_nz<40>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
     case 48: launch_relax_nz<48>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
-    case 80: case 96: case 128: if (mgxk_relax_tall(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph)) return 1; break;
+    case 80: case 96: case 128: if (const int tall = mgxk_relax_tall(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph)) return tall; break;
 #endif
     default: break;
   }
@@ -649,7 +573,7 @@ int mgxk_relax_colour(hipStream_t st, const LevView *L, int i0, int istep, int n
 int mgxk_has_reg_kernel(const LevView *L) {
   switch (L->nz) {
     case 2: case 4: case 8: case 16: case 32: case 64: case 12: case 20: case 24: case 40: case 48: return 1;
-    case 80: case 96: case 128: return L->zy != nullptr && getenv("MGX_NO_TALL") == nullptr;
+    case 80: case 96: case 128: return getenv("MGX_NO_TALL") == nullptr;  // matrix-free or stored: mgxk_relax_tall has both
     default: return 0;
   }
 }

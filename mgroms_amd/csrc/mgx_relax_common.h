@@ -1,5 +1,6 @@
 // What the colour-pass kernels of the z-line smoother share (mgx_relax.hip, mgx_relax_tall.hip, mgx_relax_ks.hip): the XCD-aware
-// block map and the one definition of the matrix-free column pass (COL_POS, COL_IMAGES: mgx_device.h).
+// block map, the one definition of the matrix-free column pass and, at the end, the one of the stored-coefficient column pass
+// (COL_POS, COL_IMAGES: mgx_device.h).
 #pragma once
 #include "mgx_device.h"
 
@@ -198,4 +199,95 @@
     pjm_m = pjm_0; pjm_0 = pjm_p; pim_m = pim_0; pim_0 = pim_p;                                           \
     pjp_m = pjp_0; pjp_0 = pjp_p; pip_m = pip_0; pip_0 = pip_p;                                           \
     zy_m = zy_0; zy_0 = zy_p; zx_m = zx_0; zx_0 = zx_p;                                                   \
+  }
+
+// ------------------------------------------------------------------------------------------------
+// The stored-coefficient column pass: ONE text for relax_col_nz (mgx_relax.hip, nz <= 64) and relax_col_st_tall
+// (mgx_relax_tall.hip): slots 2-8 and the pivots bet as define_matrices or mgx_set_field(cA) left them, nothing regenerated (masked
+// domains, user matrices, MGX_NO_MF).  The rhs of a row after mg_relax.f90:262-301, same terms in the same order.  Macros for the
+// reason given above; the instances of relax_col_nz compile to the instructions they had when this text stood in their function.
+//
+// The caller has in scope: NZ, D (look-ahead rows), REAL, SNAP, ST (compile-time); L, i, c, jm, jp; and two sinks,
+//   SC_G_PUT(k, v)  gam(k) = a2(k)*bet(k-1), k = 2 .. NZ
+//   SC_X_PUT(k, v)  the forward value of row k, k = 1 .. NZ.
+// SC_PROLOGUE(XN, GN) declares the column's pointers, load rings, x[XN], g[GN] and fills the rings; SC_ROW(k) is one forward row, to
+// be called for k = 1 .. NZ in order from fully unrolled loops.
+// ------------------------------------------------------------------------------------------------
+#define SC_NB_LOAD(q)                                                            \
+  if ((q) <= NZ) {                                                               \
+    const long long ro_ = (long long)((q)-1) * RS; const int s_ = (q) % RN;      \
+    r_pjm[s_] = p[o + ro_ + jm]; r_pim[s_] = p[om + ro_ + c];                    \
+    r_pjp[s_] = p[o + ro_ + jp]; r_pip[s_] = p[op + ro_ + c];                    \
+    r_a3[s_] = a3[o + ro_ + jp]; r_a4[s_] = a4[o + ro_ + jp]; r_a5[s_] = a5[o + ro_ + jp]; \
+    r_a6[s_] = a6[op + ro_ + c]; r_a7[s_] = a7[op + ro_ + c]; r_a8[s_] = a8[op + ro_ + c]; \
+  }
+#define SC_OW_LOAD(q)                                                            \
+  if ((q) <= NZ) {                                                               \
+    const long long ko_ = o + (long long)((q)-1) * RS + c; const int s_ = (q) % RO; \
+    o_b[s_] = ld_stream<ST>(b + ko_); o_a2[s_] = ld_stream<ST>(a2 + ko_); o_a3[s_] = ld_stream<ST>(a3 + ko_); o_a4[s_] = ld_stream<ST>(a4 + ko_); o_a5[s_] = ld_stream<ST>(a5 + ko_); \
+    o_a6[s_] = ld_stream<ST>(a6 + ko_); o_a7[s_] = ld_stream<ST>(a7 + ko_); o_a8[s_] = ld_stream<ST>(a8 + ko_); o_bet[s_] = ld_stream<ST>(bet + ko_); \
+  }
+// products of a raw neighbour row (computed when the row is first needed)
+#define SC_NB_USE(q, PJM, PIM, M3, M4, M5, N6, N7, N8)                           \
+  { const int s_ = (q) % RN; PJM = r_pjm[s_]; PIM = r_pim[s_];                   \
+    M3 = r_a3[s_] * r_pjp[s_]; M4 = r_a4[s_] * r_pjp[s_]; M5 = r_a5[s_] * r_pjp[s_]; \
+    N6 = r_a6[s_] * r_pip[s_]; N7 = r_a7[s_] * r_pip[s_]; N8 = r_a8[s_] * r_pip[s_]; }
+
+#define SC_PROLOGUE(XN, GN)                                                                               \
+  const long long RS = L.RS;                                                                              \
+  double *__restrict__ p = L.p;                                                                           \
+  const double *__restrict__ b = L.b;                                                                     \
+  const double *__restrict__ a2 = L.cA[1], *__restrict__ a3 = L.cA[2], *__restrict__ a4 = L.cA[3],        \
+               *__restrict__ a5 = L.cA[4], *__restrict__ a6 = L.cA[5], *__restrict__ a7 = L.cA[6],        \
+               *__restrict__ a8 = L.cA[7], *__restrict__ bet = L.bet;                                     \
+  const long long o = (long long)i * L.plane, om = o - L.plane, op = o + L.plane;                         \
+  constexpr int RN = D + 1;  /* raw neighbour rows in flight */                                           \
+  constexpr int RO = D + 1;  /* raw own rows in flight */                                                 \
+  double r_pjm[RN], r_pim[RN], r_pjp[RN], r_pip[RN], r_a3[RN], r_a4[RN], r_a5[RN], r_a6[RN], r_a7[RN], r_a8[RN]; \
+  double o_b[RO], o_a2[RO], o_a3[RO], o_a4[RO], o_a5[RO], o_a6[RO], o_a7[RO], o_a8[RO], o_bet[RO];        \
+  double x[XN], g[GN];  /* the forward values and gam that stay in registers (the sinks' business) */     \
+  /* k = 1 horizontal-diagonal terms (issued first: independent of everything else); red-black reads them from the snapshot */ \
+  double d1 = 0, d2 = 0, d3 = 0, d4 = 0, e1 = 0, e2 = 0, e3 = 0, e4 = 0;                                  \
+  if (REAL) {                                                                                             \
+    const double *__restrict__ q1 = SNAP ? L.p1 : p;                                                      \
+    const long long s = SNAP ? (long long)i * RS : o, sm = SNAP ? s - RS : om, sp = SNAP ? s + RS : op;   \
+    d1 = q1[sm + jp]; d2 = q1[sp + jm]; d3 = q1[sm + jm]; d4 = q1[sp + jp];                               \
+    e1 = a5[o + c]; e2 = a5[op + jm]; e3 = a8[o + c]; e4 = a8[op + jp];                                   \
+  }                                                                                                       \
+  /* neighbour rows 1..1+D and own rows 1..D */                                                           \
+  _Pragma("unroll") for (int q = 1; q <= 1 + D; q++) { SC_NB_LOAD(q) }                                    \
+  _Pragma("unroll") for (int q = 1; q <= D; q++) { SC_OW_LOAD(q) }                                        \
+  double pjm_m = 0, pjm_0, pjm_p, pim_m = 0, pim_0, pim_p;                                                \
+  double m3_m = 0, m3_0, m4_0, m5_p, n6_m = 0, n6_0, n7_0, n8_p, m3_p, m4_p, n6_p, n7_p, dum5, dum8;      \
+  SC_NB_USE(1, pjm_0, pim_0, m3_0, m4_0, dum5, n6_0, n7_0, dum8)                                          \
+  (void)dum5; (void)dum8;                                                                                 \
+  double xv = 0.0, betp = 0.0;
+
+#define SC_ROW(k)                                                                                         \
+  {                                                                                                       \
+    /* keep the pipeline full */                                                                          \
+    SC_NB_LOAD(k + 1 + D)                                                                                 \
+    SC_OW_LOAD(k + D)                                                                                     \
+    if (k < NZ) { SC_NB_USE(k + 1, pjm_p, pim_p, m3_p, m4_p, m5_p, n6_p, n7_p, n8_p) }                    \
+    const int s = k % RO;                                                                                 \
+    double rhs;                                                                                           \
+    /* gam(k) = dd(k-1)*bet(k-1) (mg_relax.f90:325), from values already in registers: no gam stream from HBM */ \
+    if (k > 1) SC_G_PUT(k, o_a2[s] * betp)                                                                \
+    betp = o_bet[s];                                                                                      \
+    if (k == 1) {                                                                                         \
+      rhs = o_b[s] - o_a3[s] * pjm_p - o_a4[s] * pjm_0 - m4_0 - m5_p - o_a6[s] * pim_p - o_a7[s] * pim_0 - n7_0 - n8_p; \
+      if (REAL) rhs = rhs - e1 * d1 - e2 * d2 - e3 * d3 - e4 * d4;                                        \
+      xv = rhs * o_bet[s];                                                                                \
+    } else if (k < NZ) {                                                                                  \
+      rhs = o_b[s] - o_a3[s] * pjm_p - m3_m - o_a4[s] * pjm_0 - m4_0 - o_a5[s] * pjm_m - m5_p             \
+                   - o_a6[s] * pim_p - n6_m - o_a7[s] * pim_0 - n7_0 - o_a8[s] * pim_m - n8_p;            \
+      xv = (rhs - o_a2[s] * xv) * o_bet[s];                                                               \
+    } else {                                                                                              \
+      rhs = o_b[s] - m3_m - o_a4[s] * pjm_0 - m4_0 - o_a5[s] * pjm_m - n6_m - o_a7[s] * pim_0 - n7_0 - o_a8[s] * pim_m; \
+      xv = (rhs - o_a2[s] * xv) * o_bet[s];                                                               \
+    }                                                                                                     \
+    SC_X_PUT(k, xv)                                                                                       \
+    /* rotate the three-row window */                                                                     \
+    pjm_m = pjm_0; pjm_0 = pjm_p; pim_m = pim_0; pim_0 = pim_p;                                           \
+    m3_m = m3_0; m3_0 = m3_p; m4_0 = m4_p; n6_m = n6_0; n6_0 = n6_p; n7_0 = n7_p;                         \
   }
