@@ -235,6 +235,14 @@ int mgx_set_verbose(int level);
  *   fields, allocated at the first solve with the option on and freed by mgx_clean (143 MB each at 512x512x64: 1.4 GB for m = 4).  Refused by
  *   solve_p together with "cycle_precision" = 32.  Three all-reduce calls per iteration on a process grid (one per pass).
  *   Read-only: "krylov_restarts" (times the last solve fell back to the true residual).
+ * "krylov_precision" (64 default, or 32; any other value is refused; survives mgx_clean / mgx_init; acts only while "krylov" > 0, inert otherwise):
+ *   32 = the preconditioner of the Krylov loop is the fp32 F-cycle of "cycle_precision" = 32 (A e = r / N from e = 0 on the fp32 copies, N = the
+ *   residual norm the loop holds as the iteration starts).  The iterate, the recurrence, every inner product, the true residual and the stopping
+ *   test stay fp64; GCR takes the inexact preconditioner as it is.  The loop adds no conversion pass in steady state: pass 3 leaves the next
+ *   cycle's right-hand side in fp32 and pass 1 reads the cycle's fp32 result (mgx_krylov.hip).  "cycle_precision" stays 64 (the pair "krylov" > 0,
+ *   "cycle_precision" = 32 is refused as before).  Refused at the first such solve like "cycle_precision" = 32 and in its words: a process
+ *   grid larger than 1 x 1, relax_method = 'GS', option "rb_exact".
+ *   Read-only: "krylov_mixed_iterations" (Krylov iterations run with an fp32 cycle since mgx_init); "mixed_iterations" does not count them.
  * Read-only through mgx_get_option: "p2p_failed" (a peer-to-peer wait of THIS rank timed out since the ranks last agreed: see below),
  *   "overlapped_passes", "tall_stored_passes" (colour passes of nz = 80, 96, 128 levels served by the stored-coefficient tall-column kernel
  *   since mgx_init: bmask, mgx_set_field(cA) or MGX_NO_MF; 0 while the matrix-free form runs or under MGX_NO_TALL). */
@@ -281,6 +289,11 @@ int mgx_mixed_op(const char *op, int lev, int n);
  *                  (z -= sum beta_n z_n, q -= sum beta_n q_n, beta_n = sin[n] / sin[8 + slot[n]]); sout[0] = (q, q), sout[1] = (r, q).
  *   op = "update": fields = p, r, z, q; sin = {s, t}; the new pair's ring slot is nd.  p += (t / s) z, r -= (t / s) q are rewritten;
  *                  sout[0] = ||r||^2, or -1 when s, t allow no step (p, r untouched); sout[1] = what the pass filed under that slot (s).
+ *   op = "apply32":  pass 1 of "krylov_precision" = 32.  fields = e, z, q, q_1 .. q_nd; sin[0] = 1 / sigma.  e holds doubles that fp32
+ *                  represents exactly; the hook demotes them into the fp32 copy of level 1.  z = (double)e * sin[0] (whole array, halo cells
+ *                  included) and q = A z are written; sout[0..nd-1] = (q, q_n).  Refused where "cycle_precision" = 32 is.
+ *   op = "update32": pass 3 of "krylov_precision" = 32.  fields = p, r, z, q, f; sin = {s, t, sigma}.  As "update", and f (demoted into the fp32
+ *                  copy on the way in, promoted exactly on the way out) receives (float)(sigma r) of the new r; no step: f untouched too.
  * Sums run over interior cells.  path (may be NULL) receives the launch taken: matrix-free operator (1) or stored slots (0), cmatrix='real',
  * the non-temporal variant, gx, gy of pass 1's block map.  No Fortran counterpart. */
 int mgx_krylov_op(const char *op, int nd, double *const *fields, const int *slot, const double *sin, double *sout, int *path);

@@ -72,6 +72,7 @@ const Opt OPTIONS[] = {
   {"fuse_tail",           &State::use_fuse,         nullptr,       nullptr,                   ENV_NONE, RW, true},
   {"cycle_precision",     &State::cycle_precision,  nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 32 / 64 only
   {"krylov",              &State::krylov,           nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0..8 only
+  {"krylov_precision",    &State::krylov_precision, nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 32 / 64 only (no preset: the table's would pass any number by)
   // reads as off while a time-out of this solver holds (ksp_down, which mgx_clean does not carry); set: see mgx_set_option
   {"ksp",                 &State::use_ksp,          [](const State &s) { return (s.use_ksp && !s.ksp_down) ? 1 : 0; }, "MGX_NO_KSP", ENV_ZERO, RW, true},
   {"p2p",                 nullptr,                  [](const State &s) { return s.p2p_on ? 1 : 0; }, nullptr, ENV_NONE, RW, false},   // set: see mgx_set_option
@@ -85,6 +86,7 @@ const Opt OPTIONS[] = {
   {"tall_stored_passes", nullptr, CNT(n_tall_stored), nullptr, ENV_NONE, RO, false},
   {"mixed_iterations", nullptr, CNT(n_mixed), nullptr, ENV_NONE, RO, false},
   {"krylov_restarts", nullptr, CNT(kr_restarts), nullptr, ENV_NONE, RO, false},
+  {"krylov_mixed_iterations", nullptr, CNT(n_kr_mixed), nullptr, ENV_NONE, RO, false},
   {"p2p_failed", nullptr, CNT(p2p_failed), nullptr, ENV_NONE, RO, false},
 };
 #undef PAR
@@ -376,6 +378,7 @@ int mgx_level_table(int nx, int ny, int nz, int npx, int npy, int rank, int nsma
 int mgx_set_option(const char *name, int value) {
   // the options with behaviour of their own
   if (streq(name, "cycle_precision") && value != 32 && value != 64) return fail("cycle_precision must be 64 (fp64 cycles) or 32 (fp32 cycles under fp64 refinement), got %d", value);
+  if (streq(name, "krylov_precision") && value != 32 && value != 64) return fail("krylov_precision must be 64 (fp64 cycles under the Krylov loop) or 32 (fp32 cycles under it), got %d", value);
   if (streq(name, "krylov") && (value < 0 || value > 8)) return fail("krylov must be 0 (off) or 1..8 (retained direction pairs of the truncated GCR), got %d", value);
   if (streq(name, "ksp")) { S.use_ksp = value; if (value) S.ksp_down = 0; return 0; }  // switching it on again also clears a time-out of this solver
   if (streq(name, "rbseq_timeout_ms")) { if (mgxk_set_rbseq_timeout((double)value)) return fail("rbseq_timeout_ms: could not set the device constant"); return 0; }

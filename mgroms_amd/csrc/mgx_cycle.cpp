@@ -621,6 +621,11 @@ int solve_p_mixed(double tol, int maxite, int *nite_out, double *res_out, double
 // the m retained pairs, p += (t / s) z, r -= (t / s) q with s = (q, q), t = (r, q).  The F-cycle reads level 1 through its view, so the
 // view's p / b / r are pointed at (z, r, scratch) for the cycle and back afterwards: nothing is copied.  r of the recurrence lives in
 // grid(1)%r; the scratch r of the cycle is the q of the pair in work, which is only written after the cycle.
+// Option "krylov_precision" = 32: M is the fp32 F-cycle of solve_p_mixed, A e = f from e = 0 on the shadows with f = r / N, and z = N e.  GCR
+// takes an inexact, even a varying, preconditioner, and N only has to keep |f| <= ~1, so N is the norm the host already holds as the
+// iteration starts: the true residual's after the start and after a restart, the recurrence's otherwise (the history is monotone).  Pass 3
+// leaves f for the next cycle (k_kr_update32) and pass 1 reads e (k_kr_apply32): the only conversion launch is the k_to32 of a fresh r.  The
+// fp32 cycle never touches the fp64 view, so no ViewSwap around it.
 // The recurrence's r drifts away from b - A p near round-off, so no convergence is reported on its word: the true residual is computed
 // (compute_residual(1)) before the loop is left, and where it is not below tol it becomes r, the retained pairs are dropped
 // (kr_restarts) and the loop goes on.  On every exit grid(1)%r, *res and the last hist entry are the true residual's.
@@ -649,10 +654,13 @@ int krylov_allreduce(double *buf, int n) {
 
 int solve_p_krylov(double tol, int maxite, int *nite_out, double *res_out, double *hist) {
   const int m = S.krylov;
+  const bool lowp = S.krylov_precision == 32;
+  if (lowp) { CHK(mixed_check()); CHK(mixed_prepare()); }
   CHK(krylov_prepare(m));
   SolveRun run(hist);
   Level &L = run.L;
   double rnorm; CHK(run.begin(&rnorm));   // the true residual, into grid(1)%r
+  double rabs = rnorm, fnorm = 1.0;       // lowp: ||r|| as the iteration starts (see above); the shadow's f holds r / fnorm
   ViewSwap own(L.v);
   double *sc = S.kr_sc, *qq = S.kr_sc + 16;
   int kept = 0, head = 0;   // retained pairs: the `kept` slots before `head` in the ring of m + 1; head = the pair in work
@@ -661,7 +669,12 @@ int solve_p_krylov(double tol, int maxite, int *nite_out, double *res_out, doubl
   for (;;) {
     while (run.more(tol, maxite)) {
       double *z = S.kr_z[head], *q = S.kr_q[head];
-      {  // z = M r: Fcycle on (p, b) = (0, r).  The first leg restricts the view's r, the rest of the cycle may use it as scratch.
+      const double nscale = rabs > 0.0 ? rabs : 1.0;
+      if (lowp) {  // e = M f on the shadows; z is formed by pass 1
+        if (fresh) { fnorm = nscale; mgxx_to32(S.stream, &L.v, &L.v32, own.r, L.v32.f, 1.0 / fnorm); S.n_launch++; }
+        HIPCHK(hipMemsetAsync(L.v32.e, 0, L.n3js32 * sizeof(float), S.stream));
+        fcycle32();
+      } else {  // z = M r: Fcycle on (p, b) = (0, r).  The first leg restricts the view's r, the rest of the cycle may use it as scratch.
         HIPCHK(hipMemsetAsync(z, 0, L.n3js * sizeof(double), S.stream));
         L.v.p = z; L.v.b = own.r; L.v.r = own.r;
         int rc = S.nlevs >= 2 ? fine2coarse(1, true) : 0;
@@ -675,7 +688,9 @@ int solve_p_krylov(double tol, int maxite, int *nite_out, double *res_out, doubl
       {
         TicScope t1(1, "krylov_apply");
         LevView zv = L.v; zv.p = z;
-        mgxq_apply(S.stream, &zv, q, qi, kept, S.kr_partial, sc, S.real); S.n_launch += kept ? 2 : 1;
+        if (lowp) mgxq_apply32(S.stream, &L.v, &L.v32, fnorm, z, q, qi, kept, S.kr_partial, sc, S.real);
+        else mgxq_apply(S.stream, &zv, q, qi, kept, S.kr_partial, sc, S.real);
+        S.n_launch += kept ? 2 : 1;
         CHK(krylov_allreduce(sc, kept));
       }
       {
@@ -686,18 +701,22 @@ int solve_p_krylov(double tol, int maxite, int *nite_out, double *res_out, doubl
       double s2;
       {
         TicScope t3(1, "krylov_update");
-        mgxq_update(S.stream, &L.v, own.p, own.r, z, q, sc + 8, qq + head, S.kr_partial, S.d_scalar); S.n_launch += 2;
+        if (lowp) { mgxq_update32(S.stream, &L.v, &L.v32, own.p, own.r, z, q, 1.0 / nscale, sc + 8, qq + head, S.kr_partial, S.d_scalar); fnorm = nscale; }
+        else mgxq_update(S.stream, &L.v, own.p, own.r, z, q, sc + 8, qq + head, S.kr_partial, S.d_scalar);
+        S.n_launch += 2;
         CHK(global_sum(L, &s2));   // the iteration's one host synchronisation: the stopping test
       }
       fresh = false;
       if (!(s2 >= 0.0)) { broke = true; break; }   // no step was taken (s == 0 or a non-finite scalar): p is what it was
-      run.step(sqrt(s2) / run.bnorm);
+      rabs = sqrt(s2);
+      run.step(rabs / run.bnorm);
+      if (lowp) S.n_kr_mixed++;
       if (kept < m) kept++;
       head = (head + 1) % (m + 1);
     }
     if (fresh) break;
     CHK(residual(1, &rnorm));   // b - A p into grid(1)%r: the word that counts
-    fresh = true;
+    fresh = true; rabs = rnorm;
     run.res0 = rnorm / run.bnorm;   // (not printed: the lines above are the recurrence's)
     if (hist) hist[run.nite] = run.res0;
     if (broke || run.nite >= maxite || !(run.res0 > tol)) break;
@@ -713,8 +732,9 @@ int solve_p_krylov(double tol, int maxite, int *nite_out, double *res_out, doubl
 // The retained pair n sits in ring slot slot[n] (0..nd, distinct; nullptr = 0..nd-1) and the pair in work in the slot left free.
 int krylov_op(const char *op, int nd, double *const *f, const int *slot, const double *sin, double *sout, int *path) {
   if (!op) return fail("mgx_krylov_op: op is NULL");
-  const int which = streq(op, "apply") ? 1 : streq(op, "ortho") ? 2 : streq(op, "update") ? 3 : 0;
-  if (!which) return fail("mgx_krylov_op: unknown pass '%s' (apply, ortho, update)", op);
+  const int which = streq(op, "apply") ? 1 : streq(op, "ortho") ? 2 : streq(op, "update") ? 3 : streq(op, "apply32") ? 4 : streq(op, "update32") ? 5 : 0;
+  if (!which) return fail("mgx_krylov_op: unknown pass '%s' (apply, ortho, update, apply32, update32)", op);
+  if (which >= 4) { CHK(mixed_check()); CHK(mixed_prepare()); }
   if (nd < 0 || nd > 8) return fail("mgx_krylov_op(%s): nd = %d retained pairs (0..8)", op, nd);
   int sl[8], head = nd, used = 0;
   for (int n = 0; n < nd; n++) {
@@ -722,7 +742,7 @@ int krylov_op(const char *op, int nd, double *const *f, const int *slot, const d
     if (sl[n] < 0 || sl[n] > nd || (used >> sl[n] & 1)) return fail("mgx_krylov_op(%s): slot[%d] = %d (distinct values of 0..%d)", op, n, sl[n], nd);
     used |= 1 << sl[n];
   }
-  if (which != 3) for (head = 0; used >> head & 1;) head++;
+  if (which != 3 && which != 5) for (head = 0; used >> head & 1;) head++;
   CHK(krylov_prepare(nd));
   Level &L = S.lev[0];
   const size_t n3 = (size_t)L.nz * (L.ny + 2) * (L.nx + 2);
@@ -756,6 +776,27 @@ int krylov_op(const char *op, int nd, double *const *f, const int *slot, const d
     mgxq_ortho(S.stream, &L.v, z, q, L.v.r, zi, qi, sl, nd, sc, qq, S.kr_partial, sc + 8);
     CHK(get(f[0], z)); CHK(get(f[1], q));
     HIPCHK(hipMemcpyAsync(sout, sc + 8, 2 * sizeof(double), hipMemcpyDeviceToHost, S.stream));
+  } else if (which == 4) {   // f = e (doubles that fp32 holds exactly), z, q (both out), q_1 .. q_nd; sin[0] = 1 / sigma; sout[0..nd-1] = (q, q_i)
+    CHK(put(f[0], L.v.p));     // e reaches the shadow through grid(1)%p
+    mgxx_to32(S.stream, &L.v, &L.v32, L.v.p, L.v32.e, 1.0);
+    { const std::vector<double> nan(n3, std::nan("")); CHK(put(nan.data(), z)); CHK(sync_stream()); }   // a cell of z the pass leaves out reads back as not-a-number
+    for (int n = 0; n < nd; n++) CHK(put(f[3 + n], S.kr_q[sl[n]]));
+    mgxq_apply32(S.stream, &L.v, &L.v32, sin[0], z, q, qi, nd, S.kr_partial, sc, S.real);
+    CHK(get(f[1], z)); CHK(get(f[2], q));
+    if (nd) HIPCHK(hipMemcpyAsync(sout, sc, nd * sizeof(double), hipMemcpyDeviceToHost, S.stream));
+  } else if (which == 5) {   // f = p, r (both rewritten), z, q, f (rewritten: the shadow's f, promoted); sin = {s, t, sigma}; slot and sout as "update"
+    CHK(put(f[4], L.v.p));     // f reaches the shadow through grid(1)%p
+    mgxx_to32(S.stream, &L.v, &L.v32, L.v.p, L.v32.f, 1.0);
+    CHK(put(f[0], L.v.p)); CHK(put(f[1], L.v.r)); CHK(put(f[2], z)); CHK(put(f[3], q));
+    L.r_halo_stale = false;
+    HIPCHK(hipMemcpyAsync(sc + 8, sin, 2 * sizeof(double), hipMemcpyHostToDevice, S.stream));
+    HIPCHK(hipMemsetAsync(qq, 0xff, 9 * sizeof(double), S.stream));
+    mgxq_update32(S.stream, &L.v, &L.v32, L.v.p, L.v.r, z, q, sin[2], sc + 8, qq + head, S.kr_partial, S.d_scalar);
+    CHK(get(f[0], L.v.p)); CHK(get(f[1], L.v.r));
+    mgxx_to64(S.stream, &L.v, &L.v32, L.v32.f, z, 1.0, 0);
+    CHK(get(f[4], z));
+    HIPCHK(hipMemcpyAsync(sout, S.d_scalar, sizeof(double), hipMemcpyDeviceToHost, S.stream));
+    HIPCHK(hipMemcpyAsync(sout + 1, qq + head, sizeof(double), hipMemcpyDeviceToHost, S.stream));
   } else {                   // f = p, r (both rewritten), z, q; sin = {s, t}; the new pair's ring slot is nd; sout = {||r||^2 or -1, what was filed there}
     CHK(put(f[0], L.v.p)); CHK(put(f[1], L.v.r)); CHK(put(f[2], z)); CHK(put(f[3], q));
     L.r_halo_stale = false;

@@ -150,6 +150,11 @@ struct State {
   int krylov = 0;
   int kr_restarts = 0;            // read-only option "krylov_restarts": times the last solve fell back to the true residual
   int kr_n = 0;
+  // option "krylov_precision" (64 default, 32; acts while krylov > 0): the preconditioner is the fp32 F-cycle of "cycle_precision" = 32 on the
+  // shadows, A e = sigma r from e = 0.  The two conversions live in passes the loop runs anyway (k_kr_update32 leaves f = (float)(sigma r),
+  // k_kr_apply32[_mf] reads z = e / sigma straight from the shadow): no conversion launch in steady state.
+  int krylov_precision = 64;
+  long long n_kr_mixed = 0;       // read-only option "krylov_mixed_iterations": Krylov iterations run with an fp32 cycle since mgx_init
   double *kr_z[9] = {}, *kr_q[9] = {}, *kr_sc = nullptr, *kr_partial = nullptr;
   long long n_mixed = 0;          // read-only option "mixed_iterations": solve_p iterations run with fp32 cycles since mgx_init
   bool mx_ready = false;

@@ -30,7 +30,7 @@ __global__ __launch_bounds__(256) void k_residual(LevView L, double *__restrict_
     COL_POS(L, jh, jodd, c, jm, jp)
     const double *__restrict__ b = L.b;
     double *__restrict__ r = L.r;
-    OP_COLUMN(RES_RHS, RES_SINK)
+    OP_COLUMN(OP_P, RES_RHS, RES_SINK)
   }
   if (!want_norm) return;
   OP_BLOCK_SUM(acc, partial, blockIdx.x)
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void k_residual_mf(LevView L, double *__restri
     COL_POS(L, jh, jodd, c, jm, jp)
     const double *__restrict__ b = L.b;
     double *__restrict__ r = L.r;
-    OP_COLUMN_MF(RES_RHS_MF, RES_SINK_MF)
+    OP_COLUMN_MF(OP_P, OP_P2, RES_RHS_MF, RES_SINK_MF)
   }
   if (!want_norm) return;
   OP_BLOCK_SUM(acc, partial, blockIdx.x)

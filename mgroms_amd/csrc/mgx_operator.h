@@ -41,20 +41,27 @@ __device__ __forceinline__ void op_block_map(int gx, int gy, int &bx, int &by, i
 
 // ------------------------------------------------------------------------------------------------
 // The column from the stored slots: rr(k) = rhs(k) - (A p)(k), k = 1 .. nz, one lane = one (j, i) column.
-// The caller has in scope: REAL (compile-time); L, i, jh, jodd, c, jm, jp; and two hooks,
+// The caller has in scope: REAL (compile-time); L, i, jh, jodd, c, jm, jp; and three hooks,
+//   PV(pl, ro, kr, pos)  the value of p at plane offset pl (o, om, op), row offset ro = kr * RS (kr = the row, from 0), position pos
+//                     (c, jm, jp), every argument spelt by its name here: OP_P reads L.p; pass 1 of the Krylov loop with an fp32
+//                     preconditioner (mgx_krylov.hip) promotes the cycle's fp32 result instead, which lives in another layout, and
+//                     finds it by those names.  With OP_P the text is, token for token, what it was with p[...] written out.
 //   RHS(ko)           the row's right-hand side (ko = the row's offset in a level-1 array)
 //   SINK(ro, ko, rr)  the row's sink (ro = the row's offset inside its plane; jcol = the column's j is in scope, declared where
-//                     the residual has always computed it: earlier, its kernel allocates registers differently)
+//                     the residual has always computed it: earlier, its kernel allocates registers differently; pc_0 = the column's
+//                     own p of this row, in either column text)
 // ------------------------------------------------------------------------------------------------
-#define LOAD_ROW(q, PJM, PIM, PC, A2, M3, M4, M5, N6, N7, N8)                                                                                \
+#define OP_P(pl, ro, kr, pos) p[pl + ro + pos]
+#define OP_P2(pl, ro, kr, pos, A, B) LD_PAIR(p + pl + ro + pos, A, B)
+#define LOAD_ROW(PV, q, PJM, PIM, PC, A2, M3, M4, M5, N6, N7, N8)                                                                            \
   {                                                                                                                                          \
     const long long ro = (long long)((q)-1) * RS;                                                                                            \
-    PJM = p[o + ro + jm]; PIM = p[om + ro + c]; PC = p[o + ro + c]; A2 = a2[o + ro + c];                                                     \
-    const double pj_ = p[o + ro + jp], pi_ = p[op + ro + c];                                                                                 \
+    PJM = PV(o, ro, (q)-1, jm); PIM = PV(om, ro, (q)-1, c); PC = PV(o, ro, (q)-1, c); A2 = a2[o + ro + c];                                   \
+    const double pj_ = PV(o, ro, (q)-1, jp), pi_ = PV(op, ro, (q)-1, c);                                                                     \
     M3 = a3[o + ro + jp] * pj_; M4 = a4[o + ro + jp] * pj_; M5 = a5[o + ro + jp] * pj_;                                                      \
     N6 = a6[op + ro + c] * pi_; N7 = a7[op + ro + c] * pi_; N8 = a8[op + ro + c] * pi_;                                                      \
   }
-#define OP_COLUMN(RHS, SINK)                                                                                                                 \
+#define OP_COLUMN(PV, RHS, SINK)                                                                                                             \
   {                                                                                                                                          \
     const long long RS = L.RS;                                                                                                               \
     const int nz = L.nz;                                                                                                                     \
@@ -66,20 +73,20 @@ __device__ __forceinline__ void op_block_map(int gx, int gy, int &bx, int &by, i
     double pjm_m, pjm_0, pjm_p, pim_m, pim_0, pim_p, pc_m, pc_0, pc_p, a2_0, a2_p;                                                           \
     double m3_m, m3_0, m4_0, m5_p, n6_m, n6_0, n7_0, n8_p, m3_p, m4_p, n6_p, n7_p;                                                           \
     double dum5, dum8;                                                                                                                       \
-    LOAD_ROW(1, pjm_0, pim_0, pc_0, a2_0, m3_0, m4_0, dum5, n6_0, n7_0, dum8);                                                               \
-    LOAD_ROW(2, pjm_p, pim_p, pc_p, a2_p, m3_p, m4_p, m5_p, n6_p, n7_p, n8_p);                                                               \
+    LOAD_ROW(PV, 1, pjm_0, pim_0, pc_0, a2_0, m3_0, m4_0, dum5, n6_0, n7_0, dum8);                                                           \
+    LOAD_ROW(PV, 2, pjm_p, pim_p, pc_p, a2_p, m3_p, m4_p, m5_p, n6_p, n7_p, n8_p);                                                           \
     (void)dum5; (void)dum8;                                                                                                                  \
     /* k = 1 (:464-482) */                                                                                                                   \
     double rr = RHS(o + c) - a1[o + c] * pc_0 - a2_p * pc_p - a3[o + c] * pjm_p - a4[o + c] * pjm_0 - m4_0 - m5_p                            \
                 - a6[o + c] * pim_p - a7[o + c] * pim_0 - n7_0 - n8_p;                                                                       \
     if (REAL)                                                                                                                                \
-      rr = rr - a5[o + c] * p[om + jp] - a5[op + jm] * p[op + jm] - a8[o + c] * p[om + jm] - a8[op + jp] * p[op + jp];                       \
+      rr = rr - a5[o + c] * PV(om, 0, 0, jp) - a5[op + jm] * PV(op, 0, 0, jm) - a8[o + c] * PV(om, 0, 0, jm) - a8[op + jp] * PV(op, 0, 0, jp); \
     const int jcol = jodd ? 2 * jh + 1 : 2 * jh + 2;  /* the column's j, for a sink that stores the physical images */                       \
     SINK(0, o + c, rr)                                                                                                                       \
     for (int k = 2; k <= nz - 1; k++) {  /* (:484-496) */                                                                                    \
       pjm_m = pjm_0; pjm_0 = pjm_p; pim_m = pim_0; pim_0 = pim_p; pc_m = pc_0; pc_0 = pc_p; a2_0 = a2_p;                                     \
       m3_m = m3_0; m3_0 = m3_p; m4_0 = m4_p; n6_m = n6_0; n6_0 = n6_p; n7_0 = n7_p;                                                          \
-      LOAD_ROW(k + 1, pjm_p, pim_p, pc_p, a2_p, m3_p, m4_p, m5_p, n6_p, n7_p, n8_p);                                                         \
+      LOAD_ROW(PV, k + 1, pjm_p, pim_p, pc_p, a2_p, m3_p, m4_p, m5_p, n6_p, n7_p, n8_p);                                                     \
       const long long ko = o + (long long)(k - 1) * RS + c;                                                                                  \
       rr = RHS(ko) - a1[ko] * pc_0 - a2_0 * pc_m - a2_p * pc_p - a3[ko] * pjm_p - m3_m - a4[ko] * pjm_0 - m4_0                               \
                    - a5[ko] * pjm_m - m5_p - a6[ko] * pim_p - n6_m - a7[ko] * pim_0 - n7_0 - a8[ko] * pim_m - n8_p;                          \
@@ -101,19 +108,21 @@ __device__ __forceinline__ void op_block_map(int gx, int gy, int &bx, int &by, i
 // bits as the stored slot 1 -- as the smoother and the fused residual+restriction do); rows 1 and nz, whose formula differs, read the
 // stored one.  The j-1 / j+1 neighbours of p and zy sit side by side in the other half-row: one 16-byte load each.  What only this lane
 // reads (a2, the right-hand side) is streamed past the caches on a level that does not fit them.
-// The caller has in scope: REAL (compile-time); L, i, c, jm, jp, stream; and two hooks,
+// The caller has in scope: REAL (compile-time); L, i, c, jm, jp, stream; PV as above, PV2(pl, ro, kr, pos, A, B) = the values at pos and
+// pos + 1 into A and B (OP_P2: one 16-byte load), and two hooks,
 //   RHS_LOAD(ko)      the request for the row's right-hand side, issued one step ahead with the row's own values (a load or a constant)
 //   SINK(ro, ko, rr)  the row's sink
 // ------------------------------------------------------------------------------------------------
-#define LOAD_WIN(q, PC, PJM, PIM, PJP, PIP, ZY, ZX, A2)                                                                                      \
+#define LOAD_WIN(PV, PV2, q, PC, PJM, PIM, PJP, PIP, ZY, ZX, A2)                                                                                      \
   { const long long ro = (long long)(((q) <= nz ? (q) : nz) - 1) * RS;                                                                       \
-    PC = p[o + ro + c]; LD_PAIR(p + o + ro + jm, PJM, PJP) PIM = p[om + ro + c]; PIP = p[op + ro + c];                                       \
+    const int kr = ((q) <= nz ? (q) : nz) - 1;                                                                                               \
+    PC = PV(o, ro, kr, c); PV2(o, ro, kr, jm, PJM, PJP) PIM = PV(om, ro, kr, c); PIP = PV(op, ro, kr, c);                                    \
     ZY = *(zy + o + ro + c); ZX = *(zx + o + ro + c); A2 = ld_rt(a2 + o + ro + c, stream); }
 #define LOAD_ROWV(RHS_LOAD, q, ZYJM, ZYJP, ZXIM, ZXIP, A4O, A4JP, A7O, A7IP, BK)                                                             \
   { const long long ro = (long long)(((q) <= nz ? (q) : nz) - 1) * RS, ko = o + ro + c;                                                      \
     LD_PAIR(zy + o + ro + jm, ZYJM, ZYJP) ZXIM = zx[om + ro + c]; ZXIP = zx[op + ro + c];                                                    \
     A4O = *(a4 + ko); A4JP = a4[o + ro + jp]; A7O = *(a7 + ko); A7IP = a7[op + ro + c]; BK = RHS_LOAD(ko); }
-#define OP_COLUMN_MF(RHS_LOAD, SINK)                                                                                                         \
+#define OP_COLUMN_MF(PV, PV2, RHS_LOAD, SINK)                                                                                                 \
   {                                                                                                                                          \
     const long long RS = L.RS;                                                                                                               \
     const int nz = L.nz;                                                                                                                     \
@@ -131,13 +140,13 @@ __device__ __forceinline__ void op_block_map(int gx, int gy, int &bx, int &by, i
     /* rows 1 and nz: stored diagonal; row 1: the k = 1 diagonal slots and the four corner values of p (cmatrix = 'real', mg_relax.f90:475-479) */ \
     const double d_first = a1[o + c], d_last = a1[o + (long long)(nz - 1) * RS + c];                                                         \
     double e0 = 0, e1 = 0, e2 = 0, e3 = 0, e4 = 0, e5 = 0, e6 = 0, e7 = 0;                                                                   \
-    if (REAL) { e0 = a5[o + c]; e1 = p[om + jp]; e2 = a5[op + jm]; e3 = p[op + jm]; e4 = a8[o + c]; e5 = p[om + jm]; e6 = a8[op + jp]; e7 = p[op + jp]; } \
-    LOAD_WIN(1, pc_0, pjm_0, pim_0, pjp_0, pip_0, zy_0, zx_0, a2_0)                                                                          \
+    if (REAL) { e0 = a5[o + c]; e1 = PV(om, 0, 0, jp); e2 = a5[op + jm]; e3 = PV(op, 0, 0, jm); e4 = a8[o + c]; e5 = PV(om, 0, 0, jm); e6 = a8[op + jp]; e7 = PV(op, 0, 0, jp); } \
+    LOAD_WIN(PV, PV2, 1, pc_0, pjm_0, pim_0, pjp_0, pip_0, zy_0, zx_0, a2_0)                                                                          \
     LOAD_ROWV(RHS_LOAD, 1, zyjm, zyjp, zxim, zxip, a4o, a4jp, a7o, a7ip, bk)                                                                 \
-    LOAD_WIN(2, pc_p, pjm_p, pim_p, pjp_p, pip_p, zy_p, zx_p, a2_p)                                                                          \
+    LOAD_WIN(PV, PV2, 2, pc_p, pjm_p, pim_p, pjp_p, pip_p, zy_p, zx_p, a2_p)                                                                 \
     for (int k = 1; k <= nz; k++) {                                                                                                          \
       const long long ro = (long long)(k - 1) * RS, ko = o + ro + c;                                                                         \
-      LOAD_WIN(k + 2, pc_n, pjm_n, pim_n, pjp_n, pip_n, zy_n, zx_n, a2_n)                                                                    \
+      LOAD_WIN(PV, PV2, k + 2, pc_n, pjm_n, pim_n, pjp_n, pip_n, zy_n, zx_n, a2_n)                                                           \
       LOAD_ROWV(RHS_LOAD, k + 1, zyjm_n, zyjp_n, zxim_n, zxip_n, a4o_n, a4jp_n, a7o_n, a7ip_n, bk_n)                                         \
       double rr;                                                                                                                             \
       if (k == 1) {                                                                                                                          \

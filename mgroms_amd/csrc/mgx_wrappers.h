@@ -127,10 +127,14 @@ void mgxx_to64(hipStream_t st, const LevView *D, const LevView32 *S, const float
 long long mgxq_partials(const LevView *L);
 void mgxq_path(const LevView *L, int *out);
 void mgxq_apply(hipStream_t st, const LevView *L, double *qout, const double *const *qi, int nd, double *partial, double *sc, int real);
+void mgxq_apply32(hipStream_t st, const LevView *L, const LevView32 *S, double isg, double *zout, double *qout, const double *const *qi, int nd, double *partial,
+                  double *sc, int real);
 void mgxq_ortho(hipStream_t st, const LevView *L, double *z, double *q, const double *r, const double *const *zi, const double *const *qi,
                 const int *slot, int nd, const double *sc, const double *qq, double *partial, double *out);
 void mgxq_update(hipStream_t st, const LevView *L, double *p, double *r, const double *z, const double *q, const double *st2v, double *qq_new,
                  double *partial, double *out);
+void mgxq_update32(hipStream_t st, const LevView *L, const LevView32 *S, double *p, double *r, const double *z, const double *q, double sigma, const double *st2v,
+                   double *qq_new, double *partial, double *out);
 
 // ---- mgx_rccl.cpp ----
 const char *mgxr_last_error(void);

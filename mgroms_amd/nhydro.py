@@ -217,12 +217,12 @@ def mixed_op(op, lev, n=1):
 def krylov_op(op, fields, nd=0, slot=None, sin=(), nout=2):
     """one pass of option "krylov" on level 1 (include/mgx.h: mgx_krylov_op).  fields: the pass's level-1 arrays (nx+2, ny+2, nz) in the
     header's order, C-contiguous float64; the ones the pass writes are rewritten in place.  -> (sout[:nout], path), path = the launch taken
-    as a dict (mf, real, stream, gx, gy)."""
+    as a dict (mf, real, stream, gx, gy).  "apply32" / "update32": the two passes of option "krylov_precision" = 32."""
     nx, ny, nz = _state.dims
     for a in fields:
         if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.shape == (nx + 2, ny + 2, nz)):
             raise ValueError(f"krylov_op: need C-contiguous float64 arrays of shape {(nx + 2, ny + 2, nz)}")
-    want = {"apply": 2 + nd, "ortho": 3 + 2 * nd, "update": 4}.get(op)
+    want = {"apply": 2 + nd, "ortho": 3 + 2 * nd, "update": 4, "apply32": 3 + nd, "update32": 5}.get(op)
     if want is not None and 0 <= nd <= 8 and len(fields) != want:   # (an unknown op or nd is the library's to refuse)
         raise ValueError(f"krylov_op({op}, nd = {nd}): {want} fields expected, got {len(fields)}")
     ptrs = (_DP * max(len(fields), 1))(*[_dp(a) for a in fields])
