@@ -40,6 +40,20 @@ module mgx_c
        real(c_double), intent(inout) :: u(*), v(*), w(*)
        type(c_ptr), value :: rmask
      end function mgx_check_nondivergence
+     ! the set-up half of a device-resident time step: every array argument is a DEVICE pointer (include/mgx.h)
+     integer(c_int) function mgx_matrices_device(dx, dy, zeta, h, rmask, hc, theta_b, theta_s) bind(C, name='mgx_matrices_device')
+       import :: c_int, c_double, c_ptr
+       type(c_ptr), value :: dx, dy, zeta, h, rmask
+       real(c_double), value :: hc, theta_b, theta_s
+     end function mgx_matrices_device
+     integer(c_int) function mgx_update_zeta_device(zeta) bind(C, name='mgx_update_zeta_device')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: zeta
+     end function mgx_update_zeta_device
+     integer(c_int) function mgx_check_nondivergence_device(u, v, w, rmask) bind(C, name='mgx_check_nondivergence_device')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: u, v, w, rmask
+     end function mgx_check_nondivergence_device
      subroutine mgx_clean() bind(C, name='mgx_clean')
      end subroutine mgx_clean
      integer(c_int) function mgx_get_field(lev, field, host) bind(C, name='mgx_get_field')

@@ -75,6 +75,26 @@ contains
     call mgx_check(mgx_check_nondivergence(ua, va, wa, c_loc(rmaska)), 'nhydro_check_nondivergence')
   end subroutine nhydro_check_nondivergence
 
+  !--------------------------------------------------------------  (no counterpart in the reference, whose model lives on the host)
+  ! The set-up half of a time step for a model that keeps its state on the GPU: every argument is the DEVICE address of an array in the
+  ! layout of the host call of the same name (c_null_ptr for an absent rmask).  nhydro_update_zeta_device is the per-step call: a new
+  ! zeta under the dx, dy, h, rmask, hc, theta_b, theta_s of the last nhydro_matrices / nhydro_matrices_device (include/mgx.h).
+  subroutine nhydro_matrices_device(dx, dy, zeta, h, rmask, hc, theta_b, theta_s)
+    type(c_ptr), value, intent(in) :: dx, dy, zeta, h, rmask
+    real(kind=rp), intent(in) :: hc, theta_b, theta_s
+    call mgx_check(mgx_matrices_device(dx, dy, zeta, h, rmask, hc, theta_b, theta_s), 'nhydro_matrices_device')
+  end subroutine nhydro_matrices_device
+
+  subroutine nhydro_update_zeta_device(zeta)
+    type(c_ptr), value, intent(in) :: zeta
+    call mgx_check(mgx_update_zeta_device(zeta), 'nhydro_update_zeta_device')
+  end subroutine nhydro_update_zeta_device
+
+  subroutine nhydro_check_nondivergence_device(rmaska, ua, va, wa)
+    type(c_ptr), value, intent(in) :: rmaska, ua, va, wa
+    call mgx_check(mgx_check_nondivergence_device(ua, va, wa, rmaska), 'nhydro_check_nondivergence_device')
+  end subroutine nhydro_check_nondivergence_device
+
   !--------------------------------------------------------------  (nhydro.f90:137-141)
   subroutine nhydro_clean()
     call mgx_clean()

@@ -88,6 +88,36 @@ int mgx_check_nondivergence(double *u, double *v, double *w, const double *rmask
 /* nhydro_clean (nhydro.f90:137-141) */
 void mgx_clean(void);
 
+/* ---- the set-up half of a device-resident time step (no Fortran counterpart: the reference's model is on the host) ----
+ * mgx_matrices with DEVICE pointers: same layouts ((0:ny+1, 0:nx+1), j fastest), same refusals in the same words, the five copies
+ * device-to-device on the solver's stream.  rmask_dev may be NULL unless bmask.  The arrays are read in stream order: keep them
+ * unchanged until the call has returned (option "async" = 0) or until the next mgx_synchronize ("async" = 1). */
+int mgx_matrices_device(const double *dx_dev, const double *dy_dev, const double *zeta_dev, const double *h_dev,
+                        const double *rmask_dev, double hc, double theta_b, double theta_s);
+/* The per-step call of a model with a moving free surface: a new level-1 zeta (device pointer, layout as above) under the dx, dy, h,
+ * rmask, hc, theta_b, theta_s of the last mgx_matrices / mgx_matrices_device.  Refused before the first of those.
+ * Rebuilt, by the kernels of mgx_matrices in their order, hence bit for bit what mgx_matrices(dx, dy, zeta_new, h, rmask, ...) leaves:
+ * zeta, zr, zw, cw and cA of every level (both layouts), the pivots, the slopes, the red-black extras (g, rho, the decay figures:
+ * mgx_rbseq_window_info / _rows), the 2-D zeta of the matrix-free passes and the model-space copies of zw, dzw, cw, zxdy, zydx.
+ * Kept, and not recomputed: dx, dy, h of every level and their halos, the coarse masks, the sigma tables, the 2-D metric factors, the
+ * model-space copies of dx, dy, rmask.  Invalidated as mgx_matrices does: the direct coarsest operator ("coarsest_direct": rebuilt at
+ * the next cycle) and the fp32 copies of "cycle_precision" / "krylov_precision" = 32 (converted again at the next such solve).
+ * A matrix installed with mgx_set_field(lev, MGX_CA, ...) is OVERWRITTEN, as mgx_matrices would overwrite it; dx, dy, h, rmask changed
+ * through mgx_set_field on level 1 are taken as they are, on coarser levels they are kept as set.
+ * On a hierarchy whose levels are all closed and un-gathered (a single rank) zeta reaches every level, halos included, in one launch
+ * (mgx_setup.hip: k_zeta_chain; a second one from 7 levels on); levels with neighbours or a gather take one coarsening, one all-gather
+ * where the level gathers and one halo fill each -- the call is then collective.
+ * Waiting: with option "async" = 0 both calls return when the device has finished, like mgx_matrices.  With "async" = 1 they only enqueue,
+ * and errors surface at mgx_synchronize -- unless relax_method = 'RB' with cmatrix = 'real' runs in the sequential order ("rb_seq" = 1), whose
+ * windowed walk is sized on the host from rho and the decay figures of the new coefficients: then the read-back and its wait stay.  (Red-black
+ * with "rb_seq" = 0 under "async" = 1 skips the read-back: mgx_rbseq_window_info then reports no window until the next waiting set-up.)
+ * Read-only options: "zeta_refreshes" (default 0; calls of mgx_update_zeta_device served since mgx_init) and "zeta_chain_launches"
+ * (default 0; how many of them took the one-launch path for the 2-D part). */
+int mgx_update_zeta_device(const double *zeta_dev);
+/* nhydro_check_nondivergence with the model state on the GPU (the pattern of mgx_solve_device): u, v, w and rmask (may be NULL) are DEVICE
+ * pointers and are only read; the divergence is left in grid(1)%b.  Waits for the device. */
+int mgx_check_nondivergence_device(double *u_dev, double *v_dev, double *w_dev, const double *rmask_dev);
+
 /* mg_solvers.f90:17-101 solve_p(tol,maxite).  *nite = iterations done, *res = last ||r||/||b||,
  * hist (may be NULL, else >= maxite+1 doubles) = normalised residual after each iteration, hist[0] = initial. */
 int mgx_solve_p(double tol, int maxite, int *nite, double *res, double *hist);

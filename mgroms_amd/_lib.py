@@ -33,6 +33,9 @@ _SIGS = {
     "mgx_solve": (C.c_int, [_DP, _DP, _DP, _DP]),
     "mgx_solve_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgx_check_nondivergence": (C.c_int, [_DP, _DP, _DP, _DP]),
+    "mgx_matrices_device": (C.c_int, [C.c_void_p] * 5 + [C.c_double] * 3),
+    "mgx_update_zeta_device": (C.c_int, [C.c_void_p]),
+    "mgx_check_nondivergence_device": (C.c_int, [C.c_void_p] * 4),
     "mgx_clean": (None, []),
     "mgx_solve_p": (C.c_int, [C.c_double, C.c_int, C.POINTER(C.c_int), _DP, _DP]),
     "mgx_fcycle": (C.c_int, []),

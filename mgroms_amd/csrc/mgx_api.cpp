@@ -88,6 +88,8 @@ const Opt OPTIONS[] = {
   {"krylov_restarts", nullptr, CNT(kr_restarts), nullptr, ENV_NONE, RO, false},
   {"krylov_mixed_iterations", nullptr, CNT(n_kr_mixed), nullptr, ENV_NONE, RO, false},
   {"p2p_failed", nullptr, CNT(p2p_failed), nullptr, ENV_NONE, RO, false},
+  {"zeta_refreshes", nullptr, CNT(n_zeta_refresh), nullptr, ENV_NONE, RO, false},
+  {"zeta_chain_launches", nullptr, CNT(n_zeta_chain), nullptr, ENV_NONE, RO, false},
 };
 #undef PAR
 #undef CNT
@@ -231,20 +233,44 @@ int mgx_read_namelist(const char *path, mgx_params *p) {
   return 0;
 }
 
-int mgx_matrices(const double *dx, const double *dy, const double *zeta, const double *h, const double *rmask, double hc,
-                 double theta_b, double theta_s) {
+// nhydro_matrices from host (dev = false) or device (dev = true) arrays: the level-1 geometry, then define_matrices
+static int matrices_from(const double *dx, const double *dy, const double *zeta, const double *h, const double *rmask, double hc,
+                         double theta_b, double theta_s, bool dev) {
   NEED_INIT();
   if (S.par.bmask && !rmask) return fail("bmask=.true. needs rmask in mgx_matrices (nhydro.f90:52-55)");
   if (S.verbose && S.rank == 0) printf("  nhydro_matrices:\n");
   S.hlim = hc; S.theta_b = theta_b; S.theta_s = theta_s;
   Level &L = S.lev[0];
   const size_t n2 = (size_t)(L.ny + 2) * (L.nx + 2) * sizeof(double);
-  HIPCHK(hipMemcpyAsync(L.g.dx, dx, n2, hipMemcpyHostToDevice, S.stream));
-  HIPCHK(hipMemcpyAsync(L.g.dy, dy, n2, hipMemcpyHostToDevice, S.stream));
-  HIPCHK(hipMemcpyAsync(L.g.zeta, zeta, n2, hipMemcpyHostToDevice, S.stream));
-  HIPCHK(hipMemcpyAsync(L.g.h, h, n2, hipMemcpyHostToDevice, S.stream));
-  if (S.par.bmask) HIPCHK(hipMemcpyAsync(L.g.rmask, rmask, n2, hipMemcpyHostToDevice, S.stream));  // grid(1)%rmask = rmask
-  return define_matrices();
+  const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  HIPCHK(hipMemcpyAsync(L.g.dx, dx, n2, kind, S.stream));
+  HIPCHK(hipMemcpyAsync(L.g.dy, dy, n2, kind, S.stream));
+  HIPCHK(hipMemcpyAsync(L.g.zeta, zeta, n2, kind, S.stream));
+  HIPCHK(hipMemcpyAsync(L.g.h, h, n2, kind, S.stream));
+  if (S.par.bmask) HIPCHK(hipMemcpyAsync(L.g.rmask, rmask, n2, kind, S.stream));  // grid(1)%rmask = rmask
+  return define_matrices(DM_ALL, dev);
+}
+
+int mgx_matrices(const double *dx, const double *dy, const double *zeta, const double *h, const double *rmask, double hc,
+                 double theta_b, double theta_s) {
+  return matrices_from(dx, dy, zeta, h, rmask, hc, theta_b, theta_s, false);
+}
+
+int mgx_matrices_device(const double *dx_dev, const double *dy_dev, const double *zeta_dev, const double *h_dev, const double *rmask_dev,
+                        double hc, double theta_b, double theta_s) {
+  return matrices_from(dx_dev, dy_dev, zeta_dev, h_dev, rmask_dev, hc, theta_b, theta_s, true);
+}
+
+// the per-step call of a resident model with a moving free surface: a new level-1 zeta, everything that depends on it rebuilt
+int mgx_update_zeta_device(const double *zeta_dev) {
+  NEED_INIT();
+  if (!S.have_geometry) return fail("mgx_update_zeta_device: no dx, dy, h to keep: call mgx_matrices or mgx_matrices_device first");
+  if (!zeta_dev) return fail("mgx_update_zeta_device: zeta_dev is NULL");
+  Level &L = S.lev[0];
+  HIPCHK(hipMemcpyAsync(L.g.zeta, zeta_dev, (size_t)(L.ny + 2) * (L.nx + 2) * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
+  CHK(define_matrices(DM_ZETA, true));
+  S.n_zeta_refresh++;
+  return 0;
 }
 
 int mgx_compute_rhs(const double *u, const double *v, const double *w, const double *rmask) {
@@ -294,6 +320,20 @@ int mgx_solve_device(double *u_dev, double *v_dev, double *w_dev, const double *
 int mgx_check_nondivergence(double *u, double *v, double *w, const double *rmask) {
   if (S.verbose && S.rank == 0) printf(" - check non-divergence:\n");
   return mgx_compute_rhs(u, v, w, rmask);
+}
+
+// nhydro_check_nondivergence on the model's own device arrays (the pattern of mgx_solve_device): the divergence into grid(1)%b
+int mgx_check_nondivergence_device(double *u_dev, double *v_dev, double *w_dev, const double *rmask_dev) {
+  NEED_INIT();
+  if (!S.have_matrix) return fail("mgx_matrices must be called before mgx_check_nondivergence_device");
+  if (S.verbose && S.rank == 0) printf(" - check non-divergence:\n");
+  CHK(set_call_mask(rmask_dev, true));
+  double *su = S.d_u, *sv = S.d_v, *sw = S.d_w;
+  S.d_u = u_dev; S.d_v = v_dev; S.d_w = w_dev;
+  int rc = compute_rhs_dev();
+  if (!rc) rc = sync_stream();
+  S.d_u = su; S.d_v = sv; S.d_w = sw;
+  return rc;
 }
 
 int mgx_solve_p(double tol, int maxite, int *nite, double *res, double *hist) {

@@ -86,10 +86,11 @@ int gather2d(Level &L, double *src_tmp, double *dst) {
 }
 
 // the planes of warm-up each level's windowed red-black walk needs (mgx_rbseq.hip: k_rbseq_window), from the rho the set-up has just copied back
-void set_window_planes() {
+// (known = false: the set-up did not copy rho and the decay figures back -- every level keeps the walk over the whole level)
+void set_window_planes(bool known) {
   for (int l = 0; l < S.nlevs && l < 32; l++) {
     Level &L = S.lev[l];
-    if (!L.v.gk || !S.rho_dev) { L.rbs_rho = -1.0; L.rbs_m = 0; L.rbs_rows = L.nz; continue; }
+    if (!L.v.gk || !S.rho_dev || !known) { L.rbs_rho = -1.0; L.rbs_m = 0; L.rbs_rows = L.nz; continue; }
     L.rbs_rho = S.rho_host[l];
     L.rbs_m = mgxk_rbseq_window_planes(L.rbs_rho);
     L.rbs_rows = (L.gdec && !L.gdec_h.empty()) ? mgxk_rbseq_window_rows(L.gdec_h.data(), L.nz) : L.nz;
@@ -97,8 +98,36 @@ void set_window_planes() {
   }
 }
 
-int define_matrices() {
+// zeta of a hierarchy whose levels are all closed and un-gathered, from the interior of level 1: every coarser level and the halos of all
+// of them in one launch per mgxs_zeta_chain_depth() levels (mgx_setup.hip: k_zeta_chain).  false = not such a hierarchy, nothing was enqueued.
+static bool zeta_chain() {
+  for (int l = 0; l < S.nlevs; l++) {
+    const Level &L = S.lev[l];
+    if (L.gather || !all_physical(sides_of(L))) return false;
+    if (l > 0 && (2 * L.nx != S.lev[l - 1].nx || 2 * L.ny != S.lev[l - 1].ny)) return false;
+  }
+  const int D = mgxs_zeta_chain_depth();
+  for (int s = 0;; s += D) {
+    const int nd = std::min(D, S.nlevs - 1 - s);
+    double *a[16];
+    for (int d = 0; d <= nd; d++) a[d] = S.lev[s + d].g.zeta;
+    mgxs_zeta_chain(S.stream, a, S.lev[s].ny, S.lev[s].nx, nd); S.n_launch++;
+    if (s + nd >= S.nlevs - 1) break;
+  }
+  return true;
+}
+
+// what = DM_ALL: the level-1 dx, dy, zeta, h (and rmask) are new (mgx_matrices, mgx_matrices_device).  what = DM_ZETA: only the level-1 zeta is
+// (mgx_update_zeta_device) -- dx, dy, h of every level, their halos, the coarse masks, the sigma tables, the 2-D factors of k_zw_js and the
+// model-space copies of dx, dy, rmask are what the last DM_ALL left and stay; everything zeta reaches is rebuilt by the same kernels in the
+// same order.  may_return_early: the caller is one of the device entry points, which under option "async" only enqueue -- unless the
+// sequential-order red-black needs rho and the decay figures of the new coefficients on the host (set_window_planes).
+int define_matrices(int what, bool may_return_early) {
+  const bool all = what == DM_ALL;
+  const bool wait = !(may_return_early && S.async_ops) || (S.rho_dev && S.rb_seq);
   if (S.rho_dev) HIPCHK(hipMemsetAsync(S.rho_dev, 0, sizeof S.rho_host, S.stream));
+  const bool chained = !all && zeta_chain();
+  if (chained) S.n_zeta_chain++;
   for (int l = 0; l < S.nlevs; l++) {
     Level &L = S.lev[l];
     if (l > 0) {
@@ -108,20 +137,21 @@ int define_matrices() {
       double *own[4] = {L.g.dx, L.g.dy, L.g.zeta, L.g.h};
       const double fac[4] = {0.5, 0.5, 0.25, 0.25};
       for (int q = 0; q < 4; q++) {
+        if (!all && (q != 2 || chained)) continue;
         mgxs_coarsen2d(S.stream, src[q], L.gather ? L.tmp2[q] : own[q], F.ny, nyc, nxc, fac[q]); S.n_launch++;
         if (L.gather) CHK(gather2d(L, L.tmp2[q], own[q]));
       }
     }
-    CHK(rl_fill_halo(L, L.g.dx, 1, 1, 0));
-    CHK(rl_fill_halo(L, L.g.dy, 1, 1, 0));
-    CHK(rl_fill_halo(L, L.g.zeta, 1, 1, 0));
-    CHK(rl_fill_halo(L, L.g.h, 1, 1, 0));
+    if (all) CHK(rl_fill_halo(L, L.g.dx, 1, 1, 0));
+    if (all) CHK(rl_fill_halo(L, L.g.dy, 1, 1, 0));
+    if (!chained) CHK(rl_fill_halo(L, L.g.zeta, 1, 1, 0));
+    if (all) CHK(rl_fill_halo(L, L.g.h, 1, 1, 0));
     mgxs_zr_zw(S.stream, &L.g, S.hlim, S.theta_b, S.theta_s); S.n_launch++;
     CHK(rl_fill_halo(L, L.g.zr, L.nz, 2, 0));
     CHK(rl_fill_halo(L, L.g.zw, L.nz + 1, 2, 0));
     // (no clearing of the cA scratch: k_cA_offdiag stores every slot of every cell, zeros included)
     L.g.bmask = S.par.bmask ? 1 : 0;
-    if (l > 0) {  // boundary mask of a coarse level = 1, 0 in the physical halo when bmask (:157-161, fill_halo_2D_bmask)
+    if (l > 0 && all) {  // boundary mask of a coarse level = 1, 0 in the physical halo when bmask (:157-161, fill_halo_2D_bmask)
       rect(L.g.rmask, 0, 5, 1, 1, L.ny, 0, L.ny + 1, 0, L.nx + 1);
       if (S.par.bmask) {
         if (L.neighb[0] < 0) rect(L.g.rmask, 0, 2, 1, 1, L.ny, 0, 0, 0, L.nx + 1);
@@ -142,10 +172,13 @@ int define_matrices() {
       mgxm_ref2model(S.stream, L.g.cw, L.g.mcw, L.nz + 1, 1, L.nx, L.ny);
       mgxm_ref2model(S.stream, L.g.zxdy, L.g.mzxdy, L.nz, 1, L.nx, L.ny);
       mgxm_ref2model(S.stream, L.g.zydx, L.g.mzydx, L.nz, 1, L.nx, L.ny);
-      mgxm_ref2model_2d(S.stream, L.g.dx, L.g.mdx, L.nx, L.ny);
-      mgxm_ref2model_2d(S.stream, L.g.dy, L.g.mdy, L.nx, L.ny);
-      mgxm_ref2model_2d(S.stream, L.g.rmask, L.g.mrmask, L.nx, L.ny);
-      S.n_launch += 8;
+      S.n_launch += 5;
+      if (all) {
+        mgxm_ref2model_2d(S.stream, L.g.dx, L.g.mdx, L.nx, L.ny);
+        mgxm_ref2model_2d(S.stream, L.g.dy, L.g.mdy, L.nx, L.ny);
+        mgxm_ref2model_2d(S.stream, L.g.rmask, L.g.mrmask, L.nx, L.ny);
+        S.n_launch += 3;
+      }
     }
     if (L.nz <= 1024) { mgxk_convert8(S.stream, &L.v, L.g.cA); S.n_launch++; }  // LDS-tiled transposition, one slot per block
     else for (int s = 0; s < 8; s++) { mgxk_convert(S.stream, &L.v, L.v.cA[s], L.g.cA + (size_t)s * L.nz * (L.ny + 2) * (L.nx + 2), 1, 0, 0); S.n_launch++; }
@@ -155,7 +188,7 @@ int define_matrices() {
     if (L.v.gk && L.gdec) {
       HIPCHK(hipMemsetAsync(L.gdec, 0, (size_t)L.nz * sizeof(double), S.stream));
       mgxk_rbseq_gdecay(S.stream, &L.v, L.gdec); S.n_launch++;
-      HIPCHK(hipMemcpyAsync(L.gdec_h.data(), L.gdec, (size_t)L.nz * sizeof(double), hipMemcpyDeviceToHost, S.stream));
+      if (wait) HIPCHK(hipMemcpyAsync(L.gdec_h.data(), L.gdec, (size_t)L.nz * sizeof(double), hipMemcpyDeviceToHost, S.stream));
     }
     L.v.zy = L.zy_store; L.v.zx = L.zx_store;
     if (L.nz <= 1024) { mgxk_convert2(S.stream, &L.v, L.zy_store, L.zx_store, L.g.szy); S.n_launch++; }
@@ -163,15 +196,19 @@ int define_matrices() {
     L.v.m4 = L.f2d_store[0]; L.v.d4 = L.f2d_store[1]; L.v.m7 = L.f2d_store[2]; L.v.d7 = L.f2d_store[3];
     L.v.h2 = L.f2d_store[4]; L.v.hi2 = L.f2d_store[5]; L.v.ze2 = L.f2d_store[6]; L.v.cffw = L.tab_store[0]; L.v.csw = L.tab_store[1];
     L.v.dx2 = L.zg_store[0]; L.v.dy2 = L.zg_store[1]; L.v.cffr = L.zg_store[2]; L.v.csr = L.zg_store[3];
-    mgxs_zw_js(S.stream, &L.g, &L.v, S.hlim, S.theta_b, S.theta_s); S.n_launch += 3;
+    if (all) { mgxs_zw_js(S.stream, &L.g, &L.v, S.hlim, S.theta_b, S.theta_s); S.n_launch += 3; }
+    else { mgxs_ze2_js(S.stream, &L.g, &L.v); S.n_launch++; }  // of the 2-D factors and tables only ze2 holds zeta
     if (S.no_mf || S.par.bmask) { L.v.zy = L.v.zx = nullptr; L.v.m4 = nullptr; }  // masked coefficients are not rebuilt from the slopes
   }
-  if (S.rho_dev) HIPCHK(hipMemcpyAsync(S.rho_host, S.rho_dev, sizeof S.rho_host, hipMemcpyDeviceToHost, S.stream));
-  CHK(sync_stream());
-  set_window_planes();
+  if (wait) {
+    if (S.rho_dev) HIPCHK(hipMemcpyAsync(S.rho_host, S.rho_dev, sizeof S.rho_host, hipMemcpyDeviceToHost, S.stream));
+    CHK(sync_stream());
+  }
+  set_window_planes(wait);
   S.cd_valid = 0;
   S.coef_gen++;
   S.have_matrix = true;
+  S.have_geometry = true;
   return 0;
 }
 

@@ -66,6 +66,8 @@ struct HostTic { int lev, sub; std::chrono::steady_clock::time_point t0; };  // 
 
 struct State {
   bool inited = false, have_matrix = false;
+  bool have_geometry = false;   // define_matrices has run: level 1 holds dx, dy, h, rmask and S the hc, theta_b, theta_s a zeta refresh keeps
+  long long n_zeta_refresh = 0, n_zeta_chain = 0;   // read-only options "zeta_refreshes", "zeta_chain_launches"
   mgx_params par;
   int method = M_RB, real = 1, linear = 1;
   int nlevs = 0, npx = 1, npy = 1, nranks = 1, rank = 0, pi = 0, pj = 0;
@@ -213,8 +215,9 @@ int roundup(int a, int m);
 void make_view(LevView &v, int nx, int ny, int nz);
 int find_grid_levels(int npxg, int npyg, int nx, int ny, int nz);
 void rank_level_table(int rank, std::vector<Level> &T, int npx0, int npy0, int nsmall);
-void set_window_planes();
-int define_matrices();
+void set_window_planes(bool known = true);
+enum { DM_ALL = 0, DM_ZETA = 1 };
+int define_matrices(int what = DM_ALL, bool may_return_early = false);
 int set_call_mask(const double *rmask, bool dev);
 int compute_rhs_dev();
 int correct_uvw_dev();

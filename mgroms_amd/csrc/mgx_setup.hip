@@ -131,6 +131,71 @@ __global__ void k_halo_ref_closed(double *__restrict__ a, int nzz, int nh, int n
 #undef AI
 }
 
+// The zeta refresh of a time step (mgx_update_zeta_device) on a hierarchy whose levels are all closed and un-gathered: k_coarsen2d and
+// k_halo_ref_closed (nzz = 1, nh = 1) of EVERY level in one launch.  A workgroup owns the aligned ZC_T x ZC_T tile of the chain's first
+// level (whose interior is given) and what lies under it on the coarser ones: it loads the tile into LDS (lanes along j, the fastest index:
+// one 256-byte run per i), and halves it level by level, each cell the four-term sum of k_coarsen2d in its order with its factor -- the same
+// bits.  Every level's cells go to global memory as they are formed, and a cell on the rim of its level also goes to the halo entries
+// k_halo_ref_closed takes from it (the edge images and, from the four corner cells, the diagonal one): halo cells are copies of interior
+// cells of the same level, so no workgroup reads what another one writes.  Level sizes are even all the way down (mgx_init refuses
+// others), so a tile cut by the end of the grid keeps whole 2 x 2 groups on every level it reaches; ZC_MAXD coarser levels fit under one
+// tile, a deeper hierarchy chains a second launch from the last level of the first.  (The stride-2 LDS reads are 2-way bank conflicts on
+// a few thousand reads per workgroup: the kernel is a few microseconds of launch latency, which is what it is there to save.)
+#define ZC_T 32
+#define ZC_MAXD 5
+struct ZetaChain { double *a[ZC_MAXD + 1]; int ny, nx, nd; };   // a[0]: (0:ny+1, 0:nx+1), a[d]: (0:(ny>>d)+1, 0:(nx>>d)+1); nd = coarser levels to form
+static_assert(ZC_T == 1 << ZC_MAXD, "one tile ends in one cell");
+
+// cell (j,i), 1-based, of a closed level (0:ny+1, 0:nx+1): the interior entry when asked, and the physical halo entries that mirror it
+__device__ __forceinline__ void zc_store(double *__restrict__ a, int ny, int nx, int j, int i, double v, bool interior) {
+  const long long W = ny + 2;
+  if (interior) a[i * W + j] = v;
+  const int hj = j == 1 ? 0 : (j == ny ? ny + 1 : -1), hi = i == 1 ? 0 : (i == nx ? nx + 1 : -1);
+  if (hj >= 0) a[i * W + hj] = v;
+  if (hi >= 0) a[hi * W + j] = v;
+  if (hj >= 0 && hi >= 0) a[hi * W + hj] = v;
+}
+
+__global__ void __launch_bounds__(256) k_zeta_chain(ZetaChain C) {
+  __shared__ double lds[ZC_T * ZC_T + ZC_T * ZC_T / 2];   // the tile, then its halvings one after the other (1/4 + 1/16 + ... < 1/2)
+  const int tid = threadIdx.x;
+  const int j0 = blockIdx.x * ZC_T, i0 = blockIdx.y * ZC_T;
+  for (int q = tid; q < ZC_T * ZC_T; q += 256) {
+    const int j = j0 + (q & (ZC_T - 1)) + 1, i = i0 + q / ZC_T + 1;
+    if (j <= C.ny && i <= C.nx) {
+      const double v = C.a[0][(long long)i * (C.ny + 2) + j];
+      lds[q] = v;
+      zc_store(C.a[0], C.ny, C.nx, j, i, v, false);
+    }
+  }
+  __syncthreads();
+  const double *src = lds;
+#pragma unroll
+  for (int d = 1; d <= ZC_MAXD; d++) {
+    if (d > C.nd) break;   // uniform: the barrier below is reached by all or none
+    const int e = ZC_T >> (d - 1), ec = e >> 1, ny = C.ny >> d, nx = C.nx >> d;
+    double *dst = const_cast<double *>(src) + e * e;
+    for (int q = tid; q < ec * ec; q += 256) {
+      const int jl = q & (ec - 1), il = q >> (ZC_MAXD - d);
+      const int j = (j0 >> d) + jl + 1, i = (i0 >> d) + il + 1;
+      if (j <= ny && i <= nx) {
+        const double *s = src + (2 * il) * e + 2 * jl;
+        const double v = 0.25 * (s[0] + s[1] + s[e] + s[e + 1]);   // k_coarsen2d: (fj,fi) + (fj+1,fi) + (fj,fi+1) + (fj+1,fi+1)
+        dst[q] = v;
+        zc_store(C.a[d], ny, nx, j, i, v, true);
+      }
+    }
+    __syncthreads();
+    src = dst;
+  }
+}
+
+// the only zeta-dependent store of k_zw_js (below), for the refresh that leaves the others alone
+__global__ void k_ze2_js(GeoView G, LevView L) {
+  COLUMN_THREAD(0, G.ny + 1, 0, G.nx + 1)
+  L.ze2[(long long)i * L.RS + jpos(L, j)] = A2(G.zeta, j, i);
+}
+
 // mg_zr_zw.f90:98-170 setup_zr_zw_croco, 'new_s_coord', computed on 0:n+1 (:91).  Lanes run along k, the fastest index of zr / zw: a
 // wave writes whole k-runs (with a lane per column every store hit 64 lines: 1.3 GB written for 0.27 GB of depths, counters of round 3).
 __global__ void k_zr_zw(GeoView G, double hlim, double theta_b, double theta_s) {
@@ -420,6 +485,15 @@ void mgxs_halo_ref_closed(hipStream_t st, double *a, int nzz, int nh, int ny, in
   const long long n = (long long)nzz * (2LL * nh * (ny + 2 * nh) + 2LL * nh * nx);
   hipLaunchKernelGGL(k_halo_ref_closed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, nzz, nh, ny, nx);
 }
+int mgxs_zeta_chain_depth(void) { return ZC_MAXD; }
+// lev[0]: the level whose interior is given; lev[1..nd]: the nd <= mgxs_zeta_chain_depth() levels below it, each half the size of the one before
+void mgxs_zeta_chain(hipStream_t st, double *const *lev, int ny, int nx, int nd) {
+  ZetaChain C = {};
+  for (int d = 0; d <= nd && d <= ZC_MAXD; d++) C.a[d] = lev[d];
+  C.ny = ny; C.nx = nx; C.nd = nd < ZC_MAXD ? nd : ZC_MAXD;
+  hipLaunchKernelGGL(k_zeta_chain, dim3((ny + ZC_T - 1) / ZC_T, (nx + ZC_T - 1) / ZC_T), dim3(256), 0, st, C);
+}
+void mgxs_ze2_js(hipStream_t st, const GeoView *G, const LevView *L) { hipLaunchKernelGGL(k_ze2_js, cgrid(G->ny + 2, G->nx + 2), CBLK, 0, st, *G, *L); }
 void mgxs_zr_zw(hipStream_t st, const GeoView *G, double hlim, double theta_b, double theta_s) {
   hipLaunchKernelGGL(k_zr_zw, kgrid(G->nz + 1, G->ny + 2, G->nx + 2), dim3(256), 0, st, *G, hlim, theta_b, theta_s);
 }

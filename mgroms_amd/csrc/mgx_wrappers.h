@@ -95,6 +95,9 @@ void mgxk_split(hipStream_t st, const LevView *C, const LevView *Cs, const doubl
 void mgxs_coarsen2d(hipStream_t st, const double *src, double *dst, int nyf, int nyc, int nxc, double fac);
 void mgxs_rect(hipStream_t st, double *a, double *buf, const RectOp *R);
 void mgxs_halo_ref_closed(hipStream_t st, double *a, int nzz, int nh, int ny, int nx);
+int mgxs_zeta_chain_depth(void);
+void mgxs_zeta_chain(hipStream_t st, double *const *lev, int ny, int nx, int nd);
+void mgxs_ze2_js(hipStream_t st, const GeoView *G, const LevView *L);
 void mgxs_zr_zw(hipStream_t st, const GeoView *G, double hlim, double theta_b, double theta_s);
 void mgxs_define_matrix(hipStream_t st, const GeoView *G, int lev1, int phase);
 void mgxs_slopes_ref(hipStream_t st, const GeoView *G);

@@ -135,6 +135,49 @@ def nhydro_solve_device(u, v, w, rmask=None):
                                  None if rmask is None else C.c_void_p(rmask.data_ptr())))
 
 
+def _dev(a, shape, name):
+    """data pointer of a torch CUDA tensor after the checks of nhydro_solve_device (float64, contiguous, exact shape, on the device)"""
+    ok = hasattr(a, "is_cuda") and a.is_cuda and a.is_contiguous() and tuple(a.shape) == tuple(shape) and str(a.dtype) == "torch.float64"
+    if not ok:
+        raise ValueError(f"{name}: need a contiguous float64 CUDA tensor of shape {tuple(shape)}")
+    return C.c_void_p(a.data_ptr())
+
+
+def _wait_for_caller():
+    import torch
+    torch.cuda.current_stream().synchronize()
+
+
+def nhydro_matrices_device(dx, dy, zeta, h, rmask=None, hc=0.0, theta_b=0.0, theta_s=0.0):
+    """nhydro_matrices on torch CUDA tensors of shape (nx+2, ny+2): no host round trip (include/mgx.h: mgx_matrices_device)."""
+    nx, ny, _ = _state.dims
+    sh = (nx + 2, ny + 2)
+    ptrs = [_dev(a, sh, n) for a, n in ((dx, "dx"), (dy, "dy"), (zeta, "zeta"), (h, "h"))]
+    prm = None if rmask is None else _dev(rmask, sh, "rmask")
+    _wait_for_caller()
+    check(lib().mgx_matrices_device(*ptrs, prm, hc, theta_b, theta_s))
+
+
+def nhydro_update_zeta_device(zeta):
+    """the per-step call of a resident model: a new zeta (torch CUDA tensor, (nx+2, ny+2)) under the dx, dy, h, rmask of the last
+    nhydro_matrices / nhydro_matrices_device; everything that depends on zeta is rebuilt (include/mgx.h: mgx_update_zeta_device)."""
+    if _state.dims is None:
+        check(lib().mgx_update_zeta_device(None))   # the library's refusal (no mgx_init), in its words
+    nx, ny, _ = _state.dims
+    p = _dev(zeta, (nx + 2, ny + 2), "zeta")
+    _wait_for_caller()
+    check(lib().mgx_update_zeta_device(p))
+
+
+def nhydro_check_nondivergence_device(u, v, w, rmask=None):
+    """nhydro_check_nondivergence on torch CUDA tensors (shapes as nhydro_solve_device): the divergence is left in grid(1).b"""
+    nx, ny, nz = _state.dims
+    ptrs = [_dev(a, sh, n) for a, sh, n in ((u, (nz, ny + 2, nx + 1), "u"), (v, (nz, ny + 1, nx + 2), "v"), (w, (nz + 1, ny + 2, nx + 2), "w"))]
+    prm = None if rmask is None else _dev(rmask, (nx + 2, ny + 2), "rmask")
+    _wait_for_caller()
+    check(lib().mgx_check_nondivergence_device(*ptrs, prm))
+
+
 def nhydro_check_nondivergence(u, v, w, rmask=None):
     _uvw(u, v, w)
     rm, prm = _mask(rmask)
