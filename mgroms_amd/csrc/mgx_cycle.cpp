@@ -44,136 +44,162 @@ void tt_collect() {
 }
 
 // ---- operators ------------------------------------------------------------------------------------
+// relax(): one file-local function per smoother mode; what a colour pass reports is PASS_* of mgx_wrappers.h
+namespace {
+
+// exact lexicographic order by hyperplanes; halo fill once per sweep (mg_relax.f90:131-141)
+int relax_gs(Level &L, int lev, int nsweeps) {
+  for (int it = 1; it <= nsweeps; it++) {
+    if (!mgxk_relax_gs_sweep(S.stream, &L.v, S.real)) return fail("relax_method='GS': the sweep of level %d could not be launched", lev);
+    S.n_launch += L.ny + 2 * L.nx - 2;
+    CHK(fill_halo_js(L, L.v.p));
+  }
+  return 0;
+}
+
+// The reference's red-black loop is sequential (mg_relax.f90:170-186): with cmatrix='real' a column of plane i reads the
+// same-colour k=1 diagonals (j+-1,i-1) already updated and (j+-1,i+1) not yet (:271-276).  Columns of one colour inside a
+// plane are independent, so one launch per plane, in order, reproduces the loop bit for bit -- on one rank and, with the
+// halo filled after each colour as in the reference, its decomposition-dependent result on several.
+int relax_rb_exact(Level &L, int nsweeps, Sides ph) {
+  for (int it = 1; it <= nsweeps; it++)
+    for (int rb = 1; rb <= 2; rb++) {
+      int pass = 0;
+      for (int i = 1; i <= L.nx; i++) { pass = mgxk_relax_colour(S.stream, &L.v, i, 1, 1, -1, rb, 1, 0, ph); S.n_launch++; }
+      if (pass & PASS_TALL_STORED) S.n_tall_stored++;
+      CHK(fill_halo_js(L, L.v.p, pass & PASS_MIRRORS));
+    }
+  return 0;
+}
+
+// Sequential-order red-black, after the parallel pass of colour rb (`pass`: what it reported) has left y in p: the walk over the planes, then
+// p += g s with the mirrors (mgx_rbseq.hip), by the first of window, walk-apply, fused scan, scan + apply that serves the level.
+// *mirrors (in: the pass stored them) tells on return whether the physical images of every row are in place.
+int rbseq_correct(Level &L, int rb, int pass, bool closed, int *mirrors) {
+  const int have_d0 = (pass & PASS_D0) ? 1 : 0;
+  const Sides ph = sides_of(L);
+  // the windowed walk where the level's contraction bound allows it (k_rbseq_window): one launch, no hand-off, no walk over the level
+  if (S.rbseq_window && L.rbs_m > 0) {
+    if (!have_d0) { mgxk_rbseq_d0(S.stream, &L.v, rb); S.n_launch++; }   // (the nz = 128 colour pass does not leave it)
+  }
+  const int kcut = S.rbseq_rowcut ? L.rbs_rows : L.nz;
+  if (S.rbseq_window && L.rbs_m > 0 && mgxk_rbseq_window(S.stream, &L.v, rb, ph, closed ? 1 : 0, L.rbs_m, kcut)) {
+    // the window stores the physical images of the rows it corrects (k < kcut) only: the rows below the cut keep those of the
+    // colour pass, which the generic kernel (no register instance for this nz / matrix) does not store
+    S.n_launch++; S.n_window++; *mirrors = (pass & PASS_MIRRORS) || kcut >= L.nz;
+    return 0;
+  }
+  // small levels whose pass left d0 in u1: walk and correction in one launch, every workgroup walking for itself (k_rbseq_walk_apply)
+  if (have_d0 && S.rbseq_fuse && mgxk_rbseq_walk_apply(S.stream, &L.v, rb, ph, closed ? 1 : 0)) {
+    S.n_launch++; *mirrors = 1;
+    return 0;
+  }
+  // (where an instance exists the correction runs inside the walk's launch, chasing it: option "rbseq_fuse")
+  const int ran = S.rbseq_fuse ? mgxk_rbseq_scan_apply(S.stream, &L.v, rb, ph, closed ? 1 : 0, have_d0, L.rbs_flag, ++L.rbs_seq, S.kerr, S.rbseq_test_stall, (long long)S.rbseq_fuse_min) : mgxk_rbseq_scan(S.stream, &L.v, rb, have_d0);
+  if (ran == 2) S.rbseq_test_stall = 0;
+  // a level wider than the walk takes (ny > 2048) would have to run plane by plane: refuse loudly rather than fall back to another iteration
+  if (!ran) return fail("rb_seq: level %d (ny = %d) has no scan instance; set option rb_exact or rb_seq = 0", (int)(&L - S.lev.data()) + 1, L.ny);
+  if (ran == 1) { mgxk_rbseq_apply(S.stream, &L.v, rb, ph, closed ? 1 : 0); S.n_launch++; }
+  S.n_launch += 2 - have_d0;
+  *mirrors = 1;  // the correction stores the physical images of every column it updates
+  return 0;
+}
+
+// The parallel red-black pass, one colour at a time, and behind it (seq) the correction to the reference's sequential order.
+int relax_rb(Level &L, int nsweeps, Sides ph, bool seq) {
+  const bool closed = all_physical(ph);
+  double *const p1a = L.v.p1;
+  // cmatrix='real': the k=1 diagonal neighbours have the column's own colour and must be read as they were before the
+  // pass (snapshot).  On a closed level the register kernels write the next sweep's snapshot themselves (two buffers
+  // swapped per sweep: a pass reads only entries of its own colour, which the other colour's pass never touches), so
+  // one snapshot launch per relax call suffices; with neighbours the halo part changes after every exchange.
+  const bool chain = S.rb_chain && S.real && closed && mgxk_has_reg_kernel(&L.v) && !seq;
+  for (int it = 1; it <= nsweeps; it++) {
+    if (chain) {
+      if (it == 1) { mgxk_snapshot_k1(S.stream, &L.v); S.n_launch++; }
+      L.v.p1w = (L.v.p1 == p1a) ? L.p1b : p1a;
+    }
+    for (int rb = 1; rb <= 2; rb++) {
+      // seq on a closed level: the correction keeps the snapshot current (its colour's new bottom values and their physical images), so one
+      // snapshot launch per relax call; with neighbours the halo part changes with every exchange
+      if (S.real && !chain && !(seq && closed && !(it == 1 && rb == 1))) { mgxk_snapshot_k1(S.stream, &L.v); S.n_launch++; }
+      // (seq, wide half-rows: the pass also leaves the walk's d0 = y(k=1) - snapshot in u1 where its kernel can -- one launch less)
+      L.v.d0w = (seq && S.rbseq_d0_in_pass && (mgxk_rbseq_wants_d0(&L.v) || (S.rbseq_window && L.rbs_m > 0))) ? L.v.u1 : nullptr;
+      const int pass = mgxk_relax_colour(S.stream, &L.v, 1, 1, L.nx, -1, rb, S.real, S.real, ph); S.n_launch++;
+      L.v.d0w = nullptr;
+      if (pass & PASS_TALL_STORED) S.n_tall_stored++;
+      int mirrors = (pass & PASS_MIRRORS) ? 1 : 0;
+      if (seq) CHK(rbseq_correct(L, rb, pass, closed, &mirrors));
+      CHK(fill_halo_js(L, L.v.p, mirrors));
+    }
+    if (chain) { L.v.p1 = L.v.p1w; L.v.p1w = nullptr; if (it == nsweeps) L.v.p1 = p1a; }
+  }
+  return 0;
+}
+
+// One colour of a four-colour sweep on a level with neighbours, halos by the pushes: the boundary part of the colour (the waves that hold a
+// column next to a neighbour's halo -- what the exchange sends, and all that reads what the last exchange delivered) and the exchange behind
+// it go to a second stream; the interior part runs beside them on the solver's stream and waits only for the previous colour's boundary part
+// (mg_relax.f90:181,224 exchange after every colour; SURVEY 7 "split boundary columns from interior, exchange while the interior runs").
+int relax_fc_overlapped(Level &L, int fc1, int fc2, Sides ph) {
+  Sides ps = ph;
+  HIPCHK(hipEventRecord(S.ev_a, S.stream));                 // the interior of the previous colour (and whatever came before)
+  HIPCHK(hipStreamWaitEvent(S.stream2, S.ev_a, 0));
+  ps.part = 1;
+  const int pass = mgxk_relax_colour(S.stream2, &L.v, 1 + (fc1 - 1) % 2, 2, L.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0, ps);
+  HIPCHK(hipEventRecord(S.ev_s, S.stream2));
+  { hipStream_t keep = S.stream; S.stream = S.stream2; const int rc = fill_halo_js(L, L.v.p, pass & PASS_MIRRORS); S.stream = keep; if (rc) return rc; }
+  ps.part = 2;
+  mgxk_relax_colour(S.stream, &L.v, 1 + (fc1 - 1) % 2, 2, L.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0, ps);
+  HIPCHK(hipStreamWaitEvent(S.stream, S.ev_s, 0));          // what follows on the solver's stream reads this colour's boundary part -- not its exchange
+  S.n_launch += 2; S.n_overlap++;
+  if (pass & PASS_TALL_STORED) S.n_tall_stored++;
+  return 0;
+}
+
+// four colours (mg_relax.f90:193-234), one launch per colour -- or per colour pair, or two beside the exchange
+int relax_fc(Level &L, int nsweeps, Sides ph) {
+  const bool closed = all_physical(ph);
+  const bool ov = S.overlap && S.p2p_on && S.stream2 && !closed && mgxk_has_reg_kernel(&L.v);
+  for (int it = 1; it <= nsweeps; it++)
+    for (int fc1 = 1; fc1 <= 2; fc1++) {
+      // closed mid levels: the two colours of a plane set in one launch (mgx_relax_ks.hip)
+      if (closed && mgxk_relax_ks_pair(S.stream, &L.v, fc1, L.nx / 2, S.real, ph)) { S.n_launch++; continue; }
+      for (int fc2 = 1; fc2 <= 2; fc2++) {
+        if (ov) { CHK(relax_fc_overlapped(L, fc1, fc2, ph)); continue; }
+        const int pass = mgxk_relax_colour(S.stream, &L.v, 1 + (fc1 - 1) % 2, 2, L.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0, ph); S.n_launch++;
+        if (pass & PASS_TALL_STORED) S.n_tall_stored++;
+        CHK(fill_halo_js(L, L.v.p, pass & PASS_MIRRORS));
+      }
+    }
+  if (ov && nsweeps >= 1) {  // the call ends: the solver's stream continues behind the last exchange
+    HIPCHK(hipEventRecord(S.ev_x, S.stream2));
+    HIPCHK(hipStreamWaitEvent(S.stream, S.ev_x, 0));
+  }
+  return 0;
+}
+
+}  // namespace
+
 // mg_relax.f90:16-47 relax ; :151-190 RB ; :193-234 FC
 int relax(int lev, int nsweeps) {
   Level &L = S.lev[lev - 1];
   TicScope ts(lev, S.method == M_RB ? "relax_3D_8_RB" : (S.method == M_FC ? "relax_3D_8_FC" : "relax_3D_8_GS"));  // mg_relax.f90:128,167,209
   if (S.tictoc && S.tt_done.size() > 4096) tt_collect();
-  if (S.method == M_GS) {  // exact lexicographic order by hyperplanes; halo fill once per sweep (mg_relax.f90:131-141)
-    for (int it = 1; it <= nsweeps; it++) {
-      if (!mgxk_relax_gs_sweep(S.stream, &L.v, S.real)) return fail("relax_method='GS': the sweep of level %d could not be launched", lev);
-      S.n_launch += L.ny + 2 * L.nx - 2;
-      CHK(fill_halo_js(L, L.v.p));
-    }
-    return 0;
-  }
+  if (S.method == M_GS) return relax_gs(L, lev, nsweeps);
   const Sides ph = sides_of(L);
   const int rbm = rb_mode(L), exact = rbm == RB_EXACT;
   // sequential-order red-black (mgx_rbseq.hip); the one-workgroup kernels of the small levels run the reference's plane loop itself
   const int seq = rbm == RB_SEQ;
   if (S.use_small && nsweeps > 0 && mgxk_relax_small(S.stream, &L.v, nsweeps, S.method, S.real, ph, exact ? 1 : (seq ? 2 : 0))) { S.n_launch++; return 0; }
-  const bool closed = all_physical(ph);
   // closed mid levels, four colours: the whole call in one persistent launch, one workgroup per plane (mgx_relax_ks.hip: k_relax_ksp)
-  if (S.method == M_FC && closed && S.use_ksp && !S.ksp_down && live_instances() == 1 && mgxk_relax_ks_persist(S.stream, &L.v, nsweeps, S.real, ph, L.ksp_done, L.ksp_seq, S.kerr, S.ksp_test_stall)) {
+  if (S.method == M_FC && all_physical(ph) && S.use_ksp && !S.ksp_down && live_instances() == 1 && mgxk_relax_ks_persist(S.stream, &L.v, nsweeps, S.real, ph, L.ksp_done, L.ksp_seq, S.kerr, S.ksp_test_stall)) {
     S.ksp_test_stall = 0;
     L.ksp_seq += (unsigned int)nsweeps; S.n_launch++;
     return 0;
   }
-  double *const p1a = L.v.p1;
-  for (int it = 1; it <= nsweeps; it++) {
-    if (exact) {
-      // The reference's red-black loop is sequential (mg_relax.f90:170-186): with cmatrix='real' a column of plane i reads the
-      // same-colour k=1 diagonals (j+-1,i-1) already updated and (j+-1,i+1) not yet (:271-276).  Columns of one colour inside a
-      // plane are independent, so one launch per plane, in order, reproduces the loop bit for bit -- on one rank and, with the
-      // halo filled after each colour as in the reference, its decomposition-dependent result on several.
-      for (int rb = 1; rb <= 2; rb++) {
-        int fused = 0;
-        for (int i = 1; i <= L.nx; i++) { fused = mgxk_relax_colour(S.stream, &L.v, i, 1, 1, -1, rb, 1, 0, ph); S.n_launch++; }
-        if (fused & 4) S.n_tall_stored++;
-        CHK(fill_halo_js(L, L.v.p, fused));
-      }
-      continue;
-    }
-    if (S.method == M_RB) {
-      // cmatrix='real': the k=1 diagonal neighbours have the column's own colour and must be read as they were before the
-      // pass (snapshot).  On a closed level the register kernels write the next sweep's snapshot themselves (two buffers
-      // swapped per sweep: a pass reads only entries of its own colour, which the other colour's pass never touches), so
-      // one snapshot launch per relax call suffices; with neighbours the halo part changes after every exchange.
-      const bool chain = S.rb_chain && S.real && closed && mgxk_has_reg_kernel(&L.v) && !seq;
-      if (chain) {
-        if (it == 1) { mgxk_snapshot_k1(S.stream, &L.v); S.n_launch++; }
-        L.v.p1w = (L.v.p1 == p1a) ? L.p1b : p1a;
-      }
-      for (int rb = 1; rb <= 2; rb++) {
-        // seq on a closed level: the correction keeps the snapshot current (its colour's new bottom values and their physical images), so one
-        // snapshot launch per relax call; with neighbours the halo part changes with every exchange
-        if (S.real && !chain && !(seq && closed && !(it == 1 && rb == 1))) { mgxk_snapshot_k1(S.stream, &L.v); S.n_launch++; }
-        // (seq, wide half-rows: the pass also leaves the walk's d0 = y(k=1) - snapshot in u1 where its kernel can -- one launch less)
-        L.v.d0w = (seq && S.rbseq_d0_in_pass && (mgxk_rbseq_wants_d0(&L.v) || (S.rbseq_window && L.rbs_m > 0))) ? L.v.u1 : nullptr;
-        const int pass = mgxk_relax_colour(S.stream, &L.v, 1, 1, L.nx, -1, rb, S.real, S.real, ph); S.n_launch++;
-        L.v.d0w = nullptr;
-        if (pass & 4) S.n_tall_stored++;
-        int fused = pass & 1;
-        const int have_d0 = (pass & 2) ? 1 : 0;
-        if (seq) {
-          // y is in p; the walk over the planes, then p += g s with the mirrors (mgx_rbseq.hip).  A level wider than the walk takes
-          // (ny > 2048) would have to run plane by plane: refuse loudly rather than fall back to another iteration
-          // small levels whose pass left d0 in u1: walk and correction in one launch, every workgroup walking for itself (k_rbseq_walk_apply)
-          // the windowed walk where the level's contraction bound allows it (k_rbseq_window): one launch, no hand-off, no walk over the level
-          if (S.rbseq_window && L.rbs_m > 0) {
-            if (!have_d0) { mgxk_rbseq_d0(S.stream, &L.v, rb); S.n_launch++; }   // (the nz = 128 colour pass does not leave it)
-          }
-          const int kcut = S.rbseq_rowcut ? L.rbs_rows : L.nz;
-          if (S.rbseq_window && L.rbs_m > 0 && mgxk_rbseq_window(S.stream, &L.v, rb, ph, closed ? 1 : 0, L.rbs_m, kcut)) {
-            // the window stores the physical images of the rows it corrects (k < kcut) only: the rows below the cut keep those of the
-            // colour pass, which the generic kernel (no register instance for this nz / matrix) does not store
-            S.n_launch++; S.n_window++; fused = (pass & 1) || kcut >= L.nz;
-            CHK(fill_halo_js(L, L.v.p, fused));
-            continue;
-          }
-          if (have_d0 && S.rbseq_fuse && mgxk_rbseq_walk_apply(S.stream, &L.v, rb, ph, closed ? 1 : 0)) {
-            S.n_launch++; fused = 1;
-            CHK(fill_halo_js(L, L.v.p, fused));
-            continue;
-          }
-          // (where an instance exists the correction runs inside the walk's launch, chasing it: option "rbseq_fuse")
-          const int ran = S.rbseq_fuse ? mgxk_rbseq_scan_apply(S.stream, &L.v, rb, ph, closed ? 1 : 0, have_d0, L.rbs_flag, ++L.rbs_seq, S.kerr, S.rbseq_test_stall, (long long)S.rbseq_fuse_min) : mgxk_rbseq_scan(S.stream, &L.v, rb, have_d0);
-          if (ran == 2) S.rbseq_test_stall = 0;
-          if (!ran) return fail("rb_seq: level %d (ny = %d) has no scan instance; set option rb_exact or rb_seq = 0", lev, L.ny);
-          if (ran == 1) { mgxk_rbseq_apply(S.stream, &L.v, rb, ph, closed ? 1 : 0); S.n_launch++; }
-          S.n_launch += 2 - have_d0;
-          fused = 1;  // the correction stores the physical images of every column it updates
-        }
-        CHK(fill_halo_js(L, L.v.p, fused));
-      }
-      if (chain) { L.v.p1 = L.v.p1w; L.v.p1w = nullptr; if (it == nsweeps) L.v.p1 = p1a; }
-    } else {
-      // A level with neighbours, halos by the pushes: the boundary part of a colour (the waves that hold a column next to a neighbour's
-      // halo -- what the exchange sends, and all that reads what the last exchange delivered) and the exchange behind it go to a second
-      // stream; the interior part runs beside them on the solver's stream and waits only for the previous colour's boundary part
-      // (mg_relax.f90:181,224 exchange after every colour; SURVEY 7 "split boundary columns from interior, exchange while the interior runs").
-      const bool ov = S.overlap && S.p2p_on && S.stream2 && !closed && mgxk_has_reg_kernel(&L.v);
-      for (int fc1 = 1; fc1 <= 2; fc1++) {
-        // closed mid levels: the two colours of a plane set in one launch (mgx_relax_ks.hip)
-        if (closed && mgxk_relax_ks_pair(S.stream, &L.v, fc1, L.nx / 2, S.real, ph)) { S.n_launch++; continue; }
-        for (int fc2 = 1; fc2 <= 2; fc2++) {
-          if (ov) {
-            Sides ps = ph;
-            HIPCHK(hipEventRecord(S.ev_a, S.stream));                 // the interior of the previous colour (and whatever came before)
-            HIPCHK(hipStreamWaitEvent(S.stream2, S.ev_a, 0));
-            ps.part = 1;
-            const int fused = mgxk_relax_colour(S.stream2, &L.v, 1 + (fc1 - 1) % 2, 2, L.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0, ps);
-            HIPCHK(hipEventRecord(S.ev_s, S.stream2));
-            { hipStream_t keep = S.stream; S.stream = S.stream2; const int rc = fill_halo_js(L, L.v.p, fused); S.stream = keep; if (rc) return rc; }
-            ps.part = 2;
-            mgxk_relax_colour(S.stream, &L.v, 1 + (fc1 - 1) % 2, 2, L.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0, ps);
-            HIPCHK(hipStreamWaitEvent(S.stream, S.ev_s, 0));          // what follows on the solver's stream reads this colour's boundary part -- not its exchange
-            S.n_launch += 2; S.n_overlap++;
-            if (fused & 4) S.n_tall_stored++;
-            continue;
-          }
-          const int fused = mgxk_relax_colour(S.stream, &L.v, 1 + (fc1 - 1) % 2, 2, L.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0, ph); S.n_launch++;
-          if (fused & 4) S.n_tall_stored++;
-          CHK(fill_halo_js(L, L.v.p, fused));
-        }
-      }
-      if (ov && it == nsweeps) {  // the call ends: the solver's stream continues behind the last exchange
-        HIPCHK(hipEventRecord(S.ev_x, S.stream2));
-        HIPCHK(hipStreamWaitEvent(S.stream, S.ev_x, 0));
-      }
-    }
-  }
-  return 0;
+  if (exact) return relax_rb_exact(L, nsweeps, ph);
+  return S.method == M_RB ? relax_rb(L, nsweeps, ph, seq) : relax_fc(L, nsweeps, ph);
 }
 
 // mg_relax.f90:337-383 compute_residual.  res == nullptr: the caller discards the norm (mg_solvers.f90:140),

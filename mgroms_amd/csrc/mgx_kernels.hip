@@ -6,8 +6,7 @@
 //
 // Thread mapping everywhere: one lane = one (j,i) column, lanes run along the unit-stride half-row of
 // the JS layout (mgx_internal.h), so every global access of a wave is one contiguous 512-byte run.
-#include <cstdlib>
-
+#include "mgx_switches.h"
 #include "mgx_operator.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -179,75 +178,41 @@ __global__ __launch_bounds__(256) void k_fine2coarse(LevView F, LevView C, doubl
 // ------------------------------------------------------------------------------------------------
 // prolongation + correction: fine r = interp(coarse p); fine p += fine r (interior).
 // mg_intergrids.f90:366-450 (tri-linear, top level x 1/2), :336-363 (nearest), :226 (p = p + r).
-// One lane = one coarse column = 2x2 fine columns.  `src` is the coarse p (or the split block).
+// `src` is the coarse p (or the split block).  k_coarse2fine_nearest: one lane = one coarse cell = 2x2x2 fine cells; the tri-linear default is
+// k_coarse2fine_run below.
 // WR = false: the interpolated correction is added to p without being stored in the fine r.  Inside a cycle nothing reads that r
 // before the next compute_residual rewrites it (mg_solvers.f90:129-151), and at level 1 it is a third of this kernel's traffic.
 // ------------------------------------------------------------------------------------------------
-template <bool LINEAR, bool WR>
-__global__ __launch_bounds__(256) void k_coarse2fine(LevView F, LevView C, const double *__restrict__ xc, Sides ph, int stream) {
+template <bool WR>
+__global__ __launch_bounds__(256) void k_coarse2fine_nearest(LevView F, LevView C, const double *__restrict__ xc, Sides ph, int stream) {
   const int j2 = 1 + blockIdx.x * WAVE + threadIdx.x;
   const int k2 = 1 + blockIdx.y * blockDim.y + threadIdx.y;
   const int i2 = 1 + blockIdx.z;
   if (j2 > C.ny || k2 > C.nz) return;
   const int i = 2 * i2 - 1;
   const int po = F.HO + (j2 - 1), pe = F.EO + j2;  // fine j (odd) and j+1 (even)
-  const int c0 = jpos(C, j2), cm = jpos(C, j2 - 1), cp = jpos(C, j2 + 1);
-  const long long q0 = (long long)i2 * C.plane, qm = q0 - C.plane, qp = q0 + C.plane;
   const long long o0 = (long long)i * F.plane, o1 = o0 + F.plane;
   double *__restrict__ rf = F.r;
   double *__restrict__ pf = F.p;
-  const int nz = C.nz;
-#define XC(kk, JJ, QQ) xc[QQ + (long long)((kk)-1) * C.RS + JJ]
 #define PUT(k, OO, PP, val) { const long long ro_ = (long long)((k)-1) * F.RS, t_ = OO + ro_ + PP; const double v_ = (val), w_ = ld_rt(pf + t_, stream) + v_; if (WR) st_rt(rf + t_, v_, stream); st_rt(pf + t_, w_, stream); \
     const int jf_ = (PP == po) ? 2 * j2 - 1 : 2 * j2, if_ = (OO == o0) ? i : i + 1; \
     if (WR) mirror_store(F, rf, ro_, jf_, if_, PP, v_, ph); mirror_store(F, pf, ro_, jf_, if_, PP, w_, ph); }
-  if (!LINEAR) {
-    const double v = XC(k2, c0, q0);
-    const int k = 2 * k2 - 1;
-    PUT(k, o0, po, v); PUT(k + 1, o0, po, v); PUT(k, o0, pe, v); PUT(k + 1, o0, pe, v);
-    PUT(k, o1, po, v); PUT(k + 1, o1, po, v); PUT(k, o1, pe, v); PUT(k + 1, o1, pe, v);
-    return;
-  }
-  const double a = 9. / 16., b = 3. / 16., c = 1. / 16., d = 27. / 64., e = 9. / 64., f = 3. / 64., g = 1. / 64.;
-  // the 9 coarse values of level k2 around (j2,i2)
-  const double x00 = XC(k2, c0, q0), xmm = XC(k2, cm, qm), xm0 = XC(k2, cm, q0), x0m = XC(k2, c0, qm),
-               xpm = XC(k2, cp, qm), xp0 = XC(k2, cp, q0), xmp = XC(k2, cm, qp), x0p = XC(k2, c0, qp), xpp = XC(k2, cp, qp);
-#pragma unroll
-  for (int half = 0; half < 2; half++) {
-    const int k = 2 * k2 - 1 + half;  // fine level
-    if (k == 1) {                      // bottom level: bilinear (mg_intergrids.f90:392-405)
-      PUT(1, o0, po, +a * x00 + c * xmm + b * xm0 + b * x0m);
-      PUT(1, o0, pe, +a * x00 + c * xpm + b * xp0 + b * x0m);
-      PUT(1, o1, po, +a * x00 + c * xmp + b * xm0 + b * x0p);
-      PUT(1, o1, pe, +a * x00 + c * xpp + b * xp0 + b * x0p);
-    } else if (k == 2 * nz) {          // top level: 1/2 bilinear (:434-446)
-      PUT(k, o0, po, 0.5 * (a * x00 + c * xmm + b * xm0 + b * x0m));
-      PUT(k, o0, pe, 0.5 * (a * x00 + c * xpm + b * xp0 + b * x0m));
-      PUT(k, o1, po, 0.5 * (a * x00 + c * xmp + b * xm0 + b * x0p));
-      PUT(k, o1, pe, 0.5 * (a * x00 + c * xpp + b * xp0 + b * x0p));
-    } else {                           // interior: tri-linear, kp = k2-1 for odd k, k2+1 for even k (:407-432)
-      const int kp = k2 - ((k % 2) * 2 - 1);
-      const double y00 = XC(kp, c0, q0), ymm = XC(kp, cm, qm), ym0 = XC(kp, cm, q0), y0m = XC(kp, c0, qm),
-                   ypm = XC(kp, cp, qm), yp0 = XC(kp, cp, q0), ymp = XC(kp, cm, qp), y0p = XC(kp, c0, qp), ypp = XC(kp, cp, qp);
-      PUT(k, o0, po, +d * x00 + f * xmm + e * xm0 + e * x0m + e * y00 + g * ymm + f * ym0 + f * y0m);
-      PUT(k, o0, pe, +d * x00 + f * xpm + e * xp0 + e * x0m + e * y00 + g * ypm + f * yp0 + f * y0m);
-      PUT(k, o1, po, +d * x00 + f * xmp + e * xm0 + e * x0p + e * y00 + g * ymp + f * ym0 + f * y0p);
-      PUT(k, o1, pe, +d * x00 + f * xpp + e * xp0 + e * x0p + e * y00 + g * ypp + f * yp0 + f * y0p);
-    }
-  }
-#undef XC
+  const double v = xc[(long long)i2 * C.plane + (long long)(k2 - 1) * C.RS + jpos(C, j2)];
+  const int k = 2 * k2 - 1;
+  PUT(k, o0, po, v); PUT(k + 1, o0, po, v); PUT(k, o0, pe, v); PUT(k + 1, o0, pe, v);
+  PUT(k, o1, po, v); PUT(k + 1, o1, po, v); PUT(k, o1, pe, v); PUT(k + 1, o1, pe, v);
 #undef PUT
 }
 
 // Tri-linear prolongation + correction, one lane = a run of KC coarse levels of one coarse column.
-// k_coarse2fine above fetches 18 coarse values per lane for 8 fine cells (the 3x3 neighbourhood of two coarse levels): 2.25
-// cache accesses per fine cell next to the one load and one store the cell itself needs -- the texture path was busy 80 % of
-// the kernel (rocprofv3 MemUnitStalled) and the level-1 launch ran at 4 TB/s.  Here a lane reads only its OWN column of the three
-// coarse planes i2-1, i2, i2+1, takes the j2-1 / j2+1 columns from its neighbour lanes (the first and last lane of the wave
+// (The kernel this one replaced, one lane per coarse cell, fetched 18 coarse values per lane for 8 fine cells -- the 3x3 neighbourhood of
+// two coarse levels: 2.25 cache accesses per fine cell next to the one load and one store the cell itself needs; the texture path was busy
+// 80 % of the kernel, rocprofv3 MemUnitStalled, and the level-1 launch ran at 4 TB/s.  Measured, decided and removed.)
+// Here a lane reads only its OWN column of the three coarse planes i2-1, i2, i2+1, takes the j2-1 / j2+1 columns from its neighbour lanes (the first and last lane of the wave
 // fetch theirs), and keeps a three-level window while it walks up: 3 / (8 KC) coarse loads per fine cell instead of 2.25; the fine
 // p of the next coarse level are requested before the current level is stored (without that look-ahead the run is a chain of
-// load -> store round trips and loses: 106 us; with it 71 us against 83 us of k_coarse2fine at 512x512x64, WR = false).
-// Same expressions in the same order as above (mg_intergrids.f90:392-446): bit-identical.
+// load -> store round trips and loses: 106 us; with it 71 us against 83 us of the per-cell kernel at 512x512x64, WR = false).
+// The reference's expressions in the reference's order (mg_intergrids.f90:392-446): bit-identical.
 // SK: the fine columns (i odd, j odd) are left alone -- the first colour of the four-colour sweep that follows overwrites them without
 // reading them (a line solve reads only the other columns; mg_relax.f90:212-230), which is a quarter of this kernel's traffic.  Except
 // next to a physical south / west boundary: there the column reads its own old value through the mirrored halo cell (p(0) = p(1)),
@@ -731,30 +696,24 @@ void mgxk_fine2coarse(hipStream_t st, const LevView *F, const LevView *C, double
 }
 // skip1: the caller guarantees that a four-colour relax of the fine level follows (cycles only; see k_coarse2fine_run, SK)
 void mgxk_coarse2fine(hipStream_t st, const LevView *F, const LevView *C, const double *src, int linear, Sides ph, int keep_r, int skip1) {
-  static const bool norun = getenv("MGX_C2F_OLD") != nullptr;
-  if (linear && !norun) {
+  if (linear) {
     // runs of KC coarse levels per lane: long enough to amortise the three-level window, short enough to keep >= ~2 waves per SIMD
-    static const int kcenv = getenv("MGX_C2F_KC") ? atoi(getenv("MGX_C2F_KC")) : 0;
-    int KC = kcenv > 0 ? kcenv : 16;
+    int KC = mgx_switches().c2f_kc > 0 ? mgx_switches().c2f_kc : 16;
     const long long wav = (long long)((C->ny + WAVE - 1) / WAVE) * C->nx;
     while (KC > 1 && wav * ((C->nz + KC - 1) / KC) < 2048) KC >>= 1;
     if (KC > C->nz) KC = C->nz;
     const int nrun = (C->nz + KC - 1) / KC, byr = nrun >= 4 ? 4 : nrun;
     dim3 blk(WAVE, byr), grd((C->ny + WAVE - 1) / WAVE, (nrun + byr - 1) / byr, C->nx);
-    static const int ntenv = getenv("MGX_C2F_NT") ? atoi(getenv("MGX_C2F_NT")) : -1;  // A/B: force the streaming hints on / off
-    const int nt = ntenv >= 0 ? ntenv : level_streams(F);
-    static const bool nosk = getenv("MGX_C2F_NOSKIP") != nullptr;
+    const int nt = mgx_switches().c2f_nt >= 0 ? mgx_switches().c2f_nt : level_streams(F);  // A/B: the streaming hints forced on / off
     if (keep_r) hipLaunchKernelGGL((k_coarse2fine_run<true, false>), grd, blk, 0, st, *F, *C, src, ph, nt, KC);
-    else if (skip1 && !nosk && !(F->nx & 1) && !(F->ny & 1)) hipLaunchKernelGGL((k_coarse2fine_run<false, true>), grd, blk, 0, st, *F, *C, src, ph, nt, KC);
+    else if (skip1 && !(F->nx & 1) && !(F->ny & 1)) hipLaunchKernelGGL((k_coarse2fine_run<false, true>), grd, blk, 0, st, *F, *C, src, ph, nt, KC);
     else hipLaunchKernelGGL((k_coarse2fine_run<false, false>), grd, blk, 0, st, *F, *C, src, ph, nt, KC);
     return;
   }
   const int by = C->nz >= 4 ? 4 : C->nz;
   dim3 blk(WAVE, by), grd((C->ny + WAVE - 1) / WAVE, (C->nz + by - 1) / by, C->nx);
-#define C2F(LIN, WRV) hipLaunchKernelGGL((k_coarse2fine<LIN, WRV>), grd, blk, 0, st, *F, *C, src, ph, level_streams(F))
-  if (linear) { if (keep_r) C2F(true, true); else C2F(true, false); }
-  else { if (keep_r) C2F(false, true); else C2F(false, false); }
-#undef C2F
+  if (keep_r) hipLaunchKernelGGL((k_coarse2fine_nearest<true>), grd, blk, 0, st, *F, *C, src, ph, level_streams(F));
+  else hipLaunchKernelGGL((k_coarse2fine_nearest<false>), grd, blk, 0, st, *F, *C, src, ph, level_streams(F));
 }
 void mgxk_divc_selftest(hipStream_t st, const double *a, const double *b, int n, unsigned long long *bad) {
   hipLaunchKernelGGL(k_divc_selftest, dim3((n + 255) / 256), dim3(256), 0, st, a, b, n, bad);
@@ -780,11 +739,11 @@ void mgxk_halo_p2p(hipStream_t st, const LevView *L, double *a, double *const *r
   // a 512-VGPR smoother wave off its SIMD: harmless when the GPU belongs to one rank (the smoother is behind us in the
   // stream), fatal when several ranks share one GPU as in the tests (the neighbour's smoother would never start).  So the
   // grid is kept small -- at most 128 blocks = 512 of the 1024 SIMDs -- and longer edges give each thread several items.
-  static const int maxblk = getenv("MGX_P2P_MAXBLK") ? atoi(getenv("MGX_P2P_MAXBLK")) : 128;
+  const int maxblk = mgx_switches().p2p_maxblk;  // default 128
   long long items = 0;
   for (int d = 0; d < 8; d++) if (present[d]) items += (long long)L->nz * ((d == 0 || d == 2) ? L->nx : ((d == 1 || d == 3) ? L->ny : 1));
   pp.ipt = (int)((items + 256LL * maxblk - 1) / (256LL * maxblk)) + 1;  // +1: per-direction round-up never exceeds maxblk
-  static const int ipt_min = getenv("MGX_P2P_IPT") ? atoi(getenv("MGX_P2P_IPT")) : 1;  // test hook for the multi-item path
+  const int ipt_min = mgx_switches().p2p_ipt;  // test hook for the multi-item path
   if (pp.ipt < ipt_min) pp.ipt = ipt_min;
   const int per = 256 * pp.ipt;
   int nb = 0;

@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256) void k_restrict32(LevView32 F, LevView32 C, co
 
 // ------------------------------------------------------------------------------------------------
 // coarse2fine: fine e += interp(coarse e), mg_intergrids.f90:366-450 (tri-linear, top level x 1/2), :336-363 (nearest), :226.
-// The expressions of k_coarse2fine (mgx_kernels.hip); the interpolated correction is not stored in r.
+// The expressions of k_coarse2fine_run and k_coarse2fine_nearest (mgx_kernels.hip); the interpolated correction is not stored in r.
 // ------------------------------------------------------------------------------------------------
 template <bool LINEAR>
 __global__ __launch_bounds__(256) void k_coarse2fine32(LevView32 F, LevView32 C) {

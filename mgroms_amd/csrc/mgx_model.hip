@@ -5,8 +5,7 @@
 // of a wave is one contiguous run.  The result b goes to the solver's JS layout through an LDS-tiled transpose, and the
 // pressure comes back the same way for correct_uvw.  Operation order follows the reference line by line
 // (compiled with -ffp-contract=off): results are bit-identical to the CPU oracle.
-#include <cstdlib>
-
+#include "mgx_switches.h"
 #include "mgx_internal.h"
 
 #define U(i, j, k) M.u[(((long long)((k)-1)) * (ny + 2) + (j)) * (nx + 1) + ((i)-1)]
@@ -293,7 +292,7 @@ void mgxm_js_model(hipStream_t st, const LevView *L, double *js, double *md, int
 // runs of 1..7 rows -- every row, or nearly, a run start that reloads the carried values -- can be forced too.
 static inline dim3 igrid_k(int ni, int nj, int klast, int *KR) { *KR = klast >= 16 ? 8 : klast; return dim3((ni + 63) / 64, (nj + 3) / 4, (klast + *KR - 1) / *KR); }
 static inline dim3 igrid_run(int ni, int nj, int klast, int *KR) {
-  static const int krenv = getenv("MGX_MODEL_KR") ? atoi(getenv("MGX_MODEL_KR")) : 0;
+  const int krenv = mgx_switches().model_kr;
   const long long waves = (long long)((ni + 63) / 64) * nj;
   long long nrun = krenv > 0 ? (klast + krenv - 1) / krenv : (16384 + waves - 1) / waves;
   if (nrun < 1) nrun = 1;

@@ -19,8 +19,7 @@
 // shift).  What a plane step costs is its instruction issue (~190 cycles: 4-8 memory instructions, the DPP + FMA chain) and, where the
 // operands live in HBM (level 1), the latency that at most 63 requests in flight per wave leave uncovered -- helper workgroups pull them
 // into the walking wave's L2 (k_rbseq_scan).
-#include <cstdlib>
-
+#include "mgx_switches.h"
 #include "mgx_device.h"
 
 // g = T^-1 e1 of every interior column with tridiag's own recurrences (mg_relax.f90:320-332; bet, gam from k_pivots), and the two
@@ -542,7 +541,7 @@ __global__ __launch_bounds__(256) void k_rbseq_walk_apply(LevView L, int rb, Sid
 // Workgroup = chunk ch of plane i, rows [kz*4*KR, (kz+1)*4*KR): waves 0-3 hold KR rows each (KR = 16 at nz = 64 ... 1 at nz = 4), wave 4 walks.
 constexpr int RBW_MAXM = 48;
 // Measured on level 1 of 512x512x64 (sweep of two passes + two of these launches, HIP events): ring depth 8 at 4 waves per SIMD 0.304-0.315 ms,
-// depth 4 or 2 at 5-6 waves per SIMD 0.304-0.313: the same.  With no plane walked at all (timing probe MGX_RBW_PROBE_M=0) 0.295-0.296, with 14 planes
+// depth 4 or 2 at 5-6 waves per SIMD 0.304-0.313: the same.  With no plane walked at all (a timing probe, since removed) 0.295-0.296, with 14 planes
 // 0.306-0.310: the walk costs ~6 us of the launch's ~45 (201 MB algorithmic, 210 MB counted: profiles/r04_pmc_traffic_rb_window.json) -- the dependent
 // chain of 14 steps in ONE wave that shares its SIMD's issue slots with three row waves; at raised priority (s_setprio) ~4 of the 6 come back.
 template <int CPL, int KR, bool SNAPW, int RBW_D = 8>
@@ -746,10 +745,9 @@ static void rbseq_apply_shape(const LevView *L, int *ku, int *kr) {
 static int rbseq_scan_launch(hipStream_t st, const LevView *L, int rb, RbFuse *fz, int snapw, int have_d0) {
   const int nyh = L->ny / 2, nx = L->nx;
   if (L->gk == nullptr || nyh > 16 * WAVE || (nx & 1)) return 0;
-  static const bool two_waves = getenv("MGX_RBSEQ_TWO_WAVES") != nullptr, d0_out = getenv("MGX_RBSEQ_D0_KERNEL") != nullptr;
+  const bool d0_out = mgx_switches().rbseq_d0_kernel;
   const int rbp = rb & 1;
   // helper workgroups that pull the walk's operands into its L2 (k_rbseq_scan): one per ~32 KB of operands, at most 32 (one per compute unit of an XCD)
-  static const int help_env = getenv("MGX_RBSEQ_HELPERS") ? atoi(getenv("MGX_RBSEQ_HELPERS")) : -1;
   // Measured (512x512x64, rocprofv3): level 1 (4.2 MB of operands, HBM-resident) one wave 88.4 us without helpers, 59.7 with 32; two waves
   // (a barrier per plane) 73; levels 2-4 (1 MB and less) 20.9 / 11.0 / 7.6 us with or without them -- there the walk is bound by the ~190
   // cycles a plane step costs to issue (4-5 memory instructions, the dependent DPP + FMA chain), and a few dozen extra workgroups only add
@@ -758,7 +756,6 @@ static int rbseq_scan_launch(hipStream_t st, const LevView *L, int rb, RbFuse *f
   int nhelp = opbytes >= (2LL << 20) ? (int)((opbytes + 131071) / 131072) : 0;
   if (nhelp > 32) nhelp = 32;
   if (nhelp > nx) nhelp = nx;
-  if (help_env >= 0) nhelp = help_env < nx ? help_env : nx;
   RbFuse none = {};
   // the correction inside the walk's launch: instances for full half-rows, the deepest ring, nz a multiple of 8
   int ku, kr;
@@ -788,7 +785,7 @@ static int rbseq_scan_launch(hipStream_t st, const LevView *L, int rb, RbFuse *f
   // small half-rows: one wave forms d0 itself (the level lives in L2; the walk is bound by its dependent chain, not by its requests)
   // (half-rows of 65..128 columns whose pass wrote d0: the walk reads it -- three requests and a store per plane, 16 planes of look-ahead
   // instead of 8 with five: level 2 of 512x512x64 20.5 -> ~16 us per colour, Vcycle 3.12 -> 3.08 ms; MGX_RBSEQ_NO_D0_MID: A/B)
-  static const bool d0_mid = getenv("MGX_RBSEQ_NO_D0_MID") == nullptr;
+  const bool d0_mid = mgx_switches().rbseq_d0_mid;
   if (nyh <= 2 * WAVE && !d0_out && !(have_d0 && d0_mid && nyh > WAVE)) {
     if (nyh <= WAVE) SCAN_CPL(1, 16, 1, true)   // y, snapshot, the multiplier pair, the store of u: 4 operations per plane, 16 planes deep
     SCAN_CPL(2, 8, 1, true)
@@ -799,7 +796,6 @@ static int rbseq_scan_launch(hipStream_t st, const LevView *L, int rb, RbFuse *f
   // wide half-rows: the requests of ONE wave (at most 63 in flight) do not cover the latency of a level that lives in HBM: several waves
   // (256 columns per half-row: ONE wave with the helpers beats two waves with a barrier per plane, 59.7 against 73 us; wider half-rows
   // -- 512 and 1024 columns, BASELINE config 5 -- would need 16 / 32 memory instructions per plane in one wave: several waves there, unmeasured)
-  if (nyh == 4 * WAVE && two_waves) SCAN_CPL(2, 16, 2, false)
   if (nyh == 8 * WAVE) SCAN_CPL(2, 16, 4, false)
   if (nyh == 16 * WAVE) SCAN_CPL(2, 16, 8, false)
   if (nyh <= 4 * WAVE) SCAN_CPL(4, 8, 1, false)
@@ -814,9 +810,8 @@ static int rbseq_scan_launch(hipStream_t st, const LevView *L, int rb, RbFuse *f
 int mgxk_rbseq_scan(hipStream_t st, const LevView *L, int rb, int have_d0) { return rbseq_scan_launch(st, L, rb, nullptr, 0, have_d0); }
 // does the walk of this level read d0 from u1 (wide half-rows) rather than form it itself?  Then the colour pass should write it (LevView::d0w)
 int mgxk_rbseq_wants_d0(const LevView *L) {
-  static const bool d0_out = getenv("MGX_RBSEQ_D0_KERNEL") != nullptr;
+  const bool d0_out = mgx_switches().rbseq_d0_kernel, d0_mid = mgx_switches().rbseq_d0_mid;
   // (wide half-rows: the walk reads d0; small levels: k_rbseq_walk_apply needs it where no workgroup of its launch writes)
-  static const bool d0_mid = getenv("MGX_RBSEQ_NO_D0_MID") == nullptr;
   return L->gk != nullptr && (L->ny / 2 > 2 * WAVE || d0_out || (L->ny / 2 <= WAVE && L->nx <= 128) || (d0_mid && L->ny / 2 > WAVE));
 }
 
@@ -834,8 +829,7 @@ int mgxk_rbseq_scan_apply(hipStream_t st, const LevView *L, int rb, Sides ph, in
 // (b) + (c) of a small level in ONE launch (k_rbseq_walk_apply); needs d0 in u1 (the colour pass wrote it).  Returns 1 when launched.
 int mgxk_rbseq_walk_apply(hipStream_t st, const LevView *L, int rb, Sides ph, int snapw) {
   const int nyh = L->ny / 2, nx = L->nx, nz = L->nz;
-  static const bool off = getenv("MGX_NO_RBSEQ_WALK_APPLY") != nullptr;
-  if (off || L->gk == nullptr || nyh > WAVE || nx > 128 || (nx & 1) || nz < 4 || (nz & 3)) return 0;
+  if (mgx_switches().no_rbseq_walk_apply || L->gk == nullptr || nyh > WAVE || nx > 128 || (nx & 1) || nz < 4 || (nz & 3)) return 0;
   mgx_before_launch();
   constexpr int DW = 16;
   const size_t lds = (size_t)(nx + DW + 1) * 64 * sizeof(double);
@@ -895,16 +889,12 @@ int mgxk_rbseq_window(hipStream_t st, const LevView *L, int rb, Sides ph, int sn
   if (kcut < 1 || kcut > nz) kcut = nz;
   // the rows the correction reaches, spread over the four row waves of a workgroup (16 of 64 rows: four rows per wave rather than one wave with all
   // sixteen and three idle), and only the row groups that hold any are launched
-  static const bool no_spread = getenv("MGX_RBW_NO_SPREAD") != nullptr;   // A/B
-  while (!no_spread && kr > 1 && 4 * (kr / 2) >= kcut) kr /= 2;
+  while (kr > 1 && 4 * (kr / 2) >= kcut) kr /= 2;
   mgx_before_launch();
-  static const bool no_xmap = getenv("MGX_RBSEQ_WINDOW_NO_XMAP") != nullptr;   // A/B
   // the walking wave at raised priority (s_setprio 3): level-1 sweep 0.3075-0.3150 -> 0.2989-0.3073 ms (three runs each, alternating); MGX_RBW_PRIO=0: A/B
-  static const int prio = getenv("MGX_RBW_PRIO") ? atoi(getenv("MGX_RBW_PRIO")) : 1;
-  static const int probe_m = getenv("MGX_RBW_PROBE_M") ? atoi(getenv("MGX_RBW_PROBE_M")) : -1;   // timing probe only (wrong results): another number of planes walked
-  if (probe_m >= 0) m = probe_m;
+  const int prio = mgx_switches().rbw_prio;
   const int nt = level_streams(L), cpl = nyh <= WAVE ? 1 : 2, nch = (nyh + WAVE - 1) / WAVE, nkz = (kcut + 4 * kr - 1) / (4 * kr);
-  const int xmap = !no_xmap && L->nx % 8 == 0 && (long long)nch * L->nx * nkz < (1LL << 31);
+  const int xmap = !mgx_switches().rbseq_window_no_xmap && L->nx % 8 == 0 && (long long)nch * L->nx * nkz < (1LL << 31);
   const dim3 grd = xmap ? dim3(nch * L->nx * nkz) : dim3(nch, L->nx, nkz), blk(320);
 #define WIN_CASE(CPLV, KRV)                                                                                          \
   { if (snapw) hipLaunchKernelGGL((k_rbseq_window<CPLV, KRV, true, (KRV <= 4 ? 4 : 8)>), grd, blk, 0, st, *L, rb, ph, m, nt, xmap, nch, nkz, prio, kcut); \

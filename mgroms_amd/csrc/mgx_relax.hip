@@ -6,8 +6,7 @@
 //
 // Thread mapping everywhere: one lane = one (j,i) column, lanes run along the unit-stride half-row of
 // the JS layout (mgx_internal.h), so every global access of a wave is one contiguous 512-byte run.
-#include <cstdlib>
-
+#include "mgx_switches.h"
 #include "mgx_relax_common.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -431,8 +430,7 @@ __global__ __launch_bounds__(256) void k_relax_tiny(LevView G, int nsweeps, int 
 
 template <int NZ, int D>
 static void launch_relax_nz_d(hipStream_t st, const LevView *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, Sides ph) {
-  static const bool noxcd = getenv("MGX_NO_XCD") != nullptr;
-  const int gx0 = (L->ny / 2 + WAVE - 1) / WAVE, gx = noxcd ? -gx0 : gx0;
+  const int gx0 = (L->ny / 2 + WAVE - 1) / WAVE, gx = mgx_switches().no_xcd ? -gx0 : gx0;
   // two planes per workgroup only when there are plenty of workgroups (it halves the number of CUs a small level uses)
   const int by = gx0 * nplanes >= 2048 ? 2 : 1;
   dim3 blk(WAVE, by), grd(gx0 * ((nplanes + by - 1) / by));
@@ -489,10 +487,9 @@ int mgxk_relax_small(hipStream_t st, const LevView *L, int nsweeps, int method, 
   if (mgxk_relax_wave(st, L, nsweeps, method, real, ph, mode)) return 1;  // <= 256 columns, nz = 2: the whole level in one wave
   const int exact = mode != 0;
   {  // one thread per column, coefficients in registers, p in LDS
-    static const bool noreg = getenv("MGX_NO_REG") != nullptr;
     const int ncols = L->nx * L->ny;
     const bool closed = ph.S && ph.E && ph.N && ph.W;
-    if (!noreg && closed && method != 0 && ((L->nz == 2 && ncols <= 1024) || (L->nz == 4 && ncols <= 256))) {
+    if (!mgx_switches().no_reg && closed && method != 0 && ((L->nz == 2 && ncols <= 1024) || (L->nz == 4 && ncols <= 256))) {
       const size_t bytes = ((size_t)L->nz + 1) * (L->nx + 2) * (L->ny + 2) * sizeof(double);
       const int nth = (ncols + 63) / 64 * 64;
       if (L->nz == 2) { if (real) hipLaunchKernelGGL((k_relax_reg<2, true, 1024>), dim3(1), dim3(nth), bytes, st, *L, nsweeps, method, ph, exact);
@@ -503,9 +500,8 @@ int mgxk_relax_small(hipStream_t st, const LevView *L, int nsweeps, int method, 
     }
   }
   {  // everything in LDS? (11 arrays of the compact level + the k=1 snapshot)
-    static const bool notiny = getenv("MGX_NO_TINY") != nullptr;
     const size_t n3 = (size_t)(L->nx + 2) * (L->ny + 2) * L->nz, bytes = (11 * n3 + (size_t)(L->nx + 2) * (L->ny + 2)) * sizeof(double);
-    if (!notiny && !(exact && method == 1 && real) && bytes <= 64 * 1024 && (ph.S && ph.E && ph.N && ph.W) && (L->nz == 2 || L->nz == 4)) {
+    if (!mgx_switches().no_tiny && !(exact && method == 1 && real) && bytes <= 64 * 1024 && (ph.S && ph.E && ph.N && ph.W) && (L->nz == 2 || L->nz == 4)) {
       const int ncolt = method == 2 ? (L->nx / 2) * (L->ny / 2) : L->nx * (L->ny / 2);
       const int ntht = ncolt <= 64 ? 64 : 256;
       if (L->nz == 2) { if (real) hipLaunchKernelGGL((k_relax_tiny<2, true>), dim3(1), dim3(ntht), bytes, st, *L, nsweeps, method, ph);
@@ -539,44 +535,49 @@ int mgxk_relax_small(hipStream_t st, const LevView *L, int nsweeps, int method, 
 #undef SMALL_CASE
 }
 
-// returns bit 0: the kernel stored the physical mirrors of p itself (no k_halo_phys needed); bit 1: it wrote L->d0w; bit 2: it was the
-// stored-coefficient tall-column pass (mgx_relax_tall.hip; relax() counts those)
+// the nz of the register-resident instances of the colour pass (k_relax_nz): the powers of two, and the vertical sizes that are not (ROMS /
+// CROCO users choose nz for their physics) with their coarser levels.  X(nz) once per instance; nz = 80, 96, 128 are mgxk_relax_tall's.
+#ifdef MGX_QUICK  // -DMGX_QUICK: only the nz=64 instantiations (resource-usage checks of the level-1 kernel in seconds)
+#define REG_NZ_LIST(X) X(64)
+#else
+#define REG_NZ_LIST(X) X(2) X(4) X(8) X(16) X(32) X(64) X(12) X(20) X(24) X(40) X(48)
+#endif
+
+// returns what the pass did (mgx_wrappers.h): PASS_MIRRORS the kernel stored the physical mirrors of p itself (no k_halo_phys needed); PASS_D0 it
+// wrote L->d0w; PASS_TALL_STORED it was the stored-coefficient tall-column pass (mgx_relax_tall.hip; relax() counts those)
 int mgxk_relax_colour(hipStream_t st, const LevView *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, Sides ph) {
   if (const int ks = mgxk_relax_ks(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph)) return ks;  // mid levels: rows split over the waves of a workgroup
   switch (L->nz) {
-#ifndef MGX_QUICK  // -DMGX_QUICK: only the nz=64 instantiations (resource-usage checks of the level-1 kernel in seconds)
-    case 2: launch_relax_nz<2>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
-    case 4: launch_relax_nz<4>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
-    case 8: launch_relax_nz<8>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
-    case 16: launch_relax_nz<16>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
-    case 32: launch_relax_nz<32>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
-#endif
-    case 64: launch_relax_nz<64>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
+#define REG_CASE(NZV) case NZV: launch_relax_nz<NZV>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); break;
+    REG_NZ_LIST(REG_CASE)
+#undef REG_CASE
 #ifndef MGX_QUICK
-    // vertical sizes that are not powers of two (ROMS / CROCO users choose nz for their physics) and their coarser levels
-    case 12: launch_relax_nz<12>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
-    case 20: launch_relax_nz<20>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
-    case 24: launch_relax_nz<24>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
-    case 40: launch_relax_nz<40>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
-    case 48: launch_relax_nz<48>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); return (real && snap && L->d0w != nullptr) ? 3 : 1;
-    case 80: case 96: case 128: if (const int tall = mgxk_relax_tall(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph)) return tall; break;
+    case 80: case 96: case 128: if (const int tall = mgxk_relax_tall(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph)) return tall;
 #endif
-    default: break;
+    // fall through
+    default: {
+      dim3 blk(WAVE, 4), grd = col_grid(L->ny / 2, nplanes);
+      if (real && snap) hipLaunchKernelGGL((k_relax_colour<true, true>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph);
+      else if (real) hipLaunchKernelGGL((k_relax_colour<true, false>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph);
+      else hipLaunchKernelGGL((k_relax_colour<false, false>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph);
+      return 0;
+    }
   }
-  dim3 blk(WAVE, 4), grd = col_grid(L->ny / 2, nplanes);
-  if (real && snap) hipLaunchKernelGGL((k_relax_colour<true, true>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph);
-  else if (real) hipLaunchKernelGGL((k_relax_colour<true, false>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph);
-  else hipLaunchKernelGGL((k_relax_colour<false, false>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph);
-  return 0;
+  return (real && snap && L->d0w != nullptr) ? PASS_MIRRORS | PASS_D0 : PASS_MIRRORS;
 }
 // does mgxk_relax_colour run a register-resident kernel (which writes mirrors and chained snapshots) on this level?
 int mgxk_has_reg_kernel(const LevView *L) {
   switch (L->nz) {
-    case 2: case 4: case 8: case 16: case 32: case 64: case 12: case 20: case 24: case 40: case 48: return 1;
-    case 80: case 96: case 128: return getenv("MGX_NO_TALL") == nullptr;  // matrix-free or stored: mgxk_relax_tall has both
+#define REG_CASE(NZV) case NZV:
+    REG_NZ_LIST(REG_CASE) return 1;
+#undef REG_CASE
+#ifndef MGX_QUICK
+    case 80: case 96: case 128: return !mgx_switches().no_tall;  // matrix-free or stored: mgxk_relax_tall has both
+#endif
     default: return 0;
   }
 }
+#undef REG_NZ_LIST
 void mgxk_snapshot_k1(hipStream_t st, const LevView *L) {
   hipLaunchKernelGGL(k_snapshot_k1, dim3((L->RS + 255) / 256, L->nx + 2), dim3(256), 0, st, *L);
 }

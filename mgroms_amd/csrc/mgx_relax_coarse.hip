@@ -12,15 +12,14 @@
 // through indices clamped to the interior -- no mirror stores, no branches in a pass (they were a third of its instructions); the halo of
 // the global array is rebuilt once, when p is written back.
 // Same expressions in the same order as relax_col_nz / k_relax_reg: bit-identical.
-#include <cstdlib>
-
+#include "mgx_switches.h"
 #include "mgx_device.h"
 
 // flags (round 3; the level below the coarsest one in a cycle): 1 = coarse2fine(lev) first -- p += the tri-linear interpolation of the
 // coarse p of C (mg_intergrids.f90:366-450 + :226), applied while p is loaded into LDS; 2 = compute_residual(lev) + fine2coarse(lev)
 // afterwards (mg_relax.f90:421-515, mg_intergrids.f90:139-162, p_c = 0 :70) from the coefficients the lane holds anyway -- a lane's 2x2
 // block of columns is exactly one coarse column, so the 8-cell sum closes inside the lane.  Two launches less per level visit; the same
-// expressions in the same order as k_coarse2fine, k_residual and k_fine2coarse (the stored diagonal; the matrix-free kernels rebuild
+// expressions in the same order as k_coarse2fine_run, k_residual and k_fine2coarse (the stored diagonal; the matrix-free kernels rebuild
 // the same bits).
 // FZ: the instance that can fold the transfers in (instantiated for nz = 4 only: the plain kernels keep their register budget)
 // SEQ: red-black in the reference's sequential order (the walk below; REAL only) -- its own instances, so that the others keep their registers
@@ -371,13 +370,11 @@ extern "C" {
 // reference's sequential order by the walk (k_relax_wave's seq)
 static int relax_wave_launch(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode, const LevView *Cv, int flags, int nbatch = 1, long long bstride = 0) {
   mgx_before_launch();
-  static const bool off = getenv("MGX_NO_WAVE") != nullptr, off4 = getenv("MGX_NO_WAVE4") != nullptr, off8 = getenv("MGX_NO_WAVE8") != nullptr;
-  if (off || (L->nz != 2 && L->nz != 4) || method == 0 || (mode == 1 && method == 1 && real)) return 0;
+  if (mgx_switches().no_wave || (L->nz != 2 && L->nz != 4) || method == 0 || (mode == 1 && method == 1 && real)) return 0;
   const int seq = (mode == 2 && method == 1 && real) ? 1 : 0;
   if (seq && L->ny / 2 > WAVE) return 0;  // the walk keeps a half-row on the lanes of one wave; wider levels: k_relax_reg's plane loop
   const int nblk = (L->nx / 2) * (L->ny / 2);
-  if (!(ph.S && ph.E && ph.N && ph.W) || (L->nx & 1) || (L->ny & 1) || nblk > (L->nz == 2 && !off8 ? 8 : 4) * WAVE) return 0;
-  if ((nblk > WAVE || L->nz == 4) && off4) return 0;
+  if (!(ph.S && ph.E && ph.N && ph.W) || (L->nx & 1) || (L->ny & 1) || nblk > (L->nz == 2 ? 8 : 4) * WAVE) return 0;
   size_t bytes = ((size_t)L->nz + 1) * (L->nx + 2) * (L->ny + 2) * sizeof(double);
   if (seq) {  // p, the snapshot and u, interiors only
     bytes = ((2 * (size_t)L->nz + 5) * L->nx * L->ny + 4 + 64 * 18) * sizeof(double);  // p, the snapshot, the operand quads (+ a zero quad), g, the register walk's d0 / s rows
@@ -504,8 +501,7 @@ int mgxk_coarse_direct_slabs(int n) { return (n + CDB - 1) / CDB; }
 // compute_residual(lev) + fine2coarse(lev) folded behind (flags & 2); C = level lev+1 (closed, exactly half the size, not gathered).
 // Returns 1 when launched, 0 = the caller runs the separate operators.
 int mgxk_relax_wave_fused(hipStream_t st, const LevView *L, const LevView *C, int nsweeps, int method, int real, Sides ph, int flags, int mode) {
-  static const bool off = getenv("MGX_NO_WAVE_FUSE") != nullptr;
-  if (off || !C || C->nx * 2 != L->nx || C->ny * 2 != L->ny || C->nz * 2 != L->nz || nsweeps < 0) return 0;
+  if (mgx_switches().no_wave_fuse || !C || C->nx * 2 != L->nx || C->ny * 2 != L->ny || C->nz * 2 != L->nz || nsweeps < 0) return 0;
   return relax_wave_launch(st, L, nsweeps, method, real, ph, mode, C, flags);
 }
 

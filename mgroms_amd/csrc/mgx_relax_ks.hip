@@ -9,8 +9,7 @@
 // parks them in LDS, wave 0 runs the two sweeps of the recurrence from LDS, and all waves store their rows of p.
 // Four (or eight) times the loads in flight per column, two round trips instead of nine.
 // Same expressions in the same order as relax_col_mf: bit-identical results.
-#include <cstdlib>
-
+#include "mgx_switches.h"
 #include "mgx_relax_common.h"
 
 // H > 1 (nz = 64, the second level of an nz = 128 hierarchy): a wave's NZ/NW rows are built in H runs of R rows one after the other (the register
@@ -559,28 +558,27 @@ __global__ __launch_bounds__(64 * NW, 1) void k_relax_ksp(LevView L, int nsweeps
 
 extern "C" {
 
-// returns 1 when the pass was launched here (the level qualifies), 0 to let the row-by-row kernels take it
+// returns 0 to let the row-by-row kernels take the pass, else what the pass launched here did (the level qualifies): PASS_MIRRORS, and
+// PASS_D0 when it wrote L->d0w
 int mgxk_relax_ks(hipStream_t st, const LevView *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, Sides ph) {
   mgx_before_launch();
-  static const bool off = getenv("MGX_NO_KS") != nullptr, noxcd = getenv("MGX_NO_XCD") != nullptr;
-  static const int nw_env = getenv("MGX_KS_NW") ? atoi(getenv("MGX_KS_NW")) : 0;
-  static const bool ks8 = getenv("MGX_NO_KS8") == nullptr;
-  static const bool ks64 = getenv("MGX_NO_KS64") == nullptr;
-  if (off || L->zy == nullptr || (L->nz != 32 && L->nz != 16 && !(L->nz == 8 && ks8) && !(L->nz == 64 && ks64 && !snap))) return 0;
+  const Switches &sw = mgx_switches();
+  const int nw_env = sw.ks_nw;
+  if (sw.no_ks || L->zy == nullptr || (L->nz != 32 && L->nz != 16 && !(L->nz == 8 && sw.ks8) && !(L->nz == 64 && sw.ks64 && !snap))) return 0;
   const int gx0 = (L->ny / 2 + WAVE - 1) / WAVE;
   // worth it only while a colour has fewer waves than the chip has SIMDs (1024); a bandwidth-bound level keeps one wave per column set
   if (gx0 * nplanes > 512) return 0;
   // the level must live in the caches (no streaming hints here)
-  const int gx = noxcd ? -gx0 : gx0;
+  const int gx = sw.no_xcd ? -gx0 : gx0;
   dim3 grd(gx0 * nplanes);
 #define KS_LAUNCH(NZV, NWV)                                                                                                     \
   {                                                                                                                              \
     dim3 blk(WAVE, NWV);                                                                                                         \
     const size_t lds = (size_t)3 * NZV * WAVE * sizeof(double);                                                                  \
-    if (real && snap) { hipLaunchKernelGGL((k_relax_ks<NZV, NWV, true, true>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx); return mgx_launched() ? (L->d0w != nullptr ? 3 : 1) : 0; } \
+    if (real && snap) { hipLaunchKernelGGL((k_relax_ks<NZV, NWV, true, true>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx); return mgx_launched() ? (L->d0w != nullptr ? PASS_MIRRORS | PASS_D0 : PASS_MIRRORS) : 0; } \
     else if (real) hipLaunchKernelGGL((k_relax_ks<NZV, NWV, true, false>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx);     \
     else hipLaunchKernelGGL((k_relax_ks<NZV, NWV, false, false>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx);              \
-    return mgx_launched();                                                                                                       \
+    return mgx_launched() ? PASS_MIRRORS : 0;                                                                             \
   }
   if (L->nz == 64) {  // 96 KB of dynamic LDS: above the 64 KB a kernel gets without asking
     static bool attr = false;
@@ -593,7 +591,7 @@ int mgxk_relax_ks(hipStream_t st, const LevView *L, int i0, int istep, int nplan
     dim3 blk(WAVE, 8);
     if (real) hipLaunchKernelGGL((k_relax_ks<64, 8, true, false, 2>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx);
     else hipLaunchKernelGGL((k_relax_ks<64, 8, false, false, 2>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx);
-    return mgx_launched();
+    return mgx_launched() ? PASS_MIRRORS : 0;
   }
   // measured (256x256x32 / 128x128x16, four-colour sweep): 8 waves 47.0 / 21.6 us, 4 waves 53.3 / 23.3, row by row 57.6 / 28.2
   if (L->nz == 32) { if (nw_env == 4) KS_LAUNCH(32, 4) else KS_LAUNCH(32, 8) }
@@ -602,12 +600,10 @@ int mgxk_relax_ks(hipStream_t st, const LevView *L, int i0, int istep, int nplan
 #undef KS_LAUNCH
 }
 
-// (mgxk_relax_ks returns 0 = not launched, 1 = launched, 3 = launched and L->d0w written)
 // both colours of the planes i0, i0+2, ... of a four-colour sweep in one launch; returns 1 when launched (closed level, one column set per plane)
 int mgxk_relax_ks_pair(hipStream_t st, const LevView *L, int i0, int nplanes, int real, Sides ph) {
   mgx_before_launch();
-  static const bool off = getenv("MGX_NO_KS") != nullptr || getenv("MGX_NO_KS2") != nullptr;
-  if (off || L->zy == nullptr || !(ph.S && ph.E && ph.N && ph.W) || (L->ny & 1) || L->ny / 2 > WAVE) return 0;
+  if (mgx_switches().no_ks || mgx_switches().no_ks2 || L->zy == nullptr || !(ph.S && ph.E && ph.N && ph.W) || (L->ny & 1) || L->ny / 2 > WAVE) return 0;
   if (L->nz != 16 && L->nz != 8) return 0;
   dim3 grd(nplanes), blk(WAVE, 8);
   if (L->nz == 16) { if (real) hipLaunchKernelGGL((k_relax_ks2<16, 8, true>), grd, blk, 0, st, *L, i0, nplanes, ph);
@@ -626,11 +622,11 @@ int mgxk_set_ksp_timeout(double ms) {
 // stall: test hook, the plane whose workgroup returns at once (0 = none)
 int mgxk_relax_ks_persist(hipStream_t st, const LevView *L, int nsweeps, int real, Sides ph, unsigned int *done, unsigned int base, int *err, int stall) {
   mgx_before_launch();
-  static const bool off = getenv("MGX_NO_KS") != nullptr || getenv("MGX_NO_KS2") != nullptr || getenv("MGX_NO_KSP") != nullptr;
+  const Switches &sw = mgx_switches();
   // default: plain accesses between agent-scope release / acquire fences (the architecturally guaranteed hand-off); MGX_KSP_SC1=1: the
   // fence-free form with sc1 stores and loads (measured on gfx950 only) -- the two time the same (F-cycle 283-285 vs 285 it/s)
-  static const bool fence = getenv("MGX_KSP_SC1") == nullptr;
-  if (off || nsweeps < 1 || L->zy == nullptr || !(ph.S && ph.E && ph.N && ph.W) || (L->ny & 1) || (L->nx & 1) || L->ny / 2 > WAVE) return 0;
+  const bool fence = sw.ksp_fence;
+  if (sw.no_ks || sw.no_ks2 || sw.no_ksp || nsweeps < 1 || L->zy == nullptr || !(ph.S && ph.E && ph.N && ph.W) || (L->ny & 1) || (L->nx & 1) || L->ny / 2 > WAVE) return 0;
   if ((L->nz != 16 && L->nz != 8 && L->nz != 4) || L->nx > 128 || done == nullptr || err == nullptr) return 0;
   // nz = 16: four waves of four rows (both colours' coefficients of a lane: 288 registers, one wave per SIMD); nz = 8: eight waves of one row;
   // nz = 4: four waves of one row (the 128x64x4 level that eight GPUs gather; a single GPU's 32x32x4 level is k_relax_wave's)

@@ -6,8 +6,7 @@
 // regenerated zw and the own slopes from regenerated zr do.
 // The forward rows of both forms are the shared texts of mgx_relax_common.h (MF_ROW with relax_col_mf, SC_ROW with relax_col_nz: the
 // instances of mgx_relax.hip compile to the instructions they had before the stored text was shared); the way down is TALL_DOWN below.
-#include <cstdlib>
-
+#include "mgx_switches.h"
 #include "mgx_relax_common.h"
 
 // Tall columns (nz = 128, BASELINE config 5): x and gam of 128 rows do not fit the register file next to the load rings.
@@ -118,14 +117,13 @@ TALL_KERNEL(k_relax_tall_st, relax_col_st_tall)
 
 // nz = 128 (BASELINE config 5), 96 and 80, lower 64 rows through LDS: the matrix-free form where the level has its slopes (L->zy), the
 // stored-coefficient form where it has not.  Returns 0 = nothing ran (the caller's generic column takes the pass), 1 = the matrix-free
-// pass ran, 5 = the stored one (bit 0: the physical mirrors are written; bit 2 is what relax() counts as "tall_stored_passes").
+// pass ran (PASS_MIRRORS: the physical mirrors are written), with PASS_TALL_STORED the stored one (what relax() counts as "tall_stored_passes").
 extern "C" int mgxk_relax_tall(hipStream_t st, const LevView *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, Sides ph) {
   if (L->nz != 128 && L->nz != 96 && L->nz != 80) return 0;
   mgx_before_launch();
-  static const bool noxcd = getenv("MGX_NO_XCD") != nullptr, notall = getenv("MGX_NO_TALL") != nullptr;
-  if (notall) return 0;
+  if (mgx_switches().no_tall) return 0;
   const bool mf = L->zy != nullptr;
-  const int gx0 = (L->ny / 2 + WAVE - 1) / WAVE, gx = noxcd ? -gx0 : gx0;
+  const int gx0 = (L->ny / 2 + WAVE - 1) / WAVE, gx = mgx_switches().no_xcd ? -gx0 : gx0;
   const int by = gx0 * nplanes >= 2048 ? 2 : 1;
   dim3 blk(WAVE, by), grd(gx0 * ((nplanes + by - 1) / by));
   const bool stream = (double)L->nx * L->ny * L->nz * 72.0 > 256e6;
@@ -156,5 +154,5 @@ extern "C" int mgxk_relax_tall(hipStream_t st, const LevView *L, int i0, int ist
 #undef LAUNCH_TALL
 #undef LAUNCH_TALL_ONE
   if (!mgx_launched()) return 0;
-  return mf ? 1 : 5;
+  return mf ? PASS_MIRRORS : PASS_MIRRORS | PASS_TALL_STORED;
 }

@@ -14,8 +14,7 @@
 // The residuals and the 8-term sum use the reference's expressions in the reference's order: b_c is bit-identical to
 // compute_residual followed by fine2coarse.  Matrix-free cross terms (needs the slopes zy, zx: the matrix must be the one
 // define_matrices built); other cases keep the two separate kernels.
-#include <cstdlib>
-
+#include "mgx_switches.h"
 #include "mgx_device.h"
 
 namespace {
@@ -335,26 +334,21 @@ extern "C" {
 // returns 1 when launched (matrix-free slopes present, level large enough to be bandwidth-bound), 0 = use mgxk_residual + mgxk_fine2coarse
 // partial != nullptr: also sum r^2 (partials, one per workgroup; *npartial_out = their number); dup: second destination of the coarse sums
 int mgxk_residual_restrict_grid(const LevView *F, const LevView *C) {  // workgroups (= norm partials) of the launch below
-  static const long long flatmax = getenv("MGX_RESREST_FLAT_MAX") ? atoll(getenv("MGX_RESREST_FLAT_MAX")) : 256LL * 256 * 64;
   const int gx = (C->ny + 31) / 32;
-  if ((long long)F->nx * F->ny * F->nz <= flatmax) {
-    static const int senv = getenv("MGX_RESREST_FLAT_S") ? atoi(getenv("MGX_RESREST_FLAT_S")) : 0;
-    const int Sv = (senv >= 4 && F->nz >= 4) ? 4 : 2;
+  if ((long long)F->nx * F->ny * F->nz <= mgx_switches().resrest_flat_max) {
+    const int Sv = (mgx_switches().resrest_flat_s >= 4 && F->nz >= 4) ? 4 : 2;
     return gx * C->nx * ((F->nz + Sv - 1) / Sv);
   }
   return gx * ((C->nx + 3) / 4);
 }
 int mgxk_residual_restrict_ex(hipStream_t st, const LevView *F, const LevView *C, double *dst, int real, Sides ph, double *zero, double *partial, double *dup) {
   mgx_before_launch();
-  static const bool off = getenv("MGX_NO_RESREST") != nullptr;
-  static const long long mincells = getenv("MGX_RESREST_MIN") ? atoll(getenv("MGX_RESREST_MIN")) : 0;
-  if (off || F->zy == nullptr || F->nz < 2 || (F->nz & 1)) return 0;
+  const Switches &sw = mgx_switches();
+  if (sw.no_resrest || F->zy == nullptr || F->nz < 2 || (F->nz & 1)) return 0;
   if (C->nx * 2 != F->nx || C->ny * 2 != F->ny) return 0;
-  if ((long long)F->nx * F->ny * F->nz < mincells) return 0;
-  static const long long flatmax = getenv("MGX_RESREST_FLAT_MAX") ? atoll(getenv("MGX_RESREST_FLAT_MAX")) : 256LL * 256 * 64;
-  if ((long long)F->nx * F->ny * F->nz <= flatmax) {  // no walk: one wave per S fine rows, one round trip
-    static const int senv = getenv("MGX_RESREST_FLAT_S") ? atoi(getenv("MGX_RESREST_FLAT_S")) : 0;
-    const int gx = (C->ny + 31) / 32, Sr = senv ? senv : 2;
+  if ((long long)F->nx * F->ny * F->nz < sw.resrest_min) return 0;
+  if ((long long)F->nx * F->ny * F->nz <= sw.resrest_flat_max) {  // no walk: one wave per S fine rows, one round trip
+    const int gx = (C->ny + 31) / 32, Sr = sw.resrest_flat_s ? sw.resrest_flat_s : 2;
     dim3 blk(WAVE);
 #define RRF(REALV, SV, NV) hipLaunchKernelGGL((k_residual_restrict_flat<REALV, SV, NV>), dim3((unsigned)gx * C->nx * ((F->nz + SV - 1) / SV)), blk, 0, st, *F, *C, dst, ph, zero, gx, partial, dup)
 #define RRF2(SV) { if (partial) { if (real) RRF(true, SV, true); else RRF(false, SV, true); } else { if (real) RRF(true, SV, false); else RRF(false, SV, false); } }
@@ -365,7 +359,7 @@ int mgxk_residual_restrict_ex(hipStream_t st, const LevView *F, const LevView *C
   }
   const int by = 4, gx = (C->ny + 31) / 32, gy = (C->nx + by - 1) / by;
   dim3 blk(WAVE, by), grd(gx * gy);
-  static const int deep = getenv("MGX_RESREST_AHEAD") ? atoi(getenv("MGX_RESREST_AHEAD")) : 11;  // 10 * AW + AR (A/B: scripts/probe/ab_resrest_ahead.sh -- 11, 12, 21 within 5 % of each other once the requests are unconditional)
+  const int deep = sw.resrest_ahead;  // 10 * AW + AR, default 11 (A/B: scripts/probe/ab_resrest_ahead.sh -- 11, 12, 21 within 5 % of each other once the requests are unconditional)
 #define RRW(REALV, AWV, ARV, NV) hipLaunchKernelGGL((k_residual_restrict<REALV, AWV, ARV, NV>), grd, blk, 0, st, *F, *C, dst, ph, zero, gx, gy, partial, dup)
 #define RRW2(AWV, ARV) { if (partial) { if (real) RRW(true, AWV, ARV, true); else RRW(false, AWV, ARV, true); } else { if (real) RRW(true, AWV, ARV, false); else RRW(false, AWV, ARV, false); } }
   switch (deep) {

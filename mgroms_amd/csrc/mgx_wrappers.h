@@ -11,6 +11,13 @@ struct ModelView { double *u, *v, *w, *rmask; int bmask; };  // rmask: i-fastest
 
 extern "C" {
 
+// what a colour pass reports: the return value of mgxk_relax_colour, mgxk_relax_ks and mgxk_relax_tall (0 from the last two: nothing ran)
+enum {
+  PASS_MIRRORS = 1,      // the kernel stored the physical images of p itself: no k_halo_phys behind it
+  PASS_D0 = 2,           // it wrote L->d0w, the walk's d0 of sequential-order red-black
+  PASS_TALL_STORED = 4,  // it was the stored-coefficient tall-column pass (counter "tall_stored_passes")
+};
+
 // ---- mgx_relax.hip ----
 int mgxk_relax_gs_sweep(hipStream_t st, const LevView *L, int real);
 int mgxk_relax_small(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode);

@@ -271,6 +271,51 @@ def test_rb_sequential_order_correction_inside_the_walk_launch(mg, dims):
     assert np.abs(ref[lev] - c).max() <= 1e-12 * np.abs(c).max()
 
 
+_RB_ROUTES_REF = {}
+
+
+@pytest.mark.parametrize("route", ["window", "walk_apply", "scan_apply"])
+def test_rb_sequential_order_every_correction_route(mg, route):
+    """relax() hands the correction of sequential-order red-black to the first of four routes that serves the level: the windowed walk, walk
+    and correction per workgroup (k_rbseq_walk_apply), the correction inside the walk's launch, the walk and the correction as two launches.
+    One relax call of three sweeps at 32x32x8 with cmatrix='real' (level 1: 512 columns per colour -- too many for the one-workgroup
+    kernels --, half-rows of 16 columns, nz a multiple of 4) by each route this size has, against "rb_exact" from the same state: the
+    project's bound per call for this mode, 1e-12 of max|p|.  The counters say which route ran: per call one snapshot launch, then per
+    colour the pass (which leaves d0) and -- window: one launch, counted in "rbseq_window_colours"; walk_apply: one launch; scan_apply:
+    the walk and the correction, two.  (The third route has no instance for half-rows that do not fill a wave: it is what
+    test_rb_sequential_order_correction_inside_the_walk_launch and ..._fused_launch_bounded_waits run at half-rows of 256 columns.)"""
+    nx, ny, nz = 32, 32, 8
+    _setup(mg, nx, ny, nz, "seamount", relax_method="RB")
+    g = mg.grid(1)
+    if not _RB_ROUTES_REF:
+        rng = np.random.default_rng(53)
+        p0 = rng.standard_normal(g._shape("p")); b0 = rng.standard_normal(g._shape("b"))
+        g.set("p", p0); g.set("b", b0); mg.fill_halo(1, "p")
+        mg.nhydro.set_option("rb_exact", 1)
+        try:
+            mg.relax(1, 3)
+        finally:
+            mg.nhydro.set_option("rb_exact", 0)
+        _RB_ROUTES_REF.update(p0=p0, b0=b0, ref=g.get("p"))
+    p0, b0, ref = _RB_ROUTES_REF["p0"], _RB_ROUTES_REF["b0"], _RB_ROUTES_REF["ref"]
+    assert mg.nhydro.get_option("rb_seq") == 1 and mg.nhydro.get_option("rb_exact") == 0
+    window, fuse = {"window": (1, 1), "walk_apply": (0, 1), "scan_apply": (0, 0)}[route]
+    g.set("p", p0); g.set("b", b0); mg.fill_halo(1, "p")
+    try:
+        mg.nhydro.set_option("rbseq_window", window); mg.nhydro.set_option("rbseq_fuse", fuse)
+        n0 = mg.nhydro.counters()["launches"]; w0 = mg.nhydro.get_option("rbseq_window_colours")
+        mg.relax(1, 3)
+        got = g.get("p")
+        launches = mg.nhydro.counters()["launches"] - n0; windows = mg.nhydro.get_option("rbseq_window_colours") - w0
+    finally:
+        mg.nhydro.set_option("rbseq_window", 1); mg.nhydro.set_option("rbseq_fuse", 1)
+    err = np.abs(got - ref).max() / np.abs(ref).max()
+    print(f"rb_seq route {route}: {launches} launches, {windows} window colours, {err:.3e} of max|p| from rb_exact")
+    assert windows == (6 if route == "window" else 0), (route, windows)
+    assert launches == 1 + 6 * (3 if route == "scan_apply" else 2), (route, launches)
+    assert err <= 1e-12, (route, err)
+
+
 def test_rb_sequential_order_fused_launch_bounded_waits(mg):
     """The waits inside the fused walk + correction launch are bounded: with the test hook "rbseq_test_stall" the walk keeps its progress
     to itself, the forwarding waves give up after "rbseq_timeout_ms", release every word (the launch drains) and raise the error word:

@@ -215,3 +215,44 @@ def test_windowed_walk_bounds_host_logic(built):
     assert nrows([1.0] + [0.0] * 31) == 1
     assert nrows([1.0, 1e-30, float("inf"), 0.0]) == 4 and nrows([1.0, float("nan"), 0.0, 0.0]) == 4   # a figure that is not finite: no cut
     assert nrows([1.0, 1e-25, 1e-10, 1e-30]) == 3                  # (not monotone: the LAST row above the threshold counts)
+
+
+def test_ab_switches_live_in_one_table():
+    """The A/B switches are read by the one table of mgx_switches.cpp and nowhere else: under mgroms_amd/csrc `getenv(` occurs only there, in
+    options_from_env (mgx_api.cpp: the variables that preset an option), in mgx_init (mgx_define.cpp: MGX_NO_SMALL, MGX_NO_MF and
+    MGX_P2P_TIMEOUT_MS, read at every mgx_init) and in mgx_p2p_connect (mgx_comm.cpp: the test hook MGX_P2P_TEST_FAIL_CONNECT).  Every
+    variable of the table is documented in DESIGN.md, and the switches that were retired with their code have left the sources."""
+    csrc = os.path.join(ROOT, "mgroms_amd", "csrc")
+    allowed = {"mgx_switches.cpp": ("mgx_switches", None),
+               "mgx_api.cpp": ("options_from_env", None),
+               "mgx_define.cpp": ("mgx_init", {"MGX_NO_SMALL", "MGX_NO_MF", "MGX_P2P_TIMEOUT_MS"}),
+               "mgx_comm.cpp": ("mgx_p2p_connect", {"MGX_P2P_TEST_FAIL_CONNECT"})}
+    retired = ("MGX_RBSEQ_TWO_WAVES", "MGX_RBSEQ_HELPERS", "MGX_C2F_OLD", "MGX_NO_WAVE4", "MGX_NO_WAVE8", "MGX_RBW_PROBE_M", "MGX_RBW_NO_SPREAD")
+    seen = set()
+    for name in sorted(os.listdir(csrc)):
+        path = os.path.join(csrc, name)
+        if not os.path.isfile(path) or not name.endswith((".hip", ".cpp", ".h")):
+            continue
+        lines = open(path).read().split("\n")
+        for r in retired:
+            assert not any(r in ln for ln in lines), (name, r)
+        func = None    # the function a line belongs to: the last definition that started in column 0
+        for n, ln in enumerate(lines, 1):
+            m = re.match(r"[A-Za-z_][\w \*&:<>]*?\b(\w+)\(.*\{\s*$", ln)
+            if m:
+                func = m.group(1)
+            if "getenv(" not in ln:
+                continue
+            assert name in allowed, (name, n, ln.strip())
+            want_func, want_vars = allowed[name]
+            assert func == want_func, (name, n, func)
+            if want_vars is not None:
+                got = set(re.findall(r'getenv\("(\w+)"\)', ln))
+                assert got and got <= want_vars and ln.count("getenv(") == len(re.findall(r'getenv\("\w+"\)', ln)), (name, n, ln.strip())
+            seen.add(name)
+    assert seen == set(allowed), seen
+    table = re.findall(r'^\s*\{"(MGX_\w+)",\s*&Switches::\w+,', open(os.path.join(csrc, "mgx_switches.cpp")).read(), re.M)
+    assert len(table) >= 20 and len(set(table)) == len(table), table
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    documented = re.findall(r"^\| `(MGX_\w+)` \|", design, re.M)
+    assert documented == table, (documented, table)     # the same rows in the same order
