@@ -681,7 +681,9 @@ def test_compute_rhs_and_correct_uvw(mg):
 def test_bmask_bitwise(mg, dims, geom):
     """bmask=.true.: masked coefficients on every level, masked compute_rhs / correct_uvw and the
     whole solve, bit for bit against the oracle.  The reference holds no known answers for this branch, so the
-    oracle's bmask branch is itself unpinned: this test proves GPU == restatement, no more."""
+    oracle's bmask branch is itself unpinned: this test proves GPU == restatement.  That the masked matrix is the
+    divergence of the masked gradient on water-interior columns is held separately, without the oracle
+    (tests/test_gpu_operator_identity.py); coast columns, the smoother and the coarse levels of this branch have this test only."""
     from oracle.mgoracle import Oracle, seamount_geometry, rndtopo_geometry
     from mgroms_amd.testcases import island_mask
     nx, ny, nz = dims
