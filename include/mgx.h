@@ -273,6 +273,23 @@ int mgx_set_verbose(int level);
  *   "cycle_precision" = 32 is refused as before).  Refused at the first such solve like "cycle_precision" = 32 and in its words: a process
  *   grid larger than 1 x 1, relax_method = 'GS', option "rb_exact".
  *   Read-only: "krylov_mixed_iterations" (Krylov iterations run with an fp32 cycle since mgx_init); "mixed_iterations" does not count them.
+ * "periodic" (default 0; a bit mask, any value outside 0..3 is refused; survives mgx_clean): 1 = the domain wraps in the i direction (east-west,
+ *   the plane index of the solver's layout), 2 = in the j direction (north-south), 3 = both.  Read by mgx_init: set it BEFORE mgx_init; while a
+ *   solver is initialised a different value is refused (mgx_clean, set, mgx_init).  ONE RANK ONLY: with "periodic" != 0 mgx_init refuses a
+ *   process grid larger than 1 x 1.  On a periodic side of every level the rank is its own neighbour (mgx_level_info), so the side is an open
+ *   side like a rank seam: no mirror halo, no zero flux in compute_rhs, and the velocity on it is corrected.  Every halo cell in a periodic
+ *   direction of every field of every level (p, b, r; dx, dy, zeta, h; zr, zw with two halo columns; cA; the masks) is the image of the interior
+ *   cell one period away; a closed direction is what it was; a corner between a periodic and a closed side is the closed side's image of the
+ *   wrapped edge, a corner between two periodic sides wraps both ways.  Inputs: the halo entries of dx, dy, zeta, h, rmask in a periodic direction
+ *   are ignored (replaced by the wrapped interior); u, v, w come as a model hands them over after its own exchange -- halo columns in a periodic
+ *   direction hold the wrapped values and u(nx+1) = u(1) (v(ny+1) = v(1)); the duplicated faces come back equal bit for bit if they went in so.
+ *   Served: relax_method 'FC', 'RB' (the sequential order starts its walk at plane 1 and reads the wrapped image of plane nx as it was before
+ *   the pass, the rule of a rank seam) and 'GS' (the hyperplane sweep of a level with neighbours: the wrapped images are those of the sweep
+ *   before, filled once per sweep -- the rule of a rank seam too), "krylov", bmask, the per-call mask, "warm_start", the device entry points,
+ *   "async".  Refused at the solve: "cycle_precision" = 32 and "krylov_precision" = 32 (the fp32 copies have mirror halos only).  The halo fill
+ *   of a solver field is one launch (mgx_kernels.hip: k_halo_wrap) behind every colour pass; the kernels that need a closed level (the
+ *   persistent and one-workgroup relax, the restriction chain, the zeta chain, the direct coarsest solve) decline such a level, so a periodic
+ *   hierarchy runs the launches of a level with neighbours (profiles/periodic_time.json).  mgx_transport() reports the wrap.
  * Read-only through mgx_get_option: "p2p_failed" (a peer-to-peer wait of THIS rank timed out since the ranks last agreed: see below),
  *   "overlapped_passes", "tall_stored_passes" (colour passes of nz = 80, 96, 128 levels served by the stored-coefficient tall-column kernel
  *   since mgx_init: bmask, mgx_set_field(cA) or MGX_NO_MF; 0 while the matrix-free form runs or under MGX_NO_TALL). */

@@ -73,6 +73,7 @@ const Opt OPTIONS[] = {
   {"cycle_precision",     &State::cycle_precision,  nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 32 / 64 only
   {"krylov",              &State::krylov,           nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0..8 only
   {"krylov_precision",    &State::krylov_precision, nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 32 / 64 only (no preset: the table's would pass any number by)
+  {"periodic",            &State::periodic,         nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0..3 only, and not while initialised (read by mgx_init)
   // reads as off while a time-out of this solver holds (ksp_down, which mgx_clean does not carry); set: see mgx_set_option
   {"ksp",                 &State::use_ksp,          [](const State &s) { return (s.use_ksp && !s.ksp_down) ? 1 : 0; }, "MGX_NO_KSP", ENV_ZERO, RW, true},
   {"p2p",                 nullptr,                  [](const State &s) { return s.p2p_on ? 1 : 0; }, nullptr, ENV_NONE, RW, false},   // set: see mgx_set_option
@@ -420,6 +421,11 @@ int mgx_set_option(const char *name, int value) {
   if (streq(name, "cycle_precision") && value != 32 && value != 64) return fail("cycle_precision must be 64 (fp64 cycles) or 32 (fp32 cycles under fp64 refinement), got %d", value);
   if (streq(name, "krylov_precision") && value != 32 && value != 64) return fail("krylov_precision must be 64 (fp64 cycles under the Krylov loop) or 32 (fp32 cycles under it), got %d", value);
   if (streq(name, "krylov") && (value < 0 || value > 8)) return fail("krylov must be 0 (off) or 1..8 (retained direction pairs of the truncated GCR), got %d", value);
+  if (streq(name, "periodic")) {
+    if (value < 0 || value > 3) return fail("periodic must be 0 (closed), 1 (the i direction, east-west), 2 (the j direction, north-south) or 3 (both), got %d", value);
+    if (S.inited && value != S.periodic)
+      return fail("periodic = %d: the hierarchy in use was built with periodic = %d and the option takes effect at mgx_init: call mgx_clean, set it, then mgx_init", value, S.periodic);
+  }
   if (streq(name, "ksp")) { S.use_ksp = value; if (value) S.ksp_down = 0; return 0; }  // switching it on again also clears a time-out of this solver
   if (streq(name, "rbseq_timeout_ms")) { if (mgxk_set_rbseq_timeout((double)value)) return fail("rbseq_timeout_ms: could not set the device constant"); return 0; }
   if (streq(name, "ksp_timeout_ms")) { if (mgxk_set_ksp_timeout((double)value)) return fail("ksp_timeout_ms: could not set the device constant"); return 0; }
@@ -500,7 +506,7 @@ int mgx_rbseq_window_rows(int lev, int *rows) { NEED_LEV(lev); *rows = S.lev[lev
 int mgx_level_info(int lev, int *out) {
   NEED_LEV(lev);
   const Level &L = S.lev[lev - 1];
-  const int v[10] = {L.npx, L.npy, L.incx, L.incy, L.gather, L.ngx, L.ngy, L.key, L.color, 0};
+  const int v[10] = {L.npx, L.npy, L.incx, L.incy, L.gather, L.ngx, L.ngy, L.key, L.color, S.periodic};   // [9]: option "periodic" (a periodic side's neighbour is the rank itself)
   memcpy(out, v, sizeof(v)); memcpy(out + 10, L.neighb, 8 * sizeof(int));
   return 0;
 }

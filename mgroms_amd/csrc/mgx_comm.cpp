@@ -9,7 +9,22 @@ thread_local hipError_t mgx_pending_error = hipSuccess;
 namespace mgx_host {
 
 // ---- halo exchange buffers ---------------------------------------------------------------------------
-int exchange(int n, const int *peer, double *const *sb, double *const *rb, const int *cnt) {
+// dir[q] = the direction (0 S, 1 E, 2 N, 3 W, 4 SW, 5 SE, 6 NE, 7 NW) entry q was packed for.  Option "periodic": a peer that is the rank itself
+// is served here, without hooks -- what was packed for direction d is what the neighbour in direction d receives from its opposite side, so
+// it goes into the receive buffer of the entry of direction opp(d), by a device copy on the solver's stream.
+int exchange(int n, const int *peer, double *const *sb, double *const *rb, const int *cnt, const int *dir) {
+  if (S.periodic && S.nranks == 1 && n > 0) {
+    static const int opp[8] = {2, 3, 0, 1, 6, 7, 4, 5};
+    if (!dir) return fail("exchange: a local wrap (option \"periodic\") needs the directions of its entries");
+    S.n_exch++;
+    for (int q = 0; q < n; q++) {
+      int q2 = -1;
+      for (int t = 0; t < n; t++) if (dir[t] == opp[dir[q]]) q2 = t;
+      if (peer[q] != S.rank || q2 < 0 || cnt[q2] != cnt[q]) return fail("exchange: direction %d of a local wrap (option \"periodic\") has no opposite entry", dir[q]);
+      HIPCHK(hipMemcpyAsync(rb[q2], sb[q], (size_t)cnt[q] * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
+    }
+    return 0;
+  }
   if (!S.ex) return fail("a halo exchange is needed (npx*npy > 1) but mgx_set_comm was not called");
   S.n_exch++;
   if (S.ex(S.ctx, n, peer, sb, rb, cnt)) return fail("exchange callback failed%s%s", S.native_rccl ? ": " : "", S.native_rccl ? mgxr_last_error() : "");
@@ -27,14 +42,23 @@ int fill_halo_js(Level &L, double *a, bool phys_done, bool xonly) {
   S.n_halo++;
   const int *nb = L.neighb;
   const Sides ph = sides_of(L);
+  if (S.periodic) {  // every neighbour is the rank itself: the wrap, and with it the images of the closed sides where they are still due, in one launch
+    int np = 0, nself = 0;
+    for (int d = 0; d < 8; d++) if (nb[d] >= 0) { np++; nself += nb[d] == S.rank; }
+    if (np && nself == np) {
+      const int closed_rule = phys_done ? 0 : 2;
+      mgxk_halo_wrap(S.stream, &L.v, a, nb[1] >= 0 ? 1 : closed_rule, nb[0] >= 0 ? 1 : closed_rule); S.n_launch++;
+      return 0;
+    }
+  }
   if (!phys_done && any_physical(ph)) { mgxk_halo_phys(S.stream, &L.v, a, ph); S.n_launch++; }
-  int n = 0, peer[8], cnt[8], present[8];
+  int n = 0, peer[8], cnt[8], present[8], dr[8];
   double *sb[8], *rb[8];
   for (int d = 0; d < 8; d++) {
     present[d] = nb[d] >= 0;
     if (nb[d] < 0) continue;
     const int c = L.nz * ((d == 0 || d == 2) ? L.nx : ((d == 1 || d == 3) ? L.ny : 1));
-    peer[n] = nb[d]; cnt[n] = c; sb[n] = S.xbuf[d]; rb[n] = S.xbuf[8 + d]; n++;
+    peer[n] = nb[d]; cnt[n] = c; sb[n] = S.xbuf[d]; rb[n] = S.xbuf[8 + d]; dr[n] = d; n++;
   }
   int m[4] = {0, 0, 0, 0};  // mixed corners SW,SE,NE,NW: 1 = copy across the physical W/E side, 2 = across S/N (:720-743)
   bool any = false;
@@ -66,7 +90,7 @@ int fill_halo_js(Level &L, double *a, bool phys_done, bool xonly) {
     S.n_launch++; S.n_p2p++;
   } else if (n) {
     mgxk_halo_pack_all(S.stream, &L.v, a, S.xbuf, present, 0); S.n_launch++;       // all edges + corners, one launch
-    CHK(exchange(n, peer, sb, rb, cnt));
+    CHK(exchange(n, peer, sb, rb, cnt, dr));
     mgxk_halo_pack_all(S.stream, &L.v, a, S.xbuf + 8, present, 1); S.n_launch++;
     if (any) { mgxk_halo_mixed_corners(S.stream, &L.v, a, m[0], m[1], m[2], m[3]); S.n_launch++; }
   }
@@ -118,7 +142,7 @@ int rl_fill_halo(Level &L, double *a, int nzz, int nh, char c, bool xonly) {
   if (NW < 0) { if (zNW) rect(a, 0, 2, nzz, nh, ny, ny + 1, ny + nh, 1 - nh, 0); else if (N < 0 && W < 0) rect(a, 0, 0, nzz, nh, ny, ny + 1, ny + nh, 1 - nh, 0, 1, 2 * ny + 1, 1, 1); }
   }
   // phase 2: exchange with the existing neighbours
-  int n = 0, peer[8], cnt[8];
+  int n = 0, peer[8], cnt[8], dr[8];
   double *sb[8], *rb[8];
   int rr[8][4];
   for (int d = 0; d < 8; d++) {
@@ -131,11 +155,11 @@ int rl_fill_halo(Level &L, double *a, int nzz, int nh, char c, bool xonly) {
     const int count = nzz * (sj1 - sj0 + 1) * (si1 - si0 + 1);
     if ((size_t)count > S.xbuf_n) return fail("halo buffer too small");
     rect(a, S.xbuf[d], 3, nzz, nh, ny, sj0, sj1, si0, si1);
-    peer[n] = nb[d]; cnt[n] = count; sb[n] = S.xbuf[d]; rb[n] = S.xbuf[8 + d];
+    peer[n] = nb[d]; cnt[n] = count; sb[n] = S.xbuf[d]; rb[n] = S.xbuf[8 + d]; dr[n] = d;
     rr[n][0] = rj0; rr[n][1] = rj1; rr[n][2] = ri0; rr[n][3] = ri1; n++;
   }
   if (n) {
-    CHK(exchange(n, peer, sb, rb, cnt));
+    CHK(exchange(n, peer, sb, rb, cnt, dr));
     for (int q = 0; q < n; q++) rect(a, rb[q], 4, nzz, nh, ny, rr[q][0], rr[q][1], rr[q][2], rr[q][3]);
   }
   if (xonly) return 0;
@@ -347,7 +371,8 @@ int mgx_rccl_selftest(void) {
 // which transport carries the neighbour traffic right now
 const char *mgx_transport(void) {
   std::string &t = S.transport_name;
-  if (S.nranks <= 1 && !S.native_rccl) t = "none (one rank)";
+  if (S.nranks <= 1 && !S.native_rccl && S.periodic) t = std::string("none (one rank; periodic ") + (S.periodic == 1 ? "i" : S.periodic == 2 ? "j" : "ij") + ": local wrap)";
+  else if (S.nranks <= 1 && !S.native_rccl) t = "none (one rank)";
   else {
     t = S.native_rccl ? std::string("RCCL, native (") + mgxr_library() + ")" : (S.ex ? "host callbacks (mgx_set_comm)" : "none");
     if (S.p2p_on) t = "peer-to-peer pushes over hipIpc-shared buffers for the cycle's halos and gathers; " + t + " for set-up halos and the norm";

@@ -543,6 +543,7 @@ int fmalloc(float **p, size_t n) { double *q = nullptr; CHK(dmalloc(&q, (n + 1) 
 
 // the combinations the fp32 cycle does not serve
 int mixed_check() {
+  if (S.periodic) return fail("option \"periodic\" = %d is not served by the fp32 cycles (cycle_precision = 32, krylov_precision = 32): the fp32 shadow has mirror halos only", S.periodic);
   if (S.nranks > 1) return fail("cycle_precision = 32 needs a single rank (process grid %d x %d): the halo and gather callbacks carry doubles", S.npx, S.npy);
   if (S.method == M_GS) return fail("cycle_precision = 32 does not serve relax_method = 'GS' (four colours or red-black only)");
   if (S.rb_exact) return fail("cycle_precision = 32 does not serve option rb_exact (the fp32 red-black pass is the parallel one)");

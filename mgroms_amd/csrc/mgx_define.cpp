@@ -33,7 +33,9 @@ int find_grid_levels(int npxg, int npyg, int nx, int ny, int nz) {
 }
 
 // level table of an arbitrary rank (needed to form gather groups without communication)
-void rank_level_table(int rank, std::vector<Level> &T, int npx0, int npy0, int nsmall) {
+// periodic (option "periodic", one rank only): on a periodic side the neighbour is the rank itself; a corner is the rank itself where both of its
+// sides are periodic and absent otherwise (the mixed-corner rule of the halo fills then takes the closed side's image of the wrapped edge)
+void rank_level_table(int rank, std::vector<Level> &T, int npx0, int npy0, int nsmall, int periodic) {
   const int pi = rank % npx0, pj = rank / npx0;
   int nx = T[0].nx, ny = T[0].ny, nz = T[0].nz, npx = npx0, npy = npy0, incx = 1, incy = 1;
   T[0].npx = npx; T[0].npy = npy; T[0].incx = 1; T[0].incy = 1; T[0].gather = 0; T[0].ngx = 1; T[0].ngy = 1; T[0].key = 0; T[0].color = 0;
@@ -59,6 +61,9 @@ void rank_level_table(int rank, std::vector<Level> &T, int npx0, int npy0, int n
     L.neighb[5] = (pj >= iy && pi < npx0 - ix) ? (pj - iy) * npx0 + pi + ix : -1;
     L.neighb[6] = (pj < npy0 - iy && pi < npx0 - ix) ? (pj + iy) * npx0 + pi + ix : -1;
     L.neighb[7] = (pj < npy0 - iy && pi >= ix) ? (pj + iy) * npx0 + pi - ix : -1;
+    if (periodic & 1) L.neighb[1] = L.neighb[3] = rank;
+    if (periodic & 2) L.neighb[0] = L.neighb[2] = rank;
+    if ((periodic & 3) == 3) for (int c = 4; c < 8; c++) L.neighb[c] = rank;
   }
   for (int l = 1; l < (int)T.size(); l++) {  // define_gather_informations :664-738
     Level &L = T[l];
@@ -146,6 +151,12 @@ int define_matrices(int what, bool may_return_early) {
     if (all) CHK(rl_fill_halo(L, L.g.dy, 1, 1, 0));
     if (!chained) CHK(rl_fill_halo(L, L.g.zeta, 1, 1, 0));
     if (all) CHK(rl_fill_halo(L, L.g.h, 1, 1, 0));
+    // option "periodic": the caller's mask wraps like the geometry; whole rows and planes, so that a corner between a periodic and a closed side is
+    // the wrapped image of the mask the caller gave on the closed side (the closed halo of a mask is the caller's to set, never a mirror)
+    if (all && l == 0 && S.par.bmask && S.periodic) {
+      if (S.periodic & 1) { rect(L.g.rmask, 0, 0, 1, 1, L.ny, 0, L.ny + 1, 0, 0, 0, 0, 0, L.nx); rect(L.g.rmask, 0, 0, 1, 1, L.ny, 0, L.ny + 1, L.nx + 1, L.nx + 1, 0, 0, 0, -L.nx); }
+      if (S.periodic & 2) { rect(L.g.rmask, 0, 0, 1, 1, L.ny, 0, 0, 0, L.nx + 1, 0, L.ny, 0, 0); rect(L.g.rmask, 0, 0, 1, 1, L.ny, L.ny + 1, L.ny + 1, 0, L.nx + 1, 0, -L.ny, 0, 0); }
+    }
     mgxs_zr_zw(S.stream, &L.g, S.hlim, S.theta_b, S.theta_s); S.n_launch++;
     CHK(rl_fill_halo(L, L.g.zr, L.nz, 2, 0));
     CHK(rl_fill_halo(L, L.g.zw, L.nz + 1, 2, 0));
@@ -243,11 +254,11 @@ int flux_halo(Level &L, int face, double *fx) {
   if (lo < 0 && hi < 0) return 0;
   if ((size_t)cnt > S.xbuf_n) return fail("halo buffer too small");
   // the exchange callback moves equal counts both ways with every peer: the unused direction carries a zero buffer
-  int n = 0, peer[2], cn[2]; double *sb[2], *rb[2];
-  if (lo >= 0) { mgxm_flux_face_copy(S.stream, &L.g, fx, S.xbuf[0], face, 1, 0); S.n_launch++; peer[n] = lo; cn[n] = cnt; sb[n] = S.xbuf[0]; rb[n] = S.xbuf[8]; n++; }
-  if (hi >= 0) { peer[n] = hi; cn[n] = cnt; sb[n] = S.xbuf[2]; rb[n] = S.xbuf[9]; n++; }
+  int n = 0, peer[2], cn[2], dr[2]; double *sb[2], *rb[2];
+  if (lo >= 0) { mgxm_flux_face_copy(S.stream, &L.g, fx, S.xbuf[0], face, 1, 0); S.n_launch++; peer[n] = lo; cn[n] = cnt; sb[n] = S.xbuf[0]; rb[n] = S.xbuf[8]; dr[n] = face == 0 ? 3 : 0; n++; }
+  if (hi >= 0) { peer[n] = hi; cn[n] = cnt; sb[n] = S.xbuf[2]; rb[n] = S.xbuf[9]; dr[n] = face == 0 ? 1 : 2; n++; }
   if (hi >= 0) HIPCHK(hipMemsetAsync(S.xbuf[2], 0, (size_t)cnt * sizeof(double), S.stream));
-  CHK(exchange(n, peer, sb, rb, cn));
+  CHK(exchange(n, peer, sb, rb, cn, dr));
   if (hi >= 0) { mgxm_flux_face_copy(S.stream, &L.g, fx, S.xbuf[9], face, last, 1); S.n_launch++; }
   return 0;
 }
@@ -338,12 +349,14 @@ int mgx_init(int nx, int ny, int nz, int npx, int npy, int rank, const mgx_param
   if (nx < 2 || ny < 2 || nz < 2 || (nx & 1) || (ny & 1) || (nz & 1)) return fail("nx,ny,nz must be even and >= 2 (got %d %d %d)", nx, ny, nz);
   if (npx < 1 || npy < 1 || (npx & (npx - 1)) || (npy & (npy - 1))) return fail("the process grid must be powers of two in both directions (got %d x %d)", npx, npy);
   if (rank < 0 || rank >= npx * npy) return fail("rank %d outside the %d x %d process grid", rank, npx, npy);
+  if (S.periodic && npx * npy > 1)
+    return fail("option \"periodic\" = %d needs a single rank (process grid %d x %d): periodic sides on a process grid are not served", S.periodic, npx, npy);
   S.npx = npx; S.npy = npy; S.nranks = npx * npy; S.rank = rank; S.pi = rank % npx; S.pj = rank / npx;
   S.nlevs = find_grid_levels(npx, npy, nx, ny, nz);
   if (S.nlevs < 1) return fail("grid %dx%dx%d too small for a multigrid hierarchy", nx * npx, ny * npy, nz);
   S.lev.assign(S.nlevs, Level());
   S.lev[0].nx = nx; S.lev[0].ny = ny; S.lev[0].nz = nz;
-  rank_level_table(rank, S.lev, npx, npy, S.par.nsmall);
+  rank_level_table(rank, S.lev, npx, npy, S.par.nsmall, S.periodic);
   for (int l = 0; l < S.nlevs; l++) {
     const Level &L = S.lev[l];
     if ((L.nx & 1) || (L.ny & 1) || L.nz < 2) return fail("level %d has local size %dx%dx%d: odd sizes are not supported (assumptions:1-2)", l + 1, L.nx, L.ny, L.nz);

@@ -161,6 +161,10 @@ struct State {
   long long n_mixed = 0;          // read-only option "mixed_iterations": solve_p iterations run with fp32 cycles since mgx_init
   bool mx_ready = false;
   unsigned long long coef_gen = 0, mx_gen = ~0ULL;
+  // option "periodic" (0 default; bit 1 = the i direction, east-west; bit 2 = the j direction, north-south): read by mgx_init, which makes the rank
+  // its own neighbour on the periodic sides of every level (rank_level_table).  Such a side is an open side like a rank seam: every kernel
+  // reads what the last halo fill left there, and the fill is a local wrap (fill_halo_js: k_halo_wrap; exchange(): device copies).  One rank only.
+  int periodic = 0;
   int c2f_skip = 1;   // the cycles' prolongation leaves the columns alone that the first colour of the following four-colour relax overwrites unread (option "c2f_skip", MGX_C2F_NOSKIP=1)
   long long n_launch = 0, n_halo = 0, n_exch = 0, n_allred = 0;
   std::string err, transport_name;
@@ -214,7 +218,7 @@ int dmalloc(double **p, size_t n);
 int roundup(int a, int m);
 void make_view(LevView &v, int nx, int ny, int nz);
 int find_grid_levels(int npxg, int npyg, int nx, int ny, int nz);
-void rank_level_table(int rank, std::vector<Level> &T, int npx0, int npy0, int nsmall);
+void rank_level_table(int rank, std::vector<Level> &T, int npx0, int npy0, int nsmall, int periodic = 0);
 void set_window_planes(bool known = true);
 enum { DM_ALL = 0, DM_ZETA = 1 };
 int define_matrices(int what = DM_ALL, bool may_return_early = false);
@@ -224,7 +228,7 @@ int correct_uvw_dev();
 int upload_uvw(const double *u, const double *v, const double *w);
 
 // ---- mgx_comm.cpp ----
-int exchange(int n, const int *peer, double *const *sb, double *const *rb, const int *cnt);
+int exchange(int n, const int *peer, double *const *sb, double *const *rb, const int *cnt, const int *dir = nullptr);
 int fill_halo_js(Level &L, double *a, bool phys_done = false, bool xonly = false);
 void rect(double *a, double *buf, int op, int nzz, int nh, int ny, int j0, int j1, int i0, int i1, int mj = 0, int cj = 0, int mi = 0,
           int ci = 0, int mj2 = 0, int cj2 = 0, int mi2 = 0, int ci2 = 0);

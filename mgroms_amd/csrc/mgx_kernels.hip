@@ -360,6 +360,49 @@ __global__ __launch_bounds__(256) void k_halo_phys(LevView L, double *__restrict
   }
 }
 
+// Halo fill of a level whose neighbours are all the rank itself (option "periodic" on one rank): the wrap in ONE launch, plain loads and
+// stores in stream order.  im, jm: what the halo planes i = 0, nx+1 and the halo entries j = 0, ny+1 of a row become -- 0 = left as they are (a
+// closed side whose images the producing kernel stored), 1 = the interior one period away (planes nx, 1; entries ny, 1), 2 = the image of a
+// closed side that is still due (planes 1, nx; entries 1, ny: k_halo_phys's rule).
+//   blockIdx.y = 0, 1: plane 0 / nx+1 as a whole plane of nz * RS doubles, 16 bytes per lane: a streaming copy, contiguous and 128-byte aligned by
+//     the layout.  The two j-halo entries of a row are NOT taken from the source plane's halo, which this same launch may be writing (y = 2): they
+//     are formed from the source plane's interior by the rule jm, so both kinds of corner come out right whatever the order of the blocks
+//     (wrap x wrap: the diagonal cell; wrap x closed: the closed side's image of the wrapped edge).  jm = 0: copied as found (stored earlier).
+//   blockIdx.y = 2: the entries j = 0, ny+1 of every row of the planes 1..nx -- of 0..nx+1 when the halo planes are left (im = 0): their corners are
+//     then the wrap of the images an earlier kernel stored there.  Two scattered doubles per row; lanes along k, the shorter stride (RS).
+// NT: the level does not fit the Infinity Cache (level_streams): the plane copy carries the non-temporal hint like the colour pass.
+typedef double v2d __attribute__((ext_vector_type(2)));
+template <bool NT>
+__global__ __launch_bounds__(256) void k_halo_wrap(LevView L, double *__restrict__ a, int im, int jm) {
+  const int nx = L.nx, ny = L.ny;
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int c0 = jpos(L, 0), cN = jpos(L, ny + 1);                                                    // the j-halo entries of a row ...
+  const int s0 = jm == 1 ? jpos(L, ny) : jpos(L, 1), sN = jm == 1 ? jpos(L, 1) : jpos(L, ny);          // ... and their sources
+  if (blockIdx.y < 2) {
+    if (!im || 2 * t >= L.plane) return;
+    const int east = blockIdx.y;
+    const int src = im == 1 ? (east ? 1 : nx) : (east ? nx : 1), dst = east ? nx + 1 : 0;
+    const double *__restrict__ s = a + (long long)src * L.plane;
+    const long long e = 2 * t;   // (RS is a multiple of 16: a pair never straddles two rows)
+    v2d v = NT ? __builtin_nontemporal_load((const v2d *)(s + e)) : *(const v2d *)(s + e);
+    if (jm) {
+      const int c = (int)(e % L.RS);
+      const long long ro = e - c;
+      if (c == c0) v.x = s[ro + s0]; else if (c + 1 == c0) v.y = s[ro + s0];
+      if (c == cN) v.x = s[ro + sN]; else if (c + 1 == cN) v.y = s[ro + sN];
+    }
+    v2d *d = (v2d *)(a + (long long)dst * L.plane + e);
+    if (NT) __builtin_nontemporal_store(v, d); else *d = v;
+  } else {
+    if (!jm) return;
+    const int i0 = im ? 1 : 0, np = im ? nx : nx + 2;
+    if (t >= (long long)np * L.nz) return;
+    const long long o = (long long)(i0 + (int)(t / L.nz)) * L.plane + (t % L.nz) * L.RS;
+    a[o + c0] = a[o + s0];
+    a[o + cN] = a[o + sN];
+  }
+}
+
 // mixed corners, after the edge halos have been received (mg_mpi_exchange.f90:720-743).
 // mode per corner (SW,SE,NE,NW): 0 nothing, 1 copy along i from the received S/N halo row, 2 copy along j
 // from the received W/E halo plane.
@@ -721,6 +764,13 @@ void mgxk_divc_selftest(hipStream_t st, const double *a, const double *b, int n,
 void mgxk_halo_phys(hipStream_t st, const LevView *L, double *a, Sides ph) {
   const int n = L->nx + L->ny + 1;
   hipLaunchKernelGGL(k_halo_phys, dim3((n + 255) / 256, L->nz), dim3(256), 0, st, *L, a, ph);
+}
+void mgxk_halo_wrap(hipStream_t st, const LevView *L, double *a, int im, int jm) {
+  if (!im && !jm) return;
+  const long long npl = im ? (L->plane / 2 + 255) / 256 : 0, nj = jm ? ((long long)(L->nx + 2) * L->nz + 255) / 256 : 0;
+  const dim3 grd((unsigned)(npl > nj ? npl : nj), 3), blk(256);
+  if (level_streams(L)) hipLaunchKernelGGL((k_halo_wrap<true>), grd, blk, 0, st, *L, a, im, jm);
+  else hipLaunchKernelGGL((k_halo_wrap<false>), grd, blk, 0, st, *L, a, im, jm);
 }
 void mgxk_halo_mixed_corners(hipStream_t st, const LevView *L, double *a, int mSW, int mSE, int mNE, int mNW) {
   hipLaunchKernelGGL(k_halo_mixed_corners, dim3((L->nz + 63) / 64), dim3(64), 0, st, *L, a, mSW, mSE, mNE, mNW);

@@ -80,6 +80,7 @@ void mgxk_fine2coarse(hipStream_t st, const LevView *F, const LevView *C, double
 void mgxk_coarse2fine(hipStream_t st, const LevView *F, const LevView *C, const double *src, int linear, Sides ph, int keep_r, int skip1);
 void mgxk_divc_selftest(hipStream_t st, const double *a, const double *b, int n, unsigned long long *bad);
 void mgxk_halo_phys(hipStream_t st, const LevView *L, double *a, Sides ph);
+void mgxk_halo_wrap(hipStream_t st, const LevView *L, double *a, int im, int jm);
 void mgxk_halo_mixed_corners(hipStream_t st, const LevView *L, double *a, int mSW, int mSE, int mNE, int mNW);
 void mgxk_halo_pack_all(hipStream_t st, const LevView *L, double *a, double *const *bufs, const int *present, int unpack);
 void mgxk_halo_p2p(hipStream_t st, const LevView *L, double *a, double *const *rbuf, double *const *lbuf, unsigned long long *const *rflag,
