@@ -153,6 +153,16 @@ int mgx_level_info(int lev, int *out);
  * (mg_grids.f90:468-738) for any rank, usable before mgx_init and without a GPU.  out: 20 ints per level =
  * nx,ny,nz,npx,npy,incx,incy,gather,ngx,ngy,key,color, neighbours S,E,N,W,SW,SE,NE,NW.  Returns nlevs, or -1. */
 int mgx_level_table(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int maxlev, int *out);
+/* The same with option "periodic" (0..3) as an argument: the neighbours of any rank of a periodic process grid, as mgx_init will build them.
+ * periodic = 0 is mgx_level_table.  Host only. */
+int mgx_level_table_periodic(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int maxlev, int *out);
+/* The entry list of one halo exchange of `rank` whose neighbours are neighb[0..7] (S,E,N,W,SW,SE,NE,NW; -1 = none), as the library hands it to
+ * the exchange hook: entries[3t..3t+2] = peer, send direction, receive direction of entry t -- sendbuf[t] holds what was packed for the send
+ * direction, recvbuf[t] is unpacked into the halo of the receive direction; both are of one kind (S/N edge, E/W edge, corner).  For each peer
+ * the sends go in ascending direction and the receive slots in ascending order of the SENDER's direction (the opposite of the slot's).
+ * Directions whose neighbour is the rank itself are not entries: their bits are set in *self_mask (may be NULL).  Returns the number of
+ * entries (<= 8), -1 for a table no decomposition produces.  Pure host logic, usable without a GPU. */
+int mgx_exchange_plan(const int *neighb, int rank, int *entries, int *self_mask);
 /* In a multi-rank run mgx_get_field(lev, MGX_R | MGX_B, ...) is COLLECTIVE when the neighbour part of that field's halo is still
  * pending (the cycle defers the exchanges nothing reads): every rank must ask, as with mgx_fill_halo. */
 int mgx_get_field(int lev, int field, double *host);
@@ -166,7 +176,13 @@ int mgx_set_field(int lev, int field, const double *host);
  *  allreduce: in-place sum of n doubles over all ranks                          (global_sum, :1555-1571)
  *  allgather: gather `count` doubles from each of the `ng` ranks in `group` (ordered as the reference's
  *             localcomm, mg_grids.f90:702-718) into recvbuf                     (gather_3D, mg_gather.f90:126)
- * Each returns 0 on success.  Work must be enqueued on / ordered with the stream given to mgx_set_stream. */
+ * Each returns 0 on success.  Work must be enqueued on / ordered with the stream given to mgx_set_stream.
+ * CONTRACT of exchange: entries that name ONE peer are matched in list order -- the k-th send to a peer is the message that peer's k-th receive
+ * from this rank takes, on both sides.  With option "periodic" on a process grid one rank is the neighbour on several sides at once (east and
+ * west with two ranks along a periodic direction; S, SW and SE with one), the counts are equal, and any other matching is a silent swap of
+ * halos.  The library orders its lists for this rule (mgx_exchange_plan).  Kept by: torch.distributed batch_isend_irecv, MPI point-to-point
+ * with one tag (non-overtaking), the thread-rank queues, the grouped ncclSend / ncclRecv of the native transport.  The rank itself is never a
+ * peer of the list. */
 typedef int (*mgx_exchange_fn)(void *ctx, int n, const int *peer, double *const *sendbuf, double *const *recvbuf,
                                const int *count);
 typedef int (*mgx_allreduce_fn)(void *ctx, double *devbuf, int n);
@@ -275,19 +291,29 @@ int mgx_set_verbose(int level);
  *   Read-only: "krylov_mixed_iterations" (Krylov iterations run with an fp32 cycle since mgx_init); "mixed_iterations" does not count them.
  * "periodic" (default 0; a bit mask, any value outside 0..3 is refused; survives mgx_clean): 1 = the domain wraps in the i direction (east-west,
  *   the plane index of the solver's layout), 2 = in the j direction (north-south), 3 = both.  Read by mgx_init: set it BEFORE mgx_init; while a
- *   solver is initialised a different value is refused (mgx_clean, set, mgx_init).  ONE RANK ONLY: with "periodic" != 0 mgx_init refuses a
- *   process grid larger than 1 x 1.  On a periodic side of every level the rank is its own neighbour (mgx_level_info), so the side is an open
+ *   solver is initialised a different value is refused (mgx_clean, set, mgx_init).  Served on one rank and on every process grid mgx_init
+ *   takes; on a grid the hooks (mgx_set_comm, mgx_rccl_connect) must be installed BEFORE mgx_init, which refuses a periodic grid without them.  Along a periodic direction a level with ONE rank has the rank itself as neighbour (the local wrap: the un-decomposed direction of a
+ *   strip of ranks, and every fully gathered level, where each rank holds the whole periodic domain); a level with several has the rank at the
+ *   other end of the row or column, (pi +- incx) mod npx -- then one rank can be the neighbour on several sides (mgx_exchange_plan,
+ *   mgx_level_table_periodic).  Either way (mgx_level_info) the side is an open
  *   side like a rank seam: no mirror halo, no zero flux in compute_rhs, and the velocity on it is corrected.  Every halo cell in a periodic
  *   direction of every field of every level (p, b, r; dx, dy, zeta, h; zr, zw with two halo columns; cA; the masks) is the image of the interior
  *   cell one period away; a closed direction is what it was; a corner between a periodic and a closed side is the closed side's image of the
- *   wrapped edge, a corner between two periodic sides wraps both ways.  Inputs: the halo entries of dx, dy, zeta, h, rmask in a periodic direction
- *   are ignored (replaced by the wrapped interior); u, v, w come as a model hands them over after its own exchange -- halo columns in a periodic
- *   direction hold the wrapped values and u(nx+1) = u(1) (v(ny+1) = v(1)); the duplicated faces come back equal bit for bit if they went in so.
+ *   wrapped edge, a corner between two periodic sides wraps both ways.  Inputs: the halo entries of dx, dy, zeta, h, rmask ON a periodic side of the
+ *   domain are ignored (replaced by the interior one period away -- the rank's own, or that of the rank at the other end); a rank seam inside
+ *   the domain is what it was (the halo of rmask there is the caller's, cut from the global mask).  u, v, w come as a model hands them over after
+ *   its own exchange -- halo columns across a periodic side hold the values from one period away, and the face on the wrap seam is held twice:
+ *   u(nx+1) of the last rank of a row is u(1) of its first rank (on one rank, its own), likewise v(ny+1); the duplicated faces come back equal
+ *   bit for bit if they went in so.
  *   Served: relax_method 'FC', 'RB' (the sequential order starts its walk at plane 1 and reads the wrapped image of plane nx as it was before
  *   the pass, the rule of a rank seam) and 'GS' (the hyperplane sweep of a level with neighbours: the wrapped images are those of the sweep
  *   before, filled once per sweep -- the rule of a rank seam too), "krylov", bmask, the per-call mask, "warm_start", the device entry points,
- *   "async".  Refused at the solve: "cycle_precision" = 32 and "krylov_precision" = 32 (the fp32 copies have mirror halos only).  The halo fill
- *   of a solver field is one launch (mgx_kernels.hip: k_halo_wrap) behind every colour pass; the kernels that need a closed level (the
+ *   "async".  Refused at the solve, on one rank and on a grid: "cycle_precision" = 32 and "krylov_precision" = 32 (the fp32 copies have mirror
+ *   halos only); refused at the set: a change of the option under a live hierarchy.  The halo fill of a solver field is one launch behind
+ *   every colour pass: k_halo_wrap where every neighbour is the rank itself; with the pushes, k_halo_exchange on a level that has other ranks too
+ *   (a direction whose neighbour is the rank itself is a direct copy inside it: no slab, no flag); on the hooks that copy rides in the unpack
+ *   launch.  Option "overlap" = 1 runs its one-stream pass on a periodic hierarchy (same bits).  Four colours give every rank, bit for bit, its
+ *   block of the one-rank solution (tests/test_gpu_periodic_grid.py); the kernels that need a closed level (the
  *   persistent and one-workgroup relax, the restriction chain, the zeta chain, the direct coarsest solve) decline such a level, so a periodic
  *   hierarchy runs the launches of a level with neighbours (profiles/periodic_time.json).  mgx_transport() reports the wrap.
  * Read-only through mgx_get_option: "p2p_failed" (a peer-to-peer wait of THIS rank timed out since the ranks last agreed: see below),

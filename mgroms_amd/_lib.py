@@ -54,6 +54,8 @@ _SIGS = {
     "mgx_rbseq_window_rows": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
     "mgx_level_info": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
     "mgx_level_table": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int)]),
+    "mgx_level_table_periodic": (C.c_int, [C.c_int] * 9 + [C.POINTER(C.c_int)]),
+    "mgx_exchange_plan": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mgx_get_field": (C.c_int, [C.c_int, C.c_int, _DP]),
     "mgx_set_field": (C.c_int, [C.c_int, C.c_int, _DP]),
     "mgx_set_comm": (C.c_int, [EXCHANGE_FN, ALLREDUCE_FN, ALLGATHER_FN, C.c_void_p]),

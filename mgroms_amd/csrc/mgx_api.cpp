@@ -401,19 +401,32 @@ int mgx_testgalerkin(int lev, double *norm_c, double *norm_f) {
   return 0;
 }
 
-int mgx_level_table(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int maxlev, int *out) {
-  if (nx < 2 || ny < 2 || nz < 2 || npx < 1 || npy < 1 || rank < 0 || rank >= npx * npy) return -1;
+static int level_table(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int maxlev, int *out) {
+  if (nx < 2 || ny < 2 || nz < 2 || npx < 1 || npy < 1 || rank < 0 || rank >= npx * npy || periodic < 0 || periodic > 3) return -1;
   const int nl = find_grid_levels(npx, npy, nx, ny, nz);
   if (nl < 1 || nl > maxlev) return -1;
   std::vector<Level> T(nl);
   T[0].nx = nx; T[0].ny = ny; T[0].nz = nz;
-  rank_level_table(rank, T, npx, npy, nsmall);
+  rank_level_table(rank, T, npx, npy, nsmall, periodic);
   for (int l = 0; l < nl; l++) {
     const Level &L = T[l];
     const int v[12] = {L.nx, L.ny, L.nz, L.npx, L.npy, L.incx, L.incy, L.gather, L.ngx, L.ngy, L.key, L.color};
     memcpy(out + 20 * l, v, sizeof(v)); memcpy(out + 20 * l + 12, L.neighb, 8 * sizeof(int));
   }
   return nl;
+}
+int mgx_level_table(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int maxlev, int *out) {
+  return level_table(nx, ny, nz, npx, npy, rank, nsmall, 0, maxlev, out);
+}
+int mgx_level_table_periodic(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int maxlev, int *out) {
+  return level_table(nx, ny, nz, npx, npy, rank, nsmall, periodic, maxlev, out);
+}
+int mgx_exchange_plan(const int *neighb, int rank, int *entries, int *self_mask) {
+  if (!neighb || !entries) return -1;
+  XEntry pl[8];
+  const int n = exchange_plan(neighb, rank, pl, self_mask);
+  for (int t = 0; t < n; t++) { entries[3 * t] = pl[t].peer; entries[3 * t + 1] = pl[t].sd; entries[3 * t + 2] = pl[t].rd; }
+  return n;
 }
 
 int mgx_set_option(const char *name, int value) {

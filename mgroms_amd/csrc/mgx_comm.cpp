@@ -9,25 +9,76 @@ thread_local hipError_t mgx_pending_error = hipSuccess;
 namespace mgx_host {
 
 // ---- halo exchange buffers ---------------------------------------------------------------------------
-// dir[q] = the direction (0 S, 1 E, 2 N, 3 W, 4 SW, 5 SE, 6 NE, 7 NW) entry q was packed for.  Option "periodic": a peer that is the rank itself
-// is served here, without hooks -- what was packed for direction d is what the neighbour in direction d receives from its opposite side, so
-// it goes into the receive buffer of the entry of direction opp(d), by a device copy on the solver's stream.
-int exchange(int n, const int *peer, double *const *sb, double *const *rb, const int *cnt, const int *dir) {
-  if (S.periodic && S.nranks == 1 && n > 0) {
-    static const int opp[8] = {2, 3, 0, 1, 6, 7, 4, 5};
-    if (!dir) return fail("exchange: a local wrap (option \"periodic\") needs the directions of its entries");
-    S.n_exch++;
-    for (int q = 0; q < n; q++) {
-      int q2 = -1;
-      for (int t = 0; t < n; t++) if (dir[t] == opp[dir[q]]) q2 = t;
-      if (peer[q] != S.rank || q2 < 0 || cnt[q2] != cnt[q]) return fail("exchange: direction %d of a local wrap (option \"periodic\") has no opposite entry", dir[q]);
-      HIPCHK(hipMemcpyAsync(rb[q2], sb[q], (size_t)cnt[q] * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
+// The entry list of one exchange, from the neighbour table of the level (0 S, 1 E, 2 N, 3 W, 4 SW, 5 SE, 6 NE, 7 NW; -1 = no neighbour).  Pure.
+// Every transport behind mgx_set_comm matches the messages of one pair of ranks in list order, and with option "periodic" on a process grid one rank
+// can be the neighbour on several sides at once (two ranks along a periodic direction: east and west; one rank along it: S, SW and SE; a doubly
+// periodic 2 x 2 grid: all four corners).  So for each peer the sends go in ascending direction d, and the receive slots in ascending order of the
+// SENDER's direction opp(e): the k-th message a peer sends is the one this rank expects k-th, and what was packed for d lands in slot opp(d) over
+// there.  Entries are listed by ascending send direction, which for distinct peers is the plain direction order.  A direction whose peer is the
+// rank itself is not an entry: its bit is set in *self_mask (exchange() serves it by a device copy).  The two directions of an entry are of one kind
+// (S/N edge, E/W edge, corner), so one count serves both.  Returns the number of entries, -1 for a table no decomposition produces.
+int exchange_plan(const int *neighb, int rank, XEntry *out, int *self_mask) {
+  static const int opp[8] = {2, 3, 0, 1, 6, 7, 4, 5};
+  auto kind = [](int d) { return d >= 4 ? 2 : (d & 1); };
+  int n = 0, self = 0;
+  for (int d = 0; d < 8; d++) {
+    if (neighb[d] < 0) continue;
+    if (neighb[d] == rank) { self |= 1 << d; continue; }
+    // the receive slot: among the slots of this peer, the one whose sender's direction has the rank this send has among the sends to the peer
+    int k = 0, rd = -1;
+    for (int t = 0; t < d; t++) k += neighb[t] == neighb[d];
+    for (int f = 0; f < 8 && rd < 0; f++) {   // f = opp(e) ascending
+      const int e = opp[f];
+      if (neighb[e] != neighb[d]) continue;
+      if (k-- == 0) rd = e;
     }
+    if (rd < 0 || kind(rd) != kind(d)) return -1;
+    out[n].peer = neighb[d]; out[n].sd = d; out[n].rd = rd; n++;
+  }
+  for (int d = 0; d < 8; d++) if ((self >> d & 1) && !(self >> opp[d] & 1)) return -1;   // a wrap has both of its ends here
+  if (self_mask) *self_mask = self;
+  return n;
+}
+
+// dir[q] = the direction entry q was packed for: sb[q] holds what the neighbour in that direction needs, rb[q] is where the halo of that side is
+// unpacked from.  The entries go through exchange_plan(): a peer that is the rank itself (option "periodic", one rank along the direction) is served
+// here, without hooks -- what was packed for direction d is what the neighbour in direction d receives from its opposite side, so it goes into the
+// receive buffer of the entry of direction opp(d), by a device copy on the solver's stream; the others are handed to the hook in the plan's order.
+// dir == nullptr (the self-test of the native transport): the list as given.
+int exchange(int n, const int *peer, double *const *sb, double *const *rb, const int *cnt, const int *dir) {
+  if (!dir) {
+    if (S.periodic && S.nranks == 1 && n > 0) return fail("exchange: a local wrap (option \"periodic\") needs the directions of its entries");
+    if (!S.ex) return fail("a halo exchange is needed (npx*npy > 1) but mgx_set_comm was not called");
+    S.n_exch++;
+    if (S.ex(S.ctx, n, peer, sb, rb, cnt)) return fail("exchange callback failed%s%s", S.native_rccl ? ": " : "", S.native_rccl ? mgxr_last_error() : "");
     return 0;
   }
-  if (!S.ex) return fail("a halo exchange is needed (npx*npy > 1) but mgx_set_comm was not called");
-  S.n_exch++;
-  if (S.ex(S.ctx, n, peer, sb, rb, cnt)) return fail("exchange callback failed%s%s", S.native_rccl ? ": " : "", S.native_rccl ? mgxr_last_error() : "");
+  static const int opp[8] = {2, 3, 0, 1, 6, 7, 4, 5};
+  int nbv[8], qof[8], self = 0;
+  for (int d = 0; d < 8; d++) nbv[d] = qof[d] = -1;
+  for (int q = 0; q < n; q++) {
+    if (dir[q] < 0 || dir[q] > 7 || qof[dir[q]] >= 0 || peer[q] < 0) return fail("exchange: entry %d names direction %d", q, dir[q]);
+    nbv[dir[q]] = peer[q]; qof[dir[q]] = q;
+  }
+  XEntry pl[8];
+  const int nh = exchange_plan(nbv, S.rank, pl, &self);
+  if (nh < 0) return fail("exchange: the entries of rank %d have no matching order (a wrap without its opposite side, or one peer on sides of two kinds)", S.rank);
+  if (nh && !S.ex) return fail("a halo exchange is needed (npx*npy > 1) but mgx_set_comm was not called");
+  if (n > 0) S.n_exch++;
+  for (int d = 0; d < 8; d++) {
+    if (!(self >> d & 1)) continue;
+    const int q = qof[d], q2 = qof[opp[d]];
+    if (cnt[q2] != cnt[q]) return fail("exchange: direction %d of a local wrap (option \"periodic\") has no opposite entry of its size", d);
+    HIPCHK(hipMemcpyAsync(rb[q2], sb[q], (size_t)cnt[q] * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
+  }
+  if (!nh) return 0;
+  int hp[8], hc[8]; double *hs[8], *hr[8];
+  for (int t = 0; t < nh; t++) {
+    const int qs = qof[pl[t].sd], qr = qof[pl[t].rd];
+    if (cnt[qs] != cnt[qr]) return fail("exchange: directions %d and %d of peer %d differ in size", pl[t].sd, pl[t].rd, pl[t].peer);
+    hp[t] = pl[t].peer; hc[t] = cnt[qs]; hs[t] = sb[qs]; hr[t] = rb[qr];
+  }
+  if (S.ex(S.ctx, nh, hp, hs, hr, hc)) return fail("exchange callback failed%s%s", S.native_rccl ? ": " : "", S.native_rccl ? mgxr_last_error() : "");
   return 0;
 }
 
@@ -42,27 +93,29 @@ int fill_halo_js(Level &L, double *a, bool phys_done, bool xonly) {
   S.n_halo++;
   const int *nb = L.neighb;
   const Sides ph = sides_of(L);
-  if (S.periodic) {  // every neighbour is the rank itself: the wrap, and with it the images of the closed sides where they are still due, in one launch
-    int np = 0, nself = 0;
-    for (int d = 0; d < 8; d++) if (nb[d] >= 0) { np++; nself += nb[d] == S.rank; }
-    if (np && nself == np) {
-      const int closed_rule = phys_done ? 0 : 2;
-      mgxk_halo_wrap(S.stream, &L.v, a, nb[1] >= 0 ? 1 : closed_rule, nb[0] >= 0 ? 1 : closed_rule); S.n_launch++;
-      return 0;
-    }
+  int np = 0, nself = 0;
+  for (int d = 0; d < 8; d++) if (nb[d] >= 0) { np++; nself += nb[d] == S.rank; }
+  if (np && nself == np) {  // every neighbour is the rank itself: the wrap, and with it the images of the closed sides where they are still due, in one launch
+    const int closed_rule = phys_done ? 0 : 2;
+    mgxk_halo_wrap(S.stream, &L.v, a, nb[1] >= 0 ? 1 : closed_rule, nb[0] >= 0 ? 1 : closed_rule); S.n_launch++;
+    return 0;
   }
-  if (!phys_done && any_physical(ph)) { mgxk_halo_phys(S.stream, &L.v, a, ph); S.n_launch++; }
-  int n = 0, peer[8], cnt[8], present[8], dr[8];
+  // A mixed level (option "periodic" on a strip of ranks: the wrap is local in one direction, the other has real peers): a self direction takes no
+  // slab, flag or hook entry -- the kernel that unpacks copies its halo from the interior the opposite side would have packed.  On the push path the
+  // images of the closed sides that are still due ride in the same launch (a mixed level has no corner between two closed sides).
+  const bool push = np && S.p2p_on, fold = push && nself > 0;
+  if (!phys_done && any_physical(ph) && !fold) { mgxk_halo_phys(S.stream, &L.v, a, ph); S.n_launch++; }
+  int n = 0, peer[8], cnt[8], present[8], dr[8];   // present: 0 no neighbour, 1 another rank, 2 the rank itself, 3 a closed side whose image is due (HALO_* of mgx_wrappers.h)
   double *sb[8], *rb[8];
   for (int d = 0; d < 8; d++) {
-    present[d] = nb[d] >= 0;
-    if (nb[d] < 0) continue;
+    present[d] = nb[d] < 0 ? ((fold && !phys_done && d < 4) ? HALO_MIRROR : HALO_NONE) : (nb[d] == S.rank ? HALO_SELF : HALO_PEER);
+    if (present[d] != HALO_PEER) continue;
     const int c = L.nz * ((d == 0 || d == 2) ? L.nx : ((d == 1 || d == 3) ? L.ny : 1));
     peer[n] = nb[d]; cnt[n] = c; sb[n] = S.xbuf[d]; rb[n] = S.xbuf[8 + d]; dr[n] = d; n++;
   }
   int m[4] = {0, 0, 0, 0};  // mixed corners SW,SE,NE,NW: 1 = copy across the physical W/E side, 2 = across S/N (:720-743)
   bool any = false;
-  if (n) {
+  if (np) {
     const int side1[4] = {0, 0, 2, 2}, side2[4] = {3, 1, 1, 3};  // SW:(S,W) SE:(S,E) NE:(N,E) NW:(N,W)
     for (int c = 0; c < 4; c++) {
       if (nb[4 + c] < 0) { if (nb[side1[c]] >= 0) m[c] = 1; else if (nb[side2[c]] >= 0) m[c] = 2; }
@@ -70,7 +123,7 @@ int fill_halo_js(Level &L, double *a, bool phys_done, bool xonly) {
       any |= m[c] != 0;
     }
   }
-  if (n && S.p2p_on) {  // push into the neighbours' receive buffers over xGMI, then wait on the local flags: no host step
+  if (push) {  // push into the neighbours' receive buffers over xGMI, then wait on the local flags: no host step
     static const int opp[8] = {2, 3, 0, 1, 6, 7, 4, 5};
     const unsigned long long seq = ++L.p2p_seq;
     const int par = (int)(seq & 1), li = (int)(&L - &S.lev[0]);
@@ -78,7 +131,7 @@ int fill_halo_js(Level &L, double *a, bool phys_done, bool xonly) {
     unsigned long long *rflag[8], *lflag[8];
     for (int d = 0; d < 8; d++) {
       rbuf[d] = lbuf[d] = nullptr; rflag[d] = lflag[d] = nullptr;
-      if (nb[d] < 0) continue;
+      if (present[d] != HALO_PEER) continue;
       rbuf[d] = S.peer_slab[nb[d]] + L.p2p_off[opp[d]][par];
       rflag[d] = S.peer_flags[nb[d]] + (li * 8 + opp[d]) * 2 + par;
       lbuf[d] = S.p2p_slab + L.p2p_off[d][par];
@@ -88,7 +141,7 @@ int fill_halo_js(Level &L, double *a, bool phys_done, bool xonly) {
     if (S.p2p_test_drop > 0 && --S.p2p_test_drop == 0) drop = 1;
     mgxk_halo_p2p(S.stream, &L.v, a, rbuf, lbuf, rflag, lflag, present, seq, S.p2p_counter, S.p2p_err, m, drop);  // push, wait, unpack, mixed corners
     S.n_launch++; S.n_p2p++;
-  } else if (n) {
+  } else if (np) {
     mgxk_halo_pack_all(S.stream, &L.v, a, S.xbuf, present, 0); S.n_launch++;       // all edges + corners, one launch
     CHK(exchange(n, peer, sb, rb, cnt, dr));
     mgxk_halo_pack_all(S.stream, &L.v, a, S.xbuf + 8, present, 1); S.n_launch++;
@@ -371,11 +424,13 @@ int mgx_rccl_selftest(void) {
 // which transport carries the neighbour traffic right now
 const char *mgx_transport(void) {
   std::string &t = S.transport_name;
-  if (S.nranks <= 1 && !S.native_rccl && S.periodic) t = std::string("none (one rank; periodic ") + (S.periodic == 1 ? "i" : S.periodic == 2 ? "j" : "ij") + ": local wrap)";
+  const std::string per = S.periodic == 1 ? "i" : S.periodic == 2 ? "j" : "ij";
+  if (S.nranks <= 1 && !S.native_rccl && S.periodic) t = "none (one rank; periodic " + per + ": local wrap)";
   else if (S.nranks <= 1 && !S.native_rccl) t = "none (one rank)";
   else {
     t = S.native_rccl ? std::string("RCCL, native (") + mgxr_library() + ")" : (S.ex ? "host callbacks (mgx_set_comm)" : "none");
     if (S.p2p_on) t = "peer-to-peer pushes over hipIpc-shared buffers for the cycle's halos and gathers; " + t + " for set-up halos and the norm";
+    if (S.periodic) t += "; periodic " + per + ": the wrap crosses ranks like a rank seam where a level has several ranks along the direction, local wrap where it has one";
   }
   return t.c_str();
 }

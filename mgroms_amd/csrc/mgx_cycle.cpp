@@ -160,7 +160,8 @@ int relax_fc_overlapped(Level &L, int fc1, int fc2, Sides ph) {
 // four colours (mg_relax.f90:193-234), one launch per colour -- or per colour pair, or two beside the exchange
 int relax_fc(Level &L, int nsweeps, Sides ph) {
   const bool closed = all_physical(ph);
-  const bool ov = S.overlap && S.p2p_on && S.stream2 && !closed && mgxk_has_reg_kernel(&L.v);
+  // (option "periodic": every level then has a periodic side, whose fill may be a local copy with no exchange to hide -- such a level takes the one-stream pass, same bits)
+  const bool ov = S.overlap && S.p2p_on && S.stream2 && !closed && !S.periodic && mgxk_has_reg_kernel(&L.v);
   for (int it = 1; it <= nsweeps; it++)
     for (int fc1 = 1; fc1 <= 2; fc1++) {
       // closed mid levels: the two colours of a plane set in one launch (mgx_relax_ks.hip)

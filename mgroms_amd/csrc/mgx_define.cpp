@@ -33,8 +33,9 @@ int find_grid_levels(int npxg, int npyg, int nx, int ny, int nz) {
 }
 
 // level table of an arbitrary rank (needed to form gather groups without communication)
-// periodic (option "periodic", one rank only): on a periodic side the neighbour is the rank itself; a corner is the rank itself where both of its
-// sides are periodic and absent otherwise (the mixed-corner rule of the halo fills then takes the closed side's image of the wrapped edge)
+// periodic (option "periodic"): one step of the level past the last column of a periodic i direction wraps to column (pi +- incx) mod npx0 of the same
+// row -- the rank's own column on a level with one rank along i -- and likewise in j; a corner exists exactly where both of its steps resolve, so
+// between a periodic and a closed side it is absent (the mixed-corner rule of the halo fills then takes the closed side's image of the wrapped edge)
 void rank_level_table(int rank, std::vector<Level> &T, int npx0, int npy0, int nsmall, int periodic) {
   const int pi = rank % npx0, pj = rank / npx0;
   int nx = T[0].nx, ny = T[0].ny, nz = T[0].nz, npx = npx0, npy = npy0, incx = 1, incy = 1;
@@ -53,17 +54,13 @@ void rank_level_table(int rank, std::vector<Level> &T, int npx0, int npy0, int n
   }
   for (auto &L : T) {  // define_neighbours :580-661
     const int ix = L.incx, iy = L.incy;
-    L.neighb[0] = (pj >= iy) ? (pj - iy) * npx0 + pi : -1;
-    L.neighb[1] = (pi < npx0 - ix) ? pj * npx0 + pi + ix : -1;
-    L.neighb[2] = (pj < npy0 - iy) ? (pj + iy) * npx0 + pi : -1;
-    L.neighb[3] = (pi >= ix) ? pj * npx0 + pi - ix : -1;
-    L.neighb[4] = (pj >= iy && pi >= ix) ? (pj - iy) * npx0 + pi - ix : -1;
-    L.neighb[5] = (pj >= iy && pi < npx0 - ix) ? (pj - iy) * npx0 + pi + ix : -1;
-    L.neighb[6] = (pj < npy0 - iy && pi < npx0 - ix) ? (pj + iy) * npx0 + pi + ix : -1;
-    L.neighb[7] = (pj < npy0 - iy && pi >= ix) ? (pj + iy) * npx0 + pi - ix : -1;
-    if (periodic & 1) L.neighb[1] = L.neighb[3] = rank;
-    if (periodic & 2) L.neighb[0] = L.neighb[2] = rank;
-    if ((periodic & 3) == 3) for (int c = 4; c < 8; c++) L.neighb[c] = rank;
+    auto col = [&](int s) { const int t = pi + s * ix; return (t >= 0 && t < npx0) ? t : ((periodic & 1) ? ((t % npx0) + npx0) % npx0 : -1); };
+    auto row = [&](int s) { const int t = pj + s * iy; return (t >= 0 && t < npy0) ? t : ((periodic & 2) ? ((t % npy0) + npy0) % npy0 : -1); };
+    static const int di[8] = {0, 1, 0, -1, -1, 1, 1, -1}, dj[8] = {-1, 0, 1, 0, -1, -1, 1, 1};  // S,E,N,W,SW,SE,NE,NW
+    for (int d = 0; d < 8; d++) {
+      const int c = col(di[d]), r = row(dj[d]);
+      L.neighb[d] = (c >= 0 && r >= 0) ? r * npx0 + c : -1;
+    }
   }
   for (int l = 1; l < (int)T.size(); l++) {  // define_gather_informations :664-738
     Level &L = T[l];
@@ -122,6 +119,29 @@ static bool zeta_chain() {
   return true;
 }
 
+// The level-1 mask across the periodic sides: first the i direction, whole planes (j = 0..ny+1 as they stand), then the j direction, whole rows
+// (i = 0..nx+1, the planes just wrapped included) -- the order that makes the result the one-rank array on every process grid.  Only the sides ON the
+// wrap seam are replaced (the first and last rank of a row or column; a rank seam inside the domain keeps the halo the caller gave): by the
+// interior of the rank at the other end, through exchange(), which serves a rank that is its own neighbour by device copies.
+static int wrap_rmask(Level &L) {
+  for (int ax = 0; ax < 2; ax++) {
+    if (!(S.periodic & (1 << ax))) continue;
+    const int lo = ax == 0 ? 3 : 0, hi = ax == 0 ? 1 : 2;                                    // W,E or S,N
+    const bool first = ax == 0 ? S.pi == 0 : S.pj == 0, last = ax == 0 ? S.pi == S.npx - 1 : S.pj == S.npy - 1;
+    const int nn = ax == 0 ? L.nx : L.ny, cnt = (ax == 0 ? L.ny : L.nx) + 2;
+    if ((size_t)cnt > S.xbuf_n) return fail("halo buffer too small");
+    auto line = [&](double *buf, int op, int c) { if (ax == 0) rect(L.g.rmask, buf, op, 1, 1, L.ny, 0, L.ny + 1, c, c); else rect(L.g.rmask, buf, op, 1, 1, L.ny, c, c, 0, L.nx + 1); };
+    int n = 0, peer[2], cn[2], dr[2]; double *sb[2], *rb[2];
+    if (first) { line(S.xbuf[lo], 3, 1); peer[n] = L.neighb[lo]; cn[n] = cnt; sb[n] = S.xbuf[lo]; rb[n] = S.xbuf[8 + lo]; dr[n] = lo; n++; }
+    if (last) { line(S.xbuf[hi], 3, nn); peer[n] = L.neighb[hi]; cn[n] = cnt; sb[n] = S.xbuf[hi]; rb[n] = S.xbuf[8 + hi]; dr[n] = hi; n++; }
+    if (!n) continue;
+    CHK(exchange(n, peer, sb, rb, cn, dr));
+    if (first) line(S.xbuf[8 + lo], 4, 0);
+    if (last) line(S.xbuf[8 + hi], 4, nn + 1);
+  }
+  return 0;
+}
+
 // what = DM_ALL: the level-1 dx, dy, zeta, h (and rmask) are new (mgx_matrices, mgx_matrices_device).  what = DM_ZETA: only the level-1 zeta is
 // (mgx_update_zeta_device) -- dx, dy, h of every level, their halos, the coarse masks, the sigma tables, the 2-D factors of k_zw_js and the
 // model-space copies of dx, dy, rmask are what the last DM_ALL left and stay; everything zeta reaches is rebuilt by the same kernels in the
@@ -153,10 +173,7 @@ int define_matrices(int what, bool may_return_early) {
     if (all) CHK(rl_fill_halo(L, L.g.h, 1, 1, 0));
     // option "periodic": the caller's mask wraps like the geometry; whole rows and planes, so that a corner between a periodic and a closed side is
     // the wrapped image of the mask the caller gave on the closed side (the closed halo of a mask is the caller's to set, never a mirror)
-    if (all && l == 0 && S.par.bmask && S.periodic) {
-      if (S.periodic & 1) { rect(L.g.rmask, 0, 0, 1, 1, L.ny, 0, L.ny + 1, 0, 0, 0, 0, 0, L.nx); rect(L.g.rmask, 0, 0, 1, 1, L.ny, 0, L.ny + 1, L.nx + 1, L.nx + 1, 0, 0, 0, -L.nx); }
-      if (S.periodic & 2) { rect(L.g.rmask, 0, 0, 1, 1, L.ny, 0, 0, 0, L.nx + 1, 0, L.ny, 0, 0); rect(L.g.rmask, 0, 0, 1, 1, L.ny, L.ny + 1, L.ny + 1, 0, L.nx + 1, 0, -L.ny, 0, 0); }
-    }
+    if (all && l == 0 && S.par.bmask && S.periodic) CHK(wrap_rmask(L));
     mgxs_zr_zw(S.stream, &L.g, S.hlim, S.theta_b, S.theta_s); S.n_launch++;
     CHK(rl_fill_halo(L, L.g.zr, L.nz, 2, 0));
     CHK(rl_fill_halo(L, L.g.zw, L.nz + 1, 2, 0));
@@ -349,8 +366,10 @@ int mgx_init(int nx, int ny, int nz, int npx, int npy, int rank, const mgx_param
   if (nx < 2 || ny < 2 || nz < 2 || (nx & 1) || (ny & 1) || (nz & 1)) return fail("nx,ny,nz must be even and >= 2 (got %d %d %d)", nx, ny, nz);
   if (npx < 1 || npy < 1 || (npx & (npx - 1)) || (npy & (npy - 1))) return fail("the process grid must be powers of two in both directions (got %d x %d)", npx, npy);
   if (rank < 0 || rank >= npx * npy) return fail("rank %d outside the %d x %d process grid", rank, npx, npy);
-  if (S.periodic && npx * npy > 1)
-    return fail("option \"periodic\" = %d needs a single rank (process grid %d x %d): periodic sides on a process grid are not served", S.periodic, npx, npy);
+  // a periodic process grid is served through the transports of a rank seam: unlike a closed grid, whose first exchange reports missing hooks,
+  // it is refused here, before anything is built, while the ranks are not connected
+  if (S.periodic && npx * npy > 1 && !S.ex)
+    return fail("option \"periodic\" = %d needs a single rank (process grid %d x %d) or connected ranks: install the hooks (mgx_set_comm, mgx_rccl_connect) before mgx_init", S.periodic, npx, npy);
   S.npx = npx; S.npy = npy; S.nranks = npx * npy; S.rank = rank; S.pi = rank % npx; S.pj = rank / npx;
   S.nlevs = find_grid_levels(npx, npy, nx, ny, nz);
   if (S.nlevs < 1) return fail("grid %dx%dx%d too small for a multigrid hierarchy", nx * npx, ny * npy, nz);

@@ -163,7 +163,10 @@ struct State {
   unsigned long long coef_gen = 0, mx_gen = ~0ULL;
   // option "periodic" (0 default; bit 1 = the i direction, east-west; bit 2 = the j direction, north-south): read by mgx_init, which makes the rank
   // its own neighbour on the periodic sides of every level (rank_level_table).  Such a side is an open side like a rank seam: every kernel
-  // reads what the last halo fill left there, and the fill is a local wrap (fill_halo_js: k_halo_wrap; exchange(): device copies).  One rank only.
+  // reads what the last halo fill left there.  Where the level has one rank along the direction the neighbour is the rank itself and the fill a local
+  // wrap (fill_halo_js: k_halo_wrap, or the direct copies of k_halo_exchange / k_halo_pack_all on a level that also has other ranks as neighbours;
+  // exchange(): device copies); where it has more, the neighbour is the rank at the other end of the row or column and the fill the exchange of a
+  // rank seam.  One rank is then the neighbour on several sides at once: exchange_plan() orders the entries of such a peer.
   int periodic = 0;
   int c2f_skip = 1;   // the cycles' prolongation leaves the columns alone that the first colour of the following four-colour relax overwrites unread (option "c2f_skip", MGX_C2F_NOSKIP=1)
   long long n_launch = 0, n_halo = 0, n_exch = 0, n_allred = 0;
@@ -228,6 +231,8 @@ int correct_uvw_dev();
 int upload_uvw(const double *u, const double *v, const double *w);
 
 // ---- mgx_comm.cpp ----
+struct XEntry { int peer, sd, rd; };   // one message pair of an exchange: what was packed for direction sd goes to peer, what peer sends lands in the halo of direction rd
+int exchange_plan(const int *neighb, int rank, XEntry *out, int *self_mask);
 int exchange(int n, const int *peer, double *const *sb, double *const *rb, const int *cnt, const int *dir = nullptr);
 int fill_halo_js(Level &L, double *a, bool phys_done = false, bool xonly = false);
 void rect(double *a, double *buf, int op, int nzz, int nh, int ny, int j0, int j1, int i0, int i1, int mj = 0, int cj = 0, int mi = 0,

@@ -443,11 +443,23 @@ __device__ __forceinline__ bool halo_elem(const LevView &L, int dir, int q, int 
   t = (long long)k * n + q;
   return true;
 }
+// present[dir] = HALO_SELF (option "periodic": the neighbour in this direction is the rank itself, on a level that has other ranks as neighbours too):
+// nothing is packed; the unpack launch assigns halo element (dir, q, k) the interior element that halo_elem packs for the opposite direction.
+__device__ __forceinline__ int halo_opp(int d) { return d < 4 ? (d ^ 2) : 4 + ((d - 4) ^ 2); }
+// MIXED = false (no self direction: every level of a closed grid) is the kernel as it was before the option existed.
+template <bool MIXED>
 __global__ void k_halo_pack_all(LevView L, double *__restrict__ a, HaloBufs hb, int unpack) {
-  const int dir = blockIdx.z;
-  if (!hb.present[dir]) return;
+  const int dir = blockIdx.z, pr = hb.present[dir];
+  if (MIXED ? (pr != HALO_PEER && !(pr == HALO_SELF && unpack)) : !pr) return;
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
   long long e, t;
-  if (!halo_elem(L, dir, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y, unpack, e, t)) return;
+  if (!halo_elem(L, dir, q, blockIdx.y, unpack, e, t)) return;
+  if (MIXED && pr == HALO_SELF) {
+    long long es, ts;
+    halo_elem(L, halo_opp(dir), q, blockIdx.y, 0, es, ts);
+    a[e] = a[es];
+    return;
+  }
   double *__restrict__ buf = hb.b[dir];
   if (unpack) a[e] = buf[t]; else buf[t] = a[e];
 }
@@ -469,6 +481,7 @@ struct HaloP2P {
   int mSW, mSE, mNE, mNW;       // unpack: mixed corners (one side physical, the other a neighbour), see k_halo_mixed_corners
   int blk0[9];                  // compact 1-D grid: blocks blk0[d] .. blk0[d+1]-1 serve direction d (empty when absent)
   int ipt;                      // items per thread (> 1 only for very long edges: keeps the grid within what is resident)
+  int nreal;                    // blocks that serve a real peer: the ones that push, report in and wait
 };
 // item w of direction d is buffer element w = k*n_d + q: consecutive lanes = consecutive buffer elements
 __device__ __forceinline__ int halo_dir(const HaloP2P &pp) {
@@ -490,9 +503,36 @@ __device__ __forceinline__ bool halo_item(const LevView &L, const HaloP2P &pp, i
 // directions only, several items per thread on long edges), well below what the GPU keeps resident, so a block that
 // spins never keeps a pushing block from starting; should that ever fail the 5 s time-out turns it into an error.
 struct HaloXchg { double *rbuf[8]; double *lbuf[8]; unsigned long long *rflag[8]; unsigned long long *lflag[8]; int present[8]; };
+// hx.present[d] = HALO_SELF / HALO_MIRROR (a mixed level of option "periodic": the wrap is local in one direction, the other has real peers): the
+// blocks of such a direction take no part in the protocol -- no slab, no counter, no flag raised or waited on.  They assign halo element (d, q, k)
+// the interior element that halo_elem packs for opp(d) (the rank is its own neighbour) or for d (the image of a closed side), with the same
+// mixed-corner stores, and return.  Every halo cell is written from interior cells only, so the directions need no order among them.
+__device__ __forceinline__ void halo_store(const LevView &L, const HaloP2P &pp, double *__restrict__ a, int dir, int q, int k, long long e, double v) {
+  const int nx = L.nx, ny = L.ny;
+  a[e] = v;
+  // mixed corners (mg_mpi_exchange.f90:720-743): the corner next to a physical side mirrors the edge halo cell that was
+  // just received -- written here by the thread that unpacked that cell instead of a separate launch
+  const long long ro = (long long)k * L.RS, W0 = ro, E0 = (long long)(nx + 1) * L.plane + ro;
+  if (dir == 0) { if (q == 0 && pp.mSW == 1) a[W0 + jpos(L, 0)] = v; if (q == nx - 1 && pp.mSE == 1) a[E0 + jpos(L, 0)] = v; }
+  else if (dir == 2) { if (q == 0 && pp.mNW == 1) a[W0 + jpos(L, ny + 1)] = v; if (q == nx - 1 && pp.mNE == 1) a[E0 + jpos(L, ny + 1)] = v; }
+  else if (dir == 3) { if (q == 0 && pp.mSW == 2) a[W0 + jpos(L, 0)] = v; if (q == ny - 1 && pp.mNW == 2) a[W0 + jpos(L, ny + 1)] = v; }
+  else if (dir == 1) { if (q == 0 && pp.mSE == 2) a[E0 + jpos(L, 0)] = v; if (q == ny - 1 && pp.mNE == 2) a[E0 + jpos(L, ny + 1)] = v; }
+}
+// MIXED = false (every present direction is another rank: every level of a closed grid) is the kernel as it was before the option existed.
+template <bool MIXED>
 __global__ __launch_bounds__(256) void k_halo_exchange(LevView L, double *__restrict__ a, HaloXchg hx, HaloP2P pp) {
   const int dir = halo_dir(pp);  // block-uniform
   int q, k; long long e, t;
+  if (MIXED && hx.present[dir] != HALO_PEER) {  // block-uniform: the rank itself, or a closed side's image
+    const int sdir = hx.present[dir] == HALO_SELF ? halo_opp(dir) : dir;
+    for (int r = 0; r < pp.ipt; r++) {
+      if (!halo_item(L, pp, dir, r, 1, q, k, e, t)) continue;
+      long long es, ts;
+      halo_elem(L, sdir, q, k, 0, es, ts);
+      halo_store(L, pp, a, dir, q, k, e, a[es]);
+    }
+    return;
+  }
   for (int r = 0; r < pp.ipt; r++)
     if (halo_item(L, pp, dir, r, 0, q, k, e, t)) hx.rbuf[dir][t] = a[e];
   // every storing wave drains its remote writes, the block meets, ONE lane issues the system-scope release before the block reports in
@@ -503,11 +543,11 @@ __global__ __launch_bounds__(256) void k_halo_exchange(LevView L, double *__rest
   if (threadIdx.x == 0) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (__hip_atomic_fetch_add(pp.counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
+    if (__hip_atomic_fetch_add(pp.counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (MIXED ? (unsigned int)pp.nreal : gridDim.x) - 1) {
       __hip_atomic_store(pp.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __threadfence_system();
       for (int d = 0; d < 8; d++)
-        if (hx.present[d] && !pp.drop) __hip_atomic_store(hx.rflag[d], pp.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        if ((MIXED ? hx.present[d] == HALO_PEER : hx.present[d] != 0) && !pp.drop) __hip_atomic_store(hx.rflag[d], pp.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     ok = 0;
     const long long t0 = wall_clock64(), tmax = g_p2p_timeout_ticks;
@@ -520,18 +560,9 @@ __global__ __launch_bounds__(256) void k_halo_exchange(LevView L, double *__rest
   __syncthreads();
   if (!ok) { if (threadIdx.x == 0) *pp.err = 1; return; }
   __threadfence_system();
-  const int nx = L.nx, ny = L.ny;
   for (int r = 0; r < pp.ipt; r++) {
     if (!halo_item(L, pp, dir, r, 1, q, k, e, t)) continue;
-    const double v = __builtin_nontemporal_load(hx.lbuf[dir] + t);
-    a[e] = v;
-    // mixed corners (mg_mpi_exchange.f90:720-743): the corner next to a physical side mirrors the edge halo cell that was
-    // just received -- written here by the thread that unpacked that cell instead of a separate launch
-    const long long ro = (long long)k * L.RS, W0 = ro, E0 = (long long)(nx + 1) * L.plane + ro;
-    if (dir == 0) { if (q == 0 && pp.mSW == 1) a[W0 + jpos(L, 0)] = v; if (q == nx - 1 && pp.mSE == 1) a[E0 + jpos(L, 0)] = v; }
-    else if (dir == 2) { if (q == 0 && pp.mNW == 1) a[W0 + jpos(L, ny + 1)] = v; if (q == nx - 1 && pp.mNE == 1) a[E0 + jpos(L, ny + 1)] = v; }
-    else if (dir == 3) { if (q == 0 && pp.mSW == 2) a[W0 + jpos(L, 0)] = v; if (q == ny - 1 && pp.mNW == 2) a[W0 + jpos(L, ny + 1)] = v; }
-    else if (dir == 1) { if (q == 0 && pp.mSE == 2) a[E0 + jpos(L, 0)] = v; if (q == ny - 1 && pp.mNE == 2) a[E0 + jpos(L, ny + 1)] = v; }
+    halo_store(L, pp, a, dir, q, k, e, __builtin_nontemporal_load(hx.lbuf[dir] + t));
   }
 }
 
@@ -779,7 +810,10 @@ void mgxk_halo_pack_all(hipStream_t st, const LevView *L, double *a, double *con
   HaloBufs hb;
   for (int d = 0; d < 8; d++) { hb.b[d] = bufs[d]; hb.present[d] = present[d]; }
   const int n = L->nx > L->ny ? L->nx : L->ny;
-  hipLaunchKernelGGL(k_halo_pack_all, dim3((n + 63) / 64, L->nz, 8), dim3(64), 0, st, *L, a, hb, unpack);
+  bool mixed = false;
+  for (int d = 0; d < 8; d++) mixed |= present[d] > HALO_PEER;
+  if (mixed) hipLaunchKernelGGL((k_halo_pack_all<true>), dim3((n + 63) / 64, L->nz, 8), dim3(64), 0, st, *L, a, hb, unpack);
+  else hipLaunchKernelGGL((k_halo_pack_all<false>), dim3((n + 63) / 64, L->nz, 8), dim3(64), 0, st, *L, a, hb, unpack);
 }
 void mgxk_halo_p2p(hipStream_t st, const LevView *L, double *a, double *const *rbuf, double *const *lbuf, unsigned long long *const *rflag,
                    unsigned long long *const *lflag, const int *present, unsigned long long seq, unsigned int *counter, int *err, const int *mixed, int drop) {
@@ -791,25 +825,29 @@ void mgxk_halo_p2p(hipStream_t st, const LevView *L, double *a, double *const *r
   // grid is kept small -- at most 128 blocks = 512 of the 1024 SIMDs -- and longer edges give each thread several items.
   const int maxblk = mgx_switches().p2p_maxblk;  // default 128
   long long items = 0;
-  for (int d = 0; d < 8; d++) if (present[d]) items += (long long)L->nz * ((d == 0 || d == 2) ? L->nx : ((d == 1 || d == 3) ? L->ny : 1));
+  for (int d = 0; d < 8; d++) if (present[d] == HALO_PEER) items += (long long)L->nz * ((d == 0 || d == 2) ? L->nx : ((d == 1 || d == 3) ? L->ny : 1));
   pp.ipt = (int)((items + 256LL * maxblk - 1) / (256LL * maxblk)) + 1;  // +1: per-direction round-up never exceeds maxblk
   const int ipt_min = mgx_switches().p2p_ipt;  // test hook for the multi-item path
   if (pp.ipt < ipt_min) pp.ipt = ipt_min;
   const int per = 256 * pp.ipt;
   int nb = 0;
+  pp.nreal = 0;
   for (int d = 0; d < 8; d++) {
     hx.rbuf[d] = rbuf[d]; hx.lbuf[d] = lbuf[d]; hx.rflag[d] = rflag[d]; hx.lflag[d] = lflag[d]; hx.present[d] = present[d];
     pp.flag[d] = nullptr;
     pp.blk0[d] = nb;
-    if (present[d]) nb += (L->nz * ((d == 0 || d == 2) ? L->nx : ((d == 1 || d == 3) ? L->ny : 1)) + per - 1) / per;
+    const int nd = present[d] ? (L->nz * ((d == 0 || d == 2) ? L->nx : ((d == 1 || d == 3) ? L->ny : 1)) + per - 1) / per : 0;
+    nb += nd;
+    if (present[d] == HALO_PEER) pp.nreal += nd;   // the blocks of a self or mirror direction only copy: they neither push nor spin
   }
   pp.blk0[8] = nb;
   // halo_item picks the LAST d with blk0[d] <= block index: absent directions are moved past the end
   for (int d = 7; d >= 0; d--) if (!present[d]) pp.blk0[d] = nb + 1;
   pp.seq = seq; pp.counter = counter; pp.err = err;
   pp.mSW = mixed[0]; pp.mSE = mixed[1]; pp.mNE = mixed[2]; pp.mNW = mixed[3];
-  if (nb == 0) return;
-  hipLaunchKernelGGL(k_halo_exchange, dim3(nb), dim3(256), 0, st, *L, a, hx, pp);
+  if (nb == 0 || pp.nreal == 0) return;
+  if (pp.nreal != nb) hipLaunchKernelGGL((k_halo_exchange<true>), dim3(nb), dim3(256), 0, st, *L, a, hx, pp);
+  else hipLaunchKernelGGL((k_halo_exchange<false>), dim3(nb), dim3(256), 0, st, *L, a, hx, pp);
 }
 // the bound of every p2p flag wait, in milliseconds (device global of this library; all instances of the process)
 int mgxk_set_p2p_timeout(double ms) {

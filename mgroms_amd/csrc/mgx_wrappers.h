@@ -18,6 +18,14 @@ enum {
   PASS_TALL_STORED = 4,  // it was the stored-coefficient tall-column pass (counter "tall_stored_passes")
 };
 
+// what serves a direction of a halo fill: present[d] of mgxk_halo_pack_all and mgxk_halo_p2p
+enum {
+  HALO_NONE = 0,    // no neighbour, nothing due
+  HALO_PEER = 1,    // another rank: buffers (and, with the pushes, flags)
+  HALO_SELF = 2,    // the rank itself (option "periodic", one rank along the direction): the halo is the interior the opposite side packs
+  HALO_MIRROR = 3,  // a closed side whose image is still due (mgxk_halo_p2p on a mixed level only): the halo is the interior this side packs
+};
+
 // ---- mgx_relax.hip ----
 int mgxk_relax_gs_sweep(hipStream_t st, const LevView *L, int real);
 int mgxk_relax_small(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode);

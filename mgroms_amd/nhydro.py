@@ -331,12 +331,9 @@ def grid(lev):
     return _Level(lev)
 
 
-def level_table(nx, ny, nz, npx=1, npy=1, rank=0, nsmall=8):
-    """Level hierarchy of `rank` (mg_grids.f90:468-738) as a list of dicts; pure host logic, no GPU needed."""
-    out = (C.c_int * (20 * 32))()
-    nl = lib().mgx_level_table(nx, ny, nz, npx, npy, rank, nsmall, 32, out)
+def _table(nl, out, what):
     if nl < 0:
-        raise MgxError("level_table: invalid arguments")
+        raise MgxError(f"{what}: invalid arguments")
     keys = ["nx", "ny", "nz", "npx", "npy", "incx", "incy", "gather", "ngx", "ngy", "key", "color"]
     res = []
     for l in range(nl):
@@ -344,6 +341,32 @@ def level_table(nx, ny, nz, npx=1, npy=1, rank=0, nsmall=8):
         d["neighb"] = list(out[20 * l + 12:20 * l + 20])
         res.append(d)
     return res
+
+
+def level_table(nx, ny, nz, npx=1, npy=1, rank=0, nsmall=8):
+    """Level hierarchy of `rank` (mg_grids.f90:468-738) as a list of dicts; pure host logic, no GPU needed."""
+    out = (C.c_int * (20 * 32))()
+    return _table(lib().mgx_level_table(nx, ny, nz, npx, npy, rank, nsmall, 32, out), out, "level_table")
+
+
+def level_table_periodic(nx, ny, nz, npx=1, npy=1, rank=0, nsmall=8, periodic=0):
+    """level_table with option "periodic" (bit 1: i, bit 2: j): the neighbour past the end of a periodic row or column of ranks is the rank
+    at its other end, the rank itself on a level with one rank along the direction; pure host logic."""
+    out = (C.c_int * (20 * 32))()
+    return _table(lib().mgx_level_table_periodic(nx, ny, nz, npx, npy, rank, nsmall, periodic, 32, out), out, "level_table_periodic")
+
+
+def exchange_plan(neighb, rank):
+    """(entries, self_dirs) of one halo exchange of a rank with the neighbour table `neighb` (S, E, N, W, SW, SE, NE, NW; -1 = none): entries =
+    [(peer, send direction, receive direction)] in the order handed to the exchange hook, self_dirs = the directions whose neighbour is the
+    rank itself (served by device copies, never in the list).  include/mgx.h: mgx_exchange_plan; pure host logic."""
+    nb = (C.c_int * 8)(*[int(v) for v in neighb])
+    out = (C.c_int * 24)()
+    mask = C.c_int()
+    n = lib().mgx_exchange_plan(nb, rank, out, C.byref(mask))
+    if n < 0:
+        raise MgxError("exchange_plan: no decomposition produces this neighbour table")
+    return [tuple(out[3 * t:3 * t + 3]) for t in range(n)], [d for d in range(8) if mask.value >> d & 1]
 
 
 # ---- measurement helpers (bench.py) -------------------------------------------------------------
