@@ -156,6 +156,10 @@ int mgx_level_table(int nx, int ny, int nz, int npx, int npy, int rank, int nsma
 /* The same with option "periodic" (0..3) as an argument: the neighbours of any rank of a periodic process grid, as mgx_init will build them.
  * periodic = 0 is mgx_level_table.  Host only. */
 int mgx_level_table_periodic(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int maxlev, int *out);
+/* The first level of the tail of an fp32 cycle (option "mixed_tail") on the one-rank hierarchy of nx x ny x nz: *first = the finest level from
+ * which every level down to the coarsest has at most 32768 cells and nz <= 32, 0 = no level is that small.  Pure host logic, usable before
+ * mgx_init and without a GPU.  Returns 0, or non-zero (mgx_last_error) for sizes that make no hierarchy. */
+int mgx_mixed_tail_first(int nx, int ny, int nz, int *first);
 /* The entry list of one halo exchange of `rank` whose neighbours are neighb[0..7] (S,E,N,W,SW,SE,NE,NW; -1 = none), as the library hands it to
  * the exchange hook: entries[3t..3t+2] = peer, send direction, receive direction of entry t -- sendbuf[t] holds what was packed for the send
  * direction, recvbuf[t] is unpacked into the halo of the receive direction; both are of one kind (S/N edge, E/W edge, corner).  For each peer
@@ -289,6 +293,14 @@ int mgx_set_verbose(int level);
  *   "cycle_precision" = 32 is refused as before).  Refused at the first such solve like "cycle_precision" = 32 and in its words: a process
  *   grid larger than 1 x 1, relax_method = 'GS', option "rb_exact".
  *   Read-only: "krylov_mixed_iterations" (Krylov iterations run with an fp32 cycle since mgx_init); "mixed_iterations" does not count them.
+ * "mixed_tail" (default 0, or 1; any other value is refused; survives mgx_clean / mgx_init; acts on the fp32 cycles of "cycle_precision" = 32 and
+ *   "krylov_precision" = 32 only): the tail of a cycle -- the run of coarsest levels that are all small, a level being small with at most 32768
+ *   cells and nz <= 32 (mgx_mixed_tail_first) -- runs inside one workgroup: one launch for a relax call on a small level, one for the part of a
+ *   V-cycle from the first tail level down to the coarsest and back, one for the F-cycle's first leg, coarsest relax and the V-cycles that start
+ *   inside the tail (k_tail32, mgx_mixed.hip).  The same device text as the per-launch kernels: the same bits as 0, which is one launch per colour
+ *   pass and transfer on every level.  The levels above the tail keep their launches.  What changes is the launch count of mgx_counters: a
+ *   tail launch counts as one, which is why the option is off until asked for.
+ *   Read-only: "mixed_tail_launches" (launches of the tail kernel since mgx_init).
  * "periodic" (default 0; a bit mask, any value outside 0..3 is refused; survives mgx_clean): 1 = the domain wraps in the i direction (east-west,
  *   the plane index of the solver's layout), 2 = in the j direction (north-south), 3 = both.  Read by mgx_init: set it BEFORE mgx_init; while a
  *   solver is initialised a different value is refused (mgx_clean, set, mgx_init).  Served on one rank and on every process grid mgx_init
@@ -351,7 +363,9 @@ int mgx_counters(long long *out);
 /* test hook of the fp32 cycle of option "cycle_precision" = 32 (single rank): converts the level's fp64 fields into its fp32 copy, runs one
  * fp32 operator, converts the result back.  op = "relax" (n sweeps on p, b of level lev -> p), "residual" (p, b -> r), "fine2coarse"
  * (r of lev -> b of lev+1, p of lev+1 = 0), "coarse2fine" (p of lev += interpolation of p of lev+1), "resrest" (restriction of b - A p of lev
- * -> b of lev+1, p of lev+1 = 0: the down leg of a V-cycle).  No Fortran counterpart. */
+ * -> b of lev+1, p of lev+1 = 0: the down leg of a V-cycle), "vcycle" (Vcycle(lev) on the copies from p, b of level lev; p of every level
+ * lev .. nlevs = the correction the cycle leaves there: every entry of the tail kernel of option "mixed_tail" from a rough state, where a solve
+ * only ever enters with a zero correction).  No Fortran counterpart. */
 int mgx_mixed_op(const char *op, int lev, int n);
 /* test hook of the three passes of option "krylov" (mgx_krylov.hip; single rank, after mgx_matrices): runs ONE pass on level 1 through the
  * wrapper solve_p calls for it, on the buffers solve_p uses (its ring of direction pairs, partial sums and device scalars, grid(1)%p and %r,

@@ -73,6 +73,7 @@ const Opt OPTIONS[] = {
   {"cycle_precision",     &State::cycle_precision,  nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 32 / 64 only
   {"krylov",              &State::krylov,           nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0..8 only
   {"krylov_precision",    &State::krylov_precision, nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 32 / 64 only (no preset: the table's would pass any number by)
+  {"mixed_tail",          &State::mixed_tail,       nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0 / 1 only
   {"periodic",            &State::periodic,         nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0..3 only, and not while initialised (read by mgx_init)
   // reads as off while a time-out of this solver holds (ksp_down, which mgx_clean does not carry); set: see mgx_set_option
   {"ksp",                 &State::use_ksp,          [](const State &s) { return (s.use_ksp && !s.ksp_down) ? 1 : 0; }, "MGX_NO_KSP", ENV_ZERO, RW, true},
@@ -86,6 +87,7 @@ const Opt OPTIONS[] = {
   {"overlapped_passes", nullptr, CNT(n_overlap), nullptr, ENV_NONE, RO, false},
   {"tall_stored_passes", nullptr, CNT(n_tall_stored), nullptr, ENV_NONE, RO, false},
   {"mixed_iterations", nullptr, CNT(n_mixed), nullptr, ENV_NONE, RO, false},
+  {"mixed_tail_launches", nullptr, CNT(n_mixed_tail), nullptr, ENV_NONE, RO, false},
   {"krylov_restarts", nullptr, CNT(kr_restarts), nullptr, ENV_NONE, RO, false},
   {"krylov_mixed_iterations", nullptr, CNT(n_kr_mixed), nullptr, ENV_NONE, RO, false},
   {"p2p_failed", nullptr, CNT(p2p_failed), nullptr, ENV_NONE, RO, false},
@@ -421,6 +423,19 @@ int mgx_level_table(int nx, int ny, int nz, int npx, int npy, int rank, int nsma
 int mgx_level_table_periodic(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int maxlev, int *out) {
   return level_table(nx, ny, nz, npx, npy, rank, nsmall, periodic, maxlev, out);
 }
+// the first level of the tail of an fp32 cycle (option "mixed_tail") on a one-rank hierarchy, 0 = no level is small
+int mgx_mixed_tail_first(int nx, int ny, int nz, int *first) {
+  if (!first) return fail("mgx_mixed_tail_first: first is NULL");
+  if (nx < 2 || ny < 2 || nz < 2) return fail("mgx_mixed_tail_first: %d x %d x %d is not a level-1 size", nx, ny, nz);
+  const int nl = find_grid_levels(1, 1, nx, ny, nz);
+  if (nl < 1) return fail("mgx_mixed_tail_first: %d x %d x %d has no hierarchy", nx, ny, nz);
+  std::vector<Level> T(nl);
+  T[0].nx = nx; T[0].ny = ny; T[0].nz = nz;
+  rank_level_table(0, T, 1, 1, 8);
+  *first = 0;
+  for (int lev = nl; lev >= 1 && mixed_tail_small(T[lev - 1].nx, T[lev - 1].ny, T[lev - 1].nz); lev--) *first = lev;
+  return 0;
+}
 int mgx_exchange_plan(const int *neighb, int rank, int *entries, int *self_mask) {
   if (!neighb || !entries) return -1;
   XEntry pl[8];
@@ -434,6 +449,7 @@ int mgx_set_option(const char *name, int value) {
   if (streq(name, "cycle_precision") && value != 32 && value != 64) return fail("cycle_precision must be 64 (fp64 cycles) or 32 (fp32 cycles under fp64 refinement), got %d", value);
   if (streq(name, "krylov_precision") && value != 32 && value != 64) return fail("krylov_precision must be 64 (fp64 cycles under the Krylov loop) or 32 (fp32 cycles under it), got %d", value);
   if (streq(name, "krylov") && (value < 0 || value > 8)) return fail("krylov must be 0 (off) or 1..8 (retained direction pairs of the truncated GCR), got %d", value);
+  if (streq(name, "mixed_tail") && value != 0 && value != 1) return fail("mixed_tail must be 1 (the small levels of an fp32 cycle in one launch) or 0 (one launch per colour pass and transfer), got %d", value);
   if (streq(name, "periodic")) {
     if (value < 0 || value > 3) return fail("periodic must be 0 (closed), 1 (the i direction, east-west), 2 (the j direction, north-south) or 3 (both), got %d", value);
     if (S.inited && value != S.periodic)
@@ -643,8 +659,12 @@ int mgx_mixed_op(const char *op, int lev, int n) {
   if (streq(op, "relax")) {
     if (n < 0) return fail("mgx_mixed_op(relax): n = %d sweeps", n);
     mgxx_to32(S.stream, &L.v, &L.v32, L.v.p, L.v32.e, 1.0); mgxx_to32(S.stream, &L.v, &L.v32, L.v.b, L.v32.f, 1.0);
-    relax32(lev, n);
+    CHK(relax32(lev, n));
     mgxx_to64(S.stream, &L.v, &L.v32, L.v32.e, L.v.p, 1.0, 0);
+  } else if (streq(op, "vcycle")) {   // Vcycle(lev) on the shadow from grid(lev)%p, %b; grid(lev..nlevs)%p = the e it leaves on every level
+    mgxx_to32(S.stream, &L.v, &L.v32, L.v.p, L.v32.e, 1.0); mgxx_to32(S.stream, &L.v, &L.v32, L.v.b, L.v32.f, 1.0);
+    CHK(vcycle32(lev, false));
+    for (int q = lev; q <= S.nlevs; q++) { Level &Q = S.lev[q - 1]; mgxx_to64(S.stream, &Q.v, &Q.v32, Q.v32.e, Q.v.p, 1.0, 0); }
   } else if (streq(op, "residual")) {
     mgxx_to32(S.stream, &L.v, &L.v32, L.v.p, L.v32.e, 1.0); mgxx_to32(S.stream, &L.v, &L.v32, L.v.b, L.v32.f, 1.0);
     mgxx_residual(S.stream, &L.v32, S.real);
@@ -667,7 +687,7 @@ int mgx_mixed_op(const char *op, int lev, int n) {
     mgxx_to32(S.stream, &C.v, &C.v32, C.v.p, C.v32.e, 1.0); mgxx_to32(S.stream, &L.v, &L.v32, L.v.p, L.v32.e, 1.0);
     coarse2fine32(lev);
     mgxx_to64(S.stream, &L.v, &L.v32, L.v32.e, L.v.p, 1.0, 0);
-  } else return fail("mgx_mixed_op: unknown operator '%s' (relax, residual, fine2coarse, coarse2fine, resrest)", op);
+  } else return fail("mgx_mixed_op: unknown operator '%s' (relax, vcycle, residual, fine2coarse, coarse2fine, resrest)", op);
   return sync_stream();
 }
 

@@ -567,6 +567,9 @@ int mixed_prepare() {
     }
     S.mx_ready = true;
     S.mx_gen = ~0ULL;
+    // the tail of the cycles: the run of coarsest levels that are all small (0: none)
+    S.mx_tail_first = 0;
+    for (int lev = S.nlevs; lev >= 1 && mixed_tail_small(S.lev[lev - 1].nx, S.lev[lev - 1].ny, S.lev[lev - 1].nz); lev--) S.mx_tail_first = lev;
   }
   if (S.mx_gen != S.coef_gen) {
     for (auto &L : S.lev) {
@@ -579,10 +582,31 @@ int mixed_prepare() {
   return 0;
 }
 
+// Option "mixed_tail": the level at which a cycle entered at lev1 hands over to the tail kernel (k_tail32, mgx_mixed.hip), 0 = nowhere:
+// the option is off, no level is small, or the levels from there down are more than one launch takes -- the cycle then keeps its launches
+// (a tail of 32768 cells at the most has at most four levels, which is what a launch takes: mgx_mixed.hip).
+int tail_hand(int lev1) {
+  if (!S.mixed_tail || !S.mx_tail_first) return 0;
+  const int hand = std::max(lev1, S.mx_tail_first);
+  return S.nlevs - hand + 1 <= mgxx_tail_max_levels() ? hand : 0;
+}
+// one launch of the tail kernel on levels lev .. last (tail_hand has counted them)
+int tail32(int lev, int last, int mode, bool lead, int n) {
+  const LevView32 *vs[8];
+  const int nl = last - lev + 1;
+  if (nl < 1 || nl > 8) return fail("mixed_tail: levels %d..%d", lev, last);
+  for (int q = 0; q < nl; q++) vs[q] = &S.lev[lev - 1 + q].v32;
+  if (!mgxx_tail(S.stream, vs, nl, mode, lead ? 1 : 0, n, S.par.ns_pre, S.par.ns_post, S.par.ns_coarsest, S.method == M_RB, S.real, S.linear))
+    return fail("mixed_tail: the tail kernel does not serve levels %d..%d (set option mixed_tail = 0)", lev, last);
+  S.n_launch++; S.n_mixed_tail++;
+  return 0;
+}
+
 // relax(lev, nsweeps) on the fp32 shadow: four colours, or the parallel red-black pass (k = 1 same-colour diagonals from a snapshot
-// taken before each colour: the fp64 pass with rb_seq = 0)
-void relax32(int lev, int nsweeps) {
+// taken before each colour: the fp64 pass with rb_seq = 0); a small level in one launch (option "mixed_tail")
+int relax32(int lev, int nsweeps) {
   LevView32 &v = S.lev[lev - 1].v32;
+  if (nsweeps > 0 && S.mixed_tail && S.mx_tail_first && lev >= S.mx_tail_first) return tail32(lev, lev, TAIL_RELAX, false, nsweeps);
   for (int it = 1; it <= nsweeps; it++) {
     if (S.method == M_FC) {
       for (int fc1 = 1; fc1 <= 2; fc1++)
@@ -594,31 +618,41 @@ void relax32(int lev, int nsweeps) {
       }
     }
   }
+  return 0;
 }
 void coarse2fine32(int lev) { mgxx_coarse2fine(S.stream, &S.lev[lev - 1].v32, &S.lev[lev].v32, S.linear); S.n_launch++; }
 
-// mg_solvers.f90:129-151 on the shadow; lead_c2f: Fcycle's coarse2fine(lev1) comes first (:119-120)
-void vcycle32(int lev1, bool lead_c2f) {
-  for (int lev = lev1; lev <= S.nlevs - 1; lev++) {
+// mg_solvers.f90:129-151 on the shadow; lead_c2f: Fcycle's coarse2fine(lev1) comes first (:119-120).  Option "mixed_tail": from level
+// `hand` down to the coarsest relax and back up to hand's post-smoothing in one launch; the levels above keep theirs, the transfers
+// between hand - 1 and hand included.
+int vcycle32(int lev1, bool lead_c2f) {
+  const int hand = tail_hand(lev1), bottom = hand ? hand : S.nlevs;
+  for (int lev = lev1; lev <= bottom - 1; lev++) {
     if (lead_c2f && lev == lev1) coarse2fine32(lev);
-    relax32(lev, S.par.ns_pre);
+    CHK(relax32(lev, S.par.ns_pre));
     mgxx_resrest(S.stream, &S.lev[lev - 1].v32, &S.lev[lev].v32, S.real); S.n_launch++;   // compute_residual(lev) + fine2coarse(lev)
   }
-  relax32(S.nlevs, S.par.ns_coarsest);
-  for (int lev = S.nlevs - 1; lev >= lev1; lev--) {
+  if (hand) CHK(tail32(hand, S.nlevs, TAIL_VCYCLE, lead_c2f && hand == lev1, 0));
+  else CHK(relax32(S.nlevs, S.par.ns_coarsest));
+  for (int lev = bottom - 1; lev >= lev1; lev--) {
     coarse2fine32(lev);
-    relax32(lev, S.par.ns_post);
+    CHK(relax32(lev, S.par.ns_post));
   }
+  return 0;
 }
 
-// mg_solvers.f90:104-126 on the shadow, level 1 holding (e, f) = (0, s r): the first leg restricts f (the residual of e = 0)
-void fcycle32() {
+// mg_solvers.f90:104-126 on the shadow, level 1 holding (e, f) = (0, s r): the first leg restricts f (the residual of e = 0).
+// Option "mixed_tail": the first leg from level `hand` on, the coarsest relax and the V-cycles that start inside the tail in one launch.
+int fcycle32() {
   TicScope ts(1, "Fcycle");
-  for (int lev = 1; lev <= S.nlevs - 1; lev++) {
+  const int hand = tail_hand(1), bottom = hand ? hand : S.nlevs;
+  for (int lev = 1; lev <= bottom - 1; lev++) {
     mgxx_restrict(S.stream, &S.lev[lev - 1].v32, &S.lev[lev].v32, S.lev[lev - 1].v32.f); S.n_launch++;
   }
-  relax32(S.nlevs, S.par.ns_coarsest);
-  for (int lev = S.nlevs - 1; lev >= 1; lev--) vcycle32(lev, true);
+  if (hand) CHK(tail32(hand, S.nlevs, TAIL_FCYCLE, false, 0));
+  else CHK(relax32(S.nlevs, S.par.ns_coarsest));
+  for (int lev = bottom - 1; lev >= 1; lev--) CHK(vcycle32(lev, true));
+  return 0;
 }
 
 // solve_p with fp32 cycles: the same prints, fort.100 lines, history, warm_start handling and res0 relative to ||b|| as solve_p
@@ -633,7 +667,7 @@ int solve_p_mixed(double tol, int maxite, int *nite_out, double *res_out, double
     const double sc = rabs > 0.0 ? 1.0 / rabs : 1.0;
     mgxx_to32(S.stream, &L.v, &L.v32, L.v.r, L.v32.f, sc); S.n_launch++;
     HIPCHK(hipMemsetAsync(L.v32.e, 0, L.n3js32 * sizeof(float), S.stream));
-    fcycle32();
+    CHK(fcycle32());
     mgxx_to64(S.stream, &L.v, &L.v32, L.v32.e, L.v.p, rabs > 0.0 ? rabs : 1.0, 1); S.n_launch++;   // p += e / s, halo images included
     CHK(residual(1, &rabs));
     S.n_mixed++;
@@ -701,7 +735,7 @@ int solve_p_krylov(double tol, int maxite, int *nite_out, double *res_out, doubl
       if (lowp) {  // e = M f on the shadows; z is formed by pass 1
         if (fresh) { fnorm = nscale; mgxx_to32(S.stream, &L.v, &L.v32, own.r, L.v32.f, 1.0 / fnorm); S.n_launch++; }
         HIPCHK(hipMemsetAsync(L.v32.e, 0, L.n3js32 * sizeof(float), S.stream));
-        fcycle32();
+        CHK(fcycle32());
       } else {  // z = M r: Fcycle on (p, b) = (0, r).  The first leg restricts the view's r, the rest of the cycle may use it as scratch.
         HIPCHK(hipMemsetAsync(z, 0, L.n3js * sizeof(double), S.stream));
         L.v.p = z; L.v.b = own.r; L.v.r = own.r;

@@ -160,6 +160,13 @@ struct State {
   double *kr_z[9] = {}, *kr_q[9] = {}, *kr_sc = nullptr, *kr_partial = nullptr;
   long long n_mixed = 0;          // read-only option "mixed_iterations": solve_p iterations run with fp32 cycles since mgx_init
   bool mx_ready = false;
+  // option "mixed_tail" (0 default, 1): the fp32 cycles run their tail -- the coarsest levels that are all small (mixed_tail_small,
+  // mgx_internal.h) -- inside one workgroup, one launch per relax call, V-cycle tail or F-cycle tail (k_tail32, mgx_mixed.hip), the same
+  // device text as the per-launch kernels and the same bits; 0 = one launch per colour pass and transfer on every level.  Off by default
+  // because it changes what mgx_counters reports for an fp32 cycle, which callers (and tests/test_gpu_krylov_mixed.py) count by hand.
+  int mixed_tail = 0;
+  int mx_tail_first = 0;          // first level of that tail, 0 = no level is small (mixed_prepare)
+  long long n_mixed_tail = 0;     // read-only option "mixed_tail_launches": launches of the tail kernel since mgx_init
   unsigned long long coef_gen = 0, mx_gen = ~0ULL;
   // option "periodic" (0 default; bit 1 = the i direction, east-west; bit 2 = the j direction, north-south): read by mgx_init, which makes the rank
   // its own neighbour on the periodic sides of every level (rank_level_table).  Such a side is an open side like a rank seam: every kernel
@@ -261,7 +268,8 @@ int solve_p_opt(double tol, int maxite, int *nite_out, double *res_out, double *
 int krylov_op(const char *op, int nd, double *const *f, const int *slot, const double *sin, double *sout, int *path);
 int mixed_check();
 int mixed_prepare();
-void relax32(int lev, int nsweeps);
+int relax32(int lev, int nsweeps);
 void coarse2fine32(int lev);
+int vcycle32(int lev1, bool lead_c2f);
 
 }  // namespace mgx_host

@@ -83,5 +83,13 @@ struct LevView32 {
 
 __host__ __device__ inline int jpos32(const LevView32 &L, int j) { return (j & 1) ? L.HO + (j >> 1) : L.EO + (j >> 1); }
 
+// Option "mixed_tail": a level is small when one workgroup runs it at the cost of what it moves -- at most MIXED_TAIL_MAX_CELLS cells
+// (inclusive), and nz <= 32 so that the register instance of its colour pass (relax32_col<NZ>, mgx_mixed.hip) fits the registers of a wave
+// without scratch.  The tail of a cycle is the run of coarsest levels that are all small.
+#ifndef MIXED_TAIL_MAX_CELLS
+#define MIXED_TAIL_MAX_CELLS 32768
+#endif
+inline bool mixed_tail_small(int nx, int ny, int nz) { return (long long)nx * ny * nz <= MIXED_TAIL_MAX_CELLS && nz <= 32; }
+
 // the kernel wrappers: one prototype each, seen by the file that defines a wrapper and by every file that calls it
 #include "mgx_wrappers.h"

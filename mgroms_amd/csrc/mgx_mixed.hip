@@ -159,10 +159,7 @@ __global__ __launch_bounds__(256) void k_residual32(LevView32 L) {
 // (mg_intergrids.f90:139-162), e_c = 0; no r written, no norm.  One lane = one coarse column = 2 x 2 fine columns.
 // ------------------------------------------------------------------------------------------------
 template <bool REAL>
-__global__ __launch_bounds__(256) void k_resrest32(LevView32 F, LevView32 C) {
-  const int j2 = 1 + blockIdx.x * WAVE + threadIdx.x;
-  const int i2 = 1 + blockIdx.y * blockDim.y + threadIdx.y;
-  if (j2 > C.ny || i2 > C.nx) return;
+__device__ __forceinline__ void resrest32_col(const LevView32 &F, const LevView32 &C, const int j2, const int i2) {
   const int i = 2 * i2 - 1, jh = j2 - 1;
   int co, jmo, jpo, ce, jme, jpe;
   col_pos(F, jh, 1, co, jmo, jpo);   // fine j = 2 j2 - 1
@@ -182,13 +179,17 @@ __global__ __launch_bounds__(256) void k_resrest32(LevView32 F, LevView32 C) {
     C.e[oc + ro] = 0.f; mirror32(C, C.e, ro, j2, i2, cc, 0.f);
   }
 }
-
-// First leg of the F-cycle (mg_solvers.f90:110-115): f_c = sum of the 8 fine values of `src` (the fine f, which is the fine residual
-// there because the fine e is 0), e_c = 0.  mg_intergrids.f90:139-162.
-__global__ __launch_bounds__(256) void k_restrict32(LevView32 F, LevView32 C, const float *__restrict__ x) {
+template <bool REAL>
+__global__ __launch_bounds__(256) void k_resrest32(LevView32 F, LevView32 C) {
   const int j2 = 1 + blockIdx.x * WAVE + threadIdx.x;
   const int i2 = 1 + blockIdx.y * blockDim.y + threadIdx.y;
   if (j2 > C.ny || i2 > C.nx) return;
+  resrest32_col<REAL>(F, C, j2, i2);
+}
+
+// First leg of the F-cycle (mg_solvers.f90:110-115): f_c = sum of the 8 fine values of `src` (the fine f, which is the fine residual
+// there because the fine e is 0), e_c = 0.  mg_intergrids.f90:139-162.
+__device__ __forceinline__ void restrict32_col(const LevView32 &F, const LevView32 &C, const float *x, const int j2, const int i2) {
   const int i = 2 * i2 - 1;
   const int po = F.HO + (j2 - 1), pe = F.EO + j2;  // fine j = 2*j2-1 (odd) and 2*j2 (even)
   const long long o0 = (long long)i * F.plane, o1 = o0 + F.plane;
@@ -202,17 +203,19 @@ __global__ __launch_bounds__(256) void k_restrict32(LevView32 F, LevView32 C, co
     C.e[oc + ro] = 0.f; mirror32(C, C.e, ro, j2, i2, cc, 0.f);
   }
 }
+__global__ __launch_bounds__(256) void k_restrict32(LevView32 F, LevView32 C, const float *__restrict__ x) {
+  const int j2 = 1 + blockIdx.x * WAVE + threadIdx.x;
+  const int i2 = 1 + blockIdx.y * blockDim.y + threadIdx.y;
+  if (j2 > C.ny || i2 > C.nx) return;
+  restrict32_col(F, C, x, j2, i2);
+}
 
 // ------------------------------------------------------------------------------------------------
 // coarse2fine: fine e += interp(coarse e), mg_intergrids.f90:366-450 (tri-linear, top level x 1/2), :336-363 (nearest), :226.
 // The expressions of k_coarse2fine_run and k_coarse2fine_nearest (mgx_kernels.hip); the interpolated correction is not stored in r.
 // ------------------------------------------------------------------------------------------------
 template <bool LINEAR>
-__global__ __launch_bounds__(256) void k_coarse2fine32(LevView32 F, LevView32 C) {
-  const int j2 = 1 + blockIdx.x * WAVE + threadIdx.x;
-  const int k2 = 1 + blockIdx.y * blockDim.y + threadIdx.y;
-  const int i2 = 1 + blockIdx.z;
-  if (j2 > C.ny || k2 > C.nz) return;
+__device__ __forceinline__ void coarse2fine32_cell(const LevView32 &F, const LevView32 &C, const int j2, const int k2, const int i2) {
   const int i = 2 * i2 - 1;
   const int po = F.HO + (j2 - 1), pe = F.EO + j2;
   const int c0 = jpos32(C, j2), cm = jpos32(C, j2 - 1), cp = jpos32(C, j2 + 1);
@@ -260,6 +263,147 @@ __global__ __launch_bounds__(256) void k_coarse2fine32(LevView32 F, LevView32 C)
 #undef XC
 #undef PUT
 }
+template <bool LINEAR>
+__global__ __launch_bounds__(256) void k_coarse2fine32(LevView32 F, LevView32 C) {
+  const int j2 = 1 + blockIdx.x * WAVE + threadIdx.x;
+  const int k2 = 1 + blockIdx.y * blockDim.y + threadIdx.y;
+  const int i2 = 1 + blockIdx.z;
+  if (j2 > C.ny || k2 > C.nz) return;
+  coarse2fine32_cell<LINEAR>(F, C, j2, k2, i2);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The tail of a cycle in ONE workgroup (option "mixed_tail"): the coarsest levels that are all small (mixed_tail_small, mgx_internal.h)
+// cost a per-launch cycle its launch latency and nothing else (16x16x2: 960 launches per F-cycle), so here the schedule of relax32 /
+// vcycle32 / fcycle32 (mgx_cycle.cpp) on those levels runs inside one launch of up to 768 lanes.  Lane 0 writes the schedule as a list of
+// phases into LDS (tail_program); every phase is a workgroup-strided loop over the work items the per-launch kernel of the same name gives a
+// lane, calls that kernel's device function, and ends with __syncthreads() -- the only synchronisation there is: one workgroup, no flags, no
+// atomics, nothing to wait for.  No lane leaves a phase early, so every lane reaches every barrier.  e, f and p1 change from phase to phase
+// and are read through the plain pointers of the by-value LevView32 (nothing marks them invariant); a column's mirror images are stored by
+// the lane that owns the column, before the barrier.
+// ------------------------------------------------------------------------------------------------
+// levels one launch takes.  A tail has no more: its coarsest level has at least 4 x 4 x 2 cells and every finer one 8 times as many (more where
+// an odd nz was halved), so the fifth from the bottom is past MIXED_TAIL_MAX_CELLS = 32768.
+#define MIXED_TAIL_MAX_LEVELS 4
+// Two register classes, both without scratch: a tail whose levels take the instances relax32_col<2>, <4>, <8> or the generic pass needs 164
+// registers (the residual + restriction's loads in flight) and runs with up to 768 lanes (3 waves per SIMD, 170 registers each); one with an
+// nz = 16 or 32 level needs 251-256 (relax32_col<32>: 239 in its own kernel), and runs with up to 256 lanes (1 wave per SIMD, 512 registers).
+#define MIXED_TAIL_LANES_A 768
+#define MIXED_TAIL_LANES_B 256
+// a phase: kind | level (index into Tail32::L) << 2 | which sweep count << 5
+enum { TP_RELAX = 0, TP_RESREST = 1, TP_RESTRICT = 2, TP_C2F = 3 };
+enum { TN_CALL = 0, TN_PRE = 1, TN_POST = 2, TN_COARSEST = 3 };
+#define TAIL_OP(kind, lev, nsel) (unsigned char)((kind) | (lev) << 2 | (nsel) << 5)
+// the F-cycle of nl levels: nl restrictions and coarsest relax, then V-cycles of 2 + 4 d phases from d = 1 .. nl - 1 levels above the coarsest
+#define MIXED_TAIL_MAX_OPS (MIXED_TAIL_MAX_LEVELS + 2 * (MIXED_TAIL_MAX_LEVELS - 1) * (MIXED_TAIL_MAX_LEVELS + 1))
+struct Tail32 {
+  LevView32 L[MIXED_TAIL_MAX_LEVELS];   // the tail's levels, finest first
+  int nl, mode, lead;                   // mode: TAIL_* of mgx_wrappers.h; lead: the V-cycle starts with coarse2fine onto L[0]
+  int n, ns_pre, ns_post, ns_coarsest, linear;
+  // the NZ instance of each level's colour pass, as mgxx_relax_pass picks it (0 = the generic pass).  Apart from L[].nz on purpose: inside
+  // `case 8:` of a switch over L.nz the compiler knows L.nz, folds the `k < L.nz` of off32 / res32 that the per-launch kernels test at run
+  // time, and -ffp-contract=fast then fuses across what were block boundaries: other roundings than theirs.
+  int inst[MIXED_TAIL_MAX_LEVELS];
+};
+
+// vcycle32(a, lead) on levels a .. nl-1 (indices into Tail32::L)
+__device__ __forceinline__ int tail_vcycle(unsigned char *p, int q, const int a, const int nl, const bool lead) {
+  for (int l = a; l < nl - 1; l++) {
+    if (lead && l == a) p[q++] = TAIL_OP(TP_C2F, l, 0);
+    p[q++] = TAIL_OP(TP_RELAX, l, TN_PRE);
+    p[q++] = TAIL_OP(TP_RESREST, l, 0);
+  }
+  p[q++] = TAIL_OP(TP_RELAX, nl - 1, TN_COARSEST);
+  for (int l = nl - 2; l >= a; l--) {
+    p[q++] = TAIL_OP(TP_C2F, l, 0);
+    p[q++] = TAIL_OP(TP_RELAX, l, TN_POST);
+  }
+  return q;
+}
+__device__ __forceinline__ int tail_program(const Tail32 &T, unsigned char *p) {
+  if (T.mode == TAIL_RELAX) { p[0] = TAIL_OP(TP_RELAX, 0, TN_CALL); return 1; }
+  if (T.mode == TAIL_VCYCLE) return tail_vcycle(p, 0, 0, T.nl, T.lead != 0);
+  int q = 0;   // TAIL_FCYCLE: fcycle32 with L[0] as its finest level
+  for (int l = 0; l < T.nl - 1; l++) p[q++] = TAIL_OP(TP_RESTRICT, l, 0);
+  p[q++] = TAIL_OP(TP_RELAX, T.nl - 1, TN_COARSEST);
+  for (int l = T.nl - 2; l >= 0; l--) q = tail_vcycle(p, q, l, T.nl, true);
+  return q;
+}
+
+// relax32(lev, nsweeps): the colour passes of k_relax32 (and k_snapshot32 before each red-black colour of cmatrix='real')
+template <int NZ, bool REAL, bool RB>
+__device__ __forceinline__ void tail_relax(const LevView32 &L, const int nsweeps) {
+  const int nh = L.ny >> 1, nt = blockDim.x, tid = threadIdx.x;
+  for (int it = 0; it < nsweeps; it++) {
+    if (RB) {
+#pragma nounroll
+      for (int rb = 1; rb <= 2; rb++) {
+        if (REAL) {
+          const int RS = L.RS, n = (L.nx + 2) * RS;
+          for (int t = tid; t < n; t += nt) { const int i = t / RS; L.p1[t] = L.e[(long long)i * L.plane + (t - i * RS)]; }
+          __syncthreads();
+        }
+        const int n = nh * L.nx;
+        for (int t = tid; t < n; t += nt) {
+          const int ipl = t / nh, jh = t - ipl * nh, i = 1 + ipl;
+          relax32_col<NZ, REAL, REAL>(L, i, jh, ((i + rb) & 1) == 0);
+        }
+        __syncthreads();
+      }
+    } else {
+#pragma nounroll
+      for (int fc = 0; fc < 4; fc++) {   // (fc1, fc2) = (1,1), (1,2), (2,1), (2,2)
+        const int i0 = 1 + (fc >> 1), jodd = (fc & 1) == 0, n = nh * (L.nx >> 1);
+        for (int t = tid; t < n; t += nt) {
+          const int ipl = t / nh, jh = t - ipl * nh;
+          relax32_col<NZ, REAL, false>(L, i0 + 2 * ipl, jh, jodd);
+        }
+        __syncthreads();
+      }
+    }
+  }
+}
+
+// NZMAX: the largest register instance of the colour pass compiled in (a level with a larger one goes to the other class: launch_tail)
+template <bool REAL, bool RB, int NZMAX, int LANES>
+__global__ __launch_bounds__(LANES) void k_tail32(const Tail32 T) {
+  __shared__ unsigned char prog[MIXED_TAIL_MAX_OPS];
+  __shared__ int nprog;
+  if (threadIdx.x == 0) nprog = tail_program(T, prog);
+  __syncthreads();
+  const int np = __builtin_amdgcn_readfirstlane(nprog), nt = blockDim.x, tid = threadIdx.x;
+  for (int pc = 0; pc < np; pc++) {
+    const int op = __builtin_amdgcn_readfirstlane((int)prog[pc]), kind = op & 3, l = (op >> 2) & 7, nsel = op >> 5;
+    const LevView32 &L = T.L[l];
+    if (kind == TP_RELAX) {
+      const int ns = nsel == TN_CALL ? T.n : (nsel == TN_PRE ? T.ns_pre : (nsel == TN_POST ? T.ns_post : T.ns_coarsest));
+      switch (T.inst[l]) {   // the instance mgxx_relax_pass picks
+        case 2: tail_relax<2, REAL, RB>(L, ns); break;
+        case 4: tail_relax<4, REAL, RB>(L, ns); break;
+        case 8: tail_relax<8, REAL, RB>(L, ns); break;
+        case 16: if constexpr (NZMAX >= 16) { tail_relax<16, REAL, RB>(L, ns); } break;
+        case 32: if constexpr (NZMAX >= 32) { tail_relax<32, REAL, RB>(L, ns); } break;
+        default: tail_relax<0, REAL, RB>(L, ns); break;
+      }
+      continue;   // (every colour pass has ended with its barrier)
+    }
+    const LevView32 &C = T.L[l + 1];
+    if (kind == TP_C2F) {
+      const int n = C.ny * C.nz * C.nx;
+      for (int t = tid; t < n; t += nt) {
+        const int q = t / C.ny, j2 = 1 + (t - q * C.ny), i2 = 1 + q / C.nz, k2 = 1 + (q - (i2 - 1) * C.nz);
+        if (T.linear) coarse2fine32_cell<true>(L, C, j2, k2, i2); else coarse2fine32_cell<false>(L, C, j2, k2, i2);
+      }
+    } else {
+      const int n = C.ny * C.nx;
+      for (int t = tid; t < n; t += nt) {
+        const int q = t / C.ny, j2 = 1 + (t - q * C.ny), i2 = 1 + q;
+        if (kind == TP_RESREST) resrest32_col<REAL>(L, C, j2, i2); else restrict32_col(L, C, L.f, j2, i2);
+      }
+    }
+    __syncthreads();
+  }
+}
 
 // ------------------------------------------------------------------------------------------------
 // fp64 <-> fp32 over a whole JS array, halo included (the two layouts differ in EO / HO / RS).  One lane = one half-row position
@@ -295,6 +439,14 @@ static void launch_relax32(hipStream_t st, const LevView32 *L, int i0, int istep
   else hipLaunchKernelGGL((k_relax32<NZ, false, false>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb);
 }
 
+template <int NZMAX, int LANES>
+static void launch_tail(hipStream_t st, const Tail32 &T, int cols, int real, int rb) {
+  const dim3 blk(cols >= LANES ? LANES : (cols + WAVE - 1) / WAVE * WAVE);
+  if (real && rb) hipLaunchKernelGGL((k_tail32<true, true, NZMAX, LANES>), dim3(1), blk, 0, st, T);
+  else if (real) hipLaunchKernelGGL((k_tail32<true, false, NZMAX, LANES>), dim3(1), blk, 0, st, T);
+  else if (rb) hipLaunchKernelGGL((k_tail32<false, true, NZMAX, LANES>), dim3(1), blk, 0, st, T);
+  else hipLaunchKernelGGL((k_tail32<false, false, NZMAX, LANES>), dim3(1), blk, 0, st, T);
+}
 static dim3 whole_grid(int ny, int nx) { return dim3((ny / 2 + 1 + WAVE - 1) / WAVE, (nx + 2 + 3) / 4, 2); }
 
 extern "C" {
@@ -333,6 +485,32 @@ void mgxx_coarse2fine(hipStream_t st, const LevView32 *F, const LevView32 *C, in
   if (linear) hipLaunchKernelGGL(k_coarse2fine32<true>, grd, blk, 0, st, *F, *C);
   else hipLaunchKernelGGL(k_coarse2fine32<false>, grd, blk, 0, st, *F, *C);
 }
+// The tail kernel on levels levs[0 .. nl-1] (consecutive, finest first, all small): mode TAIL_RELAX = n sweeps of levs[0] (nl = 1),
+// TAIL_VCYCLE = vcycle32(levs[0], lead) down to levs[nl-1] and back, TAIL_FCYCLE = fcycle32 with levs[0] as its finest level.  Returns 0,
+// nothing launched, where the kernel does not serve the call (more levels than it takes, a level that is not small, levels that are not
+// consecutive): tail_hand (mgx_cycle.cpp) keeps a cycle of more levels on its launches, anything else is the caller's error to report.
+int mgxx_tail(hipStream_t st, const LevView32 *const *levs, int nl, int mode, int lead, int n, int ns_pre, int ns_post, int ns_coarsest, int rb,
+              int real, int linear) {
+  if (nl < 1 || nl > MIXED_TAIL_MAX_LEVELS || (mode == TAIL_RELAX && nl != 1)) return 0;
+  Tail32 T = {};
+  for (int l = 0; l < nl; l++) {
+    const LevView32 &v = *levs[l];
+    if (!mixed_tail_small(v.nx, v.ny, v.nz) || (rb && real && !v.p1)) return 0;
+    // (nz halves by integer division: 20, 10, 5, 2 is a hierarchy, and the transfers walk the coarse rows only)
+    if (l > 0 && (2 * v.nx != levs[l - 1]->nx || 2 * v.ny != levs[l - 1]->ny || v.nz != levs[l - 1]->nz / 2)) return 0;
+    T.L[l] = v;
+    T.inst[l] = (v.nz == 2 || v.nz == 4 || v.nz == 8 || v.nz == 16 || v.nz == 32) ? v.nz : 0;
+  }
+  T.nl = nl; T.mode = mode; T.lead = lead; T.n = n; T.ns_pre = ns_pre; T.ns_post = ns_post; T.ns_coarsest = ns_coarsest; T.linear = linear;
+  // one lane per column of the largest colour pass, whole waves, the instance's lanes at the most (the strided loops take the rest)
+  const int cols = T.L[0].nx * (T.L[0].ny / 2);
+  bool big = false;
+  for (int l = 0; l < nl; l++) big = big || T.L[l].nz == 16 || T.L[l].nz == 32;
+  if (big) launch_tail<32, MIXED_TAIL_LANES_B>(st, T, cols, real, rb);
+  else launch_tail<8, MIXED_TAIL_LANES_A>(st, T, cols, real, rb);
+  return 1;
+}
+int mgxx_tail_max_levels(void) { return MIXED_TAIL_MAX_LEVELS; }
 void mgxx_to32(hipStream_t st, const LevView *D, const LevView32 *S, const double *src, float *dst, double scale) {
   hipLaunchKernelGGL(k_to32, whole_grid(D->ny, D->nx), dim3(WAVE, 4), 0, st, *D, *S, src, dst, scale);
 }

@@ -253,8 +253,16 @@ def nlevs():
 
 def mixed_op(op, lev, n=1):
     """one fp32 operator of the mixed-precision cycle (option "cycle_precision" = 32) on level lev's fp64 fields, converted in and
-    back: "relax" (n sweeps), "residual", "fine2coarse", "coarse2fine", "resrest" (include/mgx.h: mgx_mixed_op)."""
+    back: "relax" (n sweeps), "residual", "fine2coarse", "coarse2fine", "resrest", "vcycle" (include/mgx.h: mgx_mixed_op)."""
     check(lib().mgx_mixed_op(op.encode(), int(lev), int(n)))
+
+
+def mixed_tail_first(nx, ny, nz):
+    """first level of the tail of an fp32 cycle on the one-rank hierarchy of nx x ny x nz (option "mixed_tail"): from there down every level has
+    at most 32768 cells and nz <= 32; 0 = no level is that small.  Pure host logic (include/mgx.h: mgx_mixed_tail_first)."""
+    first = C.c_int()
+    check(lib().mgx_mixed_tail_first(int(nx), int(ny), int(nz), C.byref(first)))
+    return first.value
 
 
 def krylov_op(op, fields, nd=0, slot=None, sin=(), nout=2):
