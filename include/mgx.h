@@ -156,6 +156,10 @@ int mgx_level_table(int nx, int ny, int nz, int npx, int npy, int rank, int nsma
 /* The same with option "periodic" (0..3) as an argument: the neighbours of any rank of a periodic process grid, as mgx_init will build them.
  * periodic = 0 is mgx_level_table.  Host only. */
 int mgx_level_table_periodic(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int maxlev, int *out);
+/* The same with options "periodic" (0..3) and "hold_odd_nz" (0, 1) as arguments: the table mgx_init will build under them.  hold = 1: level
+ * l + 1 exists iff l < nl1 (the horizontal bound of find_grid_levels) and nz_l != 2, with nz_{l+1} = nz_l / 2 for an even nz_l and nz_l for an odd
+ * one; nx, ny and the gathers are those of hold = 0.  hold = 0 is mgx_level_table_periodic.  Host only. */
+int mgx_level_table_hold(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int hold, int maxlev, int *out);
 /* The first level of the tail of an fp32 cycle (option "mixed_tail") on the one-rank hierarchy of nx x ny x nz: *first = the finest level from
  * which every level down to the coarsest has at most 32768 cells and nz <= 32, 0 = no level is that small.  Pure host logic, usable before
  * mgx_init and without a GPU.  Returns 0, or non-zero (mgx_last_error) for sizes that make no hierarchy. */
@@ -328,6 +332,18 @@ int mgx_set_verbose(int level);
  *   block of the one-rank solution (tests/test_gpu_periodic_grid.py); the kernels that need a closed level (the
  *   persistent and one-workgroup relax, the restriction chain, the zeta chain, the direct coarsest solve) decline such a level, so a periodic
  *   hierarchy runs the launches of a level with neighbours (profiles/periodic_time.json).  mgx_transport() reports the wrap.
+ * "hold_odd_nz" (default 0, or 1; any other value is refused; survives mgx_clean; no environment variable): 1 = once a level has an odd nz the
+ *   coarser levels keep that nz and go on coarsening in x and y only, down to the horizontal bound of the hierarchy (mgx_level_table_hold), instead
+ *   of the reference's nz / 2, which drops the top row of an odd level and diverges wherever such a level is not the coarsest (128 x 128 x 40:
+ *   nz 40, 20, 10, 5, 2 becomes 40, 20, 10, 5, 5, 5).  Vertical sizes such as 20, 28, 40, 80 then converge like their even neighbours.  Read by
+ *   mgx_init: set it BEFORE mgx_init; while a solver is initialised a different value is refused (mgx_clean, set, mgx_init).  A size whose nz
+ *   stays even down to 2 has the same table, kernels, launch counts and bits with either value.  Between two levels of equal nz (a held pair)
+ *   fine2coarse and coarse2fine are the reference's 2-D operators applied to every row (fine2coarse_2D, coarse2fine_2D_linear / _nearest,
+ *   mg_intergrids.f90) in the reference's order of operations (mgx_hold.hip); the down leg of a cycle runs compute_residual and the restriction as
+ *   two launches there, and the kernels that fold a transfer into another pass decline the pair.  An odd nx or ny on a level and an odd nz on level 1
+ *   stay refused.  Served: relax_method 'FC', 'RB' in its modes and 'GS', "krylov" with fp64 cycles, bmask, "periodic", process grids, the device
+ *   entry points.  Refused at the solve where the hierarchy has a held pair: "cycle_precision" = 32, "krylov_precision" = 32 and with them
+ *   "mixed_tail" (the transfers of the fp32 copies halve nz).  mgx_mixed_tail_first keeps describing the hierarchy of hold_odd_nz = 0.
  * Read-only through mgx_get_option: "p2p_failed" (a peer-to-peer wait of THIS rank timed out since the ranks last agreed: see below),
  *   "overlapped_passes", "tall_stored_passes" (colour passes of nz = 80, 96, 128 levels served by the stored-coefficient tall-column kernel
  *   since mgx_init: bmask, mgx_set_field(cA) or MGX_NO_MF; 0 while the matrix-free form runs or under MGX_NO_TALL). */

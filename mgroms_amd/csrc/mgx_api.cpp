@@ -75,6 +75,7 @@ const Opt OPTIONS[] = {
   {"krylov_precision",    &State::krylov_precision, nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 32 / 64 only (no preset: the table's would pass any number by)
   {"mixed_tail",          &State::mixed_tail,       nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0 / 1 only
   {"periodic",            &State::periodic,         nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0..3 only, and not while initialised (read by mgx_init)
+  {"hold_odd_nz",         &State::hold_odd_nz,      nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0 / 1 only, and not while initialised (read by mgx_init)
   // reads as off while a time-out of this solver holds (ksp_down, which mgx_clean does not carry); set: see mgx_set_option
   {"ksp",                 &State::use_ksp,          [](const State &s) { return (s.use_ksp && !s.ksp_down) ? 1 : 0; }, "MGX_NO_KSP", ENV_ZERO, RW, true},
   {"p2p",                 nullptr,                  [](const State &s) { return s.p2p_on ? 1 : 0; }, nullptr, ENV_NONE, RW, false},   // set: see mgx_set_option
@@ -403,13 +404,13 @@ int mgx_testgalerkin(int lev, double *norm_c, double *norm_f) {
   return 0;
 }
 
-static int level_table(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int maxlev, int *out) {
-  if (nx < 2 || ny < 2 || nz < 2 || npx < 1 || npy < 1 || rank < 0 || rank >= npx * npy || periodic < 0 || periodic > 3) return -1;
-  const int nl = find_grid_levels(npx, npy, nx, ny, nz);
+static int level_table(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int hold, int maxlev, int *out) {
+  if (nx < 2 || ny < 2 || nz < 2 || npx < 1 || npy < 1 || rank < 0 || rank >= npx * npy || periodic < 0 || periodic > 3 || hold < 0 || hold > 1) return -1;
+  const int nl = find_grid_levels(npx, npy, nx, ny, nz, hold);
   if (nl < 1 || nl > maxlev) return -1;
   std::vector<Level> T(nl);
   T[0].nx = nx; T[0].ny = ny; T[0].nz = nz;
-  rank_level_table(rank, T, npx, npy, nsmall, periodic);
+  rank_level_table(rank, T, npx, npy, nsmall, periodic, hold);
   for (int l = 0; l < nl; l++) {
     const Level &L = T[l];
     const int v[12] = {L.nx, L.ny, L.nz, L.npx, L.npy, L.incx, L.incy, L.gather, L.ngx, L.ngy, L.key, L.color};
@@ -418,10 +419,13 @@ static int level_table(int nx, int ny, int nz, int npx, int npy, int rank, int n
   return nl;
 }
 int mgx_level_table(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int maxlev, int *out) {
-  return level_table(nx, ny, nz, npx, npy, rank, nsmall, 0, maxlev, out);
+  return level_table(nx, ny, nz, npx, npy, rank, nsmall, 0, 0, maxlev, out);
 }
 int mgx_level_table_periodic(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int maxlev, int *out) {
-  return level_table(nx, ny, nz, npx, npy, rank, nsmall, periodic, maxlev, out);
+  return level_table(nx, ny, nz, npx, npy, rank, nsmall, periodic, 0, maxlev, out);
+}
+int mgx_level_table_hold(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int hold, int maxlev, int *out) {
+  return level_table(nx, ny, nz, npx, npy, rank, nsmall, periodic, hold, maxlev, out);
 }
 // the first level of the tail of an fp32 cycle (option "mixed_tail") on a one-rank hierarchy, 0 = no level is small
 int mgx_mixed_tail_first(int nx, int ny, int nz, int *first) {
@@ -454,6 +458,11 @@ int mgx_set_option(const char *name, int value) {
     if (value < 0 || value > 3) return fail("periodic must be 0 (closed), 1 (the i direction, east-west), 2 (the j direction, north-south) or 3 (both), got %d", value);
     if (S.inited && value != S.periodic)
       return fail("periodic = %d: the hierarchy in use was built with periodic = %d and the option takes effect at mgx_init: call mgx_clean, set it, then mgx_init", value, S.periodic);
+  }
+  if (streq(name, "hold_odd_nz")) {
+    if (value != 0 && value != 1) return fail("hold_odd_nz must be 0 (every level halves nz, the reference's hierarchy) or 1 (an odd nz is held on the coarser levels), got %d", value);
+    if (S.inited && value != S.hold_odd_nz)
+      return fail("hold_odd_nz = %d: the hierarchy in use was built with hold_odd_nz = %d and the option takes effect at mgx_init: call mgx_clean, set it, then mgx_init", value, S.hold_odd_nz);
   }
   if (streq(name, "ksp")) { S.use_ksp = value; if (value) S.ksp_down = 0; return 0; }  // switching it on again also clears a time-out of this solver
   if (streq(name, "rbseq_timeout_ms")) { if (mgxk_set_rbseq_timeout((double)value)) return fail("rbseq_timeout_ms: could not set the device constant"); return 0; }

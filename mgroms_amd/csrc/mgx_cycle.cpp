@@ -224,10 +224,16 @@ int fine2coarse(int lev, bool dup_r, bool with_residual) {
   Level &F = S.lev[lev - 1], &C = S.lev[lev];
   const Sides phc = sides_of(C), none = {0, 0, 0, 0};
   bool fused = false;
+  // a held pair (option "hold_odd_nz": C.nz == F.nz): the 2-D restriction row by row (mgx_hold.hip), behind the residual as a launch of its own
+  const bool held = held_pair(F, C);
+  auto restrict = [&](const LevView *Cv, double *dst, Sides ph, double *dup, double *zero) {
+    if (held) mgxk_fine2coarse_held(S.stream, &F.v, Cv, dst, ph, dup, zero); else mgxk_fine2coarse(S.stream, &F.v, Cv, dst, ph, dup, zero);
+    S.n_launch++;
+  };
   // returns true when the fused residual+restriction kernel took the job
   auto down = [&](const LevView *Cv, double *dst, Sides ph, double *zero) -> int {
     if (!with_residual) return 0;
-    if (!S.exact_halos && !S.keep_r && !dup_r) {  // keep_r: the caller wants the reference's r, which the fused kernel never writes
+    if (!held && !S.exact_halos && !S.keep_r && !dup_r) {  // keep_r: the caller wants the reference's r, which the fused kernel never writes
       TicScope ts(lev, "residual_3D_8");
       if (mgxk_residual_restrict(S.stream, &F.v, Cv, dst, S.real, ph, zero)) { S.n_launch++; return 1; }
     }
@@ -238,11 +244,11 @@ int fine2coarse(int lev, bool dup_r, bool with_residual) {
     fused = all_physical(phc);
     const int d = down(&C.v, C.v.b, phc, fused ? C.v.p : nullptr);
     if (d < 0) return 1;
-    if (!d) { mgxk_fine2coarse(S.stream, &F.v, &C.v, C.v.b, phc, fused && dup_r ? C.v.r : nullptr, fused ? C.v.p : nullptr); S.n_launch++; }
+    if (!d) restrict(&C.v, C.v.b, phc, fused && dup_r ? C.v.r : nullptr, fused ? C.v.p : nullptr);
   } else {
     const int d = down(&C.vs, C.vs.b, none, nullptr);
     if (d < 0) return 1;
-    if (!d) { mgxk_fine2coarse(S.stream, &F.v, &C.vs, C.vs.b, none, nullptr, nullptr); S.n_launch++; }
+    if (!d) restrict(&C.vs, C.vs.b, none, nullptr, nullptr);
     const int Ng = C.nz * (C.vs.ny + 2) * (C.vs.nx + 2);
     if (S.p2p_on) {  // gather_3D (mg_gather.f90:95-174) as pushes into the members' gather buffers
       const unsigned long long seq = ++C.p2p_gseq;
@@ -288,11 +294,13 @@ int fine2coarse(int lev, bool dup_r, bool with_residual) {
 int coarse2fine(int lev, bool keep_r, bool skip1) {
   Level &F = S.lev[lev - 1], &C = S.lev[lev];
   const Sides phf = sides_of(F);
+  // a held pair (option "hold_odd_nz"): the 2-D prolongation row by row (mgx_hold.hip)
+  const auto prolong = held_pair(F, C) ? mgxk_coarse2fine_held : mgxk_coarse2fine;
   if (!C.gather) {
-    mgxk_coarse2fine(S.stream, &F.v, &C.v, C.v.p, S.linear, phf, keep_r, skip1 && !keep_r); S.n_launch++;
+    prolong(S.stream, &F.v, &C.v, C.v.p, S.linear, phf, keep_r, skip1 && !keep_r); S.n_launch++;
   } else {
     mgxk_split(S.stream, &C.v, &C.vs, C.v.p, C.vs.p, C.key % 2, C.key / 2); S.n_launch++;
-    mgxk_coarse2fine(S.stream, &F.v, &C.vs, C.vs.p, S.linear, phf, keep_r, skip1 && !keep_r); S.n_launch++;
+    prolong(S.stream, &F.v, &C.vs, C.vs.p, S.linear, phf, keep_r, skip1 && !keep_r); S.n_launch++;
   }
   if (S.exact_halos && keep_r) CHK(fill_halo_js(F, F.v.r, true)); else F.r_halo_stale = true;
   // p = p + r over the whole array: the interior was updated by the kernel; the halo of p + halo of r
@@ -310,7 +318,7 @@ int relax_fused(int lev, int nsweeps, int flags) {
   const int mode = rb_mode(F);
   if (mode == RB_EXACT) return 0;
   const Sides phf = sides_of(F), phc = sides_of(C);
-  if (!all_physical(phf) || !all_physical(phc) || C.gather) return 0;
+  if (!all_physical(phf) || !all_physical(phc) || C.gather || held_pair(F, C)) return 0;   // (the folded transfers halve nz)
   if (!mgxk_relax_wave_fused(S.stream, &F.v, &C.v, nsweeps, S.method, S.real, phf, flags, mode)) return 0;
   S.n_launch++;
   if (flags & 1) F.r_halo_stale = true;  // what coarse2fine leaves (the correction is not stored in r inside a cycle)
@@ -399,7 +407,8 @@ int fcycle(int have_r2) {
       bool ok = true;
       for (int q = lev - 1; q < S.nlevs && ok; q++) { const Level &Lq = S.lev[q]; ok = all_physical(sides_of(Lq)) && (q == lev - 1 || !Lq.gather); }
       if (ok) {
-        while (dep < 4 && lev + dep < S.nlevs) { dep++; vs[dep] = &S.lev[lev - 1 + dep].v; }
+        // (a held pair -- option "hold_odd_nz" -- is no 8-cell sum: the chain ends above it)
+        while (dep < 4 && lev + dep < S.nlevs && !held_pair(S.lev[lev - 1 + dep], S.lev[lev + dep])) { dep++; vs[dep] = &S.lev[lev - 1 + dep].v; }
         const Level &F = S.lev[lev - 1];
         if (dep >= 2 && F.nx % (1 << dep) == 0 && F.ny % (1 << dep) == 0 && F.nz % (1 << dep) == 0) {
           const Sides all = {1, 1, 1, 1};
@@ -548,6 +557,9 @@ int mixed_check() {
   if (S.nranks > 1) return fail("cycle_precision = 32 needs a single rank (process grid %d x %d): the halo and gather callbacks carry doubles", S.npx, S.npy);
   if (S.method == M_GS) return fail("cycle_precision = 32 does not serve relax_method = 'GS' (four colours or red-black only)");
   if (S.rb_exact) return fail("cycle_precision = 32 does not serve option rb_exact (the fp32 red-black pass is the parallel one)");
+  for (int l = 1; l < S.nlevs; l++)
+    if (held_pair(S.lev[l - 1], S.lev[l]))
+      return fail("option \"hold_odd_nz\" = 1 holds nz = %d from level %d on, which the fp32 cycles (cycle_precision = 32, krylov_precision = 32, mixed_tail) do not serve: the transfers of the fp32 shadow halve nz", S.lev[l].nz, l);
   return 0;
 }
 

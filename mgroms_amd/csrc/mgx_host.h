@@ -59,6 +59,7 @@ struct Level {
   LevView32 v32 = {};           // fp32 shadow of the mixed-precision solve_p (allocated at the first mixed solve)
   size_t n3js32 = 0;            // floats in one of its JS arrays
 };
+inline bool held_pair(const Level &F, const Level &C) { return F.nz == C.nz; }   // option "hold_odd_nz": the pair coarsens in x and y only
 inline Sides sides_of(const Level &L) { return {L.neighb[0] < 0, L.neighb[1] < 0, L.neighb[2] < 0, L.neighb[3] < 0}; }
 
 struct TicRec { int lev, sub; hipEvent_t e0, e1; };
@@ -175,6 +176,11 @@ struct State {
   // exchange(): device copies); where it has more, the neighbour is the rank at the other end of the row or column and the fill the exchange of a
   // rank seam.  One rank is then the neighbour on several sides at once: exchange_plan() orders the entries of such a peer.
   int periodic = 0;
+  // option "hold_odd_nz" (0 default, 1): read by mgx_init.  A level with an odd nz hands its nz on to the next level, which then coarsens in x and
+  // y only (a "held pair": F.nz == C.nz), down to the horizontal bound of the hierarchy, instead of the reference's nz / 2 that drops the top row
+  // and diverges.  The transfers of a held pair are the reference's 2-D operators row by row (mgx_hold.hip); every fast path that
+  // assumes nz_c = nz_f / 2 declines such a pair.  0: the reference's table, word for word.
+  int hold_odd_nz = 0;
   int c2f_skip = 1;   // the cycles' prolongation leaves the columns alone that the first colour of the following four-colour relax overwrites unread (option "c2f_skip", MGX_C2F_NOSKIP=1)
   long long n_launch = 0, n_halo = 0, n_exch = 0, n_allred = 0;
   std::string err, transport_name;
@@ -227,8 +233,8 @@ void options_restore(const std::vector<int> &);   // ... and back into the fresh
 int dmalloc(double **p, size_t n);
 int roundup(int a, int m);
 void make_view(LevView &v, int nx, int ny, int nz);
-int find_grid_levels(int npxg, int npyg, int nx, int ny, int nz);
-void rank_level_table(int rank, std::vector<Level> &T, int npx0, int npy0, int nsmall, int periodic = 0);
+int find_grid_levels(int npxg, int npyg, int nx, int ny, int nz, int hold = 0);
+void rank_level_table(int rank, std::vector<Level> &T, int npx0, int npy0, int nsmall, int periodic = 0, int hold = 0);
 void set_window_planes(bool known = true);
 enum { DM_ALL = 0, DM_ZETA = 1 };
 int define_matrices(int what = DM_ALL, bool may_return_early = false);

@@ -107,6 +107,10 @@ void mgxk_gather_place_wait(hipStream_t st, const LevView *C, double *dstjs, con
                             unsigned long long *flag, unsigned long long seq, int *err);
 void mgxk_split(hipStream_t st, const LevView *C, const LevView *Cs, const double *pc, double *dst, int l, int m);
 
+// ---- mgx_hold.hip ----
+void mgxk_fine2coarse_held(hipStream_t st, const LevView *F, const LevView *C, double *dst, Sides ph, double *dup, double *zero);
+void mgxk_coarse2fine_held(hipStream_t st, const LevView *F, const LevView *C, const double *src, int linear, Sides ph, int keep_r, int skip1);
+
 // ---- mgx_setup.hip ----
 void mgxs_coarsen2d(hipStream_t st, const double *src, double *dst, int nyf, int nyc, int nxc, double fac);
 void mgxs_rect(hipStream_t st, double *a, double *buf, const RectOp *R);

@@ -351,16 +351,22 @@ def _table(nl, out, what):
     return res
 
 
-def level_table(nx, ny, nz, npx=1, npy=1, rank=0, nsmall=8):
-    """Level hierarchy of `rank` (mg_grids.f90:468-738) as a list of dicts; pure host logic, no GPU needed."""
+def level_table(nx, ny, nz, npx=1, npy=1, rank=0, nsmall=8, hold_odd_nz=0):
+    """Level hierarchy of `rank` (mg_grids.f90:468-738) as a list of dicts; pure host logic, no GPU needed.
+    hold_odd_nz=1: the table mgx_init builds under option "hold_odd_nz" -- an odd nz is handed on to the coarser levels, which go on
+    coarsening in x and y down to the horizontal bound (include/mgx.h: mgx_level_table_hold)."""
     out = (C.c_int * (20 * 32))()
+    if hold_odd_nz:
+        return _table(lib().mgx_level_table_hold(nx, ny, nz, npx, npy, rank, nsmall, 0, int(hold_odd_nz), 32, out), out, "level_table")
     return _table(lib().mgx_level_table(nx, ny, nz, npx, npy, rank, nsmall, 32, out), out, "level_table")
 
 
-def level_table_periodic(nx, ny, nz, npx=1, npy=1, rank=0, nsmall=8, periodic=0):
+def level_table_periodic(nx, ny, nz, npx=1, npy=1, rank=0, nsmall=8, periodic=0, hold_odd_nz=0):
     """level_table with option "periodic" (bit 1: i, bit 2: j): the neighbour past the end of a periodic row or column of ranks is the rank
-    at its other end, the rank itself on a level with one rank along the direction; pure host logic."""
+    at its other end, the rank itself on a level with one rank along the direction; pure host logic.  hold_odd_nz: as in level_table."""
     out = (C.c_int * (20 * 32))()
+    if hold_odd_nz:
+        return _table(lib().mgx_level_table_hold(nx, ny, nz, npx, npy, rank, nsmall, periodic, int(hold_odd_nz), 32, out), out, "level_table_periodic")
     return _table(lib().mgx_level_table_periodic(nx, ny, nz, npx, npy, rank, nsmall, periodic, 32, out), out, "level_table_periodic")
 
 
