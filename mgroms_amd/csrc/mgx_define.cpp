@@ -460,7 +460,7 @@ int mgx_init(int nx, int ny, int nz, int npx, int npy, int rank, const mgx_param
     if (np > max_part) max_part = np;
   }
   S.npartial = (int)max_part;
-  CHK(dmalloc(&S.d_partial, max_part));
+  CHK(dmalloc(&S.d_partial, 2 * max_part));  // the residual norms leave a pair per workgroup (dd_add, mgx_device.h)
   CHK(dmalloc(&S.d_scalar, 8));
   if (S.method == M_RB && S.real) CHK(dmalloc(&S.rho_dev, 32));
   HIPCHK(hipHostMalloc((void **)&S.h_scalar, 8 * sizeof(double)));

@@ -81,6 +81,22 @@ extern thread_local hipError_t mgx_pending_error;  // mgx_comm.cpp
 static inline void mgx_before_launch() { const hipError_t e = hipGetLastError(); if (e != hipSuccess && mgx_pending_error == hipSuccess) mgx_pending_error = e; }
 static inline int mgx_launched() { return hipGetLastError() == hipSuccess ? 1 : 0; }
 
+// The sum of r^2 of a residual norm, carried as an unevaluated pair hi + lo (Knuth's two-sum: the rounding error of every addition to
+// hi is exact and goes to lo; compiled with -ffp-contract=off and without reassociation).  The pair holds the sum to ~2^-100, so its
+// rounded value does not depend on how a kernel groups the cells: k_residual, k_residual_mf and the fused residual + restriction
+// (mgx_resrest.hip), whose lanes, waves and workgroups cut the level differently, leave the same norm.  Each term is one cell's rounded
+// r * r.  Partials: hi at partial[idx], lo at partial[n + idx], n = the launch's workgroups; k_reduce_partials_dd closes them.
+__device__ __forceinline__ void dd_add(double &hi, double &lo, const double t) {
+  const double s = hi + t, bb = s - hi;
+  lo = lo + ((hi - (s - bb)) + (t - bb));
+  hi = s;
+}
+__device__ __forceinline__ void dd_merge(double &hi, double &lo, const double ohi, const double olo) {
+  const double s = hi + ohi, bb = s - hi;
+  lo = (lo + olo) + ((hi - (s - bb)) + (ohi - bb));
+  hi = s;
+}
+
 static inline dim3 col_grid(int ncol_half, int nplanes, int z = 1) { return dim3((ncol_half + WAVE - 1) / WAVE, (nplanes + 3) / 4, z); }
 
 // ---- helpers shared by the smoother translation units ---------------------------------------------------------------
@@ -91,6 +107,10 @@ static inline dim3 col_grid(int ncol_half, int nplanes, int z = 1) { return dim3
 #define RCP_REF(b) ({ const double b_ = (b); double r_ = __builtin_amdgcn_rcp(b_); double e_ = __builtin_fma(-b_, r_, 1.0); r_ = __builtin_fma(r_, e_, r_); \
                       e_ = __builtin_fma(-b_, r_, 1.0); __builtin_fma(r_, e_, r_); })
 #define DIVC(a, b, rb) ({ const double a_ = (a); const double q_ = a_ * (rb); const double e_ = __builtin_fma(-(b), q_, a_); __builtin_fma(e_, (rb), q_); })
+// zw(kk, column q) by its generating formula (mg_zr_zw.f90:140-145): ONE text for the colour passes (MF_ROW, mgx_relax_common.h) and the
+// residual + restriction (mgx_resrest.hip), whose generated slots 4 / 7 must be the same bits.  In scope: the sigma tables cffw, csw and
+// h, hinv, zeta of the caller's columns as hh[], hv[], hz[].
+#define ZW_GEN(kk, q) ({ const double z0_ = cffw[(kk)-1] + csw[(kk)-1] * hh[q]; z0_ * hh[q] * hv[q] + hz[q] * (1. + z0_ * hv[q]); })
 // The j-1 and j+1 neighbours of a column sit side by side in the other half-row (jp = jm + 1): ONE 16-byte load per lane fetches
 // both, instead of two 8-byte loads whose wave-wide footprints overlap by 63/64 (half the wave-level requests for these streams;
 // 8-byte alignment only: gfx950 global loads do not need natural alignment)

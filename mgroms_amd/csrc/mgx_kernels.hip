@@ -15,7 +15,7 @@
 // 1-D grid of gx * gy * 2 blocks (op_block_map): bz = 0 handles the odd-j half-rows, bz = 1 the even-j ones.
 // ------------------------------------------------------------------------------------------------
 #define RES_RHS(ko) b[ko]
-#define RES_SINK(ro, ko, rr) { r[ko] = rr; mirror_store(L, r, ro, jcol, i, c, rr, ph); acc = acc + rr * rr; }
+#define RES_SINK(ro, ko, rr) { r[ko] = rr; mirror_store(L, r, ro, jcol, i, c, rr, ph); dd_add(acc, acl, rr * rr); }
 template <bool REAL>
 __global__ __launch_bounds__(256) void k_residual(LevView L, double *__restrict__ partial, int want_norm, int gx, int gy, Sides ph, int stream) {
   int bx, by, bz;
@@ -23,7 +23,7 @@ __global__ __launch_bounds__(256) void k_residual(LevView L, double *__restrict_
   const int jh = bx * WAVE + threadIdx.x;
   const int i = 1 + by * blockDim.y + threadIdx.y;
   const int jodd = bz == 0;
-  double acc = 0.0;
+  double acc = 0.0, acl = 0.0;  // the sum of r^2 as a pair (dd_add, mgx_device.h)
   if (jh < (L.ny >> 1) && i <= L.nx) {
     int c, jm, jp;
     COL_POS(L, jh, jodd, c, jm, jp)
@@ -32,12 +32,12 @@ __global__ __launch_bounds__(256) void k_residual(LevView L, double *__restrict_
     OP_COLUMN(OP_P, RES_RHS, RES_SINK)
   }
   if (!want_norm) return;
-  OP_BLOCK_SUM(acc, partial, blockIdx.x)
+  OP_BLOCK_SUM_DD(acc, acl, partial, blockIdx.x, gridDim.x)
 }
 
 // residual with matrix-free cross terms (OP_COLUMN_MF, mgx_operator.h): b and r of a level that does not fit the caches are streamed past them
 #define RES_RHS_MF(ko) ld_rt(b + ko, stream)
-#define RES_SINK_MF(ro, ko, rr) { st_rt(r + ko, rr, stream); mirror_store(L, r, ro, jodd ? 2 * jh + 1 : 2 * jh + 2, i, c, rr, ph); acc = acc + rr * rr; }
+#define RES_SINK_MF(ro, ko, rr) { st_rt(r + ko, rr, stream); mirror_store(L, r, ro, jodd ? 2 * jh + 1 : 2 * jh + 2, i, c, rr, ph); dd_add(acc, acl, rr * rr); }
 template <bool REAL>
 __global__ __launch_bounds__(256) void k_residual_mf(LevView L, double *__restrict__ partial, int want_norm, int gx, int gy, Sides ph, int stream) {
   int bx, by, bz;
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void k_residual_mf(LevView L, double *__restri
   const int jh = bx * WAVE + threadIdx.x;
   const int i = 1 + by * blockDim.y + threadIdx.y;
   const int jodd = bz == 0;
-  double acc = 0.0;
+  double acc = 0.0, acl = 0.0;  // the sum of r^2 as a pair (dd_add, mgx_device.h)
   if (jh < (L.ny >> 1) && i <= L.nx) {
     int c, jm, jp;
     COL_POS(L, jh, jodd, c, jm, jp)
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void k_residual_mf(LevView L, double *__restri
     OP_COLUMN_MF(OP_P, OP_P2, RES_RHS_MF, RES_SINK_MF)
   }
   if (!want_norm) return;
-  OP_BLOCK_SUM(acc, partial, blockIdx.x)
+  OP_BLOCK_SUM_DD(acc, acl, partial, blockIdx.x, gridDim.x)
 }
 
 // sum of squares of the interior of a JS field (bnorm of solve_p, mg_solvers.f90:50)
@@ -95,6 +95,23 @@ __global__ __launch_bounds__(256) void k_reduce_partials(const double *__restric
     __syncthreads();
   }
   if (threadIdx.x == 0) out[0] = red[0];
+}
+
+// second stage of a sum whose n partials are pairs (dd_add, mgx_device.h: hi at partial[q], lo at partial[n + q]) -> out[0], rounded once
+__global__ __launch_bounds__(256) void k_reduce_partials_dd(const double *__restrict__ partial, int n, double *__restrict__ out) {
+  __shared__ double red[512];
+  double s = 0.0, sl = 0.0;
+  for (int q = threadIdx.x; q < n; q += 256) dd_merge(s, sl, partial[q], partial[n + q]);
+  red[threadIdx.x] = s; red[256 + threadIdx.x] = sl;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) {
+      dd_merge(s, sl, red[threadIdx.x + off], red[256 + threadIdx.x + off]);
+      red[threadIdx.x] = s; red[256 + threadIdx.x] = sl;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = s + sl;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -729,10 +746,10 @@ void mgxk_residual(hipStream_t st, const LevView *L, double *partial, double *ou
     else hipLaunchKernelGGL((k_residual_mf<false>), grd, blk, 0, st, *L, partial, want_norm, gx, gy, ph, level_streams(L));
   } else if (real) hipLaunchKernelGGL((k_residual<true>), grd, blk, 0, st, *L, partial, want_norm, gx, gy, ph, level_streams(L));
   else hipLaunchKernelGGL((k_residual<false>), grd, blk, 0, st, *L, partial, want_norm, gx, gy, ph, level_streams(L));
-  if (want_norm) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, st, partial, (int)grd.x, out);
+  if (want_norm) hipLaunchKernelGGL(k_reduce_partials_dd, dim3(1), dim3(256), 0, st, partial, (int)grd.x, out);
 }
-// second stage of a norm whose partials another kernel wrote (one per workgroup, summed in index order)
-void mgxk_reduce(hipStream_t st, const double *partial, int n, double *out) { hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, st, partial, n, out); }
+// second stage of a norm whose partials another kernel wrote (one pair per workgroup: the fused residual + restriction, mgx_resrest.hip)
+void mgxk_reduce(hipStream_t st, const double *partial, int n, double *out) { hipLaunchKernelGGL(k_reduce_partials_dd, dim3(1), dim3(256), 0, st, partial, n, out); }
 void mgxk_sumsq(hipStream_t st, const LevView *L, const double *a, double *partial, double *out) {
   dim3 blk(WAVE, 4), grd = col_grid(L->ny / 2, L->nx, 2);
   hipLaunchKernelGGL(k_sumsq, grd, blk, 0, st, *L, a, partial);

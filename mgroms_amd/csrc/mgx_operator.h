@@ -39,6 +39,22 @@ __device__ __forceinline__ void op_block_map(int gx, int gy, int &bx, int &by, i
     }                                                                                                                                        \
   }
 
+// The same for a sum carried as a pair (dd_add, mgx_device.h): hi -> partial[idx], lo -> partial[n + idx], n = the launch's workgroups
+#define OP_BLOCK_SUM_DD(acc, acl, partial, idx, n)                                                                                           \
+  {                                                                                                                                          \
+    for (int off = 32; off > 0; off >>= 1) { const double oh_ = __shfl_down(acc, off, 64), ol_ = __shfl_down(acl, off, 64); dd_merge(acc, acl, oh_, ol_); } \
+    __shared__ double red[32];                                                                                                               \
+    const int tid = threadIdx.y * blockDim.x + threadIdx.x, w = tid >> 6;                                                                    \
+    if ((tid & 63) == 0) { red[w] = acc; red[16 + w] = acl; }                                                                                \
+    __syncthreads();                                                                                                                         \
+    if (tid == 0) {                                                                                                                          \
+      double s = 0.0, sl = 0.0;                                                                                                              \
+      const int nw = (blockDim.x * blockDim.y + 63) >> 6;                                                                                    \
+      for (int q = 0; q < nw; q++) dd_merge(s, sl, red[q], red[16 + q]);                                                                     \
+      partial[idx] = s; partial[(n) + (idx)] = sl;                                                                                           \
+    }                                                                                                                                        \
+  }
+
 // ------------------------------------------------------------------------------------------------
 // The column from the stored slots: rr(k) = rhs(k) - (A p)(k), k = 1 .. nz, one lane = one (j, i) column.
 // The caller has in scope: REAL (compile-time); L, i, jh, jodd, c, jm, jp; and three hooks,

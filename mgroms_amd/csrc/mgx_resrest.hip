@@ -13,7 +13,14 @@
 // levels of up to 256x256x64 cells take k_residual_restrict_flat below (256x256x32: 24 us against 47 + 13).
 // The residuals and the 8-term sum use the reference's expressions in the reference's order: b_c is bit-identical to
 // compute_residual followed by fine2coarse.  Matrix-free cross terms (needs the slopes zy, zx: the matrix must be the one
-// define_matrices built); other cases keep the two separate kernels.
+// define_matrices built); other cases keep the two separate kernels.  The norm of the closing residual (NORM) is bit-identical too:
+// here and in k_residual / k_residual_mf the sum of r^2 is carried as a pair and rounded once (dd_add, mgx_device.h), so the way a
+// kernel groups the cells does not reach it.
+// ZW (the walking form without the norm, where the level carries the 2-D factors and sigma tables of the smoother's ZW form): the
+// interior rows of slots 4 and 7 are not streamed either but generated from the depth formula, with the smoother's expressions
+// (ZW_GEN, RCP_REF, DIVC of mgx_device.h; MF_ROW of mgx_relax_common.h) -- same bits, 755 MB moved instead of 1005 (FETCH x 2 + WRITE)
+// and 197-199 us instead of 216-219 at 512x512x64.  The kernel then issues ~650 instructions per row on its one wave per SIMD: it is
+// bound by issue, not by its 3.8 TB/s, which is why a quarter less traffic buys a tenth of the time (profiles/resrest_zw.json).
 #include "mgx_switches.h"
 #include "mgx_device.h"
 
@@ -46,7 +53,6 @@ struct Geo {
 
 // jA-1 and jB sit side by side in the even half-row, jA and jB+1 in the odd one (c[2] = c[0] + 1, c[3] = c[1] + 1): one 16-byte
 // load per pair instead of two 8-byte loads whose wave-wide footprints overlap
-#define LD_PAIR(ptr, A, B) { double2 t2_; __builtin_memcpy(&t2_, (ptr), 16); A = t2_.x; B = t2_.y; }
 __device__ __forceinline__ void load_w(RowW &w, const LevView &F, const Geo &g, const long long ro) {
   const double *__restrict__ p = F.p, *__restrict__ zy = F.zy, *__restrict__ zx = F.zx, *__restrict__ a2 = F.cA[1];
   LD_PAIR(p + g.o + ro + g.c[0], w.P[0], w.P[2])
@@ -61,32 +67,62 @@ __device__ __forceinline__ void load_w(RowW &w, const LevView &F, const Geo &g, 
   }
 }
 
+// ZW: without slots 4 and 7 (the walking form generates them, k_residual_restrict)
+template <bool ZW = false>
 __device__ __forceinline__ void load_r(RowR &r, const LevView &F, const Geo &g, const long long ro) {
   const double *__restrict__ b = F.b, *__restrict__ zx = F.zx, *__restrict__ a4 = F.cA[3], *__restrict__ a7 = F.cA[6];
-  LD_PAIR(a4 + g.o + ro + g.c[1], r.A4[0], r.A4[2])
-  r.A4[1] = a4[g.o + ro + g.c[2]];
+  if (!ZW) {
+    LD_PAIR(a4 + g.o + ro + g.c[1], r.A4[0], r.A4[2])
+    r.A4[1] = a4[g.o + ro + g.c[2]];
+  }
 #pragma unroll
   for (int jj = 0; jj < 2; jj++) {
     const int c = g.c[jj + 1];
     r.ZXm[jj] = zx[g.om + ro + c]; r.ZXp[jj] = zx[g.op + ro + c];
-    r.A7[jj] = a7[g.o + ro + c]; r.A7p[jj] = a7[g.op + ro + c];
+    if (!ZW) { r.A7[jj] = a7[g.o + ro + c]; r.A7p[jj] = a7[g.op + ro + c]; }
     r.B[jj] = b[g.o + ro + c];
   }
 }
+// slots 4 and 7 of one row alone (ZW: rows 1 and nz, whose formulas differ, stay stored)
+__device__ __forceinline__ void load_s(RowR &r, const LevView &F, const Geo &g, const long long ro) {
+  const double *__restrict__ a4 = F.cA[3], *__restrict__ a7 = F.cA[6];
+  LD_PAIR(a4 + g.o + ro + g.c[1], r.A4[0], r.A4[2])
+  r.A4[1] = a4[g.o + ro + g.c[2]];
+#pragma unroll
+  for (int jj = 0; jj < 2; jj++) { const int c = g.c[jj + 1]; r.A7[jj] = a7[g.o + ro + c]; r.A7p[jj] = a7[g.op + ro + c]; }
+}
+
+// the value of lane ^ m, every lane of the wave active: what __shfl_xor(x, m, 64) moves, without its width test, whose operands the
+// walking form's ZW instance has no registers to keep
+__device__ __forceinline__ double lane_xor(double x, int m) {
+  const int idx = (__lane_id() ^ m) << 2;
+  const int lo = __builtin_amdgcn_ds_bpermute(idx, __double2loint(x)), hi = __builtin_amdgcn_ds_bpermute(idx, __double2hiint(x));
+  return __hiloint2double(hi, lo);
+}
+#define RR_XOR(x, m) (ZW ? lane_xor(x, m) : __shfl_xor(x, m, 64))
 
 }  // namespace
 
 // grid: 1-D, gx j-chunks of 32 coarse columns x gy groups of blockDim.y coarse planes, XCD-aware as k_relax_nz.
 // One wave per SIMD (AW = AR = 1: four window rows + two row buffers, ~450 registers with the requests kept ahead of their use;
 // squeezed to 256 registers for two waves per SIMD it spills and loses: 250 vs 236 us at 512x512x64 in round 2).
-// NORM: also the sum of r^2 over the block's fine cells -> partial[blockIdx.x] (the closing compute_residual of a solve_p iteration,
+// ZW: 496 registers, no scratch, 18 KB of LDS -- six depth columns per lane (two more come from the partner lane), both depth rows of a
+// step generated at the step, row nz's stored values parked in LDS; AW = AR = 1 and no NORM (neither fits beside it).
+// NORM: also the sum of r^2 over the block's fine cells, as a pair -> partial[blockIdx.x], partial[gridDim.x + blockIdx.x] (the closing compute_residual of a solve_p iteration,
 // mg_solvers.f90:65, whose r the next Fcycle restricts first thing, :112-115: one pass over the level instead of two and no r written).
 // dup: a second destination of the coarse sums (Fcycle's grid(lev+1)%r = grid(lev+1)%b, :113).
-template <bool REAL, int AW, int AR, bool NORM = false>
+template <bool REAL, int AW, int AR, bool NORM = false, bool ZW = false>
 __global__ __launch_bounds__(256, 1) void k_residual_restrict(LevView F, LevView C, double *__restrict__ dst, Sides ph, double *__restrict__ zero, int gx, int gy,
                                                              double *__restrict__ partial = nullptr, double *__restrict__ dup = nullptr) {
-  __shared__ double red_ss[4];
-  double ss = 0.0;
+  __shared__ double red_ss[8];  // the waves' sums of r^2, pairs (dd_add, mgx_device.h): hi 0-3, lo 4-7
+  // ZW without NORM only: with the lane's sum of r^2 beside everything else the form does not fit the registers, and with that sum kept
+  // in LDS (one read and one write per row) it fits and loses: solve_p 296.1 against 297.5 it/s (profiles/resrest_zw.json)
+  static_assert(!(ZW && NORM), "the closing residual of solve_p streams its slots");
+  // ZW: what the registers have no room to carry up the column, one entry per lane (nobody else's: no barrier): what the prologue reads
+  // and row nz alone needs, the stored slots 4 / 7 of that row (0-6) and its diagonal (7, 8)
+  __shared__ double park[ZW ? 9 * 256 : 1];
+  const double *parked = park + threadIdx.y * 64 + threadIdx.x;
+  double ss = 0.0, sl = 0.0;
   int bx, by;
   if ((gy & 7) == 0) { const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3; by = xcd * (gy >> 3) + local / gx; bx = local - (local / gx) * gx; }
   else { by = blockIdx.x / gx; bx = blockIdx.x - by * gx; }
@@ -94,7 +130,7 @@ __global__ __launch_bounds__(256, 1) void k_residual_restrict(LevView F, LevView
   int j2 = 1 + bx * 32 + (threadIdx.x & 31);
   const int i2 = 1 + by * blockDim.y + threadIdx.y;
   if (i2 > C.nx) {                                       // wave-uniform
-    if (NORM) { if ((threadIdx.x & 63) == 0) red_ss[threadIdx.y] = 0.0; __syncthreads(); if (threadIdx.x == 0 && threadIdx.y == 0) partial[blockIdx.x] = red_ss[0] + red_ss[1] + red_ss[2] + red_ss[3]; }
+    if (NORM) { if ((threadIdx.x & 63) == 0) { red_ss[threadIdx.y] = 0.0; red_ss[4 + threadIdx.y] = 0.0; } __syncthreads(); }  // wave 0 always has a plane: it closes the block's sum
     return;
   }
   const bool live = j2 <= C.ny;
@@ -123,6 +159,37 @@ __global__ __launch_bounds__(256, 1) void k_residual_restrict(LevView F, LevView
       e[jj][4] = a8[g.o + c]; e[jj][5] = F.p[g.om + jm]; e[jj][6] = a8[g.op + jp]; e[jj][7] = F.p[g.op + jp];
     }
   }
+  // ZW: the stored slots 4 / 7 of rows 1 and nz (their formulas differ, mg_define_matrix.f90:361-372, 577-590); h, hinv, zeta of the
+  // six depth columns (0-3: jA-1, jA, jB, jB+1 of the own plane; 4, 5: jA, jB of the FAR plane, i-1 for half 0 and i+1 for half 1);
+  // the column factors of slots 4 (jA, jB, jB+1) and 7 (own plane, plane i+1) with the refined reciprocals of their divisors
+  double hh[6], hv[6], hz[6];
+  double m4[3], d4[3], r4[3], m7[2], d7[2], r7[2], m7p[2], d7p[2], r7p[2];
+  const double *__restrict__ cffw = F.cffw, *__restrict__ csw = F.csw;
+  RowR S1;
+  if (ZW) {
+    RowR Sn;
+    load_s(S1, F, g, 0);
+    load_s(Sn, F, g, (long long)(nz - 1) * RS);
+    const long long q2 = (long long)(2 * i2 - 1 + half) * RS, qf = half ? q2 + RS : q2 - RS;
+#pragma unroll
+    for (int jj = 0; jj < 2; jj++) {
+      hh[4 + jj] = F.h2[qf + g.c[jj + 1]]; hv[4 + jj] = F.hi2[qf + g.c[jj + 1]]; hz[4 + jj] = F.ze2[qf + g.c[jj + 1]];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++) { hh[q] = F.h2[q2 + g.c[q]]; hv[q] = F.hi2[q2 + g.c[q]]; hz[q] = F.ze2[q2 + g.c[q]]; }
+#pragma unroll
+    for (int q = 0; q < 3; q++) { m4[q] = F.m4[q2 + g.c[q + 1]]; d4[q] = F.d4[q2 + g.c[q + 1]]; r4[q] = RCP_REF(d4[q]); }
+#pragma unroll
+    for (int jj = 0; jj < 2; jj++) {
+      m7[jj] = F.m7[q2 + g.c[jj + 1]]; d7[jj] = F.d7[q2 + g.c[jj + 1]]; r7[jj] = RCP_REF(d7[jj]);
+      m7p[jj] = F.m7[q2 + RS + g.c[jj + 1]]; d7p[jj] = F.d7[q2 + RS + g.c[jj + 1]]; r7p[jj] = RCP_REF(d7p[jj]);
+    }
+    double *mine = park + threadIdx.y * 64 + threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < 3; q++) mine[q * 256] = Sn.A4[q];
+#pragma unroll
+    for (int jj = 0; jj < 2; jj++) { mine[(3 + jj) * 256] = Sn.A7[jj]; mine[(5 + jj) * 256] = Sn.A7p[jj]; mine[(7 + jj) * 256] = dlast[jj]; }
+  }
   // Look-ahead: the window rows are requested AW steps and the rows' own values AR steps before their first use (A/B of the depths,
   // scripts/probe/ab_resrest_ahead.sh: (1,1) 224 us, (1,2) 233, (2,1) 225 -- once the requests are unconditional, below, the depth is
   // not what bounds the kernel).
@@ -137,17 +204,17 @@ __global__ __launch_bounds__(256, 1) void k_residual_restrict(LevView F, LevView
   // round trip per row, whatever AW / AR).
 #pragma unroll
   for (int q = 0; q < AW + 2; q++) load_w(W[q], F, g, (long long)(q + 1 <= nz ? q : nz - 1) * RS);
-  load_r(R[NRB - 1], F, g, 0);
+  load_r<ZW>(R[NRB - 1], F, g, 0);
 #pragma unroll
-  for (int q = 0; q < AR - 1; q++) load_r(R[q], F, g, (long long)(q + 2 <= nz ? q + 1 : nz - 1) * RS);
+  for (int q = 0; q < AR - 1; q++) load_r<ZW>(R[q], F, g, (long long)(q + 2 <= nz ? q + 1 : nz - 1) * RS);
   double z = 0.0;
   const long long oc = (long long)i2 * C.plane + jpos(C, j2);
 
   // one fine row k: Wm / W0 / Wp hold rows k-1, k, k+1; Wn receives row k+1+AW and Rn row k+AR while row k is computed
 #define RR_LOADS(k, Wn, Rn)                                                                                                 \
     load_w(Wn, F, g, (long long)((k) + 1 + AW <= nz ? (k) + AW : nz - 1) * RS);                                              \
-    load_r(Rn, F, g, (long long)((k) + AR <= nz ? (k) + AR - 1 : nz - 1) * RS);
-#define RR_CELL_IN(Wm, W0, Wp, R0)                                                                                          \
+    load_r<ZW>(Rn, F, g, (long long)((k) + AR <= nz ? (k) + AR - 1 : nz - 1) * RS);
+#define RR_CELL_IN(Wm, W0, Wp, R0, S4, S7, S7P)                                                                                        \
       const double pc_m = Wm.P[jj + 1], pc_0 = W0.P[jj + 1], pc_p = Wp.P[jj + 1];                                            \
       const double pjm_m = Wm.P[jj], pjm_0 = W0.P[jj], pjm_p = Wp.P[jj];                                                     \
       const double pjp_m = Wm.P[jj + 2], pjp_0 = W0.P[jj + 2], pjp_p = Wp.P[jj + 2];                                         \
@@ -156,7 +223,7 @@ __global__ __launch_bounds__(256, 1) void k_residual_restrict(LevView F, LevView
       const double zy_m = Wm.ZY4[jj + 1], zy_p = Wp.ZY4[jj + 1], zx_m = Wm.ZX[jj], zx_p = Wp.ZX[jj];                         \
       const double zyjm = W0.ZY4[jj], zyjp = W0.ZY4[jj + 2];                                                                \
       const double zxim = R0.ZXm[jj], zxip = R0.ZXp[jj];                                                                    \
-      const double a4o = R0.A4[jj], a4jp = R0.A4[jj + 1], a7o = R0.A7[jj], a7ip = R0.A7p[jj];                                \
+      const double a4o = S4[jj], a4jp = S4[jj + 1], a7o = S7[jj], a7ip = S7P[jj];                                            \
       const double a2_0 = W0.A2[jj], a2_p = Wp.A2[jj];                                                                      \
       const double c3 = qrt * (zy_p + zyjm), c3m = qrt * (zyjp + zy_m), c5 = -qrt * (zy_m + zyjm), c5m = -qrt * (zyjp + zy_p); \
       const double c6 = qrt * (zx_p + zxim), c6m = qrt * (zxip + zx_m), c8 = -qrt * (zx_m + zxim), c8m = -qrt * (zxip + zx_p); \
@@ -164,8 +231,8 @@ __global__ __launch_bounds__(256, 1) void k_residual_restrict(LevView F, LevView
   /* fine2coarse_3D (mg_intergrids.f90:149-160): (k,jA,iA) + (k,jA,iB) + (k,jB,iA) + (k,jB,iB), then the same of k+1;
      the iB values come from the partner lane (lane ^ 32) */
 #define RR_SUM(k, r)                                                                                                        \
-    if (NORM && live) ss = ss + (r[0] * r[0] + r[1] * r[1]);                                                                \
-    const double rA_B = __shfl_xor(r[0], 32, 64), rB_B = __shfl_xor(r[1], 32, 64);                                          \
+    if (NORM && live) { dd_add(ss, sl, r[0] * r[0]); dd_add(ss, sl, r[1] * r[1]); }                                         \
+    const double rA_B = RR_XOR(r[0], 32), rB_B = RR_XOR(r[1], 32);                                                          \
     if ((k) & 1) z = r[0] + rA_B + r[1] + rB_B;                                                                             \
     else {                                                                                                                  \
       z = z + r[0] + rA_B + r[1] + rB_B;                                                                                    \
@@ -187,30 +254,63 @@ __global__ __launch_bounds__(256, 1) void k_residual_restrict(LevView F, LevView
                       - c8 * pim_m - c8m * pip_p;                                                                            \
       }
   /* last row, :498-509 (stored diagonal) */
-#define RR_LAST(rr, R0)                                                                                                     \
+#define RR_LAST(rr, R0, DL)                                                                                                 \
       {                                                                                                                     \
-        rr = R0.B[jj] - dlast[jj] * pc_0 - a2_0 * pc_m - c3m * pjp_m - a4o * pjm_0 - a4jp * pjp_0                           \
+        rr = R0.B[jj] - (DL) * pc_0 - a2_0 * pc_m - c3m * pjp_m - a4o * pjm_0 - a4jp * pjp_0                           \
                       - c5 * pjm_m - c6m * pip_m - a7o * pim_0 - a7ip * pip_0 - c8 * pim_m;                                  \
       }
+  /* ZW: zw of row kk (mg_zr_zw.f90:140-145, ZW_GEN of mgx_device.h) at jA-1, jA, jB, jB+1 of the own plane (zo) and at jA, jB of planes
+     i-1 (zm) and i+1 (zp).  One of the two is the partner's plane (lane ^ 32: i+1 for half 0, i-1 for half 1), whose depths are the
+     partner's own zo[1], zo[2]; the far one is generated here.  A select, not a branch: both halves take part in the exchange. */
+#define RR_ZW_ROW(kk, zo, zm, zp)                                                                                           \
+    {                                                                                                                       \
+      const int kz_ = (kk);  /* the caller's row expression may name q */                                                   \
+      _Pragma("unroll") for (int q = 0; q < 4; q++) zo[q] = ZW_GEN(kz_, q);                                                  \
+      _Pragma("unroll") for (int jj = 0; jj < 2; jj++) {                                                                     \
+        double zf_;                                                                                                         \
+        zf_ = ZW_GEN(kz_, 4 + jj);                                                                                                       \
+        const double zx_ = lane_xor(zo[jj + 1], 32);                                                                        \
+        zm[jj] = half ? zx_ : zf_; zp[jj] = half ? zf_ : zx_;                                                               \
+      }                                                                                                                     \
+    }
+  /* ZW: slots 4 and 7 of row k (a4 at jA, jB, jB+1; a7 at jA, jB of the own plane and of plane i+1), not streamed: the interior formula
+     (mg_define_matrix.f90:532-534, 549-551) as MF_ROW of mgx_relax_common.h spells it, on zw of rows k and k+1 -- both generated at
+     the step: a carried row k costs 16 registers that the walk does not have; row nz from where the prologue parked it */
+#define RR_SLOTS(k)                                                                                                         \
+    double s4[3], s7[2], s7p[2];                                                                                            \
+    if (!ZW) ;                                                                                                              \
+    else if ((k) < nz) {                                                                                                    \
+      double zlo[4], zlm[2], zlp[2], zhi[4], zhm[2], zhp[2];                                                                \
+      RR_ZW_ROW(k, zlo, zlm, zlp)                                                                                           \
+      RR_ZW_ROW((k) + 1, zhi, zhm, zhp)                                                                                     \
+      _Pragma("unroll") for (int q = 0; q < 3; q++) s4[q] = DIVC(qrt * (zhi[q + 1] - zlo[q + 1] + zhi[q] - zlo[q]) * m4[q], d4[q], r4[q]); \
+      _Pragma("unroll") for (int jj = 0; jj < 2; jj++) {                                                                     \
+        s7[jj] = DIVC(qrt * (zhi[jj + 1] - zlo[jj + 1] + zhm[jj] - zlm[jj]) * m7[jj], d7[jj], r7[jj]);                       \
+        s7p[jj] = DIVC(qrt * (zhp[jj] - zlp[jj] + zhi[jj + 1] - zlo[jj + 1]) * m7p[jj], d7p[jj], r7p[jj]);                   \
+      }                                                                                                                     \
+    } else { _Pragma("unroll") for (int q = 0; q < 3; q++) s4[q] = parked[q * 256];                                          \
+             _Pragma("unroll") for (int jj = 0; jj < 2; jj++) { s7[jj] = parked[(3 + jj) * 256]; s7p[jj] = parked[(5 + jj) * 256]; } }
 #define RR_STEP(k, Wm, W0, Wp, Wn, R0, Rn)                                                                                  \
   {                                                                                                                         \
     RR_LOADS(k, Wn, Rn)                                                                                                     \
+    RR_SLOTS(k)                                                                                                             \
     double r[2];                                                                                                            \
     _Pragma("unroll") for (int jj = 0; jj < 2; jj++) {                                                                     \
-      RR_CELL_IN(Wm, W0, Wp, R0)                                                                                            \
+      RR_CELL_IN(Wm, W0, Wp, R0, (ZW ? s4 : R0.A4), (ZW ? s7 : R0.A7), (ZW ? s7p : R0.A7p))                                      \
       double rr;                                                                                                            \
       if ((k) < nz) RR_GENERAL(rr, R0)                                                                                       \
-      else RR_LAST(rr, R0)                                                                                                  \
+      else RR_LAST(rr, R0, ZW ? parked[(7 + jj) * 256] : dlast[jj])                                                         \
       r[jj] = rr;                                                                                                           \
     }                                                                                                                       \
     RR_SUM(k, r)                                                                                                            \
   }
   {  // k = 1 (mg_relax.f90:464-482), peeled
     RR_LOADS(1, W[AW + 2], R[AR - 1])
+    const RowR &R1 = ZW ? S1 : R[NRB - 1];
     double r[2];
 #pragma unroll
     for (int jj = 0; jj < 2; jj++) {
-      RR_CELL_IN(W[0], W[0], W[1], R[NRB - 1])
+      RR_CELL_IN(W[0], W[0], W[1], R[NRB - 1], R1.A4, R1.A7, R1.A7p)
       double rr = R[NRB - 1].B[jj] - dedge[jj] * pc_0 - a2_p * pc_p - c3 * pjm_p - a4o * pjm_0 - a4jp * pjp_0
                                    - c5m * pjp_p - c6 * pim_p - a7o * pim_0 - a7ip * pip_0 - c8m * pip_p;
       if (REAL) rr = rr - e[jj][0] * e[jj][1] - e[jj][2] * e[jj][3] - e[jj][4] * e[jj][5] - e[jj][6] * e[jj][7];
@@ -230,13 +330,18 @@ __global__ __launch_bounds__(256, 1) void k_residual_restrict(LevView F, LevView
     if (k + q <= nz) RR_STEP(k + q, W[q % NWB], W[(q + 1) % NWB], W[(q + 2) % NWB], W[(q + 2 + AW) % NWB], R[q % NRB], R[(q + AR) % NRB])
   }
 #undef RR_STEP
+#undef RR_SLOTS
+#undef RR_ZW_ROW
 #undef RR_LOADS
-  if (NORM) {  // wave sum (lanes in index order pairs), then the block's four waves in order
+  if (NORM) {  // wave sum, then the block's four waves: pairs throughout, so the grouping does not show in the norm (dd_add, mgx_device.h)
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
-    if ((threadIdx.x & 63) == 0) red_ss[threadIdx.y] = ss;
+    for (int off = 32; off > 0; off >>= 1) { const double oh = __shfl_xor(ss, off, 64), ol = __shfl_xor(sl, off, 64); dd_merge(ss, sl, oh, ol); }
+    if ((threadIdx.x & 63) == 0) { red_ss[threadIdx.y] = ss; red_ss[4 + threadIdx.y] = sl; }
     __syncthreads();
-    if (threadIdx.x == 0 && threadIdx.y == 0) partial[blockIdx.x] = red_ss[0] + red_ss[1] + red_ss[2] + red_ss[3];
+    if (threadIdx.x == 0 && threadIdx.y == 0) {
+      for (int w = 1; w < 4; w++) dd_merge(ss, sl, red_ss[w], red_ss[4 + w]);
+      partial[blockIdx.x] = ss; partial[gridDim.x + blockIdx.x] = sl;
+    }
   }
 }
 
@@ -248,7 +353,8 @@ __global__ __launch_bounds__(256, 1) void k_residual_restrict(LevView F, LevView
 template <bool REAL, int S, bool NORM = false>
 __global__ __launch_bounds__(64) void k_residual_restrict_flat(LevView F, LevView C, double *__restrict__ dst, Sides ph, double *__restrict__ zero, int gx,
                                                               double *__restrict__ partial = nullptr, double *__restrict__ dup = nullptr) {
-  double ss = 0.0;
+  constexpr bool ZW = false;  // the flat form streams its slots
+  double ss = 0.0, sl = 0.0;
   // 1-D grid, k fastest: the nz/S waves of one (plane, j-chunk) share two of their window rows with the wave above and below, so they
   // are kept together in time and on ONE XCD (workgroups are dealt to the eight XCDs round-robin), where that re-use is an L2 hit
   const int nz = F.nz, nks = (nz + S - 1) / S, ng = gx * C.nx;
@@ -305,14 +411,14 @@ __global__ __launch_bounds__(64) void k_residual_restrict_flat(LevView F, LevVie
       double rv[2];
 #pragma unroll
       for (int jj = 0; jj < 2; jj++) {
-        RR_CELL_IN(W[r], W[r + 1], W[r + 2], R[r])
+        RR_CELL_IN(W[r], W[r + 1], W[r + 2], R[r], R[r].A4, R[r].A7, R[r].A7p)
         double rr;
         if (r == 0 && kr == 1) {
           rr = R[r].B[jj] - dedge[jj] * pc_0 - a2_p * pc_p - c3 * pjm_p - a4o * pjm_0 - a4jp * pjp_0
                           - c5m * pjp_p - c6 * pim_p - a7o * pim_0 - a7ip * pip_0 - c8m * pip_p;
           if (REAL) rr = rr - e[jj][0] * e[jj][1] - e[jj][2] * e[jj][3] - e[jj][4] * e[jj][5] - e[jj][6] * e[jj][7];
         } else if (kr < nz) RR_GENERAL(rr, R[r])
-        else RR_LAST(rr, R[r])
+        else RR_LAST(rr, R[r], dlast[jj])
         rv[jj] = rr;
       }
       RR_SUM(kr, rv)  /* odd row: z = its four values; even row: z += its four values, store coarse row kr/2 */
@@ -320,11 +426,12 @@ __global__ __launch_bounds__(64) void k_residual_restrict_flat(LevView F, LevVie
   }
   if (NORM) {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
-    if (threadIdx.x == 0) partial[blockIdx.x] = ss;
+    for (int off = 32; off > 0; off >>= 1) { const double oh = __shfl_xor(ss, off, 64), ol = __shfl_xor(sl, off, 64); dd_merge(ss, sl, oh, ol); }
+    if (threadIdx.x == 0) { partial[blockIdx.x] = ss; partial[gridDim.x + blockIdx.x] = sl; }
   }
 }
 #undef RR_SUM
+#undef RR_XOR
 #undef RR_CELL_IN
 #undef RR_GENERAL
 #undef RR_LAST
@@ -332,7 +439,7 @@ __global__ __launch_bounds__(64) void k_residual_restrict_flat(LevView F, LevVie
 extern "C" {
 
 // returns 1 when launched (matrix-free slopes present, level large enough to be bandwidth-bound), 0 = use mgxk_residual + mgxk_fine2coarse
-// partial != nullptr: also sum r^2 (partials, one per workgroup; *npartial_out = their number); dup: second destination of the coarse sums
+// partial != nullptr: also sum r^2 (partials, one pair per workgroup: room for twice mgxk_residual_restrict_grid()); dup: second destination of the coarse sums
 int mgxk_residual_restrict_grid(const LevView *F, const LevView *C) {  // workgroups (= norm partials) of the launch below
   const int gx = (C->ny + 31) / 32;
   if ((long long)F->nx * F->ny * F->nz <= mgx_switches().resrest_flat_max) {
@@ -360,14 +467,19 @@ int mgxk_residual_restrict_ex(hipStream_t st, const LevView *F, const LevView *C
   const int by = 4, gx = (C->ny + 31) / 32, gy = (C->nx + by - 1) / by;
   dim3 blk(WAVE, by), grd(gx * gy);
   const int deep = sw.resrest_ahead;  // 10 * AW + AR, default 11 (A/B: scripts/probe/ab_resrest_ahead.sh -- 11, 12, 21 within 5 % of each other once the requests are unconditional)
-#define RRW(REALV, AWV, ARV, NV) hipLaunchKernelGGL((k_residual_restrict<REALV, AWV, ARV, NV>), grd, blk, 0, st, *F, *C, dst, ph, zero, gx, gy, partial, dup)
-#define RRW2(AWV, ARV) { if (partial) { if (real) RRW(true, AWV, ARV, true); else RRW(false, AWV, ARV, true); } else { if (real) RRW(true, AWV, ARV, false); else RRW(false, AWV, ARV, false); } }
+  // slots 4 and 7 generated: when the level carries what the smoother's ZW form needs, i.e. as define_matrices leaves it (not after bmask,
+  // a user matrix or MGX_NO_MF); the instance without the norm at the default look-ahead only (the others have no registers for it)
+  const bool zw = !sw.resrest_no_zw && !partial && F->m4 && F->d4 && F->m7 && F->d7 && F->h2 && F->hi2 && F->ze2 && F->cffw && F->csw;
+#define RRW(REALV, AWV, ARV, NV, ZV) hipLaunchKernelGGL((k_residual_restrict<REALV, AWV, ARV, NV, ZV>), grd, blk, 0, st, *F, *C, dst, ph, zero, gx, gy, partial, dup)
+#define RRW3(AWV, ARV, ZV) { if (partial) { if (real) RRW(true, AWV, ARV, true, ZV); else RRW(false, AWV, ARV, true, ZV); } else { if (real) RRW(true, AWV, ARV, false, ZV); else RRW(false, AWV, ARV, false, ZV); } }
+#define RRW2(AWV, ARV) RRW3(AWV, ARV, false)
   switch (deep) {
     case 12: RRW2(1, 2) break;
     case 21: RRW2(2, 1) break;
-    default: RRW2(1, 1) break;
+    default: if (zw) { if (real) RRW(true, 1, 1, false, true); else RRW(false, 1, 1, false, true); } else RRW2(1, 1) break;
   }
 #undef RRW2
+#undef RRW3
 #undef RRW
   return mgx_launched();
 }

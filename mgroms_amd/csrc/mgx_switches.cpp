@@ -46,6 +46,7 @@ const Row TABLE[] = {
   {"MGX_RESREST_FLAT_MAX",       &Switches::resrest_flat_max,      ATOLL,     256LL * 256 * 64, "fine cells up to which the fused residual + restriction takes its flat form (no walk up the column); same bits"},
   {"MGX_RESREST_FLAT_S",         &Switches::resrest_flat_s,        ATOI,      0,                ">= 4: four fine rows per wave in the flat form instead of two; same bits"},
   {"MGX_RESREST_AHEAD",          &Switches::resrest_ahead,         ATOI,      11,               "10 * AW + AR, the look-ahead of the walking form: 12 and 21 are instantiated beside 11; same bits"},
+  {"MGX_RESREST_NO_ZW",          &Switches::resrest_no_zw,         SET_TRUE,  0,                "the walking form of a cycle's down leg streams slots 4 and 7 instead of generating their interior rows from the depth formula (look-ahead 11, no norm: the others always stream); same bits"},
   {"MGX_P2P_MAXBLK",             &Switches::p2p_maxblk,            ATOI,      128,              "block cap of the halo push kernel (its grid must stay resident beside a neighbour's smoother); same bits"},
   {"MGX_P2P_IPT",                &Switches::p2p_ipt,               ATOI,      1,                "test hook: at least that many items per thread in the halo push kernel; same bits"},
   {"MGX_MODEL_KR",               &Switches::model_kr,              ATOI,      0,                "> 0 (A/B and test hook): runs of exactly that many rows in the flux kernels and correct_uvw; same bits"},

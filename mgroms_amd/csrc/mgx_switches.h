@@ -18,7 +18,7 @@ struct Switches {
   int rbw_prio;
   // transfer kernels (mgx_kernels.hip, mgx_resrest.hip)
   int c2f_kc, c2f_nt;
-  bool no_resrest;
+  bool no_resrest, resrest_no_zw;
   long long resrest_min, resrest_flat_max;
   int resrest_flat_s, resrest_ahead;
   // halo pushes (mgx_kernels.hip) and the model coupling (mgx_model.hip)
