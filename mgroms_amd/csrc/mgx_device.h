@@ -111,6 +111,54 @@ static inline dim3 col_grid(int ncol_half, int nplanes, int z = 1) { return dim3
 // residual + restriction (mgx_resrest.hip), whose generated slots 4 / 7 must be the same bits.  In scope: the sigma tables cffw, csw and
 // h, hinv, zeta of the caller's columns as hh[], hv[], hz[].
 #define ZW_GEN(kk, q) ({ const double z0_ = cffw[(kk)-1] + csw[(kk)-1] * hh[q]; z0_ * hh[q] * hv[q] + hz[q] * (1. + z0_ * hv[q]); })
+// An interior row of a generated slot 4 or 7 (mg_define_matrix.f90:532-534,549-551) from the depths ZW_GEN made: hi_ / lo_ = zw(k+1) / zw(k)
+// of the two columns the coupling joins, in the reference's order; m, d = the coupling's 2-D factors, r = RCP_REF(d).  qrt in scope.
+#define SLOT47_GEN(hi_a, lo_a, hi_b, lo_b, m, d, r) DIVC(qrt * ((hi_a) - (lo_a) + (hi_b) - (lo_b)) * (m), (d), (r))
+
+// ---- the row: what the bit parity of every fp64 kernel hangs on ------------------------------------------------------------
+// The right-hand side of row k of column (j, i) is B minus its twelve off-column products, subtracted one by one in the reference's
+// order (mg_relax.f90:262-301 for the smoother; :464-509 for the residual, where B = b minus the own-column terms, which stand in
+// front of the same twelve).  ONE text for every fp64 kernel; DESIGN.md 2.1 lists who expands it.  T<n> is slot n of the cell
+// itself times the neighbour it couples to, T<n>M the mirrored coupling that the symmetric storage keeps at the j+1 / i+1 neighbour:
+//   T3 = cA(3,k,j,i) p(k+1,j-1,i)   T3M = cA(3,k-1,j+1,i) p(k-1,j+1,i)     T6 = cA(6,k,j,i) p(k+1,j,i-1)   T6M = cA(6,k-1,j,i+1) p(k-1,j,i+1)
+//   T4 = cA(4,k,j,i) p(k,j-1,i)     T4M = cA(4,k,j+1,i) p(k,j+1,i)         T7 = cA(7,k,j,i) p(k,j,i-1)     T7M = cA(7,k,j,i+1) p(k,j,i+1)
+//   T5 = cA(5,k,j,i) p(k-1,j-1,i)   T5M = cA(5,k+1,j+1,i) p(k+1,j+1,i)     T8 = cA(8,k,j,i) p(k-1,j,i-1)   T8M = cA(8,k+1,j,i+1) p(k+1,j,i+1)
+// Row 1 has no k-1 terms and row nz no k+1 terms; the k = 1 horizontal diagonals of cmatrix = 'real' (:271-276, :475-479) stay a
+// statement of their own behind the first row.  A site writes its thirteen arguments once, as a term list (#define X_TERMS B, T3, ...),
+// and keeps its own `if (k == 1) ... else if (k < nz) ... else` ladder of statements: as one ?: expression the kernels whose k is a
+// run-time value compiled differently.  The forwarders are variadic so that a term list is expanded before the arguments are counted.
+#define ROW_RHS_FIRST_(B, T3, T3M, T4, T4M, T5, T5M, T6, T6M, T7, T7M, T8, T8M) ((B) - (T3) - (T4) - (T4M) - (T5M) - (T6) - (T7) - (T7M) - (T8M))
+#define ROW_RHS_MID_(B, T3, T3M, T4, T4M, T5, T5M, T6, T6M, T7, T7M, T8, T8M) \
+  ((B) - (T3) - (T3M) - (T4) - (T4M) - (T5) - (T5M) - (T6) - (T6M) - (T7) - (T7M) - (T8) - (T8M))
+#define ROW_RHS_LAST_(B, T3, T3M, T4, T4M, T5, T5M, T6, T6M, T7, T7M, T8, T8M) ((B) - (T3M) - (T4) - (T4M) - (T5) - (T6M) - (T7) - (T7M) - (T8))
+#define ROW_RHS_FIRST(...) ROW_RHS_FIRST_(__VA_ARGS__)
+#define ROW_RHS_MID(...) ROW_RHS_MID_(__VA_ARGS__)
+#define ROW_RHS_LAST(...) ROW_RHS_LAST_(__VA_ARGS__)
+// The twelve products by the names that the column texts share; both lists bind locals of the texts that expand them.
+// ST_TERMS, stored slots: a3 .. a8 (the cell's own slots, read at ko), the windows pjm_*, pim_* and the neighbours' products m3_m .. n8_p
+// as LOAD_ROW left them, in relax_col_any (mgx_relax.hip) and OP_COLUMN (mgx_operator.h).
+// MF_TERMS, matrix-free: c3 .. c8m of MF_CROSS_COEF, slots 4 / 7 of the cell and of its j+1 / i+1 neighbour (a4o, a4jp, a7o, a7ip) and the
+// windows pjm_*, pjp_*, pim_*, pip_*, in MF_ROW (mgx_relax_common.h), OP_COLUMN_MF (mgx_operator.h) and RR_* (mgx_resrest.hip).
+#define ST_TERMS(ko) a3[ko] * pjm_p, m3_m, a4[ko] * pjm_0, m4_0, a5[ko] * pjm_m, m5_p, a6[ko] * pim_p, n6_m, a7[ko] * pim_0, n7_0, a8[ko] * pim_m, n8_p
+#define MF_TERMS c3 * pjm_p, c3m * pjp_m, a4o * pjm_0, a4jp * pjp_0, c5 * pjm_m, c5m * pjp_p, c6 * pim_p, c6m * pip_m, a7o * pim_0, a7ip * pip_0, c8 * pim_m, c8m * pip_p
+// The eight matrix-free cross coefficients of a row (mgx_relax_common.h explains them): own slots 3, 5, 6, 8 and the mirrored ones, from
+// the own slopes of rows k-1 / k+1 (zy_m, zy_p, zx_m, zx_p) and the j-1 / j+1 / i-1 / i+1 neighbours' slopes of row k.  qrt in scope.
+#define MF_CROSS_COEF(zy_m, zy_p, zyjm, zyjp, zx_m, zx_p, zxim, zxip)                                                              \
+  const double c3 = qrt * (zy_p + zyjm), c3m = qrt * (zyjp + zy_m), c5 = -qrt * (zy_m + zyjm), c5m = -qrt * (zyjp + zy_p);          \
+  const double c6 = qrt * (zx_p + zxim), c6m = qrt * (zxip + zx_m), c8 = -qrt * (zx_m + zxim), c8m = -qrt * (zxip + zx_p);
+// The k = 1 same-colour diagonals (mg_relax.f90:271-276): their four coefficients, and with them the four values of p, which a red-black
+// pass reads from the snapshot taken before it (SNAP): K1_SNAP_ADDR declares where they are, q1[sm / sp + jm / jp].
+// In scope: L, p, a5, a8, i, RS, o, om, op, c, jm, jp.
+#define K1_COEF(e1, e2, e3, e4) { e1 = a5[o + c]; e2 = a5[op + jm]; e3 = a8[o + c]; e4 = a8[op + jp]; }
+#define K1_SNAP_ADDR(SNAP)                                                                                                       \
+  const double *__restrict__ q1 = SNAP ? L.p1 : p;                                                                               \
+  const long long s = SNAP ? (long long)i * RS : o, sm = SNAP ? s - RS : om, sp = SNAP ? s + RS : op;
+#define K1_DIAG(SNAP, d1, d2, d3, d4, e1, e2, e3, e4)                                                                             \
+  {                                                                                                                              \
+    K1_SNAP_ADDR(SNAP)                                                                                                           \
+    d1 = q1[sm + jp]; d2 = q1[sp + jm]; d3 = q1[sm + jm]; d4 = q1[sp + jp];                                                      \
+    K1_COEF(e1, e2, e3, e4)                                                                                                      \
+  }
 // The j-1 and j+1 neighbours of a column sit side by side in the other half-row (jp = jm + 1): ONE 16-byte load per lane fetches
 // both, instead of two 8-byte loads whose wave-wide footprints overlap by 63/64 (half the wave-level requests for these streams;
 // 8-byte alignment only: gfx950 global loads do not need natural alignment)

@@ -1,7 +1,8 @@
 // The level-1 operator, ONE text per form: the 15-point product of compute_residual (mg_relax.f90:421-515) from the stored slots and with
 // matrix-free cross terms, for the residual kernels (mgx_kernels.hip: k_residual, k_residual_mf) and pass 1 of the Krylov loop
 // (mgx_krylov.hip: k_kr_apply, k_kr_apply_mf), which is the same operator on b = 0 with the sign turned.  Both have a bit-parity duty that
-// rests on a row being formed from the same terms in the same order: a change to a row is made here, once.  With them, the block map of
+// rests on a row being formed from the same terms in the same order: the own-column terms stand here, once, and the twelve off-column
+// terms behind them are ROW_RHS_* of mgx_device.h, the text that the smoothers expand as well.  With them, the block map of
 // these launches and the block reduction of the kernels that leave one partial sum per workgroup.  The column texts and the reduction are
 // macros with caller-supplied hooks, for the reason given in mgx_relax_common.h: the callers must compile to the instructions they had
 // as separate texts (profiles/operator_single_source_isa.json).
@@ -93,8 +94,7 @@ __device__ __forceinline__ void op_block_map(int gx, int gy, int &bx, int &by, i
     LOAD_ROW(PV, 2, pjm_p, pim_p, pc_p, a2_p, m3_p, m4_p, m5_p, n6_p, n7_p, n8_p);                                                           \
     (void)dum5; (void)dum8;                                                                                                                  \
     /* k = 1 (:464-482) */                                                                                                                   \
-    double rr = RHS(o + c) - a1[o + c] * pc_0 - a2_p * pc_p - a3[o + c] * pjm_p - a4[o + c] * pjm_0 - m4_0 - m5_p                            \
-                - a6[o + c] * pim_p - a7[o + c] * pim_0 - n7_0 - n8_p;                                                                       \
+    double rr = ROW_RHS_FIRST(RHS(o + c) - a1[o + c] * pc_0 - a2_p * pc_p, ST_TERMS(o + c));                                                 \
     if (REAL)                                                                                                                                \
       rr = rr - a5[o + c] * PV(om, 0, 0, jp) - a5[op + jm] * PV(op, 0, 0, jm) - a8[o + c] * PV(om, 0, 0, jm) - a8[op + jp] * PV(op, 0, 0, jp); \
     const int jcol = jodd ? 2 * jh + 1 : 2 * jh + 2;  /* the column's j, for a sink that stores the physical images */                       \
@@ -104,16 +104,14 @@ __device__ __forceinline__ void op_block_map(int gx, int gy, int &bx, int &by, i
       m3_m = m3_0; m3_0 = m3_p; m4_0 = m4_p; n6_m = n6_0; n6_0 = n6_p; n7_0 = n7_p;                                                          \
       LOAD_ROW(PV, k + 1, pjm_p, pim_p, pc_p, a2_p, m3_p, m4_p, m5_p, n6_p, n7_p, n8_p);                                                     \
       const long long ko = o + (long long)(k - 1) * RS + c;                                                                                  \
-      rr = RHS(ko) - a1[ko] * pc_0 - a2_0 * pc_m - a2_p * pc_p - a3[ko] * pjm_p - m3_m - a4[ko] * pjm_0 - m4_0                               \
-                   - a5[ko] * pjm_m - m5_p - a6[ko] * pim_p - n6_m - a7[ko] * pim_0 - n7_0 - a8[ko] * pim_m - n8_p;                          \
+      rr = ROW_RHS_MID(RHS(ko) - a1[ko] * pc_0 - a2_0 * pc_m - a2_p * pc_p, ST_TERMS(ko));                                                   \
       SINK((long long)(k - 1) * RS, ko, rr)                                                                                                  \
     }                                                                                                                                        \
     {  /* k = nz (:498-509) */                                                                                                               \
       pjm_m = pjm_0; pjm_0 = pjm_p; pim_m = pim_0; pim_0 = pim_p; pc_m = pc_0; pc_0 = pc_p; a2_0 = a2_p;                                     \
       m3_m = m3_0; m4_0 = m4_p; n6_m = n6_0; n7_0 = n7_p;                                                                                    \
       const long long ko = o + (long long)(nz - 1) * RS + c;                                                                                 \
-      rr = RHS(ko) - a1[ko] * pc_0 - a2_0 * pc_m - m3_m - a4[ko] * pjm_0 - m4_0 - a5[ko] * pjm_m - n6_m                                      \
-                   - a7[ko] * pim_0 - n7_0 - a8[ko] * pim_m;                                                                                 \
+      rr = ROW_RHS_LAST(RHS(ko) - a1[ko] * pc_0 - a2_0 * pc_m, ST_TERMS(ko));                                                                \
       SINK((long long)(nz - 1) * RS, ko, rr)                                                                                                 \
     }                                                                                                                                        \
   }
@@ -138,7 +136,13 @@ __device__ __forceinline__ void op_block_map(int gx, int gy, int &bx, int &by, i
   { const long long ro = (long long)(((q) <= nz ? (q) : nz) - 1) * RS, ko = o + ro + c;                                                      \
     LD_PAIR(zy + o + ro + jm, ZYJM, ZYJP) ZXIM = zx[om + ro + c]; ZXIP = zx[op + ro + c];                                                    \
     A4O = *(a4 + ko); A4JP = a4[o + ro + jp]; A7O = *(a7 + ko); A7IP = a7[op + ro + c]; BK = RHS_LOAD(ko); }
-#define OP_COLUMN_MF(PV, PV2, RHS_LOAD, SINK)                                                                                                 \
+// MF_TERMS (mgx_device.h) with the cross coefficients spelt where they are used, for rows 1 and nz of OP_COLUMN_MF: named first
+// (MF_CROSS_COEF), they reach the compiler in another order and the three kernels of this text (six instances) compile differently
+// (DESIGN.md 2.1).  Like the other term lists it stays defined: OP_COLUMN_MF expands it where a kernel expands OP_COLUMN_MF.
+#define MF_TERMS_INLINE (qrt * (zy_p + zyjm)) * pjm_p, (qrt * (zyjp + zy_m)) * pjp_m, a4o * pjm_0, a4jp * pjp_0, (-qrt * (zy_m + zyjm)) * pjm_m, \
+                        (-qrt * (zyjp + zy_p)) * pjp_p, (qrt * (zx_p + zxim)) * pim_p, (qrt * (zxip + zx_m)) * pip_m, a7o * pim_0, a7ip * pip_0, \
+                        (-qrt * (zx_m + zxim)) * pim_m, (-qrt * (zxip + zx_p)) * pip_p
+#define OP_COLUMN_MF(PV, PV2, RHS_LOAD, SINK)                                                                                               \
   {                                                                                                                                          \
     const long long RS = L.RS;                                                                                                               \
     const int nz = L.nz;                                                                                                                     \
@@ -166,22 +170,14 @@ __device__ __forceinline__ void op_block_map(int gx, int gy, int &bx, int &by, i
       LOAD_ROWV(RHS_LOAD, k + 1, zyjm_n, zyjp_n, zxim_n, zxip_n, a4o_n, a4jp_n, a7o_n, a7ip_n, bk_n)                                         \
       double rr;                                                                                                                             \
       if (k == 1) {                                                                                                                          \
-        rr = bk - d_first * pc_0 - a2_p * pc_p - (qrt * (zy_p + zyjm)) * pjm_p - a4o * pjm_0 - a4jp * pjp_0                                  \
-                   - (-qrt * (zyjp + zy_p)) * pjp_p - (qrt * (zx_p + zxim)) * pim_p - a7o * pim_0 - a7ip * pip_0                             \
-                   - (-qrt * (zxip + zx_p)) * pip_p;                                                                                         \
+        rr = ROW_RHS_FIRST(bk - d_first * pc_0 - a2_p * pc_p, MF_TERMS_INLINE);                                                              \
         if (REAL) rr = rr - e0 * e1 - e2 * e3 - e4 * e5 - e6 * e7;                                                                           \
       } else if (k < nz) {                                                                                                                   \
-        const double c3 = qrt * (zy_p + zyjm), c3m = qrt * (zyjp + zy_m), c5 = -qrt * (zy_m + zyjm), c5m = -qrt * (zyjp + zy_p);             \
-        const double c6 = qrt * (zx_p + zxim), c6m = qrt * (zxip + zx_m), c8 = -qrt * (zx_m + zxim), c8m = -qrt * (zxip + zx_p);             \
+        MF_CROSS_COEF(zy_m, zy_p, zyjm, zyjp, zx_m, zx_p, zxim, zxip)                                                                        \
         const double dk = -a2_0 - a2_p - a4o - a4jp - a7o - a7ip - c6 - c6m - c8 - c8m - c3 - c3m - c5 - c5m;  /* = cA(1,k,j,i), mg_define_matrix.f90:632-639 */ \
-        rr = bk - dk * pc_0 - a2_0 * pc_m - a2_p * pc_p - c3 * pjm_p - c3m * pjp_m                                                           \
-                   - a4o * pjm_0 - a4jp * pjp_0 - c5 * pjm_m - c5m * pjp_p                                                                   \
-                   - c6 * pim_p - c6m * pip_m - a7o * pim_0 - a7ip * pip_0                                                                   \
-                   - c8 * pim_m - c8m * pip_p;                                                                                               \
+        rr = ROW_RHS_MID(bk - dk * pc_0 - a2_0 * pc_m - a2_p * pc_p, MF_TERMS);                                                              \
       } else {                                                                                                                               \
-        rr = bk - d_last * pc_0 - a2_0 * pc_m - (qrt * (zyjp + zy_m)) * pjp_m - a4o * pjm_0 - a4jp * pjp_0                                   \
-                   - (-qrt * (zy_m + zyjm)) * pjm_m - (qrt * (zxip + zx_m)) * pip_m - a7o * pim_0 - a7ip * pip_0                             \
-                   - (-qrt * (zx_m + zxim)) * pim_m;                                                                                         \
+        rr = ROW_RHS_LAST(bk - d_last * pc_0 - a2_0 * pc_m, MF_TERMS_INLINE);                                                                \
       }                                                                                                                                      \
       SINK(ro, ko, rr)                                                                                                                       \
       pc_m = pc_0; pc_0 = pc_p; pc_p = pc_n; pjm_m = pjm_0; pjm_0 = pjm_p; pjm_p = pjm_n; pim_m = pim_0; pim_0 = pim_p; pim_p = pim_n;       \

@@ -48,10 +48,9 @@ __device__ __forceinline__ void relax_col_any(const LevView &L, const int i, con
   (void)dum5; (void)dum8;
 
   // ---- k = 1 (mg_relax.f90:262-279)
-  double rhs = b[o + c] - a3[o + c] * pjm_p - a4[o + c] * pjm_0 - m4_0 - m5_p - a6[o + c] * pim_p - a7[o + c] * pim_0 - n7_0 - n8_p;
-  if (REAL) {
-    const double *__restrict__ q1 = SNAP ? L.p1 : p;
-    const long long s = SNAP ? (long long)i * RS : o, sm = SNAP ? s - RS : om, sp = SNAP ? s + RS : op;
+  double rhs = ROW_RHS_FIRST(b[o + c], ST_TERMS(o + c));
+  if (REAL) {  // the loads stay in the products: through K1_DIAG, all eight first, the three REAL kernels of this text compile differently
+    K1_SNAP_ADDR(SNAP)
     rhs = rhs - a5[o + c] * q1[sm + jp] - a5[op + jm] * q1[sp + jm] - a8[o + c] * q1[sm + jm] - a8[op + jp] * q1[sp + jp];
   }
   double x = rhs * bet[o + c];
@@ -63,8 +62,7 @@ __device__ __forceinline__ void relax_col_any(const LevView &L, const int i, con
     m3_m = m3_0; m3_0 = m3_p; m4_0 = m4_p; n6_m = n6_0; n6_0 = n6_p; n7_0 = n7_p;
     LOAD_ROW(k + 1, pjm_p, pim_p, m3_p, m4_p, m5_p, n6_p, n7_p, n8_p);
     const long long ko = o + (long long)(k - 1) * RS + c;
-    rhs = b[ko] - a3[ko] * pjm_p - m3_m - a4[ko] * pjm_0 - m4_0 - a5[ko] * pjm_m - m5_p
-                - a6[ko] * pim_p - n6_m - a7[ko] * pim_0 - n7_0 - a8[ko] * pim_m - n8_p;
+    rhs = ROW_RHS_MID(b[ko], ST_TERMS(ko));
     x = (rhs - a2[ko] * x) * bet[ko];
     p[ko] = x;
   }
@@ -73,7 +71,7 @@ __device__ __forceinline__ void relax_col_any(const LevView &L, const int i, con
     pjm_m = pjm_0; pjm_0 = pjm_p; pim_m = pim_0; pim_0 = pim_p;
     m3_m = m3_0; m4_0 = m4_p; n6_m = n6_0; n7_0 = n7_p;
     const long long ko = o + (long long)(nz - 1) * RS + c;
-    rhs = b[ko] - m3_m - a4[ko] * pjm_0 - m4_0 - a5[ko] * pjm_m - n6_m - a7[ko] * pim_0 - n7_0 - a8[ko] * pim_m;
+    rhs = ROW_RHS_LAST(b[ko], ST_TERMS(ko));
     x = (rhs - a2[ko] * x) * bet[ko];
     p[ko] = x;
   }
@@ -109,8 +107,8 @@ __global__ __launch_bounds__(256) void k_relax_colour(LevView L, int i0, int ist
 //     once (no forward store + backward re-read), and the backward sweep does no dependent loads;
 //   * physical-boundary mirrors of the updated columns (mg_mpi_exchange.f90:509-537,552-597) are stored by
 //     the lane that owns the column, which removes the separate halo kernel after every colour.
-// Arithmetic and its order are identical to k_relax_colour (bit-identical results).  The forward rows are the stored-coefficient text of
-// mgx_relax_common.h (SC_ROW), shared with the tall-column pass of mgx_relax_tall.hip.
+// The forward rows are the stored-coefficient text of mgx_relax_common.h (SC_ROW), shared with the tall-column pass of
+// mgx_relax_tall.hip; it expands ROW_RHS_* (mgx_device.h) as relax_col_any of k_relax_colour does: bit-identical results.
 // ------------------------------------------------------------------------------------------------
 template <int NZ, bool REAL, bool SNAP, int D>
 __device__ __forceinline__ void relax_col_nz(const LevView &L, const int i, const int jh, const int jodd, const Sides ph) {
@@ -273,7 +271,7 @@ __global__ void k_snapshot_k1(LevView L) {
 // read, the k=1 diagonal slots, gam -- is loaded into registers once; only p lives in LDS (with its mirrored halo) and
 // is exchanged there.  A colour pass is then ~4 NZ LDS reads, ~30 NZ flops and one barrier (0.1-0.2 us instead of
 // 0.8 us with every operand re-read from LDS, and ~5 us as a separate launch): relax(nlevs, ns_coarsest=40) is 160
-// dependent passes.  Same expressions in the same order as relax_col_nz: bit-identical.
+// dependent passes.  The rows expand ROW_RHS_* (mgx_device.h), as relax_col_nz's do: bit-identical.
 template <int NZ, bool REAL, int MAXT>
 __global__ __launch_bounds__(MAXT) void k_relax_reg(LevView G, int nsweeps, int method, Sides ph, int exact_in) {
   extern __shared__ double ldsr[];
@@ -337,20 +335,21 @@ __global__ __launch_bounds__(MAXT) void k_relax_reg(LevView G, int nsweeps, int 
 #pragma unroll
         for (int k = 0; k < NZ; k++) {
           double rhs;
+          // row k + 1 as the arguments of ROW_RHS_* (mgx_device.h); the rows a form leaves out are never indexed
+#define REG_TERMS ob[k], a3[k] * pjm[k + 1], r3[k - 1] * pjp[k - 1], a4[k] * pjm[k], r4[k] * pjp[k], a5[k] * pjm[k - 1], r5[k + 1] * pjp[k + 1], \
+                  a6[k] * pim[k + 1], r6[k - 1] * pip[k - 1], a7[k] * pim[k], r7[k] * pip[k], a8[k] * pim[k - 1], r8[k + 1] * pip[k + 1]
           if (k == 0) {
-            rhs = ob[k] - a3[k] * pjm[k + 1] - a4[k] * pjm[k] - r4[k] * pjp[k] - r5[k + 1] * pjp[k + 1]
-                        - a6[k] * pim[k + 1] - a7[k] * pim[k] - r7[k] * pip[k] - r8[k + 1] * pip[k + 1];
+            rhs = ROW_RHS_FIRST(REG_TERMS);
             if (REAL) rhs = rhs - a5[0] * d1 - e2 * d2 - a8[0] * d3 - e4 * d4;
             xv = rhs * bet[k];
           } else if (k < NZ - 1) {
-            rhs = ob[k] - a3[k] * pjm[k + 1] - r3[k - 1] * pjp[k - 1] - a4[k] * pjm[k] - r4[k] * pjp[k] - a5[k] * pjm[k - 1] - r5[k + 1] * pjp[k + 1]
-                        - a6[k] * pim[k + 1] - r6[k - 1] * pip[k - 1] - a7[k] * pim[k] - r7[k] * pip[k] - a8[k] * pim[k - 1] - r8[k + 1] * pip[k + 1];
+            rhs = ROW_RHS_MID(REG_TERMS);
             xv = (rhs - a2[k] * xv) * bet[k];
           } else {
-            rhs = ob[k] - r3[k - 1] * pjp[k - 1] - a4[k] * pjm[k] - r4[k] * pjp[k] - a5[k] * pjm[k - 1]
-                        - r6[k - 1] * pip[k - 1] - a7[k] * pim[k] - r7[k] * pip[k] - a8[k] * pim[k - 1];
+            rhs = ROW_RHS_LAST(REG_TERMS);
             xv = (rhs - a2[k] * xv) * bet[k];
           }
+#undef REG_TERMS
           x[k] = xv;
         }
 #pragma unroll

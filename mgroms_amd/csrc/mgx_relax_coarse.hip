@@ -11,7 +11,7 @@
 // corners :552-597): p sits in LDS WITHOUT a halo and a column reads its j-1 / j+1 / i-1 / i+1 neighbours and the four k=1 diagonals
 // through indices clamped to the interior -- no mirror stores, no branches in a pass (they were a third of its instructions); the halo of
 // the global array is rebuilt once, when p is written back.
-// Same expressions in the same order as relax_col_nz / k_relax_reg: bit-identical.
+// The rows expand ROW_RHS_* (mgx_device.h), as those of relax_col_nz / k_relax_reg do: bit-identical.
 #include "mgx_switches.h"
 #include "mgx_device.h"
 
@@ -156,6 +156,11 @@ __global__ __launch_bounds__(NT, 1) void k_relax_wave(LevView G, int nsweeps, in
 #define R6(q, k) (((q) >> 1) ? xi[(q) & 1][0][k] : a6[((q) + 2) & 3][k])
 #define R7(q, k) (((q) >> 1) ? xi[(q) & 1][1][k] : a7[((q) + 2) & 3][k])
 #define R8(q, k) (((q) >> 1) ? xi[(q) & 1][2][k] : a8[((q) + 2) & 3][k])
+  // the twelve off-column products of row k + 1 of column q, the arguments of ROW_RHS_* (mgx_device.h) behind B, for the smoother (COLUMN)
+  // and for the folded residual (flags & 2) alike; the rows a form leaves out are never indexed
+#define WAVE_TERMS(q) a3[q][k] * pjm[k + 1], R3(q, k - 1) * pjp[k - 1], a4[q][k] * pjm[k], R4(q, k) * pjp[k],    \
+                      a5[q][k] * pjm[k - 1], R5(q, k + 1) * pjp[k + 1], a6[q][k] * pim[k + 1], R6(q, k - 1) * pip[k - 1],   \
+                      a7[q][k] * pim[k], R7(q, k) * pip[k], a8[q][k] * pim[k - 1], R8(q, k + 1) * pip[k + 1]
   // one column solve; Q1 = where the k=1 horizontal diagonals are read (the snapshot for red-black, p itself for four-colour)
 #define COLUMN(q)                                                                                                          \
   {                                                                                                                         \
@@ -175,19 +180,14 @@ __global__ __launch_bounds__(NT, 1) void k_relax_wave(LevView G, int nsweeps, in
     _Pragma("unroll") for (int k = 0; k < NZ; k++) {                                                                        \
       double rhs;                                                                                                           \
       if (k == 0) {                                                                                                         \
-        rhs = ob[q][k] - a3[q][k] * pjm[k + 1] - a4[q][k] * pjm[k] - R4(q, k) * pjp[k] - R5(q, k + 1) * pjp[k + 1]          \
-                       - a6[q][k] * pim[k + 1] - a7[q][k] * pim[k] - R7(q, k) * pip[k] - R8(q, k + 1) * pip[k + 1];          \
+        rhs = ROW_RHS_FIRST(ob[q][k], WAVE_TERMS(q));                                                                       \
         if (REAL) rhs = rhs - a5[q][0] * d1 - e2[q] * d2 - a8[q][0] * d3 - e4[q] * d4;                                      \
         xv = rhs * bet[q][k];                                                                                               \
       } else if (k < NZ - 1) {                                                                                              \
-        rhs = ob[q][k] - a3[q][k] * pjm[k + 1] - R3(q, k - 1) * pjp[k - 1] - a4[q][k] * pjm[k] - R4(q, k) * pjp[k]          \
-                       - a5[q][k] * pjm[k - 1] - R5(q, k + 1) * pjp[k + 1]                                                  \
-                       - a6[q][k] * pim[k + 1] - R6(q, k - 1) * pip[k - 1] - a7[q][k] * pim[k] - R7(q, k) * pip[k]          \
-                       - a8[q][k] * pim[k - 1] - R8(q, k + 1) * pip[k + 1];                                                 \
+        rhs = ROW_RHS_MID(ob[q][k], WAVE_TERMS(q));                                                                         \
         xv = (rhs - a2[q][k] * xv) * bet[q][k];                                                                             \
       } else {                                                                                                              \
-        rhs = ob[q][k] - R3(q, k - 1) * pjp[k - 1] - a4[q][k] * pjm[k] - R4(q, k) * pjp[k] - a5[q][k] * pjm[k - 1]          \
-                       - R6(q, k - 1) * pip[k - 1] - a7[q][k] * pim[k] - R7(q, k) * pip[k] - a8[q][k] * pim[k - 1];          \
+        rhs = ROW_RHS_LAST(ob[q][k], WAVE_TERMS(q));                                                                        \
         xv = (rhs - a2[q][k] * xv) * bet[q][k];                                                                             \
       }                                                                                                                     \
       x[k] = xv;                                                                                                            \
@@ -310,17 +310,12 @@ __global__ __launch_bounds__(NT, 1) void k_relax_wave(LevView G, int nsweeps, in
       for (int k = 0; k < NZ; k++) {
         double r;
         if (k == 0) {
-          r = ob[q][k] - a1[k] * pc[k] - a2[q][k + 1] * pc[k + 1] - a3[q][k] * pjm[k + 1] - a4[q][k] * pjm[k] - R4(q, k) * pjp[k] - R5(q, k + 1) * pjp[k + 1]
-                       - a6[q][k] * pim[k + 1] - a7[q][k] * pim[k] - R7(q, k) * pip[k] - R8(q, k + 1) * pip[k + 1];
+          r = ROW_RHS_FIRST(ob[q][k] - a1[k] * pc[k] - a2[q][k + 1] * pc[k + 1], WAVE_TERMS(q));
           if (REAL) r = r - a5[q][0] * P[oc + sim + sjp] - e2[q] * P[oc + sip + sjm] - a8[q][0] * P[oc + sim + sjm] - e4[q] * P[oc + sip + sjp];
         } else if (k < NZ - 1) {
-          r = ob[q][k] - a1[k] * pc[k] - a2[q][k] * pc[k - 1] - a2[q][k + 1] * pc[k + 1] - a3[q][k] * pjm[k + 1] - R3(q, k - 1) * pjp[k - 1]
-                       - a4[q][k] * pjm[k] - R4(q, k) * pjp[k] - a5[q][k] * pjm[k - 1] - R5(q, k + 1) * pjp[k + 1]
-                       - a6[q][k] * pim[k + 1] - R6(q, k - 1) * pip[k - 1] - a7[q][k] * pim[k] - R7(q, k) * pip[k]
-                       - a8[q][k] * pim[k - 1] - R8(q, k + 1) * pip[k + 1];
+          r = ROW_RHS_MID(ob[q][k] - a1[k] * pc[k] - a2[q][k] * pc[k - 1] - a2[q][k + 1] * pc[k + 1], WAVE_TERMS(q));
         } else {
-          r = ob[q][k] - a1[k] * pc[k] - a2[q][k] * pc[k - 1] - R3(q, k - 1) * pjp[k - 1] - a4[q][k] * pjm[k] - R4(q, k) * pjp[k]
-                       - a5[q][k] * pjm[k - 1] - R6(q, k - 1) * pip[k - 1] - a7[q][k] * pim[k] - R7(q, k) * pip[k] - a8[q][k] * pim[k - 1];
+          r = ROW_RHS_LAST(ob[q][k] - a1[k] * pc[k] - a2[q][k] * pc[k - 1], WAVE_TERMS(q));
         }
         rr[q][k] = r;
       }
@@ -339,6 +334,7 @@ __global__ __launch_bounds__(NT, 1) void k_relax_wave(LevView G, int nsweeps, in
     }
   }
 #undef COLUMN
+#undef WAVE_TERMS
 #undef R3
 #undef R4
 #undef R5

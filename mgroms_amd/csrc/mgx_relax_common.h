@@ -124,12 +124,7 @@
   }                                                                                                       \
   /* k = 1 horizontal-diagonal terms (mg_relax.f90:271-276); red-black reads them from the snapshot taken before the pass */ \
   double d1 = 0, d2 = 0, d3 = 0, d4 = 0, e1 = 0, e2 = 0, e3 = 0, e4 = 0;                                  \
-  if (REAL) {                                                                                             \
-    const double *__restrict__ q1 = SNAP ? L.p1 : p;                                                      \
-    const long long s = SNAP ? (long long)i * RS : o, sm = SNAP ? s - RS : om, sp = SNAP ? s + RS : op;   \
-    d1 = q1[sm + jp]; d2 = q1[sp + jm]; d3 = q1[sm + jm]; d4 = q1[sp + jp];                               \
-    e1 = a5[o + c]; e2 = a5[op + jm]; e3 = a8[o + c]; e4 = a8[op + jp];                                   \
-  }                                                                                                       \
+  if (REAL) K1_DIAG(SNAP, d1, d2, d3, d4, e1, e2, e3, e4)                                                 \
   _Pragma("unroll") for (int q = 1; q <= 1 + D; q++) { MF_NB_LOAD(q) }                                    \
   _Pragma("unroll") for (int q = 1; q <= 1 + D; q++) { MF_OW_LOAD(q) }                                    \
   /* three-row windows (k-1, k, k+1) of the neighbour columns' p and of the own slopes */                 \
@@ -154,8 +149,7 @@
     const double zyjm = r_zyjm[n], zyjp = r_zyjp[n], zxim = r_zxim[n], zxip = r_zxip[n];                  \
     /* the eight cross coefficients of this row, rebuilt from the slopes: own slots 3,5,6,8 and the mirrored ones stored at */ \
     /* the j+1 / i+1 neighbours */                                                                        \
-    const double c3 = qrt * (zy_p + zyjm), c3m = qrt * (zyjp + zy_m), c5 = -qrt * (zy_m + zyjm), c5m = -qrt * (zyjp + zy_p); \
-    const double c6 = qrt * (zx_p + zxim), c6m = qrt * (zxip + zx_m), c8 = -qrt * (zx_m + zxim), c8m = -qrt * (zxip + zx_p); \
+    MF_CROSS_COEF(zy_m, zy_p, zyjm, zyjp, zx_m, zx_p, zxim, zxip)                                         \
     double a4o, a4jp, a7o, a7ip;  /* slots 4 and 7 of the cell and of its j+1 / i+1 neighbour */          \
     if (!ZW) { a4o = o_a4[s]; a4jp = r_a4[n]; a7o = o_a7[s]; a7ip = r_a7[n]; }                            \
     else if (k == 1) { a4o = a4_1; a4jp = a4j_1; a7o = a7_1; a7ip = a7i_1; }                              \
@@ -164,10 +158,10 @@
       if (k == 2) { _Pragma("unroll") for (int q = 0; q < 5; q++) zw0[q] = ZW_GEN(2, q); }                \
       _Pragma("unroll") for (int q = 0; q < 5; q++) zw1[q] = ZW_GEN(k + 1, q);                            \
       const double wo0 = zw0[0], wop1 = zw1[0];                                                           \
-      a4o = DIVC(qrt * (wop1 - wo0 + zw1[1] - zw0[1]) * m4c, d4c, r4c);                                   \
-      a4jp = DIVC(qrt * (zw1[2] - zw0[2] + wop1 - wo0) * m4p, d4p, r4p);                                  \
-      a7o = DIVC(qrt * (wop1 - wo0 + zw1[3] - zw0[3]) * m7c, d7c, r7c);                                   \
-      a7ip = DIVC(qrt * (zw1[4] - zw0[4] + wop1 - wo0) * m7p, d7p, r7p);                                  \
+      a4o = SLOT47_GEN(wop1, wo0, zw1[1], zw0[1], m4c, d4c, r4c);                                         \
+      a4jp = SLOT47_GEN(zw1[2], zw0[2], wop1, wo0, m4p, d4p, r4p);                                        \
+      a7o = SLOT47_GEN(wop1, wo0, zw1[3], zw0[3], m7c, d7c, r7c);                                         \
+      a7ip = SLOT47_GEN(zw1[4], zw0[4], wop1, wo0, m7p, d7p, r7p);                                        \
       _Pragma("unroll") for (int q = 0; q < 5; q++) zw0[q] = zw1[q];                                      \
     }                                                                                                     \
     double dk, betk;  /* the pivots (header comment) */                                                   \
@@ -179,19 +173,14 @@
     betp = betk;                                                                                          \
     double rhs;                                                                                           \
     if (k == 1) {                                                                                         \
-      rhs = o_b[s] - c3 * pjm_p - a4o * pjm_0 - a4jp * pjp_0 - c5m * pjp_p                                \
-                   - c6 * pim_p - a7o * pim_0 - a7ip * pip_0 - c8m * pip_p;                               \
+      rhs = ROW_RHS_FIRST(o_b[s], MF_TERMS);                                                              \
       if (REAL) rhs = rhs - e1 * d1 - e2 * d2 - e3 * d3 - e4 * d4;                                        \
       xv = rhs * betk;                                                                                    \
     } else if (k < NZ) {                                                                                  \
-      rhs = o_b[s] - c3 * pjm_p - c3m * pjp_m - a4o * pjm_0 - a4jp * pjp_0                                \
-                   - c5 * pjm_m - c5m * pjp_p                                                             \
-                   - c6 * pim_p - c6m * pip_m - a7o * pim_0 - a7ip * pip_0                                \
-                   - c8 * pim_m - c8m * pip_p;                                                            \
+      rhs = ROW_RHS_MID(o_b[s], MF_TERMS);                                                                \
       xv = (rhs - o_a2[s] * xv) * betk;                                                                   \
     } else {                                                                                              \
-      rhs = o_b[s] - c3m * pjp_m - a4o * pjm_0 - a4jp * pjp_0 - c5 * pjm_m                                \
-                   - c6m * pip_m - a7o * pim_0 - a7ip * pip_0 - c8 * pim_m;                               \
+      rhs = ROW_RHS_LAST(o_b[s], MF_TERMS);                                                               \
       xv = (rhs - o_a2[s] * xv) * betk;                                                                   \
     }                                                                                                     \
     MF_X_PUT(k, xv, o_a2[s], betk)                                                                        \
@@ -203,7 +192,7 @@
 // ------------------------------------------------------------------------------------------------
 // The stored-coefficient column pass: ONE text for relax_col_nz (mgx_relax.hip, nz <= 64) and relax_col_st_tall
 // (mgx_relax_tall.hip): slots 2-8 and the pivots bet as define_matrices or mgx_set_field(cA) left them, nothing regenerated (masked
-// domains, user matrices, MGX_NO_MF).  The rhs of a row after mg_relax.f90:262-301, same terms in the same order.  Macros for the
+// domains, user matrices, MGX_NO_MF).  The rhs of a row after mg_relax.f90:262-301: ROW_RHS_* (mgx_device.h) on SC_TERMS.  Macros for the
 // reason given above; the instances of relax_col_nz compile to the instructions they had when this text stood in their function.
 //
 // The caller has in scope: NZ, D (look-ahead rows), REAL, SNAP, ST (compile-time); L, i, c, jm, jp; and two sinks,
@@ -247,12 +236,7 @@
   double x[XN], g[GN];  /* the forward values and gam that stay in registers (the sinks' business) */     \
   /* k = 1 horizontal-diagonal terms (issued first: independent of everything else); red-black reads them from the snapshot */ \
   double d1 = 0, d2 = 0, d3 = 0, d4 = 0, e1 = 0, e2 = 0, e3 = 0, e4 = 0;                                  \
-  if (REAL) {                                                                                             \
-    const double *__restrict__ q1 = SNAP ? L.p1 : p;                                                      \
-    const long long s = SNAP ? (long long)i * RS : o, sm = SNAP ? s - RS : om, sp = SNAP ? s + RS : op;   \
-    d1 = q1[sm + jp]; d2 = q1[sp + jm]; d3 = q1[sm + jm]; d4 = q1[sp + jp];                               \
-    e1 = a5[o + c]; e2 = a5[op + jm]; e3 = a8[o + c]; e4 = a8[op + jp];                                   \
-  }                                                                                                       \
+  if (REAL) K1_DIAG(SNAP, d1, d2, d3, d4, e1, e2, e3, e4)                                                 \
   /* neighbour rows 1..1+D and own rows 1..D */                                                           \
   _Pragma("unroll") for (int q = 1; q <= 1 + D; q++) { SC_NB_LOAD(q) }                                    \
   _Pragma("unroll") for (int q = 1; q <= D; q++) { SC_OW_LOAD(q) }                                        \
@@ -262,6 +246,8 @@
   (void)dum5; (void)dum8;                                                                                 \
   double xv = 0.0, betp = 0.0;
 
+// row k of SC_ROW as the arguments of ROW_RHS_* (mgx_device.h): own slots from the ring, the neighbours' products of SC_NB_USE
+#define SC_TERMS o_b[s], o_a3[s] * pjm_p, m3_m, o_a4[s] * pjm_0, m4_0, o_a5[s] * pjm_m, m5_p, o_a6[s] * pim_p, n6_m, o_a7[s] * pim_0, n7_0, o_a8[s] * pim_m, n8_p
 #define SC_ROW(k)                                                                                         \
   {                                                                                                       \
     /* keep the pipeline full */                                                                          \
@@ -274,15 +260,14 @@
     if (k > 1) SC_G_PUT(k, o_a2[s] * betp)                                                                \
     betp = o_bet[s];                                                                                      \
     if (k == 1) {                                                                                         \
-      rhs = o_b[s] - o_a3[s] * pjm_p - o_a4[s] * pjm_0 - m4_0 - m5_p - o_a6[s] * pim_p - o_a7[s] * pim_0 - n7_0 - n8_p; \
+      rhs = ROW_RHS_FIRST(SC_TERMS);                                                                      \
       if (REAL) rhs = rhs - e1 * d1 - e2 * d2 - e3 * d3 - e4 * d4;                                        \
       xv = rhs * o_bet[s];                                                                                \
     } else if (k < NZ) {                                                                                  \
-      rhs = o_b[s] - o_a3[s] * pjm_p - m3_m - o_a4[s] * pjm_0 - m4_0 - o_a5[s] * pjm_m - m5_p             \
-                   - o_a6[s] * pim_p - n6_m - o_a7[s] * pim_0 - n7_0 - o_a8[s] * pim_m - n8_p;            \
+      rhs = ROW_RHS_MID(SC_TERMS);                                                                        \
       xv = (rhs - o_a2[s] * xv) * o_bet[s];                                                               \
     } else {                                                                                              \
-      rhs = o_b[s] - m3_m - o_a4[s] * pjm_0 - m4_0 - o_a5[s] * pjm_m - n6_m - o_a7[s] * pim_0 - n7_0 - o_a8[s] * pim_m; \
+      rhs = ROW_RHS_LAST(SC_TERMS);                                                                       \
       xv = (rhs - o_a2[s] * xv) * o_bet[s];                                                               \
     }                                                                                                     \
     SC_X_PUT(k, xv)                                                                                       \

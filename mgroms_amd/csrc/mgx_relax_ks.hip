@@ -8,7 +8,7 @@
 // So NW waves share one set of 64 columns: wave w builds rhs(k) for its NZ/NW rows (all its loads issued at once),
 // parks them in LDS, wave 0 runs the two sweeps of the recurrence from LDS, and all waves store their rows of p.
 // Four (or eight) times the loads in flight per column, two round trips instead of nine.
-// Same expressions in the same order as relax_col_mf: bit-identical results.
+// The rows expand MF_CROSS_COEF and ROW_RHS_* (mgx_device.h), the text of relax_col_mf's rows: bit-identical results.
 #include "mgx_switches.h"
 #include "mgx_relax_common.h"
 
@@ -21,6 +21,11 @@ __device__ long long g_ks_stamp[1024 * 8];
 #else
 #define KS_STAMP(q)
 #endif
+// Row k = ka + r of both row builders of this file as the arguments of ROW_RHS_* (mgx_device.h), with the cross coefficients of
+// MF_CROSS_COEF and the three-row windows around row k.  It reads the rows' arrays by the names they have in k_relax_ks (bb, a4o, a4n,
+// a7o, a7n); ks_rhs binds those names to the arrays of its KsRows.
+#define KS_TERMS bb[r], c3 * pjm_p, c3m * pjp_m, a4o[r] * pjm_0, a4n[r] * pjp_0, c5 * pjm_m, c5m * pjp_p, \
+                 c6 * pim_p, c6m * pip_m, a7o[r] * pim_0, a7n[r] * pip_0, c8 * pim_m, c8m * pip_p
 template <int NZ, int NW, bool REAL, bool SNAP, int H = 1>
 __global__ __launch_bounds__(64 * NW, 1) void k_relax_ks(LevView L, int i0, int istep, int nplanes, int jodd_fixed, int rb, Sides ph, int gx) {
   constexpr int R = NZ / NW / H;  // rows per wave and run
@@ -73,12 +78,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_relax_ks(LevView L, int i0, int 
       oa2[r] = a2[o + ro + c]; obt[r] = bet[o + ro + c];
     }
     if (w == 0 && run == 0) {
-      if (REAL) {
-        const double *__restrict__ q1 = SNAP ? L.p1 : p;
-        const long long s = SNAP ? (long long)i * RS : o, sm = SNAP ? s - RS : om, sp = SNAP ? s + RS : op;
-        d1 = q1[sm + jp]; d2 = q1[sp + jm]; d3 = q1[sm + jm]; d4 = q1[sp + jp];
-        e1 = a5[o + c]; e2 = a5[op + jm]; e3 = a8[o + c]; e4 = a8[op + jp];
-      }
+      if (REAL) K1_DIAG(SNAP, d1, d2, d3, d4, e1, e2, e3, e4)
     }
 #ifdef MGX_KS_STAMP
     KS_STAMP(1)
@@ -92,21 +92,15 @@ __global__ __launch_bounds__(64 * NW, 1) void k_relax_ks(LevView L, int i0, int 
       const double pjm_m = pjm[r], pjm_0 = pjm[r + 1], pjm_p = pjm[r + 2], pim_m = pim[r], pim_0 = pim[r + 1], pim_p = pim[r + 2];
       const double pjp_m = pjp[r], pjp_0 = pjp[r + 1], pjp_p = pjp[r + 2], pip_m = pip[r], pip_0 = pip[r + 1], pip_p = pip[r + 2];
       const double zy_m = zyo[r], zy_p = zyo[r + 2], zx_m = zxo[r], zx_p = zxo[r + 2];
-      const double c3 = qrt * (zy_p + zyjm[r]), c3m = qrt * (zyjp[r] + zy_m), c5 = -qrt * (zy_m + zyjm[r]), c5m = -qrt * (zyjp[r] + zy_p);
-      const double c6 = qrt * (zx_p + zxim[r]), c6m = qrt * (zxip[r] + zx_m), c8 = -qrt * (zx_m + zxim[r]), c8m = -qrt * (zxip[r] + zx_p);
+      MF_CROSS_COEF(zy_m, zy_p, zyjm[r], zyjp[r], zx_m, zx_p, zxim[r], zxip[r])
       double rhs;
       if (k == 1) {
-        rhs = bb[r] - c3 * pjm_p - a4o[r] * pjm_0 - a4n[r] * pjp_0 - c5m * pjp_p
-                    - c6 * pim_p - a7o[r] * pim_0 - a7n[r] * pip_0 - c8m * pip_p;
+        rhs = ROW_RHS_FIRST(KS_TERMS);
         if (REAL) rhs = rhs - e1 * d1 - e2 * d2 - e3 * d3 - e4 * d4;
       } else if (k < NZ) {
-        rhs = bb[r] - c3 * pjm_p - c3m * pjp_m - a4o[r] * pjm_0 - a4n[r] * pjp_0
-                    - c5 * pjm_m - c5m * pjp_p
-                    - c6 * pim_p - c6m * pip_m - a7o[r] * pim_0 - a7n[r] * pip_0
-                    - c8 * pim_m - c8m * pip_p;
+        rhs = ROW_RHS_MID(KS_TERMS);
       } else {
-        rhs = bb[r] - c3m * pjp_m - a4o[r] * pjm_0 - a4n[r] * pjp_0 - c5 * pjm_m
-                    - c6m * pip_m - a7o[r] * pim_0 - a7n[r] * pip_0 - c8 * pim_m;
+        rhs = ROW_RHS_LAST(KS_TERMS);
       }
       sh[(k - 1) * WAVE + lane] = rhs;
       sa2[(k - 1) * WAVE + lane] = oa2[r];
@@ -188,7 +182,7 @@ extern "C" int mgxk_ks_stamps(long long *out) { return hipMemcpyFromSymbol(out, 
 // colour a, keeps its result in LDS, and runs colour b from there; everything else colour b needs is requested at the start and
 // arrives while colour a is computed.  The mid levels are launch- and latency-bound (6 and 4.8 us per pass for 4096 and 1024
 // columns): 10 launches per V-cycle-level instead of 20.  Closed levels only (no exchange between the two colours).
-// Same expressions in the same order: bit-identical to the two separate passes.
+// ks_rhs expands the row text of k_relax_ks (KS_TERMS, ROW_RHS_*): bit-identical to the two separate passes.
 // ------------------------------------------------------------------------------------------------
 namespace {
 template <int R>
@@ -222,34 +216,29 @@ __device__ __forceinline__ void ks_load(KsRows<R> &q, const LevView &L, const lo
   }
   q.e1 = q.e2 = q.e3 = q.e4 = 0.0;
   if (REAL && diag) {  // the wave that owns row 1: coefficients of the four k=1 horizontal diagonals (mg_relax.f90:271-276)
-    q.e1 = a5[o + c]; q.e2 = a5[op + jm]; q.e3 = a8[o + c]; q.e4 = a8[op + jp];
+    K1_COEF(q.e1, q.e2, q.e3, q.e4)
   }
 }
 template <int NZ, int R, bool REAL>
 __device__ __forceinline__ void ks_rhs(const KsRows<R> &q, const double *pjm, const double *pjp, const double d1, const double d2, const double d3, const double d4,
                                        const int ka, const int lane, double *__restrict__ sh, double *__restrict__ sa2, double *__restrict__ sbt) {
   const double qrt = 0.25;
+  const double(&bb)[R] = q.bb, (&a4o)[R] = q.a4o, (&a4n)[R] = q.a4n, (&a7o)[R] = q.a7o, (&a7n)[R] = q.a7n;  // the names KS_TERMS reads
 #pragma unroll
   for (int r = 0; r < R; r++) {
     const int k = ka + r;
     const double pjm_m = pjm[r], pjm_0 = pjm[r + 1], pjm_p = pjm[r + 2], pim_m = q.pim[r], pim_0 = q.pim[r + 1], pim_p = q.pim[r + 2];
     const double pjp_m = pjp[r], pjp_0 = pjp[r + 1], pjp_p = pjp[r + 2], pip_m = q.pip[r], pip_0 = q.pip[r + 1], pip_p = q.pip[r + 2];
     const double zy_m = q.zyo[r], zy_p = q.zyo[r + 2], zx_m = q.zxo[r], zx_p = q.zxo[r + 2];
-    const double c3 = qrt * (zy_p + q.zyjm[r]), c3m = qrt * (q.zyjp[r] + zy_m), c5 = -qrt * (zy_m + q.zyjm[r]), c5m = -qrt * (q.zyjp[r] + zy_p);
-    const double c6 = qrt * (zx_p + q.zxim[r]), c6m = qrt * (q.zxip[r] + zx_m), c8 = -qrt * (zx_m + q.zxim[r]), c8m = -qrt * (q.zxip[r] + zx_p);
+    MF_CROSS_COEF(zy_m, zy_p, q.zyjm[r], q.zyjp[r], zx_m, zx_p, q.zxim[r], q.zxip[r])
     double rhs;
     if (k == 1) {
-      rhs = q.bb[r] - c3 * pjm_p - q.a4o[r] * pjm_0 - q.a4n[r] * pjp_0 - c5m * pjp_p
-                    - c6 * pim_p - q.a7o[r] * pim_0 - q.a7n[r] * pip_0 - c8m * pip_p;
+      rhs = ROW_RHS_FIRST(KS_TERMS);
       if (REAL) rhs = rhs - q.e1 * d1 - q.e2 * d2 - q.e3 * d3 - q.e4 * d4;
     } else if (k < NZ) {
-      rhs = q.bb[r] - c3 * pjm_p - c3m * pjp_m - q.a4o[r] * pjm_0 - q.a4n[r] * pjp_0
-                    - c5 * pjm_m - c5m * pjp_p
-                    - c6 * pim_p - c6m * pip_m - q.a7o[r] * pim_0 - q.a7n[r] * pip_0
-                    - c8 * pim_m - c8m * pip_p;
+      rhs = ROW_RHS_MID(KS_TERMS);
     } else {
-      rhs = q.bb[r] - c3m * pjp_m - q.a4o[r] * pjm_0 - q.a4n[r] * pjp_0 - c5 * pjm_m
-                    - c6m * pip_m - q.a7o[r] * pim_0 - q.a7n[r] * pip_0 - c8 * pim_m;
+      rhs = ROW_RHS_LAST(KS_TERMS);
     }
     sh[(k - 1) * WAVE + lane] = rhs;
     sa2[(k - 1) * WAVE + lane] = q.oa2[r];
@@ -343,7 +332,7 @@ __device__ __forceinline__ void ks_load_coef(KsRows<R> &q, const LevView &L, con
     q.oa2[r] = a2[o + ro + c]; q.obt[r] = bet[o + ro + c];
   }
   q.e1 = q.e2 = q.e3 = q.e4 = 0.0;
-  if (REAL && diag) { q.e1 = a5[o + c]; q.e2 = a5[op + jm]; q.e3 = a8[o + c]; q.e4 = a8[op + jp]; }
+  if (REAL && diag) K1_COEF(q.e1, q.e2, q.e3, q.e4)
 }
 // ... and the i-1 / i+1 neighbours of p, which the neighbouring planes' workgroups rewrite every sweep
 template <int NZ, int R, bool WT>
@@ -442,7 +431,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_relax_ks2(LevView L, int i0, int
 // stores, L1-bypassing loads -- which the guide measured as sufficient on gfx950 but does not call an architectural guarantee.  All nx workgroups must be resident together (<= 128 of
 // them, one per CU: 512 threads at up to 256 registers); the poll is bounded (2 s of the constant clock -> error word, reported by
 // the next synchronising call) so that a co-tenant that keeps a workgroup off the chip cannot hang the stream.
-// Same expressions in the same order as k_relax_ks2: bit-identical.
+// The rows are those of k_relax_ks2, by the same ks_rhs (KS_TERMS, ROW_RHS_*): bit-identical.
 // ------------------------------------------------------------------------------------------------
 // bound of a plane's wait for its neighbours, ticks of the 100 MHz constant clock (2 s; mgxk_set_ksp_timeout shortens it for the test)
 __device__ long long g_ksp_timeout_ticks = 200000000LL;

@@ -14,7 +14,7 @@
 // forward-eliminated values of the lower LOW rows wait in LDS (xf: LOW rows x 64 lanes x 8 B = 32 KB per wave, one wave per SIMD = 128 KB
 // of the CU's 160 KB) instead of going out to p and coming back; their gam is rebuilt on the way down from a2(k+1) and bet(k), re-read
 // ahead of use (addresses are known: no dependent loads).  x and gam of the upper NZ-LOW rows stay in registers.
-// Same expressions, same order: bit-identical to the reference.
+// The rows expand ROW_RHS_* (mgx_device.h) through MF_ROW / SC_ROW: bit-identical to the reference.
 //
 // TALL_DOWN: the way down of both forms.  In scope: NZ, LOW, UP, SNAP, ST; L, i, jh, jodd, ph, c, o, RS, p, a2, bet, lane, xf; x[UP], g[UP]
 // of the upper rows after the forward pass and g0 = gam(LOW+1).

@@ -11,14 +11,14 @@
 // the partner lane's two values (one cross-lane exchange per row): no r traffic, no diagonal stream, one launch.
 // Measured (rocprofv3, MI355X): 512x512x64 211-224 us against 279 + 36 for the two kernels (round 2: 236-250 with guarded look-ahead);
 // levels of up to 256x256x64 cells take k_residual_restrict_flat below (256x256x32: 24 us against 47 + 13).
-// The residuals and the 8-term sum use the reference's expressions in the reference's order: b_c is bit-identical to
+// The residuals expand ROW_RHS_* and MF_CROSS_COEF (mgx_device.h) and the 8-term sum keeps the reference's order: b_c is bit-identical to
 // compute_residual followed by fine2coarse.  Matrix-free cross terms (needs the slopes zy, zx: the matrix must be the one
 // define_matrices built); other cases keep the two separate kernels.  The norm of the closing residual (NORM) is bit-identical too:
 // here and in k_residual / k_residual_mf the sum of r^2 is carried as a pair and rounded once (dd_add, mgx_device.h), so the way a
 // kernel groups the cells does not reach it.
 // ZW (the walking form without the norm, where the level carries the 2-D factors and sigma tables of the smoother's ZW form): the
 // interior rows of slots 4 and 7 are not streamed either but generated from the depth formula, with the smoother's expressions
-// (ZW_GEN, RCP_REF, DIVC of mgx_device.h; MF_ROW of mgx_relax_common.h) -- same bits, 755 MB moved instead of 1005 (FETCH x 2 + WRITE)
+// (ZW_GEN, SLOT47_GEN, RCP_REF, DIVC of mgx_device.h, which MF_ROW of mgx_relax_common.h expands too) -- same bits, 755 MB moved instead of 1005 (FETCH x 2 + WRITE)
 // and 197-199 us instead of 216-219 at 512x512x64.  The kernel then issues ~650 instructions per row on its one wave per SIMD: it is
 // bound by issue, not by its 3.8 TB/s, which is why a quarter less traffic buys a tenth of the time (profiles/resrest_zw.json).
 #include "mgx_switches.h"
@@ -225,8 +225,7 @@ __global__ __launch_bounds__(256, 1) void k_residual_restrict(LevView F, LevView
       const double zxim = R0.ZXm[jj], zxip = R0.ZXp[jj];                                                                    \
       const double a4o = S4[jj], a4jp = S4[jj + 1], a7o = S7[jj], a7ip = S7P[jj];                                            \
       const double a2_0 = W0.A2[jj], a2_p = Wp.A2[jj];                                                                      \
-      const double c3 = qrt * (zy_p + zyjm), c3m = qrt * (zyjp + zy_m), c5 = -qrt * (zy_m + zyjm), c5m = -qrt * (zyjp + zy_p); \
-      const double c6 = qrt * (zx_p + zxim), c6m = qrt * (zxip + zx_m), c8 = -qrt * (zx_m + zxim), c8m = -qrt * (zxip + zx_p); \
+      MF_CROSS_COEF(zy_m, zy_p, zyjm, zyjp, zx_m, zx_p, zxim, zxip)                                                         \
       (void)pc_m; (void)pjm_m; (void)pjp_m; (void)pim_m; (void)pip_m; (void)c3m; (void)c5; (void)c6m; (void)c8; (void)a2_0;
   /* fine2coarse_3D (mg_intergrids.f90:149-160): (k,jA,iA) + (k,jA,iB) + (k,jB,iA) + (k,jB,iB), then the same of k+1;
      the iB values come from the partner lane (lane ^ 32) */
@@ -248,16 +247,15 @@ __global__ __launch_bounds__(256, 1) void k_residual_restrict(LevView F, LevView
 #define RR_GENERAL(rr, R0)                                                                                                  \
       {                                                                                                                     \
         const double dk = -a2_0 - a2_p - a4o - a4jp - a7o - a7ip - c6 - c6m - c8 - c8m - c3 - c3m - c5 - c5m;               \
-        rr = R0.B[jj] - dk * pc_0 - a2_0 * pc_m - a2_p * pc_p - c3 * pjm_p - c3m * pjp_m                                    \
-                      - a4o * pjm_0 - a4jp * pjp_0 - c5 * pjm_m - c5m * pjp_p                                                \
-                      - c6 * pim_p - c6m * pip_m - a7o * pim_0 - a7ip * pip_0                                                \
-                      - c8 * pim_m - c8m * pip_p;                                                                            \
+        rr = ROW_RHS_MID(R0.B[jj] - dk * pc_0 - a2_0 * pc_m - a2_p * pc_p, MF_TERMS);                                       \
       }
   /* last row, :498-509 (stored diagonal) */
-#define RR_LAST(rr, R0, DL)                                                                                                 \
+#define RR_LAST(rr, R0, DL) { rr = ROW_RHS_LAST(R0.B[jj] - (DL) * pc_0 - a2_0 * pc_m, MF_TERMS); }
+  /* first row, :464-482 (stored diagonal; E = the row's four k = 1 diagonal slots, each followed by its corner value of p) */
+#define RR_FIRST(rr, R0, DE, E)                                                                                             \
       {                                                                                                                     \
-        rr = R0.B[jj] - (DL) * pc_0 - a2_0 * pc_m - c3m * pjp_m - a4o * pjm_0 - a4jp * pjp_0                           \
-                      - c5 * pjm_m - c6m * pip_m - a7o * pim_0 - a7ip * pip_0 - c8 * pim_m;                                  \
+        rr = ROW_RHS_FIRST(R0.B[jj] - (DE) * pc_0 - a2_p * pc_p, MF_TERMS);                                                 \
+        if (REAL) rr = rr - E[0] * E[1] - E[2] * E[3] - E[4] * E[5] - E[6] * E[7];                                          \
       }
   /* ZW: zw of row kk (mg_zr_zw.f90:140-145, ZW_GEN of mgx_device.h) at jA-1, jA, jB, jB+1 of the own plane (zo) and at jA, jB of planes
      i-1 (zm) and i+1 (zp).  One of the two is the partner's plane (lane ^ 32: i+1 for half 0, i-1 for half 1), whose depths are the
@@ -274,7 +272,7 @@ __global__ __launch_bounds__(256, 1) void k_residual_restrict(LevView F, LevView
       }                                                                                                                     \
     }
   /* ZW: slots 4 and 7 of row k (a4 at jA, jB, jB+1; a7 at jA, jB of the own plane and of plane i+1), not streamed: the interior formula
-     (mg_define_matrix.f90:532-534, 549-551) as MF_ROW of mgx_relax_common.h spells it, on zw of rows k and k+1 -- both generated at
+     (mg_define_matrix.f90:532-534, 549-551: SLOT47_GEN of mgx_device.h, which MF_ROW expands too), on zw of rows k and k+1 -- both generated at
      the step: a carried row k costs 16 registers that the walk does not have; row nz from where the prologue parked it */
 #define RR_SLOTS(k)                                                                                                         \
     double s4[3], s7[2], s7p[2];                                                                                            \
@@ -283,10 +281,10 @@ __global__ __launch_bounds__(256, 1) void k_residual_restrict(LevView F, LevView
       double zlo[4], zlm[2], zlp[2], zhi[4], zhm[2], zhp[2];                                                                \
       RR_ZW_ROW(k, zlo, zlm, zlp)                                                                                           \
       RR_ZW_ROW((k) + 1, zhi, zhm, zhp)                                                                                     \
-      _Pragma("unroll") for (int q = 0; q < 3; q++) s4[q] = DIVC(qrt * (zhi[q + 1] - zlo[q + 1] + zhi[q] - zlo[q]) * m4[q], d4[q], r4[q]); \
+      _Pragma("unroll") for (int q = 0; q < 3; q++) s4[q] = SLOT47_GEN(zhi[q + 1], zlo[q + 1], zhi[q], zlo[q], m4[q], d4[q], r4[q]); \
       _Pragma("unroll") for (int jj = 0; jj < 2; jj++) {                                                                     \
-        s7[jj] = DIVC(qrt * (zhi[jj + 1] - zlo[jj + 1] + zhm[jj] - zlm[jj]) * m7[jj], d7[jj], r7[jj]);                       \
-        s7p[jj] = DIVC(qrt * (zhp[jj] - zlp[jj] + zhi[jj + 1] - zlo[jj + 1]) * m7p[jj], d7p[jj], r7p[jj]);                   \
+        s7[jj] = SLOT47_GEN(zhi[jj + 1], zlo[jj + 1], zhm[jj], zlm[jj], m7[jj], d7[jj], r7[jj]);                             \
+        s7p[jj] = SLOT47_GEN(zhp[jj], zlp[jj], zhi[jj + 1], zlo[jj + 1], m7p[jj], d7p[jj], r7p[jj]);                         \
       }                                                                                                                     \
     } else { _Pragma("unroll") for (int q = 0; q < 3; q++) s4[q] = parked[q * 256];                                          \
              _Pragma("unroll") for (int jj = 0; jj < 2; jj++) { s7[jj] = parked[(3 + jj) * 256]; s7p[jj] = parked[(5 + jj) * 256]; } }
@@ -311,9 +309,8 @@ __global__ __launch_bounds__(256, 1) void k_residual_restrict(LevView F, LevView
 #pragma unroll
     for (int jj = 0; jj < 2; jj++) {
       RR_CELL_IN(W[0], W[0], W[1], R[NRB - 1], R1.A4, R1.A7, R1.A7p)
-      double rr = R[NRB - 1].B[jj] - dedge[jj] * pc_0 - a2_p * pc_p - c3 * pjm_p - a4o * pjm_0 - a4jp * pjp_0
-                                   - c5m * pjp_p - c6 * pim_p - a7o * pim_0 - a7ip * pip_0 - c8m * pip_p;
-      if (REAL) rr = rr - e[jj][0] * e[jj][1] - e[jj][2] * e[jj][3] - e[jj][4] * e[jj][5] - e[jj][6] * e[jj][7];
+      double rr;
+      RR_FIRST(rr, R[NRB - 1], dedge[jj], e[jj])
       r[jj] = rr;
     }
     RR_SUM(1, r)
@@ -348,8 +345,8 @@ __global__ __launch_bounds__(256, 1) void k_residual_restrict(LevView F, LevView
 // The same operator without the walk.  A lane that climbs its column pays one memory round trip per row step (20 us for nz = 16 and 13 us
 // for nz = 8 on 8-32 CUs, measured), but nothing in r = b - A p is sequential in k.  Here one wave owns S fine rows (S/2 coarse rows) of 32
 // coarse columns (both fine planes, as above): the S + 2 window rows and the S rows' own values are all requested at once, the rows are
-// computed and the 8-cell sums closed with the partner lane -- one round trip, nz/S times the waves.  Same expressions (the macros above),
-// same order: bit-identical.
+// computed and the 8-cell sums closed with the partner lane -- one round trip, nz/S times the waves.  The rows are RR_FIRST / RR_GENERAL /
+// RR_LAST above: bit-identical.
 template <bool REAL, int S, bool NORM = false>
 __global__ __launch_bounds__(64) void k_residual_restrict_flat(LevView F, LevView C, double *__restrict__ dst, Sides ph, double *__restrict__ zero, int gx,
                                                               double *__restrict__ partial = nullptr, double *__restrict__ dup = nullptr) {
@@ -413,11 +410,8 @@ __global__ __launch_bounds__(64) void k_residual_restrict_flat(LevView F, LevVie
       for (int jj = 0; jj < 2; jj++) {
         RR_CELL_IN(W[r], W[r + 1], W[r + 2], R[r], R[r].A4, R[r].A7, R[r].A7p)
         double rr;
-        if (r == 0 && kr == 1) {
-          rr = R[r].B[jj] - dedge[jj] * pc_0 - a2_p * pc_p - c3 * pjm_p - a4o * pjm_0 - a4jp * pjp_0
-                          - c5m * pjp_p - c6 * pim_p - a7o * pim_0 - a7ip * pip_0 - c8m * pip_p;
-          if (REAL) rr = rr - e[jj][0] * e[jj][1] - e[jj][2] * e[jj][3] - e[jj][4] * e[jj][5] - e[jj][6] * e[jj][7];
-        } else if (kr < nz) RR_GENERAL(rr, R[r])
+        if (r == 0 && kr == 1) RR_FIRST(rr, R[r], dedge[jj], e[jj])
+        else if (kr < nz) RR_GENERAL(rr, R[r])
         else RR_LAST(rr, R[r], dlast[jj])
         rv[jj] = rr;
       }
@@ -435,6 +429,7 @@ __global__ __launch_bounds__(64) void k_residual_restrict_flat(LevView F, LevVie
 #undef RR_CELL_IN
 #undef RR_GENERAL
 #undef RR_LAST
+#undef RR_FIRST
 
 extern "C" {
 
