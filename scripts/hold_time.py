@@ -17,7 +17,7 @@ import torch  # noqa: E402
 
 import mgroms_amd as mg  # noqa: E402
 from mgroms_amd import nhydro  # noqa: E402
-from mgroms_amd.testcases import seamount_geometry  # noqa: E402
+from mgroms_amd.testcases import resting_column_state, seamount_geometry  # noqa: E402
 
 
 def timed_solve(tol, maxit):
@@ -51,7 +51,7 @@ def main():
     try:
         for case in a.cases:
             nz, hold = (int(v) for v in case.split(":"))
-            u = np.zeros((nz, ny + 2, nx + 1)); v = np.zeros((nz, ny + 1, nx + 2)); w = -np.ones((nz + 1, ny + 2, nx + 2)); w[0] = 0
+            u, v, w = resting_column_state(nx, ny, nz)
             for method in a.methods:
                 mg.nhydro_clean()
                 nhydro.set_option("hold_odd_nz", hold)

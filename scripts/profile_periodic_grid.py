@@ -32,7 +32,7 @@ def rank_main(a):
     import mgroms_amd as mg
     from mgroms_amd import nhydro
     from mgroms_amd.parallel import Comm
-    from mgroms_amd.testcases import seamount_geometry
+    from mgroms_amd.testcases import resting_column_state, seamount_geometry
     nx, ny, nz = a.dims
     nhydro.set_verbose(0)
     if a.periodic:
@@ -42,8 +42,7 @@ def rank_main(a):
     assert comm.p2p_active, comm.p2p_error
     dx, dy, zeta, h = seamount_geometry(nx, ny, 2, 1, a.rank)   # (the halo entries on a periodic side are ignored)
     mg.nhydro_matrices(dx, dy, zeta, h, None, 4e3, 0.0, 0.0)
-    u = np.zeros((nz, ny + 2, nx + 1)); v = np.zeros((nz, ny + 1, nx + 2)); w = -np.ones((nz + 1, ny + 2, nx + 2)); w[0] = 0
-    nhydro.compute_rhs(u, v, w)
+    nhydro.compute_rhs(*resting_column_state(nx, ny, nz))
     out = {"transport": comm.transport()}
     for name, on in (("pushes", True), ("hooks", False)):
         comm.set_p2p(on)

@@ -4,14 +4,12 @@ mask: bmask = .true. with the island mask of mgroms_amd.testcases -- the colour 
 import os
 import sys
 
-import numpy as np
-
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 import mgroms_amd as mg  # noqa: E402
 from mgroms_amd import nhydro  # noqa: E402
-from mgroms_amd.testcases import island_mask, seamount_geometry  # noqa: E402
+from mgroms_amd.testcases import island_mask, resting_column_state, seamount_geometry  # noqa: E402
 
 nx, ny, nz = (int(a) for a in sys.argv[1:4]) if len(sys.argv) > 3 else (512, 512, 64)
 method = sys.argv[4] if len(sys.argv) > 4 else "FC"
@@ -21,8 +19,7 @@ torch.cuda.set_device(0)
 nhydro.set_verbose(0)
 mg.nhydro_init(nx, ny, nz, 1, 1, 0, nhydro.default_params(relax_method=method, bmask=1) if mask else nhydro.default_params(relax_method=method))
 mg.nhydro_matrices(*seamount_geometry(nx, ny, 1, 1, 0), island_mask(nx, ny) if mask else None, 4e3, 0.0, 0.0)
-u = np.zeros((nz, ny + 2, nx + 1)); v = np.zeros((nz, ny + 1, nx + 2)); w = -np.ones((nz + 1, ny + 2, nx + 2)); w[0] = 0
-nhydro.compute_rhs(u, v, w)
+nhydro.compute_rhs(*resting_column_state(nx, ny, nz))
 mg.Vcycle(1)
 nhydro.time_relax(1, 5)
 s = [nhydro.time_relax(1, reps) for _ in range(3)]

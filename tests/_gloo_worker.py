@@ -9,13 +9,17 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from _ranks import gloo_rank   # (tests/ is the script's directory: already on sys.path)
 
 
 def main():
     rank, world, npx, npy, port = (int(a) for a in sys.argv[1:6])
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    import torch.distributed as dist
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    with gloo_rank(rank, world, port, cuda=False):
+        rank_main(rank, world, npx, npy)
+    print(f"rank {rank} ok")
+
+
+def rank_main(rank, world, npx, npy):
     from mgroms_amd import nhydro
     from mgroms_amd.parallel import Comm
     from oracle.mgoracle import Oracle
@@ -79,9 +83,6 @@ def main():
         for q, r in enumerate(members):
             k = tabs[r][glev]["key"]
             assert (q % mine["ngx"], q // mine["ngx"]) == (k % 2, k // 2)
-    dist.barrier()
-    dist.destroy_process_group()
-    print(f"rank {rank} ok")
 
 
 if __name__ == "__main__":

@@ -10,13 +10,12 @@ watchdog ends the process if a collective is stuck.  The test runs this file und
 usage: _gpu_device_timestep_ranks.py npx npy nx ny nz nsmall"""
 import os
 import sys
-import threading
-import traceback
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from _ranks import prepare_thread_rank_process, run_threads, thread_rank   # (tests/ is the script's directory: already on sys.path)
 
 
 def rank_zeta(nx, ny, npx, npy, rank, ph, seed):
@@ -28,22 +27,13 @@ def rank_zeta(nx, ny, npx, npy, rank, ph, seed):
     return 0.8 * np.sin(2 * np.pi * i / (npx * nx) + ph) * np.cos(2 * np.pi * j / (npy * ny) - ph) + 0.05 * rng.standard_normal((nx + 2, ny + 2))
 
 
-def rank_main(rank, tw, cfg, o, results):
+def rank_main(rank, tw, cfg, o):
     import torch
     import mgroms_amd as mg
     from mgroms_amd import nhydro
-    from mgroms_amd._lib import check, lib
-    from mgroms_amd.parallel import ThreadComm
     from oracle.mgoracle import seamount_geometry
     npx, npy, nx, ny, nz, nsmall = cfg
-    try:
-        torch.cuda.set_device(0)
-        torch.cuda.set_stream(torch.cuda.Stream())
-        L = lib()
-        inst = L.mgx_instance_create()
-        check(L.mgx_instance_select(inst))
-        nhydro.set_verbose(0)
-        comm = ThreadComm(tw, rank, p2p=False)
+    with thread_rank(tw, rank, p2p=False) as comm:
         mg.nhydro_init(nx, ny, nz, npx, npy, rank, nhydro.default_params(relax_method="FC", nsmall=nsmall), comm=comm)
         dx, dy, _, h = seamount_geometry(nx, ny, npx, npy, rank)
         dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
@@ -58,30 +48,13 @@ def rank_main(rank, tw, cfg, o, results):
             for name in ("zeta", "zw", "cA"):
                 a, b = g.get(name), o.field(name, lev, rank)
                 assert np.array_equal(a, b), (rank, lev, name, np.argwhere(a != b)[:4].tolist())
-        tw.barrier.wait(60)
-        mg.nhydro_clean()
-        check(L.mgx_instance_select(0))
-        check(L.mgx_instance_destroy(inst))
-        results[rank] = f"rank {rank} ok gathered_levels={gathered}"
-    except BaseException:
-        results[rank] = "rank %d FAILED:\n%s" % (rank, traceback.format_exc())
-        try:
-            tw.barrier.abort()
-        except Exception:
-            pass
+    return f"gathered_levels={gathered}"
 
 
 def main():
     npx, npy, nx, ny, nz, nsmall = (int(a) for a in sys.argv[1:7])
     world = npx * npy
-    os.environ["OMP_NUM_THREADS"] = "8"
-    # one hardware queue per rank at least, set before HIP initialises (tests/_gpu_thread_ranks.py says why)
-    os.environ["GPU_MAX_HW_QUEUES"] = str(min(32, max(8, 3 * world)))
-    import faulthandler
-    faulthandler.dump_traceback_later(int(os.environ.get("MGX_TEST_WATCHDOG", "100")), exit=True)
-    import torch
-    torch.cuda.set_device(0)
-    from mgroms_amd.parallel import ThreadWorld
+    prepare_thread_rank_process(world)
     from oracle.mgoracle import Oracle, seamount_geometry
     o = Oracle(nx, ny, nz, npx, npy, relax_method="FC", nsmall=nsmall)
     for r in range(world):
@@ -89,18 +62,7 @@ def main():
         for name, a in (("dx", dx), ("dy", dy), ("zeta", rank_zeta(nx, ny, npx, npy, r, 1.3, 200)), ("h", h)):
             o.field(name, 1, r)[...] = a
     o.matrices(4e3, 0.0, 0.0)
-    tw = ThreadWorld(world)
-    results = [None] * world
-    th = [threading.Thread(target=rank_main, args=(r, tw, (npx, npy, nx, ny, nz, nsmall), o, results), daemon=True) for r in range(world)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(90)
-    bad = [r for r in range(world) if results[r] is None or "ok" not in results[r].split("\n")[0]]
-    for r in range(world):
-        print(results[r] if results[r] is not None else f"rank {r} did not finish")
-    sys.stdout.flush()
-    os._exit(1 if bad else 0)  # daemon threads may still sit in a collective after a failure
+    run_threads(world, lambda rank, tw: rank_main(rank, tw, (npx, npy, nx, ny, nz, nsmall), o))
 
 
 if __name__ == "__main__":

@@ -16,22 +16,23 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
+from _ranks import gloo_rank
 
 TOL_HIST = 1e-12   # p is bit-identical: only the order of the norm's reduction differs (the bound of tests/_gpu_rank_worker.py)
 
 
 def main():
     rank, world, npx, npy, port, nx, ny, nz, nsmall = (int(a) for a in sys.argv[1:10])
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    os.environ["OMP_NUM_THREADS"] = "1"
-    import torch
-    import torch.distributed as dist
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    with gloo_rank(rank, world, port):
+        rank_main(rank, npx, npy, nx, ny, nz, nsmall)
+    print(f"rank {rank} ok")
+
+
+def rank_main(rank, npx, npy, nx, ny, nz, nsmall):
     import mgroms_amd as mg
     from mgroms_amd import nhydro
     from mgroms_amd.parallel import Comm
-    from mgroms_amd.testcases import seamount_geometry
+    from mgroms_amd.testcases import resting_column_state, seamount_geometry
 
     nhydro.set_verbose(0)
     NX, NY = npx * nx, npy * ny
@@ -39,8 +40,7 @@ def main():
     par = dict(relax_method="FC", solver_prec=1e-30, nsmall=nsmall)
 
     def rhs(lx, ly):
-        u = np.zeros((nz, ly + 2, lx + 1)); v = np.zeros((nz, ly + 1, lx + 2)); w = -np.ones((nz + 1, ly + 2, lx + 2)); w[0] = 0
-        nhydro.compute_rhs(u, v, w)
+        nhydro.compute_rhs(*resting_column_state(lx, ly, nz))
 
     # ---- the yardstick: the global problem on one rank ------------------------------------------------------------------------------
     mg.nhydro_clean()
@@ -108,9 +108,6 @@ def main():
 
     mg.nhydro_clean()
     nhydro.set_option("hold_odd_nz", 0)
-    dist.barrier()
-    dist.destroy_process_group()
-    print(f"rank {rank} ok")
 
 
 if __name__ == "__main__":

@@ -29,6 +29,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
+from _ranks import gloo_rank
 
 TOL_HIST = 1e-12   # p is bit-identical: only the order of the norm's reduction differs (the bound of tests/_gpu_rank_worker.py)
 
@@ -62,13 +63,15 @@ def main():
     rank, world, npx, npy, port, nx, ny, nz, nsmall, per = (int(a) for a in sys.argv[1:11])
     method = sys.argv[11]
     opts = set(sys.argv[12].split("+")) if len(sys.argv) > 12 and sys.argv[12] else set()
+    with gloo_rank(rank, world, port):
+        rank_main(rank, world, npx, npy, nx, ny, nz, nsmall, per, method, opts)
+    print(f"rank {rank} ok")
+
+
+def rank_main(rank, world, npx, npy, nx, ny, nz, nsmall, per, method, opts):
     bmask = "bmask" in opts
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    os.environ["OMP_NUM_THREADS"] = "1"
     import torch
     import torch.distributed as dist
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     import mgroms_amd as mg
     from mgroms_amd import nhydro
     from mgroms_amd._lib import MgxError
@@ -383,9 +386,6 @@ def main():
 
     mg.nhydro_clean()
     nhydro.set_option("periodic", 0)
-    dist.barrier()
-    dist.destroy_process_group()
-    print(f"rank {rank} ok")
 
 
 if __name__ == "__main__":

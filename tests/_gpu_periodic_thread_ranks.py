@@ -6,8 +6,6 @@ every rank's level-1 p, halos included, is its block of that p indexed with wrap
 usage: _gpu_periodic_thread_ranks.py npx npy nx ny nz nsmall periodic"""
 import os
 import sys
-import threading
-import traceback
 
 import numpy as np
 
@@ -15,24 +13,15 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
+from _ranks import prepare_thread_rank_process, run_threads, thread_rank
 
 
-def rank_main(rank, tw, cfg, f, geo, uvw, ref, results):
-    import torch
+def rank_main(rank, tw, cfg, f, geo, uvw, ref):
     import mgroms_amd as mg
     from mgroms_amd import nhydro
-    from mgroms_amd._lib import check, lib
-    from mgroms_amd.parallel import ThreadComm
     npx, npy, nx, ny, nz, nsmall, per = cfg
-    try:
-        torch.cuda.set_device(0)
-        torch.cuda.set_stream(torch.cuda.Stream())
-        L = lib()
-        inst = L.mgx_instance_create()
-        check(L.mgx_instance_select(inst))
-        nhydro.set_verbose(0)
+    with thread_rank(tw, rank, p2p=True) as comm:
         nhydro.set_option("periodic", per)   # per instance
-        comm = ThreadComm(tw, rank, p2p=True)
         par = nhydro.default_params(relax_method="FC", solver_prec=1e-30, nsmall=nsmall, ns_coarsest=6)
         mg.nhydro_init(nx, ny, nz, npx, npy, rank, par, comm=comm)
         assert comm.p2p_active, comm.p2p_error
@@ -56,32 +45,14 @@ def rank_main(rank, tw, cfg, f, geo, uvw, ref, results):
         want = ref["p"][np.ix_(ii + 1, jj + 1)]
         assert n == ref["n"] and np.array_equal(mg.grid(1).p, want), rank
         assert np.all(np.abs(hist - ref["hist"]) <= 1e-12 * np.abs(ref["hist"])), (hist, ref["hist"])
-        tw.barrier.wait(120)
-        mg.nhydro_clean()
-        check(L.mgx_instance_select(0))
-        check(L.mgx_instance_destroy(inst))
-        results[rank] = f"rank {rank} ok p2p_exchanges={c['p2p_exchanges']}"
-    except BaseException:
-        results[rank] = "rank %d FAILED:\n%s" % (rank, traceback.format_exc())
-        try:
-            tw.barrier.abort()
-        except Exception:
-            pass
+    return f"p2p_exchanges={c['p2p_exchanges']}"
 
 
 def main():
     npx, npy, nx, ny, nz, nsmall, per = (int(a) for a in sys.argv[1:8])
-    world = npx * npy
-    os.environ["OMP_NUM_THREADS"] = "8"
-    # one hardware queue per rank and stream, set before HIP initialises (tests/_gpu_thread_ranks.py has the reason)
-    os.environ["GPU_MAX_HW_QUEUES"] = str(min(32, max(8, 3 * world)))
-    import faulthandler
-    faulthandler.dump_traceback_later(int(os.environ.get("MGX_TEST_WATCHDOG", "100")), exit=True)  # a stuck collective: all stacks, then exit
-    import torch
-    torch.cuda.set_device(0)
+    prepare_thread_rank_process(npx * npy)
     import mgroms_amd as mg
     from mgroms_amd import nhydro
-    from mgroms_amd.parallel import ThreadWorld
     from test_gpu_periodic import full2d, geometry, velocities_from, velocity_bases
     NX, NY = npx * nx, npy * ny
     geo = geometry(NX, NY, per)
@@ -97,19 +68,8 @@ def main():
     ref["p"] = mg.grid(1).p
     mg.nhydro_clean()
     nhydro.set_option("periodic", 0)
-    tw = ThreadWorld(world)
-    results = [None] * world
     cfg = (npx, npy, nx, ny, nz, nsmall, per)
-    th = [threading.Thread(target=rank_main, args=(r, tw, cfg, f, geo, uvw, ref, results), daemon=True) for r in range(world)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(90)
-    bad = [r for r in range(world) if results[r] is None or "ok" not in results[r].split("\n")[0]]
-    for r in range(world):
-        print(results[r] if results[r] is not None else f"rank {r} did not finish")
-    sys.stdout.flush()
-    os._exit(1 if bad else 0)  # daemon threads may still sit in a collective after a failure
+    run_threads(npx * npy, lambda rank, tw: rank_main(rank, tw, cfg, f, geo, uvw, ref))
 
 
 if __name__ == "__main__":

@@ -8,12 +8,27 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from _ranks import gloo_rank   # (tests/ is the script's directory: already on sys.path)
 
 
 def main():
     rank, world, npx, npy, port, nx, ny, nz, nsmall = (int(a) for a in sys.argv[1:10])
     method = sys.argv[10]
     opts = set(sys.argv[11].split("+")) if len(sys.argv) > 11 and sys.argv[11] else set()
+    import time
+    T0 = time.time()
+    stamps = []
+
+    def stamp(what):
+        stamps.append(f"{what}={time.time() - T0:.1f}s")
+    with gloo_rank(rank, world, port):
+        stamp("rendezvous")
+        line = rank_main(rank, npx, npy, nx, ny, nz, nsmall, method, opts, stamp)
+    stamp("teardown")
+    print(f"rank {rank} ok {line} " + " ".join(stamps))
+
+
+def rank_main(rank, npx, npy, nx, ny, nz, nsmall, method, opts, stamp):
     bmask = "bmask" in opts
     p2p = "nop2p" not in opts
     exact = "exact" in opts        # relax_method='RB' in the reference's sequential order, one launch per plane (mgx_set_option("rb_exact")): bitwise
@@ -29,20 +44,7 @@ def main():
     assert not model or method == "FC" or exact
     if connectfail:
         os.environ["MGX_P2P_TEST_FAIL_CONNECT"] = "1"
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    os.environ["OMP_NUM_THREADS"] = "1"  # every worker runs the whole emulated-MPI oracle: no OpenMP teams fighting for the cores
     import time
-    T0 = time.time()
-    stamps = []
-
-    def stamp(what):
-        stamps.append(f"{what}={time.time() - T0:.1f}s")
-    import torch
-    import torch.distributed as dist
-    torch.cuda.set_device(0)
-    stamp("import_torch")
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    stamp("rendezvous")
     import mgroms_amd as mg
     from mgroms_amd import nhydro
     from mgroms_amd.parallel import Comm
@@ -63,7 +65,7 @@ def main():
     stamp("init")
     geometry = rndtopo_geometry if rndtopo else seamount_geometry
     dx, dy, zeta, h = geometry(nx, ny, npx, npy, rank)
-    from mgroms_amd.testcases import island_mask
+    from mgroms_amd.testcases import island_mask, resting_column_state
     rmask = island_mask(nx, ny, npx, npy, rank) if bmask else None
     mg.nhydro_matrices(dx, dy, zeta, h, rmask, 4e3, 0.0, 0.0)
     def rank_uvw(r):
@@ -81,7 +83,7 @@ def main():
     if model:
         u, v, w = rank_uvw(rank)
     else:
-        u = np.zeros((nz, ny + 2, nx + 1)); v = np.zeros((nz, ny + 1, nx + 2)); w = -np.ones((nz + 1, ny + 2, nx + 2)); w[0] = 0
+        u, v, w = resting_column_state(nx, ny, nz)
     nhydro.compute_rhs(u, v, w)
     stamp("matrices_rhs")
     t0 = time.time()
@@ -200,10 +202,7 @@ def main():
             assert np.array_equal(g1.get(name), o.field(name, 1, rank)), (rank, name)
     stamp("checks")
     mg.nhydro_clean()
-    dist.barrier()
-    dist.destroy_process_group()
-    stamp("teardown")
-    print(f"rank {rank} ok nite={n} gathered_levels={gathered} exchanges={c['exchanges']} solve_s={t_solve:.1f} " + " ".join(stamps))
+    return f"nite={n} gathered_levels={gathered} exchanges={c['exchanges']} solve_s={t_solve:.1f}"
 
 
 if __name__ == "__main__":

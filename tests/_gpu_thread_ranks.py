@@ -7,43 +7,31 @@ oracle's emulated MPI ranks, through the peer-to-peer pushes and again through t
 usage: _gpu_thread_ranks.py npx npy nx ny nz nsmall [drop]     (drop: one rank goes silent for one exchange first, see rank_main)"""
 import os
 import sys
-import threading
-import traceback
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from _ranks import prepare_thread_rank_process, run_threads, thread_rank   # (tests/ is the script's directory: already on sys.path)
 
 
-def rank_main(rank, tw, cfg, o, ho, no, results):
-    import torch
+def rank_main(rank, tw, cfg, o, ho, no):
     import mgroms_amd as mg
     from mgroms_amd import nhydro
-    from mgroms_amd._lib import check, lib
-    from mgroms_amd.parallel import ThreadComm
+    from mgroms_amd.testcases import resting_column_state
     from oracle.mgoracle import seamount_geometry
     npx, npy, nx, ny, nz, nsmall, tol, maxit, nsc, drop = cfg
 
     def stage(what):
         print(f"[rank {rank}] {what}", file=sys.stderr, flush=True)
-    try:
-        torch.cuda.set_device(0)
-        torch.cuda.set_stream(torch.cuda.Stream())
-        L = lib()
-        inst = L.mgx_instance_create()
-        check(L.mgx_instance_select(inst))
-        assert L.mgx_instance_current() == inst
-        nhydro.set_verbose(0)
-        comm = ThreadComm(tw, rank, p2p=True)
+    with thread_rank(tw, rank, p2p=True) as comm:
         par = nhydro.default_params(relax_method="FC", solver_prec=tol, nsmall=nsmall, ns_coarsest=nsc)
         mg.nhydro_init(nx, ny, nz, npx, npy, rank, par, comm=comm)
         stage("init done, p2p_active=%s" % comm.p2p_active)
         assert comm.p2p_active, comm.p2p_error
         dx, dy, zeta, h = seamount_geometry(nx, ny, npx, npy, rank)
         mg.nhydro_matrices(dx, dy, zeta, h, None, 4e3, 0.0, 0.0)
-        u = np.zeros((nz, ny + 2, nx + 1)); v = np.zeros((nz, ny + 1, nx + 2)); w = -np.ones((nz + 1, ny + 2, nx + 2)); w[0] = 0
-        nhydro.compute_rhs(u, v, w)
+        nhydro.compute_rhs(*resting_column_state(nx, ny, nz))
         stage("matrices + rhs done")
         if drop:
             # A rank goes silent for one exchange (test hook: its flags stay down): its neighbours' waits time out (200 ms here).  Nobody
@@ -112,51 +100,19 @@ def rank_main(rank, tw, cfg, o, ho, no, results):
         for c4, d in (((0, 0), 4), ((-1, 0), 5), ((-1, -1), 6), ((0, -1), 7)):
             if nbr[d] >= 0:
                 assert np.all(ph[c4[0], c4[1], :] == float(nbr[d])), (rank, d)
-        tw.barrier.wait(120)
-        mg.nhydro_clean()
-        check(L.mgx_instance_select(0))
-        check(L.mgx_instance_destroy(inst))
-        results[rank] = f"rank {rank} ok nite={n} gathered_levels={gathered} p2p_exchanges={c['p2p_exchanges']}"
-    except BaseException:
-        results[rank] = "rank %d FAILED:\n%s" % (rank, traceback.format_exc())
-        try:
-            tw.barrier.abort()
-        except Exception:
-            pass
+    return f"nite={n} gathered_levels={gathered} p2p_exchanges={c['p2p_exchanges']}"
 
 
 def main():
     npx, npy, nx, ny, nz, nsmall = (int(a) for a in sys.argv[1:7])
-    world = npx * npy
-    os.environ["OMP_NUM_THREADS"] = "8"
-    # One hardware queue per rank.  The HIP runtime multiplexes the streams of a process onto GPU_MAX_HW_QUEUES hardware queues
-    # (default 4): two ranks whose streams share a queue are serialised, and a halo kernel that waits for its neighbour's push would sit
-    # in front of the very kernel that pushes.  (Process-per-rank runs have a queue set each.)  Must be set before HIP initialises, and set
-    # outright: a smaller value inherited from the environment (HIP's default is 4) deadlocks the 4x2 and 2x2 grids.
-    os.environ["GPU_MAX_HW_QUEUES"] = str(min(32, max(8, 3 * world)))  # each rank drives two streams (the exchange runs beside the interior sweep)
-    import faulthandler
-    faulthandler.dump_traceback_later(int(os.environ.get("MGX_TEST_WATCHDOG", "100")), exit=True)  # a stuck collective: all stacks, then exit
-    import torch
-    torch.cuda.set_device(0)
-    from mgroms_amd.parallel import ThreadWorld
+    prepare_thread_rank_process(npx * npy)
     from oracle.mgoracle import make_seamount
     tol, maxit, nsc = 1e-9, 3, 6
     o = make_seamount(nx, ny, nz, npx, npy, relax_method="FC", solver_prec=tol, nsmall=nsmall, ns_coarsest=nsc)
     o.compute_rhs()
     no, ho, _ = o.solve_p(tol, maxit)
-    tw = ThreadWorld(world)
-    results = [None] * world
     cfg = (npx, npy, nx, ny, nz, nsmall, tol, maxit, nsc, len(sys.argv) > 7 and sys.argv[7] == "drop")
-    th = [threading.Thread(target=rank_main, args=(r, tw, cfg, o, ho, no, results), daemon=True) for r in range(world)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(90)
-    bad = [r for r in range(world) if results[r] is None or "ok" not in results[r].split("\n")[0]]
-    for r in range(world):
-        print(results[r] if results[r] is not None else f"rank {r} did not finish")
-    sys.stdout.flush()
-    os._exit(1 if bad else 0)  # daemon threads may still sit in a collective after a failure
+    run_threads(npx * npy, lambda rank, tw: rank_main(rank, tw, cfg, o, ho, no))
 
 
 if __name__ == "__main__":

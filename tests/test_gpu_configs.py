@@ -13,19 +13,10 @@ import os
 import numpy as np
 import pytest
 
+from _gpu import gpu_module
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def mg():
-    import torch
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    import mgroms_amd as m
-    m.nhydro.set_verbose(0)
-    yield m
-    m.nhydro.set_option("rb_exact", 0)
-    m.nhydro_clean()
+mg = gpu_module(rb_exact=0)
 
 
 def _gpu(mg, nx, ny, nz, geom="seamount", **par):

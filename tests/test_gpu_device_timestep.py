@@ -14,6 +14,8 @@ import sys
 import numpy as np
 import pytest
 
+from _gpu import gpu_module
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -31,15 +33,7 @@ FIELDS = ("dx", "dy", "zeta", "h", "zr", "zw", "cw", "cA")
 HC = 4e3
 
 
-@pytest.fixture(scope="module")
-def mg():
-    import torch
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    import mgroms_amd as m
-    m.nhydro.set_verbose(0)
-    yield m
-    m.nhydro_clean()
+mg = gpu_module()
 
 
 def _zeta(nx, ny, which):
@@ -123,9 +117,8 @@ def _uvw(dims, seed=37):
 
 
 def _seamount_rhs(mg, dims):
-    nx, ny, nz = dims
-    u = np.zeros((nz, ny + 2, nx + 1)); v = np.zeros((nz, ny + 1, nx + 2)); w = -np.ones((nz + 1, ny + 2, nx + 2)); w[0] = 0
-    mg.nhydro.compute_rhs(u, v, w)
+    from mgroms_amd.testcases import resting_column_state
+    mg.nhydro.compute_rhs(*resting_column_state(*dims))
 
 
 # ---- 1 ----------------------------------------------------------------------------------------------------------------------------

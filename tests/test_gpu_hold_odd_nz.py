@@ -11,12 +11,13 @@ with "krylov" = 4 also 6 (bound: max(8, 6) + 2 = 10); 32 x 32 x 20 held: 6 with 
 with interp_type = 'nearest', 6 with "periodic" = 3; 64 x 64 x 28 held: 10.  The fp64 residuals the Oracle recomputes equal the last
 history entries to the printed digits (2.8e-11 .. 3.9e-11).  Red-black default on the held levels: <= 1.6e-16 of max|p| per relax call."""
 import os
-import socket
-import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+from _gpu import gpu_module
+from _ranks import free_port, run_process_ranks
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -24,19 +25,7 @@ sys.path.insert(0, HERE)
 HC = 4e3
 
 
-@pytest.fixture(scope="module")
-def mg():
-    import torch
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    import mgroms_amd as m
-    m.nhydro.set_verbose(0)
-    m.nhydro_clean()
-    yield m
-    m.nhydro_clean()
-    for name, value in (("hold_odd_nz", 0), ("periodic", 0), ("rb_seq", 1), ("rb_exact", 0), ("krylov", 0), ("krylov_precision", 64), ("cycle_precision", 64),
-                        ("mixed_tail", 0), ("exact_halos", 0), ("keep_r", 0)):
-        m.nhydro.set_option(name, value)
+mg = gpu_module(hold_odd_nz=0, periodic=0, rb_seq=1, rb_exact=0, krylov=0, krylov_precision=64, cycle_precision=64, mixed_tail=0, exact_halos=0, keep_r=0)
 
 
 def _init(mg, dims, hold=1, bmask=False, **par):
@@ -58,8 +47,8 @@ def _init(mg, dims, hold=1, bmask=False, **par):
 
 
 def _rhs(mg, dims):
-    nx, ny, nz = dims
-    u = np.zeros((nz, ny + 2, nx + 1)); v = np.zeros((nz, ny + 1, nx + 2)); w = -np.ones((nz + 1, ny + 2, nx + 2)); w[0] = 0
+    from mgroms_amd.testcases import resting_column_state
+    u, v, w = resting_column_state(*dims)
     mg.nhydro.compute_rhs(u, v, w)
     return u, v, w
 
@@ -234,34 +223,10 @@ def test_iterations_of_nz40_against_its_even_neighbours(mg):
 
 
 # ---- 6. process grid -------------------------------------------------------------------------------------------------------------------
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def test_process_grid_2x2_bitwise():
     """2 x 2 ranks of 16 x 16 x 20 (four processes, tests/_gpu_hold_grid_worker.py), four colours, three iterations: every rank's p on
     every level and b hold the block of the one-rank 32 x 32 x 20 run bit for bit, through the default transport and through the hooks"""
-    world, port = 4, _free_port()
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "_gpu_hold_grid_worker.py"), str(r), str(world), "2", "2", str(port), "16", "16", "20", "8"],
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(world)]
-    outs = []
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=150)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        outs.append(out)
-    for r, out in enumerate(outs):
-        print(f"---- rank {r} ----\n{out[-2500:]}")
-    for r, (p, out) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0, f"rank {r}:\n{out[-3000:]}"
-        assert f"rank {r} ok" in out
+    run_process_ranks(os.path.join(HERE, "_gpu_hold_grid_worker.py"), 4, (4, 2, 2, free_port(), 16, 16, 20, 8))
 
 
 # ---- 7. periodic -----------------------------------------------------------------------------------------------------------------------

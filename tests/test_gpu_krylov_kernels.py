@@ -12,6 +12,7 @@ import math
 import numpy as np
 import pytest
 
+from _gpu import gpu_module
 from tests import _krylov_kernel_ref as K
 
 pytestmark = pytest.mark.gpu
@@ -24,15 +25,7 @@ CASES = [pytest.param(sh, v, id=f"{sh[0]}x{sh[1]}x{sh[2]}-{v}") for v, shapes in
 SMALL = [pytest.param(sh, id=f"{sh[0]}x{sh[1]}x{sh[2]}") for sh in K.SMALL_SHAPES]
 
 
-@pytest.fixture(scope="module")
-def mg():
-    import torch
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    import mgroms_amd as m
-    m.nhydro.set_verbose(0)
-    yield m
-    m.nhydro_clean()
+mg = gpu_module()
 
 
 _now = {}

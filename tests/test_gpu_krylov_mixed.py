@@ -15,6 +15,7 @@ import sys
 import numpy as np
 import pytest
 
+from _gpu import gpu_module
 from tests import _krylov_kernel_ref as K
 
 pytestmark = pytest.mark.gpu
@@ -22,17 +23,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 OPTIONS = ("krylov", "krylov_precision", "cycle_precision", "warm_start", "rb_exact")
 
 
-@pytest.fixture(scope="module")
-def mg():
-    import torch
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    import mgroms_amd as m
-    m.nhydro.set_verbose(0)
-    yield m
-    m.nhydro.set_option("krylov", 0)
-    m.nhydro.set_option("krylov_precision", 64)
-    m.nhydro_clean()
+mg = gpu_module(krylov=0, krylov_precision=64)
 
 
 @pytest.fixture(autouse=True)
@@ -176,8 +167,8 @@ def test_update32_dense(mg):
 
 # ---- solves ------------------------------------------------------------------------------------------------------------------------
 def _uvw(nx, ny, nz):
-    u = np.zeros((nz, ny + 2, nx + 1)); v = np.zeros((nz, ny + 1, nx + 2)); w = -np.ones((nz + 1, ny + 2, nx + 2)); w[0] = 0
-    return u, v, w
+    from mgroms_amd.testcases import resting_column_state
+    return resting_column_state(nx, ny, nz)
 
 
 def _gpu(mg, nx, ny, nz, meth, bmask=False, **par):

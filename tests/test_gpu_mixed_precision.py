@@ -16,21 +16,18 @@ of 5000 for that amplification.
 import numpy as np
 import pytest
 
+from _gpu import gpu_module
+
 pytestmark = pytest.mark.gpu
+mg = gpu_module(cycle_precision=64)
 
 PREC = 1e-12
 
 
-@pytest.fixture(scope="module")
-def mg():
-    import torch
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    import mgroms_amd as m
-    m.nhydro.set_verbose(0)
-    yield m
-    m.nhydro.set_option("cycle_precision", 64)
-    m.nhydro_clean()
+@pytest.fixture(scope="module", autouse=True)
+def _worst_table(mg):
+    """what the operator tests measured, printed once at the end of the file"""
+    yield
     if _WORST:
         print("\nworst |fp32 - fp64| / max|fp64| (operators: per region):")
         for (op, region), v in sorted(_WORST.items()):
@@ -76,8 +73,8 @@ def _setup(mg, nx, ny, nz, bmask=False, zeta=None, sigma=None, oracle=True, **pa
 
 
 def _uvw(nx, ny, nz):
-    u = np.zeros((nz, ny + 2, nx + 1)); v = np.zeros((nz, ny + 1, nx + 2)); w = -np.ones((nz + 1, ny + 2, nx + 2)); w[0] = 0
-    return u, v, w
+    from mgroms_amd.testcases import resting_column_state
+    return resting_column_state(nx, ny, nz)
 
 
 def _rhs(mg, o, nx, ny, nz):

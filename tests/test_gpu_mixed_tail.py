@@ -12,6 +12,8 @@ Shapes: the smallest that take each path of the kernel (SHAPES below); at 512x51
 import numpy as np
 import pytest
 
+from _gpu import gpu_module
+
 pytestmark = pytest.mark.gpu
 
 OPTIONS = ("mixed_tail", "cycle_precision", "krylov", "krylov_precision", "rb_seq", "warm_start")
@@ -28,15 +30,7 @@ SHAPES = [((16, 16, 8), 1), ((32, 32, 24), 1), ((96, 48, 4), 1), ((64, 64, 16), 
 SHAPE_IDS = ["x".join(map(str, d)) for d, _ in SHAPES]
 
 
-@pytest.fixture(scope="module")
-def mg():
-    import torch
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    import mgroms_amd as m
-    m.nhydro.set_verbose(0)
-    yield m
-    m.nhydro_clean()
+mg = gpu_module()
 
 
 @pytest.fixture(autouse=True)
@@ -66,9 +60,8 @@ def _setup(mg, dims, method="FC", bmask=False, **par):
 
 
 def _rhs(mg, dims):
-    nx, ny, nz = dims
-    u = np.zeros((nz, ny + 2, nx + 1)); v = np.zeros((nz, ny + 1, nx + 2)); w = -np.ones((nz + 1, ny + 2, nx + 2)); w[0] = 0
-    mg.nhydro.compute_rhs(u, v, w)
+    from mgroms_amd.testcases import resting_column_state
+    mg.nhydro.compute_rhs(*resting_column_state(*dims))
 
 
 def _random_state(mg, rng):

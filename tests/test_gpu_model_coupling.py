@@ -17,19 +17,11 @@ import sys
 import numpy as np
 import pytest
 
+from _gpu import gpu_module
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-@pytest.fixture(scope="module")
-def mg():
-    import torch
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    import mgroms_amd as m
-    m.nhydro.set_verbose(0)
-    yield m
-    m.nhydro_clean()
+mg = gpu_module()
 
 
 # ---- run layouts (igrid_run / igrid_k of mgx_model.hip) -------------------------------------------------------------------------

@@ -4,22 +4,15 @@ all-reduce and coarse-level gather/split, each rank checked bit for bit against 
 (four-colour ordering).  Ranks share the one
 GPU of the test box (<= 4 ranks + this process)."""
 import os
-import socket
 import subprocess
 import sys
 
 import pytest
 
+from _ranks import free_port, run_process_ranks
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 @pytest.mark.parametrize("npx,npy,nx,ny,nz,nsmall,method", [
@@ -48,23 +41,10 @@ def _free_port():
     (1, 2, 16, 32, 8, 8, "FC+uvw+overlap0"),          # N/S only, ragged block
 ])
 def test_multirank_solve(npx, npy, nx, ny, nz, nsmall, method):
-    world, port = npx * npy, _free_port()
+    world = npx * npy
     method, _, opt = method.partition("+")  # opt: '+'-separated options of tests/_gpu_rank_worker.py
-    args = [str(a) for a in (world, npx, npy, port, nx, ny, nz, nsmall)] + [method] + ([opt] if opt else [])
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "_gpu_rank_worker.py"), str(r)] + args,
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(world)]
-    outs = []
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=150)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        outs.append(out)
-    for r, (p, out) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0, f"rank {r}:\n{out[-3000:]}"
-        assert f"rank {r} ok" in out
+    args = [world, npx, npy, free_port(), nx, ny, nz, nsmall, method] + ([opt] if opt else [])
+    run_process_ranks(os.path.join(HERE, "_gpu_rank_worker.py"), world, args)
 
 
 @pytest.mark.parametrize("npx,npy,nx,ny,nz,nsmall", [

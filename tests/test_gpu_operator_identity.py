@@ -27,6 +27,7 @@ stretched coordinate."""
 import numpy as np
 import pytest
 
+from _gpu import gpu_module
 from _operator_identity import CASES, COUPLING_TOL as TOL, MIN_FRACTION, case_inputs, coupling_defect, water_interior, assert_set_is_meaningful, inner
 
 pytestmark = pytest.mark.gpu
@@ -35,15 +36,7 @@ SYM_TOL = 1e-12      # <x, A y> = <A x, y>, relative, sums in longdouble
 HC = 4e3
 
 
-@pytest.fixture(scope="module")
-def mg():
-    import torch
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    import mgroms_amd as m
-    m.nhydro.set_verbose(0)
-    yield m
-    m.nhydro_clean()
+mg = gpu_module()
 
 
 class _Gpu:

@@ -13,18 +13,10 @@ checked at the tolerance at which the reference agrees with itself across decomp
 import numpy as np
 import pytest
 
+from _gpu import gpu_module
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def mg():
-    import torch
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    import mgroms_amd as m
-    m.nhydro.set_verbose(0)
-    yield m
-    m.nhydro_clean()
+mg = gpu_module()
 
 
 def _setup(mg, nx, ny, nz, geom="seamount", **par):
@@ -46,7 +38,8 @@ def _setup(mg, nx, ny, nz, geom="seamount", **par):
 
 def _uvw(nx, ny, nz, seed=None):
     if seed is None:
-        u = np.zeros((nz, ny + 2, nx + 1)); v = np.zeros((nz, ny + 1, nx + 2)); w = -np.ones((nz + 1, ny + 2, nx + 2)); w[0] = 0
+        from mgroms_amd.testcases import resting_column_state
+        u, v, w = resting_column_state(nx, ny, nz)
     else:
         r = np.random.default_rng(seed)
         u = r.uniform(-1, 1, (nz, ny + 2, nx + 1)); v = r.uniform(-1, 1, (nz, ny + 1, nx + 2)); w = r.uniform(-1, 1, (nz + 1, ny + 2, nx + 2))

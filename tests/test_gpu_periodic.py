@@ -18,6 +18,7 @@ distance, 2 % uniform roughness from a seeded generator on top, dx = dx0 (1 + 0.
 import numpy as np
 import pytest
 
+from _gpu import gpu_module
 from _operator_identity import COUPLING_TOL, MIN_FRACTION, MIN_LAND, scaled_defect, velocities, inner
 
 pytestmark = pytest.mark.gpu
@@ -27,19 +28,8 @@ SYM_TOL = 1e-12
 HIST_TOL = 1e-13   # residual histories of two runs whose norms are summed in another order
 
 
-@pytest.fixture(scope="module")
-def mg():
-    import torch
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    import mgroms_amd as m
-    m.nhydro.set_verbose(0)
-    m.nhydro_clean()
-    yield m
-    m.nhydro_clean()
-    for name, value in (("periodic", 0), ("rb_seq", 1), ("rb_exact", 0), ("krylov", 0), ("krylov_precision", 64), ("cycle_precision", 64),
-                        ("warm_start", 0), ("async", 0)):
-        m.nhydro.set_option(name, value)
+mg = gpu_module(periodic=0, rb_seq=1, rb_exact=0, krylov=0, krylov_precision=64, cycle_precision=64, warm_start=0,
+                **{"async": 0})   # (a Python keyword)
 
 
 def _init(mg, dims, per, monkeypatch=None, stored=False, **par):

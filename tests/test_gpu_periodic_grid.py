@@ -11,22 +11,15 @@ Measured on the MI355X: red-black in the sequential order against the plane loop
 the grid 16 iterations, 2.9e-11 and 5.7e-11 of max|p| from the one-rank four-colour solution per rank, d0 = 1.6e-10 (bound 16 d0); the
 operator identity through the model calls per rank <= 6.1e-16 (bound 3.5e-14)."""
 import os
-import socket
 import subprocess
 import sys
 
 import pytest
 
+from _ranks import free_port, run_process_ranks
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 CASES = [
@@ -51,24 +44,8 @@ def _id(c):
 @pytest.mark.parametrize("case", CASES, ids=[_id(c) for c in CASES])
 def test_periodic_grid(case):
     npx, npy, (nx, ny, nz), nsmall, per, method, opt = case
-    world, port = npx * npy, _free_port()
-    args = [str(a) for a in (world, npx, npy, port, nx, ny, nz, nsmall, per)] + [method, opt]
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "_gpu_periodic_grid_worker.py"), str(r)] + args,
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(world)]
-    outs = []
-    for p in procs:
-        try:
-            out, _ = p.communicate(timeout=150)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        outs.append(out)
-    for r, out in enumerate(outs):
-        print(f"---- rank {r} ----\n{out[-2500:]}")
-    for r, (p, out) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0, f"rank {r}:\n{out[-3000:]}"
-        assert f"rank {r} ok" in out
+    world = npx * npy
+    run_process_ranks(os.path.join(HERE, "_gpu_periodic_grid_worker.py"), world, (world, npx, npy, free_port(), nx, ny, nz, nsmall, per, method, opt))
 
 
 def test_periodic_4x2_ranks_in_one_process():

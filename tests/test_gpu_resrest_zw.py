@@ -18,11 +18,12 @@ Every case on a stretched sigma coordinate (theta_s = 6, theta_b = 0.4, hc = 250
 coordinate zw is linear in k, and a depth taken from the wrong row would leave the slots what they are.
 The switches are read once per process: each path is a child process (tests/_gpu_resrest_zw_worker.py), the three of a case side by side."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+from _ranks import run_commands
 
 pytestmark = pytest.mark.gpu
 
@@ -39,23 +40,16 @@ def _paths(case, tmp_path_factory):
     if case in _results:
         return _results[case]
     tmp = tmp_path_factory.mktemp(case)
-    procs = {}
+    cmds = []
     for name, var in PATHS.items():
         env = dict(os.environ, MGX_RESREST_FLAT_MAX="0")
         for k in ("MGX_RESREST_NO_ZW", "MGX_NO_RESREST", "MGX_NO_MF", "MGX_RESREST_AHEAD", "MGX_RESREST_MIN"):
             env.pop(k, None)
         env.update(var)
-        procs[name] = subprocess.Popen([sys.executable, os.path.join(HERE, "_gpu_resrest_zw_worker.py"), case, str(tmp / f"{name}.npz")],
-                                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+        cmds.append(([sys.executable, os.path.join(HERE, "_gpu_resrest_zw_worker.py"), case, str(tmp / f"{name}.npz")], env))
     res = {}
-    for name, pr in procs.items():
-        try:
-            so, se = pr.communicate(timeout=120)
-        except subprocess.TimeoutExpired:
-            for q in procs.values():
-                q.kill()
-            raise
-        assert pr.returncode == 0, (name, so[-2000:], se[-2000:])
+    for name, pr in zip(PATHS, run_commands(cmds, timeout=120)):
+        assert pr.returncode == 0, (name, pr.stdout[-2000:], pr.stderr[-2000:])
         res[name] = dict(np.load(tmp / f"{name}.npz"))
     _results[case] = res
     return res

@@ -24,6 +24,8 @@ import sys
 import numpy as np
 import pytest
 
+from _gpu import gpu_module
+
 gpu = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -127,16 +129,7 @@ def test_oracle_masked_tall_solve_contracts(dims):
 
 
 # ---- on the GPU --------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def mg():
-    import torch
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    import mgroms_amd as m
-    m.nhydro.set_verbose(0)
-    yield m
-    m.nhydro.set_option("rb_exact", 0)
-    m.nhydro_clean()
+mg = gpu_module(rb_exact=0)
 
 
 def _gpu_setup(mg, nx, ny, nz, method="FC", cmatrix="real", bmask=True):

@@ -13,20 +13,11 @@ import sys
 import numpy as np
 import pytest
 
+from _gpu import gpu_module
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-@pytest.fixture(scope="module")
-def mg():
-    import torch
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    import mgroms_amd as m
-    m.nhydro.set_verbose(0)
-    yield m
-    m.nhydro.set_option("rb_exact", 0)
-    m.nhydro_clean()
+mg = gpu_module(rb_exact=0)
 
 
 def _setup(mg, nx, ny, nz, bmask=False, **par):
@@ -55,7 +46,8 @@ def _setup(mg, nx, ny, nz, bmask=False, **par):
 
 def _uvw(nx, ny, nz, seed=None):
     if seed is None:
-        u = np.zeros((nz, ny + 2, nx + 1)); v = np.zeros((nz, ny + 1, nx + 2)); w = -np.ones((nz + 1, ny + 2, nx + 2)); w[0] = 0
+        from mgroms_amd.testcases import resting_column_state
+        u, v, w = resting_column_state(nx, ny, nz)
     else:
         r = np.random.default_rng(seed)
         u = r.uniform(-1, 1, (nz, ny + 2, nx + 1)); v = r.uniform(-1, 1, (nz, ny + 1, nx + 2)); w = r.uniform(-1, 1, (nz + 1, ny + 2, nx + 2))
