@@ -305,6 +305,23 @@ int mgx_set_verbose(int level);
  *   pass and transfer on every level.  The levels above the tail keep their launches.  What changes is the launch count of mgx_counters: a
  *   tail launch counts as one, which is why the option is off until asked for.
  *   Read-only: "mixed_tail_launches" (launches of the tail kernel since mgx_init).
+ * "small_any_nz" (default 0, or 1; any other value is refused; survives mgx_clean / mgx_init; no environment variable; may be set at any time:
+ *   it steers the dispatch of later relax calls only): 1 = a relax call on a small level with nz = 3, 5, 6 or 7 -- the coarse ends of the
+ *   nz = 24, 48, 96 hierarchies, and of nz = 20, 28, 40, 80 under "hold_odd_nz" -- runs in one workgroup and one launch, as the nz = 2 and 4
+ *   levels do, instead of one launch per colour pass plus one per halo fill.  Served: a level whose four sides are physical (a fully gathered
+ *   level included; not a level with neighbours or a periodic side) with even nx and ny and at most 1024 columns, relax_method 'FC' or 'RB'
+ *   (cmatrix 'simple', the parallel pass of "rb_seq" = 0, the plane loop of "rb_exact", the sequential order by default: the walk at nz = 3,
+ *   the plane loop at nz = 5).  nz = 3: four columns per lane (k_relax_wave, mgx_relax_coarse.hip); nz = 5, 6, 7: one thread per column with
+ *   the coefficients in registers up to 256 columns (k_relax_reg), the colour loop inside one workgroup above (k_relax_small,
+ *   mgx_relax.hip).  The same rows as the colour passes: four colours, 'simple', the parallel pass and "rb_exact" keep their bits; the
+ *   sequential order by default stays within its 1e-12 of max|p| per call.  A closed, un-gathered coarsest level of nz = 3 and at most 2048
+ *   cells (16 x 16 x 3) also takes the direct solve of "coarsest_direct", whose operator is rebuilt when this option changes.  Declined by
+ *   measurement, i.e. the launches of 0: the sequential order by default at nz = 6, 7, at nz = 5 above 64 columns and
+ *   at nz = 3 with ny > 128 (only the in-kernel plane loop could serve them, and it does not beat the colour passes with their walk);
+ *   'simple' red-black at nz = 6, 7 above 256 columns.  Not served either: relax_method 'GS', a timed call ("tictoc"), the folded transfers of
+ *   "fuse_tail", levels above 1024 columns, nz >= 9, the fp32 cycles.  0 = the dispatch without these instances, launch for launch; what changes with 1 is the
+ *   launch count of mgx_counters, which is why it is off until asked for.
+ *   Read-only: "small_any_nz_calls" (relax calls and direct coarsest solves served by these instances since mgx_init).
  * "periodic" (default 0; a bit mask, any value outside 0..3 is refused; survives mgx_clean): 1 = the domain wraps in the i direction (east-west,
  *   the plane index of the solver's layout), 2 = in the j direction (north-south), 3 = both.  Read by mgx_init: set it BEFORE mgx_init; while a
  *   solver is initialised a different value is refused (mgx_clean, set, mgx_init).  Served on one rank and on every process grid mgx_init

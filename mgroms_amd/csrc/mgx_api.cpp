@@ -74,6 +74,7 @@ const Opt OPTIONS[] = {
   {"krylov",              &State::krylov,           nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0..8 only
   {"krylov_precision",    &State::krylov_precision, nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 32 / 64 only (no preset: the table's would pass any number by)
   {"mixed_tail",          &State::mixed_tail,       nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0 / 1 only
+  {"small_any_nz",        &State::small_any_nz,     nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0 / 1 only
   {"periodic",            &State::periodic,         nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0..3 only, and not while initialised (read by mgx_init)
   {"hold_odd_nz",         &State::hold_odd_nz,      nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0 / 1 only, and not while initialised (read by mgx_init)
   // reads as off while a time-out of this solver holds (ksp_down, which mgx_clean does not carry); set: see mgx_set_option
@@ -89,6 +90,7 @@ const Opt OPTIONS[] = {
   {"tall_stored_passes", nullptr, CNT(n_tall_stored), nullptr, ENV_NONE, RO, false},
   {"mixed_iterations", nullptr, CNT(n_mixed), nullptr, ENV_NONE, RO, false},
   {"mixed_tail_launches", nullptr, CNT(n_mixed_tail), nullptr, ENV_NONE, RO, false},
+  {"small_any_nz_calls", nullptr, CNT(n_small_any), nullptr, ENV_NONE, RO, false},
   {"krylov_restarts", nullptr, CNT(kr_restarts), nullptr, ENV_NONE, RO, false},
   {"krylov_mixed_iterations", nullptr, CNT(n_kr_mixed), nullptr, ENV_NONE, RO, false},
   {"p2p_failed", nullptr, CNT(p2p_failed), nullptr, ENV_NONE, RO, false},
@@ -454,6 +456,7 @@ int mgx_set_option(const char *name, int value) {
   if (streq(name, "krylov_precision") && value != 32 && value != 64) return fail("krylov_precision must be 64 (fp64 cycles under the Krylov loop) or 32 (fp32 cycles under it), got %d", value);
   if (streq(name, "krylov") && (value < 0 || value > 8)) return fail("krylov must be 0 (off) or 1..8 (retained direction pairs of the truncated GCR), got %d", value);
   if (streq(name, "mixed_tail") && value != 0 && value != 1) return fail("mixed_tail must be 1 (the small levels of an fp32 cycle in one launch) or 0 (one launch per colour pass and transfer), got %d", value);
+  if (streq(name, "small_any_nz") && value != 0 && value != 1) return fail("small_any_nz must be 1 (closed levels of at most 1024 columns with nz = 3, 5, 6, 7 relax in one launch) or 0 (one launch per colour pass), got %d", value);
   if (streq(name, "periodic")) {
     if (value < 0 || value > 3) return fail("periodic must be 0 (closed), 1 (the i direction, east-west), 2 (the j direction, north-south) or 3 (both), got %d", value);
     if (S.inited && value != S.periodic)

@@ -192,7 +192,11 @@ int relax(int lev, int nsweeps) {
   const int rbm = rb_mode(L), exact = rbm == RB_EXACT;
   // sequential-order red-black (mgx_rbseq.hip); the one-workgroup kernels of the small levels run the reference's plane loop itself
   const int seq = rbm == RB_SEQ;
-  if (S.use_small && nsweeps > 0 && mgxk_relax_small(S.stream, &L.v, nsweeps, S.method, S.real, ph, exact ? 1 : (seq ? 2 : 0))) { S.n_launch++; return 0; }
+  // (option "small_any_nz": the instances for nz = 3, 5, 6, 7 report 2; a timed call keeps its launch per colour pass)
+  if (S.use_small && nsweeps > 0) {
+    const int served = mgxk_relax_small(S.stream, &L.v, nsweeps, S.method, S.real, ph, exact ? 1 : (seq ? 2 : 0), S.small_any_nz && !S.tictoc);
+    if (served) { S.n_launch++; if (served == 2) S.n_small_any++; return 0; }
+  }
   // closed mid levels, four colours: the whole call in one persistent launch, one workgroup per plane (mgx_relax_ks.hip: k_relax_ksp)
   if (S.method == M_FC && all_physical(ph) && S.use_ksp && !S.ksp_down && live_instances() == 1 && mgxk_relax_ks_persist(S.stream, &L.v, nsweeps, S.real, ph, L.ksp_done, L.ksp_seq, S.kerr, S.ksp_test_stall)) {
     S.ksp_test_stall = 0;
@@ -333,8 +337,12 @@ int coarsest_solve(bool p_zero) {
   const Sides ph = sides_of(L);
   const int rbm = rb_mode(L), exact = rbm == RB_EXACT, seq = rbm == RB_SEQ;
   const bool want = S.coarsest_direct == 2 || (S.coarsest_direct == 1 && seq);
+  // option "small_any_nz" decides whether a coarsest level of nz = 3 has an instance (k_relax_wave<3>): part of the operator's key, and a
+  // level found without an instance under the other value is asked again
+  const int any = S.small_any_nz ? 1 : 0;
+  if (S.cd_any != any) { S.cd_any = any; S.cd_valid = 0; if (S.cd_n < 0) S.cd_n = 0; }
   if (want && p_zero && S.nlevs >= 2 && S.use_small && !S.tictoc && S.method != M_GS && !exact && all_physical(ph) && !L.gather && S.par.ns_coarsest >= 1 && S.cd_n >= 0) {
-    const int n = mgxk_coarse_direct_cells(&L.v), mode = seq ? 2 : 0;
+    const int n = mgxk_coarse_direct_cells(&L.v, any), mode = seq ? 2 : 0;
     if (n > 0) {
       if (!S.cd_M) {
         CHK(dmalloc(&S.cd_pb, (size_t)2 * n * L.n3js)); CHK(dmalloc(&S.cd_M, (size_t)n * n));
@@ -343,11 +351,11 @@ int coarsest_solve(bool p_zero) {
         S.cd_n = n;
       }
       if (!S.cd_valid || S.cd_method != S.method || S.cd_mode != mode || S.cd_nsweeps != S.par.ns_coarsest) {
-        if (mgxk_coarse_direct_build(S.stream, &L.v, S.par.ns_coarsest, S.method, S.real, ph, mode, S.cd_pb, (long long)L.n3js, S.cd_M)) {
+        if (mgxk_coarse_direct_build(S.stream, &L.v, S.par.ns_coarsest, S.method, S.real, ph, mode, S.cd_pb, (long long)L.n3js, S.cd_M, any)) {
           S.cd_valid = 1; S.cd_method = S.method; S.cd_mode = mode; S.cd_nsweeps = S.par.ns_coarsest; S.n_launch += 3;
         } else { S.cd_valid = 0; S.cd_n = -1; }   // no one-workgroup kernel for this level: the sweeps
       }
-      if (S.cd_valid && mgxk_coarse_direct_apply(S.stream, &L.v, S.cd_M, S.cd_part, S.cd_cnt, ph)) { S.n_launch++; S.n_direct++; return 0; }
+      if (S.cd_valid && mgxk_coarse_direct_apply(S.stream, &L.v, S.cd_M, S.cd_part, S.cd_cnt, ph, any)) { S.n_launch++; S.n_direct++; if (L.nz == 3) S.n_small_any++; return 0; }
     } else S.cd_n = -1;
   }
   return relax(S.nlevs, S.par.ns_coarsest);

@@ -132,8 +132,14 @@ struct State {
   // 2 = every method (four colours then lose their bit parity with the reference's loop), 0 = never
   int coarsest_direct = 1;
   double *cd_pb = nullptr, *cd_M = nullptr, *cd_part = nullptr; unsigned int *cd_cnt = nullptr;
-  int cd_n = 0, cd_valid = 0, cd_method = -1, cd_mode = -1, cd_nsweeps = -1;   // cd_n: -1 = the level has no instance
+  int cd_n = 0, cd_valid = 0, cd_method = -1, cd_mode = -1, cd_nsweeps = -1, cd_any = -1;   // cd_n: -1 = the level has no instance
   long long n_direct = 0;   // coarsest solves done that way
+  // option "small_any_nz" (0 default, 1): relax calls on closed levels of at most 1024 columns with nz = 3, 5, 6, 7 (the coarse ends of the nz = 24,
+  // 48, 96 hierarchies, and of nz = 20, 28, 40, 80 under "hold_odd_nz") run in one workgroup and one launch like their nz = 2, 4 neighbours
+  // (mgxk_relax_small), and a coarsest level of nz = 3 takes the direct solve.  The same rows as the colour passes: the same bits for four colours,
+  // 'simple', the parallel pass and rb_exact.  Off by default because it changes the launch counts of those levels.  May be set at any time.
+  int small_any_nz = 0;
+  long long n_small_any = 0;   // read-only option "small_any_nz_calls": relax calls and direct coarsest solves served by those instances since mgx_init
   int rbseq_rowcut = 1;  // option "rbseq_rowcut" (A/B): the windowed walk's correction stops at the last row it reaches to 2^-64 (Level::rbs_rows); 0 = every row
   int rbseq_window = 1;  // option "rbseq_window" / MGX_NO_RBSEQ_WINDOW=1: walk and correction of a colour by the windowed walk (k_rbseq_window: no hand-off, no walk over the whole level) on the levels whose contraction bound allows it (Level::rbs_m)
   long long n_window = 0;  // colours done that way

@@ -481,10 +481,34 @@ int mgxk_relax_gs_sweep(hipStream_t st, const LevView *L, int real) {
 // one-launch relax of a small level; returns 0 if the level does not qualify
 // mode (red-black with cmatrix='real'): 0 = parallel colour passes (snapshot), 1 = the reference's plane loop bit for bit (rb_exact), 2 = the
 // same order by the walk of mgx_rbseq.hip where a kernel has it (k_relax_wave), else the plane loop
-int mgxk_relax_small(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode) {
+// any (option "small_any_nz"): a closed level of at most 1024 columns with nz = 3, 5, 6 or 7 and even nx, ny is served too, and the call then
+// returns 2 -- nz = 3 by k_relax_wave where it takes the mode, every other case by k_relax_reg up to 256 columns and by k_relax_small above
+// (a 512- or 1024-thread k_relax_reg would have 128 or 64 registers per thread for 16 nz coefficients: the operands are re-read through L2)
+int mgxk_relax_small(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode, int any) {
   mgx_before_launch();
-  if (mgxk_relax_wave(st, L, nsweeps, method, real, ph, mode)) return 1;  // <= 256 columns, nz = 2: the whole level in one wave
   const int exact = mode != 0;
+  if (any && (L->nz == 3 || (L->nz >= 5 && L->nz <= 7))) {
+    const int ncols = L->nx * L->ny;
+    if (!(ph.S && ph.E && ph.N && ph.W) || method == 0 || (L->nx & 1) || (L->ny & 1) || ncols > 1024) return 0;
+    if (L->nz == 3 && mgxk_relax_wave(st, L, nsweeps, method, real, ph, mode, 1)) return 2;  // not the plane loop of rb_exact, nor the walk of a half-row wider than a wave
+    // Declined by measurement (profiles/small_any_nz_time.json): the sequential order at speed where only the plane loop could
+    // serve it -- 2 nx barrier steps per sweep with one plane's columns at work lose against the colour pass and its walk, or only draw with
+    // them -- except nz = 5 in one wave (8 x 8 x 5: 57-63 us against 98-99 for 3 sweeps); and 'simple' red-black at nz = 6, 7 above 256
+    // columns (k_relax_small at 32 x 32 x 7: 961-977 us against 877-901 for 40 sweeps; at nz = 6 a draw)
+    if (method == 1 && real && mode == 2 && !(L->nz == 5 && ncols <= 64)) return 0;
+    if (method == 1 && !real && L->nz >= 6 && ncols > 256) return 0;
+    const size_t bytes = ((size_t)L->nz + 1) * (L->nx + 2) * (L->ny + 2) * sizeof(double);
+    const int nth = (ncols + 63) / 64 * 64;
+#define ANY_CASE(NZV) case NZV:                                                                                                                \
+      if (ncols <= 256) { if (real) hipLaunchKernelGGL((k_relax_reg<NZV, true, 256>), dim3(1), dim3(nth), bytes, st, *L, nsweeps, method, ph, exact);   \
+                          else hipLaunchKernelGGL((k_relax_reg<NZV, false, 256>), dim3(1), dim3(nth), bytes, st, *L, nsweeps, method, ph, exact); }     \
+      else { if (real) hipLaunchKernelGGL((k_relax_small<NZV, true, 256>), dim3(1), dim3(256), 0, st, *L, nsweeps, method, ph, exact);                  \
+             else hipLaunchKernelGGL((k_relax_small<NZV, false, 256>), dim3(1), dim3(256), 0, st, *L, nsweeps, method, ph, exact); }                    \
+      return mgx_launched() ? 2 : 0;
+    switch (L->nz) { ANY_CASE(3) ANY_CASE(5) ANY_CASE(6) ANY_CASE(7) default: return 0; }
+#undef ANY_CASE
+  }
+  if (mgxk_relax_wave(st, L, nsweeps, method, real, ph, mode, 0)) return 1;  // <= 256 columns, nz = 2: the whole level in one wave
   {  // one thread per column, coefficients in registers, p in LDS
     const int ncols = L->nx * L->ny;
     const bool closed = ph.S && ph.E && ph.N && ph.W;

@@ -364,9 +364,11 @@ extern "C" {
 // Cv, flags: see k_relax_wave (0 / nullptr = the plain relax call); mgxk_relax_wave_fused is the entry the cycles use
 // mode (red-black with cmatrix='real' only): 0 = parallel colour passes, 1 = the bit-exact plane loop (not here: k_relax_reg), 2 = the
 // reference's sequential order by the walk (k_relax_wave's seq)
-static int relax_wave_launch(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode, const LevView *Cv, int flags, int nbatch = 1, long long bstride = 0) {
+// any (option "small_any_nz"): nz = 3 is served too -- four columns of three rows per lane, up to 256 blocks of 2x2 columns; never with folded transfers
+static int relax_wave_launch(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode, const LevView *Cv, int flags, int nbatch = 1, long long bstride = 0, int any = 0) {
   mgx_before_launch();
-  if (mgx_switches().no_wave || (L->nz != 2 && L->nz != 4) || method == 0 || (mode == 1 && method == 1 && real)) return 0;
+  const bool nz3 = any && L->nz == 3 && !(flags & 3);
+  if (mgx_switches().no_wave || (L->nz != 2 && L->nz != 4 && !nz3) || method == 0 || (mode == 1 && method == 1 && real)) return 0;
   const int seq = (mode == 2 && method == 1 && real) ? 1 : 0;
   if (seq && L->ny / 2 > WAVE) return 0;  // the walk keeps a half-row on the lanes of one wave; wider levels: k_relax_reg's plane loop
   const int nblk = (L->nx / 2) * (L->ny / 2);
@@ -397,14 +399,15 @@ static int relax_wave_launch(hipStream_t st, const LevView *L, int nsweeps, int 
     if (nblk <= WAVE) WAVE_CASE_FZ(64) else WAVE_CASE_FZ(256)
   }
   if (L->nz == 2) { if (nblk <= WAVE) WAVE_CASE(2, 64) else if (nblk <= 4 * WAVE) WAVE_CASE(2, 256) else WAVE_CASE(2, 512) }
+  if (L->nz == 3) { if (nblk <= WAVE) WAVE_CASE(3, 64) else WAVE_CASE(3, 256) }
   if (nblk <= WAVE) WAVE_CASE(4, 64) else WAVE_CASE(4, 256)
 #undef WAVE_CASE_FZ
 #undef WAVE_LDS
 #undef WAVE_CASE
 }
 
-int mgxk_relax_wave(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode) {
-  return relax_wave_launch(st, L, nsweeps, method, real, ph, mode, nullptr, 0);
+int mgxk_relax_wave(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode, int any) {
+  return relax_wave_launch(st, L, nsweeps, method, real, ph, mode, nullptr, 0, 1, 0, any);
 }
 // ---- the coarsest-level solve of a cycle as ONE matrix-vector product (option "coarsest_direct") -----------------------------------
 // Inside a cycle the coarsest level is entered with p = 0 (fine2coarse, mg_intergrids.f90:70) and left after relax(nlevs, ns_coarsest)
@@ -466,26 +469,26 @@ __global__ __launch_bounds__(CDT) void k_coarse_direct(LevView L, const double *
   mirror_store(L, L.p, ro, j, i, c, v, ph);
 }
 
-// cells of a level the direct solve serves (a closed level of the one-workgroup kernel, at most 2048 cells), 0 = none
-int mgxk_coarse_direct_cells(const LevView *L) {
+// cells of a level the direct solve serves (a closed level of the one-workgroup kernel, at most 2048 cells), 0 = none; any: nz = 3 too
+int mgxk_coarse_direct_cells(const LevView *L, int any) {
   const long long n = (long long)L->nx * L->ny * L->nz;
-  return ((L->nz == 2 || L->nz == 4) && n <= 2048 && !(L->nx & 1) && !(L->ny & 1)) ? (int)n : 0;
+  return ((L->nz == 2 || L->nz == 4 || (any && L->nz == 3)) && n <= 2048 && !(L->nx & 1) && !(L->ny & 1)) ? (int)n : 0;
 }
 // build B (M: n * n doubles) with the level's own relax kernel; pb: scratch of 2 * n * stride doubles (stride = the level's array size).
 // Returns 1 when built (all of it enqueued on st), 0 = the level has no one-workgroup kernel for this method / mode.
-int mgxk_coarse_direct_build(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode, double *pb, long long stride, double *M) {
-  const int n = mgxk_coarse_direct_cells(L);
+int mgxk_coarse_direct_build(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode, double *pb, long long stride, double *M, int any) {
+  const int n = mgxk_coarse_direct_cells(L, any);
   if (!n || nsweeps < 1) return 0;
   hipLaunchKernelGGL(k_cd_init, dim3(n), dim3(256), 0, st, *L, pb, stride, n);
   LevView B = *L;
   B.p = pb; B.b = pb + (long long)n * stride;
-  if (!relax_wave_launch(st, &B, nsweeps, method, real, ph, mode, nullptr, 0, n, stride)) return 0;
+  if (!relax_wave_launch(st, &B, nsweeps, method, real, ph, mode, nullptr, 0, n, stride, any)) return 0;
   hipLaunchKernelGGL(k_cd_compact, dim3((n + 255) / 256, n), dim3(256), 0, st, *L, pb, stride, M, n);
   return mgx_launched();
 }
 // p = B b with the mirrors; part: (n / CDB rounded up) * n doubles, cnt: one word per 64 rows, 64 bytes apart, zero before the first call
-int mgxk_coarse_direct_apply(hipStream_t st, const LevView *L, const double *M, double *part, unsigned int *cnt, Sides ph) {
-  const int n = mgxk_coarse_direct_cells(L);
+int mgxk_coarse_direct_apply(hipStream_t st, const LevView *L, const double *M, double *part, unsigned int *cnt, Sides ph, int any) {
+  const int n = mgxk_coarse_direct_cells(L, any);
   if (!n) return 0;
   mgx_before_launch();
   hipLaunchKernelGGL(k_coarse_direct, dim3((n + CDT - 1) / CDT, (n + CDB - 1) / CDB), dim3(CDT), 0, st, *L, M, part, cnt, ph, n);

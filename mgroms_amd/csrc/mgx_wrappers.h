@@ -28,7 +28,7 @@ enum {
 
 // ---- mgx_relax.hip ----
 int mgxk_relax_gs_sweep(hipStream_t st, const LevView *L, int real);
-int mgxk_relax_small(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode);
+int mgxk_relax_small(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode, int any);
 int mgxk_relax_colour(hipStream_t st, const LevView *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, Sides ph);
 int mgxk_has_reg_kernel(const LevView *L);
 void mgxk_snapshot_k1(hipStream_t st, const LevView *L);
@@ -63,11 +63,11 @@ int mgxk_relax_ks_persist(hipStream_t st, const LevView *L, int nsweeps, int rea
                           int stall);
 
 // ---- mgx_relax_coarse.hip ----
-int mgxk_relax_wave(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode);
-int mgxk_coarse_direct_cells(const LevView *L);
+int mgxk_relax_wave(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode, int any);
+int mgxk_coarse_direct_cells(const LevView *L, int any);
 int mgxk_coarse_direct_build(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode, double *pb, long long stride,
-                             double *M);
-int mgxk_coarse_direct_apply(hipStream_t st, const LevView *L, const double *M, double *part, unsigned int *cnt, Sides ph);
+                             double *M, int any);
+int mgxk_coarse_direct_apply(hipStream_t st, const LevView *L, const double *M, double *part, unsigned int *cnt, Sides ph, int any);
 int mgxk_coarse_direct_slabs(int n);
 int mgxk_relax_wave_fused(hipStream_t st, const LevView *L, const LevView *C, int nsweeps, int method, int real, Sides ph, int flags, int mode);
 
