@@ -24,7 +24,7 @@ const Row TABLE[] = {
   {"MGX_NO_XCD",                 &Switches::no_xcd,                SET_TRUE,  0,                "plain block order instead of the per-XCD block map of the colour passes (relax, tall, k-split); same bits"},
   {"MGX_NO_REG",                 &Switches::no_reg,                SET_TRUE,  0,                "small closed levels without the one-thread-per-column kernel (k_relax_reg): the LDS-resident or the generic one; same bits"},
   {"MGX_NO_TINY",                &Switches::no_tiny,               SET_TRUE,  0,                "small closed levels without the all-in-LDS kernel (k_relax_tiny); same bits"},
-  {"MGX_NO_WAVE",                &Switches::no_wave,               SET_TRUE,  0,                "the two coarsest levels without the wave kernels (k_relax_wave, four and eight waves included): the older one-workgroup kernels; same bits"},
+  {"MGX_NO_WAVE",                &Switches::no_wave,               SET_TRUE,  0,                "the two coarsest levels without the wave kernels (k_relax_wave, four and eight waves included): the older one-workgroup kernels; same bits, except red-black with cmatrix = 'real' in the sequential order at speed: the plane loop's bits instead of the walk's, both within 1e-12 of the reference's loop"},
   {"MGX_NO_WAVE_FUSE",           &Switches::no_wave_fuse,          SET_TRUE,  0,                "coarse2fine / residual + fine2coarse as launches of their own around the coarse relax instead of folded into it; same bits"},
   {"MGX_NO_TALL",                &Switches::no_tall,               SET_TRUE,  0,                "generic colour pass at nz = 80, 96, 128 instead of the tall-column pass (and no chained snapshots there); same bits"},
   {"MGX_NO_KS",                  &Switches::no_ks,                 SET_TRUE,  0,                "row-by-row colour passes on the mid levels instead of every k-split kernel (pass, colour pair, persistent relax); same bits"},
@@ -35,7 +35,7 @@ const Row TABLE[] = {
   {"MGX_KSP_SC1",                &Switches::ksp_fence,             SET_FALSE, 1,                "the persistent relax hands planes over with sc1 accesses instead of release / acquire fences (measured on gfx950 only); same bits"},
   {"MGX_KS_NW",                  &Switches::ks_nw,                 ATOI,      0,                "= 4: four waves per workgroup instead of eight in the k-split colour pass; same bits"},
   {"MGX_RBSEQ_D0_KERNEL",        &Switches::rbseq_d0_kernel,       SET_TRUE,  0,                "sequential-order red-black: the walk reads d0 on every level, written by the colour pass or by k_rbseq_d0, instead of forming it on narrow half-rows; same bits"},
-  {"MGX_RBSEQ_NO_D0_MID",        &Switches::rbseq_d0_mid,          SET_FALSE, 1,                "half-rows of 65..128 columns: the walk forms d0 itself instead of reading what the colour pass left (same expression; no test pins the bits)"},
+  {"MGX_RBSEQ_NO_D0_MID",        &Switches::rbseq_d0_mid,          SET_FALSE, 1,                "half-rows of 65..128 columns: the walk forms d0 itself instead of reading what the colour pass left; same bits"},
   {"MGX_NO_RBSEQ_WALK_APPLY",    &Switches::no_rbseq_walk_apply,   SET_TRUE,  0,                "small levels: walk and correction by the scan kernels instead of k_rbseq_walk_apply; same bits"},
   {"MGX_RBSEQ_WINDOW_NO_XMAP",   &Switches::rbseq_window_no_xmap,  SET_TRUE,  0,                "plain block order instead of the per-XCD block map of the windowed walk; same bits"},
   {"MGX_RBW_PRIO",               &Switches::rbw_prio,              ATOI,      1,                "= 0: the walking wave of the windowed walk at normal priority instead of s_setprio 3; same bits"},

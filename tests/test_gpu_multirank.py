@@ -104,6 +104,31 @@ def test_multirank_long_edge_path(monkeypatch):
     test_multirank_solve(2, 2, 32, 32, 16, 8, "FC")
 
 
+def _push_grid(nx, ny, nz, maxblk):
+    """(items per thread, blocks per direction S, E, corner) of the halo push of a rank with one S/N, one E/W and one corner neighbour, as
+    mgxk_halo_p2p (mgx_kernels.hip) sizes it: "items" sums nz * nx, nz * ny and nz over the peer directions,
+    "pp.ipt = (items + 256 * maxblk - 1) / (256 * maxblk) + 1", "per = 256 * pp.ipt", "nd = (n + per - 1) / per" blocks for a direction of n items"""
+    n = (nz * nx, nz * ny, nz)
+    ipt = (sum(n) + 256 * maxblk - 1) // (256 * maxblk) + 1
+    return ipt, tuple((m + 256 * ipt - 1) // (256 * ipt) for m in n)
+
+
+def test_multirank_one_block_per_direction(monkeypatch):
+    """MGX_P2P_MAXBLK=1, the smallest block cap of the halo push kernel, on a 2x2 case with gathers whose long edge is more than one
+    block by default: ranks of 64x32x16, so that level 1 pushes 1024 + 512 + 16 = 1552 items.  The default cap of 128 gives two items
+    per thread and two blocks for the long edge (four blocks in all); the cap of 1 gives eight per thread and ONE block per direction
+    (three in all), four real items per thread on the long edge.  (At the 32x32x16 ranks of test_multirank_long_edge_path the cap does
+    not change the grid: 1040 items are one block per direction either way.)  Bit for bit against the oracle's emulated ranks, as
+    every four-colour case of test_multirank_solve.  MGX_P2P_TIMEOUT_MS rides along at the bound the library has without it (5 s): only
+    its read in mgx_init and the store of the device constant are exercised, no wait of a healthy run comes near it."""
+    nx, ny, nz = 64, 32, 16
+    assert _push_grid(nx, ny, nz, 128) == (2, (2, 1, 1)) and _push_grid(nx, ny, nz, 1) == (8, (1, 1, 1))   # the cap changes the grid
+    assert _push_grid(32, 32, 16, 128)[1] == _push_grid(32, 32, 16, 1)[1]                                   # ... and would not there
+    monkeypatch.setenv("MGX_P2P_MAXBLK", "1")
+    monkeypatch.setenv("MGX_P2P_TIMEOUT_MS", "5000")
+    test_multirank_solve(2, 2, nx, ny, nz, 8, "FC")
+
+
 @pytest.mark.parametrize("transport", ["mpi-hooks", "p2p"])
 def test_fortran_mpi_harness(tmp_path, transport):
     """The reference's parallel driver shape (Fortran + MPI, fortran/mg_testseamount_gpu_mpi.f90) on 2x2 ranks over
