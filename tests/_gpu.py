@@ -18,3 +18,15 @@ def gpu_module(**restore):
         for name, value in restore.items():
             m.nhydro.set_option(name, value)
     return mg
+
+
+def restore_options(*names):
+    """`_restore_options = restore_options("krylov", ...)`: an autouse fixture that puts the named options back after every test of the file
+    (the options a file touches survive nhydro_clean, and the tests that run after it read them)."""
+    @pytest.fixture(autouse=True)
+    def _restore_options(mg):
+        keep = {k: mg.nhydro.get_option(k) for k in names}
+        yield
+        for k, v in keep.items():
+            mg.nhydro.set_option(k, v)
+    return _restore_options

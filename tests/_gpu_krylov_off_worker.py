@@ -15,14 +15,13 @@ import torch  # noqa: E402
 torch.cuda.set_device(0)
 import mgroms_amd as mg  # noqa: E402
 from mgroms_amd import nhydro  # noqa: E402
-from mgroms_amd.testcases import resting_column_state, seamount_geometry  # noqa: E402
+from _problem import gpu_problem, rhs, uvw  # noqa: E402
 
 meth, touch = sys.argv[1], int(sys.argv[2])
 nx, ny, nz = 64, 64, 16
 nhydro.set_verbose(0)
-mg.nhydro_init(nx, ny, nz, 1, 1, 0, nhydro.default_params(relax_method=meth, solver_prec=1e-10))
-mg.nhydro_matrices(*seamount_geometry(nx, ny, 1, 1, 0), None, 4e3, 0.0, 0.0)
-nhydro.compute_rhs(*resting_column_state(nx, ny, nz))
+gpu_problem(mg, (nx, ny, nz), relax_method=meth, solver_prec=1e-10)
+rhs(mg, None, uvw((nx, ny, nz)))
 if touch == 2:
     import tempfile
     nhydro.set_option("tictoc", 1)

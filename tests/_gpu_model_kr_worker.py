@@ -11,14 +11,13 @@ import torch  # noqa: E402
 
 import mgroms_amd as mg  # noqa: E402
 from mgroms_amd import nhydro  # noqa: E402
-from mgroms_amd.testcases import rndtopo_geometry  # noqa: E402
+from _problem import gpu_problem  # noqa: E402
 
 nx, ny, nz = (int(a) for a in sys.argv[1:4])
 out = sys.argv[4]
 torch.cuda.set_device(0)
 nhydro.set_verbose(0)
-mg.nhydro_init(nx, ny, nz, 1, 1, 0, nhydro.default_params(relax_method="FC", solver_prec=1e-10, solver_maxiter=0))
-mg.nhydro_matrices(*rndtopo_geometry(nx, ny, 1, 1, 0), None, 4e3, 0.0, 0.0)
+gpu_problem(mg, (nx, ny, nz), geom="rndtopo", relax_method="FC", solver_prec=1e-10, solver_maxiter=0)
 rng = np.random.default_rng(23)  # the draws of _velocities(..., seed=23) in the test
 u = rng.standard_normal((nz, ny + 2, nx + 1)); v = rng.standard_normal((nz, ny + 1, nx + 2)); w = rng.standard_normal((nz + 1, ny + 2, nx + 2))
 np.save(os.path.join(out, "u0.npy"), u)

@@ -14,7 +14,7 @@ import torch  # noqa: E402
 torch.cuda.set_device(0)
 import mgroms_amd as mg  # noqa: E402
 from mgroms_amd import nhydro  # noqa: E402
-from mgroms_amd.testcases import resting_column_state, seamount_geometry  # noqa: E402
+from _problem import gpu_problem, rhs, uvw  # noqa: E402
 
 libc = ctypes.CDLL(None)
 
@@ -26,9 +26,8 @@ def mark(text):
 
 nx, ny, nz = 16, 16, 8
 nhydro.set_verbose(1)
-mg.nhydro_init(nx, ny, nz, 1, 1, 0, nhydro.default_params(relax_method="FC", solver_prec=1e-10))
-mg.nhydro_matrices(*seamount_geometry(nx, ny, 1, 1, 0), None, 4e3, 0.0, 0.0)
-nhydro.compute_rhs(*resting_column_state(nx, ny, nz))
+gpu_problem(mg, (nx, ny, nz), relax_method="FC", solver_prec=1e-10)
+rhs(mg, None, uvw((nx, ny, nz)))
 for mode, opts in (("plain", {}), ("mixed", {"cycle_precision": 32}), ("krylov", {"krylov": 2})):
     for k, val in opts.items():
         nhydro.set_option(k, val)

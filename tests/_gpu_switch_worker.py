@@ -14,7 +14,7 @@ import torch  # noqa: E402
 
 import mgroms_amd as mg  # noqa: E402
 from mgroms_amd import nhydro  # noqa: E402
-from oracle.mgoracle import Oracle, seamount_geometry  # noqa: E402
+from _problem import gpu_problem, oracle_twin  # noqa: E402
 from _switch_cases import CASES, PROBE_SETS  # noqa: E402
 
 case, dest = sys.argv[1], sys.argv[2]
@@ -34,15 +34,7 @@ def launches():
 
 
 def setup(p):
-    nx, ny, nz = p["dims"]
-    kw = dict(relax_method=p["method"], cmatrix=p["cmatrix"])
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, nhydro.default_params(**kw))
-    dx, dy, zeta, h = seamount_geometry(nx, ny, 1, 1, 0)
-    mg.nhydro_matrices(dx, dy, zeta, h, None, 4e3, 0.0, 0.0)
-    o = Oracle(nx, ny, nz, 1, 1, **kw)
-    for name, a in (("dx", dx), ("dy", dy), ("zeta", zeta), ("h", h)):
-        o.field(name)[...] = a
-    o.matrices(4e3, 0.0, 0.0)
+    o = oracle_twin(gpu_problem(mg, p["dims"], relax_method=p["method"], cmatrix=p["cmatrix"]))
     assert mg.nlevs() == o.nlevs
     return o
 

@@ -20,11 +20,10 @@ def main(nx, ny, nz):
     import torch
     import mgroms_amd as mg
     from mgroms_amd import nhydro
-    from mgroms_amd.testcases import island_mask, seamount_geometry
+    from _problem import gpu_problem
     torch.cuda.set_device(0)
     nhydro.set_verbose(0)
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, nhydro.default_params(relax_method="FC", cmatrix="real", solver_prec=1e-10, bmask=1))
-    mg.nhydro_matrices(*seamount_geometry(nx, ny, 1, 1, 0), island_mask(nx, ny), 4e3, 0.0, 0.0)
+    gpu_problem(mg, (nx, ny, nz), bmask=True, relax_method="FC", cmatrix="real", solver_prec=1e-10)
     p, b = big_state(nx, ny, nz)
     g = mg.grid(1)
     g.set("p", p); g.set("b", b); mg.fill_halo(1, "p")

@@ -11,13 +11,12 @@ import torch  # noqa: E402
 
 import mgroms_amd as mg  # noqa: E402
 from mgroms_amd import nhydro  # noqa: E402
-from mgroms_amd.testcases import seamount_geometry  # noqa: E402
+from _problem import gpu_problem  # noqa: E402
 
 nx, ny, nz = (int(a) for a in sys.argv[1:4])
 torch.cuda.set_device(0)
 nhydro.set_verbose(0)
-mg.nhydro_init(nx, ny, nz, 1, 1, 0, nhydro.default_params(relax_method="FC"))
-mg.nhydro_matrices(*seamount_geometry(nx, ny, 1, 1, 0), None, 4e3, 0.0, 0.0)
+gpu_problem(mg, (nx, ny, nz), relax_method="FC")
 rng = np.random.default_rng(5)
 u = 1e-2 * rng.standard_normal((nz, ny + 2, nx + 1)); v = 1e-2 * rng.standard_normal((nz, ny + 1, nx + 2)); w = -np.ones((nz + 1, ny + 2, nx + 2)); w[0] = 0
 nhydro.compute_rhs(u, v, w)

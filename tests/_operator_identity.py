@@ -104,15 +104,12 @@ def coupling_defect(be, nx, ny, nz, rmask, seed):
 
 def make_oracle(nx, ny, nz, inp, bmask=None, **par):
     """a one-rank CPU oracle (four colours) on case_inputs(); bmask defaults to "the case has a mask" """
-    from oracle.mgoracle import Oracle
+    from _problem import oracle_twin, problem
     bmask = (inp["rmask"] is not None) if bmask is None else bmask
-    o = Oracle(nx, ny, nz, 1, 1, relax_method="FC", bmask=bmask, **par)
-    for name in ("dx", "dy", "zeta", "h"):
-        o.field(name)[...] = inp[name]
-    if bmask:
-        o.field("rmask")[...] = inp["rmask"]
-    o.matrices(inp["hc"], inp["theta_b"], inp["theta_s"])
-    return o
+    pr = problem((nx, ny, nz), bmask=bmask, rmask=inp["rmask"] if bmask else None, sigma=(inp["hc"], inp["theta_b"], inp["theta_s"]),
+                 relax_method="FC", **par)
+    pr.fields = tuple(inp[name] for name in ("dx", "dy", "zeta", "h"))
+    return oracle_twin(pr)
 
 
 class OracleBackend:

@@ -14,36 +14,23 @@ import numpy as np
 import pytest
 
 from _gpu import gpu_module
+from _problem import gpu_problem, hist_close, on_gpu, oracle_twin, problem, random_level, rhs, uvw
 
 pytestmark = pytest.mark.gpu
 mg = gpu_module(rb_exact=0)
 
 
 def _gpu(mg, nx, ny, nz, geom="seamount", **par):
-    from mgroms_amd.testcases import seamount_geometry, rndtopo_geometry, resting_column_state
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(**par))
-    dx, dy, zeta, h = (seamount_geometry if geom == "seamount" else rndtopo_geometry)(nx, ny)
-    mg.nhydro_matrices(dx, dy, zeta, h, None, 4e3, 0.0, 0.0)
-    u, v, w = resting_column_state(nx, ny, nz)
-    mg.nhydro.compute_rhs(u, v, w)
+    """the problem on the GPU with the resting column's right-hand side; returns the record of what the GPU was given"""
+    pr = gpu_problem(mg, (nx, ny, nz), geom=geom, **par)
+    rhs(mg, None, uvw(pr.dims))
+    return pr
 
 
-def _oracle(nx, ny, nz, npx=1, npy=1, geom="seamount", threads=None, **par):
+def _oracle(pr, npx=1, npy=1):
     """the same problem on npx x npy emulated ranks (one OpenMP thread each)"""
-    from oracle.mgoracle import Oracle, seamount_geometry, rndtopo_geometry
-    o = Oracle(nx // npx, ny // npy, nz, npx, npy, **par)
-    g = seamount_geometry if geom == "seamount" else rndtopo_geometry
-    for r in range(npx * npy):
-        for name, a in zip(("dx", "dy", "zeta", "h"), g(nx // npx, ny // npy, npx, npy, r)):
-            o.field(name, 1, r)[...] = a
-    o.matrices(4e3, 0.0, 0.0)
-    for r in range(npx * npy):
-        o.field("u", 1, r)[...] = 0.0
-        o.field("v", 1, r)[...] = 0.0
-        w = o.field("w", 1, r)
-        w[0] = 0.0
-        w[1:] = -1.0
-    o.compute_rhs()
+    o = oracle_twin(pr, npx, npy)
+    rhs(None, o, uvw(pr.dims))
     return o
 
 
@@ -60,12 +47,8 @@ def _blocks_equal(p, o, name, npx, npy):
     return bad
 
 
-def _hist_close(h, ho, rtol=1e-12):
-    """against the ORACLE: the fields are bit-identical, only the order of the norm's reduction differs -> 1e-12 relative.
-    Against the reference's recorded series (tests/golden, another build's libm and reduction order): rtol=1e-10 + 1e-13, north_star's bound."""
-    return np.all(np.abs(h - ho) <= (1e-13 if rtol > 1e-11 else 0.0) + rtol * np.abs(ho))
-
-
+# Histories against the ORACLE: the fields are bit-identical, only the order of the norm's reduction differs -> 1e-12 relative.  Against the
+# reference's recorded series (tests/golden, another build's libm and reduction order): 1e-13 + 1e-10 relative, north_star's bound.
 # ---- exact-order red-black -----------------------------------------------------------------------------------------
 def test_rb_exact_matches_reference_history_and_oracle(mg, golden):
     """relax_method='RB', cmatrix='real' (the reference default) in the reference's sequential order: the 15 residuals of
@@ -73,16 +56,16 @@ def test_rb_exact_matches_reference_history_and_oracle(mg, golden):
     g = golden["seamount_64x64x16_RB_1rank"]
     mg.nhydro.set_option("rb_exact", 1)
     try:
-        _gpu(mg, 64, 64, 16, relax_method="RB", solver_prec=1e-6)
+        pr = _gpu(mg, 64, 64, 16, relax_method="RB", solver_prec=1e-6)
         n, hist = mg.solve_p(1e-6, 50)
     finally:
         mg.nhydro.set_option("rb_exact", 0)
     ref = np.array(g["res"])
     assert n == g["nite"] == len(ref)
-    assert _hist_close(hist[1:], ref, rtol=1e-10), (hist[1:], ref)
-    o = _oracle(64, 64, 16, relax_method="RB", solver_prec=1e-6)
+    assert hist_close(hist[1:], ref, rtol=1e-10, atol=1e-13, same_length=False), (hist[1:], ref)
+    o = _oracle(pr)
     no, ho, _ = o.solve_p(1e-6, 50)
-    assert no == n and _hist_close(hist, ho)
+    assert no == n and hist_close(hist, ho, rtol=1e-12, atol=0.0, same_length=False)
     p = mg.grid(1).p
     assert np.array_equal(p, o.field("p"))
     assert np.isclose((p[1:-1, 1:-1, :] ** 2).sum(), g["sum_p2"], rtol=1e-12)
@@ -97,7 +80,7 @@ def test_rb_exact_matches_reference_history_and_oracle(mg, golden):
     # and the default (sequential order at speed, mgx_rbseq.hip) is the exact one up to a few ulp
     _gpu(mg, 64, 64, 16, relax_method="RB", solver_prec=1e-6)
     n3, hist3 = mg.solve_p(1e-6, 50)
-    assert n3 == n and _hist_close(hist3, hist, rtol=1e-10)
+    assert n3 == n and hist_close(hist3, hist, rtol=1e-10, atol=1e-13, same_length=False)
     assert np.abs(mg.grid(1).p - p).max() <= 1e-10 * np.abs(p).max()
 
 
@@ -108,14 +91,10 @@ def test_rb_exact_relax_every_level(mg, dims):
     nx, ny, nz = dims
     mg.nhydro.set_option("rb_exact", 1)
     try:
-        _gpu(mg, nx, ny, nz, relax_method="RB")
-        o = _oracle(nx, ny, nz, relax_method="RB")
+        o = _oracle(_gpu(mg, nx, ny, nz, relax_method="RB"))
         rng = np.random.default_rng(5)
         for lev in range(1, o.nlevs + 1):
-            g = mg.grid(lev)
-            p = rng.standard_normal(g._shape("p")); b = rng.standard_normal(g._shape("b"))
-            g.set("p", p); g.set("b", b); mg.fill_halo(lev, "p")
-            o.field("p", lev)[...] = p; o.field("b", lev)[...] = b; o.fill_halo(lev, "p")
+            g = random_level(mg, o, lev, rng)
             mg.relax(lev, 2); o.relax(lev, 2)
             assert np.array_equal(g.get("p"), o.field("p", lev)), lev
     finally:
@@ -125,10 +104,10 @@ def test_rb_exact_relax_every_level(mg, dims):
 def test_relax_rb_parallel_deviation_is_small(mg):
     """What the parallel red-black sweep (default) actually differs by from the sequential one after ONE sweep on a smooth
     field (the solve's own iterate): the k=1 diagonal coupling times the change of one sweep."""
-    _gpu(mg, 64, 64, 16, relax_method="RB")
+    pr = _gpu(mg, 64, 64, 16, relax_method="RB")
     mg.Vcycle(1)
     p0, b0 = mg.grid(1).p, mg.grid(1).b
-    o = _oracle(64, 64, 16, relax_method="RB")
+    o = _oracle(pr)
     o.field("p")[...] = p0
     o.field("b")[...] = b0
     mg.nhydro.set_option("rb_seq", 0)
@@ -165,15 +144,15 @@ def test_config2_rb_256x256x32(mg, golden):
     assert n == 50 and abs(hist[50] - ref["res50"]) <= 0.0006e-5 + 5e-5 * ref["res50"], hist[50]
     hist_par = hist.copy()
     # (b) exact order: first 3 iterations bit for bit against the oracle on one rank; the parallel sweep within 5e-5 of it
-    o = _oracle(256, 256, 32, relax_method="RB")
-    no, ho, _ = o.solve_p(1e-12, 3)
     mg.nhydro.set_option("rb_exact", 1)
     try:
-        _gpu(mg, 256, 256, 32, relax_method="RB")
+        pr = _gpu(mg, 256, 256, 32, relax_method="RB")
         n, hist = mg.solve_p(1e-12, 3)
     finally:
         mg.nhydro.set_option("rb_exact", 0)
-    assert n == no == 3 and _hist_close(hist, ho)
+    o = _oracle(pr)
+    no, ho, _ = o.solve_p(1e-12, 3)
+    assert n == no == 3 and hist_close(hist, ho, rtol=1e-12, atol=0.0, same_length=False)
     assert np.array_equal(mg.grid(1).p, o.field("p"))
     assert np.all(np.abs(hist_par[1:4] - ho[1:]) <= 5e-5 * ho[1:])
     assert np.all(np.abs(hist_seq[1:4] - ho[1:]) <= 1e-13 + 1e-10 * ho[1:]), (hist_seq[1:4], ho[1:])
@@ -217,11 +196,11 @@ def test_rb_sequential_order_512x512x64_against_the_exact_order(mg):
 
 
 def test_config2_fc_256x256x32_bitwise(mg):
-    _gpu(mg, 256, 256, 32, relax_method="FC")
+    pr = _gpu(mg, 256, 256, 32, relax_method="FC")
     n, hist = mg.solve_p(1e-12, 3)
-    o = _oracle(256, 256, 32, 4, 2, relax_method="FC")
+    o = _oracle(pr, 4, 2)
     no, ho, _ = o.solve_p(1e-12, 3)
-    assert n == no == 3 and _hist_close(hist, ho)
+    assert n == no == 3 and hist_close(hist, ho, rtol=1e-12, atol=0.0, same_length=False)
     assert _blocks_equal(mg.grid(1).p, o, "p", 4, 2) == []
 
 
@@ -232,22 +211,21 @@ def test_fc_ragged_shapes_bitwise(mg, dims, geom):
     # colour for the colour-pair kernel, 72- and 18-block levels for the register-resident coarse kernels, runs of the prolongation
     # that end inside a wave): three F-cycle iterations, every level's p bit for bit
     nx, ny, nz = dims
-    _gpu(mg, nx, ny, nz, geom, relax_method="FC")
-    o = _oracle(nx, ny, nz, geom=geom, relax_method="FC")
+    o = _oracle(_gpu(mg, nx, ny, nz, geom, relax_method="FC"))
     assert mg.nlevs() == o.nlevs
     n, hist = mg.solve_p(1e-30, 3)
     no, ho, _ = o.solve_p(1e-30, 3)
-    assert n == no == 3 and _hist_close(hist, ho)
+    assert n == no == 3 and hist_close(hist, ho, rtol=1e-12, atol=0.0, same_length=False)
     for lev in range(1, o.nlevs + 1):
         assert np.array_equal(mg.grid(lev).p, o.field("p", lev)), lev
 
 
 def test_config3_vcycle_512x512x64_bitwise(mg, golden):
-    _gpu(mg, 512, 512, 64, relax_method="FC")
+    pr = _gpu(mg, 512, 512, 64, relax_method="FC")
     b_gpu = mg.grid(1).b
     mg.Vcycle(1)
     res = mg.compute_residual(1)
-    o = _oracle(512, 512, 64, 4, 4, relax_method="FC")
+    o = _oracle(pr, 4, 4)
     assert _blocks_equal(b_gpu, o, "b", 4, 4) == []
     o.vcycle(1)
     reso = o.residual(1)
@@ -263,14 +241,14 @@ def test_config5_vcycle_512x1024x128_bitwise(mg):
     width, the 7-level hierarchy 512x1024x128 -> 8x16x2 of SURVEY 8(a14)), one FC Vcycle(1) bit for bit (b, p, r) against the
     oracle on 4x4 emulated ranks, like config 3.  The 4x2 process grid itself, with the gather chain, is
     tests/test_gpu_multirank.py::test_config5_4x2_ranks_in_one_process."""
-    _gpu(mg, 512, 1024, 128, relax_method="FC")
+    pr = _gpu(mg, 512, 1024, 128, relax_method="FC")
     assert mg.nlevs() == 7
     b_gpu = mg.grid(1).b
     mg.Vcycle(1)
     res = mg.compute_residual(1)
     p, r = mg.grid(1).p, mg.grid(1).r
     mg.nhydro_clean()
-    o = _oracle(512, 1024, 128, 4, 4, relax_method="FC")
+    o = _oracle(pr, 4, 4)
     assert o.nlevs == 7
     assert _blocks_equal(b_gpu, o, "b", 4, 4) == []
     o.vcycle(1)
@@ -286,12 +264,11 @@ def test_coarse_levels_of_an_eight_gpu_run_bitwise(mg):
     128x64x4 and the 64x32x2 coarsest grid with its 40 sweeps.  As a one-rank problem (256x128x8 -> 3 levels) every kernel that serves them
     -- the colour-pair kernel (nx = 256 is beyond the persistent one), the persistent relax at nz = 4, the eight-wave one-workgroup
     coarsest solve -- bit for bit against the oracle over three F-cycle iterations, every level's p."""
-    _gpu(mg, 256, 128, 8, relax_method="FC")
-    o = _oracle(256, 128, 8, relax_method="FC")
+    o = _oracle(_gpu(mg, 256, 128, 8, relax_method="FC"))
     assert mg.nlevs() == o.nlevs == 3
     n, hist = mg.solve_p(1e-30, 3)
     no, ho, _ = o.solve_p(1e-30, 3)
-    assert n == no == 3 and _hist_close(hist, ho)
+    assert n == no == 3 and hist_close(hist, ho, rtol=1e-12, atol=0.0, same_length=False)
     for lev in range(1, 4):
         assert np.array_equal(mg.grid(lev).p, o.field("p", lev)), lev
     g = mg.grid(3)
@@ -303,11 +280,11 @@ def test_level1_red_black_two_waves_per_block(mg, nz):
     """The level-1 kernels with TWO waves per workgroup (512 planes x 4 j-chunks = 2048 waves: red-black at 512x512; the LDS slices of
     gam / of the lower rows are per wave): two sweeps from p = 0, bit for bit against the oracle on 4x4 emulated ranks.
     cmatrix='simple' makes red-black order independent, so the parallel sweep is exact."""
-    _gpu(mg, 512, 512, nz, relax_method="RB", cmatrix="simple")
+    pr = _gpu(mg, 512, 512, nz, relax_method="RB", cmatrix="simple")
     mg.relax(1, 2)
     p = mg.grid(1).p
     mg.nhydro_clean()
-    o = _oracle(512, 512, nz, 4, 4, relax_method="RB", cmatrix="simple")
+    o = _oracle(pr, 4, 4)
     o.relax(1, 2)
     assert np.abs(p).max() > 0
     assert _blocks_equal(p, o, "p", 4, 4) == []
@@ -320,22 +297,21 @@ def test_in_kernel_coefficients_match_stored_slots_on_stretched_grids(mg, dims, 
     (sigma-coordinate formula) in registers.  With a stretched coordinate (theta_s, theta_b > 0: cosh / exp tables), a moving free
     surface (zeta /= 0), non-uniform dx, dy and a non-zero hc, the result must equal, bit for bit, the same solve through the STORED
     coefficients (MGX_NO_MF=1: no in-kernel reconstruction) -- device against device, so libm differences do not enter."""
-    from mgroms_amd.testcases import seamount_geometry, resting_column_state
     nx, ny, nz = dims
-    dx, dy, zeta, h = seamount_geometry(nx, ny)
+    pr = problem(dims, sigma=(250.0, 0.4, 6.0), relax_method="FC")
+    dx, dy, zeta, h = pr.fields
     ii, jj = np.meshgrid(np.arange(nx + 2), np.arange(ny + 2), indexing="ij")
     dx = dx * (1.0 + 0.2 * np.sin(0.3 * ii)); dy = dy * (1.0 + 0.1 * np.cos(0.2 * jj))
     zeta = 0.4 * np.cos(0.25 * ii) * np.sin(0.15 * jj)
-    u, v, w = resting_column_state(nx, ny, nz)
+    pr.fields = (dx, dy, zeta, h)
     out = []
     for nomf in (False, True):
         if nomf:
             monkeypatch.setenv("MGX_NO_MF", "1")
         else:
             monkeypatch.delenv("MGX_NO_MF", raising=False)
-        mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(relax_method="FC"))
-        mg.nhydro_matrices(dx, dy, zeta, h, None, 250.0, 0.4, 6.0)
-        mg.nhydro.compute_rhs(u, v, w)
+        on_gpu(mg, pr)
+        rhs(mg, None, uvw(dims))
         n, hist = mg.solve_p(1e-12, 3)
         out.append((hist.copy(), mg.grid(1).p))
     monkeypatch.delenv("MGX_NO_MF", raising=False)
@@ -351,13 +327,13 @@ def test_config4_rndtopo_1024x1024x64_bitwise(mg):
     configuration's full size on one GPU against the oracle on 4x4 emulated ranks, two solve_p iterations.  The F-cycle
     DIVERGES on this input (10 m cells, depth jumps of hundreds of metres) in the oracle and on the GPU alike: a parity
     and throughput case, not a convergence case."""
-    _gpu(mg, 1024, 1024, 64, geom="rndtopo", relax_method="FC")
+    pr = _gpu(mg, 1024, 1024, 64, geom="rndtopo", relax_method="FC")
     n, hist = mg.solve_p(1e-12, 2)
     p = mg.grid(1).p
     mg.nhydro_clean()
-    o = _oracle(1024, 1024, 64, 4, 4, geom="rndtopo", relax_method="FC")
+    o = _oracle(pr, 4, 4)
     no, ho, _ = o.solve_p(1e-12, 2)
-    assert n == no == 2 and _hist_close(hist, ho), (hist, ho)
+    assert n == no == 2 and hist_close(hist, ho, rtol=1e-12, atol=0.0, same_length=False), (hist, ho)
     assert _blocks_equal(p, o, "p", 4, 4) == []
     o.close()
 
@@ -372,20 +348,10 @@ def test_call_mask_is_used(mg, bmask, dims):
     and fill (mg_testseamount.f90:97).  nhydro_solve itself declares the dummy (0:nx+1,0:ny+1) and then indexes rmask(j,i)
     (nhydro.f90:56,72; mg_compute_rhs.f90:61): on a non-square block with a non-trivial mask the reference reads element
     j+(nx+2)*i of an array filled at j+(ny+2)*i.  The library follows the drivers' layout, i.e. the intent."""
-    from oracle.mgoracle import Oracle, seamount_geometry
     from mgroms_amd.testcases import island_mask
     nx, ny, nz = dims
-    kw = dict(relax_method="FC", solver_prec=1e-9, solver_maxiter=4)
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(bmask=bmask, **kw))
-    dx, dy, zeta, h = seamount_geometry(nx, ny, 1, 1, 0)
+    o = oracle_twin(gpu_problem(mg, dims, bmask=bool(bmask), relax_method="FC", solver_prec=1e-9, solver_maxiter=4))
     m0 = island_mask(nx, ny)
-    mg.nhydro_matrices(dx, dy, zeta, h, m0 if bmask else None, 4e3, 0.0, 0.0)
-    o = Oracle(nx, ny, nz, 1, 1, bmask=bool(bmask), **kw)
-    for name, a in (("dx", dx), ("dy", dy), ("zeta", zeta), ("h", h)):
-        o.field(name)[...] = a
-    if bmask:
-        o.field("rmask")[...] = m0
-    o.matrices(4e3, 0.0, 0.0)
     rng = np.random.default_rng(3)
     mcall = m0.copy()
     mcall[5:9, ny - 12:ny - 6] = 0.0  # an extra piece of land the matrices have not seen (not symmetric under i <-> j)
@@ -443,7 +409,7 @@ def test_bench_plain_run_dumps_its_last_step(tmp_path):
     assert j["value"] > 0 and abs(j["ms_per_step"] * j["value"] - 1e3) <= 1e-9 * 1e3
     assert not {"roofline", "cpu_baseline", "also_rb", "value_sync_each_step"} & set(j)
     p = np.load(tmp_path / "p.npy")
-    o = _oracle(64, 64, 16, relax_method="FC")
+    o = _oracle(problem((64, 64, 16), relax_method="FC"))
     for _ in range(5):
         o.vcycle(1)
     assert p.dtype == np.float64 and np.array_equal(p, o.field("p")[1:-1, 1:-1, :])

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from _gpu import gpu_module
+from _problem import oracle_twin, problem, rhs, uvw
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -46,7 +47,7 @@ def _zeta(nx, ny, which):
 
 
 def _geometry(dims, bmask):
-    from oracle.mgoracle import seamount_geometry
+    from mgroms_amd.testcases import seamount_geometry
     nx, ny, _ = dims
     dx, dy, _, h = seamount_geometry(nx, ny, 1, 1, 0)
     rmask = None
@@ -116,28 +117,17 @@ def _uvw(dims, seed=37):
     return tuple(rng.standard_normal(s) for s in ((nz, ny + 2, nx + 1), (nz, ny + 1, nx + 2), (nz + 1, ny + 2, nx + 2)))
 
 
-def _seamount_rhs(mg, dims):
-    from mgroms_amd.testcases import resting_column_state
-    mg.nhydro.compute_rhs(*resting_column_state(*dims))
-
-
 # ---- 1 ----------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dims,bmask", SHAPES, ids=IDS)
 def test_matrices_device_equals_matrices(mg, dims, bmask):
     """nhydro_matrices from numpy, every field of every level read; nhydro_clean, init again, nhydro_matrices_device from tensors of the
     same data: equal.  zw, cw, cA of level 1 also equal the oracle's."""
-    from oracle.mgoracle import Oracle
     ref = _host_reference(mg, dims, bmask)
     _init(mg, dims, bmask)
     _matrices_device(mg, dims, bmask, "c")
     _assert_same(_read_all(mg, bmask), ref, "matrices_device")
-    o = Oracle(*dims, 1, 1, relax_method="FC", bmask=bool(bmask))
-    dx, dy, h, rmask = _geometry(dims, bmask)
-    for name, a in (("dx", dx), ("dy", dy), ("zeta", _zeta(dims[0], dims[1], "c")), ("h", h)):
-        o.field(name)[...] = a
-    if bmask:
-        o.field("rmask")[...] = rmask
-    o.matrices(HC, 0.0, 0.0)
+    o = oracle_twin(problem(dims, bmask=bool(bmask), rmask=_geometry(dims, bmask)[3], zeta=_zeta(dims[0], dims[1], "c"), sigma=(HC, 0.0, 0.0),
+                            relax_method="FC"))
     for name in ("zw", "cw", "cA"):
         assert np.array_equal(ref[(1, name)], o.field(name)), name
 
@@ -202,7 +192,7 @@ def test_two_resident_time_steps_against_the_oracle(mg):
 # ---- 4 ----------------------------------------------------------------------------------------------------------------------------
 def _rb_state(mg, dims):
     win = [(mg.nhydro.rbseq_window_info(lev), mg.nhydro.rbseq_window_rows(lev)) for lev in range(1, mg.nlevs() + 1)]
-    _seamount_rhs(mg, dims)
+    rhs(mg, None, uvw(dims))
     n, hist = mg.solve_p(1e-30, 3)
     return win, n, hist, mg.grid(1).p
 
@@ -235,7 +225,7 @@ def test_dependent_state_is_invalidated(mg, options):
     defaults = {"coarsest_direct": 1, "cycle_precision": 64, "krylov": 0, "krylov_precision": 64}
 
     def solve():
-        _seamount_rhs(mg, dims)
+        rhs(mg, None, uvw(dims))
         n, hist = mg.solve_p(1e-30, 3)
         return n, hist, mg.grid(1).p
     try:

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from _gpu import gpu_module
+from _problem import gpu_problem, oracle_twin, rhs, uvw
 from _ranks import free_port, run_process_ranks
 
 pytestmark = pytest.mark.gpu
@@ -30,39 +31,13 @@ mg = gpu_module(hold_odd_nz=0, periodic=0, rb_seq=1, rb_exact=0, krylov=0, krylo
 
 def _init(mg, dims, hold=1, bmask=False, **par):
     """mgx_init reads the option: clean, set, init; the seamount geometry (bmask: with the island mask)"""
-    from oracle.mgoracle import seamount_geometry
-    from mgroms_amd.testcases import island_mask
-    nx, ny, nz = dims
-    mg.nhydro_clean()
-    mg.nhydro.set_option("hold_odd_nz", hold)
-    kw = dict(relax_method="FC", solver_prec=1e-10)
-    kw.update(par)
-    if bmask:
-        kw["bmask"] = 1
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(**kw))
-    dx, dy, zeta, h = seamount_geometry(nx, ny, 1, 1, 0)
-    rmask = island_mask(nx, ny) if bmask else None
-    mg.nhydro_matrices(dx, dy, zeta, h, rmask, HC, 0.0, 0.0)
-    return dx, dy, zeta, h, rmask
+    return gpu_problem(mg, dims, bmask=bmask, sigma=(HC, 0.0, 0.0), init_options=dict(hold_odd_nz=hold),
+                       **dict(dict(relax_method="FC", solver_prec=1e-10), **par))
 
 
-def _rhs(mg, dims):
-    from mgroms_amd.testcases import resting_column_state
-    u, v, w = resting_column_state(*dims)
-    mg.nhydro.compute_rhs(u, v, w)
-    return u, v, w
-
-
-def _fp64_residual(mg, dims, geo, p, b, **par):
+def _fp64_residual(pr, p, b):
     """||b - A p|| / ||b|| by a level-1 Oracle of the full size (its own coarse levels are never used)"""
-    from oracle.mgoracle import Oracle
-    dx, dy, zeta, h, rmask = geo
-    o = Oracle(*dims, 1, 1, **par)
-    for name, a in (("dx", dx), ("dy", dy), ("zeta", zeta), ("h", h)):
-        o.field(name)[...] = a
-    if rmask is not None:
-        o.field("rmask")[...] = rmask
-    o.matrices(HC, 0.0, 0.0)
+    o = oracle_twin(pr)
     o.field("p")[...] = p; o.field("b")[...] = b
     o.residual(1)
     r = o.field("r")[1:-1, 1:-1]
@@ -177,7 +152,7 @@ def _solve(mg, dims, maxit=30, **kw):
     hold = kw.pop("hold", 1)
     bmask = kw.pop("bmask", False)
     geo = _init(mg, dims, hold=hold, bmask=bmask, **kw)
-    _rhs(mg, dims)
+    rhs(mg, None, uvw(dims))
     b = mg.grid(1).b
     n, hist = mg.solve_p(1e-10, maxit)
     return n, hist, geo, mg.grid(1).p, b
@@ -195,10 +170,7 @@ def test_solves_to_1e10(mg, dims, kw):
     print(dims, kw, "iterations", n, "history", hist)
     assert n < 30 and hist[-1] <= 1e-10, (n, hist)
     assert np.all(np.diff(hist) < 0), hist
-    okw = {k: v for k, v in kw.items() if k != "bmask"}
-    if kw.get("bmask"):
-        okw["bmask"] = True
-    res = _fp64_residual(mg, dims, geo, p, b, **okw)
+    res = _fp64_residual(geo, p, b)
     print("fp64 residual by the Oracle", res)
     assert res <= 1e-10 * (1 + 1e-6), res
 
@@ -270,7 +242,7 @@ def test_option_on_without_an_odd_level_changes_nothing(mg):
         out = []
         for hold in (0, 1):
             _init(mg, (32, 32, 16), hold=hold, relax_method=method)
-            _rhs(mg, (32, 32, 16))
+            rhs(mg, None, uvw((32, 32, 16)))
             c0 = mg.nhydro.counters()
             n, hist = mg.solve_p(1e-30, 3)
             c1 = mg.nhydro.counters()
@@ -294,7 +266,7 @@ def test_fp32_cycles_refused_with_a_held_pair_only(mg):
     try:
         for dims, served in (((32, 32, 20), False), ((32, 32, 16), True)):
             _init(mg, dims)
-            _rhs(mg, dims)
+            rhs(mg, None, uvw(dims))
             for (name, value), extra in settings():
                 for k, v in extra:
                     mg.nhydro.set_option(k, v)

@@ -12,42 +12,30 @@ import sys
 import numpy as np
 import pytest
 
-from _gpu import gpu_module
+from _gpu import gpu_module, restore_options
+from _problem import on_gpu, oracle_twin, problem, rhs, uvw
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 mg = gpu_module(krylov=0)
 
 
-@pytest.fixture(autouse=True)
-def _restore_options(mg):
-    """options survive nhydro_clean: put them back for the tests that run after this file"""
-    keep = {k: mg.nhydro.get_option(k) for k in ("krylov", "cycle_precision", "warm_start")}
-    yield
-    for k, v in keep.items():
-        mg.nhydro.set_option(k, v)
+_restore_options = restore_options("krylov", "cycle_precision", "warm_start")
 
 
-def _uvw(nx, ny, nz):
-    from mgroms_amd.testcases import resting_column_state
-    return resting_column_state(nx, ny, nz)
+def _case(nx, ny, nz, meth, bmask=False, **par):
+    """the record of a seamount case (bmask: with the island mask): what _gpu() hands to the GPU and _oracle() to the oracle"""
+    return problem((nx, ny, nz), bmask=bmask, **dict(dict(relax_method=meth, solver_prec=1e-10, solver_maxiter=50), **par))
 
 
-def _gpu(mg, nx, ny, nz, meth, bmask=False, **par):
-    from mgroms_amd.testcases import seamount_geometry, island_mask
-    kw = dict(relax_method=meth, solver_prec=1e-10, solver_maxiter=50)
-    kw.update(par)
-    if bmask:
-        kw["bmask"] = 1
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(**kw))
-    mg.nhydro_matrices(*seamount_geometry(nx, ny, 1, 1, 0), island_mask(nx, ny) if bmask else None, 4e3, 0.0, 0.0)
-    mg.nhydro.compute_rhs(*_uvw(nx, ny, nz))
+def _gpu(mg, pr):
+    on_gpu(mg, pr)
+    rhs(mg, None, uvw(pr.dims))
 
 
-def _oracle(nx, ny, nz, meth, **kw):
-    from oracle.mgoracle import make_seamount
-    o = make_seamount(nx, ny, nz, relax_method=meth, **kw)
-    o.compute_rhs()
+def _oracle(pr):
+    o = oracle_twin(pr)
+    rhs(None, o, uvw(pr.dims))
     return o
 
 
@@ -65,8 +53,9 @@ def _ratio(hist, href, floor):
 def test_history_follows_the_reference_gcr(mg):
     """64x64x16 four colours, m = 8, to 1e-10: entry by entry within 10 x eps_ref of the reference GCR, same count"""
     from tests._krylov_ref import eps_ref
-    e, nref, href = eps_ref(lambda: _oracle(64, 64, 16, "FC"), 8, 1e-10)
-    _gpu(mg, 64, 64, 16, "FC")
+    pr = _case(64, 64, 16, "FC")
+    e, nref, href = eps_ref(lambda: _oracle(pr), 8, 1e-10)
+    _gpu(mg, pr)
     n, hist = _solve(mg, 8, 1e-10)
     d = _ratio(hist, href, 1e-10)
     print(f"\n64x64x16 FC m=8: GPU {n} it, reference {nref} it, eps_ref {e:.3e}, max rel. history difference {d:.3e} = {d / e:.2f} x eps_ref")
@@ -76,33 +65,16 @@ def test_history_follows_the_reference_gcr(mg):
     assert mg.nhydro.get_option("krylov_restarts") == 0
 
 
-def _oracle_bmask(nx, ny, nz, meth):
-    """the oracle with the island mask, set up as tests/test_gpu_parity.py::test_bmask_bitwise does (make_seamount takes no mask)"""
-    from oracle.mgoracle import Oracle, seamount_geometry
-    from mgroms_amd.testcases import island_mask
-    o = Oracle(nx, ny, nz, 1, 1, relax_method=meth, bmask=True)
-    for name, a in zip(("dx", "dy", "zeta", "h"), seamount_geometry(nx, ny, 1, 1, 0)):
-        o.field(name)[...] = a
-    o.field("rmask")[...] = island_mask(nx, ny)
-    o.matrices(4e3, 0.0, 0.0)
-    u, v, w = _uvw(nx, ny, nz)
-    o.field("u")[...] = u; o.field("v")[...] = v; o.field("w")[...] = w
-    o.compute_rhs()
-    return o
-
-
 @pytest.mark.parametrize("what", ["simple", "bmask"])
 def test_history_follows_the_reference_gcr_simple_and_masked(mg, what):
     """64x64x16 four colours, m = 4, to 1e-10 with cmatrix = 'simple' (k_kr_apply_mf<false>) and with the island mask (the stored-slot operator
     k_kr_apply): entry by entry within 10 x eps_ref of the reference GCR on the same case, same count"""
     from tests._krylov_ref import eps_ref
-    if what == "simple":
-        e, nref, href = eps_ref(lambda: _oracle(64, 64, 16, "FC", cmatrix="simple"), 4, 1e-10)
-        _gpu(mg, 64, 64, 16, "FC", cmatrix="simple")
-    else:
-        e, nref, href = eps_ref(lambda: _oracle_bmask(64, 64, 16, "FC"), 4, 1e-10)
-        _gpu(mg, 64, 64, 16, "FC", bmask=True)
-        assert np.array_equal(mg.grid(1).b, _oracle_bmask(64, 64, 16, "FC").field("b"))
+    pr = _case(64, 64, 16, "FC", cmatrix="simple") if what == "simple" else _case(64, 64, 16, "FC", bmask=True)
+    e, nref, href = eps_ref(lambda: _oracle(pr), 4, 1e-10)
+    _gpu(mg, pr)
+    if what == "bmask":
+        assert np.array_equal(mg.grid(1).b, _oracle(pr).field("b"))
     n, hist = _solve(mg, 4, 1e-10)
     d = _ratio(hist, href, 1e-10)
     print(f"\n64x64x16 FC m=4 {what}: GPU {n} it, reference {nref} it, eps_ref {e:.3e}, max rel. history difference {d:.3e} = {d / e:.2f} x eps_ref")
@@ -118,9 +90,10 @@ def test_history_follows_the_reference_gcr_above_the_streaming_threshold(mg):
     from tests._krylov_ref import eps_ref
     import time
     t0 = time.time()
-    e, nref, href = eps_ref(lambda: _oracle(256, 256, 64, "FC"), 4, 1e-8)
+    pr = _case(256, 256, 64, "FC")
+    e, nref, href = eps_ref(lambda: _oracle(pr), 4, 1e-8)
     t1 = time.time() - t0
-    _gpu(mg, 256, 256, 64, "FC")
+    _gpu(mg, pr)
     n, hist = _solve(mg, 4, 1e-8)
     d = _ratio(hist, href, 1e-8)
     print(f"\n256x256x64 FC m=4: GPU {n} it, reference {nref} it ({t1:.0f} s for eps_ref), eps_ref {e:.3e}, max rel. history difference {d:.3e} = {d / e:.2f} x eps_ref")
@@ -132,8 +105,9 @@ def test_history_follows_the_reference_gcr_above_the_streaming_threshold(mg):
 @pytest.mark.parametrize("dims,meth,slack", [((128, 128, 16), "FC", 0), ((256, 256, 32), "RB", 1)])
 def test_fewer_iterations_than_plain(mg, dims, meth, slack):
     from tests._krylov_ref import gcr
-    nref, href, _ = gcr(_oracle(*dims, meth), 4, 1e-6, 50)
-    _gpu(mg, *dims, meth)
+    pr = _case(*dims, meth)
+    nref, href, _ = gcr(_oracle(pr), 4, 1e-6, 50)
+    _gpu(mg, pr)
     npl, hpl = _solve(mg, 0, 1e-6)
     n, hist = _solve(mg, 4, 1e-6)
     print(f"\n{dims} {meth}: plain {npl} it -> {hpl[-1]:.3e}; krylov(4) {n} it -> {hist[-1]:.3e}; reference GCR {nref} it -> {href[-1]:.3e}")
@@ -146,7 +120,7 @@ def test_fewer_iterations_than_plain(mg, dims, meth, slack):
                                              ((64, 64, 16), "FC", True), ((64, 64, 16), "RB", True)])
 def test_monotone_and_not_slower(mg, dims, meth, bmask):
     """an odd coarsest nz, the island mask, Gauss-Seidel once: monotone history, no more iterations than plain solve_p"""
-    _gpu(mg, *dims, meth, bmask=bmask)
+    _gpu(mg, _case(*dims, meth, bmask=bmask))
     npl, hpl = _solve(mg, 0, 1e-10)
     n, hist = _solve(mg, 4, 1e-10)
     print(f"\n{dims} {meth} bmask={bmask}: plain {npl}, krylov(4) {n}: " + " ".join(f"{v:.2e}" for v in hist))
@@ -156,7 +130,7 @@ def test_monotone_and_not_slower(mg, dims, meth, bmask):
 
 def test_reported_residual_is_the_true_one(mg):
     """128x128x32 red-black, m = 8, tol 1e-14, 20 iterations: the recurrence drifts below the true residual there"""
-    _gpu(mg, 128, 128, 32, "RB")
+    _gpu(mg, _case(128, 128, 32, "RB"))
     mg.nhydro.set_option("krylov", 8)
     from mgroms_amd._lib import lib
     import ctypes as C
@@ -190,8 +164,9 @@ def test_ranks_2x2(mg):
     """2x2 thread-ranks on one GPU, four colours, m = 4: the one-rank history within 10 x eps_ref, same count, one all-reduce per pass"""
     from tests._krylov_ref import eps_ref
     tol = 1e-8
-    e, nref, href = eps_ref(lambda: _oracle(128, 128, 16, "FC"), 4, tol)
-    _gpu(mg, 128, 128, 16, "FC")
+    pr = _case(128, 128, 16, "FC")
+    e, nref, href = eps_ref(lambda: _oracle(pr), 4, tol)
+    _gpu(mg, pr)
     n1, h1 = _solve(mg, 4, tol)
     r = subprocess.run([sys.executable, os.path.join(HERE, "_gpu_krylov_ranks.py"), "64", "64", "16", "4", str(tol), "50"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
@@ -214,18 +189,19 @@ def test_nhydro_solve_against_the_oracle(mg, device):
     import torch
     from tests._krylov_ref import gcr
     nx, ny, nz = 64, 64, 16
-    u, v, w = _uvw(nx, ny, nz)
-    o = _oracle(nx, ny, nz, "FC", solver_prec=1e-10)
+    u, v, w = uvw((nx, ny, nz))
+    pr = _case(nx, ny, nz, "FC")
+    o = _oracle(pr)
     o.field("u")[...] = u; o.field("v")[...] = v; o.field("w")[...] = w
     o.nhydro_solve()
     plain = [o.field(k).copy() for k in "uvw"]
-    o2 = _oracle(nx, ny, nz, "FC", solver_prec=1e-10)
+    o2 = _oracle(pr)
     o2.field("u")[...] = u; o2.field("v")[...] = v; o2.field("w")[...] = w
     o2.compute_rhs()
     gcr(o2, 4, 1e-10, 50)
     o2.correct_uvw()
     bound = [10 * np.abs(o2.field(k) - a).max() for k, a in zip("uvw", plain)]
-    _gpu(mg, nx, ny, nz, "FC")
+    _gpu(mg, pr)
     mg.nhydro.set_option("krylov", 4)
     if device:
         d = [torch.from_numpy(a).cuda() for a in (u, v, w)]
@@ -246,7 +222,7 @@ def test_refusals(mg):
         with pytest.raises(MgxError, match="krylov"):
             mg.nhydro.set_option("krylov", bad)
     assert mg.nhydro.get_option("krylov") == 0
-    _gpu(mg, 32, 32, 8, "FC")
+    _gpu(mg, _case(32, 32, 8, "FC"))
     mg.nhydro.set_option("krylov", 4)
     mg.nhydro.set_option("cycle_precision", 32)
     with pytest.raises(MgxError, match=r"krylov.*cycle_precision"):
@@ -260,7 +236,7 @@ def test_refusals(mg):
 
 def test_warm_start(mg):
     """warm_start: the second solve starts from the p found"""
-    _gpu(mg, 64, 64, 16, "FC")
+    _gpu(mg, _case(64, 64, 16, "FC"))
     n, hist = _solve(mg, 4, 1e-8)
     mg.nhydro.set_option("warm_start", 1)
     n2, hist2 = mg.solve_p(1e-8, 50)

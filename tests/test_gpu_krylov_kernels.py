@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from _gpu import gpu_module
+from _problem import gpu_problem, oracle_twin
 from tests import _krylov_kernel_ref as K
 
 pytestmark = pytest.mark.gpu
@@ -36,37 +37,20 @@ def _setup(mg, shape, variant="real"):
     if _now.get("key") == (shape, variant):
         return _now["o"]
     _now.clear()
-    from oracle.mgoracle import Oracle, make_seamount, seamount_geometry
-    from mgroms_amd.testcases import island_mask
     nx, ny, nz = shape
-    cm = "simple" if variant == "simple" else "real"
-    dx, dy, zeta, h = seamount_geometry(nx, ny, 1, 1, 0)
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(relax_method="FC", cmatrix=cm, bmask=1 if variant == "bmask" else 0))
-    if variant == "bmask":
-        rmask = island_mask(nx, ny)
-        mg.nhydro_matrices(dx, dy, zeta, h, rmask, 4e3, 0.0, 0.0)
-        o = Oracle(nx, ny, nz, 1, 1, relax_method="FC", bmask=True)
-        for name, a in (("dx", dx), ("dy", dy), ("zeta", zeta), ("h", h), ("rmask", rmask)):
-            o.field(name)[...] = a
-        o.matrices(4e3, 0.0, 0.0)
-    elif variant == "stretched":
-        zeta = 0.3 * np.cos(np.arange(nx + 2))[:, None] * np.ones((1, ny + 2))
-        mg.nhydro_matrices(dx, dy, zeta, h, None, 250.0, 0.4, 6.0)
-        o = Oracle(nx, ny, nz, relax_method="FC")
-        for name, a in (("dx", dx), ("dy", dy), ("zeta", zeta), ("h", h)):
-            o.field(name)[...] = a
-        o.matrices(250.0, 0.4, 6.0)
+    kw = dict(relax_method="FC", cmatrix="simple" if variant == "simple" else "real")
+    if variant == "stretched":
+        kw.update(zeta=0.3 * np.cos(np.arange(nx + 2))[:, None] * np.ones((1, ny + 2)), sigma=(250.0, 0.4, 6.0))
+    o = oracle_twin(gpu_problem(mg, shape, bmask=variant == "bmask", **kw))
+    g = mg.grid(1)
+    if variant == "stretched":
         # device cosh / exp differ from the host's in the last bit (test_stretched_sigma_coordinates): the operator is checked on the
         # coefficients the GPU built, which the oracle takes over
-        o.field("cA")[...] = mg.grid(1).get("cA")
-    else:
-        mg.nhydro_matrices(dx, dy, zeta, h, None, 4e3, 0.0, 0.0)
-        o = make_seamount(nx, ny, nz, relax_method="FC", cmatrix=cm)
-        if variant == "userA":   # a user matrix through set_field: the library falls back to the stored slots
-            g = mg.grid(1)
-            cA = g.get("cA")
-            cA[..., 2] *= 1.5; cA[..., 5] *= 1.5
-            g.set("cA", cA); o.field("cA")[...] = cA
+        o.field("cA")[...] = g.get("cA")
+    if variant == "userA":   # a user matrix through set_field: the library falls back to the stored slots
+        cA = g.get("cA")
+        cA[..., 2] *= 1.5; cA[..., 5] *= 1.5
+        g.set("cA", cA); o.field("cA")[...] = cA
     _now.update(key=(shape, variant), o=o)
     return o
 

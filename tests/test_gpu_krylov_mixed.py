@@ -15,7 +15,8 @@ import sys
 import numpy as np
 import pytest
 
-from _gpu import gpu_module
+from _gpu import gpu_module, restore_options
+from _problem import gpu_problem, on_gpu, oracle_relative_residual, oracle_twin, problem, rhs, uvw
 from tests import _krylov_kernel_ref as K
 
 pytestmark = pytest.mark.gpu
@@ -26,13 +27,7 @@ OPTIONS = ("krylov", "krylov_precision", "cycle_precision", "warm_start", "rb_ex
 mg = gpu_module(krylov=0, krylov_precision=64)
 
 
-@pytest.fixture(autouse=True)
-def _restore_options(mg):
-    """options survive nhydro_clean: put them back for the tests that run after this file"""
-    keep = {k: mg.nhydro.get_option(k) for k in OPTIONS}
-    yield
-    for k, v in keep.items():
-        mg.nhydro.set_option(k, v)
+_restore_options = restore_options(*OPTIONS)
 
 
 # ---- the two kernels ---------------------------------------------------------------------------------------------------------------
@@ -51,11 +46,7 @@ def _setup(mg, shape, variant="real"):
     """level 1 of `shape` on the GPU (kept while shape and variant stay); no oracle: the references here are numpy and the fp64 passes"""
     if _now.get("key") == (shape, variant):
         return
-    from mgroms_amd.testcases import island_mask, seamount_geometry
-    nx, ny, nz = shape
-    cm = "simple" if variant == "simple" else "real"
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(relax_method="FC", cmatrix=cm, bmask=1 if variant == "bmask" else 0))
-    mg.nhydro_matrices(*seamount_geometry(nx, ny, 1, 1, 0), island_mask(nx, ny) if variant == "bmask" else None, 4e3, 0.0, 0.0)
+    gpu_problem(mg, shape, bmask=variant == "bmask", relax_method="FC", cmatrix="simple" if variant == "simple" else "real")
     if variant == "userA":   # a user matrix through set_field: the stored-slot operator at nz >= 3
         g = mg.grid(1)
         cA = g.get("cA")
@@ -166,62 +157,31 @@ def test_update32_dense(mg):
 
 
 # ---- solves ------------------------------------------------------------------------------------------------------------------------
-def _uvw(nx, ny, nz):
-    from mgroms_amd.testcases import resting_column_state
-    return resting_column_state(nx, ny, nz)
+def _case(nx, ny, nz, meth, bmask=False, **par):
+    """the record of a seamount case (bmask: with the island mask): what _gpu() hands to the GPU and the reference's oracle is made from"""
+    return problem((nx, ny, nz), bmask=bmask, **dict(dict(relax_method=meth, solver_prec=1e-8, solver_maxiter=50), **par))
 
 
-def _gpu(mg, nx, ny, nz, meth, bmask=False, **par):
-    from mgroms_amd.testcases import seamount_geometry, island_mask
-    kw = dict(relax_method=meth, solver_prec=1e-8, solver_maxiter=50)
-    kw.update(par)
-    if bmask:
-        kw["bmask"] = 1
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(**kw))
-    mg.nhydro_matrices(*seamount_geometry(nx, ny, 1, 1, 0), island_mask(nx, ny) if bmask else None, 4e3, 0.0, 0.0)
-    mg.nhydro.compute_rhs(*_uvw(nx, ny, nz))
+def _gpu(mg, pr):
+    on_gpu(mg, pr)
+    rhs(mg, None, uvw(pr.dims))
     _now.clear()
-
-
-def _oracle(nx, ny, nz, meth, bmask=False, **kw):
-    """the CPU oracle of the case with its right-hand side set (the island mask as tests/test_gpu_krylov.py sets it up)"""
-    from oracle.mgoracle import Oracle, make_seamount, seamount_geometry
-    from mgroms_amd.testcases import island_mask
-    if not bmask:
-        o = make_seamount(nx, ny, nz, relax_method=meth, **kw)
-        o.compute_rhs()
-        return o
-    o = Oracle(nx, ny, nz, 1, 1, relax_method=meth, bmask=True)
-    for name, a in zip(("dx", "dy", "zeta", "h"), seamount_geometry(nx, ny, 1, 1, 0)):
-        o.field(name)[...] = a
-    o.field("rmask")[...] = island_mask(nx, ny)
-    o.matrices(4e3, 0.0, 0.0)
-    u, v, w = _uvw(nx, ny, nz)
-    o.field("u")[...] = u; o.field("v")[...] = v; o.field("w")[...] = w
-    o.compute_rhs()
-    return o
 
 
 _refs = {}
 
 
 def _reference(dims, meth, bmask, cmatrix, tol):
-    """iterations of the reference GCR (fp64, over the oracle, m = 4) and the oracle, computed once per case"""
+    """iterations of the reference GCR (fp64, over the oracle, m = 4), the oracle and the record it was made from, computed once per case"""
     from tests._krylov_ref import gcr
     key = (dims, meth, bmask, cmatrix, tol)
     if key not in _refs:
-        o = _oracle(*dims, meth, bmask=bmask, **({"cmatrix": cmatrix} if cmatrix else {}))
+        pr = _case(*dims, meth, bmask=bmask, **({"cmatrix": cmatrix} if cmatrix else {}))
+        o = oracle_twin(pr)
+        rhs(None, o, uvw(dims))
         nref, href, _ = gcr(o, 4, tol, 50)
-        _refs[key] = (nref, href, o)
+        _refs[key] = (nref, href, o, pr)
     return _refs[key]
-
-
-def _oracle_res(o, p):
-    """the oracle's fp64 ||b - A p|| / ||b|| of p"""
-    bn = np.sqrt(np.sum(o.field("b")[1:-1, 1:-1, :] ** 2))
-    o.field("p")[...] = p
-    o.fill_halo(1, "p")
-    return o.residual(1) / bn
 
 
 SOLVES = [((64, 64, 16), "FC", False, None, 1e-8), ((64, 64, 16), "RB", False, None, 1e-8), ((128, 128, 32), "RB", False, None, 1e-8),
@@ -240,14 +200,14 @@ def test_solve(mg, case):
     the returned p (1e-9 relative, the comparison of tests/test_gpu_mixed_precision.py); (b) at most the reference GCR's count + 2;
     (c) every iteration counted under krylov_mixed_iterations, none under mixed_iterations"""
     dims, meth, bmask, cm, tol = case
-    nref, href, o = _reference(dims, meth, bmask, cm, tol)
-    _gpu(mg, *dims, meth, bmask=bmask, **({"cmatrix": cm} if cm else {}))
+    nref, href, o, pr = _reference(dims, meth, bmask, cm, tol)
+    _gpu(mg, pr)
     assert np.array_equal(mg.grid(1).b, o.field("b"))
     mg.nhydro.set_option("krylov", 4)
     mg.nhydro.set_option("krylov_precision", 32)
     before = mg.nhydro.get_option("krylov_mixed_iterations"), mg.nhydro.get_option("mixed_iterations")
     n, hist = mg.solve_p(tol, 50)
-    ro = _oracle_res(o, mg.grid(1).p)
+    ro = oracle_relative_residual(o, mg.grid(1).p)
     print(f"\n{_solve_id(case)}: fp32-cycle GCR {n} it -> {hist[-1]:.3e} (oracle's residual of p {ro:.3e}), reference GCR {nref} it -> {href[-1]:.3e}, "
           f"restarts {mg.nhydro.get_option('krylov_restarts')}\n  " + " ".join(f"{v:.2e}" for v in hist))
     assert hist[-1] <= tol, hist
@@ -277,7 +237,7 @@ def test_steady_state_iteration_has_no_conversion_launch(mg, meth):
     cycle + pass 1 and the reduction of its inner products (2) + pass 2 and its reduction (2) + pass 3 and its reduction (2); e = 0 is a
     memset, not a launch.  fp32: the cycle as counted above and nothing else -- no k_to32, no k_to64.  fp64: the fp64 F-cycle, measured as
     the launches of one mgx_fcycle."""
-    _gpu(mg, 64, 64, 16, meth)
+    _gpu(mg, _case(64, 64, 16, meth))
     mg.nhydro.set_option("krylov", 4)
     cnt = lambda: mg.nhydro.counters()["launches"]
     diff = {}
@@ -302,7 +262,7 @@ def test_restart_refills_f(mg):
     new r: with the old f the cycle would answer a residual the loop no longer has)"""
     import ctypes as C
     from mgroms_amd._lib import lib
-    _gpu(mg, 64, 64, 16, "FC")
+    _gpu(mg, _case(64, 64, 16, "FC"))
     mg.nhydro.set_option("krylov", 8)
     mg.nhydro.set_option("krylov_precision", 32)
     n, res, hist = C.c_int(), C.c_double(), (C.c_double * 21)()
@@ -338,7 +298,7 @@ def test_other_values_refused(mg):
 @pytest.mark.parametrize("how", ["GS", "rb_exact"])
 def test_unsupported_combinations_refused(mg, how):
     from mgroms_amd._lib import MgxError
-    _gpu(mg, 32, 32, 8, "GS" if how == "GS" else "RB")
+    _gpu(mg, _case(32, 32, 8, "GS" if how == "GS" else "RB"))
     if how == "rb_exact":
         mg.nhydro.set_option("rb_exact", 1)
     mg.nhydro.set_option("krylov", 4)
@@ -361,7 +321,7 @@ def test_refused_on_a_process_grid():
 @pytest.mark.parametrize("meth", ["FC", "RB"])
 def test_inert_without_krylov(mg, meth):
     """krylov = 0: solve_p with krylov_precision = 32 gives the history and p of the default, bit for bit, and counts nothing"""
-    _gpu(mg, 64, 64, 16, meth)
+    _gpu(mg, _case(64, 64, 16, meth))
     n0, h0 = mg.solve_p(1e-8, 50)
     p0 = mg.grid(1).p
     mg.nhydro.set_option("krylov_precision", 32)
@@ -372,13 +332,13 @@ def test_inert_without_krylov(mg, meth):
 
 def test_option_survives_clean_init_and_the_old_refusal_stays(mg):
     from mgroms_amd._lib import MgxError
-    _gpu(mg, 32, 32, 8, "FC")
+    _gpu(mg, _case(32, 32, 8, "FC"))
     mg.nhydro.set_option("krylov", 4)
     mg.nhydro.set_option("krylov_precision", 32)
     n, hist = mg.solve_p(1e-8, 20)
     assert hist[-1] <= 1e-8 and mg.nhydro.get_option("krylov_mixed_iterations") == n
     mg.nhydro_clean()
-    _gpu(mg, 32, 32, 8, "FC")
+    _gpu(mg, _case(32, 32, 8, "FC"))
     assert mg.nhydro.get_option("krylov_precision") == 32
     assert mg.nhydro.get_option("krylov_mixed_iterations") == 0
     mg.nhydro.set_option("cycle_precision", 32)

@@ -16,7 +16,8 @@ of 5000 for that amplification.
 import numpy as np
 import pytest
 
-from _gpu import gpu_module
+from _gpu import gpu_module, restore_options
+from _problem import gpu_problem, oracle_relative_residual, oracle_twin, regions, rhs, uvw
 
 pytestmark = pytest.mark.gpu
 mg = gpu_module(cycle_precision=64)
@@ -34,69 +35,21 @@ def _worst_table(mg):
             print(f"  {op:28s} {region:9s} {v:.2e}")
 
 
-@pytest.fixture(autouse=True)
-def _restore_options(mg):
-    """the options this file touches survive nhydro_clean: put them back for the tests that run after it"""
-    keep = {k: mg.nhydro.get_option(k) for k in ("cycle_precision", "rb_exact", "rb_seq", "warm_start")}
-    yield
-    for k, v in keep.items():
-        mg.nhydro.set_option(k, v)
+_restore_options = restore_options("cycle_precision", "rb_exact", "rb_seq", "warm_start")
 
 
-def _setup(mg, nx, ny, nz, bmask=False, zeta=None, sigma=None, oracle=True, **par):
+def _setup(mg, nx, ny, nz, oracle=True, **kw):
     """the seamount problem on the GPU and the CPU oracle's copy of its matrix (bmask: the island mask on both; sigma: (hc, theta_b,
-    theta_s) of the GPU matrix, stretched coordinates; oracle=False: the GPU side only, returns None)"""
-    from oracle.mgoracle import Oracle, seamount_geometry
-    from mgroms_amd.testcases import island_mask
-    kw = dict(relax_method="FC", solver_prec=PREC, solver_maxiter=50)
-    kw.update(par)
-    if bmask:
-        kw["bmask"] = 1
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(**kw))
-    dx, dy, z0, h = seamount_geometry(nx, ny, 1, 1, 0)
-    if zeta is not None:
-        z0 = zeta
-    rmask = island_mask(nx, ny) if bmask else None
-    mg.nhydro_matrices(dx, dy, z0, h, rmask, *(sigma or (4e3, 0.0, 0.0)))
-    if not oracle:
-        return None
-    okw = {k: kw[k] for k in ("relax_method", "cmatrix", "interp_type") if k in kw}
-    if bmask:
-        okw["bmask"] = True
-    o = Oracle(nx, ny, nz, 1, 1, **okw)
-    for name, a in (("dx", dx), ("dy", dy), ("zeta", z0), ("h", h)):
-        o.field(name)[...] = a
-    if bmask:
-        o.field("rmask")[...] = rmask
-    o.matrices(4e3, 0.0, 0.0)
-    return o
-
-
-def _uvw(nx, ny, nz):
-    from mgroms_amd.testcases import resting_column_state
-    return resting_column_state(nx, ny, nz)
-
-
-def _rhs(mg, o, nx, ny, nz):
-    u, v, w = _uvw(nx, ny, nz)
-    mg.nhydro.compute_rhs(u, v, w)
-    if o is not None:
-        o.field("w")[...] = w
-        o.compute_rhs()
+    theta_s), stretched coordinates; oracle=False: the GPU side only, returns None).  The oracle here only ever recomputes a level-1
+    residual, never a cycle: it takes the members that shape the matrix and keeps its defaults for the rest."""
+    pr = gpu_problem(mg, (nx, ny, nz), **dict(dict(relax_method="FC", solver_prec=PREC, solver_maxiter=50), **kw))
+    return oracle_twin(pr, only=("relax_method", "cmatrix", "interp_type", "bmask")) if oracle else None
 
 
 def _solve(mg, prec, maxite=50):
     mg.nhydro.set_option("cycle_precision", prec)
     n, hist = mg.solve_p(PREC, maxite)
     return n, hist, mg.grid(1).p
-
-
-def _oracle_res(o, p):
-    """the oracle's fp64 ||b - A p|| / ||b|| of p"""
-    bn = np.sqrt(np.sum(o.field("b")[1:-1, 1:-1, :] ** 2))
-    o.field("p")[...] = p
-    o.fill_halo(1, "p")
-    return o.residual(1) / bn
 
 
 # ---- operators ------------------------------------------------------------------------------------------------------------
@@ -207,16 +160,6 @@ def _note(op, region, ratio):
     _WORST[(op, region)] = max(_WORST.get((op, region), 0.0), ratio)
 
 
-def _regions(a):
-    """the four regions of a level array (i, j, k): rows k = 2..nz-1, k = 1 and k = nz of the interior columns, and the halo cells"""
-    inner = a[1:-1, 1:-1]
-    out = {"k=1": inner[:, :, 0], "k=nz": inner[:, :, -1],
-           "halo": np.concatenate([a[0].ravel(), a[-1].ravel(), a[1:-1, 0].ravel(), a[1:-1, -1].ravel()])}
-    if a.shape[2] > 2:
-        out["interior"] = inner[:, :, 1:-1]
-    return out
-
-
 def _mirrored(a, what):
     """every physical-boundary image of a (edges and corners, all four sides: a single rank) equals its interior source bit for bit"""
     want = np.pad(a[1:-1, 1:-1], ((1, 1), (1, 1), (0, 0)), mode="edge")
@@ -226,8 +169,8 @@ def _mirrored(a, what):
 
 def _check(a, ref, op, what):
     _close(a, ref, what)
-    ra = _regions(a)
-    for name, r in _regions(ref).items():
+    ra = regions(a)
+    for name, r in regions(ref).items():
         m = np.abs(r).max()
         assert m > 0, f"{what}, {name}: the fp64 result is zero there"
         d = np.abs(ra[name] - r).max()
@@ -428,7 +371,7 @@ def test_mixed_cycle_matches_fp64(mg, case, method):
     dims = c.pop("dims")
     _setup(mg, *dims, relax_method=method, oracle=False, **c)
     mg.nhydro.set_option("rb_seq", 0)
-    _rhs(mg, None, *dims)
+    rhs(mg, None, uvw(dims))
     out = {}
     for prec in (64, 32):
         n1, _, p1 = _solve(mg, prec, 1)
@@ -451,7 +394,7 @@ def test_mixed_cycle_warm_start(mg, method):
     nx, ny, nz = 64, 64, 16
     _setup(mg, nx, ny, nz, relax_method=method, oracle=False)
     mg.nhydro.set_option("rb_seq", 0)
-    _rhs(mg, None, nx, ny, nz)
+    rhs(mg, None, uvw((nx, ny, nz)))
     _, _, p0 = _solve(mg, 64, 2)
     mg.nhydro.set_option("warm_start", 1)
     dp = {}
@@ -496,7 +439,7 @@ def test_mixed_solve(mg, case):
     o = _setup(mg, nx, ny, nz, **c)
     if nz == 48:
         assert mg.grid(mg.nlevs()).nz == 3
-    _rhs(mg, o, nx, ny, nz)
+    rhs(mg, o, uvw((nx, ny, nz)))
     n64, h64, p64 = _solve(mg, 64, maxite)
     assert h64[-1] <= PREC, (n64, h64)
     it0 = mg.nhydro.get_option("mixed_iterations")
@@ -504,7 +447,7 @@ def test_mixed_solve(mg, case):
     assert h32[-1] <= PREC, (n32, h32)
     assert mg.nhydro.get_option("mixed_iterations") - it0 == n32
     assert n32 <= n64 + 2, (n32, n64, h32, h64)
-    ro = _oracle_res(o, p32)
+    ro = oracle_relative_residual(o, p32)
     assert abs(ro - h32[-1]) <= 1e-9 * h32[-1], (ro, h32[-1])
     d = np.abs(p32 - p64).max() / np.abs(p64).max()
     assert d <= 1e-8, d
@@ -513,7 +456,7 @@ def test_mixed_solve(mg, case):
 def test_mixed_is_deterministic(mg):
     nx, ny, nz = 128, 128, 32
     _setup(mg, nx, ny, nz, relax_method="RB")
-    _rhs(mg, None, nx, ny, nz)
+    rhs(mg, None, uvw((nx, ny, nz)))
     n1, h1, p1 = _solve(mg, 32)
     n2, h2, p2 = _solve(mg, 32)
     assert n1 == n2
@@ -525,12 +468,12 @@ def test_mixed_is_deterministic(mg):
 def test_fp64_after_mixed_is_unchanged(mg, method):
     nx, ny, nz = 128, 128, 32
     _setup(mg, nx, ny, nz, relax_method=method)
-    _rhs(mg, None, nx, ny, nz)
+    rhs(mg, None, uvw((nx, ny, nz)))
     n_a, h_a, p_a = _solve(mg, 64)            # fresh fp64 solve
     _setup(mg, nx, ny, nz, relax_method=method)
-    _rhs(mg, None, nx, ny, nz)
+    rhs(mg, None, uvw((nx, ny, nz)))
     _solve(mg, 32)
-    _rhs(mg, None, nx, ny, nz)
+    rhs(mg, None, uvw((nx, ny, nz)))
     n_b, h_b, p_b = _solve(mg, 64)            # fp64 right after a mixed one, same process, same solver
     assert n_a == n_b
     assert np.array_equal(h_a, h_b)
@@ -540,29 +483,29 @@ def test_fp64_after_mixed_is_unchanged(mg, method):
 def test_mixed_follows_new_matrix(mg):
     nx, ny, nz = 64, 64, 16
     o = _setup(mg, nx, ny, nz)
-    _rhs(mg, o, nx, ny, nz)
+    rhs(mg, o, uvw((nx, ny, nz)))
     n, h, p = _solve(mg, 32)
-    assert abs(_oracle_res(o, p) - h[-1]) <= 1e-9 * h[-1]
+    assert abs(oracle_relative_residual(o, p) - h[-1]) <= 1e-9 * h[-1]
     # nhydro_matrices again with another free surface: the fp32 coefficients must follow
-    from oracle.mgoracle import seamount_geometry
+    from mgroms_amd.testcases import seamount_geometry
     dx, dy, _, hh = seamount_geometry(nx, ny, 1, 1, 0)
     i = np.arange(nx + 2)[:, None]; j = np.arange(ny + 2)[None, :]
     zeta = 5.0 * np.sin(2 * np.pi * i / nx) * np.cos(2 * np.pi * j / ny)
     o2 = _setup(mg, nx, ny, nz, zeta=zeta)
     mg.nhydro.set_option("cycle_precision", 32)
     mg.nhydro_matrices(dx, dy, zeta, hh, None, 4e3, 0.0, 0.0)
-    _rhs(mg, o2, nx, ny, nz)
+    rhs(mg, o2, uvw((nx, ny, nz)))
     n2, h2, p2 = _solve(mg, 32)
     assert h2[-1] <= PREC
-    assert abs(_oracle_res(o2, p2) - h2[-1]) <= 1e-9 * h2[-1]
+    assert abs(oracle_relative_residual(o2, p2) - h2[-1]) <= 1e-9 * h2[-1]
     # and the same within one solver: solve, change the matrix, solve again
     _setup(mg, nx, ny, nz)
-    _rhs(mg, None, nx, ny, nz)
+    rhs(mg, None, uvw((nx, ny, nz)))
     _solve(mg, 32)
     mg.nhydro_matrices(dx, dy, zeta, hh, None, 4e3, 0.0, 0.0)
-    _rhs(mg, o2, nx, ny, nz)
+    rhs(mg, o2, uvw((nx, ny, nz)))
     n3, h3, p3 = _solve(mg, 32)
-    assert abs(_oracle_res(o2, p3) - h3[-1]) <= 1e-9 * h3[-1]
+    assert abs(oracle_relative_residual(o2, p3) - h3[-1]) <= 1e-9 * h3[-1]
     assert np.array_equal(p3, p2)
 
 
@@ -574,10 +517,10 @@ def test_nhydro_solve_entry_points_go_mixed(mg):
     for prec in (64, 32):
         mg.nhydro.set_option("cycle_precision", prec)
         it0 = mg.nhydro.get_option("mixed_iterations")
-        u, v, w = _uvw(nx, ny, nz)
+        u, v, w = uvw((nx, ny, nz))
         mg.nhydro_solve(u, v, w)
         host_its = mg.nhydro.get_option("mixed_iterations") - it0
-        u2, v2, w2 = (torch.from_numpy(a.copy()).cuda() for a in _uvw(nx, ny, nz))
+        u2, v2, w2 = (torch.from_numpy(a.copy()).cuda() for a in uvw((nx, ny, nz)))
         mg.nhydro.nhydro_solve_device(u2, v2, w2)
         torch.cuda.synchronize()
         dev_its = mg.nhydro.get_option("mixed_iterations") - it0 - host_its
@@ -634,7 +577,7 @@ def test_unsupported_combinations_refused(mg, how):
     else:
         _setup(mg, nx, ny, nz, relax_method="RB")
         mg.nhydro.set_option("rb_exact", 1)
-    _rhs(mg, None, nx, ny, nz)
+    rhs(mg, None, uvw((nx, ny, nz)))
     mg.nhydro.set_option("cycle_precision", 32)
     with pytest.raises(MgxError, match="cycle_precision"):
         mg.solve_p(PREC, 50)

@@ -12,7 +12,8 @@ Shapes: the smallest that take each path of the kernel (SHAPES below); at 512x51
 import numpy as np
 import pytest
 
-from _gpu import gpu_module
+from _gpu import gpu_module, restore_options
+from _problem import gpu_problem, regions, rhs, uvw
 
 pytestmark = pytest.mark.gpu
 
@@ -33,23 +34,12 @@ SHAPE_IDS = ["x".join(map(str, d)) for d, _ in SHAPES]
 mg = gpu_module()
 
 
-@pytest.fixture(autouse=True)
-def _restore_options(mg):
-    """the options this file touches survive nhydro_clean: put them back for the tests that run after it"""
-    keep = {k: mg.nhydro.get_option(k) for k in OPTIONS}
-    yield
-    for k, v in keep.items():
-        mg.nhydro.set_option(k, v)
+_restore_options = restore_options(*OPTIONS)
 
 
 def _setup(mg, dims, method="FC", bmask=False, **par):
-    from mgroms_amd.testcases import island_mask, seamount_geometry
     nx, ny, nz = dims
-    kw = dict(METHODS[method], solver_prec=1e-12, solver_maxiter=50, **par)
-    if bmask:
-        kw["bmask"] = 1
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(**kw))
-    mg.nhydro_matrices(*seamount_geometry(nx, ny, 1, 1, 0), island_mask(nx, ny) if bmask else None, 4e3, 0.0, 0.0)
+    gpu_problem(mg, dims, bmask=bmask, **dict(METHODS[method], solver_prec=1e-12, solver_maxiter=50, **par))
     mg.nhydro.set_option("rb_seq", 0)   # the fp64 red-black pass the fp32 one restates
     for k in ("krylov", "warm_start"):
         mg.nhydro.set_option(k, 0)
@@ -57,11 +47,6 @@ def _setup(mg, dims, method="FC", bmask=False, **par):
     first = mg.nhydro.mixed_tail_first(nx, ny, nz)
     assert first >= 1
     return first
-
-
-def _rhs(mg, dims):
-    from mgroms_amd.testcases import resting_column_state
-    mg.nhydro.compute_rhs(*resting_column_state(*dims))
 
 
 def _random_state(mg, rng):
@@ -103,19 +88,9 @@ def _same(a, b, what):
         assert bad.size == 0, f"{what}: level {lev}: {len(bad)} cells of p differ, first (i, j, k) {bad[:4].tolist()}, max |diff| {np.abs(a[lev] - b[lev]).max():.3e}"
 
 
-def _regions(a):
-    """rows k = 2..nz-1, k = 1 and k = nz of the interior columns, and the halo cells (as tests/test_gpu_mixed_precision.py)"""
-    inner = a[1:-1, 1:-1]
-    out = {"k=1": inner[:, :, 0], "k=nz": inner[:, :, -1],
-           "halo": np.concatenate([a[0].ravel(), a[-1].ravel(), a[1:-1, 0].ravel(), a[1:-1, -1].ravel()])}
-    if a.shape[2] > 2:
-        out["interior"] = inner[:, :, 1:-1]
-    return out
-
-
 def _close_fp64(a, ref, what):
-    ra = _regions(a)
-    for name, r in _regions(ref).items():
+    ra = regions(a)
+    for name, r in regions(ref).items():
         m = np.abs(r).max()
         assert m > 0, f"{what}, {name}: the fp64 result is zero there"
         d = np.abs(ra[name] - r).max()
@@ -149,7 +124,7 @@ def _check_vcycles(mg, first, rng, what):
 
 
 def _check_solve(mg, dims, what, maxite=3):
-    _rhs(mg, dims)
+    rhs(mg, None, uvw(dims))
     out = []
     for tail in (0, 1):
         mg.nhydro.set_option("mixed_tail", tail)

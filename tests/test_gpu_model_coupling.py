@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from _gpu import gpu_module
+from _problem import gpu_problem, load, load_uvw, oracle_twin, problem
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -75,29 +76,10 @@ def test_shape_list_covers_every_run_layout():
 
 
 # ---- helpers ---------------------------------------------------------------------------------------------------------------
-def _geometry(nx, ny, geom):
-    from oracle.mgoracle import seamount_geometry, rndtopo_geometry
-    return (seamount_geometry if geom == "seamount" else rndtopo_geometry)(nx, ny, 1, 1, 0)
-
-
-def _setup(mg, nx, ny, nz, geom="seamount", rmask=None, **par):
-    """one GPU instance and a one-rank oracle with the same geometry and namelist (FC)"""
-    from oracle.mgoracle import Oracle
-    kw = dict(relax_method="FC", solver_prec=1e-10, solver_maxiter=0)
-    kw.update(par)
-    bmask = bool(kw.get("bmask", 0))
-    kw["bmask"] = 1 if bmask else 0
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(**kw))
-    dx, dy, zeta, h = _geometry(nx, ny, geom)
-    mg.nhydro_matrices(dx, dy, zeta, h, rmask if bmask else None, 4e3, 0.0, 0.0)
-    kw["bmask"] = bmask
-    o = Oracle(nx, ny, nz, 1, 1, **kw)
-    for name, a in (("dx", dx), ("dy", dy), ("zeta", zeta), ("h", h)):
-        o.field(name)[...] = a
-    if bmask:
-        o.field("rmask")[...] = rmask
-    o.matrices(4e3, 0.0, 0.0)
-    return o
+def _setup(mg, nx, ny, nz, geom="seamount", bmask=False, **par):
+    """one GPU instance and a one-rank oracle with the same geometry and namelist (FC; bmask: the island mask on both)"""
+    return oracle_twin(gpu_problem(mg, (nx, ny, nz), geom=geom, bmask=bmask,
+                                   **dict(dict(relax_method="FC", solver_prec=1e-10, solver_maxiter=0), **par)))
 
 
 def _velocities(nx, ny, nz, seed, kind="random"):
@@ -113,10 +95,6 @@ def _velocities(nx, ny, nz, seed, kind="random"):
         f = amp * np.sin(2 * np.pi * i / s[2] + 0.3) * np.cos(2 * np.pi * j / s[1]) * (1.0 + 0.5 * k / s[0])
         out.append(f + 0.01 * amp * rng.standard_normal(s))
     return tuple(out)
-
-
-def _to_oracle(o, u, v, w):
-    o.field("u")[...] = u; o.field("v")[...] = v; o.field("w")[...] = w
 
 
 def _assert_uvw(u, v, w, o, what=""):
@@ -158,7 +136,7 @@ def test_compute_rhs_and_correct_uvw_run_layouts(mg, dims, geom, kind):
     print(dims, _layout(nx, ny, nz))
     o = _setup(mg, nx, ny, nz, geom)
     u, v, w = _velocities(nx, ny, nz, seed=nz + nx, kind=kind)
-    _to_oracle(o, u, v, w)
+    load_uvw(o, (u, v, w))
     mg.nhydro.compute_rhs(u, v, w)
     o.compute_rhs()
     b = mg.grid(1).b
@@ -181,7 +159,7 @@ def test_nhydro_solve_end_to_end_bench_size(mg):
     o = _setup(mg, nx, ny, nz, "seamount", solver_maxiter=1)
     u, v, w = _velocities(nx, ny, nz, seed=3)
     du, dv, dw = (torch.from_numpy(a).cuda() for a in (u, v, w))
-    _to_oracle(o, u, v, w)
+    load_uvw(o, (u, v, w))
     mg.nhydro_solve(u, v, w)
     p = mg.grid(1).p
     n, hist, _ = o.nhydro_solve()
@@ -207,7 +185,7 @@ def test_masks_multi_run_shape(mg, case):
     from mgroms_amd.testcases import island_mask
     nx, ny, nz = 512, 512, 48
     m0 = island_mask(nx, ny)
-    o = _setup(mg, nx, ny, nz, "rndtopo", rmask=m0, bmask=1)
+    o = _setup(mg, nx, ny, nz, "rndtopo", bmask=True)
     mcall = m0
     if case == "call_mask":
         mcall = m0.copy()
@@ -216,7 +194,7 @@ def test_masks_multi_run_shape(mg, case):
         o.use_call_mask(True)
     u, v, w = _velocities(nx, ny, nz, seed=17)
     dev = [torch.from_numpy(a).cuda() for a in (u, v, w)]
-    _to_oracle(o, u, v, w)
+    load_uvw(o, (u, v, w))
     mg.nhydro.compute_rhs(u, v, w, mcall)
     o.compute_rhs()
     b = mg.grid(1).b
@@ -239,12 +217,7 @@ def test_forced_run_lengths_against_the_oracle(mg, tmp_path):
     writes b and the corrected u, v, w; each is compared with the oracle.  128x64x40: 3, 7 and 13 divide neither nz nor nz + 1, and
     KR = 1 makes every row a run start."""
     nx, ny, nz = 128, 64, 40
-    from oracle.mgoracle import Oracle
-    dx, dy, zeta, h = _geometry(nx, ny, "rndtopo")
-    o = Oracle(nx, ny, nz, 1, 1, relax_method="FC", solver_prec=1e-10, solver_maxiter=0)
-    for name, a in (("dx", dx), ("dy", dy), ("zeta", zeta), ("h", h)):
-        o.field(name)[...] = a
-    o.matrices(4e3, 0.0, 0.0)
+    o = oracle_twin(problem((nx, ny, nz), geom="rndtopo", relax_method="FC", solver_prec=1e-10, solver_maxiter=0))   # (the worker's call)
     u0, v0, w0 = _velocities(nx, ny, nz, seed=23)
     layouts = set()
     for kr in (None, 1, 3, 7, 13, 1000):
@@ -261,7 +234,7 @@ def test_forced_run_lengths_against_the_oracle(mg, tmp_path):
         assert r.returncode == 0, (kr, r.stdout[-2000:], r.stderr[-2000:])
         got = {n: np.load(out_dir / (n + ".npy")) for n in ("b", "p", "u", "v", "w", "u0")}
         assert np.array_equal(got["u0"], u0)  # the worker drew the same velocities
-        _to_oracle(o, u0, v0, w0)
+        load_uvw(o, (u0, v0, w0))
         o.compute_rhs()
         assert np.array_equal(got["b"], o.field("b")), ("b", kr)
         o.field("p")[...] = got["p"]
@@ -279,24 +252,22 @@ def test_two_time_steps_with_a_moving_free_surface(mg):
     previous step corrected.  theta_s = theta_b = 0: setup_zr_zw has no transcendental function, so the coefficients are bitwise
     even with zeta /= 0, and so are b, p, u, v, w after each step -- which needs the model-space copies of zw, dzw, cw, zxdy, zydx
     rebuilt by every nhydro_matrices."""
-    from oracle.mgoracle import Oracle
     nx, ny, nz = 96, 64, 24
-    kw = dict(relax_method="FC", solver_prec=1e-12, solver_maxiter=2)
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(**kw))
-    o = Oracle(nx, ny, nz, 1, 1, **kw)
-    dx, dy, _, h0 = _geometry(nx, ny, "seamount")
+    pr = problem((nx, ny, nz), relax_method="FC", solver_prec=1e-12, solver_maxiter=2)
+    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(**pr.par))
+    o = oracle_twin(pr)
+    dx, dy, _, h0 = pr.fields
     rng = np.random.default_rng(31)
     i = np.arange(nx + 2, dtype=np.float64)[:, None]
     j = np.arange(ny + 2, dtype=np.float64)[None, :]
     u, v, w = _velocities(nx, ny, nz, seed=37)
-    _to_oracle(o, u, v, w)
+    load_uvw(o, (u, v, w))
     for step, ph in enumerate((0.0, 1.3)):
         zeta = 0.8 * np.sin(2 * np.pi * i / nx + ph) * np.cos(2 * np.pi * j / ny - ph) + 0.05 * rng.standard_normal((nx + 2, ny + 2))
         h = h0 + 20.0 * rng.standard_normal((nx + 2, ny + 2))
-        mg.nhydro_matrices(dx, dy, zeta, h, None, 4e3, 0.0, 0.0)
-        for name, a in (("dx", dx), ("dy", dy), ("zeta", zeta), ("h", h)):
-            o.field(name)[...] = a
-        o.matrices(4e3, 0.0, 0.0)
+        pr.fields = (dx, dy, zeta, h)
+        mg.nhydro_matrices(*pr.fields, None, *pr.sigma)
+        load(o, pr)
         for name in ("zw", "cw", "cA"):
             assert np.array_equal(mg.grid(1).get(name), o.field(name)), (step, name)
         mg.nhydro_solve(u, v, w)

@@ -14,36 +14,18 @@ import numpy as np
 import pytest
 
 from _gpu import gpu_module
+from _problem import gpu_problem, load_uvw, on_gpu, oracle_twin, problem, random_level, rhs, uvw
 
 pytestmark = pytest.mark.gpu
 mg = gpu_module()
 
 
 def _setup(mg, nx, ny, nz, geom="seamount", **par):
-    from oracle.mgoracle import Oracle, seamount_geometry, rndtopo_geometry
-    kw = dict(relax_method="FC", solver_prec=1e-10)
-    kw.update(par)
-    p = mg.nhydro.default_params(**kw)
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, p)
-    g = seamount_geometry if geom == "seamount" else rndtopo_geometry
-    dx, dy, zeta, h = g(nx, ny, 1, 1, 0)
-    mg.nhydro_matrices(dx, dy, zeta, h, None, 4e3, 0.0, 0.0)
-    okw = {k: v for k, v in kw.items()}
-    o = Oracle(nx, ny, nz, 1, 1, **okw)
-    for name, a in (("dx", dx), ("dy", dy), ("zeta", zeta), ("h", h)):
-        o.field(name)[...] = a
-    o.matrices(4e3, 0.0, 0.0)
-    return o
+    return oracle_twin(gpu_problem(mg, (nx, ny, nz), geom=geom, **dict(dict(relax_method="FC", solver_prec=1e-10), **par)))
 
 
 def _uvw(nx, ny, nz, seed=None):
-    if seed is None:
-        from mgroms_amd.testcases import resting_column_state
-        u, v, w = resting_column_state(nx, ny, nz)
-    else:
-        r = np.random.default_rng(seed)
-        u = r.uniform(-1, 1, (nz, ny + 2, nx + 1)); v = r.uniform(-1, 1, (nz, ny + 1, nx + 2)); w = r.uniform(-1, 1, (nz + 1, ny + 2, nx + 2))
-    return u, v, w
+    return uvw((nx, ny, nz), seed)
 
 
 @pytest.mark.parametrize("dims,geom", [((16, 16, 8), "seamount"), ((64, 32, 16), "seamount"), ((32, 32, 8), "rndtopo")])
@@ -118,10 +100,7 @@ def test_relax_fc_bitwise(mg, cmatrix):
     o = _setup(mg, nx, ny, nz, cmatrix=cmatrix)
     r = np.random.default_rng(2)
     for lev in (1, 2, o.nlevs):
-        g = mg.grid(lev)
-        p = r.standard_normal(g._shape("p")); b = r.standard_normal(g._shape("b"))
-        g.set("p", p); g.set("b", b); mg.fill_halo(lev, "p")
-        o.field("p", lev)[...] = p; o.field("b", lev)[...] = b; o.fill_halo(lev, "p")
+        g = random_level(mg, o, lev, r)
         mg.relax(lev, 2)
         o.relax(lev, 2)
         assert np.array_equal(g.get("p"), o.field("p", lev)), lev
@@ -133,10 +112,7 @@ def test_relax_rb_simple_bitwise(mg):
     o = _setup(mg, nx, ny, nz, relax_method="RB", cmatrix="simple")
     r = np.random.default_rng(4)
     for lev in (1, 2, o.nlevs):
-        g = mg.grid(lev)
-        p = r.standard_normal(g._shape("p")); b = r.standard_normal(g._shape("b"))
-        g.set("p", p); g.set("b", b); mg.fill_halo(lev, "p")
-        o.field("p", lev)[...] = p; o.field("b", lev)[...] = b; o.fill_halo(lev, "p")
+        g = random_level(mg, o, lev, r)
         mg.relax(lev, 2)
         o.relax(lev, 2)
         assert np.array_equal(g.get("p"), o.field("p", lev)), lev
@@ -203,10 +179,7 @@ def test_relax_rb_sequential_order_at_speed(mg, dims, geom):
     assert mg.nhydro.get_option("rb_seq") == 1
     rng = np.random.default_rng(31)
     for lev in range(1, o.nlevs + 1):
-        g = mg.grid(lev)
-        p = rng.standard_normal(g._shape("p")); b = rng.standard_normal(g._shape("b"))
-        g.set("p", p); g.set("b", b); mg.fill_halo(lev, "p")
-        o.field("p", lev)[...] = p; o.field("b", lev)[...] = b; o.fill_halo(lev, "p")
+        g = random_level(mg, o, lev, rng)
         mg.relax(lev, 3); o.relax(lev, 3)
         a, c = g.get("p"), o.field("p", lev)
         assert np.abs(a - c).max() <= 1e-12 * np.abs(c).max(), (lev, np.abs(a - c).max() / np.abs(c).max())
@@ -418,17 +391,13 @@ def test_rb_windowed_walk_stops_where_the_correction_has_decayed(mg, dims):
     column, and the windowed walk's correction neither reads nor writes the rows above (mgx_rbseq_window_rows < nz, checked against the same figure
     from the oracle's coefficients).  Three sweeps from a rough random state on level 1 against the oracle's sequential loop (1e-12) and against every
     row corrected (1e-14); nz = 128: the colour pass (k_relax_tall) leaves no d0, k_rbseq_d0 runs in front of the window launch."""
-    from oracle.mgoracle import Oracle, seamount_geometry
     nx, ny, nz = dims
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(relax_method="RB"))
-    dx, dy, zeta, h = seamount_geometry(nx, ny, 1, 1, 0)
+    pr = problem(dims, relax_method="RB")
+    dx, dy, zeta, h = pr.fields
     dx = dx * (19.5 / dx.max()); dy = dy * (19.5 / dy.max())
     h = 4e3 - 0.01 * (4e3 - h)     # ... and the mount flattened with it (the slopes of the real grid, not of a 2 km mount across 300 m)
-    mg.nhydro_matrices(dx, dy, zeta, h, None, 4e3, 0.0, 0.0)
-    o = Oracle(nx, ny, nz, 1, 1, relax_method="RB")
-    for name, a in (("dx", dx), ("dy", dy), ("zeta", zeta), ("h", h)):
-        o.field(name)[...] = a
-    o.matrices(4e3, 0.0, 0.0)
+    pr.fields = (dx, dy, zeta, h)
+    o = oracle_twin(on_gpu(mg, pr))
     cA = o.field("cA", 1)[1:-1, 1:-1]
     d, dd = cA[..., 0], cA[..., 1]
     bet = 1.0 / d[..., 0]; x = np.zeros_like(d); gam = np.zeros_like(d); x[..., 0] = bet
@@ -477,10 +446,7 @@ def test_rb_sequential_order_window_refused_when_the_walk_contracts_slowly(mg):
     rho, m = mg.nhydro.rbseq_window_info(1)
     assert abs(rho - 0.6) < 1e-9 and m == 0, (rho, m)
     rng = np.random.default_rng(53)
-    g = mg.grid(1)
-    p = rng.standard_normal(g._shape("p")); b = rng.standard_normal(g._shape("b"))
-    g.set("p", p); g.set("b", b); mg.fill_halo(1, "p")
-    o.field("p")[...] = p; o.field("b")[...] = b; o.fill_halo(1, "p")
+    g = random_level(mg, o, 1, rng)
     n0 = mg.nhydro.get_option("rbseq_window_colours")
     mg.relax(1, 2); o.relax(1, 2)
     assert mg.nhydro.get_option("rbseq_window_colours") == n0
@@ -568,31 +534,18 @@ def test_rb_sequential_order_other_coefficient_paths(mg, case):
     ones: the masked system (bmask: stored coefficients, no in-kernel rebuild), nz = 128 (k_relax_tall with the snapshot), a stretched sigma
     coordinate with a moving free surface, and a matrix handed in through set_field('cA') (g = T^-1 e1 is rebuilt with the pivots).  Three
     sweeps per level from a rough random state against the oracle's sequential loop: 1e-12 of max|p|."""
-    from oracle.mgoracle import Oracle, seamount_geometry
-    from mgroms_amd.testcases import island_mask
     nx, ny, nz = (16, 32, 128) if case == "tall" else (32, 64, 16)
-    kw = dict(relax_method="RB", bmask=(1 if case == "bmask" else 0))
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(**kw))
-    dx, dy, zeta, h = seamount_geometry(nx, ny, 1, 1, 0)
-    hc, tb, ts = 4e3, 0.0, 0.0
+    zeta, sigma = None, (4e3, 0.0, 0.0)
     if case == "stretched":
         ii, jj = np.meshgrid(np.arange(nx + 2), np.arange(ny + 2), indexing="ij")
-        zeta = 0.4 * np.cos(0.25 * ii) * np.sin(0.15 * jj); hc, tb, ts = 250.0, 0.4, 6.0
-    rmask = island_mask(nx, ny) if case == "bmask" else None
-    mg.nhydro_matrices(dx, dy, zeta, h, rmask, hc, tb, ts)
-    o = Oracle(nx, ny, nz, 1, 1, relax_method="RB", bmask=(case == "bmask"))
-    for name, a in (("dx", dx), ("dy", dy), ("zeta", zeta), ("h", h)) + ((("rmask", rmask),) if case == "bmask" else ()):
-        o.field(name)[...] = a
-    o.matrices(hc, tb, ts)
+        zeta = 0.4 * np.cos(0.25 * ii) * np.sin(0.15 * jj); sigma = (250.0, 0.4, 6.0)
+    o = oracle_twin(gpu_problem(mg, (nx, ny, nz), bmask=(case == "bmask"), zeta=zeta, sigma=sigma, relax_method="RB"))
     if case == "user_matrix":   # the same coefficients, but through the stored-slot path of a user-supplied matrix
         for lev in range(1, o.nlevs + 1):
             mg.grid(lev).set("cA", o.field("cA", lev))
     rng = np.random.default_rng(41)
     for lev in range(1, o.nlevs + 1):
-        g = mg.grid(lev)
-        p = rng.standard_normal(g._shape("p")); b = rng.standard_normal(g._shape("b"))
-        g.set("p", p); g.set("b", b); mg.fill_halo(lev, "p")
-        o.field("p", lev)[...] = p; o.field("b", lev)[...] = b; o.fill_halo(lev, "p")
+        g = random_level(mg, o, lev, rng)
         mg.relax(lev, 3); o.relax(lev, 3)
         a, c = g.get("p"), o.field("p", lev)
         tol = 1e-12 if case != "stretched" else 1e-10   # the device's cosh / exp differ from libm's in the last bits of zr, zw (section 2)
@@ -677,18 +630,10 @@ def test_bmask_bitwise(mg, dims, geom):
     oracle's bmask branch is itself unpinned: this test proves GPU == restatement.  That the masked matrix is the
     divergence of the masked gradient on water-interior columns is held separately, without the oracle
     (tests/test_gpu_operator_identity.py); coast columns, the smoother and the coarse levels of this branch have this test only."""
-    from oracle.mgoracle import Oracle, seamount_geometry, rndtopo_geometry
-    from mgroms_amd.testcases import island_mask
     nx, ny, nz = dims
-    kw = dict(relax_method="FC", solver_prec=1e-9, solver_maxiter=6)
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(bmask=1, **kw))
-    dx, dy, zeta, h = (seamount_geometry if geom == "seamount" else rndtopo_geometry)(nx, ny, 1, 1, 0)
-    rmask = island_mask(nx, ny)
-    mg.nhydro_matrices(dx, dy, zeta, h, rmask, 4e3, 0.0, 0.0)
-    o = Oracle(nx, ny, nz, 1, 1, bmask=True, **kw)
-    for name, a in (("dx", dx), ("dy", dy), ("zeta", zeta), ("h", h), ("rmask", rmask)):
-        o.field(name)[...] = a
-    o.matrices(4e3, 0.0, 0.0)
+    pr = gpu_problem(mg, dims, geom=geom, bmask=True, relax_method="FC", solver_prec=1e-9, solver_maxiter=6)
+    (dx, dy, zeta, h), rmask = pr.fields, pr.rmask
+    o = oracle_twin(pr)
     for lev in range(1, o.nlevs + 1):
         g = mg.grid(lev)
         for name in ("rmask", "cw", "cA"):
@@ -766,10 +711,7 @@ def test_ragged_and_minimum_sizes(mg):
     # (256,128,8): coarsest level 64x32x2 = the gathered coarsest grid of an 8-GPU run (one 1024-thread launch)
     for dims in ((4, 4, 2), (8, 16, 4), (128, 32, 8), (256, 128, 8)):
         o = _setup(mg, *dims)
-        u, v, w = _uvw(*dims)
-        mg.nhydro.compute_rhs(u, v, w)
-        o.field("w")[...] = w
-        o.compute_rhs()
+        rhs(mg, o, _uvw(*dims))
         n, hist = mg.solve_p(1e-8, 5)
         no, ho, _ = o.solve_p(1e-8, 5)
         assert n == no
@@ -798,16 +740,10 @@ def test_gauss_seidel_exact(mg):
     # relax_method='GS' (mg_relax.f90:116-148): lexicographic order reproduced exactly by hyperplane launches
     o = _setup(mg, 32, 16, 8, relax_method="GS", solver_prec=1e-8)
     r = np.random.default_rng(7)
-    g = mg.grid(1)
-    p = r.standard_normal(g._shape("p")); b = r.standard_normal(g._shape("b"))
-    g.set("p", p); g.set("b", b); mg.fill_halo(1, "p")
-    o.field("p")[...] = p; o.field("b")[...] = b; o.fill_halo(1, "p")
+    g = random_level(mg, o, 1, r)
     mg.relax(1, 2); o.relax(1, 2)
     assert np.array_equal(g.get("p"), o.field("p"))
-    u, v, w = _uvw(32, 16, 8)
-    mg.nhydro.compute_rhs(u, v, w)
-    o.field("w")[...] = w
-    o.compute_rhs()
+    rhs(mg, o, _uvw(32, 16, 8))
     n, hist = mg.solve_p(1e-8, 6)
     no, ho, _ = o.solve_p(1e-8, 6)
     assert n == no and np.array_equal(mg.grid(1).p, o.field("p"))
@@ -819,10 +755,7 @@ def test_tall_columns(mg, method):
     # way back) and, once the matrix is user-supplied (stored slots), the generic colour pass
     o = _setup(mg, 16, 32, 128, relax_method=method, cmatrix="simple" if method == "RB" else "real")
     assert mg.grid(1).nz == 128
-    u, v, w = _uvw(16, 32, 128)
-    mg.nhydro.compute_rhs(u, v, w)
-    o.field("w")[...] = w
-    o.compute_rhs()
+    rhs(mg, o, _uvw(16, 32, 128))
     n, hist = mg.solve_p(1e-8, 4)
     no, ho, _ = o.solve_p(1e-8, 4)
     assert n == no and np.array_equal(mg.grid(1).p, o.field("p"))  # RB with cmatrix='simple' is order independent too
@@ -839,24 +772,14 @@ def test_tall_columns(mg, method):
 def test_stretched_sigma_coordinates(mg):
     # theta_s, theta_b > 0 exercise cosh/exp in setup_zr_zw (mg_zr_zw.f90:112-136): device libm vs host libm may
     # differ in the last bit, so this one case is compared at 1e-12 instead of bit for bit
-    from oracle.mgoracle import Oracle, seamount_geometry
     nx, ny, nz = 32, 32, 16
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(relax_method="FC", solver_prec=1e-9))
-    dx, dy, zeta, h = seamount_geometry(nx, ny, 1, 1, 0)
     zeta = 0.3 * np.cos(np.arange(nx + 2))[:, None] * np.ones((1, ny + 2))  # non-zero free surface
-    mg.nhydro_matrices(dx, dy, zeta, h, None, 250.0, 0.4, 6.0)
-    o = Oracle(nx, ny, nz, relax_method="FC", solver_prec=1e-9)
-    for name, a in (("dx", dx), ("dy", dy), ("zeta", zeta), ("h", h)):
-        o.field(name)[...] = a
-    o.matrices(250.0, 0.4, 6.0)
+    o = oracle_twin(gpu_problem(mg, (nx, ny, nz), zeta=zeta, sigma=(250.0, 0.4, 6.0), relax_method="FC", solver_prec=1e-9))
     for lev in range(1, o.nlevs + 1):
         for name in ("zr", "zw", "cA"):
             a, b = mg.grid(lev).get(name), o.field(name, lev)
             assert np.allclose(a, b, rtol=1e-12, atol=1e-12 * np.abs(b).max()), (lev, name)
-    u, v, w = _uvw(nx, ny, nz)
-    mg.nhydro.compute_rhs(u, v, w)
-    o.field("w")[...] = w
-    o.compute_rhs()
+    rhs(mg, o, _uvw(nx, ny, nz))
     n, hist = mg.solve_p(1e-9, 50)
     no, ho, _ = o.solve_p(1e-9, 50)
     # here the coefficients themselves differ in the last bits (device cosh / exp): north_star's bound, not the reduction-order one
@@ -1003,16 +926,10 @@ def test_fortran_harness_bmask(mg, tmp_path):
     out = subprocess.run([exe, "32", "48", "8"], cwd=tmp_path, capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "- bmask         : T" in out.stdout
-    from oracle.mgoracle import Oracle, seamount_geometry
     nx, ny, nz = 32, 48, 8
-    o = Oracle(nx, ny, nz, 1, 1, relax_method="FC", solver_prec=1e-9, bmask=True)
-    for name, a in zip(("dx", "dy", "zeta", "h"), seamount_geometry(nx, ny, 1, 1, 0)):
-        o.field(name)[...] = a
     m = np.ones((nx + 2, ny + 2)); m[0, :] = m[-1, :] = 0.0; m[:, 0] = m[:, -1] = 0.0
-    o.field("rmask")[...] = m
-    o.matrices(4e3, 0.0, 0.0)
-    o.field("u")[...] = 0.0; o.field("v")[...] = 0.0
-    w = o.field("w"); w[0] = 0.0; w[1:] = -1.0
+    o = oracle_twin(problem((nx, ny, nz), bmask=True, rmask=m, relax_method="FC", solver_prec=1e-9))
+    load_uvw(o, uvw((nx, ny, nz)))
     n, h, _ = o.nhydro_solve()
     its = re.findall(r"ite = *(\d+): res = *([0-9.E+-]+) / conv", out.stdout)
     assert len(its) == n
@@ -1186,10 +1103,7 @@ def test_full_size_properties(mg, golden):
     """BASELINE config 3 (512x512x64, FC): first five residuals against the reference's printed digits, plus
     size-independent properties: restriction of a constant, and linearity of the residual in p."""
     nx, ny, nz = 512, 512, 64
-    from oracle.mgoracle import seamount_geometry
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(relax_method="FC", solver_maxiter=5))
-    dx, dy, zeta, h = seamount_geometry(nx, ny, 1, 1, 0)
-    mg.nhydro_matrices(dx, dy, zeta, h, None, 4e3, 0.0, 0.0)
+    gpu_problem(mg, (nx, ny, nz), relax_method="FC", solver_maxiter=5)
     u, v, w = _uvw(nx, ny, nz)
     mg.nhydro.compute_rhs(u, v, w)
     n, hist = mg.solve_p(1e-12, 5)
@@ -1212,10 +1126,7 @@ def test_full_size_properties(mg, golden):
 def test_vcycle2_and_fcycle_ops(mg):
     # Vcycle2(lev1,lev2) (mg_solvers.f90:155-177) with lev2 = nlevs is Vcycle(lev1); Fcycle against the oracle
     o = _setup(mg, 32, 32, 16)
-    u, v, w = _uvw(32, 32, 16)
-    mg.nhydro.compute_rhs(u, v, w)
-    o.field("w")[...] = w
-    o.compute_rhs()
+    rhs(mg, o, _uvw(32, 32, 16))
     mg.Vcycle2(1, mg.nlevs()); o.vcycle(1)
     assert np.array_equal(mg.grid(1).p, o.field("p"))
     # Fcycle starts by restricting grid(1)%r (mg_solvers.f90:110-114): solve_p computes the residual first (:50), so does this test
@@ -1265,10 +1176,7 @@ def test_cycle_keeps_the_dead_r_on_request(mg):
     # coarse2fine leaves the interpolated correction in the fine r (mg_intergrids.f90:218-226); nothing reads it before the next
     # compute_residual, so the cycles skip that store unless "keep_r" (or "exact_halos") asks for the reference's state
     o = _setup(mg, 32, 32, 16)
-    u, v, w = _uvw(32, 32, 16)
-    mg.nhydro.compute_rhs(u, v, w)
-    o.field("w")[...] = w
-    o.compute_rhs()
+    rhs(mg, o, _uvw(32, 32, 16))
     mg.nhydro.set_option("keep_r", 1)
     try:
         mg.Vcycle(1); o.vcycle(1)

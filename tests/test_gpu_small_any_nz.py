@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from _gpu import gpu_module
+from _problem import gpu_problem, hist_close, oracle_twin, rhs, uvw
 from _ranks import free_port, run_process_ranks
 
 pytestmark = pytest.mark.gpu
@@ -68,45 +69,17 @@ def _served(dims, mode="FC"):
 
 def _setup(mg, dims, bmask=False, oracle=False, periodic=0, **par):
     """the seamount problem of `dims` (held where LEVELS says so); oracle: also on the CPU oracle (hierarchies without a held pair)"""
-    from oracle.mgoracle import Oracle, seamount_geometry
-    from mgroms_amd.testcases import island_mask
-    nx, ny, nz = dims
     hold = LEVELS[dims][0]
-    mg.nhydro_clean()
-    mg.nhydro.set_option("hold_odd_nz", hold)
-    mg.nhydro.set_option("periodic", periodic)
-    kw = dict(relax_method="FC", solver_prec=1e-10)
-    kw.update(par)
-    if bmask:
-        kw["bmask"] = 1
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(**kw))
-    dx, dy, zeta, h = seamount_geometry(nx, ny, 1, 1, 0)
-    rmask = island_mask(nx, ny) if bmask else None
-    mg.nhydro_matrices(dx, dy, zeta, h, rmask, HC, 0.0, 0.0)
+    pr = gpu_problem(mg, dims, bmask=bmask, sigma=(HC, 0.0, 0.0), init_options=dict(hold_odd_nz=hold, periodic=periodic),
+                     **dict(dict(relax_method="FC", solver_prec=1e-10), **par))
     got = [(mg.grid(l).nx, mg.grid(l).ny, mg.grid(l).nz) for l in range(1, mg.nlevs() + 1)]
     assert got == LEVELS[dims][1], got
     if not oracle:
         return None
     assert not hold
-    okw = dict(kw)
-    if bmask:
-        okw["bmask"] = True
-    o = Oracle(nx, ny, nz, 1, 1, **okw)
-    for name, a in (("dx", dx), ("dy", dy), ("zeta", zeta), ("h", h)):
-        o.field(name)[...] = a
-    if bmask:
-        o.field("rmask")[...] = rmask
-    o.matrices(HC, 0.0, 0.0)
+    o = oracle_twin(pr)
     assert o.nlevs == len(got)
     return o
-
-
-def _uvw(nx, ny, nz, seed=None):
-    if seed is None:
-        from mgroms_amd.testcases import resting_column_state
-        return resting_column_state(nx, ny, nz)
-    r = np.random.default_rng(seed)
-    return r.uniform(-1, 1, (nz, ny + 2, nx + 1)), r.uniform(-1, 1, (nz, ny + 1, nx + 2)), r.uniform(-1, 1, (nz + 1, ny + 2, nx + 2))
 
 
 def _calls(mg):
@@ -229,22 +202,14 @@ def test_declined_level_moves_nothing(mg, case):
 
 
 # ---- 3. solves -------------------------------------------------------------------------------------------------------------------------
-def _hist_close(h, ho, tol=1e-12):
-    return len(h) == len(ho) and np.all(np.abs(h - ho) <= 1e-13 + tol * np.abs(ho))
-
-
 def _solve3(mg, dims, small, oracle=False, **par):
     o = _setup(mg, dims, oracle=oracle, **par)
     mg.nhydro.set_option("small_any_nz", small)
-    u, v, w = _uvw(*dims)
-    mg.nhydro.compute_rhs(u, v, w)
+    rhs(mg, o, uvw(dims))
     l0, c0 = _launches(mg), _calls(mg)
     n, hist = mg.solve_p(1e-30, 3)
     out = dict(n=n, hist=hist, launches=_launches(mg) - l0, calls=_calls(mg) - c0,
                p=[mg.grid(l).get("p") for l in range(1, mg.nlevs() + 1)], b=[mg.grid(l).get("b") for l in range(1, mg.nlevs() + 1)])
-    if o is not None:
-        o.field("w")[...] = w
-        o.compute_rhs()
     return out, o
 
 
@@ -255,7 +220,7 @@ def test_fc_solve_bitwise(mg, dims):
     try:
         s0, _ = _solve3(mg, dims, 0)
         s1, o = _solve3(mg, dims, 1, oracle=not LEVELS[dims][0])
-        assert s0["n"] == s1["n"] == 3 and _hist_close(s1["hist"], s0["hist"]), (s1["hist"], s0["hist"])
+        assert s0["n"] == s1["n"] == 3 and hist_close(s1["hist"], s0["hist"], rtol=1e-12, atol=1e-13, same_length=True), (s1["hist"], s0["hist"])
         for lev, (a, c) in enumerate(zip(s1["p"], s0["p"]), 1):
             assert np.array_equal(a, c), (lev, "p", np.abs(a - c).max())
         for lev, (a, c) in enumerate(zip(s1["b"], s0["b"]), 1):
@@ -264,7 +229,7 @@ def test_fc_solve_bitwise(mg, dims):
         assert s0["calls"] == 0 and s1["calls"] > 0 and s1["launches"] < s0["launches"]
         if o is not None:
             no, ho, _ = o.solve_p(1e-30, 3)
-            assert no == 3 and _hist_close(s1["hist"], ho), (s1["hist"], ho)
+            assert no == 3 and hist_close(s1["hist"], ho, rtol=1e-12, atol=1e-13, same_length=True), (s1["hist"], ho)
             for lev in range(1, o.nlevs + 1):
                 for name in ("p", "b"):
                     a, c = s1[name][lev - 1], o.field(name, lev)
@@ -279,7 +244,7 @@ def test_rb_default_solve(mg):
     try:
         s0, _ = _solve3(mg, (64, 64, 12), 0, relax_method="RB")
         s1, _ = _solve3(mg, (64, 64, 12), 1, relax_method="RB")
-        assert s0["n"] == s1["n"] == 3 and _hist_close(s1["hist"], s0["hist"], 1e-10), (s1["hist"], s0["hist"])
+        assert s0["n"] == s1["n"] == 3 and hist_close(s1["hist"], s0["hist"], rtol=1e-10, atol=1e-13, same_length=True), (s1["hist"], s0["hist"])
         err = np.abs(s1["p"][0] - s0["p"][0]).max() / np.abs(s0["p"][0]).max()
         print(f"red-black default, 64x64x12, three iterations: p {err:.3e} of max|p| from option 0; launches {s0['launches']} -> {s1['launches']}")
         assert err <= 1e-10
@@ -296,7 +261,7 @@ def test_nhydro_solve_bitwise(mg):
         for small in (0, 1):
             _setup(mg, dims, solver_maxiter=8)
             mg.nhydro.set_option("small_any_nz", small)
-            u, v, w = _uvw(*dims, seed=17)
+            u, v, w = uvw(dims, seed=17)
             c0 = _calls(mg)
             mg.nhydro_solve(u, v, w)
             out.append((u, v, w, mg.grid(1).p, _calls(mg) - c0))
@@ -312,7 +277,7 @@ def _vcycle_rb(mg, small, direct):
     dims = (64, 64, 12)
     _setup(mg, dims, relax_method="RB")
     mg.nhydro.set_option("small_any_nz", small); mg.nhydro.set_option("coarsest_direct", direct)
-    mg.nhydro.compute_rhs(*_uvw(*dims))
+    rhs(mg, None, uvw(dims))
     d0 = mg.nhydro.get_option("coarsest_direct_solves")
     mg.nhydro.Vcycle(1)
     return mg.grid(1).get("p"), mg.nhydro.get_option("coarsest_direct_solves") - d0
@@ -344,7 +309,7 @@ def test_toggling_rebuilds_the_operator(mg):
         mg.nhydro.set_option("small_any_nz", small)
         g = mg.grid(1)
         g.set("p", np.zeros(g._shape("p")))
-        mg.nhydro.compute_rhs(*_uvw(*dims))
+        rhs(mg, None, uvw(dims))
         d0 = mg.nhydro.get_option("coarsest_direct_solves")
         n, hist = mg.solve_p(1e-30, 2)
         return g.get("p"), hist, mg.nhydro.get_option("coarsest_direct_solves") - d0

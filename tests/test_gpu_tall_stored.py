@@ -25,6 +25,7 @@ import numpy as np
 import pytest
 
 from _gpu import gpu_module
+from _problem import on_gpu, oracle_twin, problem, rhs, uvw
 
 gpu = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -40,27 +41,14 @@ def _ids(cases):
     return ["x".join(str(d) for d in c[:3]) + "".join("-" + s for s in c[3:]) for c in cases]
 
 
-def _params(nx, ny, nz, method, cmatrix, bmask):
-    kw = dict(relax_method=method, cmatrix=cmatrix, solver_prec=1e-10)
-    if bmask:
-        kw["bmask"] = 1
-    return kw
+@functools.lru_cache(maxsize=None)
+def _case(nx, ny, nz, method="FC", cmatrix="real", bmask=True):
+    """the record of a seamount case: what _gpu_setup() hands to the GPU and _oracle() to the oracle"""
+    return problem((nx, ny, nz), bmask=bmask, relax_method=method, cmatrix=cmatrix, solver_prec=1e-10)
 
 
-def _oracle(nx, ny, nz, method="FC", cmatrix="real", bmask=True):
-    from oracle.mgoracle import Oracle, seamount_geometry
-    from mgroms_amd.testcases import island_mask
-    kw = _params(nx, ny, nz, method, cmatrix, bmask)
-    if bmask:
-        kw["bmask"] = True
-    o = Oracle(nx, ny, nz, 1, 1, **kw)
-    dx, dy, zeta, h = seamount_geometry(nx, ny, 1, 1, 0)
-    for name, a in (("dx", dx), ("dy", dy), ("zeta", zeta), ("h", h)):
-        o.field(name)[...] = a
-    if bmask:
-        o.field("rmask")[...] = island_mask(nx, ny)
-    o.matrices(4e3, 0.0, 0.0)
-    return o
+def _oracle(*case, **kw):
+    return oracle_twin(_case(*case, **kw))
 
 
 def _user_matrix(cA):
@@ -104,9 +92,7 @@ def _fc_reference(case):
 def _solve_reference(dims):
     nx, ny, nz = dims
     o = _oracle(nx, ny, nz, "FC", "real", bmask=True)
-    w = -np.ones((nz + 1, ny + 2, nx + 2)); w[0] = 0
-    o.field("w")[...] = w
-    o.compute_rhs()
+    rhs(None, o, uvw(dims))
     n, hist, _ = o.solve_p(1e-30, 3)
     p = o.field("p").copy(); p.setflags(write=False)
     return dict(n=n, hist=hist, p=p)
@@ -132,10 +118,8 @@ def test_oracle_masked_tall_solve_contracts(dims):
 mg = gpu_module(rb_exact=0)
 
 
-def _gpu_setup(mg, nx, ny, nz, method="FC", cmatrix="real", bmask=True):
-    from mgroms_amd.testcases import island_mask, seamount_geometry
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(**_params(nx, ny, nz, method, cmatrix, bmask)))
-    mg.nhydro_matrices(*seamount_geometry(nx, ny, 1, 1, 0), island_mask(nx, ny) if bmask else None, 4e3, 0.0, 0.0)
+def _gpu_setup(mg, *case, **kw):
+    on_gpu(mg, _case(*case, **kw))
 
 
 def _passes(mg):

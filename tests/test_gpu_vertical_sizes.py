@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from _gpu import gpu_module
+from _problem import gpu_problem, hist_close, oracle_twin, random_level, rhs, uvw
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -22,55 +23,7 @@ mg = gpu_module(rb_exact=0)
 
 def _setup(mg, nx, ny, nz, bmask=False, **par):
     """the seamount problem on the GPU and on the oracle (bmask: the island mask on both)"""
-    from oracle.mgoracle import Oracle, seamount_geometry
-    from mgroms_amd.testcases import island_mask
-    kw = dict(relax_method="FC", solver_prec=1e-10)
-    kw.update(par)
-    if bmask:
-        kw["bmask"] = 1
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(**kw))
-    dx, dy, zeta, h = seamount_geometry(nx, ny, 1, 1, 0)
-    rmask = island_mask(nx, ny) if bmask else None
-    mg.nhydro_matrices(dx, dy, zeta, h, rmask, 4e3, 0.0, 0.0)
-    okw = dict(kw)
-    if bmask:
-        okw["bmask"] = True
-    o = Oracle(nx, ny, nz, 1, 1, **okw)
-    for name, a in (("dx", dx), ("dy", dy), ("zeta", zeta), ("h", h)):
-        o.field(name)[...] = a
-    if bmask:
-        o.field("rmask")[...] = rmask
-    o.matrices(4e3, 0.0, 0.0)
-    return o
-
-
-def _uvw(nx, ny, nz, seed=None):
-    if seed is None:
-        from mgroms_amd.testcases import resting_column_state
-        u, v, w = resting_column_state(nx, ny, nz)
-    else:
-        r = np.random.default_rng(seed)
-        u = r.uniform(-1, 1, (nz, ny + 2, nx + 1)); v = r.uniform(-1, 1, (nz, ny + 1, nx + 2)); w = r.uniform(-1, 1, (nz + 1, ny + 2, nx + 2))
-    return u, v, w
-
-
-def _rhs(mg, o, nx, ny, nz):
-    u, v, w = _uvw(nx, ny, nz)
-    mg.nhydro.compute_rhs(u, v, w)
-    o.field("w")[...] = w
-    o.compute_rhs()
-
-
-def _hist_close(h, ho):
-    return len(h) == len(ho) and np.all(np.abs(h - ho) <= 1e-13 + 1e-12 * np.abs(ho))
-
-
-def _random_level(mg, o, lev, rng):
-    g = mg.grid(lev)
-    p = rng.standard_normal(g._shape("p")); b = rng.standard_normal(g._shape("b"))
-    g.set("p", p); g.set("b", b); mg.fill_halo(lev, "p")
-    o.field("p", lev)[...] = p; o.field("b", lev)[...] = b; o.fill_halo(lev, "p")
-    return g
+    return oracle_twin(gpu_problem(mg, (nx, ny, nz), bmask=bmask, **dict(dict(relax_method="FC", solver_prec=1e-10), **par)))
 
 
 # ---- four colours ----------------------------------------------------------------------------------------------------
@@ -81,10 +34,10 @@ def test_fc_solve_bitwise(mg, dims):
     nx, ny, nz = dims
     o = _setup(mg, nx, ny, nz)
     assert mg.nlevs() == o.nlevs
-    _rhs(mg, o, nx, ny, nz)
+    rhs(mg, o, uvw(dims))
     n, hist = mg.solve_p(1e-30, 3)
     no, ho, _ = o.solve_p(1e-30, 3)
-    assert n == no == 3 and _hist_close(hist, ho), (hist, ho)
+    assert n == no == 3 and hist_close(hist, ho, rtol=1e-12, atol=1e-13, same_length=True), (hist, ho)
     for lev in range(1, o.nlevs + 1):
         g = mg.grid(lev)
         for name in ("p", "b"):
@@ -95,7 +48,7 @@ def test_fc_solve_bitwise(mg, dims):
         assert np.array_equal(a, c), (lev, "r", np.abs(a - c).max())
     # the whole nhydro_solve from a rough state
     o = _setup(mg, nx, ny, nz, solver_maxiter=8)
-    u, v, w = _uvw(nx, ny, nz, seed=17)
+    u, v, w = uvw(dims, seed=17)
     o.field("u")[...] = u; o.field("v")[...] = v; o.field("w")[...] = w
     mg.nhydro_solve(u, v, w)
     o.nhydro_solve()
@@ -107,7 +60,7 @@ def test_fc_solve_bitwise(mg, dims):
 def test_fc_relax_bench_scale(mg, nz):
     """one level-1 four-colour relax at the bench's plane size (512 x 512), bit for bit"""
     o = _setup(mg, 512, 512, nz)
-    g = _random_level(mg, o, 1, np.random.default_rng(nz))
+    g = random_level(mg, o, 1, np.random.default_rng(nz))
     mg.relax(1, 1); o.relax(1, 1)
     assert np.array_equal(g.get("p"), o.field("p"))
 
@@ -123,7 +76,7 @@ def test_rb_default_relax_every_level(mg, dims, bmask):
     assert mg.nhydro.get_option("rb_seq") == 1 and mg.nhydro.get_option("rb_exact") == 0
     rng = np.random.default_rng(41)
     for lev in range(1, o.nlevs + 1):
-        g = _random_level(mg, o, lev, rng)
+        g = random_level(mg, o, lev, rng)
         mg.relax(lev, 1); o.relax(lev, 1)
         a, c = g.get("p"), o.field("p", lev)
         assert np.abs(a - c).max() <= 1e-12 * np.abs(c).max(), (lev, np.abs(a - c).max() / np.abs(c).max())
@@ -136,7 +89,7 @@ def test_rb_exact_tall_bmask(mg):
         o = _setup(mg, 32, 32, 128, bmask=True, relax_method="RB")
         rng = np.random.default_rng(43)
         for lev in range(1, o.nlevs + 1):
-            g = _random_level(mg, o, lev, rng)
+            g = random_level(mg, o, lev, rng)
             mg.relax(lev, 1); o.relax(lev, 1)
             assert np.array_equal(g.get("p"), o.field("p", lev)), lev
     finally:
@@ -152,22 +105,20 @@ def test_gauss_seidel_any_nz(mg, dims):
     o = _setup(mg, nx, ny, nz, relax_method="GS")
     rng = np.random.default_rng(7)
     for lev in range(1, o.nlevs + 1):
-        g = _random_level(mg, o, lev, rng)
+        g = random_level(mg, o, lev, rng)
         mg.relax(lev, 2); o.relax(lev, 2)
         assert np.array_equal(g.get("p"), o.field("p", lev)), lev
     o = _setup(mg, nx, ny, nz, relax_method="GS")
-    _rhs(mg, o, nx, ny, nz)
+    rhs(mg, o, uvw(dims))
     n, hist = mg.solve_p(1e-30, 3)
     no, ho, _ = o.solve_p(1e-30, 3)
-    assert n == no == 3 and _hist_close(hist, ho), (hist, ho)
+    assert n == no == 3 and hist_close(hist, ho, rtol=1e-12, atol=1e-13, same_length=True), (hist, ho)
     assert np.array_equal(mg.grid(1).p, o.field("p"))
 
 
 # ---- kernel selection ----------------------------------------------------------------------------------------------------
 def _relax_launches(mg, nx, ny, nz, method):
-    from mgroms_amd.testcases import seamount_geometry
-    mg.nhydro_init(nx, ny, nz, 1, 1, 0, mg.nhydro.default_params(relax_method=method))
-    mg.nhydro_matrices(*seamount_geometry(nx, ny, 1, 1, 0), None, 4e3, 0.0, 0.0)
+    gpu_problem(mg, (nx, ny, nz), relax_method=method)
     mg.relax(1, 2)
     c0 = mg.nhydro.counters()
     mg.relax(1, 2)

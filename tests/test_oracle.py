@@ -128,11 +128,9 @@ def test_fc_is_decomposition_independent_on_4x2(npx, npy, nsmall):
 
 
 def _bmask_world(nx, ny, nz, npx, npy):
-    from mgroms_amd.testcases import island_mask
-    o = make_seamount(nx, ny, nz, npx, npy, relax_method="FC", solver_prec=1e-8, bmask=True)
-    for r in range(o.nranks):
-        o.field("rmask", 1, r)[...] = island_mask(nx, ny, npx, npy, r)
-    o.matrices(4e3, 0.0, 0.0)
+    from _problem import load_uvw, oracle_twin, problem, uvw
+    o = oracle_twin(problem((nx * npx, ny * npy, nz), bmask=True, relax_method="FC", solver_prec=1e-8), npx, npy)
+    load_uvw(o, uvw((nx * npx, ny * npy, nz)))
     return o
 
 
@@ -246,18 +244,13 @@ def test_call_mask_semantics():
     """The mask of the call (rmaska of nhydro_solve, nhydro.f90:56,72): handing compute_rhs / correct_uvw the mask that
     nhydro_matrices got changes nothing; with bmask off a land mask still removes the w cross terms of compute_rhs
     (mg_compute_rhs.f90:110-111) and leaves umask = vmask = 1 (:69-71)."""
-    from oracle.mgoracle import Oracle, seamount_geometry
+    from _problem import oracle_twin, problem
     nx, ny, nz = 16, 16, 8
     rng = np.random.default_rng(2)
     mask = np.ones((nx + 2, ny + 2)); mask[4:8, 6:11] = 0.0
 
     def run(bmask, call_mask):
-        o = Oracle(nx, ny, nz, bmask=bmask, relax_method="FC", solver_maxiter=3)
-        for name, a in zip(("dx", "dy", "zeta", "h"), seamount_geometry(nx, ny, 1, 1, 0)):
-            o.field(name)[...] = a
-        if bmask:
-            o.field("rmask")[...] = mask
-        o.matrices(4e3, 0.0, 0.0)
+        o = oracle_twin(problem((nx, ny, nz), bmask=bmask, rmask=mask if bmask else None, relax_method="FC", solver_maxiter=3))
         r = np.random.default_rng(7)
         o.field("u")[...] = r.uniform(-1, 1, o.field("u").shape)
         o.field("v")[...] = r.uniform(-1, 1, o.field("v").shape)
