@@ -8,6 +8,7 @@
 // the JS layout (mgx_internal.h), so every global access of a wave is one contiguous 512-byte run.
 #include "mgx_switches.h"
 #include "mgx_relax_common.h"
+#include "mgx_choice.h"
 
 // ------------------------------------------------------------------------------------------------
 // z-line smoother, one colour pass.  mg_relax.f90:237-305 (relax_3D_8_heart) + :308-334 (tridiag).
@@ -146,7 +147,6 @@ __device__ __forceinline__ void relax_col_nz(const LevView &L, const int i, cons
 // (one wave per SIMD: 128 KB of the CU's 160 KB) frees 128 registers, and the backward sweep's reads are independent of its
 // dependency chain.
 // ------------------------------------------------------------------------------------------------
-template <int NZ, bool MF> constexpr bool gam_in_lds = MF && NZ == 64;  // read by k_relax_nz and by the launch that sizes its LDS
 template <int NZ, bool REAL, bool SNAP, int D, bool ST, bool GL = false, bool ZW = false, bool ZG = false>
 __device__ __forceinline__ void relax_col_mf(const LevView &L, const int i, const int jh, const int jodd, const Sides ph, double *__restrict__ gl = nullptr) {
   int c, jm, jp;
@@ -427,180 +427,76 @@ __global__ __launch_bounds__(256) void k_relax_tiny(LevView G, int nsweeps, int 
   }
 }
 
-template <int NZ, int D>
-static void launch_relax_nz_d(hipStream_t st, const LevView *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, Sides ph) {
-  const int gx0 = (L->ny / 2 + WAVE - 1) / WAVE, gx = mgx_switches().no_xcd ? -gx0 : gx0;
-  // two planes per workgroup only when there are plenty of workgroups (it halves the number of CUs a small level uses)
-  const int by = gx0 * nplanes >= 2048 ? 2 : 1;
-  dim3 blk(WAVE, by), grd(gx0 * ((nplanes + by - 1) / by));
-  const bool mf = L->zy != nullptr && NZ >= 16;  // matrix-free cross terms on the bandwidth-bound levels
-  // streaming (nontemporal) hints only when the level cannot live in the 256 MB Infinity Cache between passes:
-  // measured +14 % on the 1.2 GB level 1, -20 % on the 150 MB level 2 which is otherwise re-read from cache
-  const bool stream = mf && (double)L->nx * L->ny * NZ * 72.0 > 256e6;
-#define LAUNCH_NZ(MFV, STV)                                                                                              \
-  {                                                                                                                       \
-    const size_t lds = gam_in_lds<NZ, MFV> ? (size_t)by * NZ * WAVE * sizeof(double) : 0;  /* 32 KB per wave (GL, relax_col_mf) */ \
-    if (real && snap) hipLaunchKernelGGL((k_relax_nz<NZ, true, true, D, MFV, STV>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx); \
-    else if (real) hipLaunchKernelGGL((k_relax_nz<NZ, true, false, D, MFV, STV>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx);   \
-    else hipLaunchKernelGGL((k_relax_nz<NZ, false, false, D, MFV, STV>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx);            \
-  }
-  if (mf && stream) LAUNCH_NZ(true, true)
-  else if (mf) LAUNCH_NZ(true, false)
-  else LAUNCH_NZ(false, false)
-#undef LAUNCH_NZ
+// ---- the launchers: a Choice (mgx_choice.h) to its template instance ----
+static void launch_small(hipStream_t st, const LevView *L, const Choice &c, int nsweeps, int method, int real, Sides ph, int exact) {
+  const dim3 grd(c.grid), blk(c.bx);
+  with_bool(real, [&](auto R) {
+    constexpr bool REAL = decltype(R)::value;
+    if (c.family == KF_TINY) with_nz<2, 4>(c.nz, [&](auto N) { hipLaunchKernelGGL((k_relax_tiny<decltype(N)::value, REAL>), grd, blk, c.lds, st, *L, nsweeps, method, ph); });
+    else if (c.family == KF_REG && c.nt == 1024) hipLaunchKernelGGL((k_relax_reg<2, REAL, 1024>), grd, blk, c.lds, st, *L, nsweeps, method, ph, exact);
+    else if (c.family == KF_REG) with_nz<3, 4, 5, 6, 7>(c.nz, [&](auto N) { hipLaunchKernelGGL((k_relax_reg<decltype(N)::value, REAL, 256>), grd, blk, c.lds, st, *L, nsweeps, method, ph, exact); });
+    else if (c.nt == 1024) hipLaunchKernelGGL((k_relax_small<2, REAL, 1024>), grd, blk, c.lds, st, *L, nsweeps, method, ph, exact);
+    else with_nz<2, 3, 4, 5, 6, 7, 8>(c.nz, [&](auto N) { hipLaunchKernelGGL((k_relax_small<decltype(N)::value, REAL, 256>), grd, blk, c.lds, st, *L, nsweeps, method, ph, exact); });
+  });
 }
-template <int NZ>
-static void launch_relax_nz(hipStream_t st, const LevView *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, Sides ph) {
-  // look-ahead depth D (rows of loads in flight)
-  // measured: NZ=16 6.3 us/pass at D=2 vs 9.3 at D=3; NZ>=32 flat for D=2..5
-  constexpr int D = NZ >= 32 ? 3 : (NZ >= 8 ? 2 : 1);
-  launch_relax_nz_d<NZ, D>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph);
+// a colour pass of k_relax_nz or of the generic column
+static void launch_colour(hipStream_t st, const LevView *L, const Choice &c, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, Sides ph) {
+  const dim3 grd(c.grid, c.gy), blk(c.bx, c.by);
+  with_real_and(real, snap, [&](auto R, auto S) {
+    constexpr bool REAL = decltype(R)::value, SNAP = decltype(S)::value;
+    if (c.family == KF_COLOUR) { hipLaunchKernelGGL((k_relax_colour<REAL, SNAP>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph); return; }
+    with_nz<REG_NZ_LIST>(c.nz, [&](auto N) {
+      constexpr int NZ = decltype(N)::value, D = ch_colour_depth(NZ);
+      with_mf_stream(c.mf, c.stream, [&](auto M, auto T) {
+        hipLaunchKernelGGL((k_relax_nz<NZ, REAL, SNAP, D, decltype(M)::value, decltype(T)::value>), grd, blk, c.lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, c.gx);
+      });
+    });
+  });
 }
 
 extern "C" {
 
-// one Gauss-Seidel sweep as ny+2nx-2 hyperplane launches (register-resident columns for nz a power of two <= 64, any nz otherwise)
+// one Gauss-Seidel sweep as ny+2nx-2 hyperplane launches
 int mgxk_relax_gs_sweep(hipStream_t st, const LevView *L, int real) {
+  const LevShape s = lev_shape(L);
   for (int t = 3; t <= L->ny + 2 * L->nx; t++) {
-    int ilo = (t - L->ny + 1) / 2; if (ilo < 1) ilo = 1;
-    int ihi = (t - 1) / 2; if (ihi > L->nx) ihi = L->nx;
-    if (ihi < ilo) continue;
-    dim3 grd((ihi - ilo + 1 + WAVE - 1) / WAVE), blk(WAVE);
-#define GS_CASE(NZV) case NZV: if (real) hipLaunchKernelGGL((k_relax_gs_front<NZV, true>), grd, blk, 0, st, *L, t); \
-                               else hipLaunchKernelGGL((k_relax_gs_front<NZV, false>), grd, blk, 0, st, *L, t); break;
-    switch (L->nz) {
-      GS_CASE(2) GS_CASE(4) GS_CASE(8) GS_CASE(16) GS_CASE(32) GS_CASE(64)
-      default: if (real) hipLaunchKernelGGL((k_relax_gs_front_any<true>), grd, blk, 0, st, *L, t);
-               else hipLaunchKernelGGL((k_relax_gs_front_any<false>), grd, blk, 0, st, *L, t);
-    }
-#undef GS_CASE
+    const Choice c = choose_gs_front(s, t);
+    if (!c.grid) continue;
+    const dim3 grd(c.grid), blk(c.bx);
+    with_bool(real, [&](auto R) {
+      constexpr bool REAL = decltype(R)::value;
+      if (c.family == KF_GS) with_nz<2, 4, 8, 16, 32, 64>(c.nz, [&](auto N) { hipLaunchKernelGGL((k_relax_gs_front<decltype(N)::value, REAL>), grd, blk, 0, st, *L, t); });
+      else hipLaunchKernelGGL((k_relax_gs_front_any<REAL>), grd, blk, 0, st, *L, t);
+    });
   }
   return 1;
 }
 
-// one-launch relax of a small level; returns 0 if the level does not qualify
-// mode (red-black with cmatrix='real'): 0 = parallel colour passes (snapshot), 1 = the reference's plane loop bit for bit (rb_exact), 2 = the
-// same order by the walk of mgx_rbseq.hip where a kernel has it (k_relax_wave), else the plane loop
-// any (option "small_any_nz"): a closed level of at most 1024 columns with nz = 3, 5, 6 or 7 and even nx, ny is served too, and the call then
-// returns 2 -- nz = 3 by k_relax_wave where it takes the mode, every other case by k_relax_reg up to 256 columns and by k_relax_small above
-// (a 512- or 1024-thread k_relax_reg would have 128 or 64 registers per thread for 16 nz coefficients: the operands are re-read through L2)
+// one-launch relax of a small level; returns 0 if the level does not qualify, else what choose_small (mgx_choice.h) says
 int mgxk_relax_small(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode, int any) {
   mgx_before_launch();
-  const int exact = mode != 0;
-  if (any && (L->nz == 3 || (L->nz >= 5 && L->nz <= 7))) {
-    const int ncols = L->nx * L->ny;
-    if (!(ph.S && ph.E && ph.N && ph.W) || method == 0 || (L->nx & 1) || (L->ny & 1) || ncols > 1024) return 0;
-    if (L->nz == 3 && mgxk_relax_wave(st, L, nsweeps, method, real, ph, mode, 1)) return 2;  // not the plane loop of rb_exact, nor the walk of a half-row wider than a wave
-    // Declined by measurement (profiles/small_any_nz_time.json): the sequential order at speed where only the plane loop could
-    // serve it -- 2 nx barrier steps per sweep with one plane's columns at work lose against the colour pass and its walk, or only draw with
-    // them -- except nz = 5 in one wave (8 x 8 x 5: 57-63 us against 98-99 for 3 sweeps); and 'simple' red-black at nz = 6, 7 above 256
-    // columns (k_relax_small at 32 x 32 x 7: 961-977 us against 877-901 for 40 sweeps; at nz = 6 a draw)
-    if (method == 1 && real && mode == 2 && !(L->nz == 5 && ncols <= 64)) return 0;
-    if (method == 1 && !real && L->nz >= 6 && ncols > 256) return 0;
-    const size_t bytes = ((size_t)L->nz + 1) * (L->nx + 2) * (L->ny + 2) * sizeof(double);
-    const int nth = (ncols + 63) / 64 * 64;
-#define ANY_CASE(NZV) case NZV:                                                                                                                \
-      if (ncols <= 256) { if (real) hipLaunchKernelGGL((k_relax_reg<NZV, true, 256>), dim3(1), dim3(nth), bytes, st, *L, nsweeps, method, ph, exact);   \
-                          else hipLaunchKernelGGL((k_relax_reg<NZV, false, 256>), dim3(1), dim3(nth), bytes, st, *L, nsweeps, method, ph, exact); }     \
-      else { if (real) hipLaunchKernelGGL((k_relax_small<NZV, true, 256>), dim3(1), dim3(256), 0, st, *L, nsweeps, method, ph, exact);                  \
-             else hipLaunchKernelGGL((k_relax_small<NZV, false, 256>), dim3(1), dim3(256), 0, st, *L, nsweeps, method, ph, exact); }                    \
-      return mgx_launched() ? 2 : 0;
-    switch (L->nz) { ANY_CASE(3) ANY_CASE(5) ANY_CASE(6) ANY_CASE(7) default: return 0; }
-#undef ANY_CASE
-  }
-  if (mgxk_relax_wave(st, L, nsweeps, method, real, ph, mode, 0)) return 1;  // <= 256 columns, nz = 2: the whole level in one wave
-  {  // one thread per column, coefficients in registers, p in LDS
-    const int ncols = L->nx * L->ny;
-    const bool closed = ph.S && ph.E && ph.N && ph.W;
-    if (!mgx_switches().no_reg && closed && method != 0 && ((L->nz == 2 && ncols <= 1024) || (L->nz == 4 && ncols <= 256))) {
-      const size_t bytes = ((size_t)L->nz + 1) * (L->nx + 2) * (L->ny + 2) * sizeof(double);
-      const int nth = (ncols + 63) / 64 * 64;
-      if (L->nz == 2) { if (real) hipLaunchKernelGGL((k_relax_reg<2, true, 1024>), dim3(1), dim3(nth), bytes, st, *L, nsweeps, method, ph, exact);
-                        else hipLaunchKernelGGL((k_relax_reg<2, false, 1024>), dim3(1), dim3(nth), bytes, st, *L, nsweeps, method, ph, exact); }
-      else { if (real) hipLaunchKernelGGL((k_relax_reg<4, true, 256>), dim3(1), dim3(nth), bytes, st, *L, nsweeps, method, ph, exact);
-             else hipLaunchKernelGGL((k_relax_reg<4, false, 256>), dim3(1), dim3(nth), bytes, st, *L, nsweeps, method, ph, exact); }
-      return mgx_launched();
-    }
-  }
-  {  // everything in LDS? (11 arrays of the compact level + the k=1 snapshot)
-    const size_t n3 = (size_t)(L->nx + 2) * (L->ny + 2) * L->nz, bytes = (11 * n3 + (size_t)(L->nx + 2) * (L->ny + 2)) * sizeof(double);
-    if (!mgx_switches().no_tiny && !(exact && method == 1 && real) && bytes <= 64 * 1024 && (ph.S && ph.E && ph.N && ph.W) && (L->nz == 2 || L->nz == 4)) {
-      const int ncolt = method == 2 ? (L->nx / 2) * (L->ny / 2) : L->nx * (L->ny / 2);
-      const int ntht = ncolt <= 64 ? 64 : 256;
-      if (L->nz == 2) { if (real) hipLaunchKernelGGL((k_relax_tiny<2, true>), dim3(1), dim3(ntht), bytes, st, *L, nsweeps, method, ph);
-                        else hipLaunchKernelGGL((k_relax_tiny<2, false>), dim3(1), dim3(ntht), bytes, st, *L, nsweeps, method, ph); }
-      else { if (real) hipLaunchKernelGGL((k_relax_tiny<4, true>), dim3(1), dim3(ntht), bytes, st, *L, nsweeps, method, ph);
-             else hipLaunchKernelGGL((k_relax_tiny<4, false>), dim3(1), dim3(ntht), bytes, st, *L, nsweeps, method, ph); }
-      return mgx_launched();
-    }
-  }
-  const int ncol = method == 2 ? (L->nx / 2) * (L->ny / 2) : L->nx * (L->ny / 2);
-  // (Measured and dropped: one cooperative launch per relax call with a grid-wide barrier between colour passes on the
-  // 1024-16384-column levels -- cg grid.sync and a hand-written atomic barrier both cost more than the kernel boundary
-  // they replace: V-cycle 2.81 -> 3.03 ms.)
-  // one CU streams ~25-50 GB/s: worth it only while the level is launch-bound, not bandwidth-bound (measured:
-  // 16x16x2 and 32x32x4 win, 64x64x8 loses 2x against separate launches over 256 CUs).  A 2-level-deep coarsest grid
-  // is still launch-bound at 1024 columns per colour (the gathered 64x32x2 grid of an 8-GPU run): 1024 threads.
-  if (!(ph.S && ph.E && ph.N && ph.W)) return 0;
-  if (L->nz == 2 && ncol > 256 && ncol <= 1024) {
-    if (real) hipLaunchKernelGGL((k_relax_small<2, true, 1024>), dim3(1), dim3(1024), 0, st, *L, nsweeps, method, ph, exact);
-    else hipLaunchKernelGGL((k_relax_small<2, false, 1024>), dim3(1), dim3(1024), 0, st, *L, nsweeps, method, ph, exact);
-    return mgx_launched();
-  }
-  if (ncol > 256 || L->nz > 8) return 0;
-  // 32x32x8 (fifth level of an nz = 128 hierarchy), four colours: two colour-pair launches per sweep (k_relax_ks2, 5.9 us each) beat this
-  // kernel's 22-32 us per sweep, which re-reads every operand through L2
-  if (L->nz == 8 && method == 2 && L->zy != nullptr && ncol > 64 && L->ny / 2 <= WAVE) return 0;
-  const int nth = ncol <= 64 ? 64 : 256;
-#define SMALL_CASE(NZV) case NZV: if (real) hipLaunchKernelGGL((k_relax_small<NZV, true, 256>), dim3(1), dim3(nth), 0, st, *L, nsweeps, method, ph, exact); \
-                                  else hipLaunchKernelGGL((k_relax_small<NZV, false, 256>), dim3(1), dim3(nth), 0, st, *L, nsweeps, method, ph, exact); return mgx_launched();
-  switch (L->nz) { SMALL_CASE(2) SMALL_CASE(4) SMALL_CASE(8) default: return 0; }
-#undef SMALL_CASE
+  const Choice c = choose_small(lev_shape(L), method, real, ph, mode, any, mgx_switches());
+  if (c.ask_wave >= 0 && mgxk_relax_wave(st, L, nsweeps, method, real, ph, mode, c.ask_wave)) return c.wave_ret;
+  if (c.family == KF_NONE) return 0;
+  launch_small(st, L, c, nsweeps, method, real, ph, mode != 0);
+  return mgx_launched() ? c.ret : 0;
 }
-
-// the nz of the register-resident instances of the colour pass (k_relax_nz): the powers of two, and the vertical sizes that are not (ROMS /
-// CROCO users choose nz for their physics) with their coarser levels.  X(nz) once per instance; nz = 80, 96, 128 are mgxk_relax_tall's.
-#ifdef MGX_QUICK  // -DMGX_QUICK: only the nz=64 instantiations (resource-usage checks of the level-1 kernel in seconds)
-#define REG_NZ_LIST(X) X(64)
-#else
-#define REG_NZ_LIST(X) X(2) X(4) X(8) X(16) X(32) X(64) X(12) X(20) X(24) X(40) X(48)
-#endif
 
 // returns what the pass did (mgx_wrappers.h): PASS_MIRRORS the kernel stored the physical mirrors of p itself (no k_halo_phys needed); PASS_D0 it
 // wrote L->d0w; PASS_TALL_STORED it was the stored-coefficient tall-column pass (mgx_relax_tall.hip; relax() counts those)
 int mgxk_relax_colour(hipStream_t st, const LevView *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, Sides ph) {
   if (const int ks = mgxk_relax_ks(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph)) return ks;  // mid levels: rows split over the waves of a workgroup
-  switch (L->nz) {
-#define REG_CASE(NZV) case NZV: launch_relax_nz<NZV>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph); break;
-    REG_NZ_LIST(REG_CASE)
-#undef REG_CASE
-#ifndef MGX_QUICK
-    case 80: case 96: case 128: if (const int tall = mgxk_relax_tall(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph)) return tall;
-#endif
-    // fall through
-    default: {
-      dim3 blk(WAVE, 4), grd = col_grid(L->ny / 2, nplanes);
-      if (real && snap) hipLaunchKernelGGL((k_relax_colour<true, true>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph);
-      else if (real) hipLaunchKernelGGL((k_relax_colour<true, false>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph);
-      else hipLaunchKernelGGL((k_relax_colour<false, false>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph);
-      return 0;
-    }
+  const LevShape s = lev_shape(L);
+  Choice c = choose_colour(s, nplanes, real, snap, mgx_switches());
+  if (c.family == KF_TALL || c.family == KF_TALL_ST) {
+    if (const int tall = mgxk_relax_tall(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph)) return tall;
+    c = choose_colour_generic(s, nplanes);  // the launch was refused
   }
-  return (real && snap && L->d0w != nullptr) ? PASS_MIRRORS | PASS_D0 : PASS_MIRRORS;
+  launch_colour(st, L, c, i0, istep, nplanes, jodd_fixed, rb, real, snap, ph);
+  return c.ret;
 }
 // does mgxk_relax_colour run a register-resident kernel (which writes mirrors and chained snapshots) on this level?
-int mgxk_has_reg_kernel(const LevView *L) {
-  switch (L->nz) {
-#define REG_CASE(NZV) case NZV:
-    REG_NZ_LIST(REG_CASE) return 1;
-#undef REG_CASE
-#ifndef MGX_QUICK
-    case 80: case 96: case 128: return !mgx_switches().no_tall;  // matrix-free or stored: mgxk_relax_tall has both
-#endif
-    default: return 0;
-  }
-}
-#undef REG_NZ_LIST
+int mgxk_has_reg_kernel(const LevView *L) { return choose_has_reg_kernel(lev_shape(L), mgx_switches()); }
 void mgxk_snapshot_k1(hipStream_t st, const LevView *L) {
   hipLaunchKernelGGL(k_snapshot_k1, dim3((L->RS + 255) / 256, L->nx + 2), dim3(256), 0, st, *L);
 }

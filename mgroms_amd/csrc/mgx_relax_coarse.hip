@@ -14,6 +14,7 @@
 // The rows expand ROW_RHS_* (mgx_device.h), as those of relax_col_nz / k_relax_reg do: bit-identical.
 #include "mgx_switches.h"
 #include "mgx_device.h"
+#include "mgx_choice.h"
 
 // flags (round 3; the level below the coarsest one in a cycle): 1 = coarse2fine(lev) first -- p += the tri-linear interpolation of the
 // coarse p of C (mg_intergrids.f90:366-450 + :226), applied while p is loaded into LDS; 2 = compute_residual(lev) + fine2coarse(lev)
@@ -355,59 +356,43 @@ __global__ __launch_bounds__(NT, 1) void k_relax_wave(LevView G, int nsweeps, in
 #undef GI
 }
 
-extern "C" {
-
-// returns 1 when launched: a closed level of <= 256 columns with nz = 2 (the coarsest grid of every BASELINE configuration) as one
-// wave, or of <= 1024 columns with nz = 2 / 4 (the 32x32x4 level above it) as four waves, or -- nz = 2 only -- of <= 2048 columns as
-// eight waves: the 64x32x2 coarsest grid that eight GPUs gather (4x2 ranks of 512x512x64: its 40 sweeps took 436 us in k_relax_small,
-// which re-reads every operand through L2, a fifth of a V-cycle on every rank)
-// Cv, flags: see k_relax_wave (0 / nullptr = the plain relax call); mgxk_relax_wave_fused is the entry the cycles use
-// mode (red-black with cmatrix='real' only): 0 = parallel colour passes, 1 = the bit-exact plane loop (not here: k_relax_reg), 2 = the
-// reference's sequential order by the walk (k_relax_wave's seq)
-// any (option "small_any_nz"): nz = 3 is served too -- four columns of three rows per lane, up to 256 blocks of 2x2 columns; never with folded transfers
-static int relax_wave_launch(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode, const LevView *Cv, int flags, int nbatch = 1, long long bstride = 0, int any = 0) {
-  mgx_before_launch();
-  const bool nz3 = any && L->nz == 3 && !(flags & 3);
-  if (mgx_switches().no_wave || (L->nz != 2 && L->nz != 4 && !nz3) || method == 0 || (mode == 1 && method == 1 && real)) return 0;
-  const int seq = (mode == 2 && method == 1 && real) ? 1 : 0;
-  if (seq && L->ny / 2 > WAVE) return 0;  // the walk keeps a half-row on the lanes of one wave; wider levels: k_relax_reg's plane loop
-  const int nblk = (L->nx / 2) * (L->ny / 2);
-  if (!(ph.S && ph.E && ph.N && ph.W) || (L->nx & 1) || (L->ny & 1) || nblk > (L->nz == 2 ? 8 : 4) * WAVE) return 0;
-  size_t bytes = ((size_t)L->nz + 1) * (L->nx + 2) * (L->ny + 2) * sizeof(double);
-  if (seq) {  // p, the snapshot and u, interiors only
-    bytes = ((2 * (size_t)L->nz + 5) * L->nx * L->ny + 4 + 64 * 18) * sizeof(double);  // p, the snapshot, the operand quads (+ a zero quad), g, the register walk's d0 / s rows
-    if (bytes > 160 * 1024) return 0;
-  }
-  const LevView Cc = Cv ? *Cv : *L;
-#define WAVE_LDS(KERNEL)                                                                                                      \
-  { static size_t granted = 65536;                                                                                               \
-    if (bytes > granted) { if (hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) { (void)hipGetLastError(); return 0; } granted = 160 * 1024; } }
-#define WAVE_CASE(NZV, NTV)                                                                                                   \
-  { if (seq) { WAVE_LDS((k_relax_wave<NZV, true, NTV, false, true>))                                                           \
-      hipLaunchKernelGGL((k_relax_wave<NZV, true, NTV, false, true>), dim3(nbatch), dim3(NTV), bytes, st, *L, nsweeps, method, ph, Cc, flags, bstride); } \
-    else if (real) hipLaunchKernelGGL((k_relax_wave<NZV, true, NTV>), dim3(nbatch), dim3(NTV), bytes, st, *L, nsweeps, method, ph, Cc, flags, bstride); \
-    else hipLaunchKernelGGL((k_relax_wave<NZV, false, NTV>), dim3(nbatch), dim3(NTV), bytes, st, *L, nsweeps, method, ph, Cc, flags, bstride);          \
-    return mgx_launched(); }
-#define WAVE_CASE_FZ(NTV)                                                                                                     \
-  { if (seq) { WAVE_LDS((k_relax_wave<4, true, NTV, true, true>))                                                              \
-      hipLaunchKernelGGL((k_relax_wave<4, true, NTV, true, true>), dim3(nbatch), dim3(NTV), bytes, st, *L, nsweeps, method, ph, Cc, flags, bstride); } \
-    else if (real) hipLaunchKernelGGL((k_relax_wave<4, true, NTV, true>), dim3(nbatch), dim3(NTV), bytes, st, *L, nsweeps, method, ph, Cc, flags, bstride); \
-    else hipLaunchKernelGGL((k_relax_wave<4, false, NTV, true>), dim3(nbatch), dim3(NTV), bytes, st, *L, nsweeps, method, ph, Cc, flags, bstride);      \
-    return mgx_launched(); }
-  if (flags & 3) {
-    if (L->nz != 4) return 0;
-    if (nblk <= WAVE) WAVE_CASE_FZ(64) else WAVE_CASE_FZ(256)
-  }
-  if (L->nz == 2) { if (nblk <= WAVE) WAVE_CASE(2, 64) else if (nblk <= 4 * WAVE) WAVE_CASE(2, 256) else WAVE_CASE(2, 512) }
-  if (L->nz == 3) { if (nblk <= WAVE) WAVE_CASE(3, 64) else WAVE_CASE(3, 256) }
-  if (nblk <= WAVE) WAVE_CASE(4, 64) else WAVE_CASE(4, 256)
-#undef WAVE_CASE_FZ
-#undef WAVE_LDS
-#undef WAVE_CASE
+// the instance of k_relax_wave a Choice names, with the one-time grant of the sequential-order instances' LDS (up to 160 KB: above the 64 KB a
+// kernel gets without asking); returns 0 when the grant or the launch was refused
+template <int NZ, int NT, bool FZ>
+static int launch_wave_nt(hipStream_t st, const LevView *L, const Choice &c, int nsweeps, int method, int real, Sides ph, const LevView &Cc, int flags, long long bstride) {
+  int ok = 1;
+  with_real_and(real, c.seq, [&](auto R, auto S) {
+    constexpr bool REAL = decltype(R)::value, SEQ = decltype(S)::value;
+    if constexpr (SEQ) {
+      static size_t granted = 65536;
+      if (c.lds > granted) {
+        if (hipFuncSetAttribute((const void *)k_relax_wave<NZ, REAL, NT, FZ, SEQ>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) { (void)hipGetLastError(); ok = 0; return; }
+        granted = 160 * 1024;
+      }
+    }
+    hipLaunchKernelGGL((k_relax_wave<NZ, REAL, NT, FZ, SEQ>), dim3(c.grid), dim3(c.bx), c.lds, st, *L, nsweeps, method, ph, Cc, flags, bstride);
+  });
+  return ok ? mgx_launched() : 0;
+}
+// Cv, flags: see k_relax_wave (0 / nullptr = the plain relax call); returns 1 when launched
+static int launch_wave(hipStream_t st, const LevView *L, const Choice &c, int nsweeps, int method, int real, Sides ph, const LevView *Cv, int flags, long long bstride = 0) {
+  if (c.family == KF_NONE) return 0;
+  const LevView &Cc = Cv ? *Cv : *L;
+  int r = 0;
+#define WAVE_NT(NZV, NTV, FZV) if (c.nt == NTV) r = launch_wave_nt<NZV, NTV, FZV>(st, L, c, nsweeps, method, real, ph, Cc, flags, bstride);
+  if (c.fz) { WAVE_NT(4, 64, true) else WAVE_NT(4, 256, true) }   // the instances that fold the transfers in: nz = 4 only
+  else if (c.nz == 2) { WAVE_NT(2, 64, false) else WAVE_NT(2, 256, false) else WAVE_NT(2, 512, false) }
+  else if (c.nz == 3) { WAVE_NT(3, 64, false) else WAVE_NT(3, 256, false) }
+  else { WAVE_NT(4, 64, false) else WAVE_NT(4, 256, false) }
+#undef WAVE_NT
+  return r;
 }
 
+extern "C" {
+
 int mgxk_relax_wave(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode, int any) {
-  return relax_wave_launch(st, L, nsweeps, method, real, ph, mode, nullptr, 0, 1, 0, any);
+  mgx_before_launch();
+  return launch_wave(st, L, choose_wave(lev_shape(L), method, real, ph, mode, 0, 1, any, mgx_switches()), nsweeps, method, real, ph, nullptr, 0);
 }
 // ---- the coarsest-level solve of a cycle as ONE matrix-vector product (option "coarsest_direct") -----------------------------------
 // Inside a cycle the coarsest level is entered with p = 0 (fine2coarse, mg_intergrids.f90:70) and left after relax(nlevs, ns_coarsest)
@@ -469,11 +454,8 @@ __global__ __launch_bounds__(CDT) void k_coarse_direct(LevView L, const double *
   mirror_store(L, L.p, ro, j, i, c, v, ph);
 }
 
-// cells of a level the direct solve serves (a closed level of the one-workgroup kernel, at most 2048 cells), 0 = none; any: nz = 3 too
-int mgxk_coarse_direct_cells(const LevView *L, int any) {
-  const long long n = (long long)L->nx * L->ny * L->nz;
-  return ((L->nz == 2 || L->nz == 4 || (any && L->nz == 3)) && n <= 2048 && !(L->nx & 1) && !(L->ny & 1)) ? (int)n : 0;
-}
+// cells of a level the direct solve serves, 0 = none
+int mgxk_coarse_direct_cells(const LevView *L, int any) { return choose_coarse_direct_cells(lev_shape(L), any); }
 // build B (M: n * n doubles) with the level's own relax kernel; pb: scratch of 2 * n * stride doubles (stride = the level's array size).
 // Returns 1 when built (all of it enqueued on st), 0 = the level has no one-workgroup kernel for this method / mode.
 int mgxk_coarse_direct_build(hipStream_t st, const LevView *L, int nsweeps, int method, int real, Sides ph, int mode, double *pb, long long stride, double *M, int any) {
@@ -482,7 +464,8 @@ int mgxk_coarse_direct_build(hipStream_t st, const LevView *L, int nsweeps, int 
   hipLaunchKernelGGL(k_cd_init, dim3(n), dim3(256), 0, st, *L, pb, stride, n);
   LevView B = *L;
   B.p = pb; B.b = pb + (long long)n * stride;
-  if (!relax_wave_launch(st, &B, nsweeps, method, real, ph, mode, nullptr, 0, n, stride, any)) return 0;
+  mgx_before_launch();
+  if (!launch_wave(st, &B, choose_wave(lev_shape(&B), method, real, ph, mode, 0, n, any, mgx_switches()), nsweeps, method, real, ph, nullptr, 0, stride)) return 0;
   hipLaunchKernelGGL(k_cd_compact, dim3((n + 255) / 256, n), dim3(256), 0, st, *L, pb, stride, M, n);
   return mgx_launched();
 }
@@ -500,8 +483,9 @@ int mgxk_coarse_direct_slabs(int n) { return (n + CDB - 1) / CDB; }
 // compute_residual(lev) + fine2coarse(lev) folded behind (flags & 2); C = level lev+1 (closed, exactly half the size, not gathered).
 // Returns 1 when launched, 0 = the caller runs the separate operators.
 int mgxk_relax_wave_fused(hipStream_t st, const LevView *L, const LevView *C, int nsweeps, int method, int real, Sides ph, int flags, int mode) {
-  if (mgx_switches().no_wave_fuse || !C || C->nx * 2 != L->nx || C->ny * 2 != L->ny || C->nz * 2 != L->nz || nsweeps < 0) return 0;
-  return relax_wave_launch(st, L, nsweeps, method, real, ph, mode, C, flags);
+  mgx_before_launch();
+  const LevShape coarse = C ? lev_shape(C) : LevShape();
+  return launch_wave(st, L, choose_wave_fused(lev_shape(L), C ? &coarse : nullptr, nsweeps, method, real, ph, flags, mode, mgx_switches()), nsweeps, method, real, ph, C, flags);
 }
 
 }  // extern "C"

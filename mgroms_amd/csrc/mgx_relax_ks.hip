@@ -11,6 +11,7 @@
 // The rows expand MF_CROSS_COEF and ROW_RHS_* (mgx_device.h), the text of relax_col_mf's rows: bit-identical results.
 #include "mgx_switches.h"
 #include "mgx_relax_common.h"
+#include "mgx_choice.h"
 
 // H > 1 (nz = 64, the second level of an nz = 128 hierarchy): a wave's NZ/NW rows are built in H runs of R rows one after the other (the register
 // arrays of a run are those of the nz = 32 kernel), the recurrence wave keeps only x(k) in registers and takes a2(k), bet(k) from LDS as it
@@ -551,54 +552,37 @@ extern "C" {
 // PASS_D0 when it wrote L->d0w
 int mgxk_relax_ks(hipStream_t st, const LevView *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, Sides ph) {
   mgx_before_launch();
-  const Switches &sw = mgx_switches();
-  const int nw_env = sw.ks_nw;
-  if (sw.no_ks || L->zy == nullptr || (L->nz != 32 && L->nz != 16 && !(L->nz == 8 && sw.ks8) && !(L->nz == 64 && sw.ks64 && !snap))) return 0;
-  const int gx0 = (L->ny / 2 + WAVE - 1) / WAVE;
-  // worth it only while a colour has fewer waves than the chip has SIMDs (1024); a bandwidth-bound level keeps one wave per column set
-  if (gx0 * nplanes > 512) return 0;
-  // the level must live in the caches (no streaming hints here)
-  const int gx = sw.no_xcd ? -gx0 : gx0;
-  dim3 grd(gx0 * nplanes);
-#define KS_LAUNCH(NZV, NWV)                                                                                                     \
-  {                                                                                                                              \
-    dim3 blk(WAVE, NWV);                                                                                                         \
-    const size_t lds = (size_t)3 * NZV * WAVE * sizeof(double);                                                                  \
-    if (real && snap) { hipLaunchKernelGGL((k_relax_ks<NZV, NWV, true, true>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx); return mgx_launched() ? (L->d0w != nullptr ? PASS_MIRRORS | PASS_D0 : PASS_MIRRORS) : 0; } \
-    else if (real) hipLaunchKernelGGL((k_relax_ks<NZV, NWV, true, false>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx);     \
-    else hipLaunchKernelGGL((k_relax_ks<NZV, NWV, false, false>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx);              \
-    return mgx_launched() ? PASS_MIRRORS : 0;                                                                             \
-  }
-  if (L->nz == 64) {  // 96 KB of dynamic LDS: above the 64 KB a kernel gets without asking
+  const Choice c = choose_ks(lev_shape(L), nplanes, real, snap, mgx_switches());
+  if (c.family == KF_NONE) return 0;
+  const dim3 grd(c.grid), blk(c.bx, c.by);
+  if (c.nz == 64) {  // its own instances (H = 2, never SNAP), and their LDS is granted once
     static bool attr = false;
-    const size_t lds = (size_t)3 * 64 * WAVE * sizeof(double);
     if (!attr) {
-      if (hipFuncSetAttribute((const void *)k_relax_ks<64, 8, true, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-          hipFuncSetAttribute((const void *)k_relax_ks<64, 8, false, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { (void)hipGetLastError(); return 0; }
+      if (hipFuncSetAttribute((const void *)k_relax_ks<64, 8, true, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds) != hipSuccess ||
+          hipFuncSetAttribute((const void *)k_relax_ks<64, 8, false, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds) != hipSuccess) { (void)hipGetLastError(); return 0; }
       attr = true;
     }
-    dim3 blk(WAVE, 8);
-    if (real) hipLaunchKernelGGL((k_relax_ks<64, 8, true, false, 2>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx);
-    else hipLaunchKernelGGL((k_relax_ks<64, 8, false, false, 2>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx);
-    return mgx_launched() ? PASS_MIRRORS : 0;
+    with_bool(real, [&](auto R) { hipLaunchKernelGGL((k_relax_ks<64, 8, decltype(R)::value, false, 2>), grd, blk, c.lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, c.gx); });
+  } else {
+    with_nz<32, 16, 8>(c.nz, [&](auto N) {
+      with_bool(c.nt == 4, [&](auto W4) {
+        with_real_and(real, snap, [&](auto R, auto S) {
+          hipLaunchKernelGGL((k_relax_ks<decltype(N)::value, decltype(W4)::value ? 4 : 8, decltype(R)::value, decltype(S)::value>), grd, blk, c.lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, c.gx);
+        });
+      });
+    });
   }
-  // measured (256x256x32 / 128x128x16, four-colour sweep): 8 waves 47.0 / 21.6 us, 4 waves 53.3 / 23.3, row by row 57.6 / 28.2
-  if (L->nz == 32) { if (nw_env == 4) KS_LAUNCH(32, 4) else KS_LAUNCH(32, 8) }
-  if (L->nz == 16) { if (nw_env == 4) KS_LAUNCH(16, 4) else KS_LAUNCH(16, 8) }
-  if (nw_env == 4) KS_LAUNCH(8, 4) else KS_LAUNCH(8, 8)
-#undef KS_LAUNCH
+  return mgx_launched() ? c.ret : 0;
 }
 
 // both colours of the planes i0, i0+2, ... of a four-colour sweep in one launch; returns 1 when launched (closed level, one column set per plane)
 int mgxk_relax_ks_pair(hipStream_t st, const LevView *L, int i0, int nplanes, int real, Sides ph) {
   mgx_before_launch();
-  if (mgx_switches().no_ks || mgx_switches().no_ks2 || L->zy == nullptr || !(ph.S && ph.E && ph.N && ph.W) || (L->ny & 1) || L->ny / 2 > WAVE) return 0;
-  if (L->nz != 16 && L->nz != 8) return 0;
-  dim3 grd(nplanes), blk(WAVE, 8);
-  if (L->nz == 16) { if (real) hipLaunchKernelGGL((k_relax_ks2<16, 8, true>), grd, blk, 0, st, *L, i0, nplanes, ph);
-                     else hipLaunchKernelGGL((k_relax_ks2<16, 8, false>), grd, blk, 0, st, *L, i0, nplanes, ph); }
-  else { if (real) hipLaunchKernelGGL((k_relax_ks2<8, 8, true>), grd, blk, 0, st, *L, i0, nplanes, ph);
-         else hipLaunchKernelGGL((k_relax_ks2<8, 8, false>), grd, blk, 0, st, *L, i0, nplanes, ph); }
+  const Choice c = choose_ks_pair(lev_shape(L), nplanes, ph, mgx_switches());
+  if (c.family == KF_NONE) return 0;
+  with_nz<16, 8>(c.nz, [&](auto N) {
+    with_bool(real, [&](auto R) { hipLaunchKernelGGL((k_relax_ks2<decltype(N)::value, 8, decltype(R)::value>), dim3(c.grid), dim3(c.bx, c.by), 0, st, *L, i0, nplanes, ph); });
+  });
   return mgx_launched();
 }
 

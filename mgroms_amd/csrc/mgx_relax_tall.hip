@@ -8,6 +8,7 @@
 // instances of mgx_relax.hip compile to the instructions they had before the stored text was shared); the way down is TALL_DOWN below.
 #include "mgx_switches.h"
 #include "mgx_relax_common.h"
+#include "mgx_choice.h"
 
 // Tall columns (nz = 128, BASELINE config 5): x and gam of 128 rows do not fit the register file next to the load rings.
 // The forward pass is the one of mgx_relax_common.h; only where its values go differs from relax_col_mf / relax_col_nz.  The
@@ -115,44 +116,34 @@ TALL_KERNEL(k_relax_tall, relax_col_mf_tall)
 TALL_KERNEL(k_relax_tall_st, relax_col_st_tall)
 #undef TALL_KERNEL
 
-// nz = 128 (BASELINE config 5), 96 and 80, lower 64 rows through LDS: the matrix-free form where the level has its slopes (L->zy), the
-// stored-coefficient form where it has not.  Returns 0 = nothing ran (the caller's generic column takes the pass), 1 = the matrix-free
-// pass ran (PASS_MIRRORS: the physical mirrors are written), with PASS_TALL_STORED the stored one (what relax() counts as "tall_stored_passes").
+// one instance of either kernel: its LDS (two waves' worth, above the 64 KB a kernel gets without asking) is granted once; false = refused
+template <auto KERNEL>
+static bool launch_tall_one(hipStream_t st, const LevView *L, const Choice &c, int i0, int istep, int nplanes, int jodd_fixed, int rb, Sides ph) {
+  static bool attr = false;
+  if (!attr) {
+    if (hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * WAVE * (int)sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return false; }
+    attr = true;
+  }
+  hipLaunchKernelGGL(KERNEL, dim3(c.grid), dim3(c.bx, c.by), c.lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, c.gx);
+  return true;
+}
+
+// The tall-column pass of choose_tall (mgx_choice.h).  Returns 0 = nothing ran (the caller's generic column takes the pass), PASS_MIRRORS = the
+// matrix-free pass ran (the physical mirrors are written), with PASS_TALL_STORED the stored one.
 extern "C" int mgxk_relax_tall(hipStream_t st, const LevView *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, Sides ph) {
-  if (L->nz != 128 && L->nz != 96 && L->nz != 80) return 0;
   mgx_before_launch();
-  if (mgx_switches().no_tall) return 0;
-  const bool mf = L->zy != nullptr;
-  const int gx0 = (L->ny / 2 + WAVE - 1) / WAVE, gx = mgx_switches().no_xcd ? -gx0 : gx0;
-  const int by = gx0 * nplanes >= 2048 ? 2 : 1;
-  dim3 blk(WAVE, by), grd(gx0 * ((nplanes + by - 1) / by));
-  const bool stream = (double)L->nx * L->ny * L->nz * 72.0 > 256e6;
-  const size_t lds = (size_t)by * 64 * WAVE * sizeof(double);  // the lower 64 rows' forward values: 32 KB per wave
-#define LAUNCH_TALL_ONE(KERNEL, NZV, RV, SV, STV)                                                                       \
-  {                                                                                                                     \
-    static bool attr = false;                                                                                           \
-    if (!attr) {                                                                                                        \
-      if (hipFuncSetAttribute((const void *)KERNEL<NZV, 64, RV, SV, TALL_D, STV>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * WAVE * (int)sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return 0; } \
-      attr = true;                                                                                                      \
-    }                                                                                                                   \
-    hipLaunchKernelGGL((KERNEL<NZV, 64, RV, SV, TALL_D, STV>), grd, blk, lds, st, *L, i0, istep, nplanes, jodd_fixed, rb, ph, gx); \
-  }
-#define LAUNCH_TALL(KERNEL, NZV, STV)                                                                                   \
-  {                                                                                                                     \
-    if (real && snap) LAUNCH_TALL_ONE(KERNEL, NZV, true, true, STV)                                                     \
-    else if (real) LAUNCH_TALL_ONE(KERNEL, NZV, true, false, STV)                                                       \
-    else LAUNCH_TALL_ONE(KERNEL, NZV, false, false, STV)                                                                \
-  }
-#define LAUNCH_TALL_NZ(KERNEL, NZV) { if (stream) LAUNCH_TALL(KERNEL, NZV, true) else LAUNCH_TALL(KERNEL, NZV, false) }
-#define LAUNCH_TALL_MF(NZV) { if (mf) LAUNCH_TALL_NZ(k_relax_tall, NZV) else LAUNCH_TALL_NZ(k_relax_tall_st, NZV) }
-  constexpr int TALL_D = 3;  // look-ahead rows of both forms
-  if (L->nz == 128) LAUNCH_TALL_MF(128)
-  else if (L->nz == 96) LAUNCH_TALL_MF(96)
-  else LAUNCH_TALL_MF(80)
-#undef LAUNCH_TALL_MF
-#undef LAUNCH_TALL_NZ
-#undef LAUNCH_TALL
-#undef LAUNCH_TALL_ONE
-  if (!mgx_launched()) return 0;
-  return mf ? PASS_MIRRORS : PASS_MIRRORS | PASS_TALL_STORED;
+  const Choice c = choose_tall(lev_shape(L), nplanes, mgx_switches());
+  if (c.family == KF_NONE) return 0;
+  bool ok = false;
+  with_nz<128, 96, 80>(c.nz, [&](auto N) {
+    with_bool(c.stream, [&](auto T) {
+      with_real_and(real, snap, [&](auto R, auto S) {
+        constexpr int NZ = decltype(N)::value, TALL_D = 3;  // choose_tall's d
+        constexpr bool REAL = decltype(R)::value, SNAP = decltype(S)::value, ST = decltype(T)::value;
+        if (c.mf) ok = launch_tall_one<k_relax_tall<NZ, 64, REAL, SNAP, TALL_D, ST>>(st, L, c, i0, istep, nplanes, jodd_fixed, rb, ph);
+        else ok = launch_tall_one<k_relax_tall_st<NZ, 64, REAL, SNAP, TALL_D, ST>>(st, L, c, i0, istep, nplanes, jodd_fixed, rb, ph);
+      });
+    });
+  });
+  return ok && mgx_launched() ? c.ret : 0;
 }

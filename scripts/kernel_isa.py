@@ -33,7 +33,8 @@ def records(path):
                 break
             ln = ln.split(";")[0].strip()
             if ln and not ln.startswith(".") and not ln.endswith(":"):  # no directives, labels, comments
-                text.append(re.sub(r"\.LBB\d+_", ".LBB_", " ".join(ln.split())))
+                # block and long-branch labels carry the function's position in the unit: the order of emission, not an instruction
+                text.append(re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", re.sub(r"\.LBB\d+_", ".LBB_", " ".join(ln.split()))))
         out[name] = {f[1:]: int(md[f]) for f in FIELDS}
         out[name].update(instructions=len(text), hash=hashlib.sha256("\n".join(text).encode()).hexdigest()[:16])
     return out
