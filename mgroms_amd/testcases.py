@@ -45,6 +45,21 @@ def island_mask(nx, ny, npx=1, npy=1, rank=0):
     return m[pi * nx:pi * nx + nx + 2, pj * ny:pj * ny + ny + 2].copy()
 
 
+def curvilinear_metric(nx, ny, npx=1, npy=1, rank=0):
+    """Factors (fx, fy) for dx, dy of one rank, (nx+2, ny+2) each: a horizontal metric that varies in i and in j as a curvilinear
+    grid's does -- within [0.75, 1.25], neither symmetric nor separable, neither a shifted copy of the other.  Defined on GLOBAL
+    indices I = 0..nxg+1, J = 0..nyg+1, halo entries included, then cut to the rank's block, so it does not depend on the
+    decomposition.  The curvilinear problem is the generator's dx, dy times fx, fy."""
+    nxg, nyg = npx * nx, npy * ny
+    pj, pi = rank // npx, rank % npx
+    I = np.arange(0, nxg + 2, dtype=np.float64)[:, None]
+    J = np.arange(0, nyg + 2, dtype=np.float64)[None, :]
+    fx = 1.0 + 0.2 * np.sin(0.37 * I + 0.9) * np.cos(0.23 * J + 0.4) + 0.05 * np.sin(1.1 * J)
+    fy = 1.0 + 0.2 * np.cos(0.29 * I + 0.2) * np.sin(0.41 * J + 1.3) + 0.05 * np.cos(0.9 * I)
+    cut = (slice(pi * nx, pi * nx + nx + 2), slice(pj * ny, pj * ny + ny + 2))
+    return fx[cut].copy(), fy[cut].copy()
+
+
 def resting_column_state(nx, ny, nz):
     """u = v = 0, w = -1 except 0 at the bottom (mg_testseamount.f90:119-123), in the model's (i,j,k) layout:
     numpy shapes (nz, ny+2, nx+1), (nz, ny+1, nx+2), (nz+1, ny+2, nx+2)."""

@@ -40,6 +40,7 @@ def rank_main(rank, npx, npy, nx, ny, nz, nsmall, method, opts, stamp):
     uvw = "uvw" in opts            # random u, v, w: one global field cut per rank, so the copies of a shared face agree
     uvw_indep = "uvw_indep" in opts  # random u, v, w drawn per rank: the copies of a shared face disagree, and the reference takes the neighbour's flux there
     overlap0 = "overlap0" in opts  # the shipped default overlap = 0 (nhydro_solve as a model calls it) instead of the exchange beside the interior sweep
+    curv = "curv" in opts          # dx, dy times this rank's block of the global curvilinear metric (testcases.curvilinear_metric): dx(i,j), dy(i,j)
     model = uvw or uvw_indep       # ... and nhydro_solve on both sides afterwards: u, v, w per rank, bit for bit
     assert not model or method == "FC" or exact
     if connectfail:
@@ -65,7 +66,16 @@ def rank_main(rank, npx, npy, nx, ny, nz, nsmall, method, opts, stamp):
     stamp("init")
     geometry = rndtopo_geometry if rndtopo else seamount_geometry
     dx, dy, zeta, h = geometry(nx, ny, npx, npy, rank)
-    from mgroms_amd.testcases import island_mask, resting_column_state
+    from mgroms_amd.testcases import curvilinear_metric, island_mask, resting_column_state
+
+    def rank_metric(r):
+        """dx, dy of rank r"""
+        gx, gy = geometry(nx, ny, npx, npy, r)[:2]
+        if curv:
+            fx, fy = curvilinear_metric(nx, ny, npx, npy, r)
+            gx, gy = gx * fx, gy * fy
+        return gx, gy
+    dx, dy = rank_metric(rank)
     rmask = island_mask(nx, ny, npx, npy, rank) if bmask else None
     mg.nhydro_matrices(dx, dy, zeta, h, rmask, 4e3, 0.0, 0.0)
     def rank_uvw(r):
@@ -92,8 +102,10 @@ def rank_main(rank, npx, npy, nx, ny, nz, nsmall, method, opts, stamp):
     stamp("solve")
 
     o = make_seamount(nx, ny, nz, npx, npy, relax_method=method, solver_prec=tol, nsmall=nsmall, ns_coarsest=nsc, bmask=bmask, **mkw)
-    if bmask or rndtopo:  # rebuild the oracle's matrices with every rank's mask / topography in place
+    if bmask or rndtopo or curv:  # rebuild the oracle's matrices with every rank's mask / topography / metric in place
         for r in range(o.nranks):
+            if curv:
+                o.field("dx", 1, r)[...], o.field("dy", 1, r)[...] = rank_metric(r)
             if bmask:
                 o.field("rmask", 1, r)[...] = island_mask(nx, ny, npx, npy, r)
             if rndtopo:
@@ -110,8 +122,10 @@ def rank_main(rank, npx, npy, nx, ny, nz, nsmall, method, opts, stamp):
     gathered = [l for l in range(1, o.nlevs + 1) if o.level_info(l, rank)["gather"]]
     for lev in range(1, o.nlevs + 1):
         g = mg.grid(lev)
-        for name in ("h", "zr", "cA"):
+        for name in ("h", "zr", "cA") + (("dx", "dy") if curv else ()):   # (dx, dy: their halos between ranks and their coarsening)
             assert np.array_equal(g.get(name), o.field(name, lev, rank)), (rank, lev, name)
+    if curv:
+        assert np.ptp(mg.grid(1).get("dx")[1:-1, 0]) > 0 and np.ptp(mg.grid(1).get("dy")[0, 1:-1]) > 0   # the metric varies along the halo
     assert np.array_equal(mg.grid(1).b, o.field("b", 1, rank))
     assert n == no, (n, no)
     if method == "FC" or exact:

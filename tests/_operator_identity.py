@@ -16,7 +16,8 @@ import collections
 import numpy as np
 
 MIN_FRACTION = 0.70   # the set must hold at least this share of the columns, or the test has stopped looking at the domain
-# coupling_defect on the CPU oracle: at most 2.2e-15 over every case the GPU runs (the figures: tests/test_gpu_operator_identity.py);
+# coupling_defect on the CPU oracle: at most 2.2e-15 over every case the GPU runs, the curvilinear ones (at most 1.4e-15) included (the
+# figures: tests/test_gpu_operator_identity.py);
 # 16 x that, the margin for other seeds
 COUPLING_TOL = 3.5e-14
 MIN_LAND = 8          # with a mask: at least this many land columns and one coast column, or the rule excluded nothing
@@ -61,11 +62,15 @@ def scaled_defect(lhs, rhs, sel, *scale_by):
     return float(np.abs(lhs[sel] - rhs[sel]).max()) / scale
 
 
-def case_inputs(nx, ny, geom="seamount", mask=False, stretched=False):
+def case_inputs(nx, ny, geom="seamount", mask=False, stretched=False, curvilinear=False):
     """dx, dy, zeta, h, rmask (or None), hc, theta_b, theta_s of a case: the seamount or the random topography; the island mask; the
-    stretched sigma coordinate (theta_s = 6, theta_b = 0.4, hc = 250) under a rough free surface zeta = 0.3 N(0, 1)"""
-    from mgroms_amd.testcases import seamount_geometry, rndtopo_geometry, island_mask
+    stretched sigma coordinate (theta_s = 6, theta_b = 0.4, hc = 250) under a rough free surface zeta = 0.3 N(0, 1); curvilinear: dx,
+    dy times testcases.curvilinear_metric, a metric that varies in i and in j"""
+    from mgroms_amd.testcases import seamount_geometry, rndtopo_geometry, island_mask, curvilinear_metric
     dx, dy, zeta, h = (seamount_geometry if geom == "seamount" else rndtopo_geometry)(nx, ny)
+    if curvilinear:
+        fx, fy = curvilinear_metric(nx, ny)
+        dx, dy = dx * fx, dy * fy
     hc, theta_b, theta_s = 4e3, 0.0, 0.0
     if stretched:
         zeta = 0.3 * np.random.default_rng(99).standard_normal((nx + 2, ny + 2))
@@ -146,7 +151,8 @@ def inner(x, y):
 
 
 # ---- the cases of the sequence: asserted on the GPU (tests/test_gpu_operator_identity.py), measured on the oracle (tests/test_oracle.py) ----
-Case = collections.namedtuple("Case", "name dims geom mask stretched stored call_mask", defaults=("seamount", False, False, False, False))
+Case = collections.namedtuple("Case", "name dims geom mask stretched stored call_mask curvilinear",
+                              defaults=("seamount", False, False, False, False, False))
 
 CASES = [
     Case("seamount-32x16x8-stored", (32, 16, 8), stored=True),
@@ -158,12 +164,18 @@ CASES = [
     # runs it: tests/test_oracle.py::test_identity_direct_form): the nearest shape it serves that is not square and keeps nz = 12
     Case("rndtopo-island-stretched-24x16x12", (24, 16, 12), "rndtopo", mask=True, stretched=True),
     Case("call-mask-32x32x8", (32, 32, 8), mask=True, call_mask=True),   # bmask = 0, the island handed to the calls only
+    # dx(i,j), dy(i,j): every fetch of a 2-D metric factor, face average and coarsened metric is told apart from its neighbours'
+    Case("curvilinear-seamount-32x16x8-stored", (32, 16, 8), stored=True, curvilinear=True),
+    Case("curvilinear-seamount-64x32x64", (64, 32, 64), curvilinear=True),
+    Case("curvilinear-seamount-32x32x24", (32, 32, 24), curvilinear=True),
+    Case("curvilinear-island-32x32x96", (32, 32, 96), mask=True, curvilinear=True),
+    Case("curvilinear-rndtopo-island-stretched-24x16x12", (24, 16, 12), "rndtopo", mask=True, stretched=True, curvilinear=True),
 ]
 
 
 def oracle_coupling_defect(case, seed=1):
     """coupling_defect of a case on the CPU oracle, as the GPU test runs it (two four-colour iterations)"""
-    inp = case_inputs(*case.dims[:2], case.geom, case.mask, case.stretched)
+    inp = case_inputs(*case.dims[:2], case.geom, case.mask, case.stretched, case.curvilinear)
     o = make_oracle(*case.dims, inp, bmask=case.mask and not case.call_mask, solver_prec=1e-30, solver_maxiter=2)
     try:
         return coupling_defect(OracleBackend(o), *case.dims, inp["rmask"], seed)

@@ -11,14 +11,21 @@ import numpy as np
 SIGMA = (4e3, 0.0, 0.0)
 
 
-def _geometry(geom, nx, ny, npx=1, npy=1, rank=0):
+def _geometry(geom, nx, ny, npx=1, npy=1, rank=0, metric="uniform"):
+    """dx, dy, zeta, h of one rank; metric="curvilinear": dx, dy times that rank's block of testcases.curvilinear_metric"""
     from mgroms_amd import testcases
-    return {"seamount": testcases.seamount_geometry, "rndtopo": testcases.rndtopo_geometry}[geom](nx, ny, npx, npy, rank)
+    dx, dy, zeta, h = {"seamount": testcases.seamount_geometry, "rndtopo": testcases.rndtopo_geometry}[geom](nx, ny, npx, npy, rank)
+    assert metric in ("uniform", "curvilinear"), metric
+    if metric == "curvilinear":
+        fx, fy = testcases.curvilinear_metric(nx, ny, npx, npy, rank)
+        dx, dy = dx * fx, dy * fy
+    return dx, dy, zeta, h
 
 
-def problem(dims, geom="seamount", bmask=False, rmask=None, zeta=None, sigma=SIGMA, **par):
+def problem(dims, geom="seamount", bmask=False, rmask=None, zeta=None, sigma=SIGMA, metric="uniform", **par):
     """The record of a one-rank problem: dims, the namelist members, (dx, dy, zeta, h), the mask and the sigma triple.  bmask: the masked
-    system, with `rmask` or the island mask; zeta: instead of the generator's."""
+    system, with `rmask` or the island mask; zeta: instead of the generator's; metric: "uniform", the generator's constant dx, dy, or
+    "curvilinear", those times testcases.curvilinear_metric (dx(i,j), dy(i,j))."""
     from mgroms_amd.testcases import island_mask
     nx, ny, nz = dims
     if bmask:
@@ -26,10 +33,10 @@ def problem(dims, geom="seamount", bmask=False, rmask=None, zeta=None, sigma=SIG
         rmask = island_mask(nx, ny) if rmask is None else rmask
     else:
         assert rmask is None
-    dx, dy, z0, h = _geometry(geom, nx, ny)
+    dx, dy, z0, h = _geometry(geom, nx, ny, metric=metric)
     if zeta is not None:
         z0 = zeta
-    return SimpleNamespace(dims=(nx, ny, nz), geom=geom, par=par, fields=(dx, dy, z0, h), rmask=rmask, sigma=tuple(sigma))
+    return SimpleNamespace(dims=(nx, ny, nz), geom=geom, metric=metric, par=par, fields=(dx, dy, z0, h), rmask=rmask, sigma=tuple(sigma))
 
 
 def on_gpu(mg, pr, init_options=None):
@@ -52,7 +59,7 @@ def gpu_problem(mg, dims, init_options=None, **kw):
 def oracle_twin(problem, npx=1, npy=1, only=None):
     """The Oracle of `problem`: every parameter of the record that Oracle.__init__ accepts (only=: just these names -- for a file whose oracle
     deliberately keeps its defaults for the rest), the record's fields, mask and sigma.  npx x npy: the same global problem on emulated ranks,
-    each with its block of the generators' geometry."""
+    each with its block of the generators' geometry under the metric the record names."""
     from oracle.mgoracle import Oracle
     nx, ny, nz = problem.dims
     accepted = set(inspect.signature(Oracle.__init__).parameters) - {"self", "nx", "ny", "nz", "npx", "npy"}
@@ -68,10 +75,10 @@ def load(o, problem):
     nx, ny, _ = problem.dims
     one = o.nranks == 1
     if not one:    # every rank makes its own block: the record must hold the generators' fields, not the caller's own
-        assert all(np.array_equal(a, c) for a, c in zip(problem.fields, _geometry(problem.geom, nx, ny)))
+        assert all(np.array_equal(a, c) for a, c in zip(problem.fields, _geometry(problem.geom, nx, ny, metric=problem.metric)))
         assert problem.rmask is None or np.array_equal(problem.rmask, island_mask(nx, ny))
     for r in range(o.nranks):
-        dx, dy, zeta, h = problem.fields if one else _geometry(problem.geom, o.nx, o.ny, o.npx, o.npy, r)
+        dx, dy, zeta, h = problem.fields if one else _geometry(problem.geom, o.nx, o.ny, o.npx, o.npy, r, problem.metric)
         for name, a in (("dx", dx), ("dy", dy), ("zeta", zeta), ("h", h)):
             o.field(name, 1, r)[...] = a
         if problem.rmask is not None:

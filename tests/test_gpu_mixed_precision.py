@@ -87,8 +87,22 @@ def _restore(mg, lev, vals):
 @pytest.mark.parametrize("dims", [(64, 64, 16), (128, 128, 48)])
 @pytest.mark.parametrize("method", ["FC", "RB"])
 def test_operators_match_fp64(mg, dims, method):
+    _operators_match_fp64(mg, dims, method)
+
+
+@pytest.mark.parametrize("method", ["FC", "RB"])
+def test_operators_match_fp64_on_a_curvilinear_metric(mg, method):
+    """the same comparison on dx(i,j), dy(i,j) (testcases.curvilinear_metric): the fp32 kernels fetch their 2-D metric factors by the
+    index arithmetic of the fp64 ones, and a factor taken one column off moves the result by the metric's variation (per cent), far
+    above 1e-5"""
+    _operators_match_fp64(mg, (64, 64, 16), method, metric="curvilinear")
+    dx, dy = mg.grid(1).get("dx"), mg.grid(1).get("dy")
+    assert np.ptp(dx, axis=0).min() > 0 and np.ptp(dx, axis=1).min() > 0 and np.ptp(dy, axis=0).min() > 0 and np.ptp(dy, axis=1).min() > 0
+
+
+def _operators_match_fp64(mg, dims, method, **kw):
     nx, ny, nz = dims
-    _setup(mg, nx, ny, nz, relax_method=method)
+    _setup(mg, nx, ny, nz, relax_method=method, **kw)
     mg.nhydro.set_option("rb_seq", 0)   # the fp32 red-black pass is the parallel one
     rng = np.random.default_rng(7)
     nl = mg.nlevs()

@@ -39,6 +39,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
     (2, 1, 64, 128, 64, 8, "FC+uvw+overlap0"),        # one global field cut per rank; nz = 64 (the bench's level-1 kernels) with an open side
     (2, 2, 16, 16, 8, 8, "FC+bmask+uvw_indep+overlap0"),  # bmask: no flux exchange (mg_compute_rhs.f90:170, 271), the local faces stay
     (1, 2, 16, 32, 8, 8, "FC+uvw+overlap0"),          # N/S only, ragged block
+    # dx(i,j), dy(i,j): every rank takes its block of one global curvilinear metric -- the dx, dy halos between ranks, their coarsening
+    # across the gather, and the flux faces of compute_rhs / correct_uvw under a metric that differs from face to face
+    (2, 2, 16, 16, 8, 8, "FC+curv+uvw+overlap0"),
+    (2, 1, 32, 16, 16, 8, "FC+curv+bmask+uvw_indep+overlap0"),
 ])
 def test_multirank_solve(npx, npy, nx, ny, nz, nsmall, method):
     world = npx * npy

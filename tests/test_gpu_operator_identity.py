@@ -12,12 +12,15 @@ max(|b|, |A p*|).  A wrong coefficient, slot, sign, metric factor or index in an
 one slot of cA: test_a_perturbed_slot_is_seen).
 
 TOL.  The same sequence on the CPU oracle (OracleBackend; tests/test_oracle.py::test_identity_through_the_model_calls prints the
-first seven), with the seeds used here, gives
+cases of the list), with the seeds used here, gives
 
     seamount-32x16x8-stored 3.3e-16       seamount-64x32x64 7.1e-16 (either path)    seamount-32x32x24 6.3e-16
     island-32x32x96 1.1e-15               rndtopo-island-stretched-24x16x12 9.7e-16  call-mask-32x32x8 3.4e-16
     zeta refresh 32x32x16: 2.2e-15 before, 1.6e-15 after                             the unperturbed case of the slot test 3.9e-16
     run layouts: 16x16x2 3.5e-16, 64x64x16 6.5e-16, 256x512x96 6.7e-16, 512x512x48 5.1e-16, 512x512x64 6.9e-16
+    on the curvilinear metric (dx(i,j), dy(i,j): testcases.curvilinear_metric)
+    seamount-32x16x8-stored 3.4e-16       seamount-64x32x64 6.1e-16                  seamount-32x32x24 4.5e-16
+    island-32x32x96 1.0e-15               rndtopo-island-stretched-24x16x12 1.4e-15
 
 and TOL = 16 x the largest of them = 16 x 2.2e-15 = 3.5e-14 (COUPLING_TOL).  The margin is for other seeds and nothing else: b, r
 and b' are reduction-free fields which the GPU computes in the oracle's operation order without FMA contraction, bit for bit where
@@ -80,7 +83,7 @@ def test_identity(mg, case, monkeypatch):
     """b' = r on the water-interior set, every case within TOL (module docstring).  call-mask: bmask = 0, so the matrix and correct_uvw
     see no land, and compute_rhs drops the w cross terms on the land of the call's mask (mg_compute_rhs.f90:110-111): by design the
     identity then holds on the set built from the CALL's mask and fails at its coast (measured on the oracle: 1e-2 of max|A p|)."""
-    inp = case_inputs(*case.dims[:2], case.geom, case.mask, case.stretched)
+    inp = case_inputs(*case.dims[:2], case.geom, case.mask, case.stretched, case.curvilinear)
     bmask = case.mask and not case.call_mask
     _init(mg, case.dims, bmask, monkeypatch, case.stored)
     mg.nhydro_matrices(inp["dx"], inp["dy"], inp["zeta"], inp["h"], inp["rmask"] if bmask else None, inp["hc"], inp["theta_b"], inp["theta_s"])

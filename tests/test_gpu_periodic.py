@@ -64,8 +64,10 @@ def _wrapped(x, c, periodic):
     return d - np.round(d) if periodic else d
 
 
-def geometry(nx, ny, per, stretched=False, seed=7, island=False):
-    """interiors (nx, ny) of dx, dy, zeta, h and, with `island`, of a mask whose island straddles the seam(s)"""
+def geometry(nx, ny, per, stretched=False, seed=7, island=False, curvilinear=False):
+    """interiors (nx, ny) of dx, dy, zeta, h and, with `island`, of a mask whose island straddles the seam(s).  curvilinear: dx(i,j),
+    dy(i,j) -- each varies in both directions, with whole wave numbers over nx and ny, so that it is periodic in whichever direction
+    wraps; not separable, and dy is no transpose or shift of dx"""
     rng = np.random.default_rng(seed)
     x = (np.arange(1, nx + 1) - 0.5) / nx
     y = (np.arange(1, ny + 1) - 0.5) / ny
@@ -74,6 +76,11 @@ def geometry(nx, ny, per, stretched=False, seed=7, island=False):
     h = 4e3 * (1.0 - 0.5 * np.exp(-ex ** 2 - ey ** 2)) * (1.0 + 0.02 * (2.0 * rng.random((nx, ny)) - 1.0))
     dx = np.repeat((1e4 / nx * (1.0 + 0.1 * np.sin(2 * np.pi * np.arange(1, nx + 1) / nx)))[:, None], ny, axis=1)
     dy = np.repeat((1e4 / ny * (1.0 + 0.1 * np.sin(2 * np.pi * np.arange(1, ny + 1) / ny)))[None, :], nx, axis=0)
+    if curvilinear:
+        ti = (2 * np.pi * np.arange(1, nx + 1) / nx)[:, None]
+        tj = (2 * np.pi * np.arange(1, ny + 1) / ny)[None, :]
+        dx = dx * (1.0 + 0.08 * np.sin(2 * ti + tj + 0.7) + 0.04 * np.cos(3 * tj))
+        dy = dy * (1.0 + 0.08 * np.cos(ti - 2 * tj + 0.3) + 0.04 * np.sin(3 * ti))
     zeta = 0.3 * rng.standard_normal((nx, ny)) if stretched else np.zeros((nx, ny))
     g = dict(dx=dx, dy=dy, zeta=zeta, h=h, rmask=None, hc=250.0 if stretched else HC, theta_b=0.4 if stretched else 0.0, theta_s=6.0 if stretched else 0.0)
     if island:
@@ -256,12 +263,16 @@ SHIFT_CASES = [
     ((32, 16, 8), 3, 0, 8, False, False, False, True),
     ((32, 32, 24), 2, 1, 16, False, False, False, True),
     ((64, 32, 64), 1, 0, 16, False, False, False, True),
+    # a ninth entry: dx(i,j), dy(i,j), periodic in both directions (geometry(curvilinear=True))
+    ((32, 16, 8), 3, 1, 8, False, False, False, False, True),
+    ((64, 32, 64), 3, 0, 16, False, False, False, False, True),
 ]
 
 
 def _shift_id(c):
-    d, per, ax, s, stored, island, stretched, rb = c
-    return "%dx%dx%d-per%d-%s%d%s%s%s%s" % (*d, per, "ij"[ax], s, "-stored" if stored else "", "-island" if island else "", "-stretched" if stretched else "", "-rb" if rb else "")
+    d, per, ax, s, stored, island, stretched, rb = c[:8]
+    return "%dx%dx%d-per%d-%s%d%s%s%s%s%s" % (*d, per, "ij"[ax], s, "-stored" if stored else "", "-island" if island else "", "-stretched" if stretched else "", "-rb" if rb else "",
+                                            "-curvilinear" if c[8:] == (True,) else "")
 
 
 @pytest.mark.parametrize("case", SHIFT_CASES, ids=[_shift_id(c) for c in SHIFT_CASES])
@@ -274,7 +285,8 @@ def test_shift_equivariance(mg, case, monkeypatch):
     Four colours, matrix-free and stored slots (MGX_NO_MF, which every nhydro_init reads), bmask with an island that straddles the seam, the
     stretched coordinate, both directions; red-black as the snapshot pass (rb_seq = 0, rb_exact = 0: the sequential order is not shift
     invariant).  The first run's inputs carry not-a-numbers in the halo entries of the periodic directions: they are ignored."""
-    dims, per, axis, s, stored, island, stretched, rb = case
+    dims, per, axis, s, stored, island, stretched, rb = case[:8]
+    curvilinear = case[8:] == (True,)
     nx, ny, nz = dims
     mg.nhydro_clean()
     mg.nhydro.set_option("rb_seq", 0 if rb else 1); mg.nhydro.set_option("rb_exact", 0)
@@ -282,7 +294,7 @@ def test_shift_equivariance(mg, case, monkeypatch):
         _init(mg, dims, per, monkeypatch, stored, relax_method="RB" if rb else "FC", solver_prec=1e-30, solver_maxiter=3, bmask=1 if island else 0)
         nlev = mg.nlevs()
         assert s % (1 << nlev) == 0 and per & (1 << axis)
-        g = geometry(nx, ny, per, stretched, island=island)
+        g = geometry(nx, ny, per, stretched, island=island, curvilinear=curvilinear)
         bases = velocity_bases(nx, ny, nz, per, 11)
         a = _outputs(mg, dims, per, g, bases, poison=True)
         g2, bases2 = _roll_inputs(g, bases, s, axis)
@@ -388,12 +400,17 @@ IDENTITY_CASES = [
     ((64, 32, 64), 1, False, False, False),
     ((64, 32, 64), 2, True, False, False),
     ((64, 32, 64), 3, False, False, True),
+    # a sixth entry: dx(i,j), dy(i,j), periodic in both directions (geometry(curvilinear=True))
+    ((32, 16, 8), 3, False, False, True, True),
+    ((64, 32, 64), 3, False, False, False, True),
+    ((32, 32, 24), 1, True, True, False, True),
 ]
 
 
 def _identity_id(c):
-    d, per, island, stretched, stored = c
-    return "%dx%dx%d-per%d%s%s%s" % (*d, per, "-island" if island else "", "-stretched" if stretched else "", "-stored" if stored else "")
+    d, per, island, stretched, stored = c[:5]
+    return "%dx%dx%d-per%d%s%s%s%s" % (*d, per, "-island" if island else "", "-stretched" if stretched else "", "-stored" if stored else "",
+                                       "-curvilinear" if c[5:] == (True,) else "")
 
 
 @pytest.mark.parametrize("case", IDENTITY_CASES, ids=[_identity_id(c) for c in IDENTITY_CASES])
@@ -401,9 +418,11 @@ def test_identity_across_the_seam(mg, case, monkeypatch):
     """No oracle call and no ring in a periodic direction: the set holds the seam columns.  The direct form and the sequence through
     nhydro_solve, both within COUPLING_TOL = 3.5e-14 (the CPU oracle keeps the identity to 4.5e-16 at an open seam of a 2 x 1
     decomposition on these geometries, as on the interior)."""
-    dims, per, island, stretched, stored = case
+    dims, per, island, stretched, stored = case[:5]
     nx, ny, nz = dims
-    g = geometry(nx, ny, per, stretched, island=island)
+    g = geometry(nx, ny, per, stretched, island=island, curvilinear=case[5:] == (True,))
+    if case[5:] == (True,):   # the metric varies along every row and every column
+        assert all(np.ptp(g[n], axis=a).min() > 0 for n in ("dx", "dy") for a in (0, 1))
     rmask = full2d(g, per)["rmask"]
     sel = periodic_set(rmask, nx, ny, per)
     assert_periodic_set(sel, rmask, per)

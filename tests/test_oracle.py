@@ -127,6 +127,31 @@ def test_fc_is_decomposition_independent_on_4x2(npx, npy, nsmall):
         assert np.array_equal(blk, p1[1 + pi * nx:1 + (pi + 1) * nx, 1 + pj * ny:1 + (pj + 1) * ny, :]), r
 
 
+@pytest.mark.parametrize("npx,npy", [(2, 2), (2, 1)])
+def test_fc_is_decomposition_independent_on_a_curvilinear_metric(npx, npy):
+    """The same on dx(i,j), dy(i,j) (testcases.curvilinear_metric) from seeded random u, v, w: every rank takes its block of the global
+    metric, so the dx, dy halos between ranks and the face averages across a rank boundary carry values that differ from both
+    neighbours'; p of every rank is the one-rank p bit for bit, the history within the same bound"""
+    from _problem import load_uvw, oracle_twin, problem, uvw
+    dims = (32, 32, 8)
+    pr = problem(dims, metric="curvilinear", relax_method="FC", solver_prec=1e-8)
+    state = uvw(dims, seed=3)
+    one, many = oracle_twin(pr), oracle_twin(pr, npx, npy)
+    assert np.ptp(one.field("dx")) > 0 and np.ptp(one.field("dy")) > 0
+    for o in (one, many):
+        load_uvw(o, state)
+    n1, h1, _ = one.nhydro_solve()
+    n2, h2, _ = many.nhydro_solve()
+    assert n1 == n2 and n1 < 30
+    assert np.all(np.abs(h1 - h2) <= 1e-14 + 1e-13 * h1)
+    p1 = one.field("p")
+    nx, ny = 32 // npx, 32 // npy
+    for r in range(npx * npy):
+        pi, pj = r % npx, r // npx
+        blk = many.field("p", 1, r)[1:-1, 1:-1, :]
+        assert np.array_equal(blk, p1[1 + pi * nx:1 + (pi + 1) * nx, 1 + pj * ny:1 + (pj + 1) * ny, :]), r
+
+
 def _bmask_world(nx, ny, nz, npx, npy):
     from _problem import load_uvw, oracle_twin, problem, uvw
     o = oracle_twin(problem((nx * npx, ny * npy, nz), bmask=True, relax_method="FC", solver_prec=1e-8), npx, npy)
@@ -313,6 +338,8 @@ _IDENTITY_CASES = {
     "rndtopo-island-stretched-24x20x12": ((24, 20, 12), "rndtopo", True, True, True),
     "seamount-32x32x24": ((32, 32, 24), "seamount", False, False, False),   # levels of 24, 12, 6, 3 rows
     "call-mask-32x32x8": ((32, 32, 8), "seamount", True, False, False),     # bmask = 0: the island is handed to the calls only
+    # the name's prefix: dx, dy times testcases.curvilinear_metric, a metric that varies in i and in j
+    "curvilinear-rndtopo-island-stretched-24x20x12": ((24, 20, 12), "rndtopo", True, True, True),
 }
 _DIRECT_TOL = 1.1e-14   # 16 x 6.7e-16 (test_identity_direct_form)
 
@@ -320,7 +347,7 @@ _DIRECT_TOL = 1.1e-14   # 16 x 6.7e-16 (test_identity_direct_form)
 def _identity_world(name):
     from _operator_identity import case_inputs, make_oracle, water_interior, assert_set_is_meaningful
     (nx, ny, nz), geom, mask, stretched, bmask = _IDENTITY_CASES[name]
-    inp = case_inputs(nx, ny, geom, mask, stretched)
+    inp = case_inputs(nx, ny, geom, mask, stretched, curvilinear=name.startswith("curvilinear-"))
     o = make_oracle(nx, ny, nz, inp, bmask=bmask)
     sel = water_interior(inp["rmask"], nx, ny)
     assert_set_is_meaningful(sel, inp["rmask"])
@@ -347,6 +374,7 @@ def test_identity_direct_form(name):
     Measured max|lhs - rhs| / max|A p| on the set (this seed; eight seeds stay below 6.7e-16):
         seamount-16x16x8 3.5e-16   rndtopo-24x20x12 5.4e-16   seamount-island-32x32x8 3.7e-16
         rndtopo-island-stretched-24x20x12 6.7e-16   seamount-32x32x24 5.3e-16   call-mask-32x32x8 3.7e-16
+        curvilinear-rndtopo-island-stretched-24x20x12 (dx(i,j), dy(i,j): testcases.curvilinear_metric) 3.6e-16
     Bound: 16 x the largest = 1.1e-14, the margin for other seeds and summation lengths.  Outside the set the same figure is
     5e-4 (seamount), 2e-5 (rndtopo), 9e-4 (island coast), 9e-7 (stretched rndtopo): the reference's own inconsistency.
 

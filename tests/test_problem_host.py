@@ -117,10 +117,23 @@ def test_gpu_and_oracle_are_given_the_same_problem(oracle_calls, dims, case, onl
 @pytest.mark.parametrize("geom,bmask", [("seamount", False), ("rndtopo", False), ("seamount", True), ("rndtopo", True)])
 def test_emulated_ranks_hold_the_blocks_of_the_same_problem(oracle_calls, geom, bmask):
     """2 x 2 emulated ranks of 8 x 8 x 8: every rank's fields are its block (with halo) of what the one GPU rank was given"""
+    _emulated_ranks_hold_the_blocks(geom, bmask, "uniform")
+
+
+@pytest.mark.parametrize("geom,bmask", [("seamount", False), ("rndtopo", False), ("seamount", True), ("rndtopo", True)])
+def test_emulated_ranks_hold_the_blocks_of_the_curvilinear_problem(oracle_calls, geom, bmask):
+    """the same with metric="curvilinear": every rank holds its block of the one global dx(i,j), dy(i,j), the halo columns it shares
+    with its neighbours included"""
+    _emulated_ranks_hold_the_blocks(geom, bmask, "curvilinear")
+
+
+def _emulated_ranks_hold_the_blocks(geom, bmask, metric):
     mg = Recorder()
-    pr = _problem.gpu_problem(mg, (16, 16, 8), geom=geom, bmask=bmask, **PAR)
+    pr = _problem.gpu_problem(mg, (16, 16, 8), geom=geom, bmask=bmask, metric=metric, **PAR)
+    assert pr.metric == metric
     o = _problem.oracle_twin(pr, 2, 2)
     par, _, fields, rmask, sigma = _given(mg)
+    assert (np.ptp(fields[0]) > 0 and np.ptp(fields[1]) > 0) == (metric == "curvilinear")
     assert (o.nx, o.ny, o.nz, o.npx, o.npy) == (8, 8, 8, 2, 2) and o.sigma == sigma
     assert o.init_kw == {k: v for k, v in par.items() if k in ORACLE_PARAMETERS}
     for r in range(4):
@@ -134,6 +147,63 @@ def test_emulated_ranks_hold_the_blocks_of_the_same_problem(oracle_calls, geom, 
     pr.fields = (pr.fields[0], pr.fields[1], pr.fields[2] + 1.0, pr.fields[3])
     with pytest.raises(AssertionError):
         _problem.oracle_twin(pr, 2, 2)
+    # nor has a record whose fields are another metric's than the one it names
+    other = "uniform" if metric == "curvilinear" else "curvilinear"
+    wrong = _problem.problem((16, 16, 8), geom=geom, bmask=bmask, metric=metric, **PAR)
+    wrong.metric = other
+    with pytest.raises(AssertionError):
+        _problem.oracle_twin(wrong, 2, 2)
+
+
+@pytest.mark.parametrize("dims", [(16, 16, 8), (8, 16, 2)], ids=lambda d: "%dx%dx%d" % d)
+@pytest.mark.parametrize("geom", ["seamount", "rndtopo"])
+def test_the_curvilinear_problem_is_the_generators_times_the_metric(oracle_calls, dims, geom):
+    """metric="curvilinear" multiplies the generator's dx, dy by testcases.curvilinear_metric and leaves zeta, h alone; both sides get it"""
+    nx, ny, _ = dims
+    mg = Recorder()
+    pr = _problem.gpu_problem(mg, dims, geom=geom, metric="curvilinear", **PAR)
+    o = _problem.oracle_twin(pr)
+    plain = _problem.problem(dims, geom=geom, **PAR)
+    assert plain.metric == "uniform" and pr.metric == "curvilinear"
+    fx, fy = testcases.curvilinear_metric(nx, ny)
+    _, _, fields, _, _ = _given(mg)
+    assert np.array_equal(fields[0], plain.fields[0] * fx) and np.array_equal(fields[1], plain.fields[1] * fy)
+    assert np.array_equal(fields[2], plain.fields[2]) and np.array_equal(fields[3], plain.fields[3])
+    for name, a in zip(("dx", "dy", "zeta", "h"), fields):
+        assert np.array_equal(o.found[name][0], a), name
+    with pytest.raises(AssertionError):
+        _problem.problem(dims, geom=geom, metric="stretched", **PAR)
+
+
+def test_curvilinear_metric_varies_in_both_directions_on_every_rank():
+    """fx, fy are defined on global indices: within [0.75, 1.25]; each varies along both axes, is neither symmetric nor separable, and
+    neither is the other or a one-cell shift of it; a rank of a process grid holds its block of the one-rank arrays, the halo columns
+    it shares with its neighbours included"""
+    for nxg, nyg in ((32, 32), (32, 16), (48, 96)):
+        fx, fy = testcases.curvilinear_metric(nxg, nyg)
+        for f in (fx, fy):
+            assert f.shape == (nxg + 2, nyg + 2) and f.dtype == np.float64
+            assert 0.75 <= f.min() and f.max() <= 1.25
+            assert np.all(np.ptp(f, axis=0) > 1e-3) and np.all(np.ptp(f, axis=1) > 1e-3)      # every row and every column varies
+            assert np.linalg.matrix_rank(f - f.mean(), tol=1e-6) >= 2                       # not a(i) + b(j), so not a(i) * b(j) either
+            assert np.abs(np.diff(f, axis=0)).min() > 0 and np.abs(np.diff(f, axis=1)).min() > 0   # no two neighbours are equal
+        if nxg == nyg:
+            assert np.abs(fx - fx.T).max() > 1e-2 and np.abs(fy - fy.T).max() > 1e-2
+            assert np.abs(fx - fy.T).max() > 1e-2
+        assert np.abs(fx - fy).max() > 1e-2
+        for a, c in ((fx[1:], fy[:-1]), (fx[:-1], fy[1:]), (fx[:, 1:], fy[:, :-1]), (fx[:, :-1], fy[:, 1:])):
+            assert np.abs(a - c).max() > 1e-2
+    fx, fy = testcases.curvilinear_metric(32, 32)
+    assert not np.array_equal(fx, fx.T)
+    for npx, npy in ((2, 2), (2, 1), (1, 2), (4, 2)):
+        nx, ny = 32 // npx, 32 // npy
+        for rank in range(npx * npy):
+            pi, pj = rank % npx, rank // npx
+            block = (slice(nx * pi, nx * pi + nx + 2), slice(ny * pj, ny * pj + ny + 2))
+            bx, by = testcases.curvilinear_metric(nx, ny, npx, npy, rank)
+            assert np.array_equal(bx, fx[block]) and np.array_equal(by, fy[block]), (npx, npy, rank)
+            dx = _problem._geometry("seamount", nx, ny, npx, npy, rank, "curvilinear")[0]
+            assert np.array_equal(dx, _problem._geometry("seamount", 32, 32, metric="curvilinear")[0][block])
 
 
 def test_init_options_are_set_between_clean_and_init():
