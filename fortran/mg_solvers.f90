@@ -40,6 +40,17 @@ module mgx_c
        real(c_double), intent(inout) :: u(*), v(*), w(*)
        type(c_ptr), value :: rmask
      end function mgx_check_nondivergence
+     ! the float state: u, v, w in single precision, the mask as ever (include/mgx.h)
+     integer(c_int) function mgx_solve_f32(u, v, w, rmask) bind(C, name='mgx_solve_f32')
+       import :: c_int, c_float, c_ptr
+       real(c_float), intent(inout) :: u(*), v(*), w(*)
+       type(c_ptr), value :: rmask
+     end function mgx_solve_f32
+     integer(c_int) function mgx_check_nondivergence_f32(u, v, w, rmask) bind(C, name='mgx_check_nondivergence_f32')
+       import :: c_int, c_float, c_ptr
+       real(c_float), intent(inout) :: u(*), v(*), w(*)
+       type(c_ptr), value :: rmask
+     end function mgx_check_nondivergence_f32
      ! the set-up half of a device-resident time step: every array argument is a DEVICE pointer (include/mgx.h)
      integer(c_int) function mgx_matrices_device(dx, dy, zeta, h, rmask, hc, theta_b, theta_s) bind(C, name='mgx_matrices_device')
        import :: c_int, c_double, c_ptr

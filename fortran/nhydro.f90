@@ -75,6 +75,28 @@ contains
     call mgx_check(mgx_check_nondivergence(ua, va, wa, c_loc(rmaska)), 'nhydro_check_nondivergence')
   end subroutine nhydro_check_nondivergence
 
+  !--------------------------------------------------------------  (no counterpart in the reference, whose state is real(kind=rp))
+  ! The same two calls for a model that keeps u, v, w in single precision: each element comes back as real(x, 4) of the x that
+  ! nhydro_solve leaves when it is given real(ua, 8), real(va, 8), real(wa, 8) -- b, p and the iteration count are those of that
+  ! call, bit for bit (include/mgx.h: the float state).  The mask stays real(kind=rp).
+  subroutine nhydro_solve_r4(nx, ny, nz, rmaska, ua, va, wa)
+    integer(kind=ip), intent(in) :: nx, ny, nz
+    real(kind=rp), dimension(0:nx+1,0:ny+1)     , target, intent(inout) :: rmaska
+    real(c_float), dimension(1:nx+1,0:ny+1,1:nz), target, intent(inout) :: ua
+    real(c_float), dimension(0:nx+1,1:ny+1,1:nz), target, intent(inout) :: va
+    real(c_float), dimension(0:nx+1,0:ny+1,0:nz), target, intent(inout) :: wa
+    call mgx_check(mgx_solve_f32(ua, va, wa, c_loc(rmaska)), 'nhydro_solve_r4')
+  end subroutine nhydro_solve_r4
+
+  subroutine nhydro_check_nondivergence_r4(nx, ny, nz, rmaska, ua, va, wa)
+    integer(kind=ip), intent(in) :: nx, ny, nz
+    real(kind=rp), dimension(0:nx+1,0:ny+1)     , target, intent(inout) :: rmaska
+    real(c_float), dimension(1:nx+1,0:ny+1,1:nz), target, intent(inout) :: ua
+    real(c_float), dimension(0:nx+1,1:ny+1,1:nz), target, intent(inout) :: va
+    real(c_float), dimension(0:nx+1,0:ny+1,0:nz), target, intent(inout) :: wa
+    call mgx_check(mgx_check_nondivergence_f32(ua, va, wa, c_loc(rmaska)), 'nhydro_check_nondivergence_r4')
+  end subroutine nhydro_check_nondivergence_r4
+
   !--------------------------------------------------------------  (no counterpart in the reference, whose model lives on the host)
   ! The set-up half of a time step for a model that keeps its state on the GPU: every argument is the DEVICE address of an array in the
   ! layout of the host call of the same name (c_null_ptr for an absent rmask).  nhydro_update_zeta_device is the per-step call: a new

@@ -118,6 +118,30 @@ int mgx_update_zeta_device(const double *zeta_dev);
  * pointers and are only read; the divergence is left in grid(1)%b.  Waits for the device. */
 int mgx_check_nondivergence_device(double *u_dev, double *v_dev, double *w_dev, const double *rmask_dev);
 
+/* ---- the float state: the model keeps u, v, w in single precision (no Fortran counterpart in the reference) ----
+ * The contract, for float arrays u32, v32, w32 in the layouts of mgx_solve:
+ *   mgx_solve_device_f32(u32, v32, w32, rmask) leaves in every element exactly (float) x, where x is what mgx_solve_device leaves in that
+ *   element when called on (double) u32, (double) v32, (double) w32 under the same options.
+ * The conversion rounds to nearest, ties to even; subnormal float results are kept; the sign of zero is kept; elements that correct_uvw
+ * does not write come back with unchanged bits.  What follows from it:
+ * - grid(1)%b, the residual history, *nite and p are bit-identical to the fp64 call on the promoted input: promotion is exact, and b is
+ *   formed in fp64 by the same expressions (one text of every formula serves both state types, mgx_model.hip).
+ * - each element of u, v, w is rounded once, at its store: correct_uvw computes in fp64, and one thread reads and writes each element once.
+ * - rmask stays const double *, as in every other entry: it is 2-D, and mgx_matrices takes it as double anyway.
+ * - every option composes and is served as in the fp64 call (relax_method, "krylov", "cycle_precision" = 32, "warm_start", bmask, the
+ *   per-call mask, "periodic", "hold_odd_nz", process grids: the flux faces neighbours exchange are fp64 either way).
+ * - no conversion pass and no 3-D allocation: each entry issues the kernel launches of its fp64 twin (mgx_counters), on the model's own
+ *   float arrays (the device entries) or on the first half of the library's staging buffers (the host entries).
+ * Rows of u hold nx + 1 floats, rows of v and w nx + 2: the arrays need the alignment of a float, no more.
+ * A NULL u, v or w is refused with the entry's name in mgx_last_error().
+ * mgx_solve_device_f32 / mgx_check_nondivergence_device_f32: DEVICE pointers, the twins of mgx_solve_device / mgx_check_nondivergence_device. */
+int mgx_solve_device_f32(float *u_dev, float *v_dev, float *w_dev, const double *rmask_dev);
+int mgx_check_nondivergence_device_f32(float *u_dev, float *v_dev, float *w_dev, const double *rmask_dev);
+/* ... and on host arrays: the twins of mgx_solve, mgx_compute_rhs and mgx_check_nondivergence (floats cross PCIe, half the bytes) */
+int mgx_solve_f32(float *u, float *v, float *w, const double *rmask);
+int mgx_compute_rhs_f32(const float *u, const float *v, const float *w, const double *rmask);
+int mgx_check_nondivergence_f32(float *u, float *v, float *w, const double *rmask);
+
 /* mg_solvers.f90:17-101 solve_p(tol,maxite).  *nite = iterations done, *res = last ||r||/||b||,
  * hist (may be NULL, else >= maxite+1 doubles) = normalised residual after each iteration, hist[0] = initial. */
 int mgx_solve_p(double tol, int maxite, int *nite, double *res, double *hist);

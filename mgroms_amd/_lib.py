@@ -25,6 +25,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_int)
 
 _DP = C.POINTER(C.c_double)
+_FP = C.POINTER(C.c_float)
 _SIGS = {
     "mgx_params_default": (C.c_int, [C.POINTER(Params)]),
     "mgx_read_namelist": (C.c_int, [C.c_char_p, C.POINTER(Params)]),
@@ -36,6 +37,11 @@ _SIGS = {
     "mgx_matrices_device": (C.c_int, [C.c_void_p] * 5 + [C.c_double] * 3),
     "mgx_update_zeta_device": (C.c_int, [C.c_void_p]),
     "mgx_check_nondivergence_device": (C.c_int, [C.c_void_p] * 4),
+    "mgx_solve_device_f32": (C.c_int, [C.c_void_p] * 4),
+    "mgx_check_nondivergence_device_f32": (C.c_int, [C.c_void_p] * 4),
+    "mgx_solve_f32": (C.c_int, [_FP, _FP, _FP, _DP]),
+    "mgx_compute_rhs_f32": (C.c_int, [_FP, _FP, _FP, _DP]),
+    "mgx_check_nondivergence_f32": (C.c_int, [_FP, _FP, _FP, _DP]),
     "mgx_clean": (None, []),
     "mgx_solve_p": (C.c_int, [C.c_double, C.c_int, C.POINTER(C.c_int), _DP, _DP]),
     "mgx_fcycle": (C.c_int, []),

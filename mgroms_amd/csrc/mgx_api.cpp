@@ -279,67 +279,86 @@ int mgx_update_zeta_device(const double *zeta_dev) {
   return 0;
 }
 
-int mgx_compute_rhs(const double *u, const double *v, const double *w, const double *rmask) {
+// The model-facing entries, each once for both scalar types of the state (f32: u, v, w are floats; include/mgx.h: "the float state").
+// `who` names the entry in its refusals.  The float entries refuse a NULL u, v or w; the fp64 ones keep taking what they are given.
+#define NEED_STATE(who) do { if (f32 && !(u && v && w)) return fail("%s: u, v or w is NULL", who); } while (0)
+
+static int compute_rhs_host(const void *u, const void *v, const void *w, const double *rmask, bool f32, const char *who) {
   NEED_INIT();
-  if (!S.have_matrix) return fail("mgx_matrices must be called before compute_rhs");
+  if (!S.have_matrix) return fail("mgx_matrices must be called before %s", who);
+  NEED_STATE(who);
   CHK(set_call_mask(rmask, false));
-  CHK(upload_uvw(u, v, w));
+  StateScope state(nullptr, nullptr, nullptr, f32);   // the staging buffers, as doubles or as floats
+  CHK(upload_uvw(u, v, w, f32 ? sizeof(float) : sizeof(double)));
   CHK(compute_rhs_dev());
   CHK(sync_stream());
   return 0;
 }
 
-int mgx_solve(double *u, double *v, double *w, const double *rmask) {
+static int solve_host(void *u, void *v, void *w, const double *rmask, bool f32, const char *who) {
   NEED_INIT();
-  if (!S.have_matrix) return fail("mgx_matrices must be called before mgx_solve");
+  if (!S.have_matrix) return fail("mgx_matrices must be called before %s", who);
+  NEED_STATE(who);
   if (S.verbose && S.rank == 0) printf("  nhydro_solve:\n");
   CHK(set_call_mask(rmask, false));
-  CHK(upload_uvw(u, v, w));
+  StateScope state(nullptr, nullptr, nullptr, f32);
+  const size_t esz = f32 ? sizeof(float) : sizeof(double);
+  CHK(upload_uvw(u, v, w, esz));
   CHK(compute_rhs_dev());
   CHK(solve_p_opt(S.par.solver_prec, S.par.solver_maxiter, nullptr, nullptr, nullptr));
-  Level &L = S.lev[0];
   CHK(correct_uvw_dev());
-  const size_t nu = (size_t)(L.nx + 1) * (L.ny + 2) * L.nz, nv = (size_t)(L.nx + 2) * (L.ny + 1) * L.nz, nw = (size_t)(L.nx + 2) * (L.ny + 2) * (L.nz + 1);
-  HIPCHK(hipMemcpyAsync(u, S.d_u, nu * sizeof(double), hipMemcpyDeviceToHost, S.stream));
-  HIPCHK(hipMemcpyAsync(v, S.d_v, nv * sizeof(double), hipMemcpyDeviceToHost, S.stream));
-  HIPCHK(hipMemcpyAsync(w, S.d_w, nw * sizeof(double), hipMemcpyDeviceToHost, S.stream));
+  CHK(download_uvw(u, v, w, esz));
   CHK(sync_stream());
   return 0;
 }
 
 // Device-resident variant of nhydro_solve: u,v,w are DEVICE pointers in the model's (i,j,k) layout
 // (e.g. torch tensors); nothing crosses PCIe.  The library's own staging copies are bypassed.
-int mgx_solve_device(double *u_dev, double *v_dev, double *w_dev, const double *rmask) {
+static int solve_device(void *u, void *v, void *w, const double *rmask, bool f32, const char *who) {
   NEED_INIT();
-  if (!S.have_matrix) return fail("mgx_matrices must be called before mgx_solve_device");
+  if (!S.have_matrix) return fail("mgx_matrices must be called before %s", who);
+  NEED_STATE(who);
   CHK(set_call_mask(rmask, true));
-  double *su = S.d_u, *sv = S.d_v, *sw = S.d_w;
-  S.d_u = u_dev; S.d_v = v_dev; S.d_w = w_dev;
-  int rc = compute_rhs_dev();
-  if (!rc) rc = solve_p_opt(S.par.solver_prec, S.par.solver_maxiter, nullptr, nullptr, nullptr);
-  if (!rc) rc = correct_uvw_dev();
-  if (!rc) rc = sync_stream();
-  S.d_u = su; S.d_v = sv; S.d_w = sw;
-  return rc;
+  StateScope state(u, v, w, f32);
+  CHK(compute_rhs_dev());
+  CHK(solve_p_opt(S.par.solver_prec, S.par.solver_maxiter, nullptr, nullptr, nullptr));
+  CHK(correct_uvw_dev());
+  CHK(sync_stream());
+  return 0;
 }
 
+// nhydro_check_nondivergence on the model's own device arrays (the pattern of mgx_solve_device): the divergence into grid(1)%b
+static int check_nondivergence_device(void *u, void *v, void *w, const double *rmask, bool f32, const char *who) {
+  NEED_INIT();
+  if (!S.have_matrix) return fail("mgx_matrices must be called before %s", who);
+  NEED_STATE(who);
+  if (S.verbose && S.rank == 0) printf(" - check non-divergence:\n");
+  CHK(set_call_mask(rmask, true));
+  StateScope state(u, v, w, f32);
+  CHK(compute_rhs_dev());
+  CHK(sync_stream());
+  return 0;
+}
+
+int mgx_compute_rhs(const double *u, const double *v, const double *w, const double *rmask) { return compute_rhs_host(u, v, w, rmask, false, "compute_rhs"); }
+int mgx_compute_rhs_f32(const float *u, const float *v, const float *w, const double *rmask) { return compute_rhs_host(u, v, w, rmask, true, "mgx_compute_rhs_f32"); }
+int mgx_solve(double *u, double *v, double *w, const double *rmask) { return solve_host(u, v, w, rmask, false, "mgx_solve"); }
+int mgx_solve_f32(float *u, float *v, float *w, const double *rmask) { return solve_host(u, v, w, rmask, true, "mgx_solve_f32"); }
+int mgx_solve_device(double *u_dev, double *v_dev, double *w_dev, const double *rmask) { return solve_device(u_dev, v_dev, w_dev, rmask, false, "mgx_solve_device"); }
+int mgx_solve_device_f32(float *u_dev, float *v_dev, float *w_dev, const double *rmask_dev) { return solve_device(u_dev, v_dev, w_dev, rmask_dev, true, "mgx_solve_device_f32"); }
 int mgx_check_nondivergence(double *u, double *v, double *w, const double *rmask) {
   if (S.verbose && S.rank == 0) printf(" - check non-divergence:\n");
   return mgx_compute_rhs(u, v, w, rmask);
 }
-
-// nhydro_check_nondivergence on the model's own device arrays (the pattern of mgx_solve_device): the divergence into grid(1)%b
-int mgx_check_nondivergence_device(double *u_dev, double *v_dev, double *w_dev, const double *rmask_dev) {
-  NEED_INIT();
-  if (!S.have_matrix) return fail("mgx_matrices must be called before mgx_check_nondivergence_device");
+int mgx_check_nondivergence_f32(float *u, float *v, float *w, const double *rmask) {
   if (S.verbose && S.rank == 0) printf(" - check non-divergence:\n");
-  CHK(set_call_mask(rmask_dev, true));
-  double *su = S.d_u, *sv = S.d_v, *sw = S.d_w;
-  S.d_u = u_dev; S.d_v = v_dev; S.d_w = w_dev;
-  int rc = compute_rhs_dev();
-  if (!rc) rc = sync_stream();
-  S.d_u = su; S.d_v = sv; S.d_w = sw;
-  return rc;
+  return compute_rhs_host(u, v, w, rmask, true, "mgx_check_nondivergence_f32");
+}
+int mgx_check_nondivergence_device(double *u_dev, double *v_dev, double *w_dev, const double *rmask_dev) {
+  return check_nondivergence_device(u_dev, v_dev, w_dev, rmask_dev, false, "mgx_check_nondivergence_device");
+}
+int mgx_check_nondivergence_device_f32(float *u_dev, float *v_dev, float *w_dev, const double *rmask_dev) {
+  return check_nondivergence_device(u_dev, v_dev, w_dev, rmask_dev, true, "mgx_check_nondivergence_device_f32");
 }
 
 int mgx_solve_p(double tol, int maxite, int *nite, double *res, double *hist) {

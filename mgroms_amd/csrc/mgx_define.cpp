@@ -253,8 +253,16 @@ int define_matrices(int what, bool may_return_early) {
 // mg_correct_uvw.f90:51-68).  Without a per-call mask (NULL): the level-1 mask of nhydro_matrices when bmask, else all ones.
 ModelView model_view() {
   double *m = S.call_mask ? S.d_rmask_m : (S.par.bmask ? S.lev[0].g.mrmask : nullptr);
-  return ModelView{S.d_u, S.d_v, S.d_w, m, S.par.bmask ? 1 : 0};
+  return ModelView{S.d_u, S.d_v, S.d_w, m, S.par.bmask ? 1 : 0, S.state_f32};
 }
+
+// the model state of one call in place of the library's fp64 staging copies: the caller's device arrays (the *_device entries), or the
+// staging buffers themselves holding floats (the host *_f32 entries: u = v = w = nullptr).  Put back when the call ends, whatever it returns.
+StateScope::StateScope(void *u, void *v, void *w, bool f32) : su(S.d_u), sv(S.d_v), sw(S.d_w), sf(S.state_f32) {
+  if (u) { S.d_u = (double *)u; S.d_v = (double *)v; S.d_w = (double *)w; }
+  S.state_f32 = f32 ? 1 : 0;
+}
+StateScope::~StateScope() { S.d_u = su; S.d_v = sv; S.d_w = sw; S.state_f32 = sf; }
 
 // rmaska of nhydro_solve / nhydro_check_nondivergence: (0:ny+1,0:nx+1), j fastest -- the layout the reference's drivers
 // allocate (mg_testseamount.f90:97) and compute_rhs indexes (rmask(j,i)).  `dev`: the pointer is a device pointer.
@@ -314,14 +322,18 @@ int correct_uvw_dev() {
   return 0;
 }
 
-int upload_uvw(const double *u, const double *v, const double *w) {
+// host u, v, w <-> the staging buffers; esz: the size of an element of the state (8, or 4 for the float state, which fills their first half)
+static int copy_uvw(void *u, void *v, void *w, size_t esz, bool up) {
   Level &L = S.lev[0];
   const size_t nu = (size_t)(L.nx + 1) * (L.ny + 2) * L.nz, nv = (size_t)(L.nx + 2) * (L.ny + 1) * L.nz, nw = (size_t)(L.nx + 2) * (L.ny + 2) * (L.nz + 1);
-  HIPCHK(hipMemcpyAsync(S.d_u, u, nu * sizeof(double), hipMemcpyHostToDevice, S.stream));
-  HIPCHK(hipMemcpyAsync(S.d_v, v, nv * sizeof(double), hipMemcpyHostToDevice, S.stream));
-  HIPCHK(hipMemcpyAsync(S.d_w, w, nw * sizeof(double), hipMemcpyHostToDevice, S.stream));
+  const hipMemcpyKind kind = up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+  HIPCHK(hipMemcpyAsync(up ? (void *)S.d_u : u, up ? u : (void *)S.d_u, nu * esz, kind, S.stream));
+  HIPCHK(hipMemcpyAsync(up ? (void *)S.d_v : v, up ? v : (void *)S.d_v, nv * esz, kind, S.stream));
+  HIPCHK(hipMemcpyAsync(up ? (void *)S.d_w : w, up ? w : (void *)S.d_w, nw * esz, kind, S.stream));
   return 0;
 }
+int upload_uvw(const void *u, const void *v, const void *w, size_t esz) { return copy_uvw((void *)u, (void *)v, (void *)w, esz, true); }
+int download_uvw(void *u, void *v, void *w, size_t esz) { return copy_uvw(u, v, w, esz, false); }
 
 int apply_params(const mgx_params &p) {
   if (streq(p.relax_method, "GS") || streq(p.relax_method, "Gauss-Seidel")) S.method = M_GS;

@@ -8,9 +8,19 @@
 #include "mgx_switches.h"
 #include "mgx_internal.h"
 
-#define U(i, j, k) M.u[(((long long)((k)-1)) * (ny + 2) + (j)) * (nx + 1) + ((i)-1)]
-#define V(i, j, k) M.v[(((long long)((k)-1)) * (ny + 1) + ((j)-1)) * (nx + 2) + (i)]
-#define Wv(i, j, k) M.w[(((long long)(k)) * (ny + 2) + (j)) * (nx + 2) + (i)]
+// The model state u, v, w is double or float (ModelViewT<T>; the float state: DESIGN.md 6.2).  The formulas read it through U, V, Wv, which
+// load one T and widen it to double (exact), so there is one text of every formula for both; correct_uvw stores through SET_U, SET_V,
+// SET_W, which round the double result to T once (to nearest even; a no-op for double).  One element per load and per store: a row of
+// floats starts 4-byte aligned (nx + 1 or nx + 2 elements), which is all such an access needs.
+#define UE(i, j, k) M.u[(((long long)((k)-1)) * (ny + 2) + (j)) * (nx + 1) + ((i)-1)]
+#define VE(i, j, k) M.v[(((long long)((k)-1)) * (ny + 1) + ((j)-1)) * (nx + 2) + (i)]
+#define WE(i, j, k) M.w[(((long long)(k)) * (ny + 2) + (j)) * (nx + 2) + (i)]
+#define U(i, j, k) ((double)UE(i, j, k))
+#define V(i, j, k) ((double)VE(i, j, k))
+#define Wv(i, j, k) ((double)WE(i, j, k))
+#define SET_U(i, j, k, x) UE(i, j, k) = (T)(x)
+#define SET_V(i, j, k, x) VE(i, j, k) = (T)(x)
+#define SET_W(i, j, k, x) WE(i, j, k) = (T)(x)
 // model-layout index of a level-1 array with rows k = 1.., j,i = 0..n+1 (i fastest)
 #define MI3(k, j, i) ((((long long)((k)-1)) * (ny + 2) + (j)) * (nx + 2) + (i))
 #define M2(a, j, i) a[((long long)(j)) * (nx + 2) + (i)]
@@ -87,7 +97,7 @@ __global__ __launch_bounds__(256) void k_js_model(LevView L, double *__restrict_
 // A lane climbs its column and keeps what row k+1 of this step is to row k of the next (zw, dzw, w; in k_rhs_wf zxdy, zydx, u, v of row
 // k-1) in registers: rows are 2 MB apart, so a value asked for again one step later comes from HBM again -- k_rhs_uf moved 1.5 GB for
 // 0.8 GB of operands (264 us = 5.6 TB/s: at the memory's rate, on the wrong bytes).  Same values in the same expressions: same bits.
-__global__ void k_rhs_uf(GeoView G, ModelView M, double *__restrict__ fx, int KR) {
+template <typename T> __global__ void k_rhs_uf(GeoView G, ModelViewT<T> M, double *__restrict__ fx, int KR) {
   COLUMN_THREAD_I(1, G.ny, 1, G.nx + 1)
   ROW_RUN(nz)
   const double two = 2.0, hlf = 0.5, qrt = 0.25;
@@ -130,7 +140,7 @@ __global__ void k_rhs_uf(GeoView G, ModelView M, double *__restrict__ fx, int KR
   }
 }
 
-__global__ void k_rhs_vf(GeoView G, ModelView M, double *__restrict__ fx, int KR) {
+template <typename T> __global__ void k_rhs_vf(GeoView G, ModelViewT<T> M, double *__restrict__ fx, int KR) {
   COLUMN_THREAD_I(1, G.ny + 1, 1, G.nx)
   ROW_RUN(nz)
   const double two = 2.0, hlf = 0.5, qrt = 0.25;
@@ -173,7 +183,7 @@ __global__ void k_rhs_vf(GeoView G, ModelView M, double *__restrict__ fx, int KR
   }
 }
 
-__global__ void k_rhs_wf(GeoView G, ModelView M, double *__restrict__ fz, int KR) {
+template <typename T> __global__ void k_rhs_wf(GeoView G, ModelViewT<T> M, double *__restrict__ fz, int KR) {
   COLUMN_THREAD_I(1, G.ny, 1, G.nx)
   ROW_RUN(nz + 1)
   const double hlf = 0.5, qrt = 0.25;
@@ -243,7 +253,7 @@ __global__ void k_rhs_accum_m(GeoView G, double *__restrict__ bm, const double *
 
 // correct_uvw (mg_correct_uvw.f90:73-108); pm = level-1 pressure in model layout (halo included).
 // dzw(k) of the reference (zr(k)-zr(k-1), top: zw(nz+1)-zr(nz)) is the same expression as grid(1)%dzw.
-__global__ void k_correct_uvw_m(GeoView G, const double *__restrict__ pm, ModelView M, int KR) {
+template <typename T> __global__ void k_correct_uvw_m(GeoView G, const double *__restrict__ pm, ModelViewT<T> M, int KR) {
   COLUMN_THREAD_I(0, G.ny + 1, 0, G.nx + 1)
   ROW_RUN(nz)
   const double one = 1.0, hlf = 0.5;
@@ -255,18 +265,18 @@ __global__ void k_correct_uvw_m(GeoView G, const double *__restrict__ pm, ModelV
   double pk0 = ka >= 2 ? PM(ka - 1, j, i) : 0.0;  // p(k-1)
   for (int k = ka; k <= kb; k++) {
     const double pk = PM(k, j, i);
-    if (doU) U(i, j, k) = U(i, j, k) - one / dxu * (pk - PM(k, j, i - 1)) * um;
-    if (doV) V(i, j, k) = V(i, j, k) - one / dyv * (pk - PM(k, j - 1, i)) * vm;
+    if (doU) SET_U(i, j, k, U(i, j, k) - one / dxu * (pk - PM(k, j, i - 1)) * um);
+    if (doV) SET_V(i, j, k, V(i, j, k) - one / dyv * (pk - PM(k, j - 1, i)) * vm);
     if (k >= 2) {
       const double dzw = MDZW(k, j, i);
-      Wv(i, j, k - 1) = Wv(i, j, k - 1) - one / dzw * (pk - pk0);
+      SET_W(i, j, k - 1, Wv(i, j, k - 1) - one / dzw * (pk - pk0));
     }
     pk0 = pk;
   }
   if (kb == nz) {
     const int k = nz + 1;
     const double dzw = MDZW(nz + 1, j, i);
-    Wv(i, j, k - 1) = Wv(i, j, k - 1) - one / dzw * (-pk0);
+    SET_W(i, j, k - 1, Wv(i, j, k - 1) - one / dzw * (-pk0));
   }
 #undef PM
 }
@@ -274,6 +284,15 @@ __global__ void k_correct_uvw_m(GeoView G, const double *__restrict__ pm, ModelV
 // ------------------------------------------------------------------------------------------------
 static inline dim3 igrid(int ni, int nj) { return dim3((ni + 63) / 64, (nj + 3) / 4); }
 static const dim3 IBLK(64, 4);
+// the kernels' view of the model state: the ModelView of the call with u, v, w as the scalar type its tag names
+template <typename T> static inline ModelViewT<T> typed(const ModelView *M) { return ModelViewT<T>{(T *)M->u, (T *)M->v, (T *)M->w, M->rmask, M->bmask}; }
+// one launch of a model kernel, the instance for the state's type; ... = the kernel's arguments with STATE(M) where it takes the state
+#define STATE(M) typed<T>(M)
+#define LAUNCH_FOR_STATE(kern, g, M, ...)                                                        \
+  do {                                                                                           \
+    if ((M)->f32) { using T = float; hipLaunchKernelGGL(kern<T>, g, IBLK, 0, st, __VA_ARGS__); } \
+    else { using T = double; hipLaunchKernelGGL(kern<T>, g, IBLK, 0, st, __VA_ARGS__); }         \
+  } while (0)
 
 extern "C" {
 void mgxm_ref2model(hipStream_t st, const double *src, double *dst, int rows, int nh, int nx, int ny) {
@@ -300,9 +319,9 @@ static inline dim3 igrid_run(int ni, int nj, int klast, int *KR) {
   *KR = (int)((klast + nrun - 1) / nrun);
   return dim3((ni + 63) / 64, (nj + 3) / 4, (klast + *KR - 1) / *KR);
 }
-void mgxm_rhs_uf(hipStream_t st, const GeoView *G, const ModelView *M, double *fx) { int KR; const dim3 g = igrid_run(G->nx + 1, G->ny, G->nz, &KR); hipLaunchKernelGGL(k_rhs_uf, g, IBLK, 0, st, *G, *M, fx, KR); }
-void mgxm_rhs_vf(hipStream_t st, const GeoView *G, const ModelView *M, double *fx) { int KR; const dim3 g = igrid_run(G->nx, G->ny + 1, G->nz, &KR); hipLaunchKernelGGL(k_rhs_vf, g, IBLK, 0, st, *G, *M, fx, KR); }
-void mgxm_rhs_wf(hipStream_t st, const GeoView *G, const ModelView *M, double *fz) { int KR; const dim3 g = igrid_run(G->nx, G->ny, G->nz + 1, &KR); hipLaunchKernelGGL(k_rhs_wf, g, IBLK, 0, st, *G, *M, fz, KR); }
+void mgxm_rhs_uf(hipStream_t st, const GeoView *G, const ModelView *M, double *fx) { int KR; const dim3 g = igrid_run(G->nx + 1, G->ny, G->nz, &KR); LAUNCH_FOR_STATE(k_rhs_uf, g, M, *G, STATE(M), fx, KR); }
+void mgxm_rhs_vf(hipStream_t st, const GeoView *G, const ModelView *M, double *fx) { int KR; const dim3 g = igrid_run(G->nx, G->ny + 1, G->nz, &KR); LAUNCH_FOR_STATE(k_rhs_vf, g, M, *G, STATE(M), fx, KR); }
+void mgxm_rhs_wf(hipStream_t st, const GeoView *G, const ModelView *M, double *fz) { int KR; const dim3 g = igrid_run(G->nx, G->ny, G->nz + 1, &KR); LAUNCH_FOR_STATE(k_rhs_wf, g, M, *G, STATE(M), fz, KR); }
 void mgxm_flux_zero_face(hipStream_t st, const GeoView *G, double *f, int face, int pl) {
   const int n = (face == 0 ? G->ny : G->nx) + 2;
   hipLaunchKernelGGL(k_flux_zero_face, dim3((n + 63) / 64, G->nz), dim3(64), 0, st, *G, f, face, pl);
@@ -317,6 +336,6 @@ void mgxm_rhs_accum(hipStream_t st, const GeoView *G, double *bm, const double *
 }
 void mgxm_correct_uvw(hipStream_t st, const GeoView *G, const double *pm, const ModelView *M) {
   int KR; const dim3 g = igrid_run(G->nx + 2, G->ny + 2, G->nz, &KR);
-  hipLaunchKernelGGL(k_correct_uvw_m, g, IBLK, 0, st, *G, pm, *M, KR);
+  LAUNCH_FOR_STATE(k_correct_uvw_m, g, M, *G, pm, STATE(M), KR);
 }
 }

@@ -7,7 +7,10 @@
 
 // one generic halo / copy operation on a reference-layout array (mgx_setup.hip: k_rect)
 struct RectOp { int op, nzz, nh, ny, j0, j1, i0, i1, mj, cj, mi, ci, mj2, cj2, mi2, ci2; };
-struct ModelView { double *u, *v, *w, *rmask; int bmask; };  // rmask: i-fastest copy of the level-1 mask (only read when bmask)
+// the model state of a call.  u, v, w point to doubles (f32 = 0) or to floats (f32 = 1: the mgx_*_f32 entries); the wrappers hand the kernels
+// the typed view of it.  rmask: i-fastest copy of the level-1 mask (only read when bmask)
+struct ModelView { void *u, *v, *w; double *rmask; int bmask, f32; };
+template <typename T> struct ModelViewT { T *u, *v, *w; double *rmask; int bmask; };
 
 extern "C" {
 

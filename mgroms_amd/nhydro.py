@@ -12,6 +12,7 @@ from ._lib import Params, MgxError, lib, check  # noqa: F401
 
 FIELD = {"p": 0, "b": 1, "r": 2, "cA": 3, "dx": 4, "dy": 5, "zeta": 6, "h": 7, "zr": 8, "zw": 9, "cw": 10, "rmask": 14}
 _DP = C.POINTER(C.c_double)
+_FP = C.POINTER(C.c_float)
 
 
 class _PerThread(threading.local):
@@ -98,11 +99,35 @@ def nhydro_matrices(dx, dy, zeta, h, rmask=None, hc=0.0, theta_b=0.0, theta_s=0.
     check(lib().mgx_matrices(_dp(dx), _dp(dy), _dp(zeta), _dp(h), None if rm is None else _dp(rm), hc, theta_b, theta_s))
 
 
-def _uvw(u, v, w):
+def _uvw_shapes():
     nx, ny, nz = _state.dims
-    for a, sh, n in ((u, (nz, ny + 2, nx + 1), "u"), (v, (nz, ny + 1, nx + 2), "v"), (w, (nz + 1, ny + 2, nx + 2), "w")):
-        if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.shape == sh):
-            raise ValueError(f"{n}: need a C-contiguous float64 array of shape {sh} (updated in place)")
+    return ((nz, ny + 2, nx + 1), "u"), ((nz, ny + 1, nx + 2), "v"), ((nz + 1, ny + 2, nx + 2), "w")
+
+
+def _one_dtype(dtypes, both, what):
+    """the scalar type of the model state: "" when u, v, w are all float64, "_f32" (the suffix of the library's float entries, include/mgx.h:
+    the float state) when they are all float32; anything else, a mix included, is refused"""
+    if len(set(dtypes)) != 1 or dtypes[0] not in both:
+        raise ValueError(f"u, v, w: need three {what} of one dtype, float64 or float32; got {', '.join(str(d) for d in dtypes)}")
+    return "" if dtypes[0] == both[0] else "_f32"
+
+
+def _uvw(u, v, w):
+    """host u, v, w: C-contiguous numpy arrays of the model's shapes, all float64 or all float32 -> (entry suffix, the three pointers)"""
+    sfx = _one_dtype([getattr(a, "dtype", type(a)) for a in (u, v, w)], (np.dtype(np.float64), np.dtype(np.float32)), "arrays")
+    for a, (sh, n) in zip((u, v, w), _uvw_shapes()):
+        if not (isinstance(a, np.ndarray) and a.flags.c_contiguous and a.shape == sh):
+            raise ValueError(f"{n}: need a C-contiguous float64 or float32 array of shape {sh} (updated in place)")
+    return sfx, [a.ctypes.data_as(_FP if sfx else _DP) for a in (u, v, w)]
+
+
+def _uvw_dev(u, v, w):
+    """device u, v, w: contiguous torch CUDA tensors of the model's shapes, all float64 or all float32 -> (entry suffix, the three pointers)"""
+    sfx = _one_dtype([str(getattr(a, "dtype", type(a))) for a in (u, v, w)], ("torch.float64", "torch.float32"), "tensors")
+    for a, (sh, n) in zip((u, v, w), _uvw_shapes()):
+        if not (hasattr(a, "is_cuda") and a.is_cuda and a.is_contiguous() and tuple(a.shape) == sh):
+            raise ValueError(f"{n}: need a contiguous float64 or float32 CUDA tensor of shape {sh}")
+    return sfx, [C.c_void_p(a.data_ptr()) for a in (u, v, w)]
 
 
 def _mask(rmask):
@@ -115,24 +140,21 @@ def _mask(rmask):
 
 
 def nhydro_solve(u, v, w, rmask=None):
-    """nhydro_solve (nhydro.f90:53): u(1:nx+1,0:ny+1,1:nz) = numpy (nz, ny+2, nx+1) etc.; corrected in place."""
-    _uvw(u, v, w)
+    """nhydro_solve (nhydro.f90:53): u(1:nx+1,0:ny+1,1:nz) = numpy (nz, ny+2, nx+1) etc.; corrected in place.  u, v, w all float64, or all
+    float32: then each element comes back as the float64 result rounded once (include/mgx.h: the float state)."""
+    sfx, ptrs = _uvw(u, v, w)
     rm, prm = _mask(rmask)
-    check(lib().mgx_solve(_dp(u), _dp(v), _dp(w), prm))
+    check(getattr(lib(), "mgx_solve" + sfx)(*ptrs, prm))
 
 
 def nhydro_solve_device(u, v, w, rmask=None):
-    """nhydro_solve on torch CUDA tensors (float64, contiguous, shapes as nhydro_solve; rmask (nx+2, ny+2)): no host round trip."""
+    """nhydro_solve on torch CUDA tensors (all float64 or all float32, contiguous, shapes as nhydro_solve; rmask float64 (nx+2, ny+2)): no host
+    round trip.  A float32 state comes back as the float64 result rounded once (include/mgx.h: the float state)."""
+    sfx, ptrs = _uvw_dev(u, v, w)
     nx, ny, nz = _state.dims
-    for a, sh, n in ((u, (nz, ny + 2, nx + 1), "u"), (v, (nz, ny + 1, nx + 2), "v"), (w, (nz + 1, ny + 2, nx + 2), "w")):
-        if not (a.is_cuda and a.is_contiguous() and tuple(a.shape) == sh and str(a.dtype) == "torch.float64"):
-            raise ValueError(f"{n}: need a contiguous float64 CUDA tensor of shape {sh}")
-    import torch
-    torch.cuda.current_stream().synchronize()
-    if rmask is not None and not (rmask.is_cuda and rmask.is_contiguous() and tuple(rmask.shape) == (nx + 2, ny + 2) and str(rmask.dtype) == "torch.float64"):
-        raise ValueError(f"rmask: need a contiguous float64 CUDA tensor of shape {(nx + 2, ny + 2)}")
-    check(lib().mgx_solve_device(C.c_void_p(u.data_ptr()), C.c_void_p(v.data_ptr()), C.c_void_p(w.data_ptr()),
-                                 None if rmask is None else C.c_void_p(rmask.data_ptr())))
+    prm = None if rmask is None else _dev(rmask, (nx + 2, ny + 2), "rmask")
+    _wait_for_caller()
+    check(getattr(lib(), "mgx_solve_device" + sfx)(*ptrs, prm))
 
 
 def _dev(a, shape, name):
@@ -171,23 +193,23 @@ def nhydro_update_zeta_device(zeta):
 
 def nhydro_check_nondivergence_device(u, v, w, rmask=None):
     """nhydro_check_nondivergence on torch CUDA tensors (shapes as nhydro_solve_device): the divergence is left in grid(1).b"""
+    sfx, ptrs = _uvw_dev(u, v, w)
     nx, ny, nz = _state.dims
-    ptrs = [_dev(a, sh, n) for a, sh, n in ((u, (nz, ny + 2, nx + 1), "u"), (v, (nz, ny + 1, nx + 2), "v"), (w, (nz + 1, ny + 2, nx + 2), "w"))]
     prm = None if rmask is None else _dev(rmask, (nx + 2, ny + 2), "rmask")
     _wait_for_caller()
-    check(lib().mgx_check_nondivergence_device(*ptrs, prm))
+    check(getattr(lib(), "mgx_check_nondivergence_device" + sfx)(*ptrs, prm))
 
 
 def nhydro_check_nondivergence(u, v, w, rmask=None):
-    _uvw(u, v, w)
+    sfx, ptrs = _uvw(u, v, w)
     rm, prm = _mask(rmask)
-    check(lib().mgx_check_nondivergence(_dp(u), _dp(v), _dp(w), prm))
+    check(getattr(lib(), "mgx_check_nondivergence" + sfx)(*ptrs, prm))
 
 
 def compute_rhs(u, v, w, rmask=None):
-    _uvw(u, v, w)
+    sfx, ptrs = _uvw(u, v, w)
     rm, prm = _mask(rmask)
-    check(lib().mgx_compute_rhs(_dp(u), _dp(v), _dp(w), prm))
+    check(getattr(lib(), "mgx_compute_rhs" + sfx)(*ptrs, prm))
 
 
 def nhydro_clean():
