@@ -1,5 +1,6 @@
-// Which kernel smooths a level: the choices of the smoother wrappers (mgx_relax.hip, mgx_relax_coarse.hip, mgx_relax_ks.hip,
-// mgx_relax_tall.hip) as pure host functions.  Each takes the level's shape, the call's flags and the A/B switches and returns a Choice by
+// Which kernel serves a level: the choices of the smoother wrappers (mgx_relax.hip, mgx_relax_coarse.hip, mgx_relax_ks.hip,
+// mgx_relax_tall.hip), of the sequential-order red-black walk (mgx_rbseq.hip) and of the fused residual + restriction (mgx_resrest.hip)
+// as pure host functions.  Each takes the level's shape, the call's flags and the A/B switches and returns a Choice by
 // value: the kernel family, the parameters of its template instance, the launch geometry, and what the wrapper reports when the launch
 // succeeded.  A wrapper is mgx_before_launch(), its choose_*(), and one launcher that maps the Choice to the instance (no condition on the
 // level's shape there).  Nothing here calls HIP, keeps state or reads the environment; tests/test_kernel_choice_host.py pins every answer
@@ -10,8 +11,14 @@
 #include "mgx_internal.h"
 #include "mgx_switches.h"
 
-struct LevShape { int nx, ny, nz; bool slopes, d0; };   // slopes: the level has zy / zx (matrix-free cross terms); d0: the pass is to write d0w
-static inline LevShape lev_shape(const LevView *L) { return {L->nx, L->ny, L->nz, L->zy != nullptr, L->d0w != nullptr}; }
+// slopes: the level has zy / zx (matrix-free cross terms); d0: the pass is to write d0w; gk: the level has what the sequential-order walk needs;
+// zw: it carries all nine fields from which slots 4 and 7 are generated (as define_matrices leaves it: not after bmask, a user matrix or
+// MGX_NO_MF); rs: the row stride of its layout
+struct LevShape { int nx, ny, nz; bool slopes, d0, gk, zw; int rs; };
+static inline LevShape lev_shape(const LevView *L) {
+  return {L->nx, L->ny, L->nz, L->zy != nullptr, L->d0w != nullptr, L->gk != nullptr,
+          L->m4 && L->d4 && L->m7 && L->d7 && L->h2 && L->hi2 && L->ze2 && L->cffw && L->csw, L->RS};
+}
 
 enum KernelFamily {
   KF_NONE,                               // nothing of this wrapper serves the call
@@ -19,6 +26,9 @@ enum KernelFamily {
   KF_KS, KF_KS2,                         // k-split colour pass and colour pair: k_relax_ks, k_relax_ks2
   KF_NZ, KF_TALL, KF_TALL_ST, KF_COLOUR, // a colour pass: k_relax_nz, k_relax_tall, k_relax_tall_st, k_relax_colour
   KF_GS, KF_GS_ANY,                      // a hyperplane of the Gauss-Seidel sweep: k_relax_gs_front, k_relax_gs_front_any
+  KF_RB_SCAN, KF_RB_SCAN_FUSED,          // the sequential-order walk over a level, alone or with the correction in its launch: k_rbseq_scan
+  KF_RB_WALK_APPLY, KF_RB_WINDOW, KF_RB_APPLY,  // walk + correction of a small level, the windowed walk, the correction alone: k_rbseq_walk_apply, _window, _apply
+  KF_RR_FLAT, KF_RR_WALK,                // residual + restriction, a wave per S fine rows or walking up the column: k_residual_restrict_flat, k_residual_restrict
 };
 
 struct Choice {
@@ -42,6 +52,7 @@ static inline int ch_chunks(int ny) { return (ny / 2 + CH_WAVE - 1) / CH_WAVE; }
 // ---- run-time values as template arguments (the launchers) ----
 // f(std::integral_constant<int, NZ>) for the NZ of the list that equals nz; false = none does
 template <int... NZ, class F> static inline bool with_nz(int nz, F &&f) { return ((nz == NZ && (f(std::integral_constant<int, NZ>{}), true)) || ...); }
+template <int... V, class F> static inline bool with_int(int v, F &&f) { return with_nz<V...>(v, static_cast<F &&>(f)); }   // the same for any other parameter
 template <class F> static inline void with_bool(bool b, F &&f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
 // (REAL, SNAP) and (REAL, SEQ) of the kernels: the second only ever with the first
 template <class F> static inline void with_real_and(bool real, bool second, F &&f) {
@@ -161,6 +172,7 @@ static inline void ch_pass_geometry(Choice &c, const LevShape &s, int nplanes, c
 }
 // streaming (nontemporal) hints only when the level cannot live in the 256 MB Infinity Cache between passes:
 // measured +14 % on the 1.2 GB level 1, -20 % on the 150 MB level 2 which is otherwise re-read from cache
+// (level_streams of mgx_device.h, the per-launch form of the hint, is this function)
 static inline bool ch_beyond_cache(const LevShape &s) { return (double)s.nx * s.ny * s.nz * 72.0 > 256e6; }
 static inline int ch_pass_ret(const LevShape &s, int real, int snap) { return (real && snap && s.d0) ? PASS_MIRRORS | PASS_D0 : PASS_MIRRORS; }
 
@@ -255,4 +267,183 @@ static inline Choice choose_gs_front(const LevShape &s, int t) {
   c.family = with_nz<2, 4, 8, 16, 32, 64>(s.nz, [](auto) {}) ? KF_GS : KF_GS_ANY;
   c.nz = s.nz; c.grid = ihi < ilo ? 0 : (ihi - ilo + 1 + CH_WAVE - 1) / CH_WAVE; c.bx = CH_WAVE; c.ret = 1;
   return c;
+}
+
+// ---- the operator of a level (mgxk_residual, mgxq_apply, mgxq_apply32, mgxq_path): matrix-free cross terms or the stored slots ----
+static inline bool choose_operator_mf(const LevShape &s) { return s.slopes && s.nz >= 3; }
+
+// ---- mgx_rbseq.hip: red-black in the reference's sequential order ----
+struct RbChoice {
+  int family = KF_NONE;
+  // the instance: CPL, D, FULL, NW, D0IN of k_rbseq_scan (fused: FUSE = 2 with the snapshot written, else 1); KU of k_rbseq_apply; CPL, KR of k_rbseq_window
+  int cpl = 0, d = 0, nw = 1, ku = 0, kr = 0;
+  bool full = false, d0in = false;
+  bool d0_first = false;   // k_rbseq_d0 runs in front of the walk: nobody has left d0 in u1
+  // the launch and its scalar arguments
+  unsigned grid = 1, gy = 1, gz = 1, bx = CH_WAVE, by = 1;
+  size_t lds = 0;
+  int nhelp = 0, nt = 0, nchunk = 0, nkz = 0, nworkers = 0;   // (nchunk: waves along a half-row -- k_rbseq_window's nch)
+  int pb = 0, xmap = 0, prio = 0, kcut = 0;
+  int ret = 0;
+};
+constexpr int RBF_CH = 8;     // planes per hand-off word of the fused walk (its ring holds whole chunks), RBF_WPB: waves of its workgroups
+constexpr int RBF_WPB = 4;
+constexpr int RBW_MAXM = 48;  // the windowed walk's longest warm-up (planes)
+
+// rows per correction wave: enough waves to fill the chip on the large levels, whole columns on the small ones
+static inline void ch_rbseq_apply_shape(const LevShape &s, int &ku, int &kr) {
+  const int nyh = s.ny / 2, nz = s.nz;
+  // (ku divides nz: an odd coarse level -- nz = 3 or 5 below nz = 24, 40, 48, 80, 96 -- takes one row at a time, or a wave would write
+  // the row above its column's top, i.e. the bottom row of the next plane)
+  ku = nz % 8 == 0 ? 8 : (nz % 4 == 0 ? 4 : (nz % 2 == 0 ? 2 : 1));
+  kr = nz;
+  const long long waves = (long long)ch_chunks(s.ny) * s.nx;
+  while (kr > ku && kr % 2 == 0 && (kr / 2) % ku == 0 && waves * (nz / kr) < 4096) kr /= 2;
+}
+// mgxk_rbseq_apply: the correction (c) as a launch of its own
+static inline RbChoice choose_rbseq_apply(const LevShape &s) {
+  RbChoice c;
+  c.family = KF_RB_APPLY;
+  ch_rbseq_apply_shape(s, c.ku, c.kr);
+  c.grid = ch_chunks(s.ny); c.gy = (s.nx + 3) / 4; c.gz = s.nz / c.kr; c.by = 4;
+  c.nt = ch_beyond_cache(s);
+  return c;
+}
+
+// Does the walk form d0 itself?  Small half-rows: one wave does (the level lives in L2; the walk is bound by its dependent chain, not by its
+// requests) -- but half-rows of 65..128 columns whose pass wrote d0 read it: three requests and a store per plane, 16 planes of look-ahead
+// instead of 8 with five: level 2 of 512x512x64 20.5 -> ~16 us per colour, Vcycle 3.12 -> 3.08 ms; MGX_RBSEQ_NO_D0_MID: A/B
+static inline bool ch_rbseq_forms_d0(const LevShape &s, int have_d0, const Switches &sw) {
+  const int nyh = s.ny / 2;
+  return nyh <= 2 * CH_WAVE && !sw.rbseq_d0_kernel && !(have_d0 && sw.rbseq_d0_mid && nyh > CH_WAVE);
+}
+// the levels k_rbseq_walk_apply is made for
+static inline bool ch_rbseq_walk_apply_size(const LevShape &s) { return s.ny / 2 <= CH_WAVE && s.nx <= 128; }
+// the fused launch counts planes in 13 bits of its progress word
+static inline bool ch_rbseq_fuse_planes(const LevShape &s) { return s.nx < (1 << 13); }
+// The deepest ring of a row of the walk's ladder (CPL columns per lane, NW waves, d0 formed or read): D * (loads + stores per plane) < 63
+// (vmcnt); the ring of a launch is the first of DMAX, 4, 2 that divides nx.  Read by the choice and by the launcher that names the instances.
+constexpr int ch_rbseq_dmax(int cpl, int nw, bool d0in) {
+  // d0 formed at CPL = 1: y, snapshot, the multiplier pair, the store of u -- 4 operations per plane, 16 planes deep
+  return d0in ? (cpl == 1 ? 16 : 8) : (nw > 1 || cpl <= 2 ? 16 : (cpl == 4 ? 8 : (cpl == 8 ? 4 : 2)));
+}
+// mgxk_rbseq_scan, mgxk_rbseq_scan_apply: (b), d0 and the walk -- and, fuse (the caller has the hand-off words, an error word and a device
+// whose placement suits; min_cells: cells of a colour from which on it wants the fused launch), the correction (c) inside the walk's launch
+// where an instance exists (ret 2 then).  ret 0: the level has no instance (no gk, odd nx, more than 1024 columns per half-row): the
+// caller runs the planes one by one.
+static inline RbChoice choose_rbseq_scan(const LevShape &s, int have_d0, bool fuse, long long min_cells, const Switches &sw) {
+  RbChoice c;
+  const int nyh = s.ny / 2, nx = s.nx;
+  if (!s.gk || nyh > 16 * CH_WAVE || (nx & 1)) return c;
+  // helper workgroups that pull the walk's operands into its L2 (k_rbseq_scan): one per ~32 KB of operands, at most 32 (one per compute unit of an XCD)
+  // Measured (512x512x64, rocprofv3): level 1 (4.2 MB of operands, HBM-resident) one wave 88.4 us without helpers, 59.7 with 32; two waves
+  // (a barrier per plane) 73; levels 2-4 (1 MB and less) 20.9 / 11.0 / 7.6 us with or without them -- there the walk is bound by the ~190
+  // cycles a plane step costs to issue (4-5 memory instructions, the dependent DPP + FMA chain), and a few dozen extra workgroups only add
+  // launch time (level 4: 9.0 against 7.6).  So: helpers from 2 MB of operands on.
+  const long long opbytes = (long long)nx * nyh * 32;
+  c.nhelp = opbytes >= (2LL << 20) ? (int)((opbytes + 131071) / 131072) : 0;
+  if (c.nhelp > 32) c.nhelp = 32;
+  if (c.nhelp > nx) c.nhelp = nx;
+  // the row of the ladder
+  if (ch_rbseq_forms_d0(s, have_d0, sw)) { c.d0in = true; c.cpl = nyh <= CH_WAVE ? 1 : 2; }
+  else {
+    c.d0_first = !have_d0;   // (the colour pass may have written it: LevView::d0w)
+    // wide half-rows: the requests of ONE wave (at most 63 in flight) do not cover the latency of a level that lives in HBM: several waves
+    // (256 columns per half-row: ONE wave with the helpers beats two waves with a barrier per plane, 59.7 against 73 us; wider half-rows
+    // -- 512 and 1024 columns, BASELINE config 5 -- would need 16 / 32 memory instructions per plane in one wave: several waves there, unmeasured)
+    if (nyh <= CH_WAVE) c.cpl = 1;
+    else if (nyh <= 2 * CH_WAVE) c.cpl = 2;
+    else if (nyh == 8 * CH_WAVE) { c.cpl = 2; c.nw = 4; }
+    else if (nyh == 16 * CH_WAVE) { c.cpl = 2; c.nw = 8; }
+    else c.cpl = nyh <= 4 * CH_WAVE ? 4 : (nyh <= 8 * CH_WAVE ? 8 : 16);
+  }
+  const int dmax = ch_rbseq_dmax(c.cpl, c.nw, c.d0in);
+  c.d = nx % dmax == 0 ? dmax : (nx % 4 == 0 ? 4 : 2);
+  c.full = nyh == c.cpl * CH_WAVE * c.nw;
+  // the correction inside the walk's launch: instances for full half-rows of one walking wave, the deepest ring in whole chunks, nz a multiple of 8
+  // ... and where it pays: the correction of a colour is 24 B per cell; below ~100 MB it takes less than what the hand-off adds (the
+  // forwarding waves lag the walk by 2-5 us, the last workers finish ~4 us later: 256x256x32, 0.111 ms per sweep fused against 0.099)
+  int ku, kr;
+  ch_rbseq_apply_shape(s, ku, kr);
+  const bool can_fuse = fuse && ku == 8 && (long long)(nx + 2) * s.rs * 8 < (1LL << 31) && (long long)nx * nyh * s.nz >= min_cells;
+  if (can_fuse && c.nw == 1 && c.full && c.d == dmax && dmax % RBF_CH == 0) {
+    c.family = KF_RB_SCAN_FUSED;
+    // eight rows per worker: what a worker does after its word is set -- 16 stores with the mirrors, ~1.4 us per eight rows under load --
+    // is the tail of the launch behind the walk's last plane (level-1 sweep at 512x512x64 with 32 / 16 / 8 rows: 0.346 / 0.345-0.357 / 0.339 ms)
+    c.kr = 8; c.nt = ch_beyond_cache(s); c.nchunk = ch_chunks(s.ny); c.nkz = s.nz / c.kr; c.nworkers = nx * c.nchunk * c.nkz;
+    // workgroup b holds RBF_WPB workers unless b % 8 == 0 (those: the walk with its forwarding waves, the helpers, nothing)
+    const int per = 7 * RBF_WPB, octets = (c.nworkers + per - 1) / per;
+    c.grid = 8 * (octets > c.nhelp + 3 ? octets : c.nhelp + 3); c.bx = CH_WAVE * RBF_WPB; c.ret = 2;
+    return c;
+  }
+  c.family = KF_RB_SCAN; c.grid = 1 + 8 * c.nhelp; c.bx = CH_WAVE * c.nw; c.ret = 1;
+  return c;
+}
+// mgxk_rbseq_walk_apply: (b) + (c) of a small level in ONE launch; needs d0 in u1 (the colour pass wrote it)
+static inline RbChoice choose_rbseq_walk_apply(const LevShape &s, const Switches &sw) {
+  RbChoice c;
+  if (sw.no_rbseq_walk_apply || !s.gk || !ch_rbseq_walk_apply_size(s) || (s.nx & 1) || s.nz < 4 || (s.nz & 3)) return c;
+  c.family = KF_RB_WALK_APPLY; c.d = 16;   // DW: planes of look-ahead
+  c.pb = s.nx > 64 ? (s.nx + 63) / 64 : 1; c.grid = (s.nx + c.pb - 1) / c.pb; c.bx = 256;
+  c.lds = (size_t)(s.nx + c.d + 1) * 64 * sizeof(double);
+  c.nt = ch_beyond_cache(s); c.ret = 1;
+  return c;
+}
+// mgxk_rbseq_wants_d0: does the walk of this level read d0 from u1 rather than form it itself?  Then the colour pass should write it
+// (LevView::d0w).  Wide half-rows: k_rbseq_scan reads it; small levels: k_rbseq_walk_apply needs it where no workgroup of its launch writes.
+// By the two predicates the choices above stand on, not by their families: it also says yes where neither then serves the level.
+static inline bool choose_rbseq_wants_d0(const LevShape &s, const Switches &sw) {
+  return s.gk && (!ch_rbseq_forms_d0(s, 1, sw) || ch_rbseq_walk_apply_size(s));
+}
+// mgxk_rbseq_window: (b) + (c) by the windowed walk; m: planes of warm-up (mgxk_rbseq_window_planes), kcut: rows the correction reaches
+static inline RbChoice choose_rbseq_window(const LevShape &s, int m, int kcut, const Switches &sw) {
+  RbChoice c;
+  const int nyh = s.ny / 2, nz = s.nz;
+  if (!s.gk || m < 1 || m > RBW_MAXM || nyh < 1 || (s.ny & 1) || s.nx > 65535) return c;
+  int kr = nz % 64 == 0 ? 16 : (nz % 32 == 0 ? 8 : (nz % 16 == 0 ? 4 : (nz % 8 == 0 ? 2 : (nz % 4 == 0 ? 1 : 0))));
+  if (!kr || nz / (4 * kr) > 65535) return c;
+  if (kcut < 1 || kcut > nz) kcut = nz;
+  // the rows the correction reaches, spread over the four row waves of a workgroup (16 of 64 rows: four rows per wave rather than one wave with all
+  // sixteen and three idle), and only the row groups that hold any are launched
+  while (kr > 1 && 4 * (kr / 2) >= kcut) kr /= 2;
+  c.family = KF_RB_WINDOW; c.kr = kr; c.kcut = kcut;
+  // the walking wave at raised priority (s_setprio 3): level-1 sweep 0.3075-0.3150 -> 0.2989-0.3073 ms (three runs each, alternating); MGX_RBW_PRIO=0: A/B
+  c.prio = sw.rbw_prio;
+  c.nt = ch_beyond_cache(s); c.cpl = nyh <= CH_WAVE ? 1 : 2; c.nchunk = ch_chunks(s.ny); c.nkz = (kcut + 4 * kr - 1) / (4 * kr);
+  c.xmap = !sw.rbseq_window_no_xmap && s.nx % 8 == 0 && (long long)c.nchunk * s.nx * c.nkz < (1LL << 31);
+  if (c.xmap) c.grid = c.nchunk * s.nx * c.nkz;
+  else { c.grid = c.nchunk; c.gy = s.nx; c.gz = c.nkz; }
+  c.bx = 320; c.ret = 1;
+  return c;
+}
+
+// ---- mgx_resrest.hip: mgxk_residual_restrict_ex ----
+struct RrChoice {
+  int family = KF_NONE;
+  int s = 0, aw = 0, ar = 0;   // S of k_residual_restrict_flat; AW, AR of k_residual_restrict
+  bool real = false, norm = false, zw = false;
+  unsigned grid = 0, by = 1;   // workgroups (= the norm's pairs of partials): filled in whether or not the launch is served -- define_matrices sizes the partials by it
+  int gx = 0, gy = 0;
+};
+// served: matrix-free slopes present, even nz, a coarse level of half the size, from resrest_min fine cells on
+static inline RrChoice choose_resrest(const LevShape &f, const LevShape &c, int real, bool want_norm, const Switches &sw) {
+  RrChoice r;
+  const long long cells = (long long)f.nx * f.ny * f.nz;
+  const bool served = !sw.no_resrest && f.slopes && f.nz >= 2 && !(f.nz & 1) && c.nx * 2 == f.nx && c.ny * 2 == f.ny && cells >= sw.resrest_min;
+  r.real = real; r.norm = want_norm;
+  r.gx = (c.ny + 31) / 32;
+  if (cells <= sw.resrest_flat_max) {  // no walk: one wave per S fine rows, one round trip
+    r.s = sw.resrest_flat_s >= 4 && f.nz >= 4 ? 4 : 2;
+    r.grid = (unsigned)r.gx * c.nx * ((f.nz + r.s - 1) / r.s);
+    if (served) r.family = KF_RR_FLAT;
+    return r;
+  }
+  r.by = 4; r.gy = (c.nx + r.by - 1) / r.by; r.grid = r.gx * r.gy;
+  // resrest_ahead = 10 * AW + AR, default 11 (A/B: scripts/probe/ab_resrest_ahead.sh -- 11, 12, 21 within 5 % of each other once the requests are unconditional)
+  r.aw = sw.resrest_ahead == 21 ? 2 : 1; r.ar = sw.resrest_ahead == 12 ? 2 : 1;
+  // slots 4 and 7 generated: when the level carries what the smoother's ZW form needs; the instance without the norm at the default
+  // look-ahead only (the others have no registers for it)
+  r.zw = r.aw == 1 && r.ar == 1 && !sw.resrest_no_zw && !want_norm && f.zw;
+  if (served) r.family = KF_RR_WALK;
+  return r;
 }

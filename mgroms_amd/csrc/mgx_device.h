@@ -1,6 +1,7 @@
 // Device helpers shared by the HIP translation units of libmgx.so.
 #pragma once
 #include "mgx_internal.h"
+#include "mgx_choice.h"
 
 #define WAVE 64
 // Cache policy.  A level that cannot live in the 256 MB Infinity Cache (level 1 of the 512x512x64 problem: 1.2 GB)
@@ -14,7 +15,7 @@
 template <bool NT> __device__ __forceinline__ double ld_stream(const double *p) { return NT ? NT_LOAD(p) : *p; }
 __device__ __forceinline__ void st_rt(double *p, double v, int nt) { if (nt) __builtin_nontemporal_store(v, p); else *p = v; }
 __device__ __forceinline__ double ld_rt(const double *p, int nt) { return nt ? __builtin_nontemporal_load(p) : *p; }
-static inline int level_streams(const LevView *L) { return (double)L->nx * L->ny * L->nz * 72.0 > 256e6; }
+static inline int level_streams(const LevView *L) { return ch_beyond_cache(lev_shape(L)); }   // one threshold: mgx_choice.h
 
 // positions c, jm, jp of columns j, j-1, j+1 inside a row of the JS layout (mgx_internal.h): j = 2 jh + 1 (jodd) or 2 jh + 2
 #define COL_POS(L, jh, jodd, c, jm, jp)                                 \

@@ -741,7 +741,7 @@ int mgxk_residual_nblocks(const LevView *L) { dim3 g = col_grid(L->ny / 2, L->nx
 void mgxk_residual(hipStream_t st, const LevView *L, double *partial, double *out, int real, int want_norm, Sides ph) {
   dim3 blk(WAVE, 4), g3 = col_grid(L->ny / 2, L->nx, 2), grd(g3.x * g3.y * 2);
   const int gx = g3.x, gy = g3.y;
-  if (L->zy != nullptr && L->nz >= 3) {
+  if (choose_operator_mf(lev_shape(L))) {
     if (real) hipLaunchKernelGGL((k_residual_mf<true>), grd, blk, 0, st, *L, partial, want_norm, gx, gy, ph, level_streams(L));
     else hipLaunchKernelGGL((k_residual_mf<false>), grd, blk, 0, st, *L, partial, want_norm, gx, gy, ph, level_streams(L));
   } else if (real) hipLaunchKernelGGL((k_residual<true>), grd, blk, 0, st, *L, partial, want_norm, gx, gy, ph, level_streams(L));

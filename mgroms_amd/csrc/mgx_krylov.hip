@@ -293,7 +293,7 @@ long long mgxq_partials(const LevView *L) {
 // stored slots (0), out[1] = the non-temporal variant of all three passes, out[2] = gx, out[3] = gy of pass 1's block map
 void mgxq_path(const LevView *L, int *out) {
   const dim3 g3 = col_grid(L->ny / 2, L->nx, 2);
-  out[0] = L->zy != nullptr && L->nz >= 3; out[1] = level_streams(L); out[2] = (int)g3.x; out[3] = (int)g3.y;
+  out[0] = choose_operator_mf(lev_shape(L)); out[1] = level_streams(L); out[2] = (int)g3.x; out[3] = (int)g3.y;
 }
 // q = A z (z = L->p, halos valid), sc[i] = (q, q_i) for the nd retained q_i
 void mgxq_apply(hipStream_t st, const LevView *L, double *qout, const double *const *qi, int nd, double *partial, double *sc, int real) {
@@ -302,7 +302,7 @@ void mgxq_apply(hipStream_t st, const LevView *L, double *qout, const double *co
   for (int n = 0; n < nd; n++) D.q[n] = qi[n];
   dim3 blk(WAVE, 4), g3 = col_grid(L->ny / 2, L->nx, 2), grd(g3.x * g3.y * 2);
   const int gx = g3.x, gy = g3.y, nt = level_streams(L);
-  if (L->zy != nullptr && L->nz >= 3) {
+  if (choose_operator_mf(lev_shape(L))) {
     if (real) hipLaunchKernelGGL((k_kr_apply_mf<true>), grd, blk, 0, st, *L, qout, D, partial, gx, gy, nt);
     else hipLaunchKernelGGL((k_kr_apply_mf<false>), grd, blk, 0, st, *L, qout, D, partial, gx, gy, nt);
   } else if (real) hipLaunchKernelGGL((k_kr_apply<true>), grd, blk, 0, st, *L, qout, D, partial, gx, gy, nt);
@@ -317,7 +317,7 @@ void mgxq_apply32(hipStream_t st, const LevView *L, const LevView32 *S, double i
   for (int n = 0; n < nd; n++) D.q[n] = qi[n];
   dim3 blk(WAVE, 4), g3 = col_grid(L->ny / 2, L->nx, 2), grd(g3.x * g3.y * 2);
   const int gx = g3.x, gy = g3.y, nt = level_streams(L);
-  if (L->zy != nullptr && L->nz >= 3) {
+  if (choose_operator_mf(lev_shape(L))) {
     if (real) hipLaunchKernelGGL((k_kr_apply32_mf<true>), grd, blk, 0, st, *L, *S, S->e, isg, zout, qout, D, partial, gx, gy, nt);
     else hipLaunchKernelGGL((k_kr_apply32_mf<false>), grd, blk, 0, st, *L, *S, S->e, isg, zout, qout, D, partial, gx, gy, nt);
   } else if (real) hipLaunchKernelGGL((k_kr_apply32<true>), grd, blk, 0, st, *L, *S, S->e, isg, zout, qout, D, partial, gx, gy, nt);

@@ -21,6 +21,7 @@
 // into the walking wave's L2 (k_rbseq_scan).
 #include "mgx_switches.h"
 #include "mgx_device.h"
+#include "mgx_choice.h"
 
 // g = T^-1 e1 of every interior column with tridiag's own recurrences (mg_relax.f90:320-332; bet, gam from k_pivots), and the two
 // multipliers of the scan.  One thread per column, lanes along j.
@@ -100,7 +101,7 @@ __device__ __forceinline__ void rbt_max(unsigned long long *a, unsigned long lon
 #endif
 // forwarding waves, workers per workgroup, planes per chunk, words between two chunk words (64 B), batches of eight rows a worker holds at most,
 // chunks between the walk and the workers that request their rows
-constexpr int RBF_NF = 8, RBF_WPB = 4, RBF_CH = 8, RBF_FS = 16, RBF_NB = 4, RBF_LEAD = 10;
+constexpr int RBF_NF = 8, RBF_FS = 16, RBF_NB = 4, RBF_LEAD = 10;   // (RBF_WPB, RBF_CH: mgx_choice.h, whose choice sizes the launch by them)
 __device__ long long g_rbs_timeout_ticks = 200000000LL;  // 2 s of the 100 MHz clock (mgxk_set_rbseq_timeout shortens it for the test)
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ unsigned int rbs_xcc_id() { return (unsigned int)__builtin_amdgcn_s_getreg(20 | (3 << 11)); }  // hwreg(HW_REG_XCC_ID, 0, 4)
@@ -539,7 +540,6 @@ __global__ __launch_bounds__(256) void k_rbseq_walk_apply(LevView L, int rb, Sid
 // k_rbseq_apply.  Nothing is handed from one workgroup to another: no progress words, no forwarding waves, no placement assumption.
 // Where rho is too close to one (m > RBW_MAXM) the walk over the whole level stays (k_rbseq_scan).
 // Workgroup = chunk ch of plane i, rows [kz*4*KR, (kz+1)*4*KR): waves 0-3 hold KR rows each (KR = 16 at nz = 64 ... 1 at nz = 4), wave 4 walks.
-constexpr int RBW_MAXM = 48;
 // Measured on level 1 of 512x512x64 (sweep of two passes + two of these launches, HIP events): ring depth 8 at 4 waves per SIMD 0.304-0.315 ms,
 // depth 4 or 2 at 5-6 waves per SIMD 0.304-0.313: the same.  With no plane walked at all (a timing probe, since removed) 0.295-0.296, with 14 planes
 // 0.306-0.310: the walk costs ~6 us of the launch's ~45 (201 MB algorithmic, 210 MB counted: profiles/r04_pmc_traffic_rb_window.json) -- the dependent
@@ -691,17 +691,29 @@ __global__ void k_rbseq_rho(LevView L, unsigned long long *out) {
   if (threadIdx.x == 0) atomicMax(out, b);
 }
 
-template <int CPL, int D, int NW, bool D0IN>
-static bool rbseq_fused_launch(hipStream_t st, const LevView *L, int nhelp, int rb, const RbFuse &F, int snapw) {
-  if constexpr (NW == 1 && D % RBF_CH == 0) {
-    const int per = 7 * RBF_WPB, octets = (F.nworkers + per - 1) / per, grid = 8 * (octets > nhelp + 3 ? octets : nhelp + 3);
-    const dim3 blk(WAVE * RBF_WPB);
-    if (snapw) { if (rb & 1) hipLaunchKernelGGL((k_rbseq_scan<CPL, D, 1, true, 1, D0IN, 2>), dim3(grid), blk, 0, st, *L, nhelp, rb, F);
-                 else hipLaunchKernelGGL((k_rbseq_scan<CPL, D, 0, true, 1, D0IN, 2>), dim3(grid), blk, 0, st, *L, nhelp, rb, F); }
-    else { if (rb & 1) hipLaunchKernelGGL((k_rbseq_scan<CPL, D, 1, true, 1, D0IN, 1>), dim3(grid), blk, 0, st, *L, nhelp, rb, F);
-           else hipLaunchKernelGGL((k_rbseq_scan<CPL, D, 0, true, 1, D0IN, 1>), dim3(grid), blk, 0, st, *L, nhelp, rb, F); }
-    return true;
-  } else return false;
+// ---- the launchers: an RbChoice (mgx_choice.h) to its template instance ----
+// One row of the walk's ladder: its rings DMAX, 4, 2, both colours, full half-rows or not, and the fused forms where the row has them (one
+// walking wave, whole chunks in the deepest ring).  (Unreachable instances the rows name: tests/test_kernel_choice_host.py lists them.)
+template <int CPL, int NW, bool D0IN>
+static void launch_rbseq_scan_row(hipStream_t st, const LevView *L, const RbChoice &c, int rb, const RbFuse &F, int snapw) {
+  constexpr int DMAX = ch_rbseq_dmax(CPL, NW, D0IN);
+  const dim3 grd(c.grid), blk(c.bx);
+  with_int<DMAX, 4, 2>(c.d, [&](auto DV) {
+    with_bool(rb & 1, [&](auto RB) {
+      constexpr int D = decltype(DV)::value, RBP = decltype(RB)::value;
+      if (c.family == KF_RB_SCAN_FUSED) {
+        if constexpr (NW == 1 && D == DMAX && D % RBF_CH == 0) {
+          if (snapw) hipLaunchKernelGGL((k_rbseq_scan<CPL, D, RBP, true, 1, D0IN, 2>), grd, blk, 0, st, *L, c.nhelp, rb, F);
+          else hipLaunchKernelGGL((k_rbseq_scan<CPL, D, RBP, true, 1, D0IN, 1>), grd, blk, 0, st, *L, c.nhelp, rb, F);
+        }
+      } else with_bool(c.full, [&](auto FU) { hipLaunchKernelGGL((k_rbseq_scan<CPL, D, RBP, decltype(FU)::value, NW, D0IN, 0>), grd, blk, 0, st, *L, c.nhelp, rb, F); });
+    });
+  });
+}
+static void launch_rbseq_scan(hipStream_t st, const LevView *L, const RbChoice &c, int rb, const RbFuse &F, int snapw) {
+  if (c.d0in) with_int<1, 2>(c.cpl, [&](auto C) { launch_rbseq_scan_row<decltype(C)::value, 1, true>(st, L, c, rb, F, snapw); });
+  else if (c.nw > 1) with_int<4, 8>(c.nw, [&](auto N) { launch_rbseq_scan_row<2, decltype(N)::value, false>(st, L, c, rb, F, snapw); });
+  else with_int<1, 2, 4, 8, 16>(c.cpl, [&](auto C) { launch_rbseq_scan_row<decltype(C)::value, 1, false>(st, L, c, rb, F, snapw); });
 }
 
 // Do the workgroups 0, 8, 16 ... of a launch share an XCD (what the forwarding waves of the fused launch rely on)?  Asked once per device.
@@ -729,91 +741,20 @@ void mgxk_rbseq_setup(hipStream_t st, const LevView *L) {
   hipLaunchKernelGGL(k_rbseq_setup, dim3((L->ny + 63) / 64, (L->nx + 3) / 4), dim3(64, 4), 0, st, *L);
 }
 
-// rows per correction wave: enough waves to fill the chip on the large levels, whole columns on the small ones
-static void rbseq_apply_shape(const LevView *L, int *ku, int *kr) {
-  const int nyh = L->ny / 2, nz = L->nz;
-  // (ku divides nz: an odd coarse level -- nz = 3 or 5 below nz = 24, 40, 48, 80, 96 -- takes one row at a time, or a wave would write
-  // the row above its column's top, i.e. the bottom row of the next plane)
-  *ku = nz % 8 == 0 ? 8 : (nz % 4 == 0 ? 4 : (nz % 2 == 0 ? 2 : 1));
-  *kr = nz;
-  const long long waves = (long long)((nyh + WAVE - 1) / WAVE) * L->nx;
-  while (*kr > *ku && *kr % 2 == 0 && (*kr / 2) % *ku == 0 && waves * (nz / *kr) < 4096) *kr /= 2;
-}
-
-// (b): d0 and the walk -- and, fz != nullptr, the correction (c) inside the walk's launch where an instance exists (returns 2 then).  Returns 0
-// when the level has no instance (more than 1024 columns per half-row): the caller then runs the planes one by one
-static int rbseq_scan_launch(hipStream_t st, const LevView *L, int rb, RbFuse *fz, int snapw, int have_d0) {
-  const int nyh = L->ny / 2, nx = L->nx;
-  if (L->gk == nullptr || nyh > 16 * WAVE || (nx & 1)) return 0;
-  const bool d0_out = mgx_switches().rbseq_d0_kernel;
-  const int rbp = rb & 1;
-  // helper workgroups that pull the walk's operands into its L2 (k_rbseq_scan): one per ~32 KB of operands, at most 32 (one per compute unit of an XCD)
-  // Measured (512x512x64, rocprofv3): level 1 (4.2 MB of operands, HBM-resident) one wave 88.4 us without helpers, 59.7 with 32; two waves
-  // (a barrier per plane) 73; levels 2-4 (1 MB and less) 20.9 / 11.0 / 7.6 us with or without them -- there the walk is bound by the ~190
-  // cycles a plane step costs to issue (4-5 memory instructions, the dependent DPP + FMA chain), and a few dozen extra workgroups only add
-  // launch time (level 4: 9.0 against 7.6).  So: helpers from 2 MB of operands on.
-  const long long opbytes = (long long)nx * nyh * 32;
-  int nhelp = opbytes >= (2LL << 20) ? (int)((opbytes + 131071) / 131072) : 0;
-  if (nhelp > 32) nhelp = 32;
-  if (nhelp > nx) nhelp = nx;
-  RbFuse none = {};
-  // the correction inside the walk's launch: instances for full half-rows, the deepest ring, nz a multiple of 8
-  int ku, kr;
-  rbseq_apply_shape(L, &ku, &kr);
-  // ... and where it pays: the correction of a colour is 24 B per cell; below ~100 MB it takes less than what the hand-off adds (the
-  // forwarding waves lag the walk by 2-5 us, the last workers finish ~4 us later: 256x256x32, 0.111 ms per sweep fused against 0.099)
-  const bool can_fuse = fz != nullptr && ku == 8 && (long long)(nx + 2) * L->RS * 8 < (1LL << 31) && (long long)nx * nyh * L->nz >= fz->min_cells;
-  // eight rows per worker there: what a worker does after its word is set -- 16 stores with the mirrors, ~1.4 us per eight rows under load --
-  // is the tail of the launch behind the walk's last plane (level-1 sweep at 512x512x64 with 32 / 16 / 8 rows: 0.346 / 0.345-0.357 / 0.339 ms)
-  if (can_fuse) kr = 8;
-  if (can_fuse) { fz->KR = kr; fz->nt = level_streams(L); fz->nchunk = (nyh + WAVE - 1) / WAVE; fz->nkz = L->nz / kr; fz->nworkers = nx * fz->nchunk * fz->nkz; }
-#define SCAN_LAUNCH(CPLV, DV, RBPV, FULLV, NWV, D0V, FUSEV, GRID, FARG)                                                \
-  hipLaunchKernelGGL((k_rbseq_scan<CPLV, DV, RBPV, FULLV, NWV, D0V, FUSEV>), dim3(GRID), dim3(WAVE * NWV), 0, st, *L, nhelp, rb, FARG)
-#define SCAN_CASE(CPLV, DV, FULLV, NWV, D0V)                                                                         \
-  { if (rbp) SCAN_LAUNCH(CPLV, DV, 1, FULLV, NWV, D0V, 0, 1 + 8 * nhelp, none); else SCAN_LAUNCH(CPLV, DV, 0, FULLV, NWV, D0V, 0, 1 + 8 * nhelp, none); \
-    return 1; }
-  // fused: workgroup b holds 1 + RBF_NF workers unless b % 8 == 0 (those: the walk with its forwarding waves, the helpers, nothing)
-#define FUSE_CASE(CPLV, DV, NWV, D0V)                                                                                \
-  if (can_fuse && NWV == 1 && nyh == CPLV * WAVE && nx % DV == 0 && rbseq_fused_launch<CPLV, DV, NWV, D0V>(st, L, nhelp, rb, *fz, snapw)) return 2;
-  // ring depth: D * (loads + stores per plane) < 63 (vmcnt), a divisor of nx
-#define SCAN_CPL(CPLV, DMAX, NWV, D0V)                                                                               \
-  { const bool full = nyh == CPLV * WAVE * NWV;                                                                      \
-    FUSE_CASE(CPLV, DMAX, NWV, D0V)                                                                                  \
-    if (nx % DMAX == 0) { if (full) SCAN_CASE(CPLV, DMAX, true, NWV, D0V) else SCAN_CASE(CPLV, DMAX, false, NWV, D0V) } \
-    if (nx % 4 == 0) { if (full) SCAN_CASE(CPLV, 4, true, NWV, D0V) else SCAN_CASE(CPLV, 4, false, NWV, D0V) }       \
-    if (full) SCAN_CASE(CPLV, 2, true, NWV, D0V) else SCAN_CASE(CPLV, 2, false, NWV, D0V) }
-  // small half-rows: one wave forms d0 itself (the level lives in L2; the walk is bound by its dependent chain, not by its requests)
-  // (half-rows of 65..128 columns whose pass wrote d0: the walk reads it -- three requests and a store per plane, 16 planes of look-ahead
-  // instead of 8 with five: level 2 of 512x512x64 20.5 -> ~16 us per colour, Vcycle 3.12 -> 3.08 ms; MGX_RBSEQ_NO_D0_MID: A/B)
-  const bool d0_mid = mgx_switches().rbseq_d0_mid;
-  if (nyh <= 2 * WAVE && !d0_out && !(have_d0 && d0_mid && nyh > WAVE)) {
-    if (nyh <= WAVE) SCAN_CPL(1, 16, 1, true)   // y, snapshot, the multiplier pair, the store of u: 4 operations per plane, 16 planes deep
-    SCAN_CPL(2, 8, 1, true)
-  }
-  if (!have_d0) hipLaunchKernelGGL(k_rbseq_d0, dim3((nyh + WAVE - 1) / WAVE, (nx + 3) / 4), dim3(WAVE, 4), 0, st, *L, rb);   // (the colour pass may have written it: LevView::d0w)
-  if (nyh <= WAVE) SCAN_CPL(1, 16, 1, false)
-  if (nyh <= 2 * WAVE) SCAN_CPL(2, 16, 1, false)
-  // wide half-rows: the requests of ONE wave (at most 63 in flight) do not cover the latency of a level that lives in HBM: several waves
-  // (256 columns per half-row: ONE wave with the helpers beats two waves with a barrier per plane, 59.7 against 73 us; wider half-rows
-  // -- 512 and 1024 columns, BASELINE config 5 -- would need 16 / 32 memory instructions per plane in one wave: several waves there, unmeasured)
-  if (nyh == 8 * WAVE) SCAN_CPL(2, 16, 4, false)
-  if (nyh == 16 * WAVE) SCAN_CPL(2, 16, 8, false)
-  if (nyh <= 4 * WAVE) SCAN_CPL(4, 8, 1, false)
-  if (nyh <= 8 * WAVE) SCAN_CPL(8, 4, 1, false)
-  SCAN_CPL(16, 2, 1, false)
-#undef SCAN_CPL
-#undef FUSE_CASE
-#undef SCAN_CASE
-#undef SCAN_LAUNCH
+// (b): d0 and the walk of choose_rbseq_scan (mgx_choice.h) -- and, fz != nullptr, the correction (c) inside the walk's launch where it says
+// so (returns 2 then).  Returns 0 when the level has no instance: the caller then runs the planes one by one
+static int rbseq_scan_launch(hipStream_t st, const LevView *L, int rb, const RbFuse *fz, int snapw, int have_d0) {
+  const RbChoice c = choose_rbseq_scan(lev_shape(L), have_d0, fz != nullptr, fz ? fz->min_cells : 0, mgx_switches());
+  if (c.family == KF_NONE) return 0;
+  if (c.d0_first) mgxk_rbseq_d0(st, L, rb);
+  RbFuse f = {};
+  if (c.family == KF_RB_SCAN_FUSED) { f = *fz; f.KR = c.kr; f.nt = c.nt; f.nchunk = c.nchunk; f.nkz = c.nkz; f.nworkers = c.nworkers; }
+  launch_rbseq_scan(st, L, c, rb, f, snapw);
+  return c.ret;
 }
 
 int mgxk_rbseq_scan(hipStream_t st, const LevView *L, int rb, int have_d0) { return rbseq_scan_launch(st, L, rb, nullptr, 0, have_d0); }
-// does the walk of this level read d0 from u1 (wide half-rows) rather than form it itself?  Then the colour pass should write it (LevView::d0w)
-int mgxk_rbseq_wants_d0(const LevView *L) {
-  const bool d0_out = mgx_switches().rbseq_d0_kernel, d0_mid = mgx_switches().rbseq_d0_mid;
-  // (wide half-rows: the walk reads d0; small levels: k_rbseq_walk_apply needs it where no workgroup of its launch writes)
-  return L->gk != nullptr && (L->ny / 2 > 2 * WAVE || d0_out || (L->ny / 2 <= WAVE && L->nx <= 128) || (d0_mid && L->ny / 2 > WAVE));
-}
+int mgxk_rbseq_wants_d0(const LevView *L) { return choose_rbseq_wants_d0(lev_shape(L), mgx_switches()); }
 
 // (b) + (c) in one launch where an instance exists (returns 2), else (b) alone (returns 1: the caller launches mgxk_rbseq_apply) or nothing (0).
 // words: this level's hand-off words (device memory, zero at allocation: nx / 8 chunk words, the walk's progress word, 64 B apart);
@@ -822,18 +763,17 @@ int mgxk_rbseq_wants_d0(const LevView *L) {
 int mgxk_rbseq_scan_apply(hipStream_t st, const LevView *L, int rb, Sides ph, int snapw, int have_d0, unsigned int *words, unsigned int seq, int *err, int test_stall, long long min_cells) {
   RbFuse f = {};
   f.ph = ph; f.flag = words; f.seq = seq; f.err = err; f.test_stall = test_stall; f.min_cells = min_cells;
-  if (L->nx >= (1 << 13) || err == nullptr || !rbseq_placement_ok(st)) return rbseq_scan_launch(st, L, rb, nullptr, 0, have_d0);
-  return rbseq_scan_launch(st, L, rb, &f, snapw, have_d0);
+  const bool fuse = ch_rbseq_fuse_planes(lev_shape(L)) && err != nullptr && rbseq_placement_ok(st);
+  return rbseq_scan_launch(st, L, rb, fuse ? &f : nullptr, snapw, have_d0);
 }
 
-// (b) + (c) of a small level in ONE launch (k_rbseq_walk_apply); needs d0 in u1 (the colour pass wrote it).  Returns 1 when launched.
+// (b) + (c) of a small level in ONE launch (choose_rbseq_walk_apply); needs d0 in u1 (the colour pass wrote it).  Returns 1 when launched.
 int mgxk_rbseq_walk_apply(hipStream_t st, const LevView *L, int rb, Sides ph, int snapw) {
-  const int nyh = L->ny / 2, nx = L->nx, nz = L->nz;
-  if (mgx_switches().no_rbseq_walk_apply || L->gk == nullptr || nyh > WAVE || nx > 128 || (nx & 1) || nz < 4 || (nz & 3)) return 0;
   mgx_before_launch();
-  constexpr int DW = 16;
-  const size_t lds = (size_t)(nx + DW + 1) * 64 * sizeof(double);
-  static bool attr = false;
+  const RbChoice c = choose_rbseq_walk_apply(lev_shape(L), mgx_switches());
+  if (c.family == KF_NONE) return 0;
+  constexpr int DW = 16;   // choose_rbseq_walk_apply's d
+  static bool attr = false;   // the LDS of a level of 128 planes (above the 64 KB a kernel gets without asking), granted to the four instances once
   if (!attr) {
     const int mx = (128 + DW + 1) * 64 * (int)sizeof(double);
     if (hipFuncSetAttribute((const void *)k_rbseq_walk_apply<DW, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
@@ -842,11 +782,11 @@ int mgxk_rbseq_walk_apply(hipStream_t st, const LevView *L, int rb, Sides ph, in
         hipFuncSetAttribute((const void *)k_rbseq_walk_apply<DW, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess) { (void)hipGetLastError(); return 0; }
     attr = true;
   }
-  const int pb = nx > 64 ? (nx + 63) / 64 : 1, nblk = (nx + pb - 1) / pb, nt = level_streams(L);
-  if (snapw) { if (rb & 1) hipLaunchKernelGGL((k_rbseq_walk_apply<DW, 1, true>), dim3(nblk), dim3(256), lds, st, *L, rb, ph, pb, nt);
-               else hipLaunchKernelGGL((k_rbseq_walk_apply<DW, 0, true>), dim3(nblk), dim3(256), lds, st, *L, rb, ph, pb, nt); }
-  else { if (rb & 1) hipLaunchKernelGGL((k_rbseq_walk_apply<DW, 1, false>), dim3(nblk), dim3(256), lds, st, *L, rb, ph, pb, nt);
-         else hipLaunchKernelGGL((k_rbseq_walk_apply<DW, 0, false>), dim3(nblk), dim3(256), lds, st, *L, rb, ph, pb, nt); }
+  with_bool(rb & 1, [&](auto RB) {
+    with_bool(snapw, [&](auto S) {
+      hipLaunchKernelGGL((k_rbseq_walk_apply<DW, decltype(RB)::value, decltype(S)::value>), dim3(c.grid), dim3(c.bx), c.lds, st, *L, rb, ph, c.pb, c.nt);
+    });
+  });
   return mgx_launched();
 }
 
@@ -879,30 +819,20 @@ int mgxk_rbseq_window_planes(double rho) {
   const double m = __builtin_ceil(64.0 * 0.6931471805599453 / -__builtin_log(rho));
   return m < 2.0 ? 2 : (m > (double)RBW_MAXM ? 0 : (int)m);
 }
-// (b) + (c) by the windowed walk (k_rbseq_window); needs d0 in u1 (the colour pass or k_rbseq_d0 wrote it) and m from mgxk_rbseq_window_planes.
+// (b) + (c) by the windowed walk (choose_rbseq_window); needs d0 in u1 (the colour pass or k_rbseq_d0 wrote it) and m from mgxk_rbseq_window_planes.
 // Returns 1 when launched.
 int mgxk_rbseq_window(hipStream_t st, const LevView *L, int rb, Sides ph, int snapw, int m, int kcut) {
-  const int nyh = L->ny / 2, nz = L->nz;
-  if (L->gk == nullptr || m < 1 || m > RBW_MAXM || nyh < 1 || (L->ny & 1) || L->nx > 65535) return 0;
-  int kr = nz % 64 == 0 ? 16 : (nz % 32 == 0 ? 8 : (nz % 16 == 0 ? 4 : (nz % 8 == 0 ? 2 : (nz % 4 == 0 ? 1 : 0))));
-  if (!kr || nz / (4 * kr) > 65535) return 0;
-  if (kcut < 1 || kcut > nz) kcut = nz;
-  // the rows the correction reaches, spread over the four row waves of a workgroup (16 of 64 rows: four rows per wave rather than one wave with all
-  // sixteen and three idle), and only the row groups that hold any are launched
-  while (kr > 1 && 4 * (kr / 2) >= kcut) kr /= 2;
   mgx_before_launch();
-  // the walking wave at raised priority (s_setprio 3): level-1 sweep 0.3075-0.3150 -> 0.2989-0.3073 ms (three runs each, alternating); MGX_RBW_PRIO=0: A/B
-  const int prio = mgx_switches().rbw_prio;
-  const int nt = level_streams(L), cpl = nyh <= WAVE ? 1 : 2, nch = (nyh + WAVE - 1) / WAVE, nkz = (kcut + 4 * kr - 1) / (4 * kr);
-  const int xmap = !mgx_switches().rbseq_window_no_xmap && L->nx % 8 == 0 && (long long)nch * L->nx * nkz < (1LL << 31);
-  const dim3 grd = xmap ? dim3(nch * L->nx * nkz) : dim3(nch, L->nx, nkz), blk(320);
-#define WIN_CASE(CPLV, KRV)                                                                                          \
-  { if (snapw) hipLaunchKernelGGL((k_rbseq_window<CPLV, KRV, true, (KRV <= 4 ? 4 : 8)>), grd, blk, 0, st, *L, rb, ph, m, nt, xmap, nch, nkz, prio, kcut); \
-    else hipLaunchKernelGGL((k_rbseq_window<CPLV, KRV, false, (KRV <= 4 ? 4 : 8)>), grd, blk, 0, st, *L, rb, ph, m, nt, xmap, nch, nkz, prio, kcut); }
-#define WIN_KR(CPLV) { if (kr == 16) WIN_CASE(CPLV, 16) else if (kr == 8) WIN_CASE(CPLV, 8) else if (kr == 4) WIN_CASE(CPLV, 4) else if (kr == 2) WIN_CASE(CPLV, 2) else WIN_CASE(CPLV, 1) }
-  if (cpl == 1) WIN_KR(1) else WIN_KR(2)
-#undef WIN_KR
-#undef WIN_CASE
+  const RbChoice c = choose_rbseq_window(lev_shape(L), m, kcut, mgx_switches());
+  if (c.family == KF_NONE) return 0;
+  with_int<1, 2>(c.cpl, [&](auto C) {
+    with_int<16, 8, 4, 2, 1>(c.kr, [&](auto K) {
+      with_bool(snapw, [&](auto S) {
+        constexpr int CPL = decltype(C)::value, KR = decltype(K)::value;
+        hipLaunchKernelGGL((k_rbseq_window<CPL, KR, decltype(S)::value, (KR <= 4 ? 4 : 8)>), dim3(c.grid, c.gy, c.gz), dim3(c.bx), 0, st, *L, rb, ph, m, c.nt, c.xmap, c.nchunk, c.nkz, c.prio, c.kcut);
+      });
+    });
+  });
   return mgx_launched();
 }
 
@@ -912,16 +842,12 @@ int mgxk_set_rbseq_timeout(double ms) {
 }
 
 void mgxk_rbseq_apply(hipStream_t st, const LevView *L, int rb, Sides ph, int snapw) {
-  const int nyh = L->ny / 2, nz = L->nz;
-  int ku, kr;
-  rbseq_apply_shape(L, &ku, &kr);
-  const dim3 grd((nyh + WAVE - 1) / WAVE, (L->nx + 3) / 4, nz / kr), blk(WAVE, 4);
-  const int nt = level_streams(L);
-#define APPLY_CASE(KUV)                                                                                              \
-  { if (snapw) hipLaunchKernelGGL((k_rbseq_apply<KUV, true>), grd, blk, 0, st, *L, rb, ph, kr, nt);                 \
-    else hipLaunchKernelGGL((k_rbseq_apply<KUV, false>), grd, blk, 0, st, *L, rb, ph, kr, nt); }
-  if (ku == 8) APPLY_CASE(8) else if (ku == 4) APPLY_CASE(4) else if (ku == 2) APPLY_CASE(2) else APPLY_CASE(1)
-#undef APPLY_CASE
+  const RbChoice c = choose_rbseq_apply(lev_shape(L));
+  with_int<8, 4, 2, 1>(c.ku, [&](auto K) {
+    with_bool(snapw, [&](auto S) {
+      hipLaunchKernelGGL((k_rbseq_apply<decltype(K)::value, decltype(S)::value>), dim3(c.grid, c.gy, c.gz), dim3(c.bx, c.by), 0, st, *L, rb, ph, c.kr, c.nt);
+    });
+  });
 }
 
 }  // extern "C"

@@ -23,6 +23,7 @@
 // bound by issue, not by its 3.8 TB/s, which is why a quarter less traffic buys a tenth of the time (profiles/resrest_zw.json).
 #include "mgx_switches.h"
 #include "mgx_device.h"
+#include "mgx_choice.h"
 
 namespace {
 
@@ -431,51 +432,42 @@ __global__ __launch_bounds__(64) void k_residual_restrict_flat(LevView F, LevVie
 #undef RR_LAST
 #undef RR_FIRST
 
+// ---- the launcher: an RrChoice (mgx_choice.h) to its template instance ----
+// the flat form with S = 4, 2; the walking form with the look-aheads (AW, AR) = (1, 1), (1, 2), (2, 1), and with generated slots 4 and 7 the
+// one instance that has the registers for them: (1, 1) without the norm
+static void launch_resrest(hipStream_t st, const LevView *F, const LevView *C, const RrChoice &c, double *dst, Sides ph, double *zero, double *partial, double *dup) {
+  with_bool(c.real, [&](auto R) {
+    constexpr bool REAL = decltype(R)::value;
+    if (c.family == KF_RR_FLAT) {
+      with_int<4, 2>(c.s, [&](auto SV) {
+        with_bool(c.norm, [&](auto N) {
+          hipLaunchKernelGGL((k_residual_restrict_flat<REAL, decltype(SV)::value, decltype(N)::value>), dim3(c.grid), dim3(WAVE), 0, st, *F, *C, dst, ph, zero, c.gx, partial, dup);
+        });
+      });
+      return;
+    }
+    const dim3 grd(c.grid), blk(WAVE, c.by);
+    if (c.zw) { hipLaunchKernelGGL((k_residual_restrict<REAL, 1, 1, false, true>), grd, blk, 0, st, *F, *C, dst, ph, zero, c.gx, c.gy, partial, dup); return; }
+    with_bool(c.norm, [&](auto N) {
+      constexpr bool NORM = decltype(N)::value;
+      if (c.aw == 2) hipLaunchKernelGGL((k_residual_restrict<REAL, 2, 1, NORM, false>), grd, blk, 0, st, *F, *C, dst, ph, zero, c.gx, c.gy, partial, dup);
+      else if (c.ar == 2) hipLaunchKernelGGL((k_residual_restrict<REAL, 1, 2, NORM, false>), grd, blk, 0, st, *F, *C, dst, ph, zero, c.gx, c.gy, partial, dup);
+      else hipLaunchKernelGGL((k_residual_restrict<REAL, 1, 1, NORM, false>), grd, blk, 0, st, *F, *C, dst, ph, zero, c.gx, c.gy, partial, dup);
+    });
+  });
+}
+
 extern "C" {
 
-// returns 1 when launched (matrix-free slopes present, level large enough to be bandwidth-bound), 0 = use mgxk_residual + mgxk_fine2coarse
+// workgroups (= pairs of norm partials) of the launch below, for a caller that sums r^2
+int mgxk_residual_restrict_grid(const LevView *F, const LevView *C) { return (int)choose_resrest(lev_shape(F), lev_shape(C), 1, true, mgx_switches()).grid; }
+// returns 1 when launched (choose_resrest, mgx_choice.h), 0 = use mgxk_residual + mgxk_fine2coarse
 // partial != nullptr: also sum r^2 (partials, one pair per workgroup: room for twice mgxk_residual_restrict_grid()); dup: second destination of the coarse sums
-int mgxk_residual_restrict_grid(const LevView *F, const LevView *C) {  // workgroups (= norm partials) of the launch below
-  const int gx = (C->ny + 31) / 32;
-  if ((long long)F->nx * F->ny * F->nz <= mgx_switches().resrest_flat_max) {
-    const int Sv = (mgx_switches().resrest_flat_s >= 4 && F->nz >= 4) ? 4 : 2;
-    return gx * C->nx * ((F->nz + Sv - 1) / Sv);
-  }
-  return gx * ((C->nx + 3) / 4);
-}
 int mgxk_residual_restrict_ex(hipStream_t st, const LevView *F, const LevView *C, double *dst, int real, Sides ph, double *zero, double *partial, double *dup) {
   mgx_before_launch();
-  const Switches &sw = mgx_switches();
-  if (sw.no_resrest || F->zy == nullptr || F->nz < 2 || (F->nz & 1)) return 0;
-  if (C->nx * 2 != F->nx || C->ny * 2 != F->ny) return 0;
-  if ((long long)F->nx * F->ny * F->nz < sw.resrest_min) return 0;
-  if ((long long)F->nx * F->ny * F->nz <= sw.resrest_flat_max) {  // no walk: one wave per S fine rows, one round trip
-    const int gx = (C->ny + 31) / 32, Sr = sw.resrest_flat_s ? sw.resrest_flat_s : 2;
-    dim3 blk(WAVE);
-#define RRF(REALV, SV, NV) hipLaunchKernelGGL((k_residual_restrict_flat<REALV, SV, NV>), dim3((unsigned)gx * C->nx * ((F->nz + SV - 1) / SV)), blk, 0, st, *F, *C, dst, ph, zero, gx, partial, dup)
-#define RRF2(SV) { if (partial) { if (real) RRF(true, SV, true); else RRF(false, SV, true); } else { if (real) RRF(true, SV, false); else RRF(false, SV, false); } }
-    if (Sr >= 4 && F->nz >= 4) RRF2(4) else RRF2(2)
-#undef RRF2
-#undef RRF
-    return mgx_launched();
-  }
-  const int by = 4, gx = (C->ny + 31) / 32, gy = (C->nx + by - 1) / by;
-  dim3 blk(WAVE, by), grd(gx * gy);
-  const int deep = sw.resrest_ahead;  // 10 * AW + AR, default 11 (A/B: scripts/probe/ab_resrest_ahead.sh -- 11, 12, 21 within 5 % of each other once the requests are unconditional)
-  // slots 4 and 7 generated: when the level carries what the smoother's ZW form needs, i.e. as define_matrices leaves it (not after bmask,
-  // a user matrix or MGX_NO_MF); the instance without the norm at the default look-ahead only (the others have no registers for it)
-  const bool zw = !sw.resrest_no_zw && !partial && F->m4 && F->d4 && F->m7 && F->d7 && F->h2 && F->hi2 && F->ze2 && F->cffw && F->csw;
-#define RRW(REALV, AWV, ARV, NV, ZV) hipLaunchKernelGGL((k_residual_restrict<REALV, AWV, ARV, NV, ZV>), grd, blk, 0, st, *F, *C, dst, ph, zero, gx, gy, partial, dup)
-#define RRW3(AWV, ARV, ZV) { if (partial) { if (real) RRW(true, AWV, ARV, true, ZV); else RRW(false, AWV, ARV, true, ZV); } else { if (real) RRW(true, AWV, ARV, false, ZV); else RRW(false, AWV, ARV, false, ZV); } }
-#define RRW2(AWV, ARV) RRW3(AWV, ARV, false)
-  switch (deep) {
-    case 12: RRW2(1, 2) break;
-    case 21: RRW2(2, 1) break;
-    default: if (zw) { if (real) RRW(true, 1, 1, false, true); else RRW(false, 1, 1, false, true); } else RRW2(1, 1) break;
-  }
-#undef RRW2
-#undef RRW3
-#undef RRW
+  const RrChoice c = choose_resrest(lev_shape(F), lev_shape(C), real, partial != nullptr, mgx_switches());
+  if (c.family == KF_NONE) return 0;
+  launch_resrest(st, F, C, c, dst, ph, zero, partial, dup);
   return mgx_launched();
 }
 int mgxk_residual_restrict(hipStream_t st, const LevView *F, const LevView *C, double *dst, int real, Sides ph, double *zero) {

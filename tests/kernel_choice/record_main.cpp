@@ -1,9 +1,11 @@
-// Which kernel serves which level: a stand-alone host program (no GPU, no HIP runtime) that calls the extern "C" smoother wrappers
-// of mgx_wrappers.h over a table of shapes, flags and A/B switches and prints, per call, one line per kernel launch (the demangled
-// template instance, grid, block, dynamic LDS bytes, scalar arguments) and the wrapper's return value.
+// Which kernel serves which level: a stand-alone host program (no GPU, no HIP runtime) that calls the extern "C" wrappers of
+// mgx_wrappers.h -- the smoother's, the sequential-order red-black walk's, the fused residual + restriction's -- over a table of shapes,
+// flags and A/B switches and prints, per call, one line per kernel launch (the demangled template instance, grid, block, dynamic LDS
+// bytes, scalar arguments) and the wrapper's return value.
 //
-// Built from mgx_relax.hip, mgx_relax_coarse.hip, mgx_relax_ks.hip and mgx_relax_tall.hip compiled host-only behind record_shim.h, which
-// sends their launches here; the stand-ins at the end of this file replace what the compiler's registration code asks of the HIP runtime.
+// Built from mgx_relax.hip, mgx_relax_coarse.hip, mgx_relax_ks.hip, mgx_relax_tall.hip, mgx_rbseq.hip and mgx_resrest.hip compiled
+// host-only behind record_shim.h, which sends their launches here; the stand-ins at the end of this file replace what the units and the
+// compiler's registration code ask of the HIP runtime.
 // tests/test_kernel_choice_host.py builds and runs it and compares digests with tests/golden/kernel_choice.json.
 //
 //   record_main [refuse|fail|names]     refuse: every hipFuncSetAttribute is refused; fail: hipGetLastError reports an error after every launch
@@ -56,6 +58,12 @@ void rec_arg(const void *p) { g_line += p ? "ptr " : "null "; }
 void rec_arg(const Sides &s) { char b[32]; snprintf(b, sizeof b, "S%d%d%d%d/%d ", s.S, s.E, s.N, s.W, s.part); g_line += b; }
 void rec_arg(const LevView &L) { char b[96]; snprintf(b, sizeof b, "L(%d,%d,%d,zy=%d,d0w=%d) ", L.nx, L.ny, L.nz, L.zy != nullptr, L.d0w != nullptr); g_line += b; }
 void rec_arg(const LevView32 &L) { char b[64]; snprintf(b, sizeof b, "L32(%d,%d,%d) ", L.nx, L.ny, L.nz); g_line += b; }
+void rec_fuse(const Sides &ph, const int (&v)[6], long long min_cells, const void *flag, unsigned int seq, const void *err) {
+  char b[160];
+  rec_arg(ph);
+  snprintf(b, sizeof b, "F(KR=%d,nt=%d,nchunk=%d,nkz=%d,nworkers=%d,stall=%d,min=%lld,flag=%d,seq=%u,err=%d) ", v[0], v[1], v[2], v[3], v[4], v[5], min_cells, flag != nullptr, seq, err != nullptr);
+  g_line += b;
+}
 void rec_end() { puts(g_line.c_str()); }
 hipError_t rec_last_error() { const hipError_t e = g_err; g_err = hipSuccess; return e; }
 hipError_t rec_set_attribute(const void *kernel, hipFuncAttribute attr, int value) {
@@ -232,6 +240,208 @@ static void pass_calls(int nz, const char *sw, int depth) {
       }
 }
 
+// ---- mgx_rbseq.hip: the sequential-order red-black walk ----
+static int g_dev = -1;              // what the stand-in hipGetDevice answers; < 0: no device
+static bool g_probe_equal = true;   // what the stand-in copy leaves in the placement probe's answer (rbseq_placement_ok asks once per device)
+static const char *const RB_SWITCHES[] = {"default", "rbseq_d0_kernel", "rbseq_no_d0_mid", "no_rbseq_walk_apply", "rbseq_window_no_xmap", "rbw_prio0"};
+constexpr int NRBSW = sizeof RB_SWITCHES / sizeof *RB_SWITCHES;
+static const char *set_rb_switch(int s) {
+  switches_default();
+  switch (s) {
+    case 1: g_sw.rbseq_d0_kernel = true; break;
+    case 2: g_sw.rbseq_d0_mid = false; break;
+    case 3: g_sw.no_rbseq_walk_apply = true; break;
+    case 4: g_sw.rbseq_window_no_xmap = true; break;
+    case 5: g_sw.rbw_prio = 0; break;
+    default: break;
+  }
+  return RB_SWITCHES[s];
+}
+static LevView level_rb(int nx, int ny, int nz, bool gk) {
+  LevView v = level(nx, ny, nz, true, false);
+  if (gk) v.gk = v.ag58 = v.u1 = g_fake;
+  return v;
+}
+// what the colour pass is told about d0 (the test: a walk that reads d0 from u1 has asked for it)
+static void wants_d0_line(const LevView &L) { printf("  wants_d0 %d\n", mgxk_rbseq_wants_d0(&L)); }
+
+// half-rows of 64, 128, 256, 512, 1024 columns, one more, and partial ones in between
+static const int RB_NY[] = {2, 100, 128, 130, 200, 256, 258, 400, 512, 514, 1000, 1024, 1026, 2000, 2048, 2050};
+// odd; divisible by 16, by 8, 4, 2 only; either side of 128; operands either side of 2 MB (254 / 256 x 512) and of the 32 helpers; either side of 1 << 13
+static const int RB_NX[] = {15, 16, 24, 12, 10, 64, 128, 130, 254, 256, 512, 2048, 8190, 8192};
+
+// both colours, the snapshot written or not; depth 2: once per shape no error word and no gk
+static void scan_calls(int nz, const char *sw, int depth) {
+  for (const int ny : RB_NY)
+    for (const int nx : RB_NX) {
+      const LevView L = level_rb(nx, ny, nz, true), L0 = level_rb(nx, ny, nz, false);
+      const long long cells = (long long)nx * (ny / 2) * nz;
+      int err = 0;
+      for (int rb = 0; rb <= 1; rb++)
+        for (int have_d0 = 0; have_d0 <= 1; have_d0++) {
+          if (nz == 5 || nz == 12 || nz == 64) {   // (the plain walk does not look at nz)
+            call_head("mgxk_rbseq_scan", nz, -1, "%dx%d rb=%d have_d0=%d gk=1 sw=%s", nx, ny, rb, have_d0, sw);
+            const int r = mgxk_rbseq_scan(nullptr, &L, rb, have_d0);
+            wants_d0_line(L);
+            call_ret(r);
+          }
+          for (int snapw = 0; snapw <= 1; snapw++)
+            for (int below = 0; below <= 1; below++) {   // min_cells = the level's cells of a colour (fused from there on), and one more
+              call_head("mgxk_rbseq_scan_apply", nz, -1, "%dx%d rb=%d have_d0=%d snapw=%d min_cells=cells+%d err=1 gk=1 sw=%s", nx, ny, rb, have_d0, snapw, below, sw);
+              const int r = mgxk_rbseq_scan_apply(nullptr, &L, rb, sides(0), snapw, have_d0, (unsigned int *)g_fake, 3, &err, 0, cells + below);
+              wants_d0_line(L);
+              call_ret(r);
+            }
+        }
+      if (depth != 2) continue;
+      call_head("mgxk_rbseq_scan_apply", nz, -1, "%dx%d rb=1 have_d0=1 snapw=1 min_cells=0 err=0 gk=1 sw=%s", nx, ny, sw);
+      int r = mgxk_rbseq_scan_apply(nullptr, &L, 1, sides(0), 1, 1, (unsigned int *)g_fake, 3, nullptr, 0, 0);
+      wants_d0_line(L);
+      call_ret(r);
+      call_head("mgxk_rbseq_scan_apply", nz, -1, "%dx%d rb=1 have_d0=1 snapw=1 min_cells=0 err=1 gk=0 sw=%s", nx, ny, sw);
+      r = mgxk_rbseq_scan_apply(nullptr, &L0, 1, sides(0), 1, 1, (unsigned int *)g_fake, 3, &err, 0, 0);
+      wants_d0_line(L0);
+      call_ret(r);
+    }
+}
+static void walk_apply_calls(int nz, const char *sw, int depth) {
+  static const int NX[] = {2, 15, 64, 66, 128, 130}, NY[] = {2, 100, 128, 130};
+  for (const int nx : NX)
+    for (const int ny : NY)
+      for (int gk = depth == 2 ? 0 : 1; gk <= 1; gk++)
+        for (int rb = depth && gk ? 0 : 1; rb <= 1; rb++)
+          for (int snapw = depth && gk ? 0 : 1; snapw <= 1; snapw++) {
+            const LevView L = level_rb(nx, ny, nz, gk);
+            call_head("mgxk_rbseq_walk_apply", nz, -1, "%dx%d rb=%d snapw=%d gk=%d sw=%s", nx, ny, rb, snapw, gk, sw);
+            const int r = mgxk_rbseq_walk_apply(nullptr, &L, rb, sides(0), snapw);
+            wants_d0_line(L);
+            call_ret(r);
+          }
+}
+// kcut = 0, 1, mid, nz, nz + 1 at m = 14 (what the seamount levels take); m = 0, 1, RBW_MAXM = 48 and one more at kcut = nz
+static void window_calls(int nz, const char *sw, int depth) {
+  static const int NX[] = {8, 12, 64, 65528, 65535, 65536}, NY[] = {2, 63, 100, 128, 130, 512};
+  for (const int nx : NX)
+    for (const int ny : NY)
+      for (int var = 0; var < 10; var++) {
+        const int kcut = var == 0 ? 0 : (var == 1 ? 1 : (var == 2 ? nz / 2 : (var == 4 ? nz + 1 : nz)));
+        const int m = var == 5 ? 0 : (var == 6 ? 1 : (var == 7 ? 48 : (var == 8 ? 49 : 14)));
+        const int gk = var != 9;
+        for (int rb = depth == 2 && var == 0 ? 0 : 1; rb <= 1; rb++)
+          for (int snapw = depth && var < 5 ? 0 : 1; snapw <= 1; snapw++) {
+            const LevView L = level_rb(nx, ny, nz, gk);
+            call_head("mgxk_rbseq_window", nz, -1, "%dx%d rb=%d snapw=%d m=%d kcut=%d gk=%d sw=%s", nx, ny, rb, snapw, m, kcut, gk, sw);
+            call_ret(mgxk_rbseq_window(nullptr, &L, rb, sides(0), snapw, m, kcut));
+          }
+      }
+}
+// waves of a colour times row groups either side of 4096
+static void apply_calls(int nz, const char *sw, int depth) {
+  static const Shape SH[] = {{16, 16}, {15, 17}, {64, 128}, {128, 128}, {256, 256}, {254, 258}, {512, 512}, {1024, 256}, {4096, 512}};
+  for (const Shape &s : SH)
+    for (int rb = depth == 2 ? 0 : 1; rb <= 1; rb++)
+      for (int snapw = depth ? 0 : 1; snapw <= 1; snapw++) {
+        const LevView L = level_rb(s.nx, s.ny, nz, true);
+        call_head("mgxk_rbseq_apply", nz, -1, "%dx%d rb=%d snapw=%d sw=%s", s.nx, s.ny, rb, snapw, sw);
+        mgxk_rbseq_apply(nullptr, &L, rb, sides(0), snapw);
+        call_ret(0);
+      }
+}
+// the launches that choose nothing (one kernel each, sized by the level), the two host functions beside them, and the placement probe's outcomes
+static void rbseq_other_calls() {
+  switches_default();
+  static const Shape SH[] = {{16, 16}, {15, 17}, {256, 256}, {130, 1026}};
+  for (const int nz : {2, 5, 64}) {
+    for (const Shape &s : SH) {
+      const LevView L = level_rb(s.nx, s.ny, nz, true);
+      call_head("mgxk_rbseq_setup", nz, -1, "%dx%d", s.nx, s.ny); mgxk_rbseq_setup(nullptr, &L); call_ret(0);
+      call_head("mgxk_rbseq_rho", nz, -1, "%dx%d", s.nx, s.ny); mgxk_rbseq_rho(nullptr, &L, g_fake); call_ret(0);
+      call_head("mgxk_rbseq_gdecay", nz, -1, "%dx%d", s.nx, s.ny); mgxk_rbseq_gdecay(nullptr, &L, g_fake); call_ret(0);
+      call_head("mgxk_rbseq_d0", nz, -1, "%dx%d", s.nx, s.ny); mgxk_rbseq_d0(nullptr, &L, 1); call_ret(0);
+    }
+    double decay[64];
+    for (int cut = 0; cut <= nz; cut++) {
+      for (int k = 0; k < nz; k++) decay[k] = k < cut ? 1.0 / (k + 1) : 1e-20;
+      call_head("mgxk_rbseq_window_rows", nz, -1, "rows above 2^-64: %d", cut);
+      call_ret(mgxk_rbseq_window_rows(decay, nz));
+    }
+  }
+  for (const double rho : {-1.0, 0.0, 1e-301, 0.03, 0.3, 0.39, 0.4, 0.99, 1.0}) {
+    call_head("mgxk_rbseq_window_planes", 0, -1, "rho=%g", rho);
+    call_ret(mgxk_rbseq_window_planes(rho));
+  }
+  call_head("mgxk_set_rbseq_timeout", 0, -1, "ms=100");
+  call_ret(mgxk_set_rbseq_timeout(100.0));
+  // a device whose workgroups 0, 8, 16 ... do not share an XCD (asked, then remembered), a device number past the table, no device: never fused
+  int err = 0;
+  const LevView L = level_rb(256, 256, 64, true);
+  static const int DEV[] = {2, 2, 64, -1, 1};
+  for (const int dev : DEV) {
+    g_dev = dev; g_probe_equal = dev == 1;
+    call_head("mgxk_rbseq_scan_apply", 64, -1, "256x256 rb=1 have_d0=1 snapw=1 min_cells=0 err=1 gk=1 device=%d probe=%s", dev, g_probe_equal ? "equal" : "unequal");
+    call_ret(mgxk_rbseq_scan_apply(nullptr, &L, 1, sides(0), 1, 1, (unsigned int *)g_fake, 3, &err, 0, 0));
+  }
+}
+
+// ---- mgx_resrest.hip: the fused residual + restriction ----
+static const char *const RR_SWITCHES[] = {"default", "no_resrest", "resrest_no_zw"};
+// zw: bit q set = the q-th of the nine fields the generated slots 4 and 7 need is present
+static LevView level_rr(int nx, int ny, int nz, bool zy, int zw) {
+  LevView v = level(nx, ny, nz, zy, false);
+  double **const f[] = {&v.m4, &v.d4, &v.m7, &v.d7, &v.h2, &v.hi2, &v.ze2};
+  for (int q = 0; q < 7; q++) if (zw >> q & 1) *f[q] = g_fake;
+  if (zw >> 7 & 1) v.cffw = g_fake;
+  if (zw >> 8 & 1) v.csw = g_fake;
+  return v;
+}
+static void rr_call(int nz, const Shape &s, int cv, int real, int partial, int zy, int zw, const char *what, const char *sw) {
+  const LevView F = level_rr(s.nx, s.ny, nz, zy, zw);
+  const LevView C = level(cv == 1 ? s.nx : s.nx / 2, cv == 2 ? s.ny : s.ny / 2, cv == 3 ? nz : nz / 2, true, false);
+  call_head("mgxk_residual_restrict_ex", nz, -1, "%dx%d coarse=%d real=%d partial=%d zy=%d zw=%03x min=%lld flat_max=%lld flat_s=%d ahead=%d (%s) sw=%s", s.nx, s.ny, cv, real, partial, zy, zw,
+            g_sw.resrest_min, g_sw.resrest_flat_max, g_sw.resrest_flat_s, g_sw.resrest_ahead, what, sw);
+  const int r = mgxk_residual_restrict_ex(nullptr, &F, &C, g_fake, real, sides(0), g_fake, partial ? g_fake : nullptr, nullptr);
+  if (partial) printf("  restrict_grid %d\n", mgxk_residual_restrict_grid(&F, &C));   // the norm's partials are sized by it (the test: = the launch's workgroups)
+  call_ret(r);
+}
+// Per shape the flat form (resrest_flat_max = the level's cells: `<=`) and the walking one (one cell less) with every value of their switches, the
+// nine fields absent in turn, resrest_min at the level's cells (`<`: served) and one more, and the coarse level not half the fine one
+static void resrest_calls(int nz, int isw, int depth) {
+  static const Shape SH[] = {{16, 16}, {30, 34}, {64, 64}, {128, 128}, {256, 256}, {258, 256}, {512, 512}};
+  const char *sw = RR_SWITCHES[isw];
+  for (const Shape &s : SH) {
+    const long long cells = (long long)s.nx * s.ny * nz;
+    for (int form = 0; form < 3; form++) {   // as the defaults have it, flat, walking
+      static const int FLAT_S[] = {0, 2, 4}, AHEAD[] = {11, 12, 21, 13};
+      const int nv = form == 0 ? 1 : (form == 1 ? 3 : 4);
+      for (int v = 0; v < nv; v++)
+        for (int real = depth ? 0 : 1; real <= 1; real++)
+          for (int partial = 0; partial <= 1; partial++)
+            for (int zw = 0; zw <= 0x1ff; zw += 0x1ff) {
+              switches_default();
+              g_sw.no_resrest = isw == 1; g_sw.resrest_no_zw = isw == 2;
+              if (form) g_sw.resrest_flat_max = form == 1 ? cells : cells - 1;
+              if (form == 1) g_sw.resrest_flat_s = FLAT_S[v];
+              if (form == 2) g_sw.resrest_ahead = AHEAD[v];
+              rr_call(nz, s, 0, real, partial, 1, zw, form == 0 ? "default" : (form == 1 ? "flat" : "walk"), sw);
+            }
+    }
+    switches_default();
+    g_sw.no_resrest = isw == 1; g_sw.resrest_no_zw = isw == 2;
+    g_sw.resrest_flat_max = cells - 1;
+    for (int q = 0; q < 9; q++) rr_call(nz, s, 0, 1, 0, 1, 0x1ff & ~(1 << q), "walk, one field absent", sw);
+    if (!depth) continue;
+    switches_default();
+    for (int more = 0; more <= 1; more++) { g_sw.resrest_min = cells + more; rr_call(nz, s, 0, 1, 1, 1, 0x1ff, "min", sw); }
+    switches_default();
+    for (int cv = 1; cv <= 3; cv++) rr_call(nz, s, cv, 1, 1, 1, 0x1ff, "coarse not half", sw);
+    rr_call(nz, s, 0, 1, 1, 0, 0x1ff, "no slopes", sw);
+    const LevView F = level_rr(s.nx, s.ny, nz, true, 0x1ff), C = level(s.nx / 2, s.ny / 2, nz / 2, true, false);
+    call_head("mgxk_residual_restrict", nz, -1, "%dx%d real=1 sw=%s", s.nx, s.ny, sw);
+    call_ret(mgxk_residual_restrict(nullptr, &F, &C, g_fake, 1, sides(0), g_fake));
+  }
+  switches_default();
+}
+
 int main(int argc, char **argv) {
   if (argc > 1 && !strcmp(argv[1], "names")) {   // mangled stub names on stdin -> the spelling of the launch lines
     char sym[4096];
@@ -261,6 +471,21 @@ int main(int argc, char **argv) {
     mgxk_snapshot_k1(nullptr, &L);
     call_ret(0);
   }
+  // the walk of the sequential-order red-black sweep, on a device whose placement probe answers yes
+  g_dev = 1; g_probe_equal = true;
+  for (int s = 0; s < (g_refuse || g_fail ? 1 : NRBSW); s++) {
+    const char *sw = set_rb_switch(s);
+    const int depth = g_refuse || g_fail ? 1 : (s == 0 ? 2 : 0);
+    for (const int nz : NZS) {
+      if (s <= 2) scan_calls(nz, sw, depth);
+      if (s == 0 || s == 3) walk_apply_calls(nz, sw, depth);
+      if (s == 0 || s >= 4) window_calls(nz, sw, depth);
+      if (s == 0) apply_calls(nz, sw, depth);
+    }
+  }
+  rbseq_other_calls();
+  for (int s = 0; s < (g_refuse || g_fail ? 1 : 3); s++)
+    for (const int nz : NZS) resrest_calls(nz, s, g_refuse || g_fail || s ? 0 : 1);
   return 0;
 }
 
@@ -273,8 +498,18 @@ void __hipRegisterFunction(void **, const void *, char *, const char *, unsigned
 void __hipRegisterVar(void **, void *, char *, const char *, int, size_t, int, int) {}
 hipError_t __hipPopCallConfiguration(dim3 *, dim3 *, size_t *, hipStream_t *) { return hipSuccess; }
 hipError_t hipLaunchKernel(const void *, dim3, dim3, void **, size_t, hipStream_t) { return hipSuccess; }
-// asked for by wrappers this program does not call (mgxk_relax_ks_persist, mgxk_set_ksp_timeout)
-hipError_t hipGetDevice(int *) { return hipErrorNoDevice; }
+// the placement probe of mgx_rbseq.hip (rbseq_placement_ok): the device number the table steers, host memory for the probe's answer, and a
+// copy that leaves there what the table asks for -- one XCD for the workgroups 0, 8, 16 ..., or one each
+hipError_t hipGetDevice(int *dev) { if (g_dev < 0) return hipErrorNoDevice; *dev = g_dev; return hipSuccess; }
+hipError_t hipMalloc(void **p, size_t n) { *p = malloc(n); return *p ? hipSuccess : hipErrorOutOfMemory; }
+hipError_t hipFree(void *p) { free(p); return hipSuccess; }
+hipError_t hipMemcpyAsync(void *dst, const void *, size_t n, hipMemcpyKind, hipStream_t) {
+  unsigned int *h = (unsigned int *)dst;
+  for (size_t q = 0; q < n / sizeof *h; q++) h[q] = g_probe_equal ? (unsigned int)(q % 8) : (unsigned int)q;
+  return hipSuccess;
+}
+hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
+// asked for by the time-limit setters (mgxk_set_rbseq_timeout is called once: it reports the failure) and by wrappers this program does not call (mgxk_relax_ks_persist)
 hipError_t hipGetDeviceProperties(hipDeviceProp_t *, int) { return hipErrorNoDevice; }
 hipError_t hipMemcpyToSymbol(const void *, const void *, size_t, size_t, hipMemcpyKind) { return hipErrorNoDevice; }
 hipError_t hipOccupancyMaxActiveBlocksPerMultiprocessor(int *, const void *, int, size_t) { return hipErrorNoDevice; }

@@ -1,9 +1,10 @@
-"""Which smoother kernel serves which level, pinned on the host (no GPU): tests/kernel_choice/record_main.cpp calls the kernel wrappers of
-mgx_relax.hip, mgx_relax_coarse.hip, mgx_relax_ks.hip and mgx_relax_tall.hip -- compiled host-only behind record_shim.h, which records a launch
-instead of making it -- over shapes, flags and A/B switches either side of every threshold, three times: plainly, with every
-hipFuncSetAttribute refused, and with an error reported after every launch.  Per group (wrapper x nz x method) the lines of the three passes
-are hashed and compared with tests/golden/kernel_choice.json; every kernel instance the four objects hold must have been launched at least
-once, but for the ones named below with the reason.
+"""Which kernel serves which level, pinned on the host (no GPU): tests/kernel_choice/record_main.cpp calls the kernel wrappers of the smoother
+units (mgx_relax.hip, mgx_relax_coarse.hip, mgx_relax_ks.hip, mgx_relax_tall.hip), of the sequential-order red-black walk (mgx_rbseq.hip) and of
+the fused residual + restriction (mgx_resrest.hip) -- compiled host-only behind record_shim.h, which records a launch instead of making it --
+over shapes, flags and A/B switches either side of every threshold, three times: plainly, with every hipFuncSetAttribute refused, and with
+an error reported after every launch.  Per group (wrapper x nz x method) the lines of the three passes are hashed and compared with
+tests/golden/kernel_choice.json; every kernel instance the objects hold must have been launched at least once, but for the ones named below
+with the reason; and the two functions that predict another wrapper's choice (mgxk_residual_restrict_grid, mgxk_rbseq_wants_d0) agree with it.
 
     python tests/test_kernel_choice_host.py --dump DIR      the full lines (normal.txt, refuse.txt, fail.txt), to diff against another checkout's
     python tests/test_kernel_choice_host.py --write-golden  regenerate the table (only ever from a commit whose choices are the wanted ones)
@@ -23,10 +24,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mgroms_amd", "csrc")
 HERE = os.path.join(ROOT, "tests", "kernel_choice")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "kernel_choice.json")
-UNITS = ["mgx_relax", "mgx_relax_coarse", "mgx_relax_ks", "mgx_relax_tall"]
+UNITS = ["mgx_relax", "mgx_relax_coarse", "mgx_relax_ks", "mgx_relax_tall", "mgx_rbseq", "mgx_resrest"]
 PASSES = ["normal", "refuse", "fail"]
 
-# Kernel instances of the four units that no call of the recorder can launch, one by one with the reason.  (The instances of k_relax_ksp
+# Kernel instances of the units that no call of the recorder can launch, one by one with the reason.  (The instances of k_relax_ksp
 # belong to mgxk_relax_ks_persist, whose workgroups wait for each other: its wrapper is not enumerated.)
 SIG = "(LevView, int, int, int, int, int, Sides, int)"
 UNREACHABLE = {
@@ -34,6 +35,14 @@ UNREACHABLE = {
     "void k_relax_nz<%d, %s, %d, true, %s>%s" % (nz, rs, 1 if nz < 8 else 2, st, SIG): "matrix-free cross terms are chosen from nz = 16 on"
     for nz in (2, 4, 8, 12) for rs in ("false, false", "true, false", "true, true") for st in ("false", "true")
 }
+# rbseq_scan_launch (mgx_rbseq.hip) names an instance per (row of its ladder, ring depth, colour, full half-rows or not); the ladder itself
+# keeps some of them from ever being asked for
+SCAN = "void k_rbseq_scan<%d, %d, %d, %s, %d, false, 0>(LevView, int, int, RbFuse)"
+UNREACHABLE.update({SCAN % (16, d, rbp, "true", 1): "a full half-row of 1024 columns is served by the eight-wave instance" for d in (2, 4) for rbp in (0, 1)})
+UNREACHABLE.update({SCAN % (16, 4, rbp, "false", 1): "the ring depth 2 divides every even nx: depth 4 is never asked of this row" for rbp in (0, 1)})
+UNREACHABLE.update({SCAN % (8, d, rbp, "true", 1): "a full half-row of 512 columns is served by the four-wave instance" for d in (2, 4) for rbp in (0, 1)})
+UNREACHABLE.update({SCAN % (2, d, rbp, "false", nw): "the several-wave instances serve full half-rows of 512 and 1024 columns only"
+                    for d in (16, 4, 2) for rbp in (0, 1) for nw in (4, 8)})
 
 
 def build(outdir, sanitize=None):
@@ -53,7 +62,7 @@ def build(outdir, sanitize=None):
         subprocess.run([hipcc, *common, "-c", "-x", "hip", os.path.join(HERE, "record_main.cpp"), "-o", obj], check=True)
         return obj
 
-    with ThreadPoolExecutor(5) as pool:
+    with ThreadPoolExecutor(len(UNITS) + 1) as pool:
         jobs = [pool.submit(unit, u) for u in UNITS] + [pool.submit(main)]
         objs = [j.result() for j in jobs]
     # the one fat-binary symbol each object refers to: defined as an absolute zero, never read
@@ -130,6 +139,42 @@ def test_every_instance_launched(run):
     assert missing == set(UNREACHABLE), sorted(missing ^ set(UNREACHABLE))
 
 
+def calls(lines):
+    """[(head, [the call's other lines])]"""
+    out = []
+    for line in lines:
+        if line.startswith("call "):
+            out.append((line, []))
+        else:
+            out[-1][1].append(line)
+    return out
+
+
+def test_restrict_grid_is_the_launch(run):
+    """the norm's partials are sized by mgxk_residual_restrict_grid: it is the workgroup count of the launch mgxk_residual_restrict_ex makes"""
+    n = 0
+    for head, body in calls(run[2]["normal"]):
+        said = [int(l.split()[1]) for l in body if l.startswith("  restrict_grid ")]
+        for l in body:
+            m = re.match(r"  launch .* grid=(\d+),(\d+),(\d+) ", l)
+            if m and said:
+                assert said == [int(m.group(1)) * int(m.group(2)) * int(m.group(3))], head
+                n += 1
+    assert n > 1000
+
+
+def test_a_walk_that_reads_d0_has_asked_for_it(run):
+    """where the walk reads d0 from u1 -- k_rbseq_scan with D0IN false, or k_rbseq_walk_apply -- mgxk_rbseq_wants_d0 told the colour pass to write it"""
+    n = 0
+    for head, body in calls(run[2]["normal"]):
+        said = [l for l in body if l.startswith("  wants_d0 ")]
+        reads = [l for l in body if re.match(r"  launch void k_rbseq_scan<\d+, \d+, \d+, \w+, \d+, false, ", l) or l.startswith("  launch void k_rbseq_walk_apply<")]
+        if said and reads:
+            assert said == ["  wants_d0 1"], head
+            n += 1
+    assert n > 1000
+
+
 def test_fall_back_passes_launch_and_report_nothing_served(run):
     """with an error behind every launch, a wrapper that reports what ran reports 0: the caller falls back"""
     lines = run[2]["fail"]
@@ -139,7 +184,8 @@ def test_fall_back_passes_launch_and_report_nothing_served(run):
     for l in lines:
         if l.startswith("call "):
             key = l.split()[1]
-        elif l.startswith("  -> ") and key in ("mgxk_relax_small", "mgxk_relax_wave", "mgxk_relax_wave_fused", "mgxk_relax_ks", "mgxk_relax_ks_pair", "mgxk_relax_tall"):
+        elif l.startswith("  -> ") and key in ("mgxk_relax_small", "mgxk_relax_wave", "mgxk_relax_wave_fused", "mgxk_relax_ks", "mgxk_relax_ks_pair", "mgxk_relax_tall",
+                                                "mgxk_rbseq_walk_apply", "mgxk_rbseq_window", "mgxk_residual_restrict_ex", "mgxk_residual_restrict"):
             heads.setdefault(key, set()).add(l)
     assert after_launch
     assert all(v == {"  -> 0"} for v in heads.values()), heads
