@@ -438,3 +438,116 @@ def test_identity_through_the_model_calls(case):
     print(case.name, f)
     assert f["Ap_over_b"] > 1e-3
     assert f["defect"] <= COUPLING_TOL, (case.name, f)
+
+
+# ---- the smoother identities: every smoother against its level's operator (tests/_smoother_identity.py) ---------------------
+def _smoother_cases():
+    from _smoother_identity import oracle_cases
+    return oracle_cases()
+
+
+@pytest.mark.parametrize("case", _smoother_cases(), ids=[c.name for c in _smoother_cases()])
+def test_smoother_identities_on_the_oracle(case):
+    """The three identities of tests/_smoother_identity.py and their controls on every level of the case, eight seeds: the fixed point
+    (every method), the first colour as a complete solve and the last colour without a residual (four colours, red-black).  This is
+    where the bounds asserted on the GPU were measured (16 x the maxima: _smoother_identity.TOL).  Largest defect per check over every
+    case, level and seed, as printed here:
+
+        check 1  1.21e-13    check 2  9.54e-14    check 3  5.95e-14   (island-32x32x96 and -32x32x128, level 1; every other case
+                                                                       stays below 8.1e-15, 6.8e-15, 3.3e-15)
+        four colours real / simple at most 8.1e-15 / 6.8e-15 / 3.3e-15 without the island; red-black real 1.3e-15 / 1.5e-15 / 1.4e-15
+        without it; red-black simple 1.2e-15 / 1.3e-15 / 6.4e-16; Gauss-Seidel 1.7e-15 (check 1)
+
+    and the smallest control: check 2 with delta on the last colour 1.3e-2 (rndtopo-island-stretched-24x16x12, its 6x4x3 level), the
+    other colours' residual in check 3 0.13 (RB-simple-32x32x24), row k = 1 of red-black 'real' 1.8e-4 (32x512x16, its 4x64x2 level).
+    The first two are asserted at three times their thresholds; the third cannot be (see _smoother_identity.py: on a level four columns wide the
+    inner columns lie at the summit, where the bottom row's diagonals vanish with the slope) and is asserted at the threshold."""
+    import _smoother_identity as S
+    from _problem import oracle_twin
+    o = oracle_twin(S.case_problem(case))
+    be = S.OracleBackend(o)
+    worst, least = {}, {}
+    for lev in range(1, o.nlevs + 1):
+        for seed in S.SEEDS:
+            f = S.run_level(be, lev, case.method, case.cmatrix == "real", seed)
+            S.assert_level(f, (case.name, lev, seed))
+            for k in ("c1", "c2", "c3"):
+                if f[k] is not None:
+                    worst[k] = max(worst.get(k, 0.0), f[k])
+            for k in ("k2", "k3", "row1"):
+                if f[k] is not None:
+                    least[k] = min(least.get(k, np.inf), f[k])
+    print(case.name, "largest", {k: "%.2e" % v for k, v in worst.items()}, "smallest control", {k: "%.2e" % v for k, v in least.items()})
+    # the recorded maxima still describe this build (a factor 2: another libm's last bits in the geometry move them a little)
+    assert worst["c1"] <= S.MEASURED[1] * 2
+    if case.method != "GS":
+        assert worst["c2"] <= S.MEASURED[2] * 2 and worst["c3"] <= S.MEASURED[3] * 2
+        assert least["k2"] >= 3 * S.CONTROL_2 and least["k3"] >= 3 * S.CONTROL_3, least
+    o.close()
+
+
+def test_smoother_identity_bounds_are_sixteen_times_the_measured():
+    import _smoother_identity as S
+    for k in (1, 2, 3):
+        assert abs(S.TOL[k] / S.MEASURED[k] - 16.0) < 0.1
+    assert abs(S.ADJOINT_TOL / 1.4e-17 - 16.0) < 0.5 and S.ADJOINT_MEASURED <= 1.4e-17
+
+
+def test_smoother_identity_sees_a_wrong_term():
+    """the checks can fail: one off-column slot of the oracle's level-2 matrix scaled by 1 + 1e-6 BETWEEN forming b = A p* and relaxing
+    (the smoother then solves another operator than the residual's) moves the fixed point by far more than the bound"""
+    import _smoother_identity as S
+    from _problem import oracle_twin
+    case = next(c for c in S.CASES if c.name == "FC-real-32x32x8")
+    o = oracle_twin(S.case_problem(case))
+
+    class Skewed(S.OracleBackend):
+        def relax(self, lev, n):
+            cA = self.o.field("cA", lev)
+            keep = cA.copy()
+            cA[..., 6] *= 1.0 + 1e-6
+            self.o.relax(lev, n)
+            cA[...] = keep
+
+    assert S.fixed_point(S.OracleBackend(o), 2, 0) <= S.TOL[1]
+    d = S.fixed_point(Skewed(o), 2, 0)
+    print("fixed point with slot 7 of the smoother off by 1e-6: %.2e" % d)
+    assert d > 1000 * S.TOL[1]
+    o.close()
+
+
+def test_nearest_transfers_are_adjoint_on_the_oracle():
+    """<R r, q> = <r, P q> for fine2coarse and the nearest coarse2fine on every level pair with an even fine nz (measured: at most
+    7.3e-18 of ||r|| ||P q||, sums in longdouble), and NOT on the pair 16x16x5 -> 8x8x2 of 64x64x20 (measured 0.16 .. 0.24): the
+    reference leaves the top row of an odd fine level out of both transfers, its own known inconsistency.  The held pairs of option
+    "hold_odd_nz" have no oracle: their reference, the numpy transfers of tests/_hold_ref.py, keeps the identity to 1.4e-17."""
+    import _smoother_identity as S
+    from _hold_ref import mirror, prolong_held, restrict_held
+    from _operator_identity import inner
+    from _problem import oracle_twin, problem
+    worst = 0.0
+    for dims in S.ADJOINT_DIMS + [S.ODD_PAIR_DIMS]:
+        o = oracle_twin(problem(dims, relax_method="FC", interp_type="nearest"))
+        be = S.OracleBackend(o)
+        odd = [lev for lev in range(1, o.nlevs) if lev not in S.even_fine_pairs(be)]
+        assert bool(odd) == (dims == S.ODD_PAIR_DIMS)
+        for lev in range(1, o.nlevs):
+            ds = [S.adjoint_defect(be, lev, seed) for seed in S.SEEDS]
+            print(dims, be.dims(lev), "->", be.dims(lev + 1), "%.2e .. %.2e" % (min(ds), max(ds)))
+            if lev in odd:
+                assert min(ds) > S.ODD_PAIR, (dims, lev, ds)
+            else:
+                assert max(ds) <= S.ADJOINT_TOL, (dims, lev, ds)
+                worst = max(worst, max(ds))
+        o.close()
+    assert worst <= S.ADJOINT_MEASURED * 2
+    held = 0.0
+    for nx, ny, nz in ((4, 4, 5), (8, 8, 5), (16, 16, 5)):
+        for seed in S.SEEDS:
+            rng = np.random.default_rng([5, nx, seed])
+            r = np.zeros((nx + 2, ny + 2, nz)); r[1:-1, 1:-1] = rng.standard_normal((nx, ny, nz))
+            q = np.zeros((nx // 2 + 2, ny // 2 + 2, nz)); q[1:-1, 1:-1] = rng.standard_normal((nx // 2, ny // 2, nz))
+            Rr, Pq = restrict_held(r)[1:-1, 1:-1], prolong_held(mirror(q.copy()), linear=False)[1:-1, 1:-1]
+            held = max(held, abs(inner(Rr, q[1:-1, 1:-1]) - inner(r[1:-1, 1:-1], Pq)) / np.sqrt(inner(r, r) * inner(Pq, Pq)))
+    print("held pairs of tests/_hold_ref.py: %.2e" % held)
+    assert held <= S.ADJOINT_TOL
