@@ -188,6 +188,16 @@ int mgx_level_table_hold(int nx, int ny, int nz, int npx, int npy, int rank, int
  * which every level down to the coarsest has at most 32768 cells and nz <= 32, 0 = no level is that small.  Pure host logic, usable before
  * mgx_init and without a GPU.  Returns 0, or non-zero (mgx_last_error) for sizes that make no hierarchy. */
 int mgx_mixed_tail_first(int nx, int ny, int nz, int *first);
+/* The levels whose fp32 colour passes option "mixed_ring" hands to the software-pipelined kernel, on the one-rank hierarchy of nx x ny x nz:
+ * bit lev-1 of *mask is set where level lev is served -- nz one of 16, 20, 24, 32, 40, 48, 64 and the level not small in the sense of
+ * mgx_mixed_tail_first (more than 32768 cells, or nz > 32).  Pure host logic, usable before mgx_init and without a GPU.  Returns 0, or
+ * non-zero (mgx_last_error) for sizes that make no hierarchy. */
+int mgx_mixed_ring_levels(int nx, int ny, int nz, int *mask);
+/* The launch that option "mixed_ring" = 1 makes for one colour pass of nplanes planes (nx / 2 with four colours, nx red-black) of a level of
+ * nx x ny x nz: out[0] = 1 where the pipelined kernel serves the level (0: the row-by-row kernel, and out[1..3] = 0), out[1] = rows of look-ahead,
+ * out[2] = planes per workgroup, out[3] = 1 for the non-temporal instance, out[4] = workgroups, out[5] = the NZ of the instance.  Pure host
+ * logic (the answer of the function the launch is made by), usable before mgx_init and without a GPU.  Returns 0, or non-zero (mgx_last_error). */
+int mgx_mixed_ring_choice(int nx, int ny, int nz, int nplanes, int *out);
 /* The entry list of one halo exchange of `rank` whose neighbours are neighb[0..7] (S,E,N,W,SW,SE,NE,NW; -1 = none), as the library hands it to
  * the exchange hook: entries[3t..3t+2] = peer, send direction, receive direction of entry t -- sendbuf[t] holds what was packed for the send
  * direction, recvbuf[t] is unpacked into the halo of the receive direction; both are of one kind (S/N edge, E/W edge, corner).  For each peer
@@ -329,6 +339,16 @@ int mgx_set_verbose(int level);
  *   pass and transfer on every level.  The levels above the tail keep their launches.  What changes is the launch count of mgx_counters: a
  *   tail launch counts as one, which is why the option is off until asked for.
  *   Read-only: "mixed_tail_launches" (launches of the tail kernel since mgx_init).
+ * "mixed_ring" (default 0, or 1; any other value is refused; survives mgx_clean / mgx_init; no environment variable; may be set at any time;
+ *   acts on the fp32 cycles of "cycle_precision" = 32 and "krylov_precision" = 32 and on mgx_mixed_op "relax" / "vcycle" only): 1 = the colour
+ *   passes of the levels that are not small (more than 32768 cells, or nz > 32) and have nz = 16, 20, 24, 32, 40, 48 or 64
+ *   (mgx_mixed_ring_levels) run the software-pipelined kernel k_relax32r (mgx_mixed.hip): the rows of the column and of its neighbours are
+ *   requested two or three rows ahead into register rings, each neighbour row is read once, x and gam stay in registers.  The same operator
+ *   and the same stored fp32 slots as the row-by-row kernel, summed in another order: other roundings, within the same 1e-5 of the fp64 pass,
+ *   and the same iteration counts.  One launch per colour pass either way: mgx_counters does not move.  Every other level -- the small
+ *   ones, so that "mixed_tail" = 0 and 1 stay the same bits under this option too, nz = 80, 96, 128 and every nz without an instance --
+ *   keeps the row-by-row kernel.  0 = every launch and every bit as without the option.
+ *   Read-only: "mixed_ring_passes" (colour passes served by the pipelined kernel since mgx_init).
  * "small_any_nz" (default 0, or 1; any other value is refused; survives mgx_clean / mgx_init; no environment variable; may be set at any time:
  *   it steers the dispatch of later relax calls only): 1 = a relax call on a small level with nz = 3, 5, 6 or 7 -- the coarse ends of the
  *   nz = 24, 48, 96 hierarchies, and of nz = 20, 28, 40, 80 under "hold_odd_nz" -- runs in one workgroup and one launch, as the nz = 2 and 4

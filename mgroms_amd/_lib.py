@@ -63,6 +63,8 @@ _SIGS = {
     "mgx_level_table_periodic": (C.c_int, [C.c_int] * 9 + [C.POINTER(C.c_int)]),
     "mgx_level_table_hold": (C.c_int, [C.c_int] * 10 + [C.POINTER(C.c_int)]),
     "mgx_mixed_tail_first": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "mgx_mixed_ring_levels": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "mgx_mixed_ring_choice": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "mgx_exchange_plan": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mgx_get_field": (C.c_int, [C.c_int, C.c_int, _DP]),
     "mgx_set_field": (C.c_int, [C.c_int, C.c_int, _DP]),

@@ -74,6 +74,7 @@ const Opt OPTIONS[] = {
   {"krylov",              &State::krylov,           nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0..8 only
   {"krylov_precision",    &State::krylov_precision, nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 32 / 64 only (no preset: the table's would pass any number by)
   {"mixed_tail",          &State::mixed_tail,       nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0 / 1 only
+  {"mixed_ring",          &State::mixed_ring,       nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0 / 1 only
   {"small_any_nz",        &State::small_any_nz,     nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0 / 1 only
   {"periodic",            &State::periodic,         nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0..3 only, and not while initialised (read by mgx_init)
   {"hold_odd_nz",         &State::hold_odd_nz,      nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0 / 1 only, and not while initialised (read by mgx_init)
@@ -90,6 +91,7 @@ const Opt OPTIONS[] = {
   {"tall_stored_passes", nullptr, CNT(n_tall_stored), nullptr, ENV_NONE, RO, false},
   {"mixed_iterations", nullptr, CNT(n_mixed), nullptr, ENV_NONE, RO, false},
   {"mixed_tail_launches", nullptr, CNT(n_mixed_tail), nullptr, ENV_NONE, RO, false},
+  {"mixed_ring_passes", nullptr, CNT(n_mixed_ring), nullptr, ENV_NONE, RO, false},
   {"small_any_nz_calls", nullptr, CNT(n_small_any), nullptr, ENV_NONE, RO, false},
   {"krylov_restarts", nullptr, CNT(kr_restarts), nullptr, ENV_NONE, RO, false},
   {"krylov_mixed_iterations", nullptr, CNT(n_kr_mixed), nullptr, ENV_NONE, RO, false},
@@ -461,6 +463,30 @@ int mgx_mixed_tail_first(int nx, int ny, int nz, int *first) {
   for (int lev = nl; lev >= 1 && mixed_tail_small(T[lev - 1].nx, T[lev - 1].ny, T[lev - 1].nz); lev--) *first = lev;
   return 0;
 }
+// the levels whose fp32 colour passes option "mixed_ring" hands to k_relax32r on a one-rank hierarchy: bit lev-1 of *mask (choose_relax32)
+int mgx_mixed_ring_levels(int nx, int ny, int nz, int *mask) {
+  if (!mask) return fail("mgx_mixed_ring_levels: mask is NULL");
+  if (nx < 2 || ny < 2 || nz < 2) return fail("mgx_mixed_ring_levels: %d x %d x %d is not a level-1 size", nx, ny, nz);
+  const int nl = find_grid_levels(1, 1, nx, ny, nz);
+  if (nl < 1 || nl > 31) return fail("mgx_mixed_ring_levels: %d x %d x %d has no hierarchy", nx, ny, nz);
+  std::vector<Level> T(nl);
+  T[0].nx = nx; T[0].ny = ny; T[0].nz = nz;
+  rank_level_table(0, T, 1, 1, 8);
+  *mask = 0;
+  for (int lev = 1; lev <= nl; lev++) {
+    int c[6];
+    mgxx_ring_choice(T[lev - 1].nx, T[lev - 1].ny, T[lev - 1].nz, T[lev - 1].nx, c);
+    if (c[0]) *mask |= 1 << (lev - 1);
+  }
+  return 0;
+}
+// the launch choose_relax32 names for a colour pass of nplanes planes of a level of nx x ny x nz under option "mixed_ring" = 1
+int mgx_mixed_ring_choice(int nx, int ny, int nz, int nplanes, int *out) {
+  if (!out) return fail("mgx_mixed_ring_choice: out is NULL");
+  if (nx < 2 || ny < 2 || nz < 2 || nplanes < 1 || nplanes > nx) return fail("mgx_mixed_ring_choice: %d planes of %d x %d x %d is not a colour pass of a level", nplanes, nx, ny, nz);
+  mgxx_ring_choice(nx, ny, nz, nplanes, out);
+  return 0;
+}
 int mgx_exchange_plan(const int *neighb, int rank, int *entries, int *self_mask) {
   if (!neighb || !entries) return -1;
   XEntry pl[8];
@@ -475,6 +501,7 @@ int mgx_set_option(const char *name, int value) {
   if (streq(name, "krylov_precision") && value != 32 && value != 64) return fail("krylov_precision must be 64 (fp64 cycles under the Krylov loop) or 32 (fp32 cycles under it), got %d", value);
   if (streq(name, "krylov") && (value < 0 || value > 8)) return fail("krylov must be 0 (off) or 1..8 (retained direction pairs of the truncated GCR), got %d", value);
   if (streq(name, "mixed_tail") && value != 0 && value != 1) return fail("mixed_tail must be 1 (the small levels of an fp32 cycle in one launch) or 0 (one launch per colour pass and transfer), got %d", value);
+  if (streq(name, "mixed_ring") && value != 0 && value != 1) return fail("mixed_ring must be 1 (the fp32 colour passes of the levels that are not small by the pipelined kernel) or 0 (k_relax32 on every level), got %d", value);
   if (streq(name, "small_any_nz") && value != 0 && value != 1) return fail("small_any_nz must be 1 (closed levels of at most 1024 columns with nz = 3, 5, 6, 7 relax in one launch) or 0 (one launch per colour pass), got %d", value);
   if (streq(name, "periodic")) {
     if (value < 0 || value > 3) return fail("periodic must be 0 (closed), 1 (the i direction, east-west), 2 (the j direction, north-south) or 3 (both), got %d", value);

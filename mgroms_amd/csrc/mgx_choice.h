@@ -29,6 +29,7 @@ enum KernelFamily {
   KF_RB_SCAN, KF_RB_SCAN_FUSED,          // the sequential-order walk over a level, alone or with the correction in its launch: k_rbseq_scan
   KF_RB_WALK_APPLY, KF_RB_WINDOW, KF_RB_APPLY,  // walk + correction of a small level, the windowed walk, the correction alone: k_rbseq_walk_apply, _window, _apply
   KF_RR_FLAT, KF_RR_WALK,                // residual + restriction, a wave per S fine rows or walking up the column: k_residual_restrict_flat, k_residual_restrict
+  KF_RELAX32, KF_RELAX32R,               // the fp32 colour pass, row by row or with its rows in register rings: k_relax32, k_relax32r (mgx_mixed.hip)
 };
 
 struct Choice {
@@ -446,4 +447,33 @@ static inline RrChoice choose_resrest(const LevShape &f, const LevShape &c, int 
   r.zw = r.aw == 1 && r.ar == 1 && !sw.resrest_no_zw && !want_norm && f.zw;
   if (served) r.family = KF_RR_WALK;
   return r;
+}
+
+// ---- mgx_mixed.hip: mgxx_relax_pass, the colour pass of the fp32 cycles ----
+static inline LevShape lev_shape32(const LevView32 *L) { return {L->nx, L->ny, L->nz, false, false, false, false, L->RS}; }
+// the nz of the instances of k_relax32r (option "mixed_ring"); the register instances of k_relax32, every other nz taking its generic form
+#define RING_NZ_LIST 16, 20, 24, 32, 40, 48, 64
+#define RELAX32_NZ_LIST 2, 4, 8, 16, 32, 64
+// look-ahead depth D of k_relax32r: 19 loads per row and at most 63 in flight per wave, so 3 rows is the most a ring can hold ahead; the
+// fp64 answer (ch_colour_depth) from nz = 16 on.  Measured at 512x512x64: D = 2 on every level is a draw with this.
+// Read by the choice and by the launcher that names the instance, as ch_colour_depth is: D is a function of NZ alone.
+constexpr int ch_ring_depth(int nz) { return nz >= 32 ? 3 : 2; }
+// ch_beyond_cache counts the 72 B per cell of the fp64 pass; the fp32 pass moves half of that.  Measured: without the hints the level-1
+// passes of an iteration at 512x512x64 take 0.19-0.21 ms more.
+static inline bool ch_ring_beyond_cache(const LevShape &s) { return (double)s.nx * s.ny * s.nz * 36.0 > 256e6; }
+// ring (option "mixed_ring"): a level that is not small (mixed_tail_small: the small ones are launch-bound, and the tail kernel owes them
+// k_relax32's bits) and whose nz has an instance takes k_relax32r in the geometry of the fp64 register passes; anything else, and every
+// level with ring = 0, k_relax32 with four planes per workgroup.  ret: 1 = the pass counts as a "mixed_ring_passes"
+static inline Choice choose_relax32(const LevShape &s, int nplanes, int real, int snap, int ring, const Switches &sw) {
+  Choice c;
+  if (ring && with_nz<RING_NZ_LIST>(s.nz, [](auto) {}) && !mixed_tail_small(s.nx, s.ny, s.nz)) {
+    c.family = KF_RELAX32R; c.nz = s.nz; c.d = ch_ring_depth(s.nz);
+    ch_pass_geometry(c, s, nplanes, sw);
+    c.stream = ch_ring_beyond_cache(s);
+    c.ret = 1;
+    return c;
+  }
+  c.family = KF_RELAX32; c.nz = with_nz<RELAX32_NZ_LIST>(s.nz, [](auto) {}) ? s.nz : 0;
+  c.grid = ch_chunks(s.ny); c.gy = (nplanes + 3) / 4; c.bx = CH_WAVE; c.by = 4;
+  return c;
 }

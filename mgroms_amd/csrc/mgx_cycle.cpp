@@ -623,18 +623,19 @@ int tail32(int lev, int last, int mode, bool lead, int n) {
 }
 
 // relax(lev, nsweeps) on the fp32 shadow: four colours, or the parallel red-black pass (k = 1 same-colour diagonals from a snapshot
-// taken before each colour: the fp64 pass with rb_seq = 0); a small level in one launch (option "mixed_tail")
+// taken before each colour: the fp64 pass with rb_seq = 0); a small level in one launch (option "mixed_tail"); the colour pass of a level
+// that is not small by the pipelined kernel (option "mixed_ring": choose_relax32, mgx_choice.h), launch for launch
 int relax32(int lev, int nsweeps) {
   LevView32 &v = S.lev[lev - 1].v32;
   if (nsweeps > 0 && S.mixed_tail && S.mx_tail_first && lev >= S.mx_tail_first) return tail32(lev, lev, TAIL_RELAX, false, nsweeps);
   for (int it = 1; it <= nsweeps; it++) {
     if (S.method == M_FC) {
       for (int fc1 = 1; fc1 <= 2; fc1++)
-        for (int fc2 = 1; fc2 <= 2; fc2++) { mgxx_relax_pass(S.stream, &v, fc1, 2, v.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0); S.n_launch++; }
+        for (int fc2 = 1; fc2 <= 2; fc2++) { S.n_mixed_ring += mgxx_relax_pass(S.stream, &v, fc1, 2, v.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0, S.mixed_ring); S.n_launch++; }
     } else {
       for (int rb = 1; rb <= 2; rb++) {
         if (S.real) { mgxx_snapshot(S.stream, &v); S.n_launch++; }
-        mgxx_relax_pass(S.stream, &v, 1, 1, v.nx, -1, rb, S.real, S.real); S.n_launch++;
+        S.n_mixed_ring += mgxx_relax_pass(S.stream, &v, 1, 1, v.nx, -1, rb, S.real, S.real, S.mixed_ring); S.n_launch++;
       }
     }
   }

@@ -175,6 +175,11 @@ struct State {
   int mixed_tail = 0;
   int mx_tail_first = 0;          // first level of that tail, 0 = no level is small (mixed_prepare)
   long long n_mixed_tail = 0;     // read-only option "mixed_tail_launches": launches of the tail kernel since mgx_init
+  // option "mixed_ring" (0 default, 1): the colour passes of the fp32 cycles on the levels that are not small and whose nz has an instance
+  // (choose_relax32, mgx_choice.h; mgx_mixed_ring_levels) run k_relax32r, the software-pipelined pass of mgx_mixed.hip, instead of k_relax32:
+  // one launch per colour pass either way, other roundings within the same bound against the fp64 pass.  0 = every launch and bit as before.
+  int mixed_ring = 0;
+  long long n_mixed_ring = 0;     // read-only option "mixed_ring_passes": colour passes served by k_relax32r since mgx_init
   unsigned long long coef_gen = 0, mx_gen = ~0ULL;
   // option "periodic" (0 default; bit 1 = the i direction, east-west; bit 2 = the j direction, north-south): read by mgx_init, which makes the rank
   // its own neighbour on the periodic sides of every level (rank_level_table).  Such a side is an open side like a rank seam: every kernel

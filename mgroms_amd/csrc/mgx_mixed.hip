@@ -8,7 +8,7 @@
 // relax_col_any), so each one can be checked against its fp64 counterpart through mgx_mixed_op.
 //
 // Thread mapping as in the fp64 kernels: one lane = one (j,i) column, lanes along the unit-stride half-row of the JS layout.
-#include "mgx_device.h"
+#include "mgx_relax_common.h"   // XCD_BLOCK_MAP (and through it mgx_device.h)
 
 // physical-boundary images of an interior value (homogeneous Neumann mirror incl. corners, as mirror_store; all four sides)
 __device__ __forceinline__ void mirror32(const LevView32 &L, float *__restrict__ a, const long long ro, const int j, const int i, const int c, const float v) {
@@ -126,6 +126,116 @@ __global__ __launch_bounds__(256) void k_relax32(LevView32 L, int i0, int istep,
   // RB: j = 1+mod(i+rb,2),ny,2 (mg_relax.f90:174) ; FC: fixed parity (:216-217)
   const int jodd = jodd_fixed >= 0 ? jodd_fixed : (((i + rb) & 1) == 0);
   relax32_col<NZ, REAL, SNAP>(L, i, jh, jodd);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same colour pass, software-pipelined (option "mixed_ring"; the levels choose_relax32 gives it: mgx_choice.h).  relax32_col asks for
+// every coupling and neighbour value of a row where it uses it -- nothing is in flight while a row waits, and each neighbour row is read for
+// the rows k-1, k and k+1.  Here, as in the fp64 stored-coefficient pass (SC_PROLOGUE / SC_ROW, mgx_relax_common.h): the k loop is fully
+// unrolled; the raw rows of the own column (f, a2 .. a8, bet: 9 loads) and of the neighbours (e at j-1, i-1, j+1, i+1; a3 .. a5 at j+1,
+// a6 .. a8 at i+1: 10 loads) are requested D rows ahead into register rings of D + 1 rows; a neighbour row is loaded once, its six
+// products formed once and kept in a three-row window; x(k) and gam(k) stay in registers (2 NZ of them: no LDS), the back substitution
+// issues no load, and e is stored once, the physical-boundary images with it.  The operator of relax32_col term for term, summed in
+// another order: not its bits (-ffp-contract=fast), the same bound against the fp64 pass.  NT: the level does not fit the Infinity Cache
+// between passes -- what the pass reads exactly once (the own rows) and what it writes carry the non-temporal hint.
+// ------------------------------------------------------------------------------------------------
+template <bool NT> __device__ __forceinline__ float ld32(const float *p) { return NT ? __builtin_nontemporal_load(p) : *p; }
+
+template <int NZ, int D, bool REAL, bool SNAP, bool NT>
+__device__ __forceinline__ void relax32r_col(const LevView32 &L, const int i, const int jh, const int jodd) {
+  int c, jm, jp;
+  col_pos(L, jh, jodd, c, jm, jp);
+  const long long RS = L.RS, o = (long long)i * L.plane, om = o - L.plane, op = o + L.plane;
+  float *__restrict__ e = L.e;
+  const float *__restrict__ f = L.f, *__restrict__ a2 = L.cA[1], *__restrict__ a3 = L.cA[2], *__restrict__ a4 = L.cA[3],
+              *__restrict__ a5 = L.cA[4], *__restrict__ a6 = L.cA[5], *__restrict__ a7 = L.cA[6], *__restrict__ a8 = L.cA[7],
+              *__restrict__ bet = L.bet;
+  constexpr int R = D + 1;   // rows of a ring: row q waits in slot q % R, which row q - R left when it was used
+  float n_jm[R], n_im[R], n_jp[R], n_ip[R], n_a3[R], n_a4[R], n_a5[R], n_a6[R], n_a7[R], n_a8[R];
+  float w_f[R], w_a2[R], w_a3[R], w_a4[R], w_a5[R], w_a6[R], w_a7[R], w_a8[R], w_bet[R];
+  float x[NZ], g[NZ];
+#define R32_NB_LOAD(q)                                                                                                     \
+  if ((q) <= NZ) {                                                                                                         \
+    const long long ro_ = (long long)((q)-1) * RS; const int s_ = (q) % R;                                                 \
+    n_jm[s_] = e[o + ro_ + jm]; n_im[s_] = e[om + ro_ + c]; n_jp[s_] = e[o + ro_ + jp]; n_ip[s_] = e[op + ro_ + c];        \
+    n_a3[s_] = a3[o + ro_ + jp]; n_a4[s_] = a4[o + ro_ + jp]; n_a5[s_] = a5[o + ro_ + jp];                                 \
+    n_a6[s_] = a6[op + ro_ + c]; n_a7[s_] = a7[op + ro_ + c]; n_a8[s_] = a8[op + ro_ + c];                                 \
+  }
+#define R32_OW_LOAD(q)                                                                                                     \
+  if ((q) <= NZ) {                                                                                                         \
+    const long long ko_ = o + (long long)((q)-1) * RS + c; const int s_ = (q) % R;                                         \
+    w_f[s_] = ld32<NT>(f + ko_); w_a2[s_] = ld32<NT>(a2 + ko_); w_a3[s_] = ld32<NT>(a3 + ko_); w_a4[s_] = ld32<NT>(a4 + ko_); \
+    w_a5[s_] = ld32<NT>(a5 + ko_); w_a6[s_] = ld32<NT>(a6 + ko_); w_a7[s_] = ld32<NT>(a7 + ko_); w_a8[s_] = ld32<NT>(a8 + ko_); \
+    w_bet[s_] = ld32<NT>(bet + ko_);                                                                                       \
+  }
+// the products of a raw neighbour row, formed when the row enters the window
+#define R32_NB_USE(q, EJM, EIM, M3, M4, M5, N6, N7, N8)                                                                    \
+  { const int s_ = (q) % R; EJM = n_jm[s_]; EIM = n_im[s_];                                                                \
+    M3 = n_a3[s_] * n_jp[s_]; M4 = n_a4[s_] * n_jp[s_]; M5 = n_a5[s_] * n_jp[s_];                                          \
+    N6 = n_a6[s_] * n_ip[s_]; N7 = n_a7[s_] * n_ip[s_]; N8 = n_a8[s_] * n_ip[s_]; }
+  // the k = 1 diagonals (requested first: they depend on nothing); red-black reads the values from the snapshot
+  float d1 = 0.f, d2 = 0.f, d3 = 0.f, d4 = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f, c4 = 0.f;
+  if (REAL) {
+    const float *__restrict__ q1 = SNAP ? L.p1 : e;
+    const long long s = (long long)i * RS, sm = SNAP ? s - RS : om, sp = SNAP ? s + RS : op;
+    d1 = q1[sm + jp]; d2 = q1[sp + jm]; d3 = q1[sm + jm]; d4 = q1[sp + jp];
+    c1 = a5[o + c]; c2 = a5[op + jm]; c3 = a8[o + c]; c4 = a8[op + jp];
+  }
+  // neighbour rows 1 .. 1 + D and own rows 1 .. D
+#pragma unroll
+  for (int q = 1; q <= 1 + D; q++) { R32_NB_LOAD(q) }
+#pragma unroll
+  for (int q = 1; q <= D; q++) { R32_OW_LOAD(q) }
+  // the window: e at j-1 and i-1 of the rows k-1, k, k+1 (_m, _0, _p) and the products a3 e .. a8 e of the j+1 and i+1 neighbours
+  float ejm_m = 0.f, ejm_0, ejm_p = 0.f, eim_m = 0.f, eim_0, eim_p = 0.f;
+  float m3_m = 0.f, m3_0, m3_p = 0.f, m4_0, m4_p = 0.f, m5_p = 0.f, n6_m = 0.f, n6_0, n6_p = 0.f, n7_0, n7_p = 0.f, n8_p = 0.f;
+  R32_NB_USE(1, ejm_0, eim_0, m3_0, m4_0, m5_p, n6_0, n7_0, n8_p)
+  float xv = 0.f, betp = 0.f;
+#pragma unroll
+  for (int k = 1; k <= NZ; k++) {
+    R32_NB_LOAD(k + 1 + D)
+    R32_OW_LOAD(k + D)
+    if (k < NZ) { R32_NB_USE(k + 1, ejm_p, eim_p, m3_p, m4_p, m5_p, n6_p, n7_p, n8_p) }
+    const int s = k % R;
+    // the twelve off-column products of off32, the neighbours' from the window
+    float t = w_a4[s] * ejm_0 + m4_0 + w_a7[s] * eim_0 + n7_0;
+    if (k > 1) t += m3_m + w_a5[s] * ejm_m + n6_m + w_a8[s] * eim_m;
+    if (k < NZ) t += w_a3[s] * ejm_p + m5_p + w_a6[s] * eim_p + n8_p;
+    if (REAL && k == 1) t += c1 * d1 + c2 * d2 + c3 * d3 + c4 * d4;
+    const float rhs = w_f[s] - t, bk = w_bet[s];
+    if (k == 1) xv = rhs * bk;
+    else { const float a = w_a2[s]; g[k - 1] = a * betp; xv = (rhs - a * xv) * bk; }
+    betp = bk;
+    x[k - 1] = xv;
+    ejm_m = ejm_0; ejm_0 = ejm_p; eim_m = eim_0; eim_0 = eim_p;
+    m3_m = m3_0; m3_0 = m3_p; m4_0 = m4_p; n6_m = n6_0; n6_0 = n6_p; n7_0 = n7_p;
+  }
+#undef R32_NB_LOAD
+#undef R32_OW_LOAD
+#undef R32_NB_USE
+#pragma unroll
+  for (int k = NZ - 1; k >= 1; k--) x[k - 1] = x[k - 1] - g[k] * x[k];
+  const int j = jodd ? 2 * jh + 1 : 2 * jh + 2;
+#pragma unroll
+  for (int k = 1; k <= NZ; k++) {
+    const long long ro = (long long)(k - 1) * RS;
+    if (NT) __builtin_nontemporal_store(x[k - 1], e + o + ro + c); else e[o + ro + c] = x[k - 1];
+    mirror32(L, e, ro, j, i, c, x[k - 1]);
+  }
+}
+
+// one wave per 64 columns of a plane, blockDim.y planes per workgroup, blocks dealt to the XCDs in runs of planes (XCD_BLOCK_MAP)
+template <int NZ, int D, bool REAL, bool SNAP, bool NT>
+__global__ __launch_bounds__(128, 1) void k_relax32r(LevView32 L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int gx) {
+  const int npair = (nplanes + blockDim.y - 1) / blockDim.y;
+  int bx, ipr;
+  XCD_BLOCK_MAP(npair, gx, bx, ipr)
+  const int ipl = ipr * blockDim.y + threadIdx.y;
+  const int jh = bx * WAVE + threadIdx.x;
+  if (jh >= (L.ny >> 1) || ipl >= nplanes) return;
+  const int i = i0 + istep * ipl;
+  const int jodd = jodd_fixed >= 0 ? jodd_fixed : (((i + rb) & 1) == 0);
+  relax32r_col<NZ, D, REAL, SNAP, NT>(L, i, jh, jodd);
 }
 
 // snapshot of e(k=1,:,:), halo included, for the red-black pass
@@ -431,12 +541,26 @@ __global__ __launch_bounds__(256) void k_to64(LevView D, LevView32 S, const floa
   }
 }
 
-template <int NZ>
-static void launch_relax32(hipStream_t st, const LevView32 *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap) {
-  const dim3 blk(WAVE, 4), grd = col_grid(L->ny / 2, nplanes);
-  if (real && snap) hipLaunchKernelGGL((k_relax32<NZ, true, true>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb);
-  else if (real) hipLaunchKernelGGL((k_relax32<NZ, true, false>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb);
-  else hipLaunchKernelGGL((k_relax32<NZ, false, false>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb);
+// the instance a Choice of choose_relax32 names (mgx_choice.h), launched
+static void launch_relax32(hipStream_t st, const LevView32 *L, const Choice &c, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap) {
+  const dim3 blk(c.bx, c.by), grd(c.grid, c.gy);
+  if (c.family == KF_RELAX32R) {
+    with_nz<RING_NZ_LIST>(c.nz, [&](auto nz) {
+      with_real_and(real, snap, [&](auto re, auto sn) {
+        with_bool(c.stream, [&](auto nt) {
+          constexpr int NZ = decltype(nz)::value;
+          hipLaunchKernelGGL((k_relax32r<NZ, ch_ring_depth(NZ), decltype(re)::value, decltype(sn)::value, decltype(nt)::value>), grd, blk, 0, st, *L, i0,
+                             istep, nplanes, jodd_fixed, rb, c.gx);
+        });
+      });
+    });
+    return;
+  }
+  with_real_and(real, snap, [&](auto re, auto sn) {
+    constexpr bool RE = decltype(re)::value, SN = decltype(sn)::value;
+    if (!with_nz<RELAX32_NZ_LIST>(c.nz, [&](auto nz) { hipLaunchKernelGGL((k_relax32<decltype(nz)::value, RE, SN>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb); }))
+      hipLaunchKernelGGL((k_relax32<0, RE, SN>), grd, blk, 0, st, *L, i0, istep, nplanes, jodd_fixed, rb);
+  });
 }
 
 template <int NZMAX, int LANES>
@@ -451,17 +575,18 @@ static dim3 whole_grid(int ny, int nx) { return dim3((ny / 2 + 1 + WAVE - 1) / W
 
 extern "C" {
 // one colour pass: planes i0, i0+istep, ... (nplanes of them), j parity jodd_fixed (-1: red-black colour rb); snap: read the k=1
-// diagonals from L->p1
-void mgxx_relax_pass(hipStream_t st, const LevView32 *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap) {
-  switch (L->nz) {
-    case 2: launch_relax32<2>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap); return;
-    case 4: launch_relax32<4>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap); return;
-    case 8: launch_relax32<8>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap); return;
-    case 16: launch_relax32<16>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap); return;
-    case 32: launch_relax32<32>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap); return;
-    case 64: launch_relax32<64>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap); return;
-    default: launch_relax32<0>(st, L, i0, istep, nplanes, jodd_fixed, rb, real, snap); return;
-  }
+// diagonals from L->p1; ring: option "mixed_ring".  Returns 1 where k_relax32r served the pass, 0 where k_relax32 did.
+int mgxx_relax_pass(hipStream_t st, const LevView32 *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, int ring) {
+  const Choice c = choose_relax32(lev_shape32(L), nplanes, real, snap, ring, mgx_switches());
+  launch_relax32(st, L, c, i0, istep, nplanes, jodd_fixed, rb, real, snap);
+  return c.ret;
+}
+// what choose_relax32 answers for a colour pass of nplanes planes on a level of nx x ny x nz with option "mixed_ring" on, no launch: out[0..5] =
+// served by k_relax32r, look-ahead D, planes per workgroup, non-temporal instance, workgroups, instance NZ (mgx_mixed_ring_levels, mgx_mixed_ring_choice)
+void mgxx_ring_choice(int nx, int ny, int nz, int nplanes, int *out) {
+  const LevShape s = {nx, ny, nz, false, false, false, false, 0};
+  const Choice c = choose_relax32(s, nplanes, 0, 0, 1, mgx_switches());
+  out[0] = c.family == KF_RELAX32R; out[1] = c.d; out[2] = (int)c.by; out[3] = c.stream; out[4] = (int)(c.grid * c.gy); out[5] = c.nz;
 }
 void mgxx_snapshot(hipStream_t st, const LevView32 *L) {
   hipLaunchKernelGGL(k_snapshot32, dim3((L->RS + 255) / 256, L->nx + 2), dim3(256), 0, st, *L);

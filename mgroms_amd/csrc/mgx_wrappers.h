@@ -140,7 +140,8 @@ void mgxm_rhs_accum(hipStream_t st, const GeoView *G, double *bm, const double *
 void mgxm_correct_uvw(hipStream_t st, const GeoView *G, const double *pm, const ModelView *M);
 
 // ---- mgx_mixed.hip ----
-void mgxx_relax_pass(hipStream_t st, const LevView32 *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap);
+int mgxx_relax_pass(hipStream_t st, const LevView32 *L, int i0, int istep, int nplanes, int jodd_fixed, int rb, int real, int snap, int ring);
+void mgxx_ring_choice(int nx, int ny, int nz, int nplanes, int *out);
 void mgxx_snapshot(hipStream_t st, const LevView32 *L);
 void mgxx_residual(hipStream_t st, const LevView32 *L, int real);
 void mgxx_resrest(hipStream_t st, const LevView32 *F, const LevView32 *C, int real);

@@ -287,6 +287,23 @@ def mixed_tail_first(nx, ny, nz):
     return first.value
 
 
+def mixed_ring_levels(nx, ny, nz):
+    """the levels of the one-rank hierarchy of nx x ny x nz whose fp32 colour passes option "mixed_ring" hands to the pipelined kernel: bit
+    lev-1 set = level lev served (nz one of 16, 20, 24, 32, 40, 48, 64 and more than 32768 cells, or nz > 32).  Pure host logic
+    (include/mgx.h: mgx_mixed_ring_levels)."""
+    mask = C.c_int()
+    check(lib().mgx_mixed_ring_levels(int(nx), int(ny), int(nz), C.byref(mask)))
+    return mask.value
+
+
+def mixed_ring_choice(nx, ny, nz, nplanes):
+    """the launch option "mixed_ring" = 1 makes for a colour pass of nplanes planes of a level of nx x ny x nz, as a dict: served, depth,
+    planes_per_workgroup, stream (the non-temporal instance), workgroups, instance_nz.  Pure host logic (include/mgx.h: mgx_mixed_ring_choice)."""
+    out = (C.c_int * 6)()
+    check(lib().mgx_mixed_ring_choice(int(nx), int(ny), int(nz), int(nplanes), out))
+    return dict(zip(("served", "depth", "planes_per_workgroup", "stream", "workgroups", "instance_nz"), out))
+
+
 def krylov_op(op, fields, nd=0, slot=None, sin=(), nout=2):
     """one pass of option "krylov" on level 1 (include/mgx.h: mgx_krylov_op).  fields: the pass's level-1 arrays (nx+2, ny+2, nz) in the
     header's order, C-contiguous float64; the ones the pass writes are rewritten in place.  -> (sout[:nout], path), path = the launch taken
