@@ -273,7 +273,7 @@ int mgx_set_verbose(int level);
  *   The fused kernel sums the norm in another order than compute_residual: between 1 and 0 the printed norms and hist agree to
  *   rounding (the tests compare them at 1e-13 relative), not bit for bit.
  * "restrict_chain" (default 1; MGX_NO_RESTRICT_CHAIN): Fcycle's first-leg restrictions below level 1 on closed levels as one launch
- *   (mgx_kernels.hip: k_restrict_chain), 0 = one launch per level; the same bits.
+ *   (mgx_transfer.hip: k_restrict_chain), 0 = one launch per level; the same bits.
  * "rbseq_fuse" (default 1; MGX_NO_RBSEQ_FUSE): with "rb_seq", walk and per-column correction of a colour in ONE launch -- on large levels
  *   the correction chases the walk across the XCDs (mgx_rbseq.hip: k_rbseq_scan, FUSE), on small levels (half-rows of at most 64 columns,
  *   at most 128 planes) every workgroup redoes the walk for its own planes (k_rbseq_walk_apply); 0 = the correction in a launch of its

@@ -4,7 +4,8 @@
 // value: the kernel family, the parameters of its template instance, the launch geometry, and what the wrapper reports when the launch
 // succeeded.  A wrapper is mgx_before_launch(), its choose_*(), and one launcher that maps the Choice to the instance (no condition on the
 // level's shape there).  Nothing here calls HIP, keeps state or reads the environment; tests/test_kernel_choice_host.py pins every answer
-// (DESIGN.md 4.9).
+// (DESIGN.md 4.9).  The choices of the units outside the smoother -- operator, transfers, transport, layout, model runs -- stand in
+// mgx_choice_transfer.h, included at the end.
 #pragma once
 #include <cstddef>
 #include <type_traits>
@@ -477,3 +478,6 @@ static inline Choice choose_relax32(const LevShape &s, int nplanes, int real, in
   c.grid = ch_chunks(s.ny); c.gy = (nplanes + 3) / 4; c.bx = CH_WAVE; c.by = 4;
   return c;
 }
+
+// ---- the units outside the smoother: operator, transfers, transport, layout, model runs ----
+#include "mgx_choice_transfer.h"

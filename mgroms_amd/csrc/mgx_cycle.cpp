@@ -417,8 +417,7 @@ int fcycle(int have_r2) {
       if (ok) {
         // (a held pair -- option "hold_odd_nz" -- is no 8-cell sum: the chain ends above it)
         while (dep < 4 && lev + dep < S.nlevs && !held_pair(S.lev[lev - 1 + dep], S.lev[lev + dep])) { dep++; vs[dep] = &S.lev[lev - 1 + dep].v; }
-        const Level &F = S.lev[lev - 1];
-        if (dep >= 2 && F.nx % (1 << dep) == 0 && F.ny % (1 << dep) == 0 && F.nz % (1 << dep) == 0) {
+        if (mgxk_restrict_chain_served(vs, dep)) {
           const Sides all = {1, 1, 1, 1};
           mgxk_restrict_chain(S.stream, vs, dep, all); S.n_launch++;
           lev += dep - 1;

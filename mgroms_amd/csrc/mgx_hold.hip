@@ -73,17 +73,12 @@ void mgxk_fine2coarse_held(hipStream_t st, const LevView *F, const LevView *C, d
 
 // skip1: the caller guarantees that a four-colour relax of the fine level follows (cycles only; see k_coarse2fine_run, SK)
 void mgxk_coarse2fine_held(hipStream_t st, const LevView *F, const LevView *C, const double *src, int linear, Sides ph, int keep_r, int skip1) {
-  const dim3 grd((C->ny + WAVE - 1) / WAVE, (C->nz + 3) / 4, C->nx), blk(WAVE, 4);
-  const bool sk = skip1 && !keep_r && !(F->nx & 1) && !(F->ny & 1);
-  if (linear) {
-    if (keep_r) hipLaunchKernelGGL((k_coarse2fine_held<true, false, true>), grd, blk, 0, st, *F, *C, src, ph);
-    else if (sk) hipLaunchKernelGGL((k_coarse2fine_held<false, true, true>), grd, blk, 0, st, *F, *C, src, ph);
-    else hipLaunchKernelGGL((k_coarse2fine_held<false, false, true>), grd, blk, 0, st, *F, *C, src, ph);
-  } else {
-    if (keep_r) hipLaunchKernelGGL((k_coarse2fine_held<true, false, false>), grd, blk, 0, st, *F, *C, src, ph);
-    else if (sk) hipLaunchKernelGGL((k_coarse2fine_held<false, true, false>), grd, blk, 0, st, *F, *C, src, ph);
-    else hipLaunchKernelGGL((k_coarse2fine_held<false, false, false>), grd, blk, 0, st, *F, *C, src, ph);
-  }
+  const C2fChoice c = choose_coarse2fine_held(lev_shape(F), lev_shape(C), linear, keep_r, skip1);
+  with_bool(c.run, [&](auto LIN) {
+    with_wr_sk(c.wr, c.sk, [&](auto WR, auto SK) {
+      hipLaunchKernelGGL((k_coarse2fine_held<WR(), SK(), LIN()>), dim3(c.gx, c.gy, c.gz), dim3(WAVE, c.by), 0, st, *F, *C, src, ph);
+    });
+  });
 }
 
 }  // extern "C"

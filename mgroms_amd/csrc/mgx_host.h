@@ -6,7 +6,7 @@
 //   mg_mpi_exchange.f90 (fill_halo_*, global_sum)         -> fill_halo_js(), rl_fill_halo(), global_sum()   (mgx_comm.cpp)
 //   mg_gather.f90 (gather, split)                         -> inside fine2coarse()/coarse2fine()   (mgx_cycle.cpp)
 //   mg_relax.f90 / mg_intergrids.f90 / mg_solvers.f90     -> relax(), residual(), fine2coarse(), ...   (mgx_cycle.cpp)
-// There is no CPU compute path: every operator is a HIP kernel launch (mgx_kernels.hip, mgx_setup.hip).
+// There is no CPU compute path: every operator is a HIP kernel launch (mgx_residual.hip, mgx_transfer.hip, mgx_halo.hip, mgx_setup.hip, ...).
 #pragma once
 #include <hip/hip_runtime.h>
 

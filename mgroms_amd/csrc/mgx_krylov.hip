@@ -1,6 +1,6 @@
 // Kernels of the Krylov-accelerated solve_p (option "krylov" = m, mgx_cycle.cpp: solve_p_krylov) for gfx950 (MI355X): truncated GCR /
 // Orthomin(m) around the F-cycle.  Three launches per iteration on level 1, each followed by a one-launch reduction of its per-workgroup
-// partial sums in index order (the order of k_reduce_partials, mgx_kernels.hip): a solve is reproducible run to run.
+// partial sums in index order (the order of k_reduce_partials, mgx_residual.hip): a solve is reproducible run to run.
 //   1. k_kr_apply[_mf]: q = A z and the inner products (q, q_i) with the retained q_i
 //   2. k_kr_ortho:      q -= sum beta_i q_i, z -= sum beta_i z_i (beta_i = (q, q_i) / (q_i, q_i)), s = (q, q), t = (r, q)
 //   3. k_kr_update:     p += (t / s) z, r -= (t / s) q, ||r||^2
@@ -282,47 +282,46 @@ __global__ __launch_bounds__(256) void k_kr_reduce(const double *__restrict__ pa
 
 extern "C" {
 
-static dim3 kr_stream_grid(const LevView *L) { return dim3((unsigned)((L->plane + KR_CHUNK - 1) / KR_CHUNK), (unsigned)(L->nx + 2)); }
+static dim3 kr_stream_grid(const LevView *L) { const KrChoice c = choose_kr_stream(lev_shape(L)); return dim3(c.gx, c.gy); }
+static_assert(KR_CHUNK == CH_KR_CHUNK, "the grid of passes 2 and 3 is sized by the chunk their kernels walk");
 // doubles the partial-sum buffer of a level needs: KR_MAX values per workgroup of pass 1, two per workgroup of pass 2
 long long mgxq_partials(const LevView *L) {
-  const dim3 g3 = col_grid(L->ny / 2, L->nx, 2), gs = kr_stream_grid(L);
-  const long long a = (long long)KR_MAX * g3.x * g3.y * 2, b = 2LL * gs.x * gs.y;
+  const KrChoice gs = choose_kr_stream(lev_shape(L));
+  const long long a = (long long)KR_MAX * choose_operator(lev_shape(L)).grid, b = 2LL * gs.gx * gs.gy;
   return a > b ? a : b;
 }
 // which launch the wrappers below choose for a level (reported by the test hook mgx_krylov_op): out[0] = pass 1 matrix-free (1) or from the
 // stored slots (0), out[1] = the non-temporal variant of all three passes, out[2] = gx, out[3] = gy of pass 1's block map
 void mgxq_path(const LevView *L, int *out) {
-  const dim3 g3 = col_grid(L->ny / 2, L->nx, 2);
-  out[0] = choose_operator_mf(lev_shape(L)); out[1] = level_streams(L); out[2] = (int)g3.x; out[3] = (int)g3.y;
+  const OpChoice c = choose_operator(lev_shape(L));
+  out[0] = c.mf; out[1] = c.stream; out[2] = c.gx; out[3] = c.gy;
 }
-// q = A z (z = L->p, halos valid), sc[i] = (q, q_i) for the nd retained q_i
-void mgxq_apply(hipStream_t st, const LevView *L, double *qout, const double *const *qi, int nd, double *partial, double *sc, int real) {
+static KrDirs kr_dirs(const double *const *qi, int nd) {
   KrDirs D = {};
   D.n = nd;
   for (int n = 0; n < nd; n++) D.q[n] = qi[n];
-  dim3 blk(WAVE, 4), g3 = col_grid(L->ny / 2, L->nx, 2), grd(g3.x * g3.y * 2);
-  const int gx = g3.x, gy = g3.y, nt = level_streams(L);
-  if (choose_operator_mf(lev_shape(L))) {
-    if (real) hipLaunchKernelGGL((k_kr_apply_mf<true>), grd, blk, 0, st, *L, qout, D, partial, gx, gy, nt);
-    else hipLaunchKernelGGL((k_kr_apply_mf<false>), grd, blk, 0, st, *L, qout, D, partial, gx, gy, nt);
-  } else if (real) hipLaunchKernelGGL((k_kr_apply<true>), grd, blk, 0, st, *L, qout, D, partial, gx, gy, nt);
-  else hipLaunchKernelGGL((k_kr_apply<false>), grd, blk, 0, st, *L, qout, D, partial, gx, gy, nt);
-  if (nd) hipLaunchKernelGGL(k_kr_reduce, dim3(nd), dim3(256), 0, st, partial, (int)grd.x, sc, (const double *)nullptr);
+  return D;
+}
+// q = A z (z = L->p, halos valid), sc[i] = (q, q_i) for the nd retained q_i
+void mgxq_apply(hipStream_t st, const LevView *L, double *qout, const double *const *qi, int nd, double *partial, double *sc, int real) {
+  const KrDirs D = kr_dirs(qi, nd);
+  const OpChoice c = choose_operator(lev_shape(L));
+  op_launch(c, real, [&](auto MF, auto REAL) {
+    if constexpr (MF()) hipLaunchKernelGGL((k_kr_apply_mf<REAL()>), dim3(c.grid), OP_BLOCK, 0, st, *L, qout, D, partial, c.gx, c.gy, c.stream);
+    else hipLaunchKernelGGL((k_kr_apply<REAL()>), dim3(c.grid), OP_BLOCK, 0, st, *L, qout, D, partial, c.gx, c.gy, c.stream);
+  });
+  if (nd) hipLaunchKernelGGL(k_kr_reduce, dim3(nd), dim3(256), 0, st, partial, (int)c.grid, sc, (const double *)nullptr);
 }
 // the same from the cycle's fp32 result: z = (double)e * isg written whole into zout, q = A z, sc[i] = (q, q_i); e = S->e
 void mgxq_apply32(hipStream_t st, const LevView *L, const LevView32 *S, double isg, double *zout, double *qout, const double *const *qi, int nd, double *partial,
                   double *sc, int real) {
-  KrDirs D = {};
-  D.n = nd;
-  for (int n = 0; n < nd; n++) D.q[n] = qi[n];
-  dim3 blk(WAVE, 4), g3 = col_grid(L->ny / 2, L->nx, 2), grd(g3.x * g3.y * 2);
-  const int gx = g3.x, gy = g3.y, nt = level_streams(L);
-  if (choose_operator_mf(lev_shape(L))) {
-    if (real) hipLaunchKernelGGL((k_kr_apply32_mf<true>), grd, blk, 0, st, *L, *S, S->e, isg, zout, qout, D, partial, gx, gy, nt);
-    else hipLaunchKernelGGL((k_kr_apply32_mf<false>), grd, blk, 0, st, *L, *S, S->e, isg, zout, qout, D, partial, gx, gy, nt);
-  } else if (real) hipLaunchKernelGGL((k_kr_apply32<true>), grd, blk, 0, st, *L, *S, S->e, isg, zout, qout, D, partial, gx, gy, nt);
-  else hipLaunchKernelGGL((k_kr_apply32<false>), grd, blk, 0, st, *L, *S, S->e, isg, zout, qout, D, partial, gx, gy, nt);
-  if (nd) hipLaunchKernelGGL(k_kr_reduce, dim3(nd), dim3(256), 0, st, partial, (int)grd.x, sc, (const double *)nullptr);
+  const KrDirs D = kr_dirs(qi, nd);
+  const OpChoice c = choose_operator(lev_shape(L));
+  op_launch(c, real, [&](auto MF, auto REAL) {
+    if constexpr (MF()) hipLaunchKernelGGL((k_kr_apply32_mf<REAL()>), dim3(c.grid), OP_BLOCK, 0, st, *L, *S, S->e, isg, zout, qout, D, partial, c.gx, c.gy, c.stream);
+    else hipLaunchKernelGGL((k_kr_apply32<REAL()>), dim3(c.grid), OP_BLOCK, 0, st, *L, *S, S->e, isg, zout, qout, D, partial, c.gx, c.gy, c.stream);
+  });
+  if (nd) hipLaunchKernelGGL(k_kr_reduce, dim3(nd), dim3(256), 0, st, partial, (int)c.grid, sc, (const double *)nullptr);
 }
 // (z, q) orthogonalised against the nd retained pairs; out[0] = (q, q), out[1] = (r, q)
 void mgxq_ortho(hipStream_t st, const LevView *L, double *z, double *q, const double *r, const double *const *zi, const double *const *qi, const int *slot, int nd,

@@ -4,7 +4,7 @@
 // mgx_internal.h), and adds e / s to p.  Hand-written, fp32, single rank (every side of every level physical).
 //
 // These kernels have no bit-parity duty: they are compiled with -ffp-contract=fast (Makefile) and sum in whatever order is
-// convenient.  They keep the operator of the fp64 kernels term for term (mgx_kernels.hip k_residual, mgx_relax.hip
+// convenient.  They keep the operator of the fp64 kernels term for term (mgx_residual.hip k_residual, mgx_relax.hip
 // relax_col_any), so each one can be checked against its fp64 counterpart through mgx_mixed_op.
 //
 // Thread mapping as in the fp64 kernels: one lane = one (j,i) column, lanes along the unit-stride half-row of the JS layout.
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(256) void k_restrict32(LevView32 F, LevView32 C, co
 
 // ------------------------------------------------------------------------------------------------
 // coarse2fine: fine e += interp(coarse e), mg_intergrids.f90:366-450 (tri-linear, top level x 1/2), :336-363 (nearest), :226.
-// The expressions of k_coarse2fine_run and k_coarse2fine_nearest (mgx_kernels.hip); the interpolated correction is not stored in r.
+// The expressions of k_coarse2fine_run and k_coarse2fine_nearest (mgx_transfer.hip); the interpolated correction is not stored in r.
 // ------------------------------------------------------------------------------------------------
 template <bool LINEAR>
 __device__ __forceinline__ void coarse2fine32_cell(const LevView32 &F, const LevView32 &C, const int j2, const int k2, const int i2) {

@@ -5,8 +5,7 @@
 // of a wave is one contiguous run.  The result b goes to the solver's JS layout through an LDS-tiled transpose, and the
 // pressure comes back the same way for correct_uvw.  Operation order follows the reference line by line
 // (compiled with -ffp-contract=off): results are bit-identical to the CPU oracle.
-#include "mgx_switches.h"
-#include "mgx_internal.h"
+#include "mgx_choice.h"
 
 // The model state u, v, w is double or float (ModelViewT<T>; the float state: DESIGN.md 6.2).  The formulas read it through U, V, Wv, which
 // load one T and widen it to double (exact), so there is one text of every formula for both; correct_uvw stores through SET_U, SET_V,
@@ -304,24 +303,12 @@ void mgxm_ref2model_2d(hipStream_t st, const double *src, double *dst, int nx, i
 void mgxm_js_model(hipStream_t st, const LevView *L, double *js, double *md, int dir) {
   hipLaunchKernelGGL(k_js_model, dim3((L->nx + 2 + 31) / 32, (L->ny + 2 + 31) / 32, L->nz), dim3(32, 8), 0, st, *L, js, md, dir);
 }
-// Rows per block in z.  The divergence pass: eight.  The flux kernels and correct_uvw carry values from row to row (a run re-reads one
-// row of its neighbour run): runs as long as possible while there are >= 16 384 waves to hide the load -> use chain of a row
-// (scripts/probe/ab_model_runs.sh at 512x512x64: runs of 16 rows 0.86 ms for the four kernels, 32 rows 0.91, whole columns 0.91).
-// MGX_MODEL_KR (A/B and test hook) asks for runs of that many rows, and gets them: the eight-row floor is the heuristic's, so that
-// runs of 1..7 rows -- every row, or nearly, a run start that reloads the carried values -- can be forced too.
-static inline dim3 igrid_k(int ni, int nj, int klast, int *KR) { *KR = klast >= 16 ? 8 : klast; return dim3((ni + 63) / 64, (nj + 3) / 4, (klast + *KR - 1) / *KR); }
-static inline dim3 igrid_run(int ni, int nj, int klast, int *KR) {
-  const int krenv = mgx_switches().model_kr;
-  const long long waves = (long long)((ni + 63) / 64) * nj;
-  long long nrun = krenv > 0 ? (klast + krenv - 1) / krenv : (16384 + waves - 1) / waves;
-  if (nrun < 1) nrun = 1;
-  if (krenv <= 0 && nrun > (klast + 7) / 8) nrun = (klast + 7) / 8;  // at least eight rows per run
-  *KR = (int)((klast + nrun - 1) / nrun);
-  return dim3((ni + 63) / 64, (nj + 3) / 4, (klast + *KR - 1) / *KR);
-}
-void mgxm_rhs_uf(hipStream_t st, const GeoView *G, const ModelView *M, double *fx) { int KR; const dim3 g = igrid_run(G->nx + 1, G->ny, G->nz, &KR); LAUNCH_FOR_STATE(k_rhs_uf, g, M, *G, STATE(M), fx, KR); }
-void mgxm_rhs_vf(hipStream_t st, const GeoView *G, const ModelView *M, double *fx) { int KR; const dim3 g = igrid_run(G->nx, G->ny + 1, G->nz, &KR); LAUNCH_FOR_STATE(k_rhs_vf, g, M, *G, STATE(M), fx, KR); }
-void mgxm_rhs_wf(hipStream_t st, const GeoView *G, const ModelView *M, double *fz) { int KR; const dim3 g = igrid_run(G->nx, G->ny, G->nz + 1, &KR); LAUNCH_FOR_STATE(k_rhs_wf, g, M, *G, STATE(M), fz, KR); }
+// rows per block in z: choose_model_k (the divergence pass) and choose_model_run (the kernels that carry values from row to row), mgx_choice_transfer.h
+static inline dim3 igrid(const ModelChoice &c) { return dim3(c.gx, c.gy, c.gz); }
+static inline ModelChoice model_run(int ni, int nj, int klast) { return choose_model_run(ni, nj, klast, mgx_switches()); }
+void mgxm_rhs_uf(hipStream_t st, const GeoView *G, const ModelView *M, double *fx) { const ModelChoice c = model_run(G->nx + 1, G->ny, G->nz); LAUNCH_FOR_STATE(k_rhs_uf, igrid(c), M, *G, STATE(M), fx, c.kr); }
+void mgxm_rhs_vf(hipStream_t st, const GeoView *G, const ModelView *M, double *fx) { const ModelChoice c = model_run(G->nx, G->ny + 1, G->nz); LAUNCH_FOR_STATE(k_rhs_vf, igrid(c), M, *G, STATE(M), fx, c.kr); }
+void mgxm_rhs_wf(hipStream_t st, const GeoView *G, const ModelView *M, double *fz) { const ModelChoice c = model_run(G->nx, G->ny, G->nz + 1); LAUNCH_FOR_STATE(k_rhs_wf, igrid(c), M, *G, STATE(M), fz, c.kr); }
 void mgxm_flux_zero_face(hipStream_t st, const GeoView *G, double *f, int face, int pl) {
   const int n = (face == 0 ? G->ny : G->nx) + 2;
   hipLaunchKernelGGL(k_flux_zero_face, dim3((n + 63) / 64, G->nz), dim3(64), 0, st, *G, f, face, pl);
@@ -331,11 +318,11 @@ void mgxm_flux_face_copy(hipStream_t st, const GeoView *G, double *f, double *bu
   hipLaunchKernelGGL(k_flux_face_copy, dim3((n + 63) / 64, G->nz), dim3(64), 0, st, *G, f, buf, face, pl, unpack);
 }
 void mgxm_rhs_accum(hipStream_t st, const GeoView *G, double *bm, const double *fu, const double *fv, const double *fw) {
-  int KR; const dim3 g = igrid_k(G->nx, G->ny, G->nz, &KR);
-  hipLaunchKernelGGL(k_rhs_accum_m, g, IBLK, 0, st, *G, bm, fu, fv, fw, KR);
+  const ModelChoice c = choose_model_k(G->nx, G->ny, G->nz);
+  hipLaunchKernelGGL(k_rhs_accum_m, igrid(c), IBLK, 0, st, *G, bm, fu, fv, fw, c.kr);
 }
 void mgxm_correct_uvw(hipStream_t st, const GeoView *G, const double *pm, const ModelView *M) {
-  int KR; const dim3 g = igrid_run(G->nx + 2, G->ny + 2, G->nz, &KR);
-  LAUNCH_FOR_STATE(k_correct_uvw_m, g, M, *G, pm, STATE(M), KR);
+  const ModelChoice c = model_run(G->nx + 2, G->ny + 2, G->nz);
+  LAUNCH_FOR_STATE(k_correct_uvw_m, igrid(c), M, *G, pm, STATE(M), c.kr);
 }
 }

@@ -1,5 +1,5 @@
 // The level-1 operator, ONE text per form: the 15-point product of compute_residual (mg_relax.f90:421-515) from the stored slots and with
-// matrix-free cross terms, for the residual kernels (mgx_kernels.hip: k_residual, k_residual_mf) and pass 1 of the Krylov loop
+// matrix-free cross terms, for the residual kernels (mgx_residual.hip: k_residual, k_residual_mf) and pass 1 of the Krylov loop
 // (mgx_krylov.hip: k_kr_apply, k_kr_apply_mf), which is the same operator on b = 0 with the sign turned.  Both have a bit-parity duty that
 // rests on a row being formed from the same terms in the same order: the own-column terms stand here, once, and the twelve off-column
 // terms behind them are ROW_RHS_* of mgx_device.h, the text that the smoothers expand as well.  With them, the block map of
@@ -8,6 +8,12 @@
 // as separate texts (profiles/operator_single_source_isa.json).
 #pragma once
 #include "mgx_device.h"
+
+// The launch of an operator kernel (choose_operator, mgx_choice_transfer.h): f(MF, REAL) names the instance of the caller's pair of kernels
+#define OP_BLOCK dim3(WAVE, 4)
+template <class F> static inline void op_launch(const OpChoice &c, int real, F &&f) {
+  with_bool(c.mf, [&](auto MF) { with_bool(real != 0, [&](auto REAL) { f(MF, REAL); }); });
+}
 
 // XCD-aware block -> (j-chunk bx, plane group by, j parity bz) map of a 1-D grid of gx * gy * 2 blocks: each XCD owns a contiguous range
 // of plane groups, as with XCD_BLOCK_MAP (mgx_relax_common.h, which explains why).  It differs from that map in its unit: the two

@@ -1,7 +1,7 @@
 // Set-up kernels (run once per geometry): coarsening of the 2-D geometry, sigma-coordinate depths,
 // the 8 stored coefficients per cell, the tridiagonal pivots (compute_rhs / correct_uvw live in mgx_model.hip).
 // These work in the reference (Fortran) layout; the coefficients
-// are then repacked into the solver's JS layout (mgx_kernels.hip:k_convert).  One lane = one (j,i) column.
+// are then repacked into the solver's JS layout (mgx_layout.hip:k_convert).  One lane = one (j,i) column.
 // Operation order follows the reference line by line (compiled with -ffp-contract=off).
 #include "mgx_internal.h"
 

@@ -16,12 +16,12 @@ struct Switches {
   // sequential-order red-black (mgx_rbseq.hip)
   bool rbseq_d0_kernel, rbseq_d0_mid, no_rbseq_walk_apply, rbseq_window_no_xmap;
   int rbw_prio;
-  // transfer kernels (mgx_kernels.hip, mgx_resrest.hip)
+  // transfer kernels (mgx_transfer.hip, mgx_resrest.hip)
   int c2f_kc, c2f_nt;
   bool no_resrest, resrest_no_zw;
   long long resrest_min, resrest_flat_max;
   int resrest_flat_s, resrest_ahead;
-  // halo pushes (mgx_kernels.hip) and the model coupling (mgx_model.hip)
+  // halo pushes (mgx_halo.hip) and the model coupling (mgx_model.hip)
   int p2p_maxblk, p2p_ipt, model_kr;
 };
 

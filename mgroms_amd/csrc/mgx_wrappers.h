@@ -80,16 +80,20 @@ int mgxk_residual_restrict_ex(hipStream_t st, const LevView *F, const LevView *C
                               double *dup);
 int mgxk_residual_restrict(hipStream_t st, const LevView *F, const LevView *C, double *dst, int real, Sides ph, double *zero);
 
-// ---- mgx_kernels.hip ----
+// ---- mgx_residual.hip ----
 int mgxk_residual_nblocks(const LevView *L);
 void mgxk_residual(hipStream_t st, const LevView *L, double *partial, double *out, int real, int want_norm, Sides ph);
 void mgxk_reduce(hipStream_t st, const double *partial, int n, double *out);
 void mgxk_sumsq(hipStream_t st, const LevView *L, const double *a, double *partial, double *out);
 void mgxk_dot(hipStream_t st, const LevView *L, const double *a, const double *b, double *partial, double *out);
+
+// ---- mgx_transfer.hip ----
+int mgxk_restrict_chain_served(const LevView *const *levels, int dep);
 void mgxk_restrict_chain(hipStream_t st, const LevView *const *levels, int dep, Sides ph);
 void mgxk_fine2coarse(hipStream_t st, const LevView *F, const LevView *C, double *dst, Sides ph, double *dup, double *zero);
 void mgxk_coarse2fine(hipStream_t st, const LevView *F, const LevView *C, const double *src, int linear, Sides ph, int keep_r, int skip1);
-void mgxk_divc_selftest(hipStream_t st, const double *a, const double *b, int n, unsigned long long *bad);
+
+// ---- mgx_halo.hip ----
 void mgxk_halo_phys(hipStream_t st, const LevView *L, double *a, Sides ph);
 void mgxk_halo_wrap(hipStream_t st, const LevView *L, double *a, int im, int jm);
 void mgxk_halo_mixed_corners(hipStream_t st, const LevView *L, double *a, int mSW, int mSE, int mNE, int mNW);
@@ -99,9 +103,6 @@ void mgxk_halo_p2p(hipStream_t st, const LevView *L, double *a, double *const *r
                    int drop);
 int mgxk_set_p2p_timeout(double ms);
 void mgxk_err_to_double(hipStream_t st, const int *err, int extra, double *out);
-void mgxk_convert(hipStream_t st, const LevView *L, double *js, double *ref, int nslot, int slot, int dir);
-void mgxk_convert8(hipStream_t st, const LevView *L, const double *ref);
-void mgxk_convert2(hipStream_t st, const LevView *L, double *out0, double *out1, const double *ref);
 void mgxk_gather_place(hipStream_t st, const LevView *C, double *dstjs, const double *blk, int nxc, int nyc, int l, int m);
 void mgxk_block_to_ref(hipStream_t st, const LevView *Cs, const double *js, double *blk);
 void mgxk_gather_push(hipStream_t st, const LevView *Cs, const double *js, double *const *dst, unsigned long long *const *flags, int ng, int me,
@@ -109,6 +110,12 @@ void mgxk_gather_push(hipStream_t st, const LevView *Cs, const double *js, doubl
 void mgxk_gather_place_wait(hipStream_t st, const LevView *C, double *dstjs, const double *blk, int nxc, int nyc, int l, int m,
                             unsigned long long *flag, unsigned long long seq, int *err);
 void mgxk_split(hipStream_t st, const LevView *C, const LevView *Cs, const double *pc, double *dst, int l, int m);
+
+// ---- mgx_layout.hip ----
+void mgxk_divc_selftest(hipStream_t st, const double *a, const double *b, int n, unsigned long long *bad);
+void mgxk_convert(hipStream_t st, const LevView *L, double *js, double *ref, int nslot, int slot, int dir);
+void mgxk_convert8(hipStream_t st, const LevView *L, const double *ref);
+void mgxk_convert2(hipStream_t st, const LevView *L, double *out0, double *out1, const double *ref);
 
 // ---- mgx_hold.hip ----
 void mgxk_fine2coarse_held(hipStream_t st, const LevView *F, const LevView *C, double *dst, Sides ph, double *dup, double *zero);

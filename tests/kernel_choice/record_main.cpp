@@ -1,17 +1,18 @@
 // Which kernel serves which level: a stand-alone host program (no GPU, no HIP runtime) that calls the extern "C" wrappers of
-// mgx_wrappers.h -- the smoother's, the sequential-order red-black walk's, the fused residual + restriction's -- over a table of shapes,
+// mgx_wrappers.h -- the smoother's, the sequential-order red-black walk's, the fused residual + restriction's, and those of the operator,
+// the transfers, the halo and gather transport, the layout conversions, the Krylov passes and the model coupling -- over a table of shapes,
 // flags and A/B switches and prints, per call, one line per kernel launch (the demangled template instance, grid, block, dynamic LDS
-// bytes, scalar arguments) and the wrapper's return value.
+// bytes, scalar arguments, by-value structs by their members) and the wrapper's return value.
 //
-// Built from mgx_relax.hip, mgx_relax_coarse.hip, mgx_relax_ks.hip, mgx_relax_tall.hip, mgx_rbseq.hip and mgx_resrest.hip compiled
+// Built from the units that tests/test_kernel_choice_host.py lists (UNITS), each compiled
 // host-only behind record_shim.h, which sends their launches here; the stand-ins at the end of this file replace what the units and the
 // compiler's registration code ask of the HIP runtime.
 // tests/test_kernel_choice_host.py builds and runs it and compares digests with tests/golden/kernel_choice.json.
 //
-//   record_main [refuse|fail|names]     refuse: every hipFuncSetAttribute is refused; fail: hipGetLastError reports an error after every launch
+//   record_main [refuse|fail|names|p2p]     refuse: every hipFuncSetAttribute is refused; fail: hipGetLastError reports an error after every launch;
+//                                           p2p: no wrapper is called -- the sweep of the peer-to-peer block plan (p2p_plan_sweep below)
 #include <hip/hip_runtime.h>
-#include "mgx_internal.h"
-#include "mgx_switches.h"
+#include "mgx_choice.h"
 #include <cxxabi.h>
 #include <dlfcn.h>
 #include <cstdarg>
@@ -64,6 +65,15 @@ void rec_fuse(const Sides &ph, const int (&v)[6], long long min_cells, const voi
   snprintf(b, sizeof b, "F(KR=%d,nt=%d,nchunk=%d,nkz=%d,nworkers=%d,stall=%d,min=%lld,flag=%d,seq=%u,err=%d) ", v[0], v[1], v[2], v[3], v[4], v[5], min_cells, flag != nullptr, seq, err != nullptr);
   g_line += b;
 }
+void rec_text(const char *fmt, ...) {
+  char b[256];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(b, sizeof b, fmt, ap);
+  va_end(ap);
+  g_line += b;
+}
+void rec_arg(const GeoView &G) { rec_text("G(%d,%d,%d,bmask=%d) ", G.nx, G.ny, G.nz, G.bmask); }
 void rec_end() { puts(g_line.c_str()); }
 hipError_t rec_last_error() { const hipError_t e = g_err; g_err = hipSuccess; return e; }
 hipError_t rec_set_attribute(const void *kernel, hipFuncAttribute attr, int value) {
@@ -137,13 +147,15 @@ static const Shape SMALL[] = {{8, 8}, {8, 10}, {8, 16}, {8, 18}, {10, 12}, {12, 
 static const Shape PASS[] = {{16, 16}, {15, 17}, {32, 32}, {64, 64}, {128, 128}, {126, 130}, {130, 126}, {256, 256}, {258, 256}, {254, 258}, {512, 256}, {516, 256}, {512, 512}, {1022, 256}, {1024, 256},
                              {1026, 256}, {512, 1024}, {510, 1026}, {1024, 1024}, {2048, 256}, {2046, 256}, {4096, 256}, {4094, 256}, {4098, 256}};
 
+static bool g_group_per_wrapper = false;
 static void call_head(const char *w, int nz, int method, const char *fmt, ...) {
   char b[256];
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(b, sizeof b, fmt, ap);
   va_end(ap);
-  if (method >= 0) printf("call %s nz=%d method=%d | %s\n", w, nz, method, b);
+  if (g_group_per_wrapper) printf("call %s nz=* method=- | nz=%d %s\n", w, nz, b);   // one digest per wrapper: the units that only choose a launch
+  else if (method >= 0) printf("call %s nz=%d method=%d | %s\n", w, nz, method, b);
   else printf("call %s nz=%d method=- | %s\n", w, nz, b);
   g_err = hipSuccess;
 }
@@ -442,7 +454,298 @@ static void resrest_calls(int nz, int isw, int depth) {
   switches_default();
 }
 
+// ---- mgx_residual.hip, mgx_krylov.hip: the operator of a level and the Krylov passes ----
+static LevView32 level32(int nx, int ny, int nz) {
+  LevView32 v;
+  memset(&v, 0, sizeof v);
+  v.nx = nx; v.ny = ny; v.nz = nz;
+  v.EO = 31; v.HO = (32 + ny / 2 + 31) / 32 * 32; v.RS = (v.HO + ny / 2 + 1 + 31) / 32 * 32;
+  v.plane = (long long)nz * v.RS;
+  v.e = v.f = v.r = (float *)g_fake;
+  return v;
+}
+// stored slots or matrix-free either side of nz = 3; cells either side of the Infinity Cache (ch_beyond_cache); odd sizes; more than one block row
+static const Shape OPS[] = {{16, 16}, {15, 18}, {130, 126}, {256, 256}, {236, 256}, {238, 256}, {512, 512}, {1024, 1024}};
+static void operator_calls(int nz) {
+  for (const Shape &s : OPS)
+    for (int zy = 0; zy <= 1; zy++) {
+      const LevView L = level(s.nx, s.ny, nz, zy, false);
+      const LevView32 S = level32(s.nx, s.ny, nz);
+      const double *qi[8] = {g_fake, g_fake, g_fake, g_fake, g_fake, g_fake, g_fake, g_fake};
+      const int slot[8] = {3, 1, 4, 1, 5, 9, 2, 6};
+      int path[4];
+      call_head("mgxk_residual_nblocks", nz, -1, "%dx%d zy=%d", s.nx, s.ny, zy);
+      call_ret(mgxk_residual_nblocks(&L));
+      call_head("mgxq_partials", nz, -1, "%dx%d zy=%d", s.nx, s.ny, zy);
+      call_ret((int)mgxq_partials(&L));
+      call_head("mgxq_path", nz, -1, "%dx%d zy=%d", s.nx, s.ny, zy);
+      mgxq_path(&L, path);
+      printf("  path %d %d %d %d\n", path[0], path[1], path[2], path[3]);
+      call_ret(0);
+      for (int real = 0; real <= 1; real++) {
+        for (int norm = 0; norm <= 1; norm++)
+          for (int sd = 0; sd <= 1; sd++) {
+            call_head("mgxk_residual", nz, -1, "%dx%d zy=%d real=%d norm=%d sides=%d", s.nx, s.ny, zy, real, norm, sd);
+            mgxk_residual(nullptr, &L, g_fake, g_fake, real, norm, sides(sd)); call_ret(0);
+          }
+        for (const int nd : {0, 1, 8}) {
+          call_head("mgxq_apply", nz, -1, "%dx%d zy=%d real=%d nd=%d", s.nx, s.ny, zy, real, nd);
+          mgxq_apply(nullptr, &L, g_fake, qi, nd, g_fake, g_fake, real); call_ret(0);
+          call_head("mgxq_apply32", nz, -1, "%dx%d zy=%d real=%d nd=%d", s.nx, s.ny, zy, real, nd);
+          mgxq_apply32(nullptr, &L, &S, 0.5, g_fake, g_fake, qi, nd, g_fake, g_fake, real); call_ret(0);
+        }
+      }
+      if (zy) continue;
+      call_head("mgxk_sumsq", nz, -1, "%dx%d", s.nx, s.ny); mgxk_sumsq(nullptr, &L, g_fake, g_fake, g_fake); call_ret(0);
+      call_head("mgxk_dot", nz, -1, "%dx%d", s.nx, s.ny); mgxk_dot(nullptr, &L, g_fake, g_fake, g_fake, g_fake); call_ret(0);
+      for (const int nd : {0, 3}) {
+        call_head("mgxq_ortho", nz, -1, "%dx%d nd=%d", s.nx, s.ny, nd);
+        mgxq_ortho(nullptr, &L, g_fake, g_fake, g_fake, qi, qi, slot, nd, g_fake, g_fake, g_fake, g_fake); call_ret(0);
+      }
+      call_head("mgxq_update", nz, -1, "%dx%d", s.nx, s.ny); mgxq_update(nullptr, &L, g_fake, g_fake, g_fake, g_fake, g_fake, g_fake, g_fake, g_fake); call_ret(0);
+      call_head("mgxq_update32", nz, -1, "%dx%d", s.nx, s.ny); mgxq_update32(nullptr, &L, &S, g_fake, g_fake, g_fake, g_fake, 2.0, g_fake, g_fake, g_fake, g_fake); call_ret(0);
+    }
+  call_head("mgxk_reduce", nz, -1, "n=%d", 100 * nz); mgxk_reduce(nullptr, g_fake, 100 * nz, g_fake); call_ret(0);
+}
+
+// ---- mgx_transfer.hip, mgx_hold.hip ----
+// The coarse level.  Restriction: its waves either side of 8192 (508 / 512 x 1024), runs of every length down to one level and of the whole
+// column.  Prolongation: waves x runs either side of 2048 with runs of 16, 8, 4, 2, 1 levels (at nz = 32: 256, 254, 128, 96, 64 planes) and
+// of more levels than the column has (the small nz); rows of more and of less than a wave; odd sizes
+static const Shape TR[] = {{8, 8}, {15, 17}, {64, 64}, {96, 128}, {128, 128}, {254, 256}, {256, 256}, {512, 512}, {508, 1024}, {512, 1024}, {1024, 1024}};
+static const char *const TR_SWITCHES[] = {"default", "c2f_kc4", "c2f_kc32", "c2f_nt0", "c2f_nt1"};
+constexpr int NTRSW = sizeof TR_SWITCHES / sizeof *TR_SWITCHES;
+static const char *set_tr_switch(int s) {
+  switches_default();
+  if (s == 1) g_sw.c2f_kc = 4;
+  if (s == 2) g_sw.c2f_kc = 32;
+  if (s == 3) g_sw.c2f_nt = 0;
+  if (s == 4) g_sw.c2f_nt = 1;
+  return TR_SWITCHES[s];
+}
+// nz: the fine level's; depth 0 (a switch on): the prolongation alone, fine level of twice the size
+static void transfer_calls(int nz, const char *sw, int depth) {
+  const int nzc = nz / 2;
+  for (const Shape &c : TR) {
+    const LevView C = level(c.nx, c.ny, nzc, true, false);
+    for (int odd = 0; odd < (depth ? 3 : 1); odd++) {   // the fine level: twice the coarse one, one plane more, one column more (SK: even nx, ny only)
+      const LevView F = level(2 * c.nx + (odd == 1), 2 * c.ny + (odd == 2), nz, true, false);
+      for (int linear = 0; linear <= 1; linear++)
+        for (int keep_r = 0; keep_r <= 1; keep_r++)
+          for (int skip1 = 0; skip1 <= 1; skip1++) {
+            call_head("mgxk_coarse2fine", nz, -1, "%dx%dx%d -> %dx%d linear=%d keep_r=%d skip1=%d sw=%s", c.nx, c.ny, nzc, F.nx, F.ny, linear, keep_r, skip1, sw);
+            mgxk_coarse2fine(nullptr, &F, &C, g_fake, linear, sides(0), keep_r, skip1); call_ret(0);
+            if (!depth) continue;
+            const LevView Ch = level(c.nx, c.ny, nz, true, false);   // a held pair: the same nz
+            call_head("mgxk_coarse2fine_held", nz, -1, "%dx%d -> %dx%d linear=%d keep_r=%d skip1=%d", c.nx, c.ny, F.nx, F.ny, linear, keep_r, skip1);
+            mgxk_coarse2fine_held(nullptr, &F, &Ch, g_fake, linear, sides(0), keep_r, skip1); call_ret(0);
+          }
+      if (!depth || odd) continue;
+      for (int extra = 0; extra <= 1; extra++) {   // r_c = b_c and p_c = 0 written too, or not
+        call_head("mgxk_fine2coarse", nz, -1, "%dx%d -> %dx%dx%d dup=%d zero=%d", F.nx, F.ny, c.nx, c.ny, nzc, extra, extra);
+        mgxk_fine2coarse(nullptr, &F, &C, g_fake, sides(extra), extra ? g_fake : nullptr, extra ? g_fake : nullptr); call_ret(0);
+        const LevView Ch = level(c.nx, c.ny, nz, true, false);
+        call_head("mgxk_fine2coarse_held", nz, -1, "%dx%d -> %dx%d dup=%d zero=%d", F.nx, F.ny, c.nx, c.ny, extra, extra);
+        mgxk_fine2coarse_held(nullptr, &F, &Ch, g_fake, sides(extra), extra ? g_fake : nullptr, extra ? g_fake : nullptr); call_ret(0);
+      }
+    }
+  }
+}
+// chains of 1 to 4 restrictions from a finest level whose nx, ny, nz are multiples of 2^dep, or one of them is not
+static void chain_calls() {
+  static const int FINE[][3] = {{16, 16, 16}, {32, 48, 16}, {256, 256, 32}, {24, 16, 16}, {16, 40, 16}, {16, 16, 8}, {16, 16, 12}, {18, 16, 16}, {16, 16, 2}, {30, 34, 6}};
+  for (const auto &f : FINE)
+    for (int dep = 1; dep <= 4; dep++) {
+      LevView v[5];
+      const LevView *vs[5];
+      for (int q = 0; q < 5; q++) {
+        const int dv = 1 << (q <= dep ? q : dep);
+        v[q] = level(f[0] / dv > 0 ? f[0] / dv : 1, f[1] / dv > 0 ? f[1] / dv : 1, f[2] / dv > 0 ? f[2] / dv : 1, true, false);
+        vs[q] = &v[q];
+      }
+      call_head("mgxk_restrict_chain", f[2], -1, "%dx%d dep=%d", f[0], f[1], dep);
+      const int served = mgxk_restrict_chain_served(vs, dep);
+      mgxk_restrict_chain(nullptr, vs, dep, sides(0));   // (the wrapper trusts its caller)
+      call_ret(served);
+    }
+}
+
+// ---- mgx_halo.hip ----
+static const int PRESENT[][8] = {
+    {0, 0, 0, 0, 0, 0, 0, 0},                                                   // no neighbour
+    {1, 0, 0, 0, 0, 0, 0, 0}, {0, 1, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 1, 0},   // one peer: an edge along i, along j, a corner
+    {1, 1, 1, 1, 0, 0, 0, 0}, {1, 1, 0, 0, 0, 1, 0, 0},                          // four peers: the edges; two edges and their corner among closed sides
+    {1, 1, 1, 1, 1, 1, 1, 1},                                                   // eight peers
+    {2, 1, 2, 1, 1, 1, 1, 1}, {1, 2, 1, 2, 1, 1, 1, 1},                          // the wrap local in one direction, peers in the other (their corners: peers)
+    {3, 1, 3, 1, 0, 0, 0, 0}, {1, 3, 0, 1, 0, 3, 0, 0},                          // images of closed sides still due beside peers
+    {2, 2, 2, 2, 2, 2, 2, 2}, {2, 0, 2, 0, 0, 0, 0, 0},                          // the rank itself everywhere: no peer
+};
+static const char *const P2P_SWITCHES[] = {"default", "p2p_maxblk1", "p2p_ipt3", "p2p_maxblk1_ipt3"};
+static const char *set_p2p_switch(int s) {
+  switches_default();
+  if (s & 1) g_sw.p2p_maxblk = 1;
+  if (s & 2) g_sw.p2p_ipt = 3;
+  return P2P_SWITCHES[s];
+}
+// edges of one block, of several, of more items than 128 blocks take one each (ipt > 1), the sizes whose plan has more than 128 pushing blocks
+static const Shape HALO[] = {{2, 2}, {16, 16}, {15, 100}, {128, 128}, {512, 512}, {1000, 1024}, {1738, 2048}, {4096, 4096}};
+static void halo_calls(int nz, const char *sw, int depth) {
+  double *bufs[8];
+  unsigned long long *flags[8];
+  for (int d = 0; d < 8; d++) { bufs[d] = g_fake; flags[d] = (unsigned long long *)g_fake; }
+  int err = 0, np = -1;
+  for (const Shape &s : HALO) {
+    const LevView L = level(s.nx, s.ny, nz, true, false);
+    for (const auto &present : PRESENT) {
+      np++;
+      char pat[9];
+      for (int d = 0; d < 8; d++) pat[d] = '0' + present[d];
+      pat[8] = 0;
+      const int mixed[4] = {np % 3, (np + 1) % 3, (np + 2) % 3, np % 2};
+      for (int drop = 0; drop <= (depth == 2 ? 1 : 0); drop++) {
+        call_head("mgxk_halo_p2p", nz, -1, "%dx%d present=%s drop=%d sw=%s", s.nx, s.ny, pat, drop, sw);
+        mgxk_halo_p2p(nullptr, &L, g_fake, bufs, bufs, flags, flags, present, 7 + np, (unsigned int *)g_fake, &err, mixed, drop); call_ret(0);
+      }
+      if (!depth) continue;
+      for (int unpack = 0; unpack <= 1; unpack++) {
+        call_head("mgxk_halo_pack_all", nz, -1, "%dx%d present=%s unpack=%d", s.nx, s.ny, pat, unpack);
+        mgxk_halo_pack_all(nullptr, &L, g_fake, bufs, present, unpack); call_ret(0);
+      }
+    }
+    if (!depth) continue;
+    for (int im = 0; im <= 2; im++)
+      for (int jm = 0; jm <= 2; jm++) {
+        call_head("mgxk_halo_wrap", nz, -1, "%dx%d im=%d jm=%d", s.nx, s.ny, im, jm);
+        mgxk_halo_wrap(nullptr, &L, g_fake, im, jm); call_ret(0);
+      }
+    call_head("mgxk_halo_phys", nz, -1, "%dx%d", s.nx, s.ny); mgxk_halo_phys(nullptr, &L, g_fake, sides(1)); call_ret(0);
+    call_head("mgxk_halo_mixed_corners", nz, -1, "%dx%d", s.nx, s.ny); mgxk_halo_mixed_corners(nullptr, &L, g_fake, 1, 2, 0, 1); call_ret(0);
+  }
+}
+// the gather and the split of a coarse level, the layout conversions (the blocks of a push either side of 256, of a waiting placement either side
+// of 128; the conversion tile at nz = 64, 128, 160 and below) and the two one-thread launches
+static void gather_layout_calls(int nz) {
+  static const Shape SH[] = {{4, 4}, {15, 17}, {30, 32}, {32, 32}, {62, 64}, {64, 64}, {254, 256}, {512, 512}};
+  double *dst[4] = {g_fake, g_fake, g_fake, g_fake};
+  unsigned long long *flags[4];
+  for (auto &f : flags) f = (unsigned long long *)g_fake;
+  int err = 0;
+  for (const Shape &s : SH) {
+    const LevView Cs = level(s.nx, s.ny, nz, true, false), C = level(2 * s.nx, 2 * s.ny, nz, true, false);
+    for (const int ng : {2, 4}) {
+      call_head("mgxk_gather_push", nz, -1, "%dx%d ng=%d", s.nx, s.ny, ng);
+      mgxk_gather_push(nullptr, &Cs, g_fake, dst, flags, ng, 1, 5, (unsigned int *)g_fake, &err); call_ret(0);
+    }
+    for (int wait = 0; wait <= 1; wait++) {
+      call_head("mgxk_gather_place_wait", nz, -1, "%dx%d wait=%d", s.nx, s.ny, wait);
+      mgxk_gather_place_wait(nullptr, &C, g_fake, g_fake, s.nx, s.ny, 1, 0, wait ? flags[0] : nullptr, 5, &err); call_ret(0);
+    }
+    call_head("mgxk_gather_place", nz, -1, "%dx%d", s.nx, s.ny); mgxk_gather_place(nullptr, &C, g_fake, g_fake, s.nx, s.ny, 0, 1); call_ret(0);
+    call_head("mgxk_block_to_ref", nz, -1, "%dx%d", s.nx, s.ny); mgxk_block_to_ref(nullptr, &Cs, g_fake, g_fake); call_ret(0);
+    call_head("mgxk_split", nz, -1, "%dx%d", s.nx, s.ny); mgxk_split(nullptr, &C, &Cs, g_fake, g_fake, 1, 1); call_ret(0);
+    for (int dir = 0; dir <= 1; dir++) {
+      call_head("mgxk_convert", nz, -1, "%dx%d dir=%d", s.nx, s.ny, dir); mgxk_convert(nullptr, &Cs, g_fake, g_fake, 8, 3, dir); call_ret(0);
+    }
+    call_head("mgxk_convert8", nz, -1, "%dx%d", s.nx, s.ny); mgxk_convert8(nullptr, &Cs, g_fake); call_ret(0);
+    call_head("mgxk_convert2", nz, -1, "%dx%d", s.nx, s.ny); mgxk_convert2(nullptr, &Cs, g_fake, g_fake, g_fake); call_ret(0);
+  }
+}
+static void one_thread_calls() {
+  int err = 0;
+  call_head("mgxk_set_p2p_timeout", 0, -1, "ms=100"); call_ret(mgxk_set_p2p_timeout(100.0));
+  for (int extra = 0; extra <= 1; extra++) { call_head("mgxk_err_to_double", 0, -1, "extra=%d", extra); mgxk_err_to_double(nullptr, &err, extra, g_fake); call_ret(0); }
+  for (const int n : {1, 256, 257}) { call_head("mgxk_divc_selftest", 0, -1, "n=%d", n); mgxk_divc_selftest(nullptr, g_fake, g_fake, n, (unsigned long long *)g_fake); call_ret(0); }
+}
+
+// ---- mgx_model.hip ----
+static const char *const MODEL_SWITCHES[] = {"default", "model_kr1", "model_kr7", "model_kr8"};
+static const int MODEL_KR[] = {0, 1, 7, 8};
+// rows: the eight-row floor, the run of the divergence pass either side of 16, columns longer than a run target; waves either side of 16 384
+static const int MODEL_NZ[] = {2, 15, 16, 17, 64, 129};
+static void model_calls(int nz, const char *sw) {
+  static const Shape SH[] = {{16, 16}, {100, 30}, {512, 512}, {1022, 1022}, {1024, 1024}, {2048, 2048}};
+  for (const Shape &s : SH) {
+    GeoView G;
+    memset(&G, 0, sizeof G);
+    G.nx = s.nx; G.ny = s.ny; G.nz = nz;
+    const LevView L = level(s.nx, s.ny, nz, true, false);
+    for (int f32 = 0; f32 <= 1; f32++) {
+      const ModelView M = {g_fake, g_fake, g_fake, nullptr, 0, f32};
+      call_head("mgxm_rhs_uf", nz, -1, "%dx%d f32=%d sw=%s", s.nx, s.ny, f32, sw); mgxm_rhs_uf(nullptr, &G, &M, g_fake); call_ret(0);
+      call_head("mgxm_rhs_vf", nz, -1, "%dx%d f32=%d sw=%s", s.nx, s.ny, f32, sw); mgxm_rhs_vf(nullptr, &G, &M, g_fake); call_ret(0);
+      call_head("mgxm_rhs_wf", nz, -1, "%dx%d f32=%d sw=%s", s.nx, s.ny, f32, sw); mgxm_rhs_wf(nullptr, &G, &M, g_fake); call_ret(0);
+      call_head("mgxm_correct_uvw", nz, -1, "%dx%d f32=%d sw=%s", s.nx, s.ny, f32, sw); mgxm_correct_uvw(nullptr, &G, g_fake, &M); call_ret(0);
+    }
+    call_head("mgxm_rhs_accum", nz, -1, "%dx%d sw=%s", s.nx, s.ny, sw); mgxm_rhs_accum(nullptr, &G, g_fake, g_fake, g_fake, g_fake); call_ret(0);
+    if (sw != MODEL_SWITCHES[0]) continue;
+    call_head("mgxm_ref2model", nz, -1, "%dx%d", s.nx, s.ny); mgxm_ref2model(nullptr, g_fake, g_fake, nz, 2, s.nx, s.ny); call_ret(0);
+    call_head("mgxm_ref2model_2d", nz, -1, "%dx%d", s.nx, s.ny); mgxm_ref2model_2d(nullptr, g_fake, g_fake, s.nx, s.ny); call_ret(0);
+    call_head("mgxm_js_model", nz, -1, "%dx%d", s.nx, s.ny); mgxm_js_model(nullptr, &L, g_fake, g_fake, 1); call_ret(0);
+    for (int face = 0; face <= 1; face++) {
+      call_head("mgxm_flux_zero_face", nz, -1, "%dx%d face=%d", s.nx, s.ny, face); mgxm_flux_zero_face(nullptr, &G, g_fake, face, 1); call_ret(0);
+      call_head("mgxm_flux_face_copy", nz, -1, "%dx%d face=%d", s.nx, s.ny, face); mgxm_flux_face_copy(nullptr, &G, g_fake, g_fake, face, 1, face); call_ret(0);
+    }
+  }
+}
+
+// ---- the block plan of the peer-to-peer exchange (choose_halo_p2p) by itself: record_main p2p ----
+// Over the shapes of halo_calls and a sweep of nz, nx, ny, all 3^4 edge patterns (absent, peer, self; a corner is absent beside an absent edge,
+// the rank itself between two self edges, else a peer) and MGX_P2P_MAXBLK = 1, 8, 128: nreal <= maxblk + 7; blk0 does not decrease over the
+// present directions and ends at nb, absent directions sit past the end; and nreal <= 128 at maxblk = 128 while nx, ny <= 1024, nz <= 128.
+static long long g_p2p_checked = 0, g_p2p_bad = 0;
+static int g_p2p_max[3] = {0, 0, 0}, g_p2p_max_small = 0;
+static void p2p_check(int nx, int ny, int nz, const int *present, int maxblk, int ipt) {
+  switches_default();
+  g_sw.p2p_maxblk = maxblk; g_sw.p2p_ipt = ipt;
+  const LevShape s = {nx, ny, nz, false, false, false, false, 0};
+  const P2pPlan c = choose_halo_p2p(s, present, g_sw);
+  bool ok = c.nreal <= maxblk + 7 && c.blk0[8] == c.nb && c.nreal <= c.nb && c.mixed == (c.nreal != c.nb);
+  int last = 0;
+  for (int d = 0; d < 8; d++) {
+    if (!present[d]) { ok = ok && c.blk0[d] == c.nb + 1; continue; }
+    ok = ok && c.blk0[d] >= last && c.blk0[d] <= c.nb;
+    last = c.blk0[d];
+  }
+  const bool small = maxblk == 128 && nx <= 1024 && ny <= 1024 && nz <= 128;
+  if (small) { ok = ok && c.nreal <= 128; if (c.nreal > g_p2p_max_small) g_p2p_max_small = c.nreal; }
+  int &mx = g_p2p_max[maxblk == 1 ? 0 : (maxblk == 8 ? 1 : 2)];
+  if (c.nreal > mx) mx = c.nreal;
+  g_p2p_checked++;
+  if (!ok) {
+    g_p2p_bad++;
+    printf("violation %dx%dx%d present=%d%d%d%d%d%d%d%d maxblk=%d ipt_min=%d: ipt=%d nb=%d nreal=%d blk0=%d,%d,%d,%d,%d,%d,%d,%d,%d\n", nx, ny, nz, present[0], present[1], present[2],
+           present[3], present[4], present[5], present[6], present[7], maxblk, ipt, c.ipt, c.nb, c.nreal, c.blk0[0], c.blk0[1], c.blk0[2], c.blk0[3], c.blk0[4], c.blk0[5], c.blk0[6],
+           c.blk0[7], c.blk0[8]);
+  }
+}
+static int p2p_plan_sweep() {
+  static const int MAXBLK[] = {1, 8, 128};
+  for (const Shape &s : HALO)
+    for (const int nz : {1, 2, 3, 16, 64, 80, 128})
+      for (const auto &present : PRESENT)
+        for (const int maxblk : MAXBLK)
+          for (const int ipt : {1, 3}) p2p_check(s.nx, s.ny, nz, present, maxblk, ipt);
+  static const int NZ[] = {1, 2, 3, 4, 8, 16, 32, 64, 80, 128}, NXY[] = {2, 16, 100, 128, 512, 1000, 1024, 2048, 4096};
+  for (int pat = 0; pat < 81; pat++) {
+    int present[8];
+    for (int d = 0, q = pat; d < 4; d++, q /= 3) present[d] = q % 3 == 2 ? HALO_SELF : q % 3;
+    static const int CORNER[4][2] = {{0, 3}, {0, 1}, {2, 1}, {2, 3}};   // SW, SE, NE, NW: the two edges a corner lies between
+    for (int q = 0; q < 4; q++) {
+      const int a = present[CORNER[q][0]], b = present[CORNER[q][1]];
+      present[4 + q] = !a || !b ? HALO_NONE : (a == HALO_SELF && b == HALO_SELF ? HALO_SELF : HALO_PEER);
+    }
+    for (const int nz : NZ)
+      for (const int nx : NXY)
+        for (const int ny : NXY)
+          for (const int maxblk : MAXBLK) p2p_check(nx, ny, nz, present, maxblk, 1);
+  }
+  printf("p2p_plan checked=%lld violations=%lld max_nreal maxblk1=%d maxblk8=%d maxblk128=%d maxblk128_to_1024x1024x128=%d\n", g_p2p_checked, g_p2p_bad, g_p2p_max[0], g_p2p_max[1],
+         g_p2p_max[2], g_p2p_max_small);
+  return g_p2p_bad ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc > 1 && !strcmp(argv[1], "p2p")) return p2p_plan_sweep();
   if (argc > 1 && !strcmp(argv[1], "names")) {   // mangled stub names on stdin -> the spelling of the launch lines
     char sym[4096];
     while (fgets(sym, sizeof sym, stdin)) {
@@ -453,7 +756,7 @@ int main(int argc, char **argv) {
   }
   if (argc > 1 && !strcmp(argv[1], "refuse")) g_refuse = true;
   else if (argc > 1 && !strcmp(argv[1], "fail")) g_fail = true;
-  else if (argc > 1) { fprintf(stderr, "usage: %s [refuse|fail|names]\n", argv[0]); return 2; }
+  else if (argc > 1) { fprintf(stderr, "usage: %s [refuse|fail|names|p2p]\n", argv[0]); return 2; }
   // the two fall-back passes: the default switches, no variation of sides, slopes and sweep counts
   for (int s = 0; s < (g_refuse || g_fail ? 1 : NSW); s++) {
     const char *sw = set_switch(s);
@@ -486,6 +789,30 @@ int main(int argc, char **argv) {
   rbseq_other_calls();
   for (int s = 0; s < (g_refuse || g_fail ? 1 : 3); s++)
     for (const int nz : NZS) resrest_calls(nz, s, g_refuse || g_fail || s ? 0 : 1);
+  // the units that choose a launch and nothing else: they report nothing, so the fall-back passes take their default switches only
+  const bool plain = !g_refuse && !g_fail;
+  g_group_per_wrapper = true;
+  switches_default();
+  for (const int nz : NZS) operator_calls(nz);
+  for (int s = 0; s < (plain ? NTRSW : 1); s++) {
+    const char *sw = set_tr_switch(s);
+    for (const int nz : NZS) transfer_calls(nz, sw, s == 0);
+  }
+  switches_default();
+  chain_calls();
+  for (int s = 0; s < (plain ? 4 : 1); s++) {
+    const char *sw = set_p2p_switch(s);
+    for (const int nz : {1, 2, 3, 16, 64, 80, 128}) halo_calls(nz, sw, s == 0 ? (plain ? 2 : 1) : 0);
+  }
+  switches_default();
+  for (const int nz : {1, 2, 5, 32, 64, 128, 160}) gather_layout_calls(nz);
+  one_thread_calls();
+  for (int s = 0; s < (plain ? 4 : 1); s++) {
+    switches_default();
+    g_sw.model_kr = MODEL_KR[s];
+    for (const int nz : MODEL_NZ) model_calls(nz, MODEL_SWITCHES[s]);
+  }
+  switches_default();
   return 0;
 }
 

@@ -110,7 +110,7 @@ def test_multirank_long_edge_path(monkeypatch):
 
 def _push_grid(nx, ny, nz, maxblk):
     """(items per thread, blocks per direction S, E, corner) of the halo push of a rank with one S/N, one E/W and one corner neighbour, as
-    mgxk_halo_p2p (mgx_kernels.hip) sizes it: "items" sums nz * nx, nz * ny and nz over the peer directions,
+    mgxk_halo_p2p (mgx_halo.hip; choose_halo_p2p, mgx_choice_transfer.h) sizes it: "items" sums nz * nx, nz * ny and nz over the peer directions,
     "pp.ipt = (items + 256 * maxblk - 1) / (256 * maxblk) + 1", "per = 256 * pp.ipt", "nd = (n + per - 1) / per" blocks for a direction of n items"""
     n = (nz * nx, nz * ny, nz)
     ipt = (sum(n) + 256 * maxblk - 1) // (256 * maxblk) + 1

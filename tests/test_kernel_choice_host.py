@@ -1,8 +1,10 @@
 """Which kernel serves which level, pinned on the host (no GPU): tests/kernel_choice/record_main.cpp calls the kernel wrappers of the smoother
-units (mgx_relax.hip, mgx_relax_coarse.hip, mgx_relax_ks.hip, mgx_relax_tall.hip), of the sequential-order red-black walk (mgx_rbseq.hip) and of
-the fused residual + restriction (mgx_resrest.hip) -- compiled host-only behind record_shim.h, which records a launch instead of making it --
+units (mgx_relax.hip, mgx_relax_coarse.hip, mgx_relax_ks.hip, mgx_relax_tall.hip), of the sequential-order red-black walk (mgx_rbseq.hip), of
+the fused residual + restriction (mgx_resrest.hip), and of the operator, the transfers, the halo and gather transport, the layout conversions,
+the Krylov passes and the model coupling (mgx_residual.hip, mgx_transfer.hip, mgx_hold.hip, mgx_halo.hip, mgx_layout.hip, mgx_krylov.hip,
+mgx_model.hip) -- compiled host-only behind record_shim.h, which records a launch instead of making it --
 over shapes, flags and A/B switches either side of every threshold, three times: plainly, with every hipFuncSetAttribute refused, and with
-an error reported after every launch.  Per group (wrapper x nz x method) the lines of the three passes are hashed and compared with
+an error reported after every launch.  Per group (wrapper x nz x method; one per wrapper for the units that only choose a launch) the lines of the three passes are hashed and compared with
 tests/golden/kernel_choice.json; every kernel instance the objects hold must have been launched at least once, but for the ones named below
 with the reason; and the two functions that predict another wrapper's choice (mgxk_residual_restrict_grid, mgxk_rbseq_wants_d0) agree with it.
 
@@ -24,7 +26,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mgroms_amd", "csrc")
 HERE = os.path.join(ROOT, "tests", "kernel_choice")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "kernel_choice.json")
-UNITS = ["mgx_relax", "mgx_relax_coarse", "mgx_relax_ks", "mgx_relax_tall", "mgx_rbseq", "mgx_resrest"]
+UNITS = ["mgx_relax", "mgx_relax_coarse", "mgx_relax_ks", "mgx_relax_tall", "mgx_rbseq", "mgx_resrest",
+         "mgx_residual", "mgx_transfer", "mgx_halo", "mgx_layout", "mgx_hold", "mgx_krylov", "mgx_model"]
 PASSES = ["normal", "refuse", "fail"]
 
 # Kernel instances of the units that no call of the recorder can launch, one by one with the reason.  (The instances of k_relax_ksp
@@ -46,7 +49,7 @@ UNREACHABLE.update({SCAN % (2, d, rbp, "false", nw): "the several-wave instances
 
 
 def build(outdir, sanitize=None):
-    """the recorder program: the four units host-only behind the shim, linked with record_main.cpp and nothing of the HIP runtime;
+    """the recorder program: the units host-only behind the shim, linked with record_main.cpp and nothing of the HIP runtime;
     sanitize: e.g. "address,undefined" (the program is stand-alone: it runs without a preload)"""
     hipcc = os.environ.get("HIPCC", "hipcc")
     common = ["--offload-arch=gfx950", "--cuda-host-only", "-O1", "-std=c++17", "-w", "-I" + CSRC, "-I" + HERE,
@@ -191,11 +194,27 @@ def test_fall_back_passes_launch_and_report_nothing_served(run):
     assert all(v == {"  -> 0"} for v in heads.values()), heads
 
 
+def test_p2p_plan(run):
+    """the block plan of the one-launch halo exchange (choose_halo_p2p) over the recorder's shapes and a sweep of nz in {1 .. 128}, nx, ny in
+    {2 .. 4096}, all 3^4 edge patterns (absent, peer, self) and MGX_P2P_MAXBLK = 1, 8, 128: nreal <= maxblk + 7, blk0 does not decrease over the
+    present directions, absent directions sit past the end, and nreal <= 128 at maxblk = 128 while nx, ny <= 1024, nz <= 128"""
+    r = subprocess.run([run[0], "p2p"], capture_output=True, text=True)
+    print(r.stdout[-2000:])
+    assert r.returncode == 0 and not [l for l in r.stdout.splitlines() if l.startswith("violation ")], r.stdout[-2000:]
+    m = re.search(r"p2p_plan checked=(\d+) violations=0 max_nreal maxblk1=(\d+) maxblk8=(\d+) maxblk128=(\d+) maxblk128_to_1024x1024x128=(\d+)", r.stdout)
+    assert m, r.stdout[-2000:]
+    checked, m1, m8, m128, small = map(int, m.groups())
+    assert checked >= 3 * 81 * 10 * 9 * 9
+    assert m1 <= 8 and m8 <= 15 and m128 <= 135 and small <= 128
+    assert m128 > 128   # the sweep does hold the sizes at which the plan exceeds maxblk: the bound is maxblk + 7, not maxblk
+
+
 if __name__ == "__main__":
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
         exe, objs = build(tmp, sys.argv[sys.argv.index("--sanitize") + 1] if "--sanitize" in sys.argv else None)
         passes = record(exe)
+        print(subprocess.run([exe, "p2p"], check=True, capture_output=True, text=True).stdout, end="")
         if "--dump" in sys.argv:
             d = sys.argv[sys.argv.index("--dump") + 1]
             os.makedirs(d, exist_ok=True)
