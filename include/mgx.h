@@ -198,6 +198,13 @@ int mgx_mixed_ring_levels(int nx, int ny, int nz, int *mask);
  * out[2] = planes per workgroup, out[3] = 1 for the non-temporal instance, out[4] = workgroups, out[5] = the NZ of the instance.  Pure host
  * logic (the answer of the function the launch is made by), usable before mgx_init and without a GPU.  Returns 0, or non-zero (mgx_last_error). */
 int mgx_mixed_ring_choice(int nx, int ny, int nz, int nplanes, int *out);
+/* Where option "mixed_direct" serves the coarsest solve of an fp32 cycle as one matrix-vector product, on the one-rank hierarchy of
+ * nx x ny x nz: *cells = the cells of the coarsest level when the product serves it, 0 when the sweeps run.  any_nz = the value of option
+ * "small_any_nz".  Served: a coarsest level with nz = 2 or 4 (or 3 with any_nz), even nx and ny and at most 2048 cells (inclusive), in a
+ * hierarchy of at least two levels -- the rule of the direct solve of "coarsest_direct".  Pure host logic (the answer of the function the launch
+ * is made by), usable before mgx_init and without a GPU; the option's value does not move it.  Returns 0, or non-zero (mgx_last_error) for
+ * sizes that make no hierarchy. */
+int mgx_mixed_direct_cells(int nx, int ny, int nz, int any_nz, int *cells);
 /* The entry list of one halo exchange of `rank` whose neighbours are neighb[0..7] (S,E,N,W,SW,SE,NE,NW; -1 = none), as the library hands it to
  * the exchange hook: entries[3t..3t+2] = peer, send direction, receive direction of entry t -- sendbuf[t] holds what was packed for the send
  * direction, recvbuf[t] is unpacked into the halo of the receive direction; both are of one kind (S/N edge, E/W edge, corner).  For each peer
@@ -349,6 +356,21 @@ int mgx_set_verbose(int level);
  *   ones, so that "mixed_tail" = 0 and 1 stay the same bits under this option too, nz = 80, 96, 128 and every nz without an instance --
  *   keeps the row-by-row kernel.  0 = every launch and every bit as without the option.
  *   Read-only: "mixed_ring_passes" (colour passes served by the pipelined kernel since mgx_init).
+ * "mixed_direct" (default 0, or 1; any other value is refused; survives mgx_clean / mgx_init; no environment variable; may be set at any time
+ *   and steers later cycles only; acts on the fp32 cycles of "cycle_precision" = 32 and "krylov_precision" = 32 and on mgx_mixed_op "vcycle" /
+ *   "coarsest" only): 1 = the coarsest solve of an fp32 cycle -- "ns_coarsest" sweeps from a zero correction, a fixed linear map of the level's
+ *   right-hand side -- is one matrix-vector product e = B32 f, as the fp64 cycles have it under "coarsest_direct".  B32 is the fp64 operator
+ *   (built from the unit vectors by the fp64 level's own relax kernel, in the parallel colour order the fp32 passes restate) rounded once to
+ *   fp32; it is built at the first served solve and again when the matrices or "small_any_nz" change.  One launch (k_coarse_direct32,
+ *   mgx_mixed.hip) instead of 4 "ns_coarsest" colour passes (2 or 4 "ns_coarsest" red-black), or one phase of the tail kernel under
+ *   "mixed_tail" = 1: the same bits either way, the terms of a row being added in an order that depends on the number of cells alone.  Served
+ *   (mgx_mixed_direct_cells): a coarsest level of nz = 2 or 4 (3 with "small_any_nz"), even nx and ny, at most 2048 cells, in a hierarchy of at
+ *   least two levels, entered from a restriction, with "ns_coarsest" >= 1 and "tictoc" off; where the fp64 level has no one-workgroup relax
+ *   kernel the sweeps run.  Not the bits of the sweeps: within the same 1e-5 of the fp64 solve, and the same iteration counts.  mgx_mixed_op
+ *   "vcycle" entered at the coarsest level and "relax" keep the sweeps (they relax the correction they find).  0 = every launch and every bit
+ *   as without the option.  The fp64 direct solve of "coarsest_direct" keeps its own operator and is not touched.
+ *   Read-only: "mixed_direct_solves" (coarsest solves of fp32 cycles served by the product since mgx_init; a tail launch counts the solves it
+ *   contains: as many as it has levels for an F-cycle tail, one for a V-cycle tail).
  * "small_any_nz" (default 0, or 1; any other value is refused; survives mgx_clean / mgx_init; no environment variable; may be set at any time:
  *   it steers the dispatch of later relax calls only): 1 = a relax call on a small level with nz = 3, 5, 6 or 7 -- the coarse ends of the
  *   nz = 24, 48, 96 hierarchies, and of nz = 20, 28, 40, 80 under "hold_odd_nz" -- runs in one workgroup and one launch, as the nz = 2 and 4
@@ -442,7 +464,9 @@ int mgx_counters(long long *out);
  * (r of lev -> b of lev+1, p of lev+1 = 0), "coarse2fine" (p of lev += interpolation of p of lev+1), "resrest" (restriction of b - A p of lev
  * -> b of lev+1, p of lev+1 = 0: the down leg of a V-cycle), "vcycle" (Vcycle(lev) on the copies from p, b of level lev; p of every level
  * lev .. nlevs = the correction the cycle leaves there: every entry of the tail kernel of option "mixed_tail" from a rough state, where a solve
- * only ever enters with a zero correction).  No Fortran counterpart. */
+ * only ever enters with a zero correction), "coarsest" (lev = nlevs only: the coarsest solve of a cycle, b of the coarsest level -> p from a
+ * zero correction -- the product where option "mixed_direct" is on and the level served, otherwise the "ns_coarsest" sweeps).  No Fortran
+ * counterpart. */
 int mgx_mixed_op(const char *op, int lev, int n);
 /* test hook of the three passes of option "krylov" (mgx_krylov.hip; single rank, after mgx_matrices): runs ONE pass on level 1 through the
  * wrapper solve_p calls for it, on the buffers solve_p uses (its ring of direction pairs, partial sums and device scalars, grid(1)%p and %r,

@@ -65,6 +65,7 @@ _SIGS = {
     "mgx_mixed_tail_first": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "mgx_mixed_ring_levels": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "mgx_mixed_ring_choice": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "mgx_mixed_direct_cells": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "mgx_exchange_plan": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mgx_get_field": (C.c_int, [C.c_int, C.c_int, _DP]),
     "mgx_set_field": (C.c_int, [C.c_int, C.c_int, _DP]),

@@ -75,6 +75,7 @@ const Opt OPTIONS[] = {
   {"krylov_precision",    &State::krylov_precision, nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 32 / 64 only (no preset: the table's would pass any number by)
   {"mixed_tail",          &State::mixed_tail,       nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0 / 1 only
   {"mixed_ring",          &State::mixed_ring,       nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0 / 1 only
+  {"mixed_direct",        &State::mixed_direct,     nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0 / 1 only
   {"small_any_nz",        &State::small_any_nz,     nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0 / 1 only
   {"periodic",            &State::periodic,         nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0..3 only, and not while initialised (read by mgx_init)
   {"hold_odd_nz",         &State::hold_odd_nz,      nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0 / 1 only, and not while initialised (read by mgx_init)
@@ -92,6 +93,7 @@ const Opt OPTIONS[] = {
   {"mixed_iterations", nullptr, CNT(n_mixed), nullptr, ENV_NONE, RO, false},
   {"mixed_tail_launches", nullptr, CNT(n_mixed_tail), nullptr, ENV_NONE, RO, false},
   {"mixed_ring_passes", nullptr, CNT(n_mixed_ring), nullptr, ENV_NONE, RO, false},
+  {"mixed_direct_solves", nullptr, CNT(n_mixed_direct), nullptr, ENV_NONE, RO, false},
   {"small_any_nz_calls", nullptr, CNT(n_small_any), nullptr, ENV_NONE, RO, false},
   {"krylov_restarts", nullptr, CNT(kr_restarts), nullptr, ENV_NONE, RO, false},
   {"krylov_mixed_iterations", nullptr, CNT(n_kr_mixed), nullptr, ENV_NONE, RO, false},
@@ -487,6 +489,18 @@ int mgx_mixed_ring_choice(int nx, int ny, int nz, int nplanes, int *out) {
   mgxx_ring_choice(nx, ny, nz, nplanes, out);
   return 0;
 }
+// cells of the coarsest level of a one-rank hierarchy where option "mixed_direct" serves its solve as a product, 0 = the sweeps (choose_mixed_direct_cells)
+int mgx_mixed_direct_cells(int nx, int ny, int nz, int any_nz, int *cells) {
+  if (!cells) return fail("mgx_mixed_direct_cells: cells is NULL");
+  if (nx < 2 || ny < 2 || nz < 2) return fail("mgx_mixed_direct_cells: %d x %d x %d is not a level-1 size", nx, ny, nz);
+  const int nl = find_grid_levels(1, 1, nx, ny, nz);
+  if (nl < 1) return fail("mgx_mixed_direct_cells: %d x %d x %d has no hierarchy", nx, ny, nz);
+  std::vector<Level> T(nl);
+  T[0].nx = nx; T[0].ny = ny; T[0].nz = nz;
+  rank_level_table(0, T, 1, 1, 8);
+  *cells = mgxx_direct32_cells(T[nl - 1].nx, T[nl - 1].ny, T[nl - 1].nz, nl, any_nz ? 1 : 0);
+  return 0;
+}
 int mgx_exchange_plan(const int *neighb, int rank, int *entries, int *self_mask) {
   if (!neighb || !entries) return -1;
   XEntry pl[8];
@@ -502,6 +516,7 @@ int mgx_set_option(const char *name, int value) {
   if (streq(name, "krylov") && (value < 0 || value > 8)) return fail("krylov must be 0 (off) or 1..8 (retained direction pairs of the truncated GCR), got %d", value);
   if (streq(name, "mixed_tail") && value != 0 && value != 1) return fail("mixed_tail must be 1 (the small levels of an fp32 cycle in one launch) or 0 (one launch per colour pass and transfer), got %d", value);
   if (streq(name, "mixed_ring") && value != 0 && value != 1) return fail("mixed_ring must be 1 (the fp32 colour passes of the levels that are not small by the pipelined kernel) or 0 (k_relax32 on every level), got %d", value);
+  if (streq(name, "mixed_direct") && value != 0 && value != 1) return fail("mixed_direct must be 1 (the coarsest solve of an fp32 cycle as one matrix-vector product) or 0 (ns_coarsest sweeps), got %d", value);
   if (streq(name, "small_any_nz") && value != 0 && value != 1) return fail("small_any_nz must be 1 (closed levels of at most 1024 columns with nz = 3, 5, 6, 7 relax in one launch) or 0 (one launch per colour pass), got %d", value);
   if (streq(name, "periodic")) {
     if (value < 0 || value > 3) return fail("periodic must be 0 (closed), 1 (the i direction, east-west), 2 (the j direction, north-south) or 3 (both), got %d", value);
@@ -723,6 +738,12 @@ int mgx_mixed_op(const char *op, int lev, int n) {
     mgxx_to32(S.stream, &L.v, &L.v32, L.v.p, L.v32.e, 1.0); mgxx_to32(S.stream, &L.v, &L.v32, L.v.b, L.v32.f, 1.0);
     CHK(vcycle32(lev, false));
     for (int q = lev; q <= S.nlevs; q++) { Level &Q = S.lev[q - 1]; mgxx_to64(S.stream, &Q.v, &Q.v32, Q.v32.e, Q.v.p, 1.0, 0); }
+  } else if (streq(op, "coarsest")) {   // the coarsest solve of a cycle: b of the coarsest level -> p, from e = 0 (the product under option "mixed_direct", else the sweeps)
+    if (lev != S.nlevs) return fail("mgx_mixed_op(coarsest, %d): the coarsest level is %d", lev, S.nlevs);
+    mgxx_to32(S.stream, &L.v, &L.v32, L.v.b, L.v32.f, 1.0);
+    HIPCHK(hipMemsetAsync(L.v32.e, 0, L.n3js32 * sizeof(float), S.stream));
+    CHK(coarsest_solve32(true));
+    mgxx_to64(S.stream, &L.v, &L.v32, L.v32.e, L.v.p, 1.0, 0);
   } else if (streq(op, "residual")) {
     mgxx_to32(S.stream, &L.v, &L.v32, L.v.p, L.v32.e, 1.0); mgxx_to32(S.stream, &L.v, &L.v32, L.v.b, L.v32.f, 1.0);
     mgxx_residual(S.stream, &L.v32, S.real);
@@ -745,7 +766,7 @@ int mgx_mixed_op(const char *op, int lev, int n) {
     mgxx_to32(S.stream, &C.v, &C.v32, C.v.p, C.v32.e, 1.0); mgxx_to32(S.stream, &L.v, &L.v32, L.v.p, L.v32.e, 1.0);
     coarse2fine32(lev);
     mgxx_to64(S.stream, &L.v, &L.v32, L.v32.e, L.v.p, 1.0, 0);
-  } else return fail("mgx_mixed_op: unknown operator '%s' (relax, vcycle, residual, fine2coarse, coarse2fine, resrest)", op);
+  } else return fail("mgx_mixed_op: unknown operator '%s' (relax, vcycle, coarsest, residual, fine2coarse, coarse2fine, resrest)", op);
   return sync_stream();
 }
 

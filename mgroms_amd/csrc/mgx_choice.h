@@ -31,6 +31,7 @@ enum KernelFamily {
   KF_RB_WALK_APPLY, KF_RB_WINDOW, KF_RB_APPLY,  // walk + correction of a small level, the windowed walk, the correction alone: k_rbseq_walk_apply, _window, _apply
   KF_RR_FLAT, KF_RR_WALK,                // residual + restriction, a wave per S fine rows or walking up the column: k_residual_restrict_flat, k_residual_restrict
   KF_RELAX32, KF_RELAX32R,               // the fp32 colour pass, row by row or with its rows in register rings: k_relax32, k_relax32r (mgx_mixed.hip)
+  KF_DIRECT32,                           // the coarsest solve of an fp32 cycle as one product: k_coarse_direct32 (mgx_mixed.hip)
 };
 
 struct Choice {
@@ -476,6 +477,27 @@ static inline Choice choose_relax32(const LevShape &s, int nplanes, int real, in
   }
   c.family = KF_RELAX32; c.nz = with_nz<RELAX32_NZ_LIST>(s.nz, [](auto) {}) ? s.nz : 0;
   c.grid = ch_chunks(s.ny); c.gy = (nplanes + 3) / 4; c.bx = CH_WAVE; c.by = 4;
+  return c;
+}
+
+// ---- mgx_mixed.hip: mgxx_coarse_direct32, the coarsest solve of the fp32 cycles as one product (option "mixed_direct") ----
+// cells of the coarsest level (shape s) of a hierarchy of nlevs levels that the product serves, 0 = the sweeps: the rule of the fp64 direct
+// solve (choose_coarse_direct_cells) on a level that is entered from a restriction, i.e. not the only one
+static inline int choose_mixed_direct_cells(const LevShape &s, int nlevs, int any) { return nlevs >= 2 ? choose_coarse_direct_cells(s, any) : 0; }
+// The product e = B f of n rows is cut into tiles of 64 rows and, along the columns, into S slabs of cps columns whose partial sums meet in
+// LDS: S is as many as 8192 partial sums hold for the padded row count, 16 at the most -- a function of n alone, and with it the order in
+// which the terms of a row are added (direct32_rows), whatever launch runs the items.
+constexpr int DIRECT32_MAX_N = 2048, DIRECT32_PART = 8192, DIRECT32_MAX_SLABS = 16;
+// (constexpr: the kernel reads them too)
+constexpr int ch_direct32_tiles(int n) { return (n + CH_WAVE - 1) / CH_WAVE; }
+constexpr int ch_direct32_slabs(int n) { const int s = DIRECT32_PART / (ch_direct32_tiles(n) * CH_WAVE); return s < DIRECT32_MAX_SLABS ? s : DIRECT32_MAX_SLABS; }
+// the stand-alone launch: one workgroup per tile of 64 rows, one wave per slab
+static inline Choice choose_coarse_direct32(const LevShape &s, int nlevs, int any) {
+  Choice c;
+  const int n = choose_mixed_direct_cells(s, nlevs, any);
+  if (!n) return c;
+  c.family = KF_DIRECT32; c.nz = s.nz; c.nt = n; c.d = ch_direct32_slabs(n);
+  c.grid = ch_direct32_tiles(n); c.bx = CH_WAVE * c.d; c.ret = 1;
   return c;
 }
 

@@ -609,15 +609,17 @@ int tail_hand(int lev1) {
   const int hand = std::max(lev1, S.mx_tail_first);
   return S.nlevs - hand + 1 <= mgxx_tail_max_levels() ? hand : 0;
 }
-// one launch of the tail kernel on levels lev .. last (tail_hand has counted them)
-int tail32(int lev, int last, int mode, bool lead, int n) {
+// one launch of the tail kernel on levels lev .. last (tail_hand has counted them).  dM (option "mixed_direct", direct32_operator): the
+// coarsest solves inside the launch are products -- nl of them in an F-cycle tail of nl levels, one in a V-cycle tail
+int tail32(int lev, int last, int mode, bool lead, int n, const float *dM = nullptr, int dn = 0) {
   const LevView32 *vs[8];
   const int nl = last - lev + 1;
   if (nl < 1 || nl > 8) return fail("mixed_tail: levels %d..%d", lev, last);
   for (int q = 0; q < nl; q++) vs[q] = &S.lev[lev - 1 + q].v32;
-  if (!mgxx_tail(S.stream, vs, nl, mode, lead ? 1 : 0, n, S.par.ns_pre, S.par.ns_post, S.par.ns_coarsest, S.method == M_RB, S.real, S.linear))
+  if (!mgxx_tail(S.stream, vs, nl, mode, lead ? 1 : 0, n, S.par.ns_pre, S.par.ns_post, S.par.ns_coarsest, S.method == M_RB, S.real, S.linear, dM, dn))
     return fail("mixed_tail: the tail kernel does not serve levels %d..%d (set option mixed_tail = 0)", lev, last);
   S.n_launch++; S.n_mixed_tail++;
+  if (dM) S.n_mixed_direct += mode == TAIL_FCYCLE ? nl : 1;
   return 0;
 }
 
@@ -642,6 +644,51 @@ int relax32(int lev, int nsweeps) {
 }
 void coarse2fine32(int lev) { mgxx_coarse2fine(S.stream, &S.lev[lev - 1].v32, &S.lev[lev].v32, S.linear); S.n_launch++; }
 
+// Option "mixed_direct": the operator of the coarsest solve of an fp32 cycle, *M = nullptr where the sweeps run (the option is off, a timed
+// call, no sweeps, a shape the product does not serve, a level the builder has no kernel for).  B32 is the fp64 operator rounded once: the
+// fp64 level's own one-workgroup relax kernel builds it from the unit vectors in its parallel colour order (mode 0, what the fp32 red-black
+// restates), then one launch converts it.  Built at the first served solve, again when the coefficients have changed (coef_gen) or option
+// "small_any_nz" has (it decides whether nz = 3 has a kernel).  State of its own: the fp64 direct solve (cd_*) is not touched -- its scratch
+// cd_pb is borrowed where it exists, every launch being ordered by the stream.
+int direct32_operator(const float **M, int *n) {
+  *M = nullptr; *n = 0;
+  if (!S.mixed_direct || S.tictoc || S.par.ns_coarsest < 1) return 0;
+  Level &L = S.lev[S.nlevs - 1];
+  const int any = S.small_any_nz ? 1 : 0;
+  const int cells = mgxx_direct32_cells(L.nx, L.ny, L.nz, S.nlevs, any);
+  if (!cells) return 0;
+  if (S.md_gen != S.coef_gen || S.md_any != any) {
+    S.md_gen = S.coef_gen; S.md_any = any; S.md_valid = 0;
+    if (S.md_n != cells) {   // (a level has one size: allocated once)
+      CHK(fmalloc(&S.md_M, (size_t)cells * cells)); CHK(dmalloc(&S.md_M64, (size_t)cells * cells));
+      if (!S.cd_pb) CHK(dmalloc(&S.md_pb, (size_t)2 * cells * L.n3js));
+      S.md_n = cells;
+    }
+    if (mgxk_coarse_direct_build(S.stream, &L.v, S.par.ns_coarsest, S.method, S.real, sides_of(L), 0, S.cd_pb ? S.cd_pb : S.md_pb, (long long)L.n3js, S.md_M64, any)) {
+      mgxx_direct32_round(S.stream, S.md_M64, S.md_M, cells);
+      S.md_valid = 1; S.n_launch += 4;
+    }   // else: no one-workgroup kernel for this level, remembered until the matrix or the option changes
+  }
+  if (S.md_valid) { *M = S.md_M; *n = cells; }
+  return 0;
+}
+
+// relax(nlevs, ns_coarsest) of a cycle on the shadow.  e_zero: the caller has just restricted onto the level, so the solve is a fixed linear
+// map of f and option "mixed_direct" may serve it as one product (k_coarse_direct32); a V-cycle entered at the coarsest level as an
+// operator relaxes whatever e it finds: the sweeps.
+int coarsest_solve32(bool e_zero) {
+  const float *M = nullptr; int n = 0;
+  if (e_zero) CHK(direct32_operator(&M, &n));
+  if (M && mgxx_coarse_direct32(S.stream, &S.lev[S.nlevs - 1].v32, M, S.nlevs, S.small_any_nz ? 1 : 0)) { S.n_launch++; S.n_mixed_direct++; return 0; }
+  return relax32(S.nlevs, S.par.ns_coarsest);
+}
+// the same decision for a cycle whose coarsest solve lies inside a tail launch on levels hand .. nlevs
+int tail32_cycle(int hand, int mode, bool lead) {
+  const float *M = nullptr; int n = 0;
+  if (hand < S.nlevs) CHK(direct32_operator(&M, &n));
+  return tail32(hand, S.nlevs, mode, lead, 0, M, n);
+}
+
 // mg_solvers.f90:129-151 on the shadow; lead_c2f: Fcycle's coarse2fine(lev1) comes first (:119-120).  Option "mixed_tail": from level
 // `hand` down to the coarsest relax and back up to hand's post-smoothing in one launch; the levels above keep theirs, the transfers
 // between hand - 1 and hand included.
@@ -652,8 +699,8 @@ int vcycle32(int lev1, bool lead_c2f) {
     CHK(relax32(lev, S.par.ns_pre));
     mgxx_resrest(S.stream, &S.lev[lev - 1].v32, &S.lev[lev].v32, S.real); S.n_launch++;   // compute_residual(lev) + fine2coarse(lev)
   }
-  if (hand) CHK(tail32(hand, S.nlevs, TAIL_VCYCLE, lead_c2f && hand == lev1, 0));
-  else CHK(relax32(S.nlevs, S.par.ns_coarsest));
+  if (hand) CHK(tail32_cycle(hand, TAIL_VCYCLE, lead_c2f && hand == lev1));
+  else CHK(coarsest_solve32(lev1 < S.nlevs));
   for (int lev = bottom - 1; lev >= lev1; lev--) {
     coarse2fine32(lev);
     CHK(relax32(lev, S.par.ns_post));
@@ -669,8 +716,8 @@ int fcycle32() {
   for (int lev = 1; lev <= bottom - 1; lev++) {
     mgxx_restrict(S.stream, &S.lev[lev - 1].v32, &S.lev[lev].v32, S.lev[lev - 1].v32.f); S.n_launch++;
   }
-  if (hand) CHK(tail32(hand, S.nlevs, TAIL_FCYCLE, false, 0));
-  else CHK(relax32(S.nlevs, S.par.ns_coarsest));
+  if (hand) CHK(tail32_cycle(hand, TAIL_FCYCLE, false));
+  else CHK(coarsest_solve32(S.nlevs >= 2));
   for (int lev = bottom - 1; lev >= 1; lev--) CHK(vcycle32(lev, true));
   return 0;
 }

@@ -180,6 +180,15 @@ struct State {
   // one launch per colour pass either way, other roundings within the same bound against the fp64 pass.  0 = every launch and bit as before.
   int mixed_ring = 0;
   long long n_mixed_ring = 0;     // read-only option "mixed_ring_passes": colour passes served by k_relax32r since mgx_init
+  // option "mixed_direct" (0 default, 1): the coarsest solve of an fp32 cycle -- ns_coarsest sweeps from e = 0, a fixed linear map of f -- as one
+  // product with B32, the operator of the fp64 level (mgxk_coarse_direct_build, parallel colour order) rounded once to fp32: k_coarse_direct32, or
+  // a phase of the tail kernel (mgx_mixed.hip).  Served where the fp64 direct solve is (choose_mixed_direct_cells, mgx_choice.h); apart from
+  // that solve's state (cd_*), of which only the scratch cd_pb is borrowed.  0 = every launch and bit as before.
+  int mixed_direct = 0;
+  float *md_M = nullptr; double *md_M64 = nullptr, *md_pb = nullptr;   // B32, the builder's fp64 matrix, its scratch where cd_pb does not exist
+  int md_n = 0, md_valid = 0, md_any = -1;      // cells allocated for; the operator is built (0 with md_gen current: the builder declined)
+  unsigned long long md_gen = ~0ULL;            // the coefficients it was built from (coef_gen)
+  long long n_mixed_direct = 0;   // read-only option "mixed_direct_solves": coarsest solves of fp32 cycles served by the product since mgx_init
   unsigned long long coef_gen = 0, mx_gen = ~0ULL;
   // option "periodic" (0 default; bit 1 = the i direction, east-west; bit 2 = the j direction, north-south): read by mgx_init, which makes the rank
   // its own neighbour on the periodic sides of every level (rank_level_table).  Such a side is an open side like a rank seam: every kernel
@@ -291,6 +300,7 @@ int krylov_op(const char *op, int nd, double *const *f, const int *slot, const d
 int mixed_check();
 int mixed_prepare();
 int relax32(int lev, int nsweeps);
+int coarsest_solve32(bool e_zero);
 void coarse2fine32(int lev);
 int vcycle32(int lev1, bool lead_c2f);
 

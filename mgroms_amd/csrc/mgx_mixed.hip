@@ -383,6 +383,60 @@ __global__ __launch_bounds__(256) void k_coarse2fine32(LevView32 F, LevView32 C)
 }
 
 // ------------------------------------------------------------------------------------------------
+// The coarsest solve of a cycle as ONE matrix-vector product (option "mixed_direct"): the level is entered with e = 0 and left after
+// ns_coarsest sweeps, a fixed linear map e = B f of its right-hand side (mgx_relax_coarse.hip has the fp64 form and the builder).  M is
+// that operator rounded once to fp32, column by column: M[c * n + r], the cells numbered r = (k - 1) + nz * ((j - 1) + ny * (i - 1)).
+// direct32_rows is the whole product on the tiles t0 .. t1 - 1 of 64 rows, by the waves of one workgroup: f is staged in LDS; an item is
+// one tile of rows times one slab of columns (ch_direct32_slabs, mgx_choice.h), lanes along r (coalesced), the columns of the slab walked
+// in ascending order by one chain of fmaf; the S partial sums of a row meet in LDS and are added in ascending order of the slab.  So the
+// order in which the terms of a row are added is a function of n alone -- not of the lane count, the launch or which wave ran an item:
+// the stand-alone launch and the phase of the tail kernel give the same bits (explicit fmaf / __fadd_rn: nothing for -ffp-contract to
+// decide).  Whole rows belong to one workgroup: no atomics, no tickets.  Lanes past n neither load nor store.  Two barriers inside;
+// the caller's follows the stores of e and of its physical-boundary images.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ long long cell_js32(const LevView32 &L, const int r, int &k0, int &j, int &i) {
+  k0 = r % L.nz; const int q = r / L.nz; j = 1 + q % L.ny; i = 1 + q / L.ny;
+  return (long long)i * L.plane + (long long)k0 * L.RS + jpos32(L, j);
+}
+__device__ __forceinline__ void direct32_rows(const LevView32 &L, const float *__restrict__ M, const int n, float *fs, float *part, const int t0, const int t1) {
+  const int tid = threadIdx.x, nt = blockDim.x, lane = tid & (WAVE - 1), wave = tid / WAVE, nwaves = nt / WAVE;
+  const int S = ch_direct32_slabs(n), cps = (n + S - 1) / S, npad = ch_direct32_tiles(n) * WAVE;
+  for (int c = tid; c < n; c += nt) { int k0, j, i; fs[c] = L.f[cell_js32(L, c, k0, j, i)]; }
+  __syncthreads();
+  for (int q = wave; q < (t1 - t0) * S; q += nwaves) {
+    const int t = t0 + q / S, s = q - (q / S) * S, r = t * WAVE + lane;
+    const int c0 = s * cps, c1 = c0 + cps < n ? c0 + cps : n;
+    if (r < n) {
+      const float *__restrict__ m = M + (long long)c0 * n + r;
+      float acc = 0.f;
+#pragma unroll 8
+      for (int c = c0; c < c1; c++, m += n) acc = __fmaf_rn(*m, fs[c], acc);
+      part[s * npad + r] = acc;
+    }
+  }
+  __syncthreads();
+  const int r1 = t1 * WAVE < n ? t1 * WAVE : n;
+  for (int r = t0 * WAVE + tid; r < r1; r += nt) {
+    float v = part[r];
+    for (int s = 1; s < S; s++) v = __fadd_rn(v, part[s * npad + r]);
+    int k0, j, i;
+    const long long o = cell_js32(L, r, k0, j, i);
+    L.e[o] = v;
+    mirror32(L, L.e, (long long)k0 * L.RS, j, i, jpos32(L, j), v);
+  }
+}
+// one workgroup per tile of 64 rows, one wave per slab (choose_coarse_direct32)
+__global__ __launch_bounds__(WAVE * DIRECT32_MAX_SLABS) void k_coarse_direct32(LevView32 L, const float *__restrict__ M, int n) {
+  __shared__ float fs[DIRECT32_MAX_N], part[DIRECT32_PART];
+  direct32_rows(L, M, n, fs, part, blockIdx.x, blockIdx.x + 1);
+}
+// B32 = the fp64 operator rounded once, same storage
+__global__ void k_direct32_round(const double *__restrict__ M64, float *__restrict__ M, long long nn) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < nn) M[t] = (float)M64[t];
+}
+
+// ------------------------------------------------------------------------------------------------
 // The tail of a cycle in ONE workgroup (option "mixed_tail"): the coarsest levels that are all small (mixed_tail_small, mgx_internal.h)
 // cost a per-launch cycle its launch latency and nothing else (16x16x2: 960 launches per F-cycle), so here the schedule of relax32 /
 // vcycle32 / fcycle32 (mgx_cycle.cpp) on those levels runs inside one launch of up to 768 lanes.  Lane 0 writes the schedule as a list of
@@ -402,7 +456,7 @@ __global__ __launch_bounds__(256) void k_coarse2fine32(LevView32 F, LevView32 C)
 #define MIXED_TAIL_LANES_B 256
 // a phase: kind | level (index into Tail32::L) << 2 | which sweep count << 5
 enum { TP_RELAX = 0, TP_RESREST = 1, TP_RESTRICT = 2, TP_C2F = 3 };
-enum { TN_CALL = 0, TN_PRE = 1, TN_POST = 2, TN_COARSEST = 3 };
+enum { TN_CALL = 0, TN_PRE = 1, TN_POST = 2, TN_COARSEST = 3, TN_DIRECT = 4 };   // TN_DIRECT: not sweeps, the product of option "mixed_direct"
 #define TAIL_OP(kind, lev, nsel) (unsigned char)((kind) | (lev) << 2 | (nsel) << 5)
 // the F-cycle of nl levels: nl restrictions and coarsest relax, then V-cycles of 2 + 4 d phases from d = 1 .. nl - 1 levels above the coarsest
 #define MIXED_TAIL_MAX_OPS (MIXED_TAIL_MAX_LEVELS + 2 * (MIXED_TAIL_MAX_LEVELS - 1) * (MIXED_TAIL_MAX_LEVELS + 1))
@@ -414,29 +468,32 @@ struct Tail32 {
   // `case 8:` of a switch over L.nz the compiler knows L.nz, folds the `k < L.nz` of off32 / res32 that the per-launch kernels test at run
   // time, and -ffp-contract=fast then fuses across what were block boundaries: other roundings than theirs.
   int inst[MIXED_TAIL_MAX_LEVELS];
+  // option "mixed_direct": the coarsest solve of a cycle is the product with dM (dn rows) instead of ns_coarsest sweeps; nullptr = the sweeps
+  const float *dM; int dn;
 };
 
 // vcycle32(a, lead) on levels a .. nl-1 (indices into Tail32::L)
-__device__ __forceinline__ int tail_vcycle(unsigned char *p, int q, const int a, const int nl, const bool lead) {
+__device__ __forceinline__ int tail_vcycle(unsigned char *p, int q, const int a, const int nl, const bool lead, const int coarsest) {
   for (int l = a; l < nl - 1; l++) {
     if (lead && l == a) p[q++] = TAIL_OP(TP_C2F, l, 0);
     p[q++] = TAIL_OP(TP_RELAX, l, TN_PRE);
     p[q++] = TAIL_OP(TP_RESREST, l, 0);
   }
-  p[q++] = TAIL_OP(TP_RELAX, nl - 1, TN_COARSEST);
+  p[q++] = TAIL_OP(TP_RELAX, nl - 1, coarsest);
   for (int l = nl - 2; l >= a; l--) {
     p[q++] = TAIL_OP(TP_C2F, l, 0);
     p[q++] = TAIL_OP(TP_RELAX, l, TN_POST);
   }
   return q;
 }
-__device__ __forceinline__ int tail_program(const Tail32 &T, unsigned char *p) {
+// coarsest: TN_COARSEST, or TN_DIRECT in the instances that have the phase (the host hands them a cycle whose coarsest level was just restricted onto)
+__device__ __forceinline__ int tail_program(const Tail32 &T, unsigned char *p, const int coarsest) {
   if (T.mode == TAIL_RELAX) { p[0] = TAIL_OP(TP_RELAX, 0, TN_CALL); return 1; }
-  if (T.mode == TAIL_VCYCLE) return tail_vcycle(p, 0, 0, T.nl, T.lead != 0);
+  if (T.mode == TAIL_VCYCLE) return tail_vcycle(p, 0, 0, T.nl, T.lead != 0, coarsest);
   int q = 0;   // TAIL_FCYCLE: fcycle32 with L[0] as its finest level
   for (int l = 0; l < T.nl - 1; l++) p[q++] = TAIL_OP(TP_RESTRICT, l, 0);
-  p[q++] = TAIL_OP(TP_RELAX, T.nl - 1, TN_COARSEST);
-  for (int l = T.nl - 2; l >= 0; l--) q = tail_vcycle(p, q, l, T.nl, true);
+  p[q++] = TAIL_OP(TP_RELAX, T.nl - 1, coarsest);
+  for (int l = T.nl - 2; l >= 0; l--) q = tail_vcycle(p, q, l, T.nl, true, coarsest);
   return q;
 }
 
@@ -474,18 +531,34 @@ __device__ __forceinline__ void tail_relax(const LevView32 &L, const int nsweeps
   }
 }
 
+// The row count of the direct phase reaches it through LDS, read inside the phase: taken from the kernel's argument, everything the phase
+// derives from it (slabs, columns per slab, the lanes' tiles) is loop-invariant, hoisted out of the phase loop and kept alive across the colour
+// passes -- 3 registers too many for the 768-lane class (16 bytes of scratch in its red-black instances).
+__device__ __forceinline__ int *tail_direct_n() { __shared__ int n; return &n; }
 // NZMAX: the largest register instance of the colour pass compiled in (a level with a larger one goes to the other class: launch_tail)
-template <bool REAL, bool RB, int NZMAX, int LANES>
+// DIRECT: the instance has the phase of option "mixed_direct" (direct32_rows on every tile of the coarsest level) and emits it for the coarsest
+// solve of its cycles; without it the kernel is the text it was before the option existed
+template <bool REAL, bool RB, int NZMAX, int LANES, bool DIRECT>
 __global__ __launch_bounds__(LANES) void k_tail32(const Tail32 T) {
   __shared__ unsigned char prog[MIXED_TAIL_MAX_OPS];
   __shared__ int nprog;
-  if (threadIdx.x == 0) nprog = tail_program(T, prog);
+  if (threadIdx.x == 0) nprog = tail_program(T, prog, DIRECT ? TN_DIRECT : TN_COARSEST);
+  if constexpr (DIRECT) { if (threadIdx.x == 0) *tail_direct_n() = T.dn; }
   __syncthreads();
   const int np = __builtin_amdgcn_readfirstlane(nprog), nt = blockDim.x, tid = threadIdx.x;
   for (int pc = 0; pc < np; pc++) {
     const int op = __builtin_amdgcn_readfirstlane((int)prog[pc]), kind = op & 3, l = (op >> 2) & 7, nsel = op >> 5;
     const LevView32 &L = T.L[l];
     if (kind == TP_RELAX) {
+      if constexpr (DIRECT) {
+        if (nsel == TN_DIRECT) {
+          __shared__ float dfs[DIRECT32_MAX_N], dpart[DIRECT32_PART];
+          const int dn = __builtin_amdgcn_readfirstlane(*tail_direct_n());
+          direct32_rows(L, T.dM, dn, dfs, dpart, 0, ch_direct32_tiles(dn));
+          __syncthreads();
+          continue;
+        }
+      }
       const int ns = nsel == TN_CALL ? T.n : (nsel == TN_PRE ? T.ns_pre : (nsel == TN_POST ? T.ns_post : T.ns_coarsest));
       switch (T.inst[l]) {   // the instance mgxx_relax_pass picks
         case 2: tail_relax<2, REAL, RB>(L, ns); break;
@@ -563,13 +636,13 @@ static void launch_relax32(hipStream_t st, const LevView32 *L, const Choice &c, 
   });
 }
 
-template <int NZMAX, int LANES>
+template <int NZMAX, int LANES, bool DIRECT>
 static void launch_tail(hipStream_t st, const Tail32 &T, int cols, int real, int rb) {
   const dim3 blk(cols >= LANES ? LANES : (cols + WAVE - 1) / WAVE * WAVE);
-  if (real && rb) hipLaunchKernelGGL((k_tail32<true, true, NZMAX, LANES>), dim3(1), blk, 0, st, T);
-  else if (real) hipLaunchKernelGGL((k_tail32<true, false, NZMAX, LANES>), dim3(1), blk, 0, st, T);
-  else if (rb) hipLaunchKernelGGL((k_tail32<false, true, NZMAX, LANES>), dim3(1), blk, 0, st, T);
-  else hipLaunchKernelGGL((k_tail32<false, false, NZMAX, LANES>), dim3(1), blk, 0, st, T);
+  if (real && rb) hipLaunchKernelGGL((k_tail32<true, true, NZMAX, LANES, DIRECT>), dim3(1), blk, 0, st, T);
+  else if (real) hipLaunchKernelGGL((k_tail32<true, false, NZMAX, LANES, DIRECT>), dim3(1), blk, 0, st, T);
+  else if (rb) hipLaunchKernelGGL((k_tail32<false, true, NZMAX, LANES, DIRECT>), dim3(1), blk, 0, st, T);
+  else hipLaunchKernelGGL((k_tail32<false, false, NZMAX, LANES, DIRECT>), dim3(1), blk, 0, st, T);
 }
 static dim3 whole_grid(int ny, int nx) { return dim3((ny / 2 + 1 + WAVE - 1) / WAVE, (nx + 2 + 3) / 4, 2); }
 
@@ -614,9 +687,12 @@ void mgxx_coarse2fine(hipStream_t st, const LevView32 *F, const LevView32 *C, in
 // TAIL_VCYCLE = vcycle32(levs[0], lead) down to levs[nl-1] and back, TAIL_FCYCLE = fcycle32 with levs[0] as its finest level.  Returns 0,
 // nothing launched, where the kernel does not serve the call (more levels than it takes, a level that is not small, levels that are not
 // consecutive): tail_hand (mgx_cycle.cpp) keeps a cycle of more levels on its launches, anything else is the caller's error to report.
+// dM (option "mixed_direct"): the operator of the coarsest level levs[nl-1], dn rows -- the coarsest solve of the cycle is then the product
+// (a TAIL_VCYCLE of one level relaxes the e it finds: never with dM); nullptr = the sweeps, by the instances without the phase.
 int mgxx_tail(hipStream_t st, const LevView32 *const *levs, int nl, int mode, int lead, int n, int ns_pre, int ns_post, int ns_coarsest, int rb,
-              int real, int linear) {
+              int real, int linear, const float *dM, int dn) {
   if (nl < 1 || nl > MIXED_TAIL_MAX_LEVELS || (mode == TAIL_RELAX && nl != 1)) return 0;
+  if (dM && (mode == TAIL_RELAX || nl < 2 || dn != levs[nl - 1]->nx * levs[nl - 1]->ny * levs[nl - 1]->nz || dn > DIRECT32_MAX_N)) return 0;
   Tail32 T = {};
   for (int l = 0; l < nl; l++) {
     const LevView32 &v = *levs[l];
@@ -627,15 +703,34 @@ int mgxx_tail(hipStream_t st, const LevView32 *const *levs, int nl, int mode, in
     T.inst[l] = (v.nz == 2 || v.nz == 4 || v.nz == 8 || v.nz == 16 || v.nz == 32) ? v.nz : 0;
   }
   T.nl = nl; T.mode = mode; T.lead = lead; T.n = n; T.ns_pre = ns_pre; T.ns_post = ns_post; T.ns_coarsest = ns_coarsest; T.linear = linear;
+  T.dM = dM; T.dn = dn;
   // one lane per column of the largest colour pass, whole waves, the instance's lanes at the most (the strided loops take the rest)
   const int cols = T.L[0].nx * (T.L[0].ny / 2);
   bool big = false;
   for (int l = 0; l < nl; l++) big = big || T.L[l].nz == 16 || T.L[l].nz == 32;
-  if (big) launch_tail<32, MIXED_TAIL_LANES_B>(st, T, cols, real, rb);
-  else launch_tail<8, MIXED_TAIL_LANES_A>(st, T, cols, real, rb);
+  if (big) { if (dM) launch_tail<32, MIXED_TAIL_LANES_B, true>(st, T, cols, real, rb); else launch_tail<32, MIXED_TAIL_LANES_B, false>(st, T, cols, real, rb); }
+  else { if (dM) launch_tail<8, MIXED_TAIL_LANES_A, true>(st, T, cols, real, rb); else launch_tail<8, MIXED_TAIL_LANES_A, false>(st, T, cols, real, rb); }
   return 1;
 }
 int mgxx_tail_max_levels(void) { return MIXED_TAIL_MAX_LEVELS; }
+// cells of the coarsest level nx x ny x nz of a hierarchy of nlevs levels that the product of option "mixed_direct" serves, 0 = the sweeps
+// (any: option "small_any_nz"): mgx_mixed_direct_cells, and the launch below is made by the same function
+int mgxx_direct32_cells(int nx, int ny, int nz, int nlevs, int any) {
+  const LevShape s = {nx, ny, nz, false, false, false, false, 0};
+  return choose_mixed_direct_cells(s, nlevs, any);
+}
+// M (n * n floats) = M64 rounded
+void mgxx_direct32_round(hipStream_t st, const double *M64, float *M, int n) {
+  const long long nn = (long long)n * n;
+  hipLaunchKernelGGL(k_direct32_round, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, M64, M, nn);
+}
+// e = M f on the coarsest level L of a hierarchy of nlevs levels, with the images of e; returns 0, nothing launched, where the level is not served
+int mgxx_coarse_direct32(hipStream_t st, const LevView32 *L, const float *M, int nlevs, int any) {
+  const Choice c = choose_coarse_direct32(lev_shape32(L), nlevs, any);
+  if (c.family != KF_DIRECT32) return 0;
+  hipLaunchKernelGGL(k_coarse_direct32, dim3(c.grid), dim3(c.bx), 0, st, *L, M, c.nt);
+  return c.ret;
+}
 void mgxx_to32(hipStream_t st, const LevView *D, const LevView32 *S, const double *src, float *dst, double scale) {
   hipLaunchKernelGGL(k_to32, whole_grid(D->ny, D->nx), dim3(WAVE, 4), 0, st, *D, *S, src, dst, scale);
 }

@@ -156,8 +156,11 @@ void mgxx_restrict(hipStream_t st, const LevView32 *F, const LevView32 *C, const
 void mgxx_coarse2fine(hipStream_t st, const LevView32 *F, const LevView32 *C, int linear);
 enum { TAIL_RELAX = 0, TAIL_VCYCLE = 1, TAIL_FCYCLE = 2 };   // what one launch of the tail kernel runs: mode of mgxx_tail
 int mgxx_tail(hipStream_t st, const LevView32 *const *levs, int nl, int mode, int lead, int n, int ns_pre, int ns_post, int ns_coarsest, int rb,
-              int real, int linear);
+              int real, int linear, const float *dM, int dn);
 int mgxx_tail_max_levels(void);
+int mgxx_direct32_cells(int nx, int ny, int nz, int nlevs, int any);
+void mgxx_direct32_round(hipStream_t st, const double *M64, float *M, int n);
+int mgxx_coarse_direct32(hipStream_t st, const LevView32 *L, const float *M, int nlevs, int any);
 void mgxx_to32(hipStream_t st, const LevView *D, const LevView32 *S, const double *src, float *dst, double scale);
 void mgxx_to64(hipStream_t st, const LevView *D, const LevView32 *S, const float *src, double *dst, double scale, int add);
 

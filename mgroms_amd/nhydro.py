@@ -275,7 +275,7 @@ def nlevs():
 
 def mixed_op(op, lev, n=1):
     """one fp32 operator of the mixed-precision cycle (option "cycle_precision" = 32) on level lev's fp64 fields, converted in and
-    back: "relax" (n sweeps), "residual", "fine2coarse", "coarse2fine", "resrest", "vcycle" (include/mgx.h: mgx_mixed_op)."""
+    back: "relax" (n sweeps), "coarsest" (the coarsest solve of a cycle, lev = nlevs), "residual", "fine2coarse", "coarse2fine", "resrest", "vcycle" (include/mgx.h: mgx_mixed_op)."""
     check(lib().mgx_mixed_op(op.encode(), int(lev), int(n)))
 
 
@@ -302,6 +302,15 @@ def mixed_ring_choice(nx, ny, nz, nplanes):
     out = (C.c_int * 6)()
     check(lib().mgx_mixed_ring_choice(int(nx), int(ny), int(nz), int(nplanes), out))
     return dict(zip(("served", "depth", "planes_per_workgroup", "stream", "workgroups", "instance_nz"), out))
+
+
+def mixed_direct_cells(nx, ny, nz, small_any_nz=0):
+    """cells of the coarsest level of the one-rank hierarchy of nx x ny x nz where option "mixed_direct" serves the coarsest solve of an fp32
+    cycle as one product (nz = 2 or 4, or 3 with small_any_nz; even nx, ny; at most 2048 cells; at least two levels), 0 = the sweeps.  Pure
+    host logic (include/mgx.h: mgx_mixed_direct_cells)."""
+    cells = C.c_int()
+    check(lib().mgx_mixed_direct_cells(int(nx), int(ny), int(nz), int(small_any_nz), C.byref(cells)))
+    return cells.value
 
 
 def krylov_op(op, fields, nd=0, slot=None, sin=(), nout=2):
