@@ -87,6 +87,14 @@ module mgx_c
        character(kind=c_char), intent(in) :: name(*)
        integer(c_int), value :: value
      end function mgx_set_option
+     ! a value for option "hold_z_levels" from the block's geometry: dx, dy, h as handed to nhydro_matrices, (0:ny+1,0:nx+1).  Host logic;
+     ! on a process grid set the MAXIMUM of m over the ranks (include/mgx.h)
+     integer(c_int) function mgx_hold_z_hint(dx, dy, h, nx, ny, nz, m) bind(C, name='mgx_hold_z_hint')
+       import :: c_int, c_double
+       real(c_double), intent(in) :: dx(*), dy(*), h(*)
+       integer(c_int), value :: nx, ny, nz
+       integer(c_int), intent(out) :: m
+     end function mgx_hold_z_hint
      integer(c_int) function mgx_level_info(lev, info) bind(C, name='mgx_level_info')
        import :: c_int
        integer(c_int), value :: lev

@@ -59,7 +59,8 @@ int mgx_read_namelist(const char *path, mgx_params *p);
  * rank: this process's rank, placed at pi=mod(rank,npx), pj=rank/npx (mg_grids.f90:593-594).
  * par == NULL: read ./nh_namelist if present, else defaults (what the reference does).
  * nx, ny, nz must be even; nz need not be a power of two.  Coarser levels halve nz as the reference does (an odd level drops its
- * top row on restriction, mg_intergrids.f90:149-160).  Level-1 colour pass: a register-resident kernel for nz in {2, 4, 8, 12, 16,
+ * top row on restriction, mg_intergrids.f90:149-160), unless option "hold_odd_nz" holds an odd nz or option "hold_z_levels" = m holds nz on
+ * the first m coarsenings (both read here, both off by default).  Level-1 colour pass: a register-resident kernel for nz in {2, 4, 8, 12, 16,
  * 20, 24, 32, 40, 48, 64}; a tall-column kernel for nz in {80, 96, 128}, in its matrix-free form when the matrix came from
  * define_matrices without bmask and on the stored coefficients otherwise (bmask, mgx_set_field(cA), MGX_NO_MF; the read-only option
  * "tall_stored_passes" counts the colour passes served that way since mgx_init); every other nz runs the generic kernel plus a
@@ -184,6 +185,17 @@ int mgx_level_table_periodic(int nx, int ny, int nz, int npx, int npy, int rank,
  * l + 1 exists iff l < nl1 (the horizontal bound of find_grid_levels) and nz_l != 2, with nz_{l+1} = nz_l / 2 for an even nz_l and nz_l for an odd
  * one; nx, ny and the gathers are those of hold = 0.  hold = 0 is mgx_level_table_periodic.  Host only. */
 int mgx_level_table_hold(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int hold, int maxlev, int *out);
+/* The same with option "hold_z_levels" (hold_z = m, 0..8) as an argument too.  The first m coarsenings (levels 1 -> 2 ... m -> m + 1) keep nz and
+ * halve nx, ny; from level m + 1 on the rule of `hold` applies unchanged.  nx, ny and the gathers are those of the reference's table.  With
+ * hold = 0 the table has min(nl1, m + nl2) levels (nl1, nl2: the horizontal and the vertical bound of find_grid_levels); an m above nl1 - 1
+ * holds every pair.  hold_z = 0 is mgx_level_table_hold.  Host only. */
+int mgx_level_table_semi(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int hold, int hold_z, int maxlev, int *out);
+/* A value for option "hold_z_levels" from the geometry of a rank's block: *m = the smallest m in 0..8 with
+ * 2^m * min(dx, dy) >= max(h) / nz, both extrema over the interior (i = 1..nx, j = 1..ny) -- the coarsenings in x and y after which the cells
+ * are no longer taller than wide.  dx, dy, h: HOST arrays in the layout of mgx_matrices, (0:ny+1, 0:nx+1) with j fastest.  Pure host logic,
+ * usable before mgx_init and without a GPU.  On a process grid every rank must build the same hierarchy: the caller takes the MAXIMUM of *m
+ * over the ranks and sets that.  Returns 0, or non-zero (mgx_last_error) for NULL arguments and a geometry that is not positive and finite. */
+int mgx_hold_z_hint(const double *dx, const double *dy, const double *h, int nx, int ny, int nz, int *m);
 /* The first level of the tail of an fp32 cycle (option "mixed_tail") on the one-rank hierarchy of nx x ny x nz: *first = the finest level from
  * which every level down to the coarsest has at most 32768 cells and nz <= 32, 0 = no level is that small.  Pure host logic, usable before
  * mgx_init and without a GPU.  Returns 0, or non-zero (mgx_last_error) for sizes that make no hierarchy. */
@@ -427,6 +439,26 @@ int mgx_set_verbose(int level);
  *   stay refused.  Served: relax_method 'FC', 'RB' in its modes and 'GS', "krylov" with fp64 cycles, bmask, "periodic", process grids, the device
  *   entry points.  Refused at the solve where the hierarchy has a held pair: "cycle_precision" = 32, "krylov_precision" = 32 and with them
  *   "mixed_tail" (the transfers of the fp32 copies halve nz).  mgx_mixed_tail_first keeps describing the hierarchy of hold_odd_nz = 0.
+ * "hold_z_levels" (default 0, or m = 1..8; any other value is refused; survives mgx_clean; no environment variable): semi-coarsening at the
+ *   fine end.  The first m coarsenings (levels 1 -> 2 ... m -> m + 1) keep nz and halve nx, ny; from level m + 1 on the hierarchy is built as
+ *   without the option -- the reference's halving, or the rule of "hold_odd_nz" where that is set (mgx_level_table_semi).  For cells that are
+ *   taller than wide (the seamount at 128 x 128 x 16: dx = 78 m against dz = 250 m), where the z-line smoother leaves the horizontally
+ *   oscillatory error alone and full coarsening never repairs the aspect ratio: mgx_hold_z_hint names the m after which the cells are no
+ *   longer taller than wide (DESIGN.md 7.1.1 has the iteration counts).  Read by mgx_init: set it BEFORE mgx_init; while a solver is
+ *   initialised a different value is refused (mgx_clean, set, mgx_init).  0 = every table, kernel, launch count and bit as without the option.
+ *   The held pairs are those of "hold_odd_nz" and are served as there: the reference's 2-D transfers row by row (mgx_hold.hip), the one-launch
+ *   restriction chain ends above a held pair and may serve the halving pairs below the last one, the transfers folded into a relax ("fuse_tail")
+ *   decline it.  New here: the down leg of a held pair with an even nz (residual + 2-D restriction) and the closing residual of a solve_p
+ *   iteration ("fuse_closing") on a held pair of levels 1 and 2 are ONE kernel that never writes r, with the bits of the two launches
+ *   (mgx_resrest_held.hip): matrix-free where the level has its slopes, on the stored slots otherwise (bmask, a matrix set through
+ *   mgx_set_field); with "keep_r", "exact_halos", "hold_z_fuse" = 0 or MGX_NO_RESREST the two launches stay, as they do on a pair with an odd nz.  Served: relax_method 'FC', 'RB' in its modes and 'GS', "krylov" with fp64
+ *   cycles, bmask and the per-call mask, "periodic", process grids, "hold_odd_nz", the device entry points (the 2-D zeta chain of
+ *   mgx_update_zeta_device does not depend on nz), the _f32 state entries.  Refused at the solve, in the words of "hold_odd_nz": the fp32
+ *   cycles.  A held level 2 has a quarter of level 1's cells instead of an eighth: a cycle costs more (profiles/hold_z_time.json).
+ *   Read-only: "hold_z_fused" (down legs and closing residuals of held pairs served by the fused kernel since mgx_init).
+ * "hold_z_fuse" (default 1, or 0; any other value is refused; survives mgx_clean; no environment variable; may be set at any time): A/B of the
+ *   one-kernel down leg of a held pair.  0 = compute_residual and the 2-D restriction stay two launches on every held pair, and the closing
+ *   residual of a solve_p iteration on a held pair of levels 1 and 2 is not fused either; the same bits (scripts/hold_z_time.py times both).
  * Read-only through mgx_get_option: "p2p_failed" (a peer-to-peer wait of THIS rank timed out since the ranks last agreed: see below),
  *   "overlapped_passes", "tall_stored_passes" (colour passes of nz = 80, 96, 128 levels served by the stored-coefficient tall-column kernel
  *   since mgx_init: bmask, mgx_set_field(cA) or MGX_NO_MF; 0 while the matrix-free form runs or under MGX_NO_TALL). */

@@ -62,6 +62,8 @@ _SIGS = {
     "mgx_level_table": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int)]),
     "mgx_level_table_periodic": (C.c_int, [C.c_int] * 9 + [C.POINTER(C.c_int)]),
     "mgx_level_table_hold": (C.c_int, [C.c_int] * 10 + [C.POINTER(C.c_int)]),
+    "mgx_level_table_semi": (C.c_int, [C.c_int] * 11 + [C.POINTER(C.c_int)]),
+    "mgx_hold_z_hint": (C.c_int, [_DP, _DP, _DP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "mgx_mixed_tail_first": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "mgx_mixed_ring_levels": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "mgx_mixed_ring_choice": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),

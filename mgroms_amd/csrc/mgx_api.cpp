@@ -79,6 +79,8 @@ const Opt OPTIONS[] = {
   {"small_any_nz",        &State::small_any_nz,     nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0 / 1 only
   {"periodic",            &State::periodic,         nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0..3 only, and not while initialised (read by mgx_init)
   {"hold_odd_nz",         &State::hold_odd_nz,      nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0 / 1 only, and not while initialised (read by mgx_init)
+  {"hold_z_levels",       &State::hold_z_levels,    nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0..8 only, and not while initialised (read by mgx_init)
+  {"hold_z_fuse",         &State::hold_z_fuse,      nullptr,       nullptr,                   ENV_NONE, RW, true},   // set: 0 / 1 only
   // reads as off while a time-out of this solver holds (ksp_down, which mgx_clean does not carry); set: see mgx_set_option
   {"ksp",                 &State::use_ksp,          [](const State &s) { return (s.use_ksp && !s.ksp_down) ? 1 : 0; }, "MGX_NO_KSP", ENV_ZERO, RW, true},
   {"p2p",                 nullptr,                  [](const State &s) { return s.p2p_on ? 1 : 0; }, nullptr, ENV_NONE, RW, false},   // set: see mgx_set_option
@@ -100,6 +102,7 @@ const Opt OPTIONS[] = {
   {"p2p_failed", nullptr, CNT(p2p_failed), nullptr, ENV_NONE, RO, false},
   {"zeta_refreshes", nullptr, CNT(n_zeta_refresh), nullptr, ENV_NONE, RO, false},
   {"zeta_chain_launches", nullptr, CNT(n_zeta_chain), nullptr, ENV_NONE, RO, false},
+  {"hold_z_fused", nullptr, CNT(n_hold_z_fused), nullptr, ENV_NONE, RO, false},
 };
 #undef PAR
 #undef CNT
@@ -429,13 +432,13 @@ int mgx_testgalerkin(int lev, double *norm_c, double *norm_f) {
   return 0;
 }
 
-static int level_table(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int hold, int maxlev, int *out) {
-  if (nx < 2 || ny < 2 || nz < 2 || npx < 1 || npy < 1 || rank < 0 || rank >= npx * npy || periodic < 0 || periodic > 3 || hold < 0 || hold > 1) return -1;
-  const int nl = find_grid_levels(npx, npy, nx, ny, nz, hold);
+static int level_table(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int hold, int hold_z, int maxlev, int *out) {
+  if (nx < 2 || ny < 2 || nz < 2 || npx < 1 || npy < 1 || rank < 0 || rank >= npx * npy || periodic < 0 || periodic > 3 || hold < 0 || hold > 1 || hold_z < 0 || hold_z > 8) return -1;
+  const int nl = find_grid_levels(npx, npy, nx, ny, nz, hold, hold_z);
   if (nl < 1 || nl > maxlev) return -1;
   std::vector<Level> T(nl);
   T[0].nx = nx; T[0].ny = ny; T[0].nz = nz;
-  rank_level_table(rank, T, npx, npy, nsmall, periodic, hold);
+  rank_level_table(rank, T, npx, npy, nsmall, periodic, hold, hold_z);
   for (int l = 0; l < nl; l++) {
     const Level &L = T[l];
     const int v[12] = {L.nx, L.ny, L.nz, L.npx, L.npy, L.incx, L.incy, L.gather, L.ngx, L.ngy, L.key, L.color};
@@ -444,13 +447,34 @@ static int level_table(int nx, int ny, int nz, int npx, int npy, int rank, int n
   return nl;
 }
 int mgx_level_table(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int maxlev, int *out) {
-  return level_table(nx, ny, nz, npx, npy, rank, nsmall, 0, 0, maxlev, out);
+  return level_table(nx, ny, nz, npx, npy, rank, nsmall, 0, 0, 0, maxlev, out);
 }
 int mgx_level_table_periodic(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int maxlev, int *out) {
-  return level_table(nx, ny, nz, npx, npy, rank, nsmall, periodic, 0, maxlev, out);
+  return level_table(nx, ny, nz, npx, npy, rank, nsmall, periodic, 0, 0, maxlev, out);
 }
 int mgx_level_table_hold(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int hold, int maxlev, int *out) {
-  return level_table(nx, ny, nz, npx, npy, rank, nsmall, periodic, hold, maxlev, out);
+  return level_table(nx, ny, nz, npx, npy, rank, nsmall, periodic, hold, 0, maxlev, out);
+}
+int mgx_level_table_semi(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int hold, int hold_z, int maxlev, int *out) {
+  return level_table(nx, ny, nz, npx, npy, rank, nsmall, periodic, hold, hold_z, maxlev, out);
+}
+// the m of option "hold_z_levels" that squares the cells of a rank's block: the smallest m in 0..8 with 2^m min(dx, dy) >= max(h) / nz over the interior
+int mgx_hold_z_hint(const double *dx, const double *dy, const double *h, int nx, int ny, int nz, int *m) {
+  if (!dx || !dy || !h || !m) return fail("mgx_hold_z_hint: dx, dy, h or m is NULL");
+  if (nx < 1 || ny < 1 || nz < 1) return fail("mgx_hold_z_hint: %d x %d x %d is not a level-1 size", nx, ny, nz);
+  double dmin = 0.0, hmax = 0.0;
+  for (int i = 1; i <= nx; i++)
+    for (int j = 1; j <= ny; j++) {
+      const size_t q = (size_t)i * (ny + 2) + j;   // (0:ny+1, 0:nx+1), j fastest
+      const double d = dx[q] < dy[q] ? dx[q] : dy[q];
+      if ((i == 1 && j == 1) || d < dmin) dmin = d;
+      if ((i == 1 && j == 1) || h[q] > hmax) hmax = h[q];
+    }
+  if (!(dmin > 0.0) || !(hmax > 0.0) || !std::isfinite(dmin) || !std::isfinite(hmax)) return fail("mgx_hold_z_hint: dx, dy and h must be positive and finite over the interior (min(dx, dy) = %g, max(h) = %g)", dmin, hmax);
+  int q = 0;
+  while (q < 8 && ldexp(dmin, q) < hmax / nz) q++;
+  *m = q;
+  return 0;
 }
 // the first level of the tail of an fp32 cycle (option "mixed_tail") on a one-rank hierarchy, 0 = no level is small
 int mgx_mixed_tail_first(int nx, int ny, int nz, int *first) {
@@ -527,6 +551,12 @@ int mgx_set_option(const char *name, int value) {
     if (value != 0 && value != 1) return fail("hold_odd_nz must be 0 (every level halves nz, the reference's hierarchy) or 1 (an odd nz is held on the coarser levels), got %d", value);
     if (S.inited && value != S.hold_odd_nz)
       return fail("hold_odd_nz = %d: the hierarchy in use was built with hold_odd_nz = %d and the option takes effect at mgx_init: call mgx_clean, set it, then mgx_init", value, S.hold_odd_nz);
+  }
+  if (streq(name, "hold_z_fuse") && value != 0 && value != 1) return fail("hold_z_fuse must be 1 (the down leg of a held pair as one kernel) or 0 (compute_residual and the 2-D restriction as two launches), got %d", value);
+  if (streq(name, "hold_z_levels")) {
+    if (value < 0 || value > 8) return fail("hold_z_levels must be 0 (every coarsening halves nz, the reference's hierarchy) or m = 1..8 (the first m coarsenings keep nz), got %d", value);
+    if (S.inited && value != S.hold_z_levels)
+      return fail("hold_z_levels = %d: the hierarchy in use was built with hold_z_levels = %d and the option takes effect at mgx_init: call mgx_clean, set it, then mgx_init", value, S.hold_z_levels);
   }
   if (streq(name, "ksp")) { S.use_ksp = value; if (value) S.ksp_down = 0; return 0; }  // switching it on again also clears a time-out of this solver
   if (streq(name, "rbseq_timeout_ms")) { if (mgxk_set_rbseq_timeout((double)value)) return fail("rbseq_timeout_ms: could not set the device constant"); return 0; }

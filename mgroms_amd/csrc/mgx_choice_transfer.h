@@ -1,5 +1,5 @@
 // Which launch serves a level outside the smoother: the operator of a level (mgx_residual.hip, pass 1 of mgx_krylov.hip) and the streaming
-// Krylov passes, the transfers (mgx_transfer.hip, mgx_hold.hip), the halo and gather transport (mgx_halo.hip), the slot conversion
+// Krylov passes, the transfers (mgx_transfer.hip, mgx_hold.hip, mgx_resrest_held.hip), the halo and gather transport (mgx_halo.hip), the slot conversion
 // (mgx_layout.hip) and the runs of the model kernels (mgx_model.hip).  Pure host functions by the rules of mgx_choice.h, which includes this
 // file: no HIP call, no state, no environment; a small result struct per group; tests/test_kernel_choice_host.py pins every answer.
 #pragma once
@@ -63,6 +63,23 @@ static inline C2fChoice choose_coarse2fine_held(const LevShape &F, const LevShap
   c.run = linear != 0; c.wr = keep_r != 0; c.sk = ch_skip_first_colour(F, keep_r, skip1); c.kc = 0; c.nt = 0;
   c.gx = (C.ny + CH_WAVE - 1) / CH_WAVE; c.gy = (C.nz + 3) / 4; c.gz = C.nx; c.by = 4;
   return c;
+}
+// mgxk_residual_restrict_held (mgx_resrest_held.hip: k_residual_restrict_held): the down leg of a held pair (C.nz == F.nz, C half of F in x
+// and y) as one kernel that never writes r.  The operator is the fine level's own (choose_operator_mf: matrix-free with its slopes, the stored
+// slots otherwise -- bmask, a user matrix, MGX_NO_MF); a wave holds the four fine columns of 16 coarse columns, a workgroup four coarse
+// planes: gx * gy workgroups, which are also the norm's pairs of partials.  Declined: an odd nz (the pairs of "hold_odd_nz" keep their two
+// launches, to the count), MGX_NO_RESREST and fewer than MGX_RESREST_MIN fine cells (the A/B switches of the halving pairs' fused kernel).
+// grid is filled in either way: mgx_init sizes the partials by it.
+constexpr int CH_HELD_COLS = 16;   // coarse columns per wave: CH_WAVE / 4
+struct HeldRrChoice { bool served, mf, real, norm; unsigned gx, gy, grid; int stream; };
+static inline HeldRrChoice choose_resrest_held(const LevShape &f, const LevShape &c, int real, bool want_norm, const Switches &sw) {
+  HeldRrChoice r;
+  r.mf = choose_operator_mf(f); r.real = real != 0; r.norm = want_norm;
+  r.gx = (c.ny + CH_HELD_COLS - 1) / CH_HELD_COLS; r.gy = (c.nx + 3) / 4; r.grid = r.gx * r.gy;
+  r.stream = r.mf && ch_beyond_cache(f);
+  r.served = !sw.no_resrest && c.nz == f.nz && f.nz >= 2 && !(f.nz & 1) && c.nx * 2 == f.nx && c.ny * 2 == f.ny && c.nx >= 1 && c.ny >= 1 &&
+             (long long)f.nx * f.ny * f.nz >= sw.resrest_min;
+  return r;
 }
 // mgxk_fine2coarse: grid.z runs of kc coarse levels -- enough waves (8192) to hide the latency of the eight loads of a level
 struct F2cChoice { int kc; unsigned gx, gy, gz; int stream; };

@@ -228,7 +228,8 @@ int fine2coarse(int lev, bool dup_r, bool with_residual) {
   Level &F = S.lev[lev - 1], &C = S.lev[lev];
   const Sides phc = sides_of(C), none = {0, 0, 0, 0};
   bool fused = false;
-  // a held pair (option "hold_odd_nz": C.nz == F.nz): the 2-D restriction row by row (mgx_hold.hip), behind the residual as a launch of its own
+  // a held pair (options "hold_odd_nz", "hold_z_levels": C.nz == F.nz): the 2-D restriction row by row (mgx_hold.hip), behind the residual as a
+  // launch of its own unless the fused kernel has an instance for the pair (down)
   const bool held = held_pair(F, C);
   auto restrict = [&](const LevView *Cv, double *dst, Sides ph, double *dup, double *zero) {
     if (held) mgxk_fine2coarse_held(S.stream, &F.v, Cv, dst, ph, dup, zero); else mgxk_fine2coarse(S.stream, &F.v, Cv, dst, ph, dup, zero);
@@ -237,9 +238,11 @@ int fine2coarse(int lev, bool dup_r, bool with_residual) {
   // returns true when the fused residual+restriction kernel took the job
   auto down = [&](const LevView *Cv, double *dst, Sides ph, double *zero) -> int {
     if (!with_residual) return 0;
-    if (!held && !S.exact_halos && !S.keep_r && !dup_r) {  // keep_r: the caller wants the reference's r, which the fused kernel never writes
+    if (!S.exact_halos && !S.keep_r && !dup_r) {  // keep_r: the caller wants the reference's r, which the fused kernel never writes
       TicScope ts(lev, "residual_3D_8");
-      if (mgxk_residual_restrict(S.stream, &F.v, Cv, dst, S.real, ph, zero)) { S.n_launch++; return 1; }
+      // (a held pair with an even nz -- option "hold_z_levels" -- has a kernel of its own, mgx_resrest_held.hip; one with an odd nz keeps the two launches)
+      if (held) { if (S.hold_z_fuse && mgxk_residual_restrict_held(S.stream, &F.v, Cv, dst, S.real, ph, zero, nullptr, nullptr)) { S.n_launch++; S.n_hold_z_fused++; return 1; } }
+      else if (mgxk_residual_restrict(S.stream, &F.v, Cv, dst, S.real, ph, zero)) { S.n_launch++; return 1; }
     }
     return residual(lev, nullptr) ? -1 : 0;
   };
@@ -439,11 +442,15 @@ int fcycle(int have_r2) {
 int residual_closing(double *res) {
   if (!S.fuse_closing || S.nlevs < 2 || S.exact_halos || S.keep_r || S.tictoc) return 0;
   Level &F = S.lev[0], &C = S.lev[1];
-  if (C.gather) return 0;
-  const int np = mgxk_residual_restrict_grid(&F.v, &C.v);
+  if (C.gather || (held_pair(F, C) && !S.hold_z_fuse)) return 0;
+  // (levels 1 and 2 are a held pair under option "hold_z_levels": the same pass by the held pair's kernel, mgx_resrest_held.hip)
+  const bool held = held_pair(F, C);
+  const int np = held ? mgxk_residual_restrict_held_grid(&F.v, &C.v) : mgxk_residual_restrict_grid(&F.v, &C.v);
   if (np > S.npartial) return 0;
   const Sides phc = sides_of(C);
-  if (!mgxk_residual_restrict_ex(S.stream, &F.v, &C.v, C.v.r, S.real, phc, nullptr, S.d_partial, nullptr)) return 0;
+  if (!(held ? mgxk_residual_restrict_held(S.stream, &F.v, &C.v, C.v.r, S.real, phc, nullptr, S.d_partial, nullptr)
+             : mgxk_residual_restrict_ex(S.stream, &F.v, &C.v, C.v.r, S.real, phc, nullptr, S.d_partial, nullptr))) return 0;
+  if (held) S.n_hold_z_fused++;
   mgxk_reduce(S.stream, S.d_partial, np, S.d_scalar); S.n_launch += 2;
   C.r_halo_stale = true;
   double s;

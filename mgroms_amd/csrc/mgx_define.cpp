@@ -26,16 +26,18 @@ void make_view(LevView &v, int nx, int ny, int nz) {
 // ---- mg_grids.f90:468-738 -------------------------------------------------------------------------
 // hold (option "hold_odd_nz"): level l + 1 exists iff l < nl1 and nz_l != 2, with nz_{l+1} = nz_l / 2 for an even nz_l and nz_l for an odd one --
 // for a size whose nz stays even down to 2 that is the reference's count
-int find_grid_levels(int npxg, int npyg, int nx, int ny, int nz, int hold) {
+// hold_z (option "hold_z_levels" = m): the first m coarsenings (levels 1 -> 2 ... m -> m + 1) keep nz, whatever it is, and the rule above --
+// the reference's or hold's -- applies from level m + 1 on: min(nl1, m + nl2) levels without hold; an m above nl1 - 1 holds every pair
+int find_grid_levels(int npxg, int npyg, int nx, int ny, int nz, int hold, int hold_z) {
   const int nxg = npxg * nx, nyg = npyg * ny, nzg = nz, ncoarsest = 4, nzmin = 2;
   const int nhoriz = nxg < nyg ? nxg : nyg;
   const int nl1 = 1 + (int)floor(log(nhoriz * 1.0 / ncoarsest * 1.0) / log(2.0));
   if (hold) {
     int l = 1;
-    for (int z = nzg; l < nl1 && z != nzmin; l++) z = (z & 1) ? z : z / 2;
+    for (int z = nzg; l < nl1 && (l <= hold_z || z != nzmin); l++) z = (l <= hold_z || (z & 1)) ? z : z / 2;
     return l;
   }
-  const int nl2 = 1 + (int)floor(log(nzg * 1.0 / nzmin * 1.0) / log(2.0));
+  const int nl2 = hold_z + 1 + (int)floor(log(nzg * 1.0 / nzmin * 1.0) / log(2.0));
   return nl1 < nl2 ? nl1 : nl2;
 }
 
@@ -44,13 +46,14 @@ int find_grid_levels(int npxg, int npyg, int nx, int ny, int nz, int hold) {
 // row -- the rank's own column on a level with one rank along i -- and likewise in j; a corner exists exactly where both of its steps resolve, so
 // between a periodic and a closed side it is absent (the mixed-corner rule of the halo fills then takes the closed side's image of the wrapped edge)
 // hold (option "hold_odd_nz"): an odd nz is handed on unchanged; nx, ny and the gathers are what they are without it
-void rank_level_table(int rank, std::vector<Level> &T, int npx0, int npy0, int nsmall, int periodic, int hold) {
+// hold_z (option "hold_z_levels"): so do levels 1 .. hold_z, whatever their nz (semi-coarsening at the fine end)
+void rank_level_table(int rank, std::vector<Level> &T, int npx0, int npy0, int nsmall, int periodic, int hold, int hold_z) {
   const int pi = rank % npx0, pj = rank / npx0;
   int nx = T[0].nx, ny = T[0].ny, nz = T[0].nz, npx = npx0, npy = npy0, incx = 1, incy = 1;
   T[0].npx = npx; T[0].npy = npy; T[0].incx = 1; T[0].incy = 1; T[0].gather = 0; T[0].ngx = 1; T[0].ngy = 1; T[0].key = 0; T[0].color = 0;
   for (int l = 1; l < (int)T.size(); l++) {  // define_grid_dims :503-577
     Level &L = T[l];
-    if (nz == 1 || (hold && (nz & 1))) { nx /= 2; ny /= 2; } else { nx /= 2; ny /= 2; nz /= 2; }
+    if (nz == 1 || (hold && (nz & 1)) || l <= hold_z) { nx /= 2; ny /= 2; } else { nx /= 2; ny /= 2; nz /= 2; }
     L.gather = 0; L.ngx = 1; L.ngy = 1; L.key = 0; L.color = 0;
     if (((nx < ny ? nx : ny) < nsmall) && (npx * npy > 1)) {
       L.gather = 1;
@@ -391,11 +394,11 @@ int mgx_init(int nx, int ny, int nz, int npx, int npy, int rank, const mgx_param
   if (S.periodic && npx * npy > 1 && !S.ex)
     return fail("option \"periodic\" = %d needs a single rank (process grid %d x %d) or connected ranks: install the hooks (mgx_set_comm, mgx_rccl_connect) before mgx_init", S.periodic, npx, npy);
   S.npx = npx; S.npy = npy; S.nranks = npx * npy; S.rank = rank; S.pi = rank % npx; S.pj = rank / npx;
-  S.nlevs = find_grid_levels(npx, npy, nx, ny, nz, S.hold_odd_nz);
+  S.nlevs = find_grid_levels(npx, npy, nx, ny, nz, S.hold_odd_nz, S.hold_z_levels);
   if (S.nlevs < 1) return fail("grid %dx%dx%d too small for a multigrid hierarchy", nx * npx, ny * npy, nz);
   S.lev.assign(S.nlevs, Level());
   S.lev[0].nx = nx; S.lev[0].ny = ny; S.lev[0].nz = nz;
-  rank_level_table(rank, S.lev, npx, npy, S.par.nsmall, S.periodic, S.hold_odd_nz);
+  rank_level_table(rank, S.lev, npx, npy, S.par.nsmall, S.periodic, S.hold_odd_nz, S.hold_z_levels);
   for (int l = 0; l < S.nlevs; l++) {
     const Level &L = S.lev[l];
     if ((L.nx & 1) || (L.ny & 1) || L.nz < 2) return fail("level %d has local size %dx%dx%d: odd sizes are not supported (assumptions:1-2)", l + 1, L.nx, L.ny, L.nz);
@@ -408,7 +411,7 @@ int mgx_init(int nx, int ny, int nz, int npx, int npy, int rank, const mgx_param
     for (int r = 0; r < S.nranks; r++) {
       std::vector<Level> T(S.nlevs);
       T[0].nx = nx; T[0].ny = ny; T[0].nz = nz;
-      rank_level_table(r, T, npx, npy, S.par.nsmall, 0, S.hold_odd_nz);
+      rank_level_table(r, T, npx, npy, S.par.nsmall, 0, S.hold_odd_nz, S.hold_z_levels);
       if (T[l].color == L.color) mem.push_back({T[l].key, r});
     }
     std::sort(mem.begin(), mem.end());
@@ -468,7 +471,10 @@ int mgx_init(int nx, int ny, int nz, int npx, int npy, int rank, const mgx_param
       for (int q = 0; q < 4; q++) CHK(dmalloc(&L.tmp2[q], (size_t)(nyc + 2) * (nxc + 2)));
     }
     size_t np = (size_t)mgxk_residual_nblocks(&L.v);
-    if (l == 1) { const size_t nf = (size_t)mgxk_residual_restrict_grid(&S.lev[0].v, &L.v); if (nf > np) np = nf; }  // the fused closing residual of solve_p
+    if (l == 1) {  // the fused closing residual of solve_p, of a halving or of a held pair
+      const size_t nf = (size_t)(held_pair(S.lev[0], L) ? mgxk_residual_restrict_held_grid(&S.lev[0].v, &L.v) : mgxk_residual_restrict_grid(&S.lev[0].v, &L.v));
+      if (nf > np) np = nf;
+    }
     if (np > max_part) max_part = np;
   }
   S.npartial = (int)max_part;

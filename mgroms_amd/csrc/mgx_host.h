@@ -59,7 +59,7 @@ struct Level {
   LevView32 v32 = {};           // fp32 shadow of the mixed-precision solve_p (allocated at the first mixed solve)
   size_t n3js32 = 0;            // floats in one of its JS arrays
 };
-inline bool held_pair(const Level &F, const Level &C) { return F.nz == C.nz; }   // option "hold_odd_nz": the pair coarsens in x and y only
+inline bool held_pair(const Level &F, const Level &C) { return F.nz == C.nz; }   // options "hold_odd_nz", "hold_z_levels": the pair coarsens in x and y only
 inline Sides sides_of(const Level &L) { return {L.neighb[0] < 0, L.neighb[1] < 0, L.neighb[2] < 0, L.neighb[3] < 0}; }
 
 struct TicRec { int lev, sub; hipEvent_t e0, e1; };
@@ -202,6 +202,14 @@ struct State {
   // and diverges.  The transfers of a held pair are the reference's 2-D operators row by row (mgx_hold.hip); every fast path that
   // assumes nz_c = nz_f / 2 declines such a pair.  0: the reference's table, word for word.
   int hold_odd_nz = 0;
+  // option "hold_z_levels" (0 default, m = 1..8): read by mgx_init.  Semi-coarsening at the FINE end: the first m coarsenings (levels 1 -> 2 ...
+  // m -> m + 1) keep nz and halve nx, ny -- held pairs like those of "hold_odd_nz", served by the same transfers -- and from level m + 1 on the
+  // rule without the option applies.  For cells taller than wide, where the z-line smoother leaves the horizontally oscillatory error alone
+  // (mgx_hold_z_hint names m).  The down leg of such a pair is one kernel that never writes r where the level has its slopes
+  // (k_residual_restrict*<HELD>, mgx_resrest.hip).  0: every table, kernel, launch count and bit as without the option.
+  int hold_z_levels = 0;
+  int hold_z_fuse = 1;   // option "hold_z_fuse" (A/B): 0 = the down leg of every held pair and the closing residual on one stay two launches; same bits
+  long long n_hold_z_fused = 0;   // read-only option "hold_z_fused": down legs and closing residuals of held pairs served by the fused kernel since mgx_init
   int c2f_skip = 1;   // the cycles' prolongation leaves the columns alone that the first colour of the following four-colour relax overwrites unread (option "c2f_skip", MGX_C2F_NOSKIP=1)
   long long n_launch = 0, n_halo = 0, n_exch = 0, n_allred = 0;
   std::string err, transport_name;
@@ -254,8 +262,8 @@ void options_restore(const std::vector<int> &);   // ... and back into the fresh
 int dmalloc(double **p, size_t n);
 int roundup(int a, int m);
 void make_view(LevView &v, int nx, int ny, int nz);
-int find_grid_levels(int npxg, int npyg, int nx, int ny, int nz, int hold = 0);
-void rank_level_table(int rank, std::vector<Level> &T, int npx0, int npy0, int nsmall, int periodic = 0, int hold = 0);
+int find_grid_levels(int npxg, int npyg, int nx, int ny, int nz, int hold = 0, int hold_z = 0);
+void rank_level_table(int rank, std::vector<Level> &T, int npx0, int npy0, int nsmall, int periodic = 0, int hold = 0, int hold_z = 0);
 void set_window_planes(bool known = true);
 enum { DM_ALL = 0, DM_ZETA = 1 };
 int define_matrices(int what = DM_ALL, bool may_return_early = false);

@@ -80,6 +80,11 @@ int mgxk_residual_restrict_ex(hipStream_t st, const LevView *F, const LevView *C
                               double *dup);
 int mgxk_residual_restrict(hipStream_t st, const LevView *F, const LevView *C, double *dst, int real, Sides ph, double *zero);
 
+// ---- mgx_resrest_held.hip ----
+int mgxk_residual_restrict_held_grid(const LevView *F, const LevView *C);
+int mgxk_residual_restrict_held(hipStream_t st, const LevView *F, const LevView *C, double *dst, int real, Sides ph, double *zero, double *partial,
+                                double *dup);
+
 // ---- mgx_residual.hip ----
 int mgxk_residual_nblocks(const LevView *L);
 void mgxk_residual(hipStream_t st, const LevView *L, double *partial, double *out, int real, int want_norm, Sides ph);

@@ -399,23 +399,41 @@ def _table(nl, out, what):
     return res
 
 
-def level_table(nx, ny, nz, npx=1, npy=1, rank=0, nsmall=8, hold_odd_nz=0):
+def level_table(nx, ny, nz, npx=1, npy=1, rank=0, nsmall=8, hold_odd_nz=0, hold_z_levels=0):
     """Level hierarchy of `rank` (mg_grids.f90:468-738) as a list of dicts; pure host logic, no GPU needed.
     hold_odd_nz=1: the table mgx_init builds under option "hold_odd_nz" -- an odd nz is handed on to the coarser levels, which go on
-    coarsening in x and y down to the horizontal bound (include/mgx.h: mgx_level_table_hold)."""
+    coarsening in x and y down to the horizontal bound (include/mgx.h: mgx_level_table_hold).
+    hold_z_levels=m: the table under option "hold_z_levels" -- the first m coarsenings keep nz (mgx_level_table_semi)."""
     out = (C.c_int * (20 * 32))()
+    if hold_z_levels:
+        return _table(lib().mgx_level_table_semi(nx, ny, nz, npx, npy, rank, nsmall, 0, int(hold_odd_nz), int(hold_z_levels), 32, out), out, "level_table")
     if hold_odd_nz:
         return _table(lib().mgx_level_table_hold(nx, ny, nz, npx, npy, rank, nsmall, 0, int(hold_odd_nz), 32, out), out, "level_table")
     return _table(lib().mgx_level_table(nx, ny, nz, npx, npy, rank, nsmall, 32, out), out, "level_table")
 
 
-def level_table_periodic(nx, ny, nz, npx=1, npy=1, rank=0, nsmall=8, periodic=0, hold_odd_nz=0):
+def level_table_periodic(nx, ny, nz, npx=1, npy=1, rank=0, nsmall=8, periodic=0, hold_odd_nz=0, hold_z_levels=0):
     """level_table with option "periodic" (bit 1: i, bit 2: j): the neighbour past the end of a periodic row or column of ranks is the rank
-    at its other end, the rank itself on a level with one rank along the direction; pure host logic.  hold_odd_nz: as in level_table."""
+    at its other end, the rank itself on a level with one rank along the direction; pure host logic.  hold_odd_nz, hold_z_levels: as in
+    level_table."""
     out = (C.c_int * (20 * 32))()
+    if hold_z_levels:
+        return _table(lib().mgx_level_table_semi(nx, ny, nz, npx, npy, rank, nsmall, periodic, int(hold_odd_nz), int(hold_z_levels), 32, out), out, "level_table_periodic")
     if hold_odd_nz:
         return _table(lib().mgx_level_table_hold(nx, ny, nz, npx, npy, rank, nsmall, periodic, int(hold_odd_nz), 32, out), out, "level_table_periodic")
     return _table(lib().mgx_level_table_periodic(nx, ny, nz, npx, npy, rank, nsmall, periodic, 32, out), out, "level_table_periodic")
+
+
+def hold_z_hint(dx, dy, h, nz):
+    """The m of option "hold_z_levels" that makes the cells of this block no taller than wide: the smallest m in 0..8 with
+    2^m * min(dx, dy) >= max(h) / nz over the interior.  dx, dy, h: (nx+2, ny+2) arrays as handed to nhydro_matrices.  Pure host logic; on a
+    process grid every rank must set the same option: take the maximum over the ranks (include/mgx.h: mgx_hold_z_hint)."""
+    dx = np.ascontiguousarray(dx, dtype=np.float64); dy = np.ascontiguousarray(dy, dtype=np.float64); h = np.ascontiguousarray(h, dtype=np.float64)
+    if dx.ndim != 2 or dx.shape != dy.shape or dx.shape != h.shape:
+        raise MgxError(f"hold_z_hint: dx, dy, h must be 2-D arrays of one shape, got {dx.shape}, {dy.shape}, {h.shape}")
+    m = C.c_int()
+    check(lib().mgx_hold_z_hint(_dp(dx), _dp(dy), _dp(h), dx.shape[0] - 2, dx.shape[1] - 2, int(nz), C.byref(m)))
+    return m.value
 
 
 def exchange_plan(neighb, rank):
