@@ -160,6 +160,30 @@ int mgx_fill_halo(int lev, int field);    /* generic fill_halo (mg_mpi_exchange.
  * prints norm_c, norm_f/4 and norm_c/norm_f*4).  The coarse field is grid(lev)%p as the caller set it (the reference draws
  * it with random_number); b of both levels is zeroed. */
 int mgx_testgalerkin(int lev, double *norm_c, double *norm_f);
+/* ---- the level operators and transfers as CSR matrices on the device (no Fortran counterpart; single rank) ----
+ * Index convention: the unknown of interior cell (k, j, i) of a level of nx x ny x nz has index ((i-1)*ny + (j-1))*nz + (k-1) -- the
+ * reference's k-fastest order, 0-based.  Halo cells are not unknowns.
+ * mgx_operator_csr: A of level lev with the sign of compute_residual, r = b - A p.  The level's halo rule is folded in: the image of a
+ *   closed side adds its coefficient to the entry of its interior source, a "periodic" wrap points at the cell one period away.  It is whatever
+ *   mgx_residual(lev) applies today: matrix-free or stored, bmask, a matrix set by mgx_set_field(lev, MGX_CA, ...), either cmatrix.
+ * mgx_transfer_csr, which = 0: R, nrows = the unknowns of lev + 1, ncols = those of lev -- what mgx_fine2coarse(lev) does to grid(lev)%r to
+ *   produce grid(lev+1)%b.  which = 1: P, nrows = the unknowns of lev, ncols = those of lev + 1 -- what mgx_coarse2fine(lev) adds to grid(lev)%p
+ *   from grid(lev+1)%p whose halo holds what mgx_fill_halo(lev + 1, MGX_P) puts there (as inside a cycle), under the live interp_type.  The held
+ *   pairs of "hold_odd_nz" / "hold_z_levels" are served.
+ * How: the library's own residual / fine2coarse / coarse2fine is applied to sums of unit vectors that no row can confuse (mgx_export.h) and the
+ *   entries are read off the result: every value is bit for bit the number the kernels use.  An export costs some dozens of operator
+ *   applications, three level-sized scratch fields and 8 bytes per row; nothing of it is kept.
+ * Output: rowptr (nrows + 1 ints), col and val (nnz each) are DEVICE pointers.  Rows are sorted by column, no column twice; entries whose
+ *   value is +-0 are dropped (a land row may be empty).  The *_size call reports the exact counts; the *_csr call must follow a *_size call for
+ *   the same matrix and refuses when the count has changed since.
+ * State: p, b, r of the level (for a transfer: of both levels), their halos and the deferred-halo state are left bit for bit as found;
+ *   mgx_counters may grow; nothing else is visible afterwards.  Both calls wait for the device.
+ * Refused: before mgx_matrices (or a mgx_set_field of cA); lev out of range, or no coarser level for a transfer; a process grid larger than
+ *   1 x 1 (a distributed CSR needs a global numbering); a level whose rows or entries do not fit an int. */
+int mgx_operator_csr_size(int lev, long long *nrows, long long *nnz);
+int mgx_operator_csr(int lev, int *rowptr_dev, int *col_dev, double *val_dev);
+int mgx_transfer_csr_size(int lev, int which, long long *nrows, long long *ncols, long long *nnz);
+int mgx_transfer_csr(int lev, int which, int *rowptr_dev, int *col_dev, double *val_dev);
 /* compute_rhs / correct_uvw on the device-resident model state (mg_compute_rhs.f90:14, mg_correct_uvw.f90:15) */
 int mgx_compute_rhs(const double *u, const double *v, const double *w, const double *rmask);
 

@@ -52,6 +52,10 @@ _SIGS = {
     "mgx_fine2coarse": (C.c_int, [C.c_int]),
     "mgx_coarse2fine": (C.c_int, [C.c_int]),
     "mgx_fill_halo": (C.c_int, [C.c_int, C.c_int]),
+    "mgx_operator_csr_size": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "mgx_operator_csr": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgx_transfer_csr_size": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "mgx_transfer_csr": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgx_compute_rhs": (C.c_int, [_DP, _DP, _DP, _DP]),
     "mgx_testgalerkin": (C.c_int, [C.c_int, _DP, _DP]),
     "mgx_nlevs": (C.c_int, []),

@@ -3,6 +3,7 @@
 // mgx_define.cpp, the mgx_p2p_* and mgx_rccl_* entry points in mgx_comm.cpp.
 // There is no CPU compute path: every operator is a HIP kernel launch (mgx_wrappers.h).
 #include "mgx_host.h"
+#include "mgx_export.h"
 
 namespace mgx_host {
 
@@ -430,6 +431,130 @@ int mgx_testgalerkin(int lev, double *norm_c, double *norm_f) {
   if (norm_c) *norm_c = nc;
   if (norm_f) *norm_f = nf;
   return 0;
+}
+
+// ---- the CSR export: A of a level, R and P of a pair of levels, as the kernels apply them (include/mgx.h) ----
+// Probing, not a second spelling of the operator: the library's own residual / fine2coarse / coarse2fine is applied to sums of unit vectors
+// that no row can confuse (the colours of mgx_export.h), and the entries are read off the result -- one times a coefficient and sums with
+// zeros are exact, so every value is the number the kernels use, with the level's halo rule, the masks and the k = 1 diagonals of
+// cmatrix = 'real' folded in by the kernels themselves.  Two sweeps over the colours: the first marks which colours each row answers to
+// (its bit mask, whose population counts are scanned into rowptr), the second scatters the entries into their sorted slots.
+namespace {
+// What an export borrows and gives back bit for bit: whole JS arrays (halo and padding included), the deferred-halo flags, the timers' switch.
+struct Borrowed {
+  struct Field { double *at, *copy; size_t n; };
+  std::vector<Field> fields;
+  std::vector<std::pair<bool *, bool>> flags;
+  std::vector<void *> scratch;
+  int tictoc;
+  Borrowed() : tictoc(S.tictoc) { S.tictoc = 0; }
+  int field(double *a, size_t n) {
+    double *c = nullptr;
+    HIPCHK(hipMalloc((void **)&c, n * sizeof(double)));
+    fields.push_back({a, c, n});
+    HIPCHK(hipMemcpyAsync(c, a, n * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
+    return 0;
+  }
+  void flag(bool *f) { flags.push_back({f, *f}); }
+  int alloc(void **p, size_t bytes) {
+    HIPCHK(hipMalloc(p, bytes));
+    scratch.push_back(*p);
+    return 0;
+  }
+  int give_back() {
+    int rc = 0;
+    for (const Field &f : fields)
+      if (hipMemcpyAsync(f.at, f.copy, f.n * sizeof(double), hipMemcpyDeviceToDevice, S.stream) != hipSuccess) rc = fail("the export could not put a borrowed field back");
+    const int rs = sync_stream();
+    for (const Field &f : fields) (void)hipFree(f.copy);
+    for (void *p : scratch) (void)hipFree(p);
+    for (const auto &f : flags) *f.first = f.second;
+    S.tictoc = tictoc;
+    return rc ? rc : rs;
+  }
+};
+}  // namespace
+
+// which: -1 = A of level lev, 0 = R (lev -> lev + 1), 1 = P (lev + 1 -> lev).  rowptr == nullptr: count only (the *_size entries)
+static int export_csr(const char *who, int lev, int which, long long *nrows, long long *ncols, long long *nnz, int *rowptr, int *col, double *val) {
+  NEED_LEV(lev);
+  const bool size_only = rowptr == nullptr && col == nullptr && val == nullptr;
+  if (which < -1 || which > 1) return fail("%s: which = %d is neither 0 (the restriction) nor 1 (the prolongation)", who, which);
+  if (which >= 0 && lev >= S.nlevs) return fail("%s(%d): no coarser level", who, lev);
+  if (S.npx * S.npy > 1) return fail("%s: a process grid (%d x %d) is out of scope: the export numbers the unknowns of one rank", who, S.npx, S.npy);
+  if (!S.have_matrix) return fail("%s: no matrix: call mgx_matrices (or mgx_set_field(lev, MGX_CA, ...)) first", who);
+  if (!size_only && (!rowptr || !col || !val)) return fail("%s: rowptr, col and val must all be device pointers", who);
+  Level &F = S.lev[lev - 1];
+  Level &C = S.lev[which >= 0 ? lev : lev - 1];
+  if (which >= 0 && (C.gather || F.nx != 2 * C.nx || F.ny != 2 * C.ny || (C.nz != F.nz && C.nz != F.nz / 2)))
+    return fail("%s(%d): levels %d x %d x %d and %d x %d x %d are not a pair the export knows", who, lev, F.nx, F.ny, F.nz, C.nx, C.ny, C.nz);
+  const int mode = which < 0 ? EX_A : (which == 0 ? EX_R : EX_P);
+  Level &Lr = mode == EX_R ? C : F, &Lc = mode == EX_P ? C : F;   // rows, columns (A: both the level itself)
+  const int *nb = Lc.neighb;
+  if ((nb[0] < 0) != (nb[2] < 0) || (nb[1] < 0) != (nb[3] < 0)) return fail("%s(%d): a level closed on one side and open on the other has no halo rule the export knows", who, lev);
+  const ExMap m = ex_map(mode, Lr.nx, Lr.ny, Lr.nz, Lc.nx, Lc.ny, Lc.nz, nb[0] < 0 ? EX_MIRROR : EX_WRAP, nb[1] < 0 ? EX_MIRROR : EX_WRAP);
+  const int ncolours = ex_ncolours(m);
+  if (ncolours > EX_MAX_COLOURS) return fail("%s(%d): a periodic level of %d x %d columns needs %d colours, the export has %d", who, lev, Lc.nx, Lc.ny, ncolours, EX_MAX_COLOURS);
+  const long long nr = (long long)Lr.nx * Lr.ny * Lr.nz, nc = (long long)Lc.nx * Lc.ny * Lc.nz;
+  if (ex_fits_int(nr, nc, 0)) return fail("%s(%d): %lld rows and %lld columns do not fit the int indices of rowptr and col", who, lev, nr, nc);
+  if (!size_only && (S.ex_lev != lev || S.ex_which != which)) return fail("%s(%d): call %s_size for this matrix first: it says how large col and val must be", who, lev, who);
+
+  Borrowed B;
+  long long total = -1;
+  const auto body = [&]() -> int {
+    unsigned long long *mask = nullptr; long long *sums = nullptr;
+    const int nsums = mgxe_csr_sums_len(nr);
+    CHK(B.alloc((void **)&mask, (size_t)nr * sizeof(unsigned long long)));
+    CHK(B.alloc((void **)&sums, (size_t)nsums * sizeof(long long)));
+    B.flag(&F.r_halo_stale);
+    if (mode == EX_A) { CHK(B.field(F.v.p, F.n3js)); CHK(B.field(F.v.b, F.n3js)); CHK(B.field(F.v.r, F.n3js)); }
+    if (mode == EX_R) { CHK(B.field(F.v.r, F.n3js)); CHK(B.field(C.v.b, C.n3js)); CHK(B.field(C.v.p, C.n3js)); B.flag(&C.b_halo_stale); }
+    if (mode == EX_P) { CHK(B.field(F.v.p, F.n3js)); CHK(B.field(F.v.r, F.n3js)); CHK(B.field(C.v.p, C.n3js)); }
+    if (mode == EX_A) HIPCHK(hipMemsetAsync(F.v.b, 0, F.n3js * sizeof(double), S.stream));
+    // the probe of one colour through the library's own operator; returns the field of the ROW level that holds the answer
+    double *probe_in = mode == EX_A ? F.v.p : (mode == EX_R ? F.v.r : C.v.p);
+    const double *answer = mode == EX_A ? F.v.r : (mode == EX_R ? C.v.b : F.v.p);
+    const auto probe = [&](int colour) -> int {
+      mgxe_probe_fill(S.stream, &Lc.v, probe_in, &m, colour); S.n_launch++;
+      CHK(fill_halo_js(Lc, probe_in));
+      if (mode == EX_A) return residual(lev, nullptr);
+      if (mode == EX_R) return fine2coarse(lev);
+      HIPCHK(hipMemsetAsync(F.v.p, 0, F.n3js * sizeof(double), S.stream));
+      return coarse2fine(lev);
+    };
+    HIPCHK(hipMemsetAsync(mask, 0, (size_t)nr * sizeof(unsigned long long), S.stream));
+    for (int c = 0; c < ncolours; c++) { CHK(probe(c)); mgxe_csr_mark(S.stream, &Lr.v, answer, &m, c, mask); S.n_launch++; }
+    mgxe_csr_count(S.stream, mask, nr, sums); S.n_launch += 2;
+    HIPCHK(hipMemcpyAsync(&total, sums + nsums - 1, sizeof total, hipMemcpyDeviceToHost, S.stream));
+    CHK(sync_stream());
+    if (ex_fits_int(nr, nc, total)) return fail("%s(%d): %lld entries do not fit the int indices of rowptr", who, lev, total);
+    if (size_only) return 0;
+    if (total != S.ex_nnz) return fail("%s(%d): the matrix has %lld entries, %s_size counted %lld: it changed in between, ask again", who, lev, total, who, S.ex_nnz);
+    mgxe_csr_rowptr(S.stream, mask, nr, sums, rowptr); S.n_launch++;
+    for (int c = 0; c < ncolours; c++) { CHK(probe(c)); mgxe_csr_scatter(S.stream, &Lr.v, answer, &m, c, mask, rowptr, col, val, mode == EX_A ? -1.0 : 1.0); S.n_launch++; }
+    return 0;
+  };
+  const int rc = body(), rb = B.give_back();
+  if (rc || rb) return rc ? rc : rb;
+  if (size_only) { S.ex_lev = lev; S.ex_which = which; S.ex_nnz = total; }
+  if (nrows) *nrows = nr;
+  if (ncols) *ncols = nc;
+  if (nnz) *nnz = total;
+  return 0;
+}
+int mgx_operator_csr_size(int lev, long long *nrows, long long *nnz) { return export_csr("mgx_operator_csr", lev, -1, nrows, nullptr, nnz, nullptr, nullptr, nullptr); }
+int mgx_operator_csr(int lev, int *rowptr_dev, int *col_dev, double *val_dev) {
+  if (!rowptr_dev || !col_dev || !val_dev) return fail("mgx_operator_csr: rowptr, col and val must all be device pointers");
+  return export_csr("mgx_operator_csr", lev, -1, nullptr, nullptr, nullptr, rowptr_dev, col_dev, val_dev);
+}
+int mgx_transfer_csr_size(int lev, int which, long long *nrows, long long *ncols, long long *nnz) {
+  if (which != 0 && which != 1) return fail("mgx_transfer_csr: which = %d is neither 0 (the restriction) nor 1 (the prolongation)", which);
+  return export_csr("mgx_transfer_csr", lev, which, nrows, ncols, nnz, nullptr, nullptr, nullptr);
+}
+int mgx_transfer_csr(int lev, int which, int *rowptr_dev, int *col_dev, double *val_dev) {
+  if (which != 0 && which != 1) return fail("mgx_transfer_csr: which = %d is neither 0 (the restriction) nor 1 (the prolongation)", which);
+  if (!rowptr_dev || !col_dev || !val_dev) return fail("mgx_transfer_csr: rowptr, col and val must all be device pointers");
+  return export_csr("mgx_transfer_csr", lev, which, nullptr, nullptr, nullptr, rowptr_dev, col_dev, val_dev);
 }
 
 static int level_table(int nx, int ny, int nz, int npx, int npy, int rank, int nsmall, int periodic, int hold, int hold_z, int maxlev, int *out) {

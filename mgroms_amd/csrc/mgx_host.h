@@ -210,6 +210,9 @@ struct State {
   int hold_z_levels = 0;
   int hold_z_fuse = 1;   // option "hold_z_fuse" (A/B): 0 = the down leg of every held pair and the closing residual on one stay two launches; same bits
   long long n_hold_z_fused = 0;   // read-only option "hold_z_fused": down legs and closing residuals of held pairs served by the fused kernel since mgx_init
+  // the CSR export (mgx_operator_csr, mgx_transfer_csr): what the last *_csr_size call counted and for which matrix (which: -1 = A, 0 = R,
+  // 1 = P) -- the *_csr call that follows fills buffers of that size and refuses any other count
+  int ex_lev = 0, ex_which = -2; long long ex_nnz = -1;
   int c2f_skip = 1;   // the cycles' prolongation leaves the columns alone that the first colour of the following four-colour relax overwrites unread (option "c2f_skip", MGX_C2F_NOSKIP=1)
   long long n_launch = 0, n_halo = 0, n_exch = 0, n_allred = 0;
   std::string err, transport_name;

@@ -11,6 +11,7 @@ struct RectOp { int op, nzz, nh, ny, j0, j1, i0, i1, mj, cj, mi, ci, mj2, cj2, m
 // the typed view of it.  rmask: i-fastest copy of the level-1 mask (only read when bmask)
 struct ModelView { void *u, *v, *w; double *rmask; int bmask, f32; };
 template <typename T> struct ModelViewT { T *u, *v, *w; double *rmask; int bmask; };
+struct ExMap;   // mgx_export.h: the geometry of one CSR export
 
 extern "C" {
 
@@ -181,6 +182,15 @@ void mgxq_update(hipStream_t st, const LevView *L, double *p, double *r, const d
                  double *partial, double *out);
 void mgxq_update32(hipStream_t st, const LevView *L, const LevView32 *S, double *p, double *r, const double *z, const double *q, double sigma, const double *st2v,
                    double *qq_new, double *partial, double *out);
+
+// ---- mgx_export.hip (ExMap: mgx_export.h, the geometry of one export) ----
+void mgxe_probe_fill(hipStream_t st, const LevView *L, double *a, const ExMap *m, int colour);
+void mgxe_csr_mark(hipStream_t st, const LevView *L, const double *a, const ExMap *m, int colour, unsigned long long *mask);
+int mgxe_csr_sums_len(long long n);
+void mgxe_csr_count(hipStream_t st, const unsigned long long *mask, long long n, long long *sums);
+void mgxe_csr_rowptr(hipStream_t st, const unsigned long long *mask, long long n, const long long *sums, int *rowptr);
+void mgxe_csr_scatter(hipStream_t st, const LevView *L, const double *a, const ExMap *m, int colour, const unsigned long long *mask, const int *rowptr,
+                      int *col, double *val, double sign);
 
 // ---- mgx_rccl.cpp ----
 const char *mgxr_last_error(void);

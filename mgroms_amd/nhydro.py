@@ -5,6 +5,7 @@ Fortran index, i.e. a field p(nz,0:ny+1,0:nx+1) is a numpy array of shape (nx+2,
 """
 import ctypes as C
 import threading
+import warnings
 
 import numpy as np
 
@@ -271,6 +272,51 @@ def testgalerkin(lev):
 
 def nlevs():
     return lib().mgx_nlevs()
+
+
+# ---- the level matrices as torch sparse CSR tensors on the device (include/mgx.h: mgx_operator_csr, mgx_transfer_csr) ----
+def _csr(size_call, fill_call):
+    """allocate from the *_size call, fill, wrap: float64 values, int32 indices, on the solver's device"""
+    import torch
+    nrows, ncols, nnz = size_call()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rowptr = torch.empty(nrows + 1, dtype=torch.int32, device=dev)
+    col = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)   # (never an empty allocation: the library refuses a null pointer)
+    val = torch.empty(max(nnz, 1), dtype=torch.float64, device=dev)
+    _wait_for_caller()
+    fill_call(C.c_void_p(rowptr.data_ptr()), C.c_void_p(col.data_ptr()), C.c_void_p(val.data_ptr()))
+    with warnings.catch_warnings():   # (torch announces once per process that its CSR support is in beta)
+        warnings.filterwarnings("ignore", message="Sparse CSR tensor support is in beta")
+        return torch.sparse_csr_tensor(rowptr, col[:nnz], val[:nnz], size=(nrows, ncols))
+
+
+def operator_csr(lev):
+    """A of level lev with the sign of compute_residual (r = b - A p), the level's halo rule folded in, as a torch.sparse_csr_tensor on the
+    device.  Unknown (k, j, i) has index ((i-1)*ny + (j-1))*nz + (k-1): for a field f of grid(lev), f[1:-1, 1:-1, :].reshape(-1)."""
+    def size():
+        n, nnz = C.c_longlong(), C.c_longlong()
+        check(lib().mgx_operator_csr_size(int(lev), C.byref(n), C.byref(nnz)))
+        return n.value, n.value, nnz.value
+    return _csr(size, lambda r, c, v: check(lib().mgx_operator_csr(int(lev), r, c, v)))
+
+
+def _transfer_csr(lev, which):
+    def size():
+        n, m, nnz = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        check(lib().mgx_transfer_csr_size(int(lev), which, C.byref(n), C.byref(m), C.byref(nnz)))
+        return n.value, m.value, nnz.value
+    return _csr(size, lambda r, c, v: check(lib().mgx_transfer_csr(int(lev), which, r, c, v)))
+
+
+def restriction_csr(lev):
+    """R from level lev to lev + 1, what fine2coarse(lev) does to grid(lev).r to produce grid(lev+1).b: (unknowns of lev+1) x (unknowns of lev)"""
+    return _transfer_csr(lev, 0)
+
+
+def prolongation_csr(lev):
+    """P from level lev + 1 to lev under the live interp_type, what coarse2fine(lev) adds to grid(lev).p from grid(lev+1).p with its halo
+    filled: (unknowns of lev) x (unknowns of lev+1)"""
+    return _transfer_csr(lev, 1)
 
 
 def mixed_op(op, lev, n=1):
