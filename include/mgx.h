@@ -143,6 +143,36 @@ int mgx_solve_f32(float *u, float *v, float *w, const double *rmask);
 int mgx_compute_rhs_f32(const float *u, const float *v, const float *w, const double *rmask);
 int mgx_check_nondivergence_f32(float *u, float *v, float *w, const double *rmask);
 
+/* ---- the state in the model's own padded arrays (no Fortran counterpart: there the compiler copies an array section in and out) ----
+ * A model keeps u, v, w in arrays with ghost cells and padding (CROCO's GLOBAL_2D_ARRAY: i fastest, two or three ghost cells per side).
+ * The *_view entries work on those arrays in place: no gather before the call, no scatter after it, no second copy of the state.
+ * Addressing.  Each pointer names the FIRST LOGICAL ELEMENT of its array, u(1,0,1), v(0,1,1), w(0,0,0); the strides are in elements of
+ * the state's type: sj from row j to row j + 1, sk from level k to level k + 1; the i stride is 1.  So
+ *     u(i,j,k) = u[(i-1) + j sj + (k-1) sk],   v(i,j,k) = v[i + (j-1) sj + (k-1) sk],   w(i,j,k) = w[i + j sj + k sk]
+ * over the shapes of mgx_solve: u(1:nx+1,0:ny+1,1:nz), v(0:nx+1,1:ny+1,1:nz), w(0:nx+1,0:ny+1,0:nz).  Only these elements are read, and
+ * only the ones correct_uvw writes are written: the padding between rows and between levels is neither read nor written.
+ * The densely packed arrays of mgx_solve_device are the strides sj = nx+1 (u) or nx+2 (v, w), sk = sj (ny+2) (u, w) or sj (ny+1) (v):
+ * with them a view entry leaves the bits of the dense entry and issues its launches (mgx_counters).  One text and one instance of every
+ * model kernel serves both (mgx_model.hip); the results never depend on the strides.
+ * f32 = 0: u, v, w point to doubles; f32 = 1: to floats, under the contract of the float state above.
+ * mgx_state_strides_check: host only, needs neither a GPU nor mgx_init.  Returns 1, with the array, the field and the offending value in
+ * mgx_last_error(), for a stride that is not positive, an sj below the row length, an sk below sj x rows, or an extent whose last element
+ * lies more than 63 bits' worth (in bytes of a double) from the first.  The view entries call it first and refuse in its words, then
+ * behave as mgx_solve_device / mgx_check_nondivergence_device do, under every option ("async", "warm_start", "krylov", "hold_z_levels",
+ * "periodic", process grids, every relax_method): they are those entries with other addresses.  A NULL u, v, w or s is refused.
+ * rmask_dev stays in the library's dense layout ((0:ny+1, 0:nx+1), j fastest; may be NULL): a mask is set-up data, not per-step traffic.
+ * mgx_update_zeta_device_view: the refresh of mgx_update_zeta_device from the model's own zeta, i FASTEST: zeta(i,j) = zeta_dev[i + j sj],
+ * i = 0..nx+1, j = 0..ny+1, row pitch sj >= nx+2 (the pointer names zeta(0,0)).  One LDS-tiled transpose launch brings it into the level-1
+ * array; from there the call is mgx_update_zeta_device and leaves bit for bit what that leaves for the transposed dense array, waits or
+ * enqueues as that does, and counts in "zeta_refreshes".
+ * Out of scope: the host-array entries (mgx_solve, mgx_solve_f32) and the Fortran module, which binds host arrays only; a pitched dx, dy,
+ * h or rmask (set-up data); strides other than 1 along i. */
+typedef struct { long long u_sj, u_sk, v_sj, v_sk, w_sj, w_sk; } mgx_state_strides;   /* in elements of the state's type */
+int mgx_state_strides_check(int nx, int ny, int nz, const mgx_state_strides *s);
+int mgx_solve_device_view(void *u, void *v, void *w, const mgx_state_strides *s, int f32, const double *rmask_dev);
+int mgx_check_nondivergence_device_view(void *u, void *v, void *w, const mgx_state_strides *s, int f32, const double *rmask_dev);
+int mgx_update_zeta_device_view(const double *zeta_dev, long long sj);
+
 /* mg_solvers.f90:17-101 solve_p(tol,maxite).  *nite = iterations done, *res = last ||r||/||b||,
  * hist (may be NULL, else >= maxite+1 doubles) = normalised residual after each iteration, hist[0] = initial. */
 int mgx_solve_p(double tol, int maxite, int *nite, double *res, double *hist);

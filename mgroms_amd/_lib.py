@@ -19,6 +19,11 @@ class Params(C.Structure):
                 ("bmask", C.c_int)]
 
 
+class StateStrides(C.Structure):
+    """mgx_state_strides (include/mgx.h): element strides from row j to j + 1 (sj) and from level k to k + 1 (sk) of u, v, w"""
+    _fields_ = [(n, C.c_longlong) for n in ("u_sj", "u_sk", "v_sj", "v_sk", "w_sj", "w_sk")]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p),
                           C.POINTER(C.c_void_p), C.POINTER(C.c_int))
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int)
@@ -39,6 +44,10 @@ _SIGS = {
     "mgx_check_nondivergence_device": (C.c_int, [C.c_void_p] * 4),
     "mgx_solve_device_f32": (C.c_int, [C.c_void_p] * 4),
     "mgx_check_nondivergence_device_f32": (C.c_int, [C.c_void_p] * 4),
+    "mgx_state_strides_check": (C.c_int, [C.c_int] * 3 + [C.POINTER(StateStrides)]),
+    "mgx_solve_device_view": (C.c_int, [C.c_void_p] * 3 + [C.POINTER(StateStrides), C.c_int, C.c_void_p]),
+    "mgx_check_nondivergence_device_view": (C.c_int, [C.c_void_p] * 3 + [C.POINTER(StateStrides), C.c_int, C.c_void_p]),
+    "mgx_update_zeta_device_view": (C.c_int, [C.c_void_p, C.c_longlong]),
     "mgx_solve_f32": (C.c_int, [_FP, _FP, _FP, _DP]),
     "mgx_compute_rhs_f32": (C.c_int, [_FP, _FP, _FP, _DP]),
     "mgx_check_nondivergence_f32": (C.c_int, [_FP, _FP, _FP, _DP]),

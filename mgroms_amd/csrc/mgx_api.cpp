@@ -4,6 +4,7 @@
 // There is no CPU compute path: every operator is a HIP kernel launch (mgx_wrappers.h).
 #include "mgx_host.h"
 #include "mgx_export.h"
+#include "mgx_state_view.h"
 
 namespace mgx_host {
 
@@ -287,9 +288,34 @@ int mgx_update_zeta_device(const double *zeta_dev) {
   return 0;
 }
 
+// the same refresh from the model's own zeta: i fastest, rows sj elements apart.  One transpose into the level-1 array, then as above.
+int mgx_update_zeta_device_view(const double *zeta_dev, long long sj) {
+  NEED_INIT();
+  if (!S.have_geometry) return fail("mgx_update_zeta_device_view: no dx, dy, h to keep: call mgx_matrices or mgx_matrices_device first");
+  if (!zeta_dev) return fail("mgx_update_zeta_device_view: zeta_dev is NULL");
+  Level &L = S.lev[0];
+  long long last;
+  if (sj < L.nx + 2) return fail("mgx_update_zeta_device_view: sj = %lld is below the row length of zeta, %d: rows would overlap", sj, L.nx + 2);
+  if (__builtin_mul_overflow(sj, (long long)L.ny + 1, &last) || last > LLONG_MAX / 8 - (L.nx + 2))
+    return fail("mgx_update_zeta_device_view: sj = %lld: the extent of zeta does not fit in 63 bits", sj);
+  mgxs_zeta_view(S.stream, zeta_dev, sj, L.g.zeta, L.nx, L.ny); S.n_launch++;
+  CHK(define_matrices(DM_ZETA, true));
+  S.n_zeta_refresh++;
+  return 0;
+}
+
 // The model-facing entries, each once for both scalar types of the state (f32: u, v, w are floats; include/mgx.h: "the float state").
 // `who` names the entry in its refusals.  The float entries refuse a NULL u, v or w; the fp64 ones keep taking what they are given.
 #define NEED_STATE(who) do { if (f32 && !(u && v && w)) return fail("%s: u, v or w is NULL", who); } while (0)
+// the view entries (str != nullptr; the dense entries pass by): the strides against the live level 1 (mgx_state_view.h), and no NULL array
+static int view_refusal(const void *u, const void *v, const void *w, const mgx_state_strides *str, const char *who) {
+  char why[256];
+  const Level &L = S.lev[0];
+  if (state_strides_refusal(L.nx, L.ny, L.nz, str, why, sizeof why)) return fail("%s: %s", who, why);
+  if (!(u && v && w)) return fail("%s: u, v or w is NULL", who);
+  return 0;
+}
+#define NEED_VIEW(who) do { if (str) CHK(view_refusal(u, v, w, str, who)); } while (0)
 
 static int compute_rhs_host(const void *u, const void *v, const void *w, const double *rmask, bool f32, const char *who) {
   NEED_INIT();
@@ -322,12 +348,14 @@ static int solve_host(void *u, void *v, void *w, const double *rmask, bool f32, 
 
 // Device-resident variant of nhydro_solve: u,v,w are DEVICE pointers in the model's (i,j,k) layout
 // (e.g. torch tensors); nothing crosses PCIe.  The library's own staging copies are bypassed.
-static int solve_device(void *u, void *v, void *w, const double *rmask, bool f32, const char *who) {
+// str: u, v, w are the model's own padded arrays with these strides (the *_view entries), checked before anything else is looked at.
+static int solve_device(void *u, void *v, void *w, const double *rmask, bool f32, const char *who, const mgx_state_strides *str = nullptr) {
   NEED_INIT();
+  NEED_VIEW(who);
   if (!S.have_matrix) return fail("mgx_matrices must be called before %s", who);
   NEED_STATE(who);
   CHK(set_call_mask(rmask, true));
-  StateScope state(u, v, w, f32);
+  StateScope state(u, v, w, f32, str);
   CHK(compute_rhs_dev());
   CHK(solve_p_opt(S.par.solver_prec, S.par.solver_maxiter, nullptr, nullptr, nullptr));
   CHK(correct_uvw_dev());
@@ -336,13 +364,14 @@ static int solve_device(void *u, void *v, void *w, const double *rmask, bool f32
 }
 
 // nhydro_check_nondivergence on the model's own device arrays (the pattern of mgx_solve_device): the divergence into grid(1)%b
-static int check_nondivergence_device(void *u, void *v, void *w, const double *rmask, bool f32, const char *who) {
+static int check_nondivergence_device(void *u, void *v, void *w, const double *rmask, bool f32, const char *who, const mgx_state_strides *str = nullptr) {
   NEED_INIT();
+  NEED_VIEW(who);
   if (!S.have_matrix) return fail("mgx_matrices must be called before %s", who);
   NEED_STATE(who);
   if (S.verbose && S.rank == 0) printf(" - check non-divergence:\n");
   CHK(set_call_mask(rmask, true));
-  StateScope state(u, v, w, f32);
+  StateScope state(u, v, w, f32, str);
   CHK(compute_rhs_dev());
   CHK(sync_stream());
   return 0;
@@ -367,6 +396,19 @@ int mgx_check_nondivergence_device(double *u_dev, double *v_dev, double *w_dev, 
 }
 int mgx_check_nondivergence_device_f32(float *u_dev, float *v_dev, float *w_dev, const double *rmask_dev) {
   return check_nondivergence_device(u_dev, v_dev, w_dev, rmask_dev, true, "mgx_check_nondivergence_device_f32");
+}
+
+int mgx_state_strides_check(int nx, int ny, int nz, const mgx_state_strides *s) {
+  char why[256];
+  return state_strides_refusal(nx, ny, nz, s, why, sizeof why) ? fail("mgx_state_strides_check: %s", why) : 0;
+}
+int mgx_solve_device_view(void *u, void *v, void *w, const mgx_state_strides *s, int f32, const double *rmask_dev) {
+  if (!s) return fail("mgx_solve_device_view: the strides are NULL");
+  return solve_device(u, v, w, rmask_dev, f32 != 0, "mgx_solve_device_view", s);
+}
+int mgx_check_nondivergence_device_view(void *u, void *v, void *w, const mgx_state_strides *s, int f32, const double *rmask_dev) {
+  if (!s) return fail("mgx_check_nondivergence_device_view: the strides are NULL");
+  return check_nondivergence_device(u, v, w, rmask_dev, f32 != 0, "mgx_check_nondivergence_device_view", s);
 }
 
 int mgx_solve_p(double tol, int maxite, int *nite, double *res, double *hist) {

@@ -256,16 +256,20 @@ int define_matrices(int what, bool may_return_early) {
 // mg_correct_uvw.f90:51-68).  Without a per-call mask (NULL): the level-1 mask of nhydro_matrices when bmask, else all ones.
 ModelView model_view() {
   double *m = S.call_mask ? S.d_rmask_m : (S.par.bmask ? S.lev[0].g.mrmask : nullptr);
-  return ModelView{S.d_u, S.d_v, S.d_w, m, S.par.bmask ? 1 : 0, S.state_f32};
+  return ModelView{S.d_u, S.d_v, S.d_w, m, S.par.bmask ? 1 : 0, S.state_f32, S.state_view, S.state_str};
 }
 
 // the model state of one call in place of the library's fp64 staging copies: the caller's device arrays (the *_device entries), or the
-// staging buffers themselves holding floats (the host *_f32 entries: u = v = w = nullptr).  Put back when the call ends, whatever it returns.
-StateScope::StateScope(void *u, void *v, void *w, bool f32) : su(S.d_u), sv(S.d_v), sw(S.d_w), sf(S.state_f32) {
+// staging buffers themselves holding floats (the host *_f32 entries: u = v = w = nullptr); with `str`, the caller's arrays are the model's own
+// padded ones (the *_view entries).  Put back when the call ends, whatever it returns.
+StateScope::StateScope(void *u, void *v, void *w, bool f32, const mgx_state_strides *str)
+    : su(S.d_u), sv(S.d_v), sw(S.d_w), sf(S.state_f32), sview(S.state_view), sstr(S.state_str) {
   if (u) { S.d_u = (double *)u; S.d_v = (double *)v; S.d_w = (double *)w; }
   S.state_f32 = f32 ? 1 : 0;
+  S.state_view = str ? 1 : 0;
+  if (str) S.state_str = *str;
 }
-StateScope::~StateScope() { S.d_u = su; S.d_v = sv; S.d_w = sw; S.state_f32 = sf; }
+StateScope::~StateScope() { S.d_u = su; S.d_v = sv; S.d_w = sw; S.state_f32 = sf; S.state_view = sview; S.state_str = sstr; }
 
 // rmaska of nhydro_solve / nhydro_check_nondivergence: (0:ny+1,0:nx+1), j fastest -- the layout the reference's drivers
 // allocate (mg_testseamount.f90:97) and compute_rhs indexes (rmask(j,i)).  `dev`: the pointer is a device pointer.

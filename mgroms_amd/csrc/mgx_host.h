@@ -95,6 +95,7 @@ struct State {
   int p2p_failed = 0;       // a wait of this rank timed out since the ranks last agreed (global_sum): reported collectively there
   int p2p_test_drop = 0;    // test hook (option "p2p_test_drop" = n): the n-th halo exchange from now does not raise its flags
   int state_f32 = 0;    // d_u, d_v, d_w of the running call hold floats (the mgx_*_f32 entries; StateScope sets and resets it)
+  int state_view = 0; mgx_state_strides state_str = {};   // d_u, d_v, d_w of the running call are the model's own padded arrays with these strides (the *_view entries; StateScope likewise)
   double *d_u = nullptr, *d_v = nullptr, *d_w = nullptr, *d_fx = nullptr, *d_fy = nullptr, *d_fz = nullptr, *d_bm = nullptr;  // model-layout scratch: the three fluxes of compute_rhs, divergence / pressure
   // the mask handed to nhydro_solve / nhydro_check_nondivergence on THIS call (nhydro.f90:72,82,98): staging copy in the
   // caller's layout and the i-fastest copy the model-space kernels read; call_mask = a mask came with the current call
@@ -276,8 +277,13 @@ int correct_uvw_dev();
 int upload_uvw(const void *u, const void *v, const void *w, size_t esz);
 int download_uvw(void *u, void *v, void *w, size_t esz);
 // the state compute_rhs_dev / correct_uvw_dev work on while the scope lives: u, v, w device arrays of doubles or (f32) of floats, or,
-// with u = nullptr, the staging buffers S.d_u, S.d_v, S.d_w themselves under that type
-struct StateScope { double *su, *sv, *sw; int sf; StateScope(void *u, void *v, void *w, bool f32); ~StateScope(); };
+// with u = nullptr, the staging buffers S.d_u, S.d_v, S.d_w themselves under that type; str: u, v, w are padded arrays with these strides
+// (checked by the caller: mgx_state_view.h), nullptr: densely packed
+struct StateScope {
+  double *su, *sv, *sw; int sf, sview; mgx_state_strides sstr;
+  StateScope(void *u, void *v, void *w, bool f32, const mgx_state_strides *str = nullptr);
+  ~StateScope();
+};
 
 // ---- mgx_comm.cpp ----
 struct XEntry { int peer, sd, rd; };   // one message pair of an exchange: what was packed for direction sd goes to peer, what peer sends lands in the halo of direction rd

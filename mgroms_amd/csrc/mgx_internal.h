@@ -92,4 +92,5 @@ __host__ __device__ inline int jpos32(const LevView32 &L, int j) { return (j & 1
 inline bool mixed_tail_small(int nx, int ny, int nz) { return (long long)nx * ny * nz <= MIXED_TAIL_MAX_CELLS && nz <= 32; }
 
 // the kernel wrappers: one prototype each, seen by the file that defines a wrapper and by every file that calls it
+#include "../../include/mgx.h"   // mgx_state_strides: the strides a ModelView carries
 #include "mgx_wrappers.h"

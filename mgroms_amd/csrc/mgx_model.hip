@@ -6,14 +6,18 @@
 // pressure comes back the same way for correct_uvw.  Operation order follows the reference line by line
 // (compiled with -ffp-contract=off): results are bit-identical to the CPU oracle.
 #include "mgx_choice.h"
+#include "mgx_state_view.h"
 
 // The model state u, v, w is double or float (ModelViewT<T>; the float state: DESIGN.md 6.2).  The formulas read it through U, V, Wv, which
 // load one T and widen it to double (exact), so there is one text of every formula for both; correct_uvw stores through SET_U, SET_V,
 // SET_W, which round the double result to T once (to nearest even; a no-op for double).  One element per load and per store: a row of
 // floats starts 4-byte aligned (nx + 1 or nx + 2 elements), which is all such an access needs.
-#define UE(i, j, k) M.u[(((long long)((k)-1)) * (ny + 2) + (j)) * (nx + 1) + ((i)-1)]
-#define VE(i, j, k) M.v[(((long long)((k)-1)) * (ny + 1) + ((j)-1)) * (nx + 2) + (i)]
-#define WE(i, j, k) M.w[(((long long)(k)) * (ny + 2) + (j)) * (nx + 2) + (i)]
+// The arrays are the model's own: u, v, w name the first logical element, u(1,0,1), v(0,1,1), w(0,0,0), and rows and levels lie sj and sk
+// elements apart (ModelViewT; the densely packed arrays are sj = nx + 1 | nx + 2, sk = sj (ny + 2 | ny + 1)).  The padding between rows and
+// between levels is never touched: every access below is to an element of the logical shape.
+#define UE(i, j, k) M.u[((long long)((k)-1)) * M.usk + ((long long)(j)) * M.usj + ((i)-1)]
+#define VE(i, j, k) M.v[((long long)((k)-1)) * M.vsk + ((long long)((j)-1)) * M.vsj + (i)]
+#define WE(i, j, k) M.w[((long long)(k)) * M.wsk + ((long long)(j)) * M.wsj + (i)]
 #define U(i, j, k) ((double)UE(i, j, k))
 #define V(i, j, k) ((double)VE(i, j, k))
 #define Wv(i, j, k) ((double)WE(i, j, k))
@@ -96,7 +100,9 @@ __global__ __launch_bounds__(256) void k_js_model(LevView L, double *__restrict_
 // A lane climbs its column and keeps what row k+1 of this step is to row k of the next (zw, dzw, w; in k_rhs_wf zxdy, zydx, u, v of row
 // k-1) in registers: rows are 2 MB apart, so a value asked for again one step later comes from HBM again -- k_rhs_uf moved 1.5 GB for
 // 0.8 GB of operands (264 us = 5.6 TB/s: at the memory's rate, on the wrong bytes).  Same values in the same expressions: same bits.
-template <typename T> __global__ void k_rhs_uf(GeoView G, ModelViewT<T> M, double *__restrict__ fx, int KR) {
+// The kernels that take the state are launched with IBLK = 64 x 4 threads and say so: without the bound the compiler budgets for 1024-thread
+// blocks, i.e. 128 VGPRs, and k_rhs_uf / k_rhs_vf spill (profiles/state_view_resources.txt).
+template <typename T> __global__ __launch_bounds__(256) void k_rhs_uf(GeoView G, ModelViewT<T> M, double *__restrict__ fx, int KR) {
   COLUMN_THREAD_I(1, G.ny, 1, G.nx + 1)
   ROW_RUN(nz)
   const double two = 2.0, hlf = 0.5, qrt = 0.25;
@@ -139,7 +145,7 @@ template <typename T> __global__ void k_rhs_uf(GeoView G, ModelViewT<T> M, doubl
   }
 }
 
-template <typename T> __global__ void k_rhs_vf(GeoView G, ModelViewT<T> M, double *__restrict__ fx, int KR) {
+template <typename T> __global__ __launch_bounds__(256) void k_rhs_vf(GeoView G, ModelViewT<T> M, double *__restrict__ fx, int KR) {
   COLUMN_THREAD_I(1, G.ny + 1, 1, G.nx)
   ROW_RUN(nz)
   const double two = 2.0, hlf = 0.5, qrt = 0.25;
@@ -182,7 +188,7 @@ template <typename T> __global__ void k_rhs_vf(GeoView G, ModelViewT<T> M, doubl
   }
 }
 
-template <typename T> __global__ void k_rhs_wf(GeoView G, ModelViewT<T> M, double *__restrict__ fz, int KR) {
+template <typename T> __global__ __launch_bounds__(256) void k_rhs_wf(GeoView G, ModelViewT<T> M, double *__restrict__ fz, int KR) {
   COLUMN_THREAD_I(1, G.ny, 1, G.nx)
   ROW_RUN(nz + 1)
   const double hlf = 0.5, qrt = 0.25;
@@ -252,7 +258,7 @@ __global__ void k_rhs_accum_m(GeoView G, double *__restrict__ bm, const double *
 
 // correct_uvw (mg_correct_uvw.f90:73-108); pm = level-1 pressure in model layout (halo included).
 // dzw(k) of the reference (zr(k)-zr(k-1), top: zw(nz+1)-zr(nz)) is the same expression as grid(1)%dzw.
-template <typename T> __global__ void k_correct_uvw_m(GeoView G, const double *__restrict__ pm, ModelViewT<T> M, int KR) {
+template <typename T> __global__ __launch_bounds__(256) void k_correct_uvw_m(GeoView G, const double *__restrict__ pm, ModelViewT<T> M, int KR) {
   COLUMN_THREAD_I(0, G.ny + 1, 0, G.nx + 1)
   ROW_RUN(nz)
   const double one = 1.0, hlf = 0.5;
@@ -284,9 +290,13 @@ template <typename T> __global__ void k_correct_uvw_m(GeoView G, const double *_
 static inline dim3 igrid(int ni, int nj) { return dim3((ni + 63) / 64, (nj + 3) / 4); }
 static const dim3 IBLK(64, 4);
 // the kernels' view of the model state: the ModelView of the call with u, v, w as the scalar type its tag names
-template <typename T> static inline ModelViewT<T> typed(const ModelView *M) { return ModelViewT<T>{(T *)M->u, (T *)M->v, (T *)M->w, M->rmask, M->bmask}; }
+// and the strides of the call (the *_view entries) or of the densely packed arrays
+template <typename T> static inline ModelViewT<T> typed(const ModelView *M, const GeoView *G) {
+  const mgx_state_strides s = M->view ? M->str : state_dense_strides(G->nx, G->ny, G->nz);
+  return ModelViewT<T>{(T *)M->u, (T *)M->v, (T *)M->w, M->rmask, M->bmask, s.u_sj, s.u_sk, s.v_sj, s.v_sk, s.w_sj, s.w_sk};
+}
 // one launch of a model kernel, the instance for the state's type; ... = the kernel's arguments with STATE(M) where it takes the state
-#define STATE(M) typed<T>(M)
+#define STATE(M) typed<T>(M, G)
 #define LAUNCH_FOR_STATE(kern, g, M, ...)                                                        \
   do {                                                                                           \
     if ((M)->f32) { using T = float; hipLaunchKernelGGL(kern<T>, g, IBLK, 0, st, __VA_ARGS__); } \

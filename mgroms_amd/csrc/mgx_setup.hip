@@ -131,6 +131,23 @@ __global__ void k_halo_ref_closed(double *__restrict__ a, int nzz, int nh, int n
 #undef AI
 }
 
+// mgx_update_zeta_device_view: the model's zeta(0:nx+1, 0:ny+1), i fastest with rows sj elements apart, into the level-1 array (0:ny+1, 0:nx+1),
+// j fastest -- an LDS-tiled transpose, 32 x 32 tiles, block 32 x 8: lanes run along i for the loads and along j for the stores.  Only the
+// logical elements of a row are read; the padding behind them is not.
+__global__ __launch_bounds__(256) void k_zeta_view(const double *__restrict__ src, long long sj, double *__restrict__ dst, int nx, int ny) {
+  __shared__ double t[32][33];
+  const int i0 = blockIdx.x * 32, j0 = blockIdx.y * 32;
+  for (int r = threadIdx.y; r < 32; r += 8) {
+    const int j = j0 + r, i = i0 + threadIdx.x;
+    if (i <= nx + 1 && j <= ny + 1) t[r][threadIdx.x] = src[(long long)j * sj + i];
+  }
+  __syncthreads();
+  for (int r = threadIdx.y; r < 32; r += 8) {
+    const int i = i0 + r, j = j0 + threadIdx.x;
+    if (i <= nx + 1 && j <= ny + 1) dst[(long long)i * (ny + 2) + j] = t[threadIdx.x][r];
+  }
+}
+
 // The zeta refresh of a time step (mgx_update_zeta_device) on a hierarchy whose levels are all closed and un-gathered: k_coarsen2d and
 // k_halo_ref_closed (nzz = 1, nh = 1) of EVERY level in one launch.  A workgroup owns the aligned ZC_T x ZC_T tile of the chain's first
 // level (whose interior is given) and what lies under it on the coarser ones: it loads the tile into LDS (lanes along j, the fastest index:
@@ -475,6 +492,9 @@ static inline dim3 kgrid(int nk, int nj, int ni) { return dim3((unsigned)(((long
 extern "C" {
 void mgxs_coarsen2d(hipStream_t st, const double *src, double *dst, int nyf, int nyc, int nxc, double fac) {
   hipLaunchKernelGGL(k_coarsen2d, cgrid(nyc, nxc), CBLK, 0, st, src, dst, nyf, nyc, nxc, fac);
+}
+void mgxs_zeta_view(hipStream_t st, const double *src, long long sj, double *dst, int nx, int ny) {
+  hipLaunchKernelGGL(k_zeta_view, dim3((nx + 2 + 31) / 32, (ny + 2 + 31) / 32), dim3(32, 8), 0, st, src, sj, dst, nx, ny);
 }
 void mgxs_rect(hipStream_t st, double *a, double *buf, const RectOp *R) {
   const long long n = (long long)(R->j1 - R->j0 + 1) * (R->i1 - R->i0 + 1) * R->nzz;

@@ -8,9 +8,12 @@
 // one generic halo / copy operation on a reference-layout array (mgx_setup.hip: k_rect)
 struct RectOp { int op, nzz, nh, ny, j0, j1, i0, i1, mj, cj, mi, ci, mj2, cj2, mi2, ci2; };
 // the model state of a call.  u, v, w point to doubles (f32 = 0) or to floats (f32 = 1: the mgx_*_f32 entries); the wrappers hand the kernels
-// the typed view of it.  rmask: i-fastest copy of the level-1 mask (only read when bmask)
-struct ModelView { void *u, *v, *w; double *rmask; int bmask, f32; };
-template <typename T> struct ModelViewT { T *u, *v, *w; double *rmask; int bmask; };
+// the typed view of it.  rmask: i-fastest copy of the level-1 mask (only read when bmask).  view = 1: u, v, w are the model's own padded arrays
+// and `str` holds their strides (the *_view entries, include/mgx.h); view = 0: the densely packed arrays, whose strides the wrappers work out
+// from the level's shape (str is not read).  u, v, w name the first logical element either way: u(1,0,1), v(0,1,1), w(0,0,0).
+struct ModelView { void *u, *v, *w; double *rmask; int bmask, f32; int view; mgx_state_strides str; };
+// the kernels' state: element strides from row j to j + 1 (sj) and from level k to k + 1 (sk) of each array; the i stride is 1
+template <typename T> struct ModelViewT { T *u, *v, *w; double *rmask; int bmask; long long usj, usk, vsj, vsk, wsj, wsk; };
 struct ExMap;   // mgx_export.h: the geometry of one CSR export
 
 extern "C" {
@@ -129,6 +132,7 @@ void mgxk_coarse2fine_held(hipStream_t st, const LevView *F, const LevView *C, c
 
 // ---- mgx_setup.hip ----
 void mgxs_coarsen2d(hipStream_t st, const double *src, double *dst, int nyf, int nyc, int nxc, double fac);
+void mgxs_zeta_view(hipStream_t st, const double *src, long long sj, double *dst, int nx, int ny);
 void mgxs_rect(hipStream_t st, double *a, double *buf, const RectOp *R);
 void mgxs_halo_ref_closed(hipStream_t st, double *a, int nzz, int nh, int ny, int nx);
 int mgxs_zeta_chain_depth(void);

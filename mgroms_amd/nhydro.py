@@ -9,7 +9,7 @@ import warnings
 
 import numpy as np
 
-from ._lib import Params, MgxError, lib, check  # noqa: F401
+from ._lib import Params, MgxError, StateStrides, lib, check  # noqa: F401
 
 FIELD = {"p": 0, "b": 1, "r": 2, "cA": 3, "dx": 4, "dy": 5, "zeta": 6, "h": 7, "zr": 8, "zw": 9, "cw": 10, "rmask": 14}
 _DP = C.POINTER(C.c_double)
@@ -199,6 +199,65 @@ def nhydro_check_nondivergence_device(u, v, w, rmask=None):
     prm = None if rmask is None else _dev(rmask, (nx + 2, ny + 2), "rmask")
     _wait_for_caller()
     check(getattr(lib(), "mgx_check_nondivergence_device" + sfx)(*ptrs, prm))
+
+
+# ---- the state in the model's own padded arrays (include/mgx.h: the *_view entries) ----
+def state_strides_check(nx, ny, nz, strides):
+    """mgx_state_strides_check: strides = (u_sj, u_sk, v_sj, v_sk, w_sj, w_sk) in elements; raises MgxError, in the library's words, for
+    strides that cannot hold an nx x ny x nz state.  Host only: needs neither a GPU nor nhydro_init."""
+    s = StateStrides(*(int(x) for x in strides))
+    check(lib().mgx_state_strides_check(int(nx), int(ny), int(nz), C.byref(s)))
+
+
+def _uvw_view(u, v, w, entry):
+    """device u, v, w that may be views: torch CUDA tensors of the model's shapes with unit stride along i, all float64 or all float32
+    -> (f32, the three pointers, the strides as the tensors have them: the library judges them)"""
+    if _state.dims is None:
+        check(getattr(lib(), entry)(None, None, None, C.byref(StateStrides()), 0, None))   # the library's refusal (no mgx_init), in its words
+    sfx = _one_dtype([str(getattr(a, "dtype", type(a))) for a in (u, v, w)], ("torch.float64", "torch.float32"), "tensors")
+    strides = []
+    for a, (sh, n) in zip((u, v, w), _uvw_shapes()):
+        if not (hasattr(a, "is_cuda") and a.is_cuda and tuple(a.shape) == sh):
+            raise ValueError(f"{n}: need a float64 or float32 CUDA tensor of shape {sh} (it may be a view)")
+        if a.stride(-1) != 1:
+            raise ValueError(f"{n}: need stride 1 along i (the last dimension), got {a.stride(-1)}")
+        strides += [a.stride(1), a.stride(0)]
+    return 1 if sfx else 0, [C.c_void_p(a.data_ptr()) for a in (u, v, w)], StateStrides(*strides)
+
+
+def _call_view(entry, u, v, w, rmask):
+    f32, ptrs, s = _uvw_view(u, v, w, entry)
+    nx, ny, nz = _state.dims
+    prm = None if rmask is None else _dev(rmask, (nx + 2, ny + 2), "rmask")
+    _wait_for_caller()
+    check(getattr(lib(), entry)(*ptrs, C.byref(s), f32, prm))
+
+
+def nhydro_solve_view(u, v, w, rmask=None):
+    """nhydro_solve_device on the model's own padded arrays: u, v, w are torch CUDA tensors of the shapes of nhydro_solve that may be views
+    -- e.g. U[:, 2:-2, 3:-2] of a tensor with ghost cells -- with unit stride along i; the other strides go to the library as they are
+    (include/mgx.h: mgx_solve_device_view).  Only the elements of the views are read or written.  rmask: dense, as in nhydro_solve_device."""
+    _call_view("mgx_solve_device_view", u, v, w, rmask)
+
+
+def nhydro_check_nondivergence_view(u, v, w, rmask=None):
+    """nhydro_check_nondivergence_device on views (as nhydro_solve_view): u, v, w are only read, the divergence is left in grid(1).b"""
+    _call_view("mgx_check_nondivergence_device_view", u, v, w, rmask)
+
+
+def nhydro_update_zeta_view(zeta):
+    """nhydro_update_zeta_device from the model's own zeta: a float64 torch CUDA tensor of shape (ny+2, nx+2) -- i fastest -- that may be a
+    view with unit stride along i; its row pitch goes to the library (include/mgx.h: mgx_update_zeta_device_view)."""
+    if _state.dims is None:
+        check(lib().mgx_update_zeta_device_view(None, 0))   # the library's refusal (no mgx_init), in its words
+    nx, ny, _ = _state.dims
+    ok = hasattr(zeta, "is_cuda") and zeta.is_cuda and tuple(zeta.shape) == (ny + 2, nx + 2) and str(zeta.dtype) == "torch.float64"
+    if not ok:
+        raise ValueError(f"zeta: need a float64 CUDA tensor of shape {(ny + 2, nx + 2)} (it may be a view)")
+    if zeta.stride(-1) != 1:
+        raise ValueError(f"zeta: need stride 1 along i (the last dimension), got {zeta.stride(-1)}")
+    _wait_for_caller()
+    check(lib().mgx_update_zeta_device_view(C.c_void_p(zeta.data_ptr()), zeta.stride(0)))
 
 
 def nhydro_check_nondivergence(u, v, w, rmask=None):
