@@ -61,6 +61,21 @@ module mgx_c
        import :: c_int, c_ptr
        type(c_ptr), value :: zeta
      end function mgx_update_zeta_device
+     ! the matrices from the model's own vertical grid (include/mgx.h): host arrays in the library's dense layout, or DEVICE pointers with
+     ! the strides of the model's padded arrays (strides = c_null_ptr: the dense layout)
+     integer(c_int) function mgx_matrices_depths(dx, dy, zr, zw, rmask) bind(C, name='mgx_matrices_depths')
+       import :: c_int, c_double, c_ptr
+       real(c_double), intent(in) :: dx(*), dy(*), zr(*), zw(*)
+       type(c_ptr), value :: rmask
+     end function mgx_matrices_depths
+     integer(c_int) function mgx_matrices_depths_device(dx, dy, zr, zw, strides, rmask) bind(C, name='mgx_matrices_depths_device')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: dx, dy, zr, zw, strides, rmask
+     end function mgx_matrices_depths_device
+     integer(c_int) function mgx_update_depths_device(zr, zw, strides) bind(C, name='mgx_update_depths_device')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: zr, zw, strides
+     end function mgx_update_depths_device
      integer(c_int) function mgx_check_nondivergence_device(u, v, w, rmask) bind(C, name='mgx_check_nondivergence_device')
        import :: c_int, c_ptr
        type(c_ptr), value :: u, v, w, rmask

@@ -117,6 +117,39 @@ contains
     call mgx_check(mgx_check_nondivergence_device(ua, va, wa, rmaska), 'nhydro_check_nondivergence_device')
   end subroutine nhydro_check_nondivergence_device
 
+  !--------------------------------------------------------------  (no counterpart in the reference, which evaluates its own stretching)
+  ! nhydro_matrices for a model that owns its vertical grid: instead of zeta, h and the sigma parameters, the depths of level 1 in the
+  ! layout grid_get(1,'zr',.) / grid_get(1,'zw',.) return, zr(nz,-1:ny+2,-1:nx+2) and zw(nz+1,-1:ny+2,-1:nx+2).  Only the columns
+  ! j = 1..ny, i = 1..nx are read; the coarser levels' depths are averages of these (include/mgx.h: mgx_matrices_depths).
+  subroutine nhydro_matrices_depths(dx, dy, zr, zw, rmask)
+    real(kind=rp), dimension(:,:)         , intent(in) :: dx, dy
+    real(kind=rp), dimension(:,:,:)       , intent(in) :: zr, zw
+    real(kind=rp), dimension(:,:), pointer, intent(in) :: rmask
+    real(kind=rp), dimension(:,:), allocatable :: a, b           ! contiguous copies of the assumed-shape arguments
+    real(kind=rp), dimension(:,:,:), allocatable :: c, d
+    real(kind=rp), dimension(:,:), allocatable, target :: m
+    allocate(a, source=dx); allocate(b, source=dy); allocate(c, source=zr); allocate(d, source=zw)
+    if (associated(rmask)) then   ! only read by the library when bmask=.true.
+       allocate(m, source=rmask)
+       call mgx_check(mgx_matrices_depths(a, b, c, d, c_loc(m)), 'nhydro_matrices_depths')
+    else
+       call mgx_check(mgx_matrices_depths(a, b, c, d, c_null_ptr), 'nhydro_matrices_depths')
+    endif
+  end subroutine nhydro_matrices_depths
+
+  ! ... and for a model that keeps them on the GPU: DEVICE addresses; strides = c_null_ptr for the layout above, else the address of the four
+  ! integer(c_long_long) zr_sj, zr_sk, zw_sj, zw_sk of the model's own i-fastest padded arrays, zr and zw then naming z_r(1,1,1) and
+  ! z_w(1,1,0).  nhydro_update_depths_device is the per-step call: new depths under the dx, dy, rmask of the last set-up.
+  subroutine nhydro_matrices_depths_device(dx, dy, zr, zw, strides, rmask)
+    type(c_ptr), value, intent(in) :: dx, dy, zr, zw, strides, rmask
+    call mgx_check(mgx_matrices_depths_device(dx, dy, zr, zw, strides, rmask), 'nhydro_matrices_depths_device')
+  end subroutine nhydro_matrices_depths_device
+
+  subroutine nhydro_update_depths_device(zr, zw, strides)
+    type(c_ptr), value, intent(in) :: zr, zw, strides
+    call mgx_check(mgx_update_depths_device(zr, zw, strides), 'nhydro_update_depths_device')
+  end subroutine nhydro_update_depths_device
+
   !--------------------------------------------------------------  (nhydro.f90:137-141)
   subroutine nhydro_clean()
     call mgx_clean()

@@ -173,6 +173,55 @@ int mgx_solve_device_view(void *u, void *v, void *w, const mgx_state_strides *s,
 int mgx_check_nondivergence_device_view(void *u, void *v, void *w, const mgx_state_strides *s, int f32, const double *rmask_dev);
 int mgx_update_zeta_device_view(const double *zeta_dev, long long sj);
 
+/* ---- the matrices from the model's own vertical grid: z_r, z_w instead of h, zeta and a stretching (no Fortran counterpart in the
+ * reference, whose nhydro_matrices evaluates setup_zr_zw_croco / new_s_coord on every level) ----
+ * For a model whose depths the library's one stretching does not produce -- the old S-coordinate, a stretching function of its own, ALE or
+ * z-tilde variants: the caller hands over the depths of its rho points, zr(k), k = 1..nz, and of its interfaces, zw(k), k = 1..nz+1
+ * (the model's z_w(0..N)), of level 1, and the library builds every level's operator from depths alone.
+ * Coarser levels.  With (J, I) a coarse column, fj = 2J-1, fi = 2I-1 its four fine columns and
+ *     avg(x) = 0.25 * (x(fj,fi) + x(fj+1,fi) + x(fj,fi+1) + x(fj+1,fi+1))     (in that order)
+ * a pair of levels that halves nz (nz_F even) takes zw_C(kc) = avg(zw_F(2kc-1)), kc = 1..nz_C+1, and zr_C(kc) = avg(zw_F(2kc)), kc = 1..nz_C:
+ * a coarse rho point is a fine interface; a held pair ("hold_z_levels", "hold_odd_nz": nz_C = nz_F) takes zw_C(k) = avg(zw_F(k)),
+ * zr_C(k) = avg(zr_F(k)).  For a constant h and zeta this is the sigma hierarchy of mgx_matrices bit for bit; elsewhere it is a hierarchy
+ * of its own (on a seamount 5e-6 ... 5e-4 of the depth away), which no reference pins.  A hierarchy that halves an ODD nz is refused, with
+ * the level named: the rule has no top interface there; option "hold_odd_nz" = 1 is the way out.
+ * Layouts.  s == NULL: the library's dense layout, what mgx_get_field(1, MGX_ZR / MGX_ZW, ...) returns -- zr(nz, -1:ny+2, -1:nx+2),
+ * zw(nz+1, -1:ny+2, -1:nx+2), k fastest, two halo cells per side; the host entry takes only this one.  With s the pointers name
+ * z_r(1,1,1) and z_w(1,1,0) of the model's own arrays, i fastest:
+ *     zr(i,j,k) = zr_dev[(i-1) + (j-1) zr_sj + (k-1) zr_sk],   zw(i,j,k) = zw_dev[(i-1) + (j-1) zw_sj + (k-1) zw_sk],   k from 1
+ * In EVERY layout only i = 1..nx, j = 1..ny are read: halos and padding are neither read nor written.  The library fills its own halos by
+ * its own rules (the fill_halo of zr, zw with two cells: extrapolation at a closed side, the neighbour's columns at a rank seam or a
+ * periodic side); h and zeta of every level are then set to -zw(1) and zw(nz+1), so that grid(lev)%h, %zeta stay what they mean.
+ * dx, dy, rmask: as in mgx_matrices / mgx_matrices_device, dense; rmask may be NULL unless bmask.
+ * Monotone depths are the caller's duty: zw strictly increasing in k and zw(k) < zr(k) < zw(k+1) in every column.  It is not checked.
+ * mgx_depth_strides_check: host only, needs neither a GPU nor mgx_init; the refusals of mgx_state_strides_check in its words, for the
+ * arrays zr (nx x ny x nz) and zw (nx x ny x (nz+1)): a stride that is not positive, an sj below the row length nx, an sk below sj x ny, an
+ * extent beyond 63 bits.  The device entries call it first and refuse in its words.
+ * mgx_update_depths_device: the per-step call -- new depths under the dx, dy, rmask of the last set-up; rebuilt, by the kernels of
+ * mgx_matrices_depths_device in their order and hence bit for bit what it leaves: zr, zw, h, zeta, cw, cA of every level, the pivots, the
+ * slopes, the red-black extras and the model-space copies.  Waits or, under option "async" = 1, only enqueues, exactly as
+ * mgx_update_zeta_device does (the read-back of sequential-order red-black included).  Counted by the read-only option "depth_refreshes".
+ * While the depths are the caller's:
+ * - mgx_update_zeta_device and mgx_update_zeta_device_view are refused: there is no h and no stretching to apply a new zeta to;
+ * - the levels keep their slopes (the operator, the transfers and the colour passes below nz = 32 stay matrix-free) and lose the nine
+ *   fields from which the fastest kernels generate slots 4 / 7 and zw: those kernels' stored-slot instances run instead, and the colour
+ *   pass of a level with nz >= 32 -- which has no instance between the two -- takes the stored coefficients.  The same bits either way.
+ * - everything else is served as after mgx_matrices_device: every relax_method, "krylov", bmask, "periodic", "hold_odd_nz",
+ *   "hold_z_levels", process grids with gathered levels (the calls are then collective), the _f32 and _view state entries,
+ *   "coarsest_direct", "small_any_nz", the CSR export, and the fp32 cycles, whose coefficients are conversions of the stored fp64 ones.
+ * A later mgx_matrices / mgx_matrices_device restores the library's own grid and its generated fields; so does mgx_clean.
+ * mgx_depths_launch: the launches of the kernels above for a level 1 of nx x ny x nz, pure host logic (mgx_choice_depths.h): out[0..7] =
+ * the transpose of the strided layout (i tiles, k tiles of zr, of zw, grid.x, grid.y, block.x, block.y, LDS bytes), out[8..9] = the dense
+ * copy (grid, block), out[10..11] = the coarsening onto level 2 (grid, block), out[12..15] = the h, zeta pass (grid.x, grid.y, block.x,
+ * block.y), out[16] = 1 where the level's colour pass takes the stored coefficients. */
+typedef struct { long long zr_sj, zr_sk, zw_sj, zw_sk; } mgx_depth_strides;   /* in elements; the i stride is 1 */
+int mgx_depth_strides_check(int nx, int ny, int nz, const mgx_depth_strides *s);
+int mgx_matrices_depths(const double *dx, const double *dy, const double *zr, const double *zw, const double *rmask);
+int mgx_matrices_depths_device(const double *dx_dev, const double *dy_dev, const double *zr_dev, const double *zw_dev,
+                               const mgx_depth_strides *s, const double *rmask_dev);
+int mgx_update_depths_device(const double *zr_dev, const double *zw_dev, const mgx_depth_strides *s);
+int mgx_depths_launch(int nx, int ny, int nz, int *out);
+
 /* mg_solvers.f90:17-101 solve_p(tol,maxite).  *nite = iterations done, *res = last ||r||/||b||,
  * hist (may be NULL, else >= maxite+1 doubles) = normalised residual after each iteration, hist[0] = initial. */
 int mgx_solve_p(double tol, int maxite, int *nite, double *res, double *hist);
@@ -248,7 +297,8 @@ int mgx_level_table_semi(int nx, int ny, int nz, int npx, int npy, int rank, int
  * 2^m * min(dx, dy) >= max(h) / nz, both extrema over the interior (i = 1..nx, j = 1..ny) -- the coarsenings in x and y after which the cells
  * are no longer taller than wide.  dx, dy, h: HOST arrays in the layout of mgx_matrices, (0:ny+1, 0:nx+1) with j fastest.  Pure host logic,
  * usable before mgx_init and without a GPU.  On a process grid every rank must build the same hierarchy: the caller takes the MAXIMUM of *m
- * over the ranks and sets that.  Returns 0, or non-zero (mgx_last_error) for NULL arguments and a geometry that is not positive and finite. */
+ * over the ranks and sets that.  Returns 0, or non-zero (mgx_last_error) for NULL arguments and a geometry that is not positive and finite.
+ * A model that hands over its own depths (mgx_matrices_depths*) has no h array of this kind: h = -zw(1), the depth of the bottom interface. */
 int mgx_hold_z_hint(const double *dx, const double *dy, const double *h, int nx, int ny, int nz, int *m);
 /* The first level of the tail of an fp32 cycle (option "mixed_tail") on the one-rank hierarchy of nx x ny x nz: *first = the finest level from
  * which every level down to the coarsest has at most 32768 cells and nz <= 32, 0 = no level is that small.  Pure host logic, usable before

@@ -9,10 +9,12 @@ from .nhydro import (nhydro_init, nhydro_matrices, nhydro_solve, nhydro_check_no
                      solve_p, Fcycle, Vcycle, Vcycle2, relax, compute_residual, fine2coarse, coarse2fine, fill_halo,
                      grid, nlevs, Params, read_nhnamelist,
                      nhydro_matrices_device, nhydro_update_zeta_device, nhydro_check_nondivergence_device,
-                     nhydro_solve_view, nhydro_check_nondivergence_view, nhydro_update_zeta_view)
+                     nhydro_solve_view, nhydro_check_nondivergence_view, nhydro_update_zeta_view,
+                     nhydro_matrices_depths, nhydro_matrices_depths_device, nhydro_update_depths_device)
 
 __all__ = ["nhydro", "nhydro_init", "nhydro_matrices", "nhydro_solve", "nhydro_check_nondivergence", "nhydro_clean",
            "solve_p", "Fcycle", "Vcycle", "Vcycle2", "relax", "compute_residual", "fine2coarse", "coarse2fine", "fill_halo",
            "grid", "nlevs", "Params", "read_nhnamelist",
            "nhydro_matrices_device", "nhydro_update_zeta_device", "nhydro_check_nondivergence_device",
-           "nhydro_solve_view", "nhydro_check_nondivergence_view", "nhydro_update_zeta_view"]
+           "nhydro_solve_view", "nhydro_check_nondivergence_view", "nhydro_update_zeta_view",
+           "nhydro_matrices_depths", "nhydro_matrices_depths_device", "nhydro_update_depths_device"]

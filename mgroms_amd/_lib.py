@@ -24,6 +24,11 @@ class StateStrides(C.Structure):
     _fields_ = [(n, C.c_longlong) for n in ("u_sj", "u_sk", "v_sj", "v_sk", "w_sj", "w_sk")]
 
 
+class DepthStrides(C.Structure):
+    """mgx_depth_strides (include/mgx.h): element strides from row j to j + 1 (sj) and from level k to k + 1 (sk) of zr, zw"""
+    _fields_ = [(n, C.c_longlong) for n in ("zr_sj", "zr_sk", "zw_sj", "zw_sk")]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p),
                           C.POINTER(C.c_void_p), C.POINTER(C.c_int))
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int)
@@ -48,6 +53,11 @@ _SIGS = {
     "mgx_solve_device_view": (C.c_int, [C.c_void_p] * 3 + [C.POINTER(StateStrides), C.c_int, C.c_void_p]),
     "mgx_check_nondivergence_device_view": (C.c_int, [C.c_void_p] * 3 + [C.POINTER(StateStrides), C.c_int, C.c_void_p]),
     "mgx_update_zeta_device_view": (C.c_int, [C.c_void_p, C.c_longlong]),
+    "mgx_depth_strides_check": (C.c_int, [C.c_int] * 3 + [C.POINTER(DepthStrides)]),
+    "mgx_matrices_depths": (C.c_int, [_DP, _DP, _DP, _DP, _DP]),
+    "mgx_matrices_depths_device": (C.c_int, [C.c_void_p] * 4 + [C.POINTER(DepthStrides), C.c_void_p]),
+    "mgx_update_depths_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DepthStrides)]),
+    "mgx_depths_launch": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_int)]),
     "mgx_solve_f32": (C.c_int, [_FP, _FP, _FP, _DP]),
     "mgx_compute_rhs_f32": (C.c_int, [_FP, _FP, _FP, _DP]),
     "mgx_check_nondivergence_f32": (C.c_int, [_FP, _FP, _FP, _DP]),

@@ -5,6 +5,7 @@
 #include "mgx_host.h"
 #include "mgx_export.h"
 #include "mgx_state_view.h"
+#include "mgx_depth_view.h"
 
 namespace mgx_host {
 
@@ -105,6 +106,7 @@ const Opt OPTIONS[] = {
   {"zeta_refreshes", nullptr, CNT(n_zeta_refresh), nullptr, ENV_NONE, RO, false},
   {"zeta_chain_launches", nullptr, CNT(n_zeta_chain), nullptr, ENV_NONE, RO, false},
   {"hold_z_fused", nullptr, CNT(n_hold_z_fused), nullptr, ENV_NONE, RO, false},
+  {"depth_refreshes", nullptr, CNT(n_depth_refresh), nullptr, ENV_NONE, RO, false},
 };
 #undef PAR
 #undef CNT
@@ -281,6 +283,7 @@ int mgx_update_zeta_device(const double *zeta_dev) {
   NEED_INIT();
   if (!S.have_geometry) return fail("mgx_update_zeta_device: no dx, dy, h to keep: call mgx_matrices or mgx_matrices_device first");
   if (!zeta_dev) return fail("mgx_update_zeta_device: zeta_dev is NULL");
+  if (S.depths_user) return fail("mgx_update_zeta_device: the depths in use are the caller's (mgx_matrices_depths): there is no h and no stretching to apply a new zeta to; hand over the new depths with mgx_update_depths_device");
   Level &L = S.lev[0];
   HIPCHK(hipMemcpyAsync(L.g.zeta, zeta_dev, (size_t)(L.ny + 2) * (L.nx + 2) * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
   CHK(define_matrices(DM_ZETA, true));
@@ -293,6 +296,7 @@ int mgx_update_zeta_device_view(const double *zeta_dev, long long sj) {
   NEED_INIT();
   if (!S.have_geometry) return fail("mgx_update_zeta_device_view: no dx, dy, h to keep: call mgx_matrices or mgx_matrices_device first");
   if (!zeta_dev) return fail("mgx_update_zeta_device_view: zeta_dev is NULL");
+  if (S.depths_user) return fail("mgx_update_zeta_device_view: the depths in use are the caller's (mgx_matrices_depths): there is no h and no stretching to apply a new zeta to; hand over the new depths with mgx_update_depths_device");
   Level &L = S.lev[0];
   long long last;
   if (sj < L.nx + 2) return fail("mgx_update_zeta_device_view: sj = %lld is below the row length of zeta, %d: rows would overlap", sj, L.nx + 2);
@@ -301,6 +305,85 @@ int mgx_update_zeta_device_view(const double *zeta_dev, long long sj) {
   mgxs_zeta_view(S.stream, zeta_dev, sj, L.g.zeta, L.nx, L.ny); S.n_launch++;
   CHK(define_matrices(DM_ZETA, true));
   S.n_zeta_refresh++;
+  return 0;
+}
+
+// ---- the matrices from the caller's own vertical grid (include/mgx.h: mgx_matrices_depths*) ----
+// the caller's zr, zw into the interior of the level-1 arrays: host arrays (the dense layout only) by two pitched copies, device arrays by
+// k_depths_copy (dense, s == nullptr) or k_depths_in (the model's i-fastest padded arrays)
+static int depths_in(const double *zr, const double *zw, const mgx_depth_strides *s, bool dev, const char *who) {
+  Level &L = S.lev[0];
+  if (!zr || !zw) return fail("%s: zr or zw is NULL", who);
+  if (s) {
+    char why[256];
+    if (depth_strides_refusal(L.nx, L.ny, L.nz, s, why, sizeof why)) return fail("%s: %s", who, why);
+    mgxd_in(S.stream, zr, zw, s, &L.g); S.n_launch++;
+  } else if (dev) {
+    mgxd_copy(S.stream, zr, zw, &L.g); S.n_launch++;
+  } else {  // per plane i the interior rows j = 1..ny are one run of ny columns
+    const double *src[2] = {zr, zw}; double *dst[2] = {L.g.zr, L.g.zw};
+    for (int q = 0; q < 2; q++) {
+      const size_t nzz = (size_t)L.nz + q, pitch = (size_t)(L.ny + 4) * nzz * sizeof(double), first = ((size_t)2 * (L.ny + 4) + 2) * nzz;
+      HIPCHK(hipMemcpy2DAsync(dst[q] + first, pitch, src[q] + first, pitch, (size_t)L.ny * nzz * sizeof(double), (size_t)L.nx, hipMemcpyHostToDevice, S.stream));
+    }
+  }
+  return 0;
+}
+
+// a pair of levels halves an odd nz: define_matrices refuses such a hierarchy, and the entries ask before they touch level 1
+static bool depths_unserved() {
+  for (int l = 1; l < S.nlevs; l++)
+    if (S.lev[l].nz != S.lev[l - 1].nz && (S.lev[l - 1].nz & 1)) return true;
+  return false;
+}
+
+static int matrices_depths_from(const double *dx, const double *dy, const double *zr, const double *zw, const mgx_depth_strides *s, const double *rmask,
+                                bool dev, const char *who) {
+  NEED_INIT();
+  if (!dx || !dy) return fail("%s: dx or dy is NULL", who);
+  if (S.par.bmask && !rmask) return fail("bmask=.true. needs rmask in %s (nhydro.f90:52-55)", who);
+  if (S.verbose && S.rank == 0) printf("  nhydro_matrices (depths):\n");
+  Level &L = S.lev[0];
+  const size_t n2 = (size_t)(L.ny + 2) * (L.nx + 2) * sizeof(double);
+  const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  // (refusals first: nothing of the level is touched by a call that is refused)
+  if (!zr || !zw) return fail("%s: zr or zw is NULL", who);
+  char why[256];
+  if (s && depth_strides_refusal(L.nx, L.ny, L.nz, s, why, sizeof why)) return fail("%s: %s", who, why);
+  if (depths_unserved()) return define_matrices(DM_DEPTHS_ALL, dev);   // its refusal, in its words
+  HIPCHK(hipMemcpyAsync(L.g.dx, dx, n2, kind, S.stream));
+  HIPCHK(hipMemcpyAsync(L.g.dy, dy, n2, kind, S.stream));
+  if (S.par.bmask) HIPCHK(hipMemcpyAsync(L.g.rmask, rmask, n2, kind, S.stream));
+  CHK(depths_in(zr, zw, s, dev, who));
+  return define_matrices(DM_DEPTHS_ALL, dev);
+}
+
+int mgx_depth_strides_check(int nx, int ny, int nz, const mgx_depth_strides *s) {
+  char why[256];
+  return depth_strides_refusal(nx, ny, nz, s, why, sizeof why) ? fail("mgx_depth_strides_check: %s", why) : 0;
+}
+int mgx_matrices_depths(const double *dx, const double *dy, const double *zr, const double *zw, const double *rmask) {
+  return matrices_depths_from(dx, dy, zr, zw, nullptr, rmask, false, "mgx_matrices_depths");
+}
+int mgx_matrices_depths_device(const double *dx_dev, const double *dy_dev, const double *zr_dev, const double *zw_dev, const mgx_depth_strides *s,
+                               const double *rmask_dev) {
+  return matrices_depths_from(dx_dev, dy_dev, zr_dev, zw_dev, s, rmask_dev, true, "mgx_matrices_depths_device");
+}
+// the per-step call of a resident model that owns its vertical grid: new depths under the dx, dy, rmask of the last set-up
+int mgx_update_depths_device(const double *zr_dev, const double *zw_dev, const mgx_depth_strides *s) {
+  NEED_INIT();
+  if (!S.have_geometry) return fail("mgx_update_depths_device: no dx, dy to keep: call mgx_matrices_depths, mgx_matrices_depths_device or mgx_matrices first");
+  if (depths_unserved()) return define_matrices(DM_DEPTHS, true);   // its refusal, in its words
+  CHK(depths_in(zr_dev, zw_dev, s, true, "mgx_update_depths_device"));
+  CHK(define_matrices(DM_DEPTHS, true));
+  S.n_depth_refresh++;
+  return 0;
+}
+// the launches of mgx_depths.hip for a level 1 of nx x ny x nz (mgx_choice_depths.h); pure host logic
+int mgx_depths_launch(int nx, int ny, int nz, int *out) {
+  if (!out) return fail("mgx_depths_launch: out is NULL");
+  if (nx < 2 || ny < 2 || nz < 2 || (nx & 1) || (ny & 1)) return fail("mgx_depths_launch: %d x %d x %d is not a level-1 size", nx, ny, nz);
+  mgxd_choice(nx, ny, nz, out);
   return 0;
 }
 

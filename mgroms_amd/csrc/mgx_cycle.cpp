@@ -47,6 +47,14 @@ void tt_collect() {
 // relax(): one file-local function per smoother mode; what a colour pass reports is PASS_* of mgx_wrappers.h
 namespace {
 
+// The view a colour pass of L takes: L.v as it stands at the call -- or, on a level built from the caller's depths whose pass would generate
+// slots 4 / 7 from the sigma fields the level no longer has (Level::pass_stored, mgx_choice_depths.h), L.v without its slopes: the
+// stored-coefficient instance of the same pass, the same bits.  The operator and the transfers of the level keep the slopes.
+struct PassView {
+  LevView t; const LevView *v;
+  explicit PassView(const Level &L) : v(&L.v) { if (L.pass_stored) { t = L.v; t.zy = t.zx = nullptr; v = &t; } }
+};
+
 // exact lexicographic order by hyperplanes; halo fill once per sweep (mg_relax.f90:131-141)
 int relax_gs(Level &L, int lev, int nsweeps) {
   for (int it = 1; it <= nsweeps; it++) {
@@ -65,7 +73,7 @@ int relax_rb_exact(Level &L, int nsweeps, Sides ph) {
   for (int it = 1; it <= nsweeps; it++)
     for (int rb = 1; rb <= 2; rb++) {
       int pass = 0;
-      for (int i = 1; i <= L.nx; i++) { pass = mgxk_relax_colour(S.stream, &L.v, i, 1, 1, -1, rb, 1, 0, ph); S.n_launch++; }
+      for (int i = 1; i <= L.nx; i++) { pass = mgxk_relax_colour(S.stream, PassView(L).v, i, 1, 1, -1, rb, 1, 0, ph); S.n_launch++; }
       if (pass & PASS_TALL_STORED) S.n_tall_stored++;
       CHK(fill_halo_js(L, L.v.p, pass & PASS_MIRRORS));
     }
@@ -125,7 +133,7 @@ int relax_rb(Level &L, int nsweeps, Sides ph, bool seq) {
       if (S.real && !chain && !(seq && closed && !(it == 1 && rb == 1))) { mgxk_snapshot_k1(S.stream, &L.v); S.n_launch++; }
       // (seq, wide half-rows: the pass also leaves the walk's d0 = y(k=1) - snapshot in u1 where its kernel can -- one launch less)
       L.v.d0w = (seq && S.rbseq_d0_in_pass && (mgxk_rbseq_wants_d0(&L.v) || (S.rbseq_window && L.rbs_m > 0))) ? L.v.u1 : nullptr;
-      const int pass = mgxk_relax_colour(S.stream, &L.v, 1, 1, L.nx, -1, rb, S.real, S.real, ph); S.n_launch++;
+      const int pass = mgxk_relax_colour(S.stream, PassView(L).v, 1, 1, L.nx, -1, rb, S.real, S.real, ph); S.n_launch++;
       L.v.d0w = nullptr;
       if (pass & PASS_TALL_STORED) S.n_tall_stored++;
       int mirrors = (pass & PASS_MIRRORS) ? 1 : 0;
@@ -146,11 +154,11 @@ int relax_fc_overlapped(Level &L, int fc1, int fc2, Sides ph) {
   HIPCHK(hipEventRecord(S.ev_a, S.stream));                 // the interior of the previous colour (and whatever came before)
   HIPCHK(hipStreamWaitEvent(S.stream2, S.ev_a, 0));
   ps.part = 1;
-  const int pass = mgxk_relax_colour(S.stream2, &L.v, 1 + (fc1 - 1) % 2, 2, L.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0, ps);
+  const int pass = mgxk_relax_colour(S.stream2, PassView(L).v, 1 + (fc1 - 1) % 2, 2, L.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0, ps);
   HIPCHK(hipEventRecord(S.ev_s, S.stream2));
   { hipStream_t keep = S.stream; S.stream = S.stream2; const int rc = fill_halo_js(L, L.v.p, pass & PASS_MIRRORS); S.stream = keep; if (rc) return rc; }
   ps.part = 2;
-  mgxk_relax_colour(S.stream, &L.v, 1 + (fc1 - 1) % 2, 2, L.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0, ps);
+  mgxk_relax_colour(S.stream, PassView(L).v, 1 + (fc1 - 1) % 2, 2, L.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0, ps);
   HIPCHK(hipStreamWaitEvent(S.stream, S.ev_s, 0));          // what follows on the solver's stream reads this colour's boundary part -- not its exchange
   S.n_launch += 2; S.n_overlap++;
   if (pass & PASS_TALL_STORED) S.n_tall_stored++;
@@ -168,7 +176,7 @@ int relax_fc(Level &L, int nsweeps, Sides ph) {
       if (closed && mgxk_relax_ks_pair(S.stream, &L.v, fc1, L.nx / 2, S.real, ph)) { S.n_launch++; continue; }
       for (int fc2 = 1; fc2 <= 2; fc2++) {
         if (ov) { CHK(relax_fc_overlapped(L, fc1, fc2, ph)); continue; }
-        const int pass = mgxk_relax_colour(S.stream, &L.v, 1 + (fc1 - 1) % 2, 2, L.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0, ph); S.n_launch++;
+        const int pass = mgxk_relax_colour(S.stream, PassView(L).v, 1 + (fc1 - 1) % 2, 2, L.nx / 2, fc2 == 1 ? 1 : 0, 0, S.real, 0, ph); S.n_launch++;
         if (pass & PASS_TALL_STORED) S.n_tall_stored++;
         CHK(fill_halo_js(L, L.v.p, pass & PASS_MIRRORS));
       }

@@ -1,6 +1,7 @@
 // Host side of libmgx.so, set-up: the level tables (mg_grids.f90), mgx_init's allocations, the matrix set-up (mg_define_matrix.f90),
 // the model coupling (mg_compute_rhs.f90, mg_correct_uvw.f90) on the device copies of u, v, w, and mgx_clean.
 #include "mgx_host.h"
+#include "mgx_choice_depths.h"
 
 namespace mgx_host {
 
@@ -98,6 +99,19 @@ int gather2d(Level &L, double *src_tmp, double *dst) {
   return 0;
 }
 
+// gather2d for the packed interior block of a 3-D depth array (nzz rows per column) the coarsening of the depths has left in `blk`:
+// all-gather into `gbuf`, then every member's block into its place in the level's array dst (nzz, -1:ny+2, -1:nx+2)
+static int gather_depths(Level &L, double *blk, double *gbuf, double *dst, int nzz) {
+  const int nxc = L.nx / L.ngx, nyc = L.ny / L.ngy, Ng = nzz * nxc * nyc;
+  if (!S.ag) return fail("a gather is needed but mgx_set_comm was not called");
+  if (S.ag(S.ctx, L.group, L.ngroup, blk, gbuf, Ng)) return fail("allgather callback failed");
+  for (int q = 0; q < L.ngroup; q++) {
+    const int l = q % L.ngx, m = q / L.ngx;
+    rect(dst, gbuf + (size_t)q * Ng, 4, nzz, 2, L.ny, 1 + m * nyc, (m + 1) * nyc, 1 + l * nxc, (l + 1) * nxc);
+  }
+  return 0;
+}
+
 // the planes of warm-up each level's windowed red-black walk needs (mgx_rbseq.hip: k_rbseq_window), from the rho the set-up has just copied back
 // (known = false: the set-up did not copy rho and the decay figures back -- every level keeps the walk over the whole level)
 void set_window_planes(bool known) {
@@ -158,11 +172,23 @@ static int wrap_rmask(Level &L) {
 // model-space copies of dx, dy, rmask are what the last DM_ALL left and stay; everything zeta reaches is rebuilt by the same kernels in the
 // same order.  may_return_early: the caller is one of the device entry points, which under option "async" only enqueue -- unless the
 // sequential-order red-black needs rho and the decay figures of the new coefficients on the host (set_window_planes).
+// what = DM_DEPTHS_ALL: the level-1 dx, dy (and rmask) are new and the interior of the level-1 zr, zw holds the caller's depths
+// (mgx_matrices_depths, mgx_matrices_depths_device); what = DM_DEPTHS: only those depths are new (mgx_update_depths_device).  No h, zeta or
+// stretching then: zeta and h are not coarsened, k_zr_zw and k_zw_js do not run; every coarser level's depths are averages of the finer
+// level's (k_depths_coarsen, the rule of DESIGN.md 6.4; through the packed blocks and an all-gather on a gathered level), h and zeta of
+// every level are read off its zw (k_depths_hz), and everything from the halo fills of zr, zw on is what the other modes run.  The levels
+// keep their slopes and lose the nine sigma fields (LevShape: slopes without zw); a level whose colour pass cannot do without them hands it
+// the stored coefficients (Level::pass_stored).  A halving from an odd nz is refused before anything is enqueued.
 int define_matrices(int what, bool may_return_early) {
-  const bool all = what == DM_ALL;
+  const bool depths = what == DM_DEPTHS_ALL || what == DM_DEPTHS;
+  const bool all = what == DM_ALL || what == DM_DEPTHS_ALL;
+  if (depths)
+    for (int l = 1; l < S.nlevs; l++)
+      if (depths_pair(S.lev[l - 1].nz, S.lev[l].nz) == DEPTHS_REFUSED)
+        return fail("the depths of level %d (nz = %d) have no coarsening onto level %d (nz = %d): halving from an odd nz has no top interface; set option \"hold_odd_nz\" = 1 before mgx_init", l, S.lev[l - 1].nz, l + 1, S.lev[l].nz);
   const bool wait = !(may_return_early && S.async_ops) || (S.rho_dev && S.rb_seq);
   if (S.rho_dev) HIPCHK(hipMemsetAsync(S.rho_dev, 0, sizeof S.rho_host, S.stream));
-  const bool chained = !all && zeta_chain();
+  const bool chained = what == DM_ZETA && zeta_chain();
   if (chained) S.n_zeta_chain++;
   for (int l = 0; l < S.nlevs; l++) {
     Level &L = S.lev[l];
@@ -173,21 +199,26 @@ int define_matrices(int what, bool may_return_early) {
       double *own[4] = {L.g.dx, L.g.dy, L.g.zeta, L.g.h};
       const double fac[4] = {0.5, 0.5, 0.25, 0.25};
       for (int q = 0; q < 4; q++) {
-        if (!all && (q != 2 || chained)) continue;
+        if (depths ? (!all || q >= 2) : (!all && (q != 2 || chained))) continue;
         mgxs_coarsen2d(S.stream, src[q], L.gather ? L.tmp2[q] : own[q], F.ny, nyc, nxc, fac[q]); S.n_launch++;
         if (L.gather) CHK(gather2d(L, L.tmp2[q], own[q]));
+      }
+      if (depths) {
+        mgxd_coarsen(S.stream, &F.g, nxc, nyc, L.nz, L.gather ? L.blk : L.g.zr, L.gather ? L.dblk : L.g.zw, L.gather ? 1 : 0); S.n_launch++;
+        if (L.gather) { CHK(gather_depths(L, L.blk, L.gbuf, L.g.zr, L.nz)); CHK(gather_depths(L, L.dblk, L.dgbuf, L.g.zw, L.nz + 1)); }
       }
     }
     if (all) CHK(rl_fill_halo(L, L.g.dx, 1, 1, 0));
     if (all) CHK(rl_fill_halo(L, L.g.dy, 1, 1, 0));
-    if (!chained) CHK(rl_fill_halo(L, L.g.zeta, 1, 1, 0));
-    if (all) CHK(rl_fill_halo(L, L.g.h, 1, 1, 0));
+    if (!chained && !depths) CHK(rl_fill_halo(L, L.g.zeta, 1, 1, 0));
+    if (all && !depths) CHK(rl_fill_halo(L, L.g.h, 1, 1, 0));
     // option "periodic": the caller's mask wraps like the geometry; whole rows and planes, so that a corner between a periodic and a closed side is
     // the wrapped image of the mask the caller gave on the closed side (the closed halo of a mask is the caller's to set, never a mirror)
     if (all && l == 0 && S.par.bmask && S.periodic) CHK(wrap_rmask(L));
-    mgxs_zr_zw(S.stream, &L.g, S.hlim, S.theta_b, S.theta_s); S.n_launch++;
+    if (!depths) { mgxs_zr_zw(S.stream, &L.g, S.hlim, S.theta_b, S.theta_s); S.n_launch++; }
     CHK(rl_fill_halo(L, L.g.zr, L.nz, 2, 0));
     CHK(rl_fill_halo(L, L.g.zw, L.nz + 1, 2, 0));
+    if (depths) { mgxd_hz(S.stream, &L.g); S.n_launch++; }   // h = -zw(1), zeta = zw(nz+1) on 0:n+1
     // (no clearing of the cA scratch: k_cA_offdiag stores every slot of every cell, zeros included)
     L.g.bmask = S.par.bmask ? 1 : 0;
     if (l > 0 && all) {  // boundary mask of a coarse level = 1, 0 in the physical halo when bmask (:157-161, fill_halo_2D_bmask)
@@ -232,11 +263,17 @@ int define_matrices(int what, bool may_return_early) {
     L.v.zy = L.zy_store; L.v.zx = L.zx_store;
     if (L.nz <= 1024) { mgxk_convert2(S.stream, &L.v, L.zy_store, L.zx_store, L.g.szy); S.n_launch++; }
     else { mgxk_convert(S.stream, &L.v, L.zy_store, L.g.szy, 1, 0, 0); mgxk_convert(S.stream, &L.v, L.zx_store, L.g.szx, 1, 0, 0); S.n_launch += 2; }
-    L.v.m4 = L.f2d_store[0]; L.v.d4 = L.f2d_store[1]; L.v.m7 = L.f2d_store[2]; L.v.d7 = L.f2d_store[3];
-    L.v.h2 = L.f2d_store[4]; L.v.hi2 = L.f2d_store[5]; L.v.ze2 = L.f2d_store[6]; L.v.cffw = L.tab_store[0]; L.v.csw = L.tab_store[1];
-    L.v.dx2 = L.zg_store[0]; L.v.dy2 = L.zg_store[1]; L.v.cffr = L.zg_store[2]; L.v.csr = L.zg_store[3];
-    if (all) { mgxs_zw_js(S.stream, &L.g, &L.v, S.hlim, S.theta_b, S.theta_s); S.n_launch += 3; }
-    else { mgxs_ze2_js(S.stream, &L.g, &L.v); S.n_launch++; }  // of the 2-D factors and tables only ze2 holds zeta
+    if (depths) {  // the caller's depths follow no formula a kernel could generate them from: slopes, and slots 4 / 7 as stored
+      L.v.m4 = L.v.d4 = L.v.m7 = L.v.d7 = L.v.h2 = L.v.hi2 = L.v.ze2 = nullptr; L.v.cffw = L.v.csw = nullptr;
+      L.v.dx2 = L.v.dy2 = nullptr; L.v.cffr = L.v.csr = nullptr;
+    } else {
+      L.v.m4 = L.f2d_store[0]; L.v.d4 = L.f2d_store[1]; L.v.m7 = L.f2d_store[2]; L.v.d7 = L.f2d_store[3];
+      L.v.h2 = L.f2d_store[4]; L.v.hi2 = L.f2d_store[5]; L.v.ze2 = L.f2d_store[6]; L.v.cffw = L.tab_store[0]; L.v.csw = L.tab_store[1];
+      L.v.dx2 = L.zg_store[0]; L.v.dy2 = L.zg_store[1]; L.v.cffr = L.zg_store[2]; L.v.csr = L.zg_store[3];
+      if (all) { mgxs_zw_js(S.stream, &L.g, &L.v, S.hlim, S.theta_b, S.theta_s); S.n_launch += 3; }
+      else { mgxs_ze2_js(S.stream, &L.g, &L.v); S.n_launch++; }  // of the 2-D factors and tables only ze2 holds zeta
+    }
+    L.pass_stored = depths && depths_pass_stored(L.nz);
     if (S.no_mf || S.par.bmask) { L.v.zy = L.v.zx = nullptr; L.v.m4 = nullptr; }  // masked coefficients are not rebuilt from the slopes
   }
   if (wait) {
@@ -248,6 +285,7 @@ int define_matrices(int what, bool may_return_early) {
   S.coef_gen++;
   S.have_matrix = true;
   S.have_geometry = true;
+  S.depths_user = depths;
   return 0;
 }
 
@@ -472,6 +510,8 @@ int mgx_init(int nx, int ny, int nz, int npx, int npy, int rank, const mgx_param
       CHK(dmalloc(&L.vs.b, ns)); CHK(dmalloc(&L.vs.p, ns));
       const size_t Ng = (size_t)L.nz * (nyc + 2) * (nxc + 2);
       CHK(dmalloc(&L.blk, Ng)); CHK(dmalloc(&L.gbuf, Ng * L.ngroup));
+      const size_t Nd = (size_t)(L.nz + 1) * nyc * nxc;   // the interior block of zw (mgx_matrices_depths*)
+      CHK(dmalloc(&L.dblk, Nd)); CHK(dmalloc(&L.dgbuf, Nd * L.ngroup));
       for (int q = 0; q < 4; q++) CHK(dmalloc(&L.tmp2[q], (size_t)(nyc + 2) * (nxc + 2)));
     }
     size_t np = (size_t)mgxk_residual_nblocks(&L.v);

@@ -41,6 +41,8 @@ struct Level {
   GeoView g;    // set-up arrays (reference layout)
   double *tmp2[4];  // pre-gather coarse dx,dy,zeta,h
   double *blk, *gbuf;  // all-gather send / receive (reference layout blocks incl. halo)
+  double *dblk = nullptr, *dgbuf = nullptr;  // the same for the interior block of zw, nz + 1 rows (the depths of mgx_matrices_depths*: blk, gbuf carry zr)
+  bool pass_stored = false;  // the depths are the caller's and the level's colour pass would generate from the sigma fields it no longer has (depths_pass_stored, mgx_choice_depths.h): the pass takes the stored coefficients
   int group[4], ngroup;
   size_t n3js;  // doubles in one JS array
   bool r_halo_stale = false, b_halo_stale = false;  // deferred neighbour exchanges (multi-rank)
@@ -69,6 +71,10 @@ struct State {
   bool inited = false, have_matrix = false;
   bool have_geometry = false;   // define_matrices has run: level 1 holds dx, dy, h, rmask and S the hc, theta_b, theta_s a zeta refresh keeps
   long long n_zeta_refresh = 0, n_zeta_chain = 0;   // read-only options "zeta_refreshes", "zeta_chain_launches"
+  // the depths of every level are the caller's (mgx_matrices_depths*, mgx_update_depths_device): there is no h and no stretching to apply a new
+  // zeta to, and no level carries the nine sigma fields; the next mgx_matrices / mgx_matrices_device clears it
+  bool depths_user = false;
+  long long n_depth_refresh = 0;   // read-only option "depth_refreshes"
   mgx_params par;
   int method = M_RB, real = 1, linear = 1;
   int nlevs = 0, npx = 1, npy = 1, nranks = 1, rank = 0, pi = 0, pj = 0;
@@ -269,7 +275,7 @@ void make_view(LevView &v, int nx, int ny, int nz);
 int find_grid_levels(int npxg, int npyg, int nx, int ny, int nz, int hold = 0, int hold_z = 0);
 void rank_level_table(int rank, std::vector<Level> &T, int npx0, int npy0, int nsmall, int periodic = 0, int hold = 0, int hold_z = 0);
 void set_window_planes(bool known = true);
-enum { DM_ALL = 0, DM_ZETA = 1 };
+enum { DM_ALL = 0, DM_ZETA = 1, DM_DEPTHS_ALL = 2, DM_DEPTHS = 3 };
 int define_matrices(int what = DM_ALL, bool may_return_early = false);
 int set_call_mask(const double *rmask, bool dev);
 int compute_rhs_dev();

@@ -144,6 +144,13 @@ void mgxs_slopes_ref(hipStream_t st, const GeoView *G);
 void mgxs_zw_js(hipStream_t st, const GeoView *G, const LevView *L, double hlim, double theta_b, double theta_s);
 void mgxs_pivots(hipStream_t st, const LevView *L);
 
+// ---- mgx_depths.hip (the launches: mgx_choice_depths.h) ----
+void mgxd_coarsen(hipStream_t st, const GeoView *F, int nxc, int nyc, int nzc, double *zrc, double *zwc, int block);
+void mgxd_in(hipStream_t st, const double *zr, const double *zw, const mgx_depth_strides *s, const GeoView *G);
+void mgxd_copy(hipStream_t st, const double *zr, const double *zw, const GeoView *G);
+void mgxd_hz(hipStream_t st, const GeoView *G);
+void mgxd_choice(int nx, int ny, int nz, int *out);
+
 // ---- mgx_model.hip ----
 void mgxm_ref2model(hipStream_t st, const double *src, double *dst, int rows, int nh, int nx, int ny);
 void mgxm_ref2model_2d(hipStream_t st, const double *src, double *dst, int nx, int ny);

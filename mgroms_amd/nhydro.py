@@ -9,7 +9,7 @@ import warnings
 
 import numpy as np
 
-from ._lib import Params, MgxError, StateStrides, lib, check  # noqa: F401
+from ._lib import Params, MgxError, StateStrides, DepthStrides, lib, check  # noqa: F401
 
 FIELD = {"p": 0, "b": 1, "r": 2, "cA": 3, "dx": 4, "dy": 5, "zeta": 6, "h": 7, "zr": 8, "zw": 9, "cw": 10, "rmask": 14}
 _DP = C.POINTER(C.c_double)
@@ -258,6 +258,83 @@ def nhydro_update_zeta_view(zeta):
         raise ValueError(f"zeta: need stride 1 along i (the last dimension), got {zeta.stride(-1)}")
     _wait_for_caller()
     check(lib().mgx_update_zeta_device_view(C.c_void_p(zeta.data_ptr()), zeta.stride(0)))
+
+
+# ---- the matrices from the model's own vertical grid (include/mgx.h: mgx_matrices_depths*) ----
+def depth_strides_check(nx, ny, nz, strides):
+    """mgx_depth_strides_check: strides = (zr_sj, zr_sk, zw_sj, zw_sk) in elements; raises MgxError, in the library's words, for strides
+    that cannot hold the depths of an nx x ny x nz level 1.  Host only: needs neither a GPU nor nhydro_init."""
+    s = DepthStrides(*(int(x) for x in strides))
+    check(lib().mgx_depth_strides_check(int(nx), int(ny), int(nz), C.byref(s)))
+
+
+def depths_launch(nx, ny, nz):
+    """the launches of the depth kernels for a level 1 of nx x ny x nz as a dict (include/mgx.h: mgx_depths_launch).  Pure host logic."""
+    out = (C.c_int * 17)()
+    check(lib().mgx_depths_launch(int(nx), int(ny), int(nz), out))
+    keys = ("in_i_tiles", "in_k_tiles_zr", "in_k_tiles_zw", "in_grid_x", "in_grid_y", "in_block_x", "in_block_y", "in_lds",
+            "copy_grid", "copy_block", "coarsen_grid", "coarsen_block", "hz_grid_x", "hz_grid_y", "hz_block_x", "hz_block_y", "pass_stored")
+    return dict(zip(keys, list(out)))
+
+
+def nhydro_matrices_depths(dx, dy, zr, zw, rmask=None):
+    """nhydro_matrices from the caller's own depths: dx, dy (and rmask) as in nhydro_matrices; zr, zw numpy arrays in the library's dense
+    layout, what grid(1).zr / grid(1).zw return -- shapes (nx+4, ny+4, nz) and (nx+4, ny+4, nz+1).  Only the interior columns are read."""
+    if _state.dims is None:
+        check(lib().mgx_matrices_depths(None, None, None, None, None))   # the library's refusal (no mgx_init), in its words
+    nx, ny, nz = _state.dims
+    sh = (nx + 2, ny + 2)
+    dx, dy = _f64(dx, sh, "dx"), _f64(dy, sh, "dy")
+    zr, zw = _f64(zr, (nx + 4, ny + 4, nz), "zr"), _f64(zw, (nx + 4, ny + 4, nz + 1), "zw")
+    rm = None if rmask is None else _f64(rmask, sh, "rmask")
+    check(lib().mgx_matrices_depths(_dp(dx), _dp(dy), _dp(zr), _dp(zw), None if rm is None else _dp(rm)))
+
+
+def _depths_dev(zr, zw):
+    """device zr, zw -> (the two pointers, the strides or None): a contiguous float64 CUDA tensor of the library's shape, (nx+4, ny+4, nz) /
+    (nx+4, ny+4, nz+1), goes dense; tensors of shape (nz, ny, nx) / (nz+1, ny, nx) with unit stride along i -- views of the model's padded
+    arrays -- go through their strides, which the library judges (as nhydro_solve_view derives them)"""
+    nx, ny, nz = _state.dims
+    for a, n in ((zr, "zr"), (zw, "zw")):
+        if not (hasattr(a, "is_cuda") and a.is_cuda and str(a.dtype) == "torch.float64"):
+            raise ValueError(f"{n}: need a float64 CUDA tensor")
+    dense = ((nx + 4, ny + 4, nz), (nx + 4, ny + 4, nz + 1))
+    view = ((nz, ny, nx), (nz + 1, ny, nx))
+    if tuple(zr.shape) == dense[0] and tuple(zw.shape) == dense[1] and zr.is_contiguous() and zw.is_contiguous():
+        return [C.c_void_p(zr.data_ptr()), C.c_void_p(zw.data_ptr())], None
+    if tuple(zr.shape) == view[0] and tuple(zw.shape) == view[1]:
+        for a, n in ((zr, "zr"), (zw, "zw")):
+            if a.stride(-1) != 1:
+                raise ValueError(f"{n}: need stride 1 along i (the last dimension), got {a.stride(-1)}")
+        s = DepthStrides(zr.stride(1), zr.stride(0), zw.stride(1), zw.stride(0))
+        return [C.c_void_p(zr.data_ptr()), C.c_void_p(zw.data_ptr())], s
+    raise ValueError(f"zr, zw: need contiguous tensors of shapes {dense[0]}, {dense[1]} (the library's layout) or i-fastest tensors, "
+                     f"which may be views, of shapes {view[0]}, {view[1]}; got {tuple(zr.shape)}, {tuple(zw.shape)}")
+
+
+def nhydro_matrices_depths_device(dx, dy, zr, zw, rmask=None):
+    """nhydro_matrices_depths on torch CUDA tensors: dx, dy, rmask dense (nx+2, ny+2) as in nhydro_matrices_device; zr, zw in the library's
+    layout or as i-fastest views of the model's own padded arrays, zr[k-1, j-1, i-1] = z_r(i,j,k), zw[k, j-1, i-1] = z_w(i,j,k) -- e.g.
+    Z_R[:, 2:-2, 2:-2] (include/mgx.h: mgx_matrices_depths_device).  Only the elements of the views are read; nothing of them is written."""
+    if _state.dims is None:
+        check(lib().mgx_matrices_depths_device(None, None, None, None, None, None))   # the library's refusal (no mgx_init), in its words
+    nx, ny, _ = _state.dims
+    sh = (nx + 2, ny + 2)
+    pxy = [_dev(a, sh, n) for a, n in ((dx, "dx"), (dy, "dy"))]
+    ptrs, s = _depths_dev(zr, zw)
+    prm = None if rmask is None else _dev(rmask, sh, "rmask")
+    _wait_for_caller()
+    check(lib().mgx_matrices_depths_device(*pxy, *ptrs, None if s is None else C.byref(s), prm))
+
+
+def nhydro_update_depths_device(zr, zw):
+    """the per-step call of a resident model that owns its vertical grid: new depths (as in nhydro_matrices_depths_device) under the dx, dy,
+    rmask of the last set-up; every level's operator is rebuilt (include/mgx.h: mgx_update_depths_device)."""
+    if _state.dims is None:
+        check(lib().mgx_update_depths_device(None, None, None))   # the library's refusal (no mgx_init), in its words
+    ptrs, s = _depths_dev(zr, zw)
+    _wait_for_caller()
+    check(lib().mgx_update_depths_device(*ptrs, None if s is None else C.byref(s)))
 
 
 def nhydro_check_nondivergence(u, v, w, rmask=None):
